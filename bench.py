@@ -123,6 +123,9 @@ def parse_args(argv=None):
     ap.add_argument("--force-collective", action="store_true", help="one rank only: initialise RCCL with world size 1 and run the per-batch "
                     "all_gather_into_tensor anyway (rehearses the collective path, its stream ordering and overlap, on a one-GPU box)")
     ap.add_argument("--full-json", default="", help="where the complete result goes (default: bench_full.json beside bench.py)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed batch returned to its "
+                    "caller (out, traj, status, iters) as DIR/<name>.npy in float32/float64, at most 64 MB in all (a fixed, seeded sample "
+                    "of instances beyond that); the inputs are the same from run to run, so two builds can be compared output for output")
     ap.add_argument("--stub", default="", help="TEST ONLY (tests/test_bench_spawn.py): 'host_twin' replaces the device solve by "
                     "the CPU build of the solver header so that the multi-process plumbing can be exercised without a GPU; "
                     "the line it prints is marked as a stub and is not a measurement")
@@ -274,6 +277,39 @@ def cpu_twin_leg(args, pkg, params, batch, w_np, budget):
     return {"value": sum(done) / wall, "unit": "solves/s", "cores": cores, "kind": "port", "one_core": one_core,
             "sample": "CPU twin, not IPOPT: %d instances of the same batch, tests/host_twin (the device solver's header built for the CPU), "
                       "%d processes" % (sum(done), cores)}
+
+
+def hw_queues():
+    """Hardware queues HIP serves this process, as the environment sets them (None: HIP's own default)."""
+    v = os.environ.get("GPU_MAX_HW_QUEUES")
+    return int(v) if v else None
+
+
+def dump_outputs(pipe, out_dir, cap_bytes=64 << 20):
+    """--dump-outputs: what the last timed batch returned to its caller (rank 0's view of the gathered batch: out [ranks, 9, B],
+    traj [ranks, 2N, B], status and iters [ranks, B]) -> out_dir/<name>.npy, floats in the batch's dtype, status/iters as float64.
+    Beyond cap_bytes the same seeded sample of instances is taken from every array and its indices go to instance_index.npy."""
+    import numpy as np
+    g = pipe.pg.result(pipe.last_slot())
+    if g is None:
+        return None
+    arrs = {}
+    for k in ("out", "traj", "status", "iters"):
+        if g.get(k) is None:
+            continue
+        a = g[k].cpu().numpy()
+        arrs[k] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    B = arrs["out"].shape[-1]
+    per_instance = sum(a.nbytes for a in arrs.values()) // B
+    if per_instance * B > cap_bytes:
+        keep = max(1, (cap_bytes - 8 * B) // (per_instance + 8))
+        idx = np.sort(np.random.default_rng(0).choice(B, size=keep, replace=False))
+        arrs = {k: np.ascontiguousarray(a[..., idx]) for k, a in arrs.items()}
+        arrs["instance_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrs.items()}
 
 
 def f32_start_on(params):
@@ -449,10 +485,10 @@ def timed_run(pipe, steps, warmup, sync_all, lockstep=False):
         pipe.run_until(lambda p: p.final_upto >= n0 + steps, issue=False)
     else:
         pipe.run_until(lambda p: p.final_upto >= n0 + steps)
-    n1 = pipe.final_upto
+    n1 = n0 + steps                                 # exactly `steps` batches timed (more may have become final in the same poll)
     t_b = pipe.marks[n1]
     outstanding = pipe.n_issued - n1
-    steady = {"steady_s": (t_b - t_a) * steps / (n1 - n0), "first_timed_batch": n0, "batches_in_the_window": n1 - n0,
+    steady = {"steady_s": t_b - t_a, "first_timed_batch": n0, "batches_in_the_window": n1 - n0,
               "batches_issued_before_the_clock": issued_a, "batches_outstanding_at_the_end": outstanding}
     kms = pipe.kernel_ms(n0, n1)
     if lockstep:
@@ -523,7 +559,7 @@ LEGS = {
 
 
 def run_leg(pkg, torch, np, args, dev, local_rank, golden, wp, sync_all, name, config, over, B, kind, f32, sweep, want_traj, nfl, population="filtered",
-            velocity_weights=(0.0, 1.0, 100.0), note=None, tail_cut=0, steps=None, f32_pure=False, f32_start=None, f32_refill=False, hw_queues=8, outstanding=0):
+            velocity_weights=(0.0, 1.0, 100.0), note=None, tail_cut=0, steps=None, f32_pure=False, f32_start=None, f32_refill=False, outstanding=0):
     t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dev, dtype=dt)
     params = pkg.params_from_json(os.path.join(golden, config), **over)
     if f32_start is not None:                         # None: as shipped (MPC_F32_START_AUTO: on for horizons of 15 steps and more)
@@ -560,7 +596,7 @@ def run_leg(pkg, torch, np, args, dev, local_rank, golden, wp, sync_all, name, c
         r["kernel_ms_avg"] = float(np.mean(tr["kernel_ms"]))
     pipe.close()
     r["batches_in_flight_advised"] = advised
-    r.update({"workload": name, "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")), "config": config, "N": params.N, "dt": params.dt, "dtype": "f32" if f32 else "f64", "trajectories": want_traj,
+    r.update({"workload": name, "hw_queues": hw_queues(), "config": config, "N": params.N, "dt": params.dt, "dtype": "f32" if f32 else "f64", "trajectories": want_traj,
               "population": population, "draws": int(b["drawn"]), "rejected": b["rejected"]})
     if note:
         r["note"] = note
@@ -570,7 +606,7 @@ def run_leg(pkg, torch, np, args, dev, local_rank, golden, wp, sync_all, name, c
 def extra_legs(args):
     """The other populations the driver-timed line reports: the headline workload drawn with SURVEY.md
     8d's own rejection only, and BASELINE.json configs[1], [3] (one GPU's share) and [4] (one GPU's share).  Each leg runs in a
-    child process of its own (`bench.py --leg NAME`): the mapping of a process's streams onto the 8 hardware queues depends on
+    child process of its own (`bench.py --leg NAME`): the mapping of a process's streams onto the hardware queues depends on
     every stream it has created before, and legs run one after the other in one process measured up to 30 % below the same
     workload run alone.  (The parent has initialised the GPU, so it starts children and never execs.)"""
     legs = {}
@@ -583,7 +619,7 @@ def extra_legs(args):
         if args.leg_tail_cut is not None:
             cmd += ["--leg-tail-cut", str(args.leg_tail_cut)]
         cmd += ["--tail-ring", str(args.tail_ring)]
-        env = dict(os.environ, GPU_MAX_HW_QUEUES=str(LEGS[name][1].get("hw_queues", 8)))     # (more than 8: two legs hung on the box)
+        env = dict(os.environ)
         for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
             env.pop(k, None)
         try:
@@ -600,7 +636,6 @@ def leg_main(args):
     sys.stdout.flush()
     json_fd = os.dup(1)
     os.dup2(2, 1)
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", str(LEGS[args.leg][1].get("hw_queues", 8)))
     import numpy as np
     import torch
     import __graft_entry__ as G
@@ -629,12 +664,6 @@ def main():
     sys.stdout.flush()
     json_fd = os.dup(1)
     os.dup2(2, 1)
-    # HIP serves 4 hardware queues per process by default; more streams in use than that need more (read at HIP start-up):
-    # batches in flight, their tail streams, the gather stream, and the heavy-tailed legs of the default run
-    want_q = (args.inflight if args.inflight > 0 else 4) * (2 if args.tail_cut else 1) + 1      # (--inflight 0: the library's advice, 2-8)
-    if want_q > 4 or (not args.no_legs and world_env == 1 and not args.stub):
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
     import numpy as np
     import torch
     import __graft_entry__ as G
@@ -736,6 +765,7 @@ def main():
     # solve_torch passes to mpc_solve_batch_device (a NULL handle is HIP's null stream = torch's default)
     # (a handle's first call allocates lazily -- second workspace, tail queues: at least one untimed step per handle)
     tr = timed_run(pipe, args.steps, max(args.warmup, pipe.nfl), sync_all, lockstep=dist is not None)
+    dumped = dump_outputs(pipe, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     elapsed, strict = tr["steady_s"], tr["strict_s"]
     if dist is not None:
         tt = torch.tensor([elapsed, strict], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
@@ -808,7 +838,7 @@ def main():
                    "parallelism": "%d independent shard(s), one %s of the packed results per %s" % (world, pg.collective_name, "batch" if pg.g == 1 else "%d batches" % pg.g),
                    "collective_mode": pg.mode, "gather_checked": gather_ok, "gather_bytes_sent_per_rank_per_batch": pg.bytes_sent_per_rank if pg.active else 0, "batches_per_collective": pg.g if pg.active else None,
                    "batches_in_flight": nfl,
-                   "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
+                   "hw_queues": hw_queues(),
                    "branch_mode": "frozen", "tol": params.tol_f32 if f32 else params.tol, "max_iter": params.max_iter,
                    "termination_polish": bool(params.polish), "bound_relax_factor": params.bound_relax_factor, "pass_cuts": cuts,
                    "mixed_precision": ("fp32 iterations to mu = %g, every instance finished in fp64" % params.mixed_switch_mu) if ((f32 and params.f32_finish) or
@@ -834,6 +864,8 @@ def main():
     }
     if stub:
         res["stub"] = "%s: CPU build of the solver header, test infrastructure only" % args.stub
+    if dumped is not None:
+        res["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
     esz = 4 if f32 else 8
     per_solve = esz * (6 + 5 + 2) + esz * 9 + (esz * 2 * params.N if want_traj else 0) + (esz * 12 if args.weights_sweep else 0)
     algo_bytes = per_solve * B

@@ -3,7 +3,7 @@
  * See mpc_oracle.h for scope and the "parity unpinned" statement.
  *
  * Every function cites the reference lines it restates (paths relative to
- * /root/reference).  Nothing here is copied from the reference: the
+ * the reference repository's root).  Nothing here is copied from the reference: the
  * reference's NLP is written on CppAD::AD<double> and solved by IPOPT; this
  * file states the same NLP on plain doubles with hand-derived derivatives and
  * solves it with a dense restatement of IPOPT's published algorithm.

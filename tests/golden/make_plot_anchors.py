@@ -8,7 +8,7 @@ known-answer anchors at plot precision (about +-1.5 pixels):
   * 14 figures for N in {10..50} x dt in {0.1, 0.05, 0.02}      (submission-report.md:250-265)
   * 6 figures of three panels each for the cost-weight sweeps       (submission-report.md:303-327)
 The fixture holds data read off output files the reference already holds; no reference source is copied.
-Needs PIL and /root/reference (this container only); tests read the committed JSON.
+Needs PIL and a checkout of the reference (python make_plot_anchors.py <reference checkout>); tests read the committed JSON.
 
 How a panel is read: the axes frames are found as long dark horizontal runs; y ticks are the short dark marks left
 of a frame, x ticks the marks below it (x = 0, 5, ..., 25); the tick LABELS cannot be read without OCR and are
@@ -23,11 +23,12 @@ Caveats kept in the fixture:
 """
 import json
 import os
+import sys
 
 import numpy as np
 from PIL import Image
 
-REF = "/root/reference/examples"
+REF = os.path.join(sys.argv[1] if len(sys.argv) > 1 else ".", "examples")
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 STD = {"cte": [0.1, 0.0, -0.1], "epsi": [0.030, 0.025, 0.020, 0.015], "delta": [0.015, 0.010, 0.005], "v": [35, 30]}

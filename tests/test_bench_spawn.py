@@ -53,3 +53,46 @@ def test_bench_parent_refuses_nothing_but_stays_gpu_free():
     src = open(os.path.join(ROOT, "bench.py")).read()
     head = src[:src.index("def cpu_baseline_legs")]
     assert "import torch" not in head and "libamdhip64" in head
+
+
+def test_bench_dump_outputs_repeatable_and_steps_exact(tmp_path):
+    """--dump-outputs: the last timed batch's results as float .npy files, the same from run to run; --steps is the number of
+    batches inside the clock."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d, full = tmp_path / ("dump%d" % k), tmp_path / ("full%d.json" % k)
+        r, _ = _run(["--gpus", "2", "--steps", "5", "--warmup", "1", "--batch", "64", "--stub", "host_twin", "--backend", "gloo",
+                     "--dump-outputs", str(d), "--full-json", str(full)])
+        assert r["steps"] == 5
+        assert json.load(open(full))["timing"]["batches_in_the_window"] == 5
+        dumps.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+    assert sorted(dumps[0]) == ["iters.npy", "out.npy", "status.npy", "traj.npy"]
+    assert dumps[0]["out.npy"].shape == (2, 9, 64) and dumps[0]["traj.npy"].shape == (2, 20, 64)
+    for f, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64), f
+        assert np.array_equal(a, dumps[1][f], equal_nan=True), f
+    assert (dumps[0]["status.npy"] == 0).all() and (dumps[0]["iters.npy"] > 0).all()
+
+
+def test_bench_dump_outputs_sample_under_the_cap(tmp_path):
+    """Beyond the size cap the same seeded instances are taken from every array, and their indices are written too."""
+    import numpy as np
+    import torch
+    import bench
+
+    B = 1000
+    full = {"out": torch.arange(9 * B, dtype=torch.float64).reshape(1, 9, B), "traj": torch.ones(1, 20, B, dtype=torch.float64),
+            "status": torch.zeros(1, B, dtype=torch.int32), "iters": torch.arange(B, dtype=torch.int32).reshape(1, B)}
+
+    class Pipe:
+        last_slot = staticmethod(lambda: 0)
+        pg = type("PG", (), {"result": staticmethod(lambda slot: full)})
+
+    shapes = [bench.dump_outputs(Pipe, str(tmp_path / d), cap_bytes=64 << 10) for d in ("a", "b")]
+    assert shapes[0] == shapes[1]
+    idx = np.load(tmp_path / "a" / "instance_index.npy")
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert 0 < len(idx) < B and total <= (64 << 10) + 4096          # (+ the .npy headers)
+    assert np.array_equal(np.load(tmp_path / "a" / "iters.npy")[0], idx)
+    assert np.array_equal(np.load(tmp_path / "a" / "out.npy"), np.load(tmp_path / "b" / "out.npy"))

@@ -2,7 +2,7 @@
 
 Tolerances (fp64, stated in BASELINE.md section 4 / SURVEY.md section 8d): |d delta0| <= 1e-6 rad,
 |d a0| <= 1e-6 m/s^2, step-1 state and trajectory points <= 1e-5 m, cost <= 1e-7 relative.
-Nothing here reads /root/reference.
+Nothing here reads the reference repository.
 """
 import ctypes as C
 import os

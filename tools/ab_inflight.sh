@@ -1,6 +1,6 @@
 #!/bin/bash
 # same-box A/B of builds of libmpc_amd.so (gpurun_in/libmpc_<tag>.so) in the steady state (tools/inflight_bench.py)
-R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
+R=$(cd "$(dirname "$0")/.." && pwd); cd $R
 cp carnd-mpc-project_amd/lib/libmpc_amd.so /tmp/libmpc_keep.so
 for round in 1 2; do
   for f in gpurun_in/libmpc_*.so; do

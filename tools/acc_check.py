@@ -2,7 +2,7 @@
 import os, sys, time, json, ctypes as C
 import multiprocessing as mp
 import numpy as np
-ROOT="/root/repo"; sys.path.insert(0, ROOT); sys.path.insert(0, ROOT+"/tests")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); sys.path.insert(0, ROOT+"/tests")
 import __graft_entry__ as G
 pkg = G.load_package()
 from helpers import twin_solve

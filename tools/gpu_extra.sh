@@ -1,6 +1,6 @@
 #!/bin/bash
 # extra measurements: other BASELINE.json configs at 1 GPU, and a 2-rank rehearsal of the multi-process bench path
-R=${GRAFT_REPO_ROOT:-/root/repo}; OUT=$R/gpurun_out; TAG=${1:-extra}
+R=$(cd "$(dirname "$0")/.." && pwd); OUT=$R/tool_out; TAG=${1:-extra}
 cd $R
 echo "== configs[1]: 4096 straight... (bench uses lake generator; straight-line batch is covered by tests) B=4096 lake" 
 timeout -k 10 300 python bench.py --batch 4096 --no-cpu-baseline > $OUT/${TAG}_b4096.json 2> $OUT/${TAG}_b4096.err; echo "exit=$?"; cat $OUT/${TAG}_b4096.json | cut -c1-300

@@ -1,12 +1,12 @@
 #!/bin/bash
 # One GPU-box session: parity tests, bench line, rocprofv3 kernel trace + PMC passes.
-# Usage (from the repo root, via gpurun):  bash tools/gpu_round.sh [tag]
+# Usage (from the repo root, on the GPU machine):  bash tools/gpu_round.sh [tag]
 set -o pipefail
 TAG=${1:-r01}
 BENCH_ARGS=${BENCH_ARGS:-}
 SKIP_TESTS=${SKIP_TESTS:-0}
-R=${GRAFT_REPO_ROOT:-/root/repo}
-OUT=$R/gpurun_out
+R=$(cd "$(dirname "$0")/.." && pwd)
+OUT=$R/tool_out
 mkdir -p $OUT
 cd $R
 echo "== start" | tee $OUT/${TAG}_progress.log

@@ -1,13 +1,14 @@
 """CPU tool: iteration counts of the CPU build of the device solver (tests/host_twin) against the oracle on SURVEY's populations.
    python tools/iter_eq.py tests/host_twin/libhost_twin.so 2048 [initial_state_rows]"""
 import os, sys, ctypes as C, numpy as np, time
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, ROOT + "/tests")
 import __graft_entry__ as G
 pkg = G.load_package()
 import oracle_lib as O
 from helpers import twin_solve
 import multiprocessing as mp
-gd = "/root/repo/tests/golden"
+gd = ROOT + "/tests/golden"
 def orc(job):
     name, over, b, idx, w = job
     from helpers import oracle_solve_batch
@@ -15,7 +16,7 @@ def orc(job):
     return oracle_solve_batch(O.load_config(name, **over), b, idx, weights=w)
 if __name__ == "__main__":
     wp = pkg.scenarios.load_waypoints(os.path.join(gd, "lake_track_waypoints.csv"))
-    twin = C.CDLL(sys.argv[1] if len(sys.argv) > 1 else "/root/repo/tests/host_twin/libhost_twin.so")
+    twin = C.CDLL(sys.argv[1] if len(sys.argv) > 1 else ROOT + "/tests/host_twin/libhost_twin.so")
     n = int(sys.argv[2]) if len(sys.argv) > 2 else 2048
     for name, over, pop, sweep in (("config-fast.json", {}, True, False), ("config-fast.json", {}, "survey", False), ("config-stable.json", dict(N=25, dt=0.05), "survey", False), ("config-fast.json", {}, "survey", True)):
         params = pkg.params_from_json(os.path.join(gd, name), **over)

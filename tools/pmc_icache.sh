@@ -1,7 +1,7 @@
 #!/bin/bash
 # PMC passes that separate instruction-fetch stalls from memory and LDS waits of the solve kernel.
 set -o pipefail
-R=${GRAFT_REPO_ROOT:-/root/repo}; OUT=$R/gpurun_out; TAG=${1:-pmci}
+R=$(cd "$(dirname "$0")/.." && pwd); OUT=$R/tool_out; TAG=${1:-pmci}
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 -L > $OUT/${TAG}_avail.txt 2>&1
 run() { # name counters...

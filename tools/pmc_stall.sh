@@ -1,7 +1,7 @@
 #!/bin/bash
 # stall breakdown of the solve kernel at a given batch:  bash tools/pmc_stall.sh <tag> <batch>
 set -o pipefail
-R=${GRAFT_REPO_ROOT:-/root/repo}; OUT=$R/gpurun_out; TAG=${1:-pmcs}; B=${2:-65536}
+R=$(cd "$(dirname "$0")/.." && pwd); OUT=$R/tool_out; TAG=${1:-pmcs}; B=${2:-65536}
 cd /tmp && export TMPDIR=/tmp
 run() { local n=$1; shift
   timeout -k 10 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/${TAG}_$n -o pmc -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --batch $B > /dev/null 2> $OUT/${TAG}_$n.err; echo "$n exit=$?"; }

@@ -1,5 +1,5 @@
 import os, sys, numpy as np, threading
-sys.path.insert(0, "/root/repo" if os.path.isdir("/root/repo/tests") else ".")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, "tests")
 import torch
 import __graft_entry__ as G

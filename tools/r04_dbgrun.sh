@@ -1,4 +1,4 @@
-cd $GRAFT_REPO_ROOT; export GPU_MAX_HW_QUEUES=8
+cd "$(dirname "$0")/.."
 timeout -k 10 600 python -m pytest tests -m gpu -q -x -k "deferred or lane_compaction or phase_refill or tail_wait or batch_matches or leave_the_central or multi_phase or staged_and_plain" 2>&1 | tail -3
 for rep in 1 2; do
 MPC_TAIL_HOLD_BATCHES=20 timeout -k 5 100 python tools/hold_test.py --tail-cut 20 2>&1 | tail -1

@@ -1,8 +1,10 @@
 """CPU tool: the oracle with and without IPOPT's second-order correction (OrcSolveOptions.max_soc) on the hard instances of SURVEY's
-N = 10 population and on a random sample.  Needs /tmp/w/iters_survey.npz (iteration counts of the population; written by an
+N = 10 population and on a random sample.  Needs <tmp>/mpc_survey/iters_survey.npz (iteration counts of the population; written by an
 earlier run of the CPU build) -- DESIGN.md section 3 quotes the output."""
-import os, sys, numpy as np, time
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+import os, sys, tempfile, numpy as np, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+WORK = os.path.join(tempfile.gettempdir(), "mpc_survey")      # intermediate files shared by survey_iterations.py and soc_check.py
+sys.path.insert(0, ROOT); sys.path.insert(0, ROOT + "/tests")
 import multiprocessing as mp
 def job(a):
     import oracle_lib as O
@@ -16,7 +18,7 @@ def job(a):
         res.append((s, info.iterations, info.n_soc_tried, info.n_soc_accepted, info.n_backtracks, o9[6]))
     return res
 if __name__ == "__main__":
-    d = np.load("/tmp/w/iters_survey.npz")
+    d = np.load(os.path.join(WORK, "iters_survey.npz"))
     it, stt = d["iters"], d["status"]
     hard = np.where((it > 22) | (stt != 0))[0]
     rnd = np.random.default_rng(1).choice(len(it), 1024, replace=False)

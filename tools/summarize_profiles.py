@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Condense the rocprofv3 output of tools/gpu_round.sh (gpurun_out/<tag>_*) into profiles/<name>_*.
+"""Condense the rocprofv3 output of tools/gpu_round.sh (tool_out/<tag>_*) into profiles/<name>_*.
    python tools/summarize_profiles.py <tag> <name>"""
 import collections
 import csv
@@ -10,7 +10,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag, name = sys.argv[1], sys.argv[2]
-G = os.path.join(ROOT, "gpurun_out")
+G = os.path.join(ROOT, "tool_out")
 P = os.path.join(ROOT, "profiles")
 os.makedirs(P, exist_ok=True)
 

@@ -1,21 +1,22 @@
 """CPU tool: iteration counts and statuses of the headline population (filtered and SURVEY 8d's) by the CPU build of the device solver
-(tests/host_twin), 8 processes: writes /tmp/w/iters_{filtered,survey}.npz, which tools/soc_check.py reads."""
-import os
-os.makedirs("/tmp/w", exist_ok=True)
-import os, sys, ctypes as C, numpy as np, time
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+(tests/host_twin), 8 processes: writes <tmp>/mpc_survey/iters_{filtered,survey}.npz, which tools/soc_check.py reads."""
+import os, sys, tempfile, ctypes as C, numpy as np, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+WORK = os.path.join(tempfile.gettempdir(), "mpc_survey")      # intermediate files shared by survey_iterations.py and soc_check.py
+os.makedirs(WORK, exist_ok=True)
+sys.path.insert(0, ROOT); sys.path.insert(0, ROOT + "/tests")
 import __graft_entry__ as G
 pkg = G.load_package()
 from helpers import twin_solve
 import multiprocessing as mp
-gd = "/root/repo/tests/golden"
+gd = ROOT + "/tests/golden"
 def work(job):
     import ctypes as C
-    sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+    sys.path.insert(0, ROOT); sys.path.insert(0, ROOT + "/tests")
     import __graft_entry__ as G
     pkg = G.load_package()
     from helpers import twin_solve
-    twin = C.CDLL("/root/repo/tests/host_twin/libhost_twin.so")
+    twin = C.CDLL(ROOT + "/tests/host_twin/libhost_twin.so")
     params = pkg.params_from_json(os.path.join(gd, "config-fast.json"))
     r = twin_solve(twin, params, job, want_traj=False)
     return r["iters"], r["status"]
@@ -31,4 +32,4 @@ if __name__ == "__main__":
             res = pool.map(work, chunks)
         it = np.concatenate([r[0] for r in res]); st = np.concatenate([r[1] for r in res])
         print(pop, "twin time", time.time() - t0, "mean iters", it.mean(), "max", it.max(), np.bincount(st))
-        np.savez("/tmp/w/iters_%s.npz" % pop, iters=it, status=st, state=b["state"], coeffs=b["coeffs"], yaw_lo=b["yaw_lo"], yaw_hi=b["yaw_hi"])
+        np.savez(os.path.join(WORK, "iters_%s.npz" % pop), iters=it, status=st, state=b["state"], coeffs=b["coeffs"], yaw_lo=b["yaw_lo"], yaw_hi=b["yaw_hi"])

@@ -1,10 +1,11 @@
 import json, os, sys
 import numpy as np
-sys.path.insert(0, "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import torch
 import __graft_entry__ as G
 pkg = G.load_package()
-gd = "/root/repo/tests/golden"
+gd = ROOT + "/tests/golden"
 wp = pkg.scenarios.load_waypoints(os.path.join(gd, "lake_track_waypoints.csv"))
 dev = torch.device("cuda:0")
 t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
