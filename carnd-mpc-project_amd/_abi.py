@@ -12,7 +12,7 @@ NCOEF = 5
 NSTATE = 6
 NOUT = 9
 MAX_N = 64
-ABI_VERSION = 4
+ABI_VERSION = 5
 PRECISION_F64, PRECISION_F32 = 0, 1
 
 STATUS_NAMES = {0: "success", 1: "maxiter", 2: "linesearch", 3: "infeasible", 4: "numeric", 5: "pending", 6: "acceptable"}
@@ -46,6 +46,7 @@ class MpcParams(C.Structure):
         ("dual_inf_tol", C.c_double), ("constr_viol_tol", C.c_double), ("compl_inf_tol", C.c_double),
         ("acceptable_tol", C.c_double), ("acceptable_dual_inf_tol", C.c_double),
         ("acceptable_constr_viol_tol", C.c_double), ("acceptable_compl_inf_tol", C.c_double), ("initial_state_rows", C.c_int32), ("wave_max_batch", C.c_int32),
+        ("max_soc", C.c_int32),
     ]
 
     def copy(self):

@@ -101,7 +101,11 @@ template <class R> struct Fields : Layout<R> {
     STG_SLOT = STG_IT_OPS + (STG_X_OPS > STG_D_OPS ? STG_X_OPS : STG_D_OPS),
     /* group stores a stage issues in each sweep (all through store_run): the counted waits let exactly these
      * stay in flight besides the newest copy group */
-    ST_BACKWARD = GAIN_SZ / L::G, ST_FORWARD = D_N / L::G, ST_TRIAL = L::IT_SZ / L::G
+    ST_BACKWARD = GAIN_SZ / L::G, ST_FORWARD = D_N / L::G, ST_TRIAL = L::IT_SZ / L::G,
+    /* Second-order correction (MpcParams.max_soc): a record of its own per stage, outside the stage records -- the corrected
+     * constraint residual c_soc of the stage's transition (6) and a copy of the original direction (D_N), which the
+     * backtracking after failed corrections goes on with.  Only the SOC builds of the solver have one (Solver::kSoc). */
+    SOC_C = 0, SOC_D = 6, SOC_SZ = SOC_D + D_N
   };
   static_assert((int)GAIN_SZ <= (int)L::IT_SZ, "the gains must fit an iterate slot");
   static_assert(L::F_ZL % L::G == 0 && L::F_ZU == L::F_ZL + 4 && L::F_U == L::F_S + 6, "blocks the forward sweep fetches");
@@ -112,12 +116,19 @@ template <class R> struct Fields : Layout<R> {
 MPC_HD int64_t workspace_fields_per_instance(int N, bool f32, bool s0_rows = false) {
   return (int64_t)(N - 1 + (s0_rows ? 1 : 0)) * (f32 ? (int)Fields<float>::STAGE_SZ : (int)Fields<double>::STAGE_SZ);
 }
+/* the SOC records of one instance (fp64 solver only) */
+MPC_HD int64_t soc_fields_per_instance(int N) { return (int64_t)(N - 1) * (int)Fields<double>::SOC_SZ; }
 
 /* Plain storage for the test-only host build: one instance, fields contiguous. */
 template <class R>
 struct HostWorkspace {
   using F = Fields<R>;
+  static constexpr bool kSocDefault = true;   /* the test-only build carries the second-order correction in every solver */
   R *base;
+  /* the SOC records live in the workspace object itself (HostWorkspace<R>{ptr} stays a complete initialisation; the Solver
+   * keeps its own copy, through which every access goes) */
+  mutable R socbuf[(MPC_MAX_N - 1) * F::SOC_SZ] = {};
+  MPC_HD R &soc(int k, int f) const { return socbuf[k * F::SOC_SZ + f]; }
   /* field f of iterate slot I (or I = 0 and an absolute field) of stage k */
   MPC_HD R &it(int k, int I, int f) const { return base[k * F::STAGE_SZ + I + f]; }
   MPC_HD R getD(int k, int j) const { return base[k * F::STAGE_SZ + F::F_D + j]; }
@@ -191,6 +202,7 @@ struct TiledWorkspace {
   using F = Fields<R>;
   typedef typename AddrSpace<R>::g greal;
   typedef typename AddrSpace<R>::l lreal;
+  static constexpr bool kSocDefault = false;
   greal *tile;   /* this wave's tile */
   lreal *lbuf;   /* LDS staging area of this wave (STAGING) */
   int lane;
@@ -287,6 +299,21 @@ struct TiledWorkspace {
   MPC_HD R sx(int buf, int k, int Fo, int j) const { return STAGING ? sl(buf, F::IT_SZ + j) : (R)it(k, 0, Fo + j); }
   MPC_HD R sg(int buf, int k, int J, int j) const { return STAGING ? sl(buf, F::IT_SZ + j) : (R)it(k, J, F::F_GK + j); }
 };
+/* The same with the SOC records (the kernels of a max_soc > 0 solve): this wave's tile of them in a buffer of its own,
+ * [stage][group][64 lanes][G] like the workspace tile, read and written with plain accesses (a correction is rare: its extra
+ * sweep is not staged).  A type of its own, so that the kernels without the correction are exactly what they were. */
+template <bool STAGING, class R>
+struct TiledSocWorkspace : TiledWorkspace<STAGING, R> {
+  using F = Fields<R>;
+  typedef typename AddrSpace<R>::g greal;
+  static constexpr bool kSocDefault = true;
+  greal *soc_tile;
+  MPC_HD greal &soc(int k, int f) const {
+    constexpr unsigned G = F::G;
+    static_assert(F::SOC_SZ % F::G == 0, "whole groups");
+    return soc_tile[(((unsigned)k * (F::SOC_SZ / G) + (unsigned)f / G) * 64u + (unsigned)this->lane) * G + (unsigned)f % G];
+  }
+};
 
 /* The N-step variables of an instance RESIDENT IN LDS: for launches of at most a few thousand instances (one or a few
  * per CU) the whole per-instance state -- two iterate slots, direction, gains: 3.7 KB at N = 10 in fp64 -- lives in the
@@ -299,6 +326,7 @@ template <class R, int LANES>
 struct LdsWorkspace {
   using F = Fields<R>;
   typedef typename AddrSpace<R>::l lreal;
+  static constexpr bool kSocDefault = false;
   lreal *base;   /* this workgroup's LDS */
   int lane;      /* < LANES */
   MPC_HD lreal &it(int k, int I, int f) const { return base[(unsigned)((k * F::STAGE_SZ + I + f) * LANES + lane)]; }
@@ -317,6 +345,15 @@ struct LdsWorkspace {
   MPC_HD R sit(int, int k, int I, int j) const { return it(k, I, j); }
   MPC_HD R sx(int, int k, int Fo, int j) const { return it(k, 0, Fo + j); }
   MPC_HD R sg(int, int k, int J, int j) const { return it(k, J, F::F_GK + j); }
+};
+/* ... with the SOC records in LDS behind the stage records, [stage][field][LANES] (only SOC launches ask for that LDS) */
+template <class R, int LANES>
+struct LdsSocWorkspace : LdsWorkspace<R, LANES> {
+  using F = Fields<R>;
+  typedef typename AddrSpace<R>::l lreal;
+  static constexpr bool kSocDefault = true;
+  lreal *soc_base;
+  MPC_HD lreal &soc(int k, int f) const { return soc_base[(unsigned)((k * F::SOC_SZ + f) * LANES + this->lane)]; }
 };
 #endif
 
@@ -359,7 +396,16 @@ template <int LPI> __device__ __forceinline__ bool wave_group_any(bool x, int ba
   if constexpr (LPI >= 64) return b != 0ull;
   else return ((b >> base) & ((1ull << LPI) - 1ull)) != 0ull;
 }
+/* An exchange between the lanes of a group through LDS (a lane reads what another one stored): the stores are ordered before the
+ * loads at the compiler level as well (DS operations of a wave are performed in order; this keeps the compiler from moving
+ * a load above a store to another address) */
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
 #else
+inline void wave_lds_sync() {}
 template <int LPI> inline double wave_bcast(double x, int, int) { return x; }
 template <int LPI> inline float wave_bcast(float x, int, int) { return x; }
 template <int LPI> inline bool wave_bcast_flag(bool x, int, int) { return x; }
@@ -637,9 +683,22 @@ struct Lin {
 /* WAVE = LPI > 0: one instance per LPI neighbouring lanes of a wavefront (mpc_solve_wave_kernel; 64 = the whole wave): every lane
  * of the group runs this state machine on the same instance, `wlane` is the lane's number in its group, `wbase` the group's first
  * lane, and the sweeps share their stages between the lanes of the group */
-template <class WS, class R, int WAVE = 0>
-struct Solver {
+/* second-order correction (Solver::kSoc): state of one line search only -- an instance is parked (Solver::park) with phase ==
+ * PH_DIR, never while it corrects -- the attempt number, the first trial's alpha, the length of the latest corrected step, theta
+ * of the point before it, and what the corrected sweeps overwrite of the original direction's summary.  An empty base in the
+ * builds without the correction: their solver object is what it was. */
+template <bool ON, class R> struct SocState {};
+template <class R> struct SocState<true, R> {
+  int soc_p;
+  R soc_a0, soc_as, soc_th_old, soc_dphi, soc_dxinf, soc_az;
+};
+
+template <class WS, class R, int WAVE = 0, bool SOC = WS::kSocDefault>
+struct Solver : SocState<SOC && sizeof(R) == 8, R> {
   using F = Fields<R>;
+  /* The second-order correction (MpcParams.max_soc, W&B A-5.5..A-5.10) is compiled into the SOC builds only: the fp64 solver of
+   * the kernels a max_soc > 0 solve launches (and of the test-only host build).  The fp32 solver never has it. */
+  static constexpr bool kSoc = SOC && sizeof(R) == 8;
   using IC = IpmConst<R>;
   typedef Eval<R> EvalR;
   typedef Lin<R> LinR;
@@ -792,7 +851,7 @@ struct Solver {
   /* The Riccati sweep with one instance per wavefront: lane k prepares stage k (inputs, model, reciprocal slacks, control and state
    * terms); the value-function recursion runs through the lanes in descending order -- the stage algebra of backward(), statement
    * for statement, on the value function the lane before broadcast (29 numbers) -- and lane k stores stage k's gains. */
-  MPC_HD bool backward_wave(R dw) {
+  MPC_HD bool backward_wave(R dw, bool soc) {
     const int I = it(cur), J = it(1 - cur);         /* J: where the gains go */
     /* value function of (x,y,psi,v,e,d) [+ c] at stage k+1; only the lower triangle of the symmetric
      * matrices is ever written or read (PM/MX pick it), so the other half never occupies registers */
@@ -844,6 +903,7 @@ struct Solver {
     const R v = sk[3];
     LinR L;
     linearise(sk, delta, acc, sn, L);
+    soc_residual(soc, k, L);
     const R sp = L.sp, cp = L.cp, se = L.se, ce = L.ce, fp = L.fp, g1 = L.g1, h3 = L.h3, fpp = L.fpp;
     const R r0 = rsc * L.c[0], r1 = rsc * L.c[1], r2 = rsc * L.c[2], r3 = rsc * L.c[3], rc = rsc * L.c[4], r4 = rsc * L.c[5];
     const R vdt = v * dt;
@@ -1007,8 +1067,8 @@ struct Solver {
     return ok_all;
   }
 
-  MPC_HD bool backward(R dw) {
-    if constexpr (WAVE) return backward_wave(dw);
+  MPC_HD bool backward(R dw, bool soc = false) {
+    if constexpr (WAVE) return backward_wave(dw, soc);
     const int I = it(cur), J = it(1 - cur);         /* J: where the gains go */
     /* value function of (x,y,psi,v,e,d) [+ c] at stage k+1; only the lower triangle of the symmetric
      * matrices is ever written or read (PM/MX pick it), so the other half never occupies registers */
@@ -1074,6 +1134,7 @@ struct Solver {
       const R v = sk[3];
       LinR L;
       linearise(sk, delta, acc, sn, L);
+      soc_residual(soc, k, L);
       const R sp = L.sp, cp = L.cp, se = L.se, ce = L.ce, fp = L.fp, g1 = L.g1, h3 = L.h3, fpp = L.fpp;
       const R r0 = rsc * L.c[0], r1 = rsc * L.c[1], r2 = rsc * L.c[2], r3 = rsc * L.c[3], rc = rsc * L.c[4], r4 = rsc * L.c[5];
       const R vdt = v * dt;
@@ -1239,7 +1300,7 @@ struct Solver {
   /* The forward sweep with one instance per wavefront: lane k prepares stage k -- model, gains, reciprocal slacks: what costs -- for
    * all stages at once; the recursion ds_k -> ds_{k+1} then runs through the lanes in order, each lane doing its stage's few
    * dozen multiply-adds on the state the lane before it broadcast (the statements of forward(), in their order: same bits). */
-  MPC_HD void forward_wave() {
+  MPC_HD void forward_wave(bool soc) {
     const int I = it(cur), J = it(1 - cur);
     const bool mine = wlane < M;
     const int k = mine ? wlane : M - 1;             /* (the lanes behind the last stage repeat it; nothing of theirs is kept) */
@@ -1253,6 +1314,7 @@ struct Solver {
     const R delta = ws.it(k, I, F_U + 0), acc = ws.it(k, I, F_U + 1);
     LinR L;
     linearise(sk, delta, acc, sn, L);
+    soc_residual(soc, k, L);
     R gk[GK_N], gf0 = ws.it(k, J, F_GK + GK_N + 0), gf1 = ws.it(k, J, F_GK + GK_N + 1);
     MPC_UNROLL
     for (int j = 0; j < GK_N; j++) gk[j] = ws.it(k, J, F_GK + j);
@@ -1334,8 +1396,8 @@ struct Solver {
     az = (rzmax > tau) ? tau / rzmax : R(1.0);
   }
 
-  MPC_HD void forward() {
-    if constexpr (WAVE) { forward_wave(); return; }
+  MPC_HD void forward(bool soc = false) {
+    if constexpr (WAVE) { forward_wave(soc); return; }
     const int I = it(cur), J = it(1 - cur);
     R d0 = 0, d1 = 0, d2 = 0, d3 = 0, d5 = 0; /* ds_k: x,y,psi,v,(c),e */
     R ddprev = 0, delprev = 0;                 /* d(delta_{k-1}), delta_{k-1} */
@@ -1382,6 +1444,7 @@ struct Solver {
       const R delta = ws.sit(bf, k, I, F_U + 0), acc = ws.sit(bf, k, I, F_U + 1);
       LinR L;
       linearise(sk, delta, acc, sn, L);
+      soc_residual(soc, k, L);
       R dd = ws.sg(bf, k, J, GK_N + 0), da = ws.sg(bf, k, J, GK_N + 1);
       /* (stage 0: the record holds zeros except for the columns of psi_0, v_0, and ds_0 is zero elsewhere) */
       dd += ws.sg(bf, k, J, 0) * d0 + ws.sg(bf, k, J, 1) * d1 + ws.sg(bf, k, J, 2) * d2 + ws.sg(bf, k, J, 3) * d3 +
@@ -1898,6 +1961,80 @@ struct Solver {
     return Ev;
   }
 
+  /* ---- second-order correction (kSoc builds; MpcParams.max_soc, W&B A-5.5 .. A-5.10) ----
+   * A corrected direction is the Newton system of the rejected step solved again -- same linearisation, same dw_cur -- with
+   * -c_soc in place of the residuals of the dynamics rows: one pass of its own (PH_SOC), backward + forward sweep with the
+   * override, then the usual trial sweep.  The pinning rows of psi_0 / v_0 are linear: a c(x) + c(x + a d) = c(x) for every a,
+   * so their corrected residual is their residual and ds_0 is the original one (trial_x0 along it with the corrected length). */
+  MPC_HD void soc_residual(bool soc, int k, LinR &L) const {
+    if constexpr (kSoc) {
+      if (soc) {
+        MPC_UNROLL
+        for (int i = 0; i < 6; i++) L.c[i] = ws.soc(k, F::SOC_C + i);
+      }
+    }
+  }
+  /* c_soc = a0 c(x) + c(x_t) before the first correction, c_soc <- as c_soc + c(x_s) after each failed one: from the trial point the
+   * last pass left in slot 1-cur (the backward sweep about to run stores its gains there).  The first also saves the original
+   * direction for the backtracking that follows failed corrections.  Wave forms: lane k does stage k. */
+  MPC_HD void soc_prepare() {
+    if constexpr (kSoc) {
+      const int I = it(cur), J = it(1 - cur);
+      const bool first = this->soc_p == 1;
+      const R at = first ? this->soc_a0 : this->soc_as;        /* step length of the trial point in slot J */
+      ws.stage_drain();
+      if constexpr (WAVE) wave_lds_sync();         /* (the trial records were stored by the other lanes) */
+      int k0 = 0, kstep = 1;
+      if constexpr (WAVE) { k0 = wlane; kstep = WAVE; }
+      for (int k = k0; k < M; k += kstep) {
+        R sk[6], sn[6];
+        if (k == 0) {
+          MPC_UNROLL
+          for (int i = 0; i < 6; i++) sk[i] = st[i];
+#if MPC_S0_VARIABLE
+          sk[2] = trial_x0(p0, st[2], at); sk[3] = trial_x0(v0k, st[3], at);
+#endif
+        } else {
+          MPC_UNROLL
+          for (int i = 0; i < 6; i++) sk[i] = ws.it(k - 1, J, F_S + i);
+        }
+        MPC_UNROLL
+        for (int i = 0; i < 6; i++) sn[i] = ws.it(k, J, F_S + i);
+        LinR Lt;
+        linearise(sk, ws.it(k, J, F_U + 0), ws.it(k, J, F_U + 1), sn, Lt);
+        if (first) {
+          load_state(k, I, sk);
+          MPC_UNROLL
+          for (int i = 0; i < 6; i++) sn[i] = ws.it(k, I, F_S + i);
+          LinR L;
+          linearise(sk, ws.it(k, I, F_U + 0), ws.it(k, I, F_U + 1), sn, L);
+          MPC_UNROLL
+          for (int i = 0; i < 6; i++) ws.soc(k, F::SOC_C + i) = at * L.c[i] + Lt.c[i];
+          MPC_UNROLL
+          for (int j = 0; j < D_N; j++) ws.soc(k, F::SOC_D + j) = ws.getD(k, j);
+        } else {
+          MPC_UNROLL
+          for (int i = 0; i < 6; i++) ws.soc(k, F::SOC_C + i) = at * (R)ws.soc(k, F::SOC_C + i) + Lt.c[i];
+        }
+      }
+      if constexpr (WAVE) wave_lds_sync();
+    }
+  }
+  /* the original direction back in place for the backtracking after the last failed correction */
+  MPC_HD void soc_restore() {
+    if constexpr (kSoc) {
+      ws.stage_drain();
+      if constexpr (WAVE) wave_lds_sync();
+      int k0 = 0, kstep = 1;
+      if constexpr (WAVE) { k0 = wlane; kstep = WAVE; }
+      for (int k = k0; k < M; k += kstep) {
+        MPC_UNROLL
+        for (int j = 0; j < D_N; j++) ws.setD(k, j, ws.soc(k, F::SOC_D + j));
+      }
+      if constexpr (WAVE) wave_lds_sync();     /* (the trial sweep's lane r also reads the direction of stage r + 1) */
+    }
+  }
+
   /* a pinned start value after a step of length alpha; exactly the pinned value once it has arrived */
   MPC_HD R trial_x0(R x0, R pinned, R alpha_) const { return x0 == pinned ? pinned : x0 + alpha_ * (pinned - x0); }
   MPC_HD R kkt_error(const EvalR &e, R mu_) const {
@@ -2039,7 +2176,7 @@ struct Solver {
   /* the interior-point iteration                                         */
   /* ------------------------------------------------------------------ */
   enum { MPC_RUNNING = -1, MPC_PROMOTE = -2 };   /* PROMOTE: the fp32 phase of a mixed-precision solve hands the instance to fp64 */
-  enum { PH_EVAL0 = 0, PH_LS = 1, PH_DIR = 2, PH_BACKTRACK = 3, PH_REG = 4 };
+  enum { PH_EVAL0 = 0, PH_LS = 1, PH_DIR = 2, PH_BACKTRACK = 3, PH_REG = 4, PH_SOC = 5 };
   enum { kMaxPolish = 6 };
   enum { kPromoteIterCap = 16 };   /* mixed precision: the fp32 phase's allowance per instance (the bulk hands over after 8-12 iterations); one that uses it up is solved in fp64 from the start point */
   /* state of the interior-point loop (see step()) */
@@ -2195,7 +2332,7 @@ struct Solver {
      * its answers lose against fp64 is mostly the barrier's pull on weakly active bounds (mu/z), not rounding, while
      * slacks of active bounds (mu/z ~ 1e-6 on a ~ 4.47) must stay above a few ulp */
     const R mu_floor = sizeof(R) == 8 ? tol / R(10.0) : tol / R(25.0);
-    if (phase == PH_LS || phase == PH_DIR || phase == PH_REG) {
+    if (phase == PH_LS || phase == PH_DIR || phase == PH_REG || (kSoc && phase == PH_SOC)) {
       if (phase != PH_REG) { dw_try = R(0.0); reg_tries = 0; }
       if (phase == PH_DIR) {
         iters = iter;
@@ -2234,13 +2371,20 @@ struct Solver {
                E.dinf, E.cmin, E.cmax, mu, E0, nf);
 #endif
       }
+      bool soc = false;                            /* a corrected direction (kSoc): the rejected step's system, -c_soc on the right */
+      if constexpr (kSoc) {
+        soc = phase == PH_SOC;
+        if (soc) soc_prepare();
+      }
       lsm = (phase == PH_LS);
       /* search direction with inertia correction, W&B section 3.1: ONE backward sweep per pass; the wrong inertia sends the
        * instance round again with the next regularisation (phase REG) */
       R dw = dw_try;
+      if constexpr (kSoc) { if (soc) dw = dw_cur; }
       bool okb = true;
-      if (!backward(dw)) {
+      if (!backward(dw, soc)) {
         if (lsm) okb = false;
+        else if (soc) return soc_give_up();   /* (cannot happen: the matrix is the one that passed) */
         else {
           if (dw == R(0.0)) dw = (dw_last == R(0.0)) ? IC::dw_0 : mpc_max(IC::dw_min, IC::kw_minus * dw_last);
           else dw *= (dw_last == R(0.0)) ? IC::kw_plus_bar : IC::kw_plus;
@@ -2250,9 +2394,14 @@ struct Solver {
         }
       }
       if (phase == PH_REG) phase = PH_DIR;
-      if (okb) forward();
+      if (okb) forward(soc);
       dw_cur = dw;
-      if (phase == PH_LS) {
+      if (soc) {
+        /* the corrected step: primal and multipliers with its own fraction-to-the-boundary length, bound duals with its own alpha_z;
+         * the acceptance test goes on with the original direction's slope and length */
+        if constexpr (kSoc) { this->soc_as = amax; dphi = this->soc_dphi; dxinf = this->soc_dxinf; }
+        alpha = amax; alpha_l = amax; alpha_z = az;
+      } else if (phase == PH_LS) {
         if (!okb) { lsm = false; ls_start = false; phase = PH_EVAL0; return MPC_RUNNING; }
         alpha = R(0.0); alpha_l = R(1.0); alpha_z = R(0.0);      /* lam <- lam_LS; primal point and bound duals unchanged */
       } else {
@@ -2294,13 +2443,15 @@ struct Solver {
     }
     /* acceptance test of the line search */
     bool accepted = false, ftype = false;
+    R a_test = alpha;                              /* a corrected step is tested with the original step length (W&B A-5.7) */
+    if constexpr (kSoc) { if (phase == PH_SOC) a_test = this->soc_a0; }
     if (tiny) { accepted = T.ok; ftype = true; }
     else if (T.ok) {
       const R phi_t = df * T.f - mu * T.L;
       const R eps_phi = R(10.0) * IC::eps * mpc_abs(phi_k);
       if (T.theta < theta_max && !filter_rejects(T.theta, phi_t)) {
-        const bool sw = dphi < R(0.0) && alpha * pdp > IC::delta_sw * pth;
-        const bool armijo = phi_t - phi_k - eps_phi <= IC::eta_phi * alpha * dphi;
+        const bool sw = dphi < R(0.0) && a_test * pdp > IC::delta_sw * pth;
+        const bool armijo = phi_t - phi_k - eps_phi <= IC::eta_phi * a_test * dphi;
         if (theta_k <= theta_min && sw) {
           if (armijo) accepted = true;
         } else if (T.theta <= (R(1.0) - IC::gamma_theta) * theta_k ||
@@ -2337,10 +2488,34 @@ struct Solver {
       phase = PH_DIR;
       return MPC_RUNNING;
     }
+    if constexpr (kSoc) {
+      if (phase == PH_SOC) {
+        /* rejected correction: the next one unless the point is not strictly inside or the violation has stopped going down (kappa_soc) */
+        if (T.ok && !(T.theta > R(0.99) * this->soc_th_old) && this->soc_p < P.max_soc) { this->soc_th_old = T.theta; ++this->soc_p; return MPC_RUNNING; }
+        return soc_give_up();
+      }
+      /* the first trial of the line search is rejected and has not reduced the violation: second-order correction */
+      if (phase == PH_DIR && P.max_soc > 0 && T.ok && !tiny && T.theta >= theta_k) {
+        this->soc_p = 1; this->soc_a0 = alpha; this->soc_th_old = theta_k; this->soc_dphi = dphi; this->soc_dxinf = dxinf; this->soc_az = az;
+        phase = PH_SOC;
+        return MPC_RUNNING;
+      }
+    }
     if (tiny) return line_search_failed();
     alpha *= R(0.5); alpha_l = alpha;
     if (alpha < amin) return line_search_failed();
     phase = PH_BACKTRACK;
+    return MPC_RUNNING;
+  }
+  /* no corrected step was accepted: backtracking along the original direction from a0 / 2 */
+  MPC_HD int soc_give_up() {
+    if constexpr (kSoc) {
+      soc_restore();
+      az = this->soc_az; alpha_z = az;
+      alpha = this->soc_a0 * R(0.5); alpha_l = alpha;
+      if (alpha < amin) return line_search_failed();
+      phase = PH_BACKTRACK;
+    }
     return MPC_RUNNING;
   }
 

@@ -172,6 +172,9 @@ struct MpcPhase {
   unsigned long long *pool_bits;   /* [8][pool_words]: bit set = tile free; nullptr = no pool */
   void *pool_base;                 /* [8][pool_tiles] tiles */
   int32_t pool_tiles, pool_words;  /* per XCD */
+  /* SOC builds (MpcParams.max_soc > 0): the SOC records, [wave of this launch][N-1][SOC_SZ / G][64][G] reals.  A correction lives
+   * within one line search of one lane, so they go with the launch's wave number, not with the workspace tile. */
+  void *soc_ws;
 };
 
 /* Copies between queue entries and a lane's workspace column.  Loads first, then stores, a stage (or 16 rows) at a time: written as
@@ -209,7 +212,7 @@ template <class RIO, class R> struct OutRef {
 /* RIO: the type of the arrays at the ABI (inputs, outputs); R: the solver's.  They differ only in the fp64 phase of a
  * mixed-precision solve on an MPC_PRECISION_F32 handle (RIO = float, R = double).  RSRC: the reals of the workspace a
  * promote_in phase takes its iterates from. */
-template <bool STAGING, class R, int OCC, class RIO = R, class RSRC = RIO>
+template <bool STAGING, class R, int OCC, class RIO = R, class RSRC = RIO, bool SOC = false>
 __global__ __launch_bounds__(kBlock, OCC) void mpc_solve_kernel(
     const MpcParams P, const int64_t B, const int64_t ld, const int64_t ldo, const RIO *__restrict__ state,
     const RIO *__restrict__ coeffs, const RIO *__restrict__ yaw_lo, const RIO *__restrict__ yaw_hi,
@@ -217,12 +220,13 @@ __global__ __launch_bounds__(kBlock, OCC) void mpc_solve_kernel(
     int32_t *__restrict__ status, int32_t *__restrict__ iters, R *__restrict__ wsbase,
     const int64_t tile_reals, const MpcPhase T) {
   extern __shared__ double smem[];
-  using WS = mpc::TiledWorkspace<STAGING, R>;
-  using SV = mpc::Solver<WS, R>;
+  using WS = std::conditional_t<SOC, mpc::TiledSocWorkspace<STAGING, R>, mpc::TiledWorkspace<STAGING, R>>;
+  using SV = mpc::Solver<WS, R, 0, SOC>;
   using FL = mpc::Fields<R>;
   static_assert(SV::PARK_N == kParkRows, "park buffer rows");
   WS ws;
   ws.tile = (typename WS::greal *)(wsbase + (int64_t)blockIdx.x * tile_reals);
+  if constexpr (SOC) ws.soc_tile = (typename WS::greal *)((R *)T.soc_ws + (int64_t)blockIdx.x * (P.N - 1) * FL::SOC_SZ * 64);
 #if defined(__HIP_DEVICE_COMPILE__)
   int pool_word = -1, pool_bit = 0;
   unsigned long long *pool_mine = nullptr;
@@ -605,17 +609,19 @@ struct MpcSliceArgs {
   int32_t *res;                    /* pinned host memory: what the pump reads when the slice has completed -- [0] survivors left,
                                     * [j] entries of source j; [25..27]: entries finished / moved on untouched / parked again */
   int32_t *tally;                  /* [4]: those three, and the most passes a wave of the slice made */
+  void *soc_ws;                    /* SOC builds: the SOC records of the slice's waves (see MpcPhase.soc_ws) */
 };
 
-template <bool STAGING, class R, int OCC, class RIO = R>
+template <bool STAGING, class R, int OCC, class RIO = R, bool SOC = false>
 __global__ __launch_bounds__(kBlock, OCC) void mpc_tail_slice_kernel(const MpcParams P, const MpcSliceArgs A, R *__restrict__ wsbase,
                                                                      const int64_t tile_reals) {
   extern __shared__ double smem[];
-  using WS = mpc::TiledWorkspace<STAGING, R>;
-  using SV = mpc::Solver<WS, R>;
+  using WS = std::conditional_t<SOC, mpc::TiledSocWorkspace<STAGING, R>, mpc::TiledWorkspace<STAGING, R>>;
+  using SV = mpc::Solver<WS, R, 0, SOC>;
   using FL = mpc::Fields<R>;
   WS ws;
   ws.tile = (typename WS::greal *)(wsbase + (int64_t)blockIdx.x * tile_reals);
+  if constexpr (SOC) ws.soc_tile = (typename WS::greal *)((R *)A.soc_ws + (int64_t)blockIdx.x * (P.N - 1) * FL::SOC_SZ * 64);
   ws.lane = threadIdx.x;
   ws.lbuf = (typename WS::lreal *)smem;
   SV S(P, ws);
@@ -816,7 +822,7 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_lds_kernel(
  * 3.7 KB per instance at N = 10 in fp64); every lane of the group
  * runs the solver's state machine on them -- the decisions are wave-uniform -- and the sweeps share their work between the
  * lanes (mpc::Solver<WS, R, true>: backward_wave, forward_wave and the wave form of costate_trial in mpc_core.h). */
-template <class R, int LPI>
+template <class R, int LPI, bool SOC = false>
 __global__ __launch_bounds__(kBlock, 1) void mpc_solve_wave_kernel(
     const MpcParams P, const int64_t B, const int64_t ld, const int64_t ldo, const R *__restrict__ state,
     const R *__restrict__ coeffs, const R *__restrict__ yaw_lo, const R *__restrict__ yaw_hi,
@@ -824,13 +830,15 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_wave_kernel(
     int32_t *__restrict__ status, int32_t *__restrict__ iters) {
   extern __shared__ double smem[];
   constexpr int G = 64 / LPI;                       /* instances per wavefront: each on LPI neighbouring lanes */
-  using WS = mpc::LdsWorkspace<R, G>;
-  using SV = mpc::Solver<WS, R, LPI>;
+  using WS = std::conditional_t<SOC, mpc::LdsSocWorkspace<R, G>, mpc::LdsWorkspace<R, G>>;
+  using SV = mpc::Solver<WS, R, LPI, SOC>;
   const int group = threadIdx.x / LPI;
   const int64_t i = (int64_t)blockIdx.x * G + group;
   if (i >= B) return;                               /* (whole groups: nobody reads their lanes) */
   WS ws;
   ws.base = (typename WS::lreal *)smem;
+  /* SOC builds: the SOC records behind the stage records (the launch asks for that much more dynamic LDS) */
+  if constexpr (SOC) ws.soc_base = ws.base + mpc::workspace_fields_per_instance(P.N, sizeof(R) == 4, P.initial_state_rows != 0) * G;
   ws.lane = group;                                  /* every lane of the group addresses the group's instance */
   SV S(P, ws);
   S.wlane = threadIdx.x % LPI; S.wbase = group * LPI;
@@ -1105,6 +1113,9 @@ struct MpcHandle {
   long long *h_final = nullptr;  /* pinned: [tail_ring] the id of the batch that has become final in each slot (written by the slices) */
   SliceRes *h_res = nullptr;     /* pinned: [kSliceRing], written by each slice's last wave */
   void *tail_ws = nullptr;
+  /* SOC records (MpcParams.max_soc > 0, fp64 solver), allocated by the first solve that asks for them: one set for the launches on
+   * the caller's stream (a tile per wave of the largest grid), one for the tail slices (they run beside those launches) */
+  void *soc_ws = nullptr, *soc_tail = nullptr;
   TailSlot tslot[kTailMaxRing];
   FreshQ fq[kFreshRing];
   BatchRec *brec = nullptr;
@@ -1191,6 +1202,7 @@ static int validate_params(const MpcParams *p) {
   if (p->tail_cut < MPC_TAIL_AUTO || p->tail_ring < 0 || p->tail_capacity < 0) { g_last_error = "bad tail_cut/tail_ring/tail_capacity"; return MPC_ERR_INVALID; }
   if (p->f64_f32_start < 0 || p->f64_f32_start > MPC_F32_START_AUTO) { g_last_error = "f64_f32_start must be 0 (off), 1 (on) or 2 (auto)"; return MPC_ERR_INVALID; }
   if (p->lane_compact < MPC_LANE_COMPACT_AUTO || p->lane_compact > 7) { g_last_error = "lane_compact must be -1 (auto), 0 (off) .. 7"; return MPC_ERR_INVALID; }
+  if (p->max_soc < 0 || p->max_soc > MPC_MAX_SOC) { g_last_error = "max_soc must be 0 (off) .. 16 (IPOPT's default is 4)"; return MPC_ERR_INVALID; }
   return MPC_OK;
 }
 
@@ -1390,6 +1402,7 @@ extern "C" void mpc_destroy(MpcHandle *h) {
   if (h->d_rstat) (void)hipFree(h->d_rstat);
   if (h->d_counter) (void)hipFree(h->d_counter);
   if (h->ws2) (void)hipFree(h->ws2);
+  if (h->soc_ws) (void)hipFree(h->soc_ws);
   pool_release(h->pool);
   if (h->d_park) (void)hipFree(h->d_park);
   if (h->d_list) (void)hipFree(h->d_list);
@@ -1397,7 +1410,7 @@ extern "C" void mpc_destroy(MpcHandle *h) {
   if (h->d_tel) (void)hipFree(h->d_tel);
   if (h->tail_ready) (void)tail_drain(h);         /* stragglers still queued are finished: their batches' arrays may be read afterwards */
   if (h->tail_stream) (void)hipStreamSynchronize(h->tail_stream);
-  for (void *q : {(void *)h->d_tcount, (void *)h->d_remaining, h->tail_ws, (void *)h->surv_dev[0].park, h->surv_dev[0].iter,
+  for (void *q : {(void *)h->d_tcount, (void *)h->d_remaining, h->tail_ws, h->soc_tail, (void *)h->surv_dev[0].park, h->surv_dev[0].iter,
                   (void *)h->surv_dev[1].park, h->surv_dev[1].iter})
     if (q) (void)hipFree(q);
   for (int q = 0; q < kFreshRing; q++) {
@@ -1428,6 +1441,13 @@ static int record_stats(MpcHandle *h, int64_t B, const int32_t *status, const in
   MPC_HIP_CHECK(hipGetLastError());
   MPC_HIP_CHECK(hipEventRecord(h->ev_stats, s));
   h->have_stats = true;
+  return MPC_OK;
+}
+
+/* The SOC records of `waves` wavefront tiles (fp64 solver), allocated once: N cannot change on a live handle */
+static int soc_alloc(MpcHandle *h, void **buf, int64_t waves) {
+  if (*buf) return MPC_OK;
+  MPC_HIP_CHECK(hipMalloc(buf, sizeof(double) * (size_t)waves * (size_t)mpc::soc_fields_per_instance(h->params.N) * 64u));
   return MPC_OK;
 }
 
@@ -1603,7 +1623,14 @@ static int tail_launch_slice(MpcHandle *h, bool force) {
   if (waves < 1) waves = 1;
   const bool f32 = !h->tail_double, io32 = h->params.precision == MPC_PRECISION_F32;
   const int64_t tail_stride = f32 ? h->ws_stride_f32 : h->ws_stride_f64;
-  if (f32 && h->occ2)
+  const bool soc = !f32 && h->params.max_soc > 0;     /* (the slice solves under the parameters it is launched with) */
+  if (soc) { const int rc = soc_alloc(h, &h->soc_tail, h->tail_waves); if (rc != MPC_OK) return rc; }
+  A.soc_ws = h->soc_tail;
+  if (soc && io32)
+    hipLaunchKernelGGL((mpc_tail_slice_kernel<true, double, 1, float, true>), dim3((unsigned)waves), dim3(kBlock), staging_lds_bytes<double>(), ts, h->params, A, (double *)h->tail_ws, tail_stride);
+  else if (soc)
+    hipLaunchKernelGGL((mpc_tail_slice_kernel<true, double, 1, double, true>), dim3((unsigned)waves), dim3(kBlock), staging_lds_bytes<double>(), ts, h->params, A, (double *)h->tail_ws, tail_stride);
+  else if (f32 && h->occ2)
     hipLaunchKernelGGL((mpc_tail_slice_kernel<true, float, 2>), dim3((unsigned)waves), dim3(kBlock), staging_lds_bytes<float>(), ts, h->params, A, (float *)h->tail_ws, tail_stride);
   else if (f32)
     hipLaunchKernelGGL((mpc_tail_slice_kernel<true, float, 1>), dim3((unsigned)waves), dim3(kBlock), staging_lds_bytes<float>(), ts, h->params, A, (float *)h->tail_ws, tail_stride);
@@ -1911,8 +1938,16 @@ static int launch_mixed(MpcHandle *h, int64_t B, int64_t ld, int64_t ldo, const 
   /* deferred tails: the fp64 phase hands its stragglers over (the fp32 phase's chains end at kPromoteIterCap anyway) */
   /* (no early hand-over of a wave's last lanes here: the waves of this phase are partly filled by construction) */
   U.tail_cut = tail.tail_cut; U.t_slot = tail.t_slot; U.t_batch = tail.t_batch; U.tq = tail.tq; U.tail_few = 0; U.tail_few_from = tail.tail_few_from;
-  hipLaunchKernelGGL((mpc_solve_kernel<true, double, 1, RIO, float>), dim3(waves2), dim3(kBlock), staging_lds_bytes<double>(), s, h->params, B, ld, ldo, state,
-                     coeffs, yaw_lo, yaw_hi, weights, out, traj, status, it_out, ws64, h->ws_stride_f64, U);
+  if (h->params.max_soc > 0) {
+    /* the fp64 phase honours MpcParams.max_soc (the fp32 phase never corrects) */
+    const int rc = soc_alloc(h, &h->soc_ws, tiles);
+    if (rc != MPC_OK) return rc;
+    U.soc_ws = h->soc_ws;
+    hipLaunchKernelGGL((mpc_solve_kernel<true, double, 1, RIO, float, true>), dim3(waves2), dim3(kBlock), staging_lds_bytes<double>(), s, h->params, B, ld, ldo, state,
+                       coeffs, yaw_lo, yaw_hi, weights, out, traj, status, it_out, ws64, h->ws_stride_f64, U);
+  } else
+    hipLaunchKernelGGL((mpc_solve_kernel<true, double, 1, RIO, float>), dim3(waves2), dim3(kBlock), staging_lds_bytes<double>(), s, h->params, B, ld, ldo, state,
+                       coeffs, yaw_lo, yaw_hi, weights, out, traj, status, it_out, ws64, h->ws_stride_f64, U);
   MPC_HIP_CHECK(hipGetLastError());
   MPC_HIP_CHECK(hipEventRecord(h->ev1, s));
   h->timed = true;
@@ -1947,7 +1982,11 @@ static int launch_solve(MpcHandle *h, int64_t B, int64_t ld, int64_t ldo, const 
   const int64_t waves_full = (B + kBlock - 1) / kBlock;
   int64_t waves = (waves_full + h->inst_per_lane - 1) / h->inst_per_lane;
   if (waves < 1) waves = 1;
-  bool defer = may_defer && h->params.tail_cut != 0 && B >= h->tail_min_batch && (h->mixed || !(h->lds_lanes > 0 && B <= h->lds_max_batch)) &&
+  /* MpcParams.max_soc > 0 on an fp64 handle: the SOC builds of the kernels (the LDS-resident one has none: those launches take the
+   * lane kernel; the mixed-precision launch decides for its fp64 phase itself) */
+  const bool soc = sizeof(R) == 8 && h->params.max_soc > 0;
+  const bool lds_path = !soc && h->lds_lanes > 0 && B <= h->lds_max_batch;
+  bool defer = may_defer && h->params.tail_cut != 0 && B >= h->tail_min_batch && (h->mixed || !lds_path) &&
                !(h->wave_max_batch > 0 && B <= h->wave_max_batch);
   MpcHandle::BatchRec *rec = nullptr;
   { const int rc = batch_rec(h, h->batch_seq, &rec); if (rc != MPC_OK) return rc; }
@@ -2028,13 +2067,28 @@ static int launch_solve(MpcHandle *h, int64_t B, int64_t ld, int64_t ldo, const 
     if (const char *e = getenv("MPC_WAVE_LPI")) lpi = atoi(e) == 16 ? 16 : (atoi(e) == 32 ? 32 : 64);
     if (lpi < h->params.N - 1) lpi = 64;
     int32_t *it_w = iters ? iters : h->d_iters;
+    if constexpr (sizeof(R) == 8) {
+      if (soc) {
+        const int64_t ps = per + mpc::soc_fields_per_instance(h->params.N) * (int64_t)sizeof(R);   /* the SOC records behind the stage records */
+        if (lpi == 16)
+          hipLaunchKernelGGL((mpc_solve_wave_kernel<R, 16, true>), dim3((unsigned)((B + 3) / 4)), dim3(kBlock), (size_t)(4 * ps), s, h->params, B, ld, ldo, state, coeffs, yaw_lo, yaw_hi,
+                             weights, out, traj, status, it_w);
+        else if (lpi == 32)
+          hipLaunchKernelGGL((mpc_solve_wave_kernel<R, 32, true>), dim3((unsigned)((B + 1) / 2)), dim3(kBlock), (size_t)(2 * ps), s, h->params, B, ld, ldo, state, coeffs, yaw_lo, yaw_hi,
+                             weights, out, traj, status, it_w);
+        else
+          hipLaunchKernelGGL((mpc_solve_wave_kernel<R, 64, true>), dim3((unsigned)B), dim3(kBlock), (size_t)ps, s, h->params, B, ld, ldo, state, coeffs, yaw_lo, yaw_hi,
+                             weights, out, traj, status, it_w);
+        lpi = 0;
+      }
+    }
     if (lpi == 16)
       hipLaunchKernelGGL((mpc_solve_wave_kernel<R, 16>), dim3((unsigned)((B + 3) / 4)), dim3(kBlock), (size_t)(4 * per), s, h->params, B, ld, ldo, state, coeffs, yaw_lo, yaw_hi,
                          weights, out, traj, status, it_w);
     else if (lpi == 32)
       hipLaunchKernelGGL((mpc_solve_wave_kernel<R, 32>), dim3((unsigned)((B + 1) / 2)), dim3(kBlock), (size_t)(2 * per), s, h->params, B, ld, ldo, state, coeffs, yaw_lo, yaw_hi,
                          weights, out, traj, status, it_w);
-    else
+    else if (lpi == 64)
       hipLaunchKernelGGL((mpc_solve_wave_kernel<R, 64>), dim3((unsigned)B), dim3(kBlock), (size_t)per, s, h->params, B, ld, ldo, state, coeffs, yaw_lo, yaw_hi,
                          weights, out, traj, status, it_w);
     MPC_HIP_CHECK(hipGetLastError());
@@ -2044,7 +2098,7 @@ static int launch_solve(MpcHandle *h, int64_t B, int64_t ld, int64_t ldo, const 
     if (with_stats) stats_later(iters ? iters : h->d_iters);
     return MPC_OK;
   }
-  if (h->lds_lanes > 0 && B <= h->lds_max_batch) {
+  if (lds_path) {
     --h->counter_seq;                              /* (this path uses no counters: the block stays clean for the next call) */
     MPC_HIP_CHECK(hipEventRecord(h->ev0, s));
     const int rc = launch_lds<R>(h, B, ld, ldo, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters ? iters : h->d_iters, s);
@@ -2056,9 +2110,21 @@ static int launch_solve(MpcHandle *h, int64_t B, int64_t ld, int64_t ldo, const 
     return MPC_OK;
   }
   int32_t *it_out = iters ? iters : h->d_iters;
+  if (soc) { const int rc = soc_alloc(h, &h->soc_ws, h->io_stride / 64); if (rc != MPC_OK) return rc; }
   MPC_HIP_CHECK(hipEventRecord(h->ev0, s));
   auto launch = [&](unsigned grid, void *wsp, const MpcPhase &tp) {
     constexpr int kOcc2 = sizeof(R) == 4 ? 2 : 1;
+    if constexpr (sizeof(R) == 8) {
+      if (soc) {
+        if (h->staging)
+          hipLaunchKernelGGL((mpc_solve_kernel<true, R, 1, R, R, true>), dim3(grid), dim3(kBlock), staging_lds_bytes<R>(), s, h->params, B, ld, ldo, state, coeffs,
+                             yaw_lo, yaw_hi, weights, out, traj, status, it_out, (R *)wsp, h->ws_stride, tp);
+        else
+          hipLaunchKernelGGL((mpc_solve_kernel<false, R, 1, R, R, true>), dim3(grid), dim3(kBlock), 0, s, h->params, B, ld, ldo, state, coeffs,
+                             yaw_lo, yaw_hi, weights, out, traj, status, it_out, (R *)wsp, h->ws_stride, tp);
+        return;
+      }
+    }
     if (h->staging && h->occ2)
       hipLaunchKernelGGL((mpc_solve_kernel<true, R, kOcc2>), dim3(grid), dim3(kBlock), staging_lds_bytes<R>(), s, h->params, B, ld, ldo, state, coeffs,
                          yaw_lo, yaw_hi, weights, out, traj, status, it_out, (R *)wsp, h->ws_stride, tp);
@@ -2096,6 +2162,7 @@ static int launch_solve(MpcHandle *h, int64_t B, int64_t ld, int64_t ldo, const 
     const bool pooled = h->pool && n_cuts == 0;      /* a parked iterate stays in its column: phases keep their own tiles */
     T.pool_bits = pooled ? h->pool->bits : nullptr; T.pool_base = pooled ? h->pool->base : nullptr;
     T.pool_tiles = pooled ? h->pool->tiles : 0; T.pool_words = pooled ? h->pool->words : 0;
+    T.soc_ws = h->soc_ws;
     launch((unsigned)waves, wr ? h->ws2 : h->ws, T);
     MPC_HIP_CHECK(hipGetLastError());
   }

@@ -29,13 +29,14 @@
 extern "C" {
 #endif
 
-#define MPC_ABI_VERSION 4
+#define MPC_ABI_VERSION 5
 #define MPC_MAX_TABLE 16
 #define MPC_NW 12      /* Config::weights entries read by FG_eval (Config.h:14-61) */
 #define MPC_NCOEF 5    /* road polynomial, zero padded: fit order is 2..4 (RoadGeometry.cpp:26-34) */
 #define MPC_NSTATE 6   /* x, y, psi, v, cte, epsi (MPC.cpp:213-218) */
 #define MPC_NOUT 9     /* x1,y1,psi1,v1,cte1,epsi1,delta0,a0,cost (MPC.cpp:322-324) */
 #define MPC_MAX_N 64   /* largest horizon the kernels are sized for */
+#define MPC_MAX_SOC 16 /* largest MpcParams.max_soc */
 
 /* return codes */
 enum {
@@ -209,6 +210,14 @@ typedef struct MpcParams {
    * a SIMD per 1-4 instances, so many launches in flight are better off with the lane kernel.  0 (default) = 1 024; < 0 = never.
    * Not used by an explicit f64_f32_start = 1 or a mixed MPC_PRECISION_F32 handle (those ask for the two-launch solve). */
   int32_t wave_max_batch;
+  /* IPOPT's second-order correction (max_soc, W&B A-5.5 .. A-5.10; IPOPT's default is 4, kappa_soc = 0.99): when the first
+   * trial point of a line search is rejected and has not reduced the constraint violation, up to max_soc corrected directions
+   * -- the same Newton system with the violation at the trial point folded into the residuals -- are tried before the step is
+   * shortened.  Measured on SURVEY's hard N = 10 instances (oracle): 8 % fewer iterations, 10 of 29 failures solved.  0 (default)
+   * = off, results bitwise those of ABI 4; 0..MPC_MAX_SOC.  fp64 solver only: an MPC_PRECISION_F32 solve ignores it, the fp64
+   * finish of one with f32_finish and the fp64 phase of f64_f32_start honour it.  Launches with max_soc > 0 run builds of the
+   * kernels that carry it (an extra buffer of 14 reals per stage and instance, allocated by the handle on first use). */
+  int32_t max_soc;
 } MpcParams;
 
 typedef struct MpcHandle MpcHandle;

@@ -121,6 +121,9 @@ struct Config {
    * iteration in fp64; 1 = always the two-launch solve.  One MPC::solve() per telemetry message runs one instance per wavefront
    * whatever the horizon (0.30 ms at N = 10) unless this is 1. */
   inline static int fp32Start = 2;
+  /* MpcParams.max_soc: IPOPT's second-order correction, up to this many corrected directions when the first trial point of a line
+   * search is rejected (IPOPT's default, the reference's solver, is 4; 0 = off, the library's default) */
+  inline static int maxSoc = 0;
 
   /* Config::load(fileName), Config.cpp:31-87 (parsing and unit conversion live behind the C ABI) */
   static void load(const std::string &fileName) {
@@ -146,6 +149,7 @@ struct Config {
     p.steer_adj_thresh = steerAdjustmentThresh; p.steer_adj_ratio = steerAdjustmentRatio; p.Lf = Lf;
     p.cte_panic = ctePanic; p.epsi_panic = epsiPanic; p.max_iter = maxIterations; p.tol = tolerance;
     p.f64_f32_start = fp32Start == 1 ? MPC_F32_START_ON : (fp32Start == 0 ? MPC_F32_START_OFF : MPC_F32_START_AUTO);
+    p.max_soc = maxSoc;
     for (int i = 0; i < MPC_NW; i++) p.weights[i] = i < (int)weights.size() ? weights[i] : 0.0;
     auto put = [](const std::vector<double> &v, double *dst, int32_t &n) {
       n = (int32_t)(v.size() < MPC_MAX_TABLE ? v.size() : MPC_MAX_TABLE);
