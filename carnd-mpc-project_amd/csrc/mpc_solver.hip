@@ -67,6 +67,15 @@ constexpr int kSliceRing = 4;       /* slices whose events and result blocks are
 constexpr int kTailInRows = 6 + MPC_NCOEF + 2 + MPC_NW;   /* the inputs of a deferred instance travel with it: 25 rows */
 constexpr int kTailMetaRows = 8;    /* ... and where it belongs: instance, slot, batch id, out, traj, status, iters, ldo */
 constexpr int kTailRows = kParkRows + kTailInRows + kTailMetaRows;
+/* fixed launch policies (measured; see MpcPhase and MpcHandle for what each one governs) */
+constexpr int kRefillMin = 16, kRefillWait = 8;     /* hand-over policy of the persistent kernel, every phase */
+constexpr int kCompactCooldown = 2;                 /* lane compaction: passes without another move after one */
+constexpr int64_t kPassCutMinBatch = 8192;          /* multi-phase solve: smaller launches run in one phase */
+constexpr int64_t kWaveWholeMax = 16;               /* one instance per wavefront: launches up to this size give it the whole wave */
+constexpr int64_t kTailMinBatch = 4096;             /* deferred tails: smaller launches finish their own stragglers */
+constexpr int kTailFewFrom = 8;                     /* ... a wave's last tail_few lanes are handed over after this many passes */
+constexpr int kSliceFreshDiv = 4;                   /* ... a tail slice's grid: a lane per survivor and one per 4 fresh entries */
+constexpr int64_t kAutoShareLo = 983, kAutoShareHi = 5243;   /* ... MPC_TAIL_AUTO: 1.5 % and 8 % of a batch, in 1/65536 */
 
 /* One queue of deferred instances: the fresh queue a launch hands its stragglers to, or the list of survivors a tail slice
  * leaves for the next one.  Entry e: column e of `park` ([kTailRows][cap]: Solver::park scalars, the instance's inputs, where
@@ -131,7 +140,6 @@ struct MpcPhase {
    * fp64 solver resuming from that list: the parked iterate, in the fp32 record layout of src_ws (tiles of src_tile_reals
    * floats), is converted field by field, the point is re-evaluated in fp64 and the solve goes on to tol and the polish. */
   int32_t promote_out, promote_in;
-  int32_t promote_cap;      /* iterations the fp32 phase may spend on an instance (0: Solver::kPromoteIterCap) */
   int64_t src_tile_reals;
   /* The promoted iterates travel in a buffer of their own, [list position / 64][N-1][IT_SZ][64] reals of the fp32 record:
    * a lane that has handed its instance over is free at once -- it takes the next instance while the launch has any, and
@@ -143,7 +151,6 @@ struct MpcPhase {
    * different times nearly every pass would have one.  So finished lanes WAIT until `refill_min` lanes of the wave are
    * waiting, or `refill_wait` passes have gone by, or nothing else is running; then all of them are served at once. */
   int32_t refill_min, refill_wait;
-  int32_t refill_floor;     /* no further takes once fewer lanes than this are running (0 = take whenever there is work) */
   /* Lane compaction (MPC_LANE_COMPACT=gap, measurement aid).  Memory is fetched in 128-byte lines = the 16-byte groups of 8
    * neighbouring lanes, so a line is fetched as long as ONE of its 8 lanes still runs (tools/traffic_model.py: the launch
    * fetches 1.24 x what its running lanes ask for).  Once the launch's counter is exhausted, a wave whose running lanes are
@@ -151,9 +158,6 @@ struct MpcPhase {
    * inside them: solver scalars through LDS (the staging buffers are idle between passes), set-up repeated from the inputs,
    * the iterate copied column to column -- the arithmetic of an instance does not depend on its lane. */
   int32_t compact_gap, compact_cooldown;   /* (passes without another move after one) */
-  /* Tile pool (MpcTilePool, optional): instead of tile number blockIdx of the handle's own workspace a wave takes a free
-   * tile from the pool of ITS XCD and gives it back when it leaves, so that the addresses the device cycles through are
-   * the tiles of the resident waves and not those of every batch in flight. */
   /* Deferred tails (MpcParams.tail_cut): an instance still running after tail_cut passes is handed to the handle's tail
    * queue -- solver scalars, its inputs and its current iterate are COPIED out, so the lane and the workspace are free at
    * once -- and reported as MPC_STATUS_PENDING; mpc_tail_kernel finishes it from another stream.  A full queue (t_cap) makes
@@ -169,9 +173,6 @@ struct MpcPhase {
   MpcTailQ tq;                     /* the batch's fresh queue */
   int32_t *zero_next;              /* first launch of a solve call: kCounterInts counters to reset for a later call (no memset launches on
                                     * the stream: on a full device each of those little launches waits for a free SIMD) */
-  unsigned long long *pool_bits;   /* [8][pool_words]: bit set = tile free; nullptr = no pool */
-  void *pool_base;                 /* [8][pool_tiles] tiles */
-  int32_t pool_tiles, pool_words;  /* per XCD */
   /* SOC builds (MpcParams.max_soc > 0): the SOC records, [wave of this launch][N-1][SOC_SZ / G][64][G] reals.  A correction lives
    * within one line search of one lane, so they go with the launch's wave number, not with the workspace tile. */
   void *soc_ws;
@@ -201,8 +202,6 @@ __device__ __forceinline__ void rows_copy(double *__restrict__ dk, int64_t dl, c
   }
 }
 
-/* OCC = waves per SIMD the register allocation is held to: the fp64 solver needs ~380 registers (1); the fp32 solver
- * fits 256 with a few spilled values (2), or runs unconstrained (1) */
 /* what Solver::unpack writes through when the arrays at the ABI are of another type than the solver's reals */
 template <class RIO, class R> struct OutRef {
   RIO *p;
@@ -212,8 +211,8 @@ template <class RIO, class R> struct OutRef {
 /* RIO: the type of the arrays at the ABI (inputs, outputs); R: the solver's.  They differ only in the fp64 phase of a
  * mixed-precision solve on an MPC_PRECISION_F32 handle (RIO = float, R = double).  RSRC: the reals of the workspace a
  * promote_in phase takes its iterates from. */
-template <bool STAGING, class R, int OCC, class RIO = R, class RSRC = RIO, bool SOC = false>
-__global__ __launch_bounds__(kBlock, OCC) void mpc_solve_kernel(
+template <bool STAGING, class R, class RIO = R, class RSRC = RIO, bool SOC = false>
+__global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
     const MpcParams P, const int64_t B, const int64_t ld, const int64_t ldo, const RIO *__restrict__ state,
     const RIO *__restrict__ coeffs, const RIO *__restrict__ yaw_lo, const RIO *__restrict__ yaw_hi,
     const RIO *__restrict__ weights, RIO *__restrict__ out, RIO *__restrict__ traj,
@@ -227,50 +226,16 @@ __global__ __launch_bounds__(kBlock, OCC) void mpc_solve_kernel(
   WS ws;
   ws.tile = (typename WS::greal *)(wsbase + (int64_t)blockIdx.x * tile_reals);
   if constexpr (SOC) ws.soc_tile = (typename WS::greal *)((R *)T.soc_ws + (int64_t)blockIdx.x * (P.N - 1) * FL::SOC_SZ * 64);
-#if defined(__HIP_DEVICE_COMPILE__)
-  int pool_word = -1, pool_bit = 0;
-  unsigned long long *pool_mine = nullptr;
-  if (T.pool_bits) {
-    /* first free tile of this XCD's pool (lowest number first: the set of tiles in use stays compact); a tile is only
-     * ever used by waves of one XCD, so everything written to it sits in one L2.  No free tile (cannot happen while the
-     * pool holds more tiles than an XCD has wave slots): the wave keeps its own tile of the handle's workspace. */
-    const unsigned xcc = (unsigned)__builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u;   /* HW_REG_XCC_ID[3:0] */
-    pool_mine = T.pool_bits + (size_t)xcc * (size_t)T.pool_words;
-    int got = -1;
-    if (threadIdx.x == 0) {
-      for (int w = 0; w < (T.pool_tiles + 63) / 64 && got < 0; ++w) {   /* the tile bits only: the XCD's last two words are its usage record */
-        unsigned long long v = __hip_atomic_load(pool_mine + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        while (v) {
-          const int b = __builtin_ctzll(v);
-          const unsigned long long m = 1ull << b;
-          const unsigned long long old = atomicAnd(pool_mine + w, ~m);
-          if (old & m) { got = w * 64 + b; break; }
-          v = old & ~m;
-        }
-      }
-    }
-    got = __builtin_amdgcn_readfirstlane(got);
-    if (got >= T.pool_tiles) got = -1;       /* (bits beyond the pool are never set; belt and braces) the wave keeps the handle's own tile */
-    if (got >= 0 && threadIdx.x == 0) {      /* usage record for mpc_debug_tile_pool: claims, highest tile number + 1 */
-      atomicAdd(pool_mine + T.pool_words - 2, 1ull);
-      atomicMax(pool_mine + T.pool_words - 1, (unsigned long long)(got + 1));
-    }
-    if (got >= 0) {
-      pool_word = got >> 6; pool_bit = got & 63;
-      ws.tile = (typename WS::greal *)((R *)T.pool_base + ((int64_t)xcc * T.pool_tiles + got) * tile_reals);
-    }
-  }
-#endif
   ws.lane = threadIdx.x;
   ws.lbuf = (typename WS::lreal *)smem;
   if (T.zero_next && blockIdx.x == 0 && threadIdx.x < kCounterInts) T.zero_next[threadIdx.x] = 0;
   SV S(P, ws);
-  if (T.promote_out) { S.promote_mu = (R)P.mixed_switch_mu; if (T.promote_cap > 0) S.promote_cap = T.promote_cap; }
+  if (T.promote_out) S.promote_mu = (R)P.mixed_switch_mu;
   int64_t i = 0;
   bool have = false, more = true, fin = false;   /* holds a running instance / may still get one / holds a finished one */
   bool queue_full = false;                       /* deferred tails: the batch's queue slot has no room left */
   bool col_busy = false;                         /* this lane's column holds a parked iterate */
-  int attempt = 0, it_total = 0, passes = 0, fin_status = 0, waited = 0, cooldown = 0, passes_wave = 0;
+  int attempt = 0, it_total = 0, passes = 0, fin_status = 0, waited = 0, cooldown = 0;
   const int64_t n_work = T.resume ? (int64_t)*T.n_in : B;
   (void)col_busy; (void)cooldown;
   for (;;) {
@@ -335,9 +300,6 @@ __global__ __launch_bounds__(kBlock, OCC) void mpc_solve_kernel(
           if (iters) iters[i] = S.iters + it_total;
           fin = false;
         }
-        /* a wave most of whose lanes have finished starts nothing new: what it would take runs denser in a wave that starts
-         * fresh (the grid has a lane for every instance), and this one would last twice as long for a handful of lanes */
-        if (T.refill_floor > 0 && passes_wave > 0 && MPC_WAVE_COUNT(have) < T.refill_floor) more = false;
         bool exhausted = false;
         if (!have && more) {
           const int64_t pos = (int64_t)atomicAdd(T.take, 1);
@@ -487,7 +449,6 @@ __global__ __launch_bounds__(kBlock, OCC) void mpc_solve_kernel(
     }
 #endif
     if (!MPC_WAVE_ANY(have || more || fin)) break;
-    ++passes_wave;
     const bool few = T.tail_few > 0 && !MPC_WAVE_ANY(more) && MPC_WAVE_COUNT(have) <= T.tail_few;
     if (have) {
       const int r = S.step();
@@ -501,7 +462,7 @@ __global__ __launch_bounds__(kBlock, OCC) void mpc_solve_kernel(
         /* mixed precision: this phase has taken the instance as far as it is asked to; it waits for the wave's next hand-over */
         fin = true; fin_status = (r == SV::MPC_PROMOTE && S.promote_clean) ? kFinPromote : kFinScratch; have = false;
       } else if (r == SV::MPC_PROMOTE || (T.promote_out && r == MPC_STATUS_NUMERIC)) {
-        /* the same with the iterate left in its column (MPC_PROMOTE_BUFFER=0): the next phase's solver takes over.
+        /* the same with the iterate left in its column (MpcParams.f32_phase_refill = 0): the next phase's solver takes over.
          * Not-a-number in the fp32 phase (states far from the origin late in a closed loop: x^4 terms, lost digits) is not a
          * verdict on the instance: the fp64 solver gets it from the start point (row 35 of the parked scalars says so). */
         const int64_t pos = (int64_t)atomicAdd(T.n_out, 1);
@@ -574,13 +535,6 @@ __global__ __launch_bounds__(kBlock, OCC) void mpc_solve_kernel(
       }
     }
   }
-#if defined(__HIP_DEVICE_COMPILE__)
-  if (pool_word >= 0) {
-    /* every store of this wave to the tile has been acknowledged before the tile can be handed on */
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (threadIdx.x == 0) atomicOr(pool_mine + pool_word, 1ull << pool_bit);
-  }
-#endif
 }
 
 /* Deferred tails: a TAIL SLICE works on everything the launches have handed over (MpcPhase.tail_cut) for a bounded number of
@@ -612,8 +566,8 @@ struct MpcSliceArgs {
   void *soc_ws;                    /* SOC builds: the SOC records of the slice's waves (see MpcPhase.soc_ws) */
 };
 
-template <bool STAGING, class R, int OCC, class RIO = R, bool SOC = false>
-__global__ __launch_bounds__(kBlock, OCC) void mpc_tail_slice_kernel(const MpcParams P, const MpcSliceArgs A, R *__restrict__ wsbase,
+template <bool STAGING, class R, class RIO = R, bool SOC = false>
+__global__ __launch_bounds__(kBlock, 1) void mpc_tail_slice_kernel(const MpcParams P, const MpcSliceArgs A, R *__restrict__ wsbase,
                                                                      const int64_t tile_reals) {
   extern __shared__ double smem[];
   using WS = std::conditional_t<SOC, mpc::TiledSocWorkspace<STAGING, R>, mpc::TiledWorkspace<STAGING, R>>;
@@ -782,41 +736,6 @@ __global__ __launch_bounds__(kBlock, OCC) void mpc_tail_slice_kernel(const MpcPa
   }
 }
 
-/* Small launches: the N-step variables of every instance resident in LDS (mpc::LdsWorkspace), one instance per lane,
- * LANES instances per workgroup (= per wave), no workspace in HBM at all.  Same solver, bitwise the same results. */
-template <class R, int LANES>
-__global__ __launch_bounds__(kBlock, 1) void mpc_solve_lds_kernel(
-    const MpcParams P, const int64_t B, const int64_t ld, const int64_t ldo, const R *__restrict__ state,
-    const R *__restrict__ coeffs, const R *__restrict__ yaw_lo, const R *__restrict__ yaw_hi,
-    const R *__restrict__ weights, R *__restrict__ out, R *__restrict__ traj,
-    int32_t *__restrict__ status, int32_t *__restrict__ iters) {
-  extern __shared__ double smem[];
-  using WS = mpc::LdsWorkspace<R, LANES>;
-  using SV = mpc::Solver<WS, R>;
-  const int lane = threadIdx.x;
-  const int64_t i = (int64_t)blockIdx.x * LANES + lane;
-  if (lane >= LANES || i >= B) return;                 /* no barriers in this kernel: lanes are independent */
-  WS ws;
-  ws.base = (typename WS::lreal *)smem;
-  ws.lane = lane;
-  SV S(P, ws);
-  R st[6], cf[MPC_NCOEF], w[MPC_NW];
-#pragma unroll
-  for (int q = 0; q < 6; q++) st[q] = state[q * ld + i];
-#pragma unroll
-  for (int q = 0; q < MPC_NCOEF; q++) cf[q] = coeffs[q * ld + i];
-#pragma unroll
-  for (int q = 0; q < MPC_NW; q++) w[q] = weights ? weights[q * ld + i] : (R)P.weights[q];
-  int r = S.setup(st, cf, yaw_lo[i], yaw_hi[i], w, true);
-  if (r == MPC_STATUS_SUCCESS) r = S.solve();
-  R *o = out + i;
-  R *t = traj ? traj + i : nullptr;
-  const int64_t l = ldo;
-  S.unpack([o, l](int q) -> R & { return o[q * l]; }, [t, l](int q) -> R & { return t[q * l]; }, traj != nullptr, yaw_lo[i], yaw_hi[i]);
-  status[i] = r;
-  if (iters) iters[i] = S.iters;
-}
-
 /* ONE INSTANCE PER WAVEFRONT, or per LPI = 16 / 32 neighbouring lanes of one (small launches: one MPC::solve() per telemetry
  * message is the reference's own use).  The instance's N-step variables live in the workgroup's LDS ([stage][field][instance],
  * 3.7 KB per instance at N = 10 in fp64); every lane of the group
@@ -973,66 +892,16 @@ __global__ void mpc_debug_math_kernel(int64_t n, const double *x, double *sn, do
 
 }  // namespace
 
-/* One pool of workspace tiles per (device, tile size), shared by every handle created with MPC_TILE_POOL=1 */
-struct MpcTilePool {
-  int device = 0;
-  size_t tile_bytes = 0;
-  int tiles = 0, words = 0;        /* per XCD */
-  void *base = nullptr;
-  unsigned long long *bits = nullptr;
-  int refs = 0;
-};
-static std::mutex g_pool_mutex;
-static std::vector<MpcTilePool *> g_pools;
-
-static MpcTilePool *pool_acquire(int device, size_t tile_bytes, int tiles_per_xcd) {
-  std::lock_guard<std::mutex> lock(g_pool_mutex);
-  for (MpcTilePool *p : g_pools)
-    if (p->device == device && p->tile_bytes == tile_bytes && p->tiles == tiles_per_xcd) { ++p->refs; return p; }
-  MpcTilePool *p = new MpcTilePool();
-  p->device = device; p->tile_bytes = tile_bytes; p->tiles = tiles_per_xcd; p->words = (tiles_per_xcd + 63) / 64;
-  /* every XCD's words on cache lines of their own; the last two words of an XCD are its usage record */
-  p->words = (p->words + 2 + 15) / 16 * 16;
-  if (hipMalloc(&p->base, tile_bytes * (size_t)tiles_per_xcd * 8) != hipSuccess ||
-      hipMalloc((void **)&p->bits, sizeof(unsigned long long) * (size_t)p->words * 8) != hipSuccess) {
-    if (p->base) (void)hipFree(p->base);
-    delete p;
-    return nullptr;
-  }
-  std::vector<unsigned long long> init((size_t)p->words * 8, 0ull);
-  for (int x = 0; x < 8; x++)
-    for (int t = 0; t < tiles_per_xcd; t++) init[(size_t)x * p->words + t / 64] |= 1ull << (t % 64);
-  if (hipMemcpy(p->bits, init.data(), init.size() * sizeof(unsigned long long), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(p->base); (void)hipFree(p->bits); delete p; return nullptr;
-  }
-  p->refs = 1;
-  g_pools.push_back(p);
-  return p;
-}
-static void pool_release(MpcTilePool *p) {
-  if (!p) return;
-  std::lock_guard<std::mutex> lock(g_pool_mutex);
-  if (--p->refs > 0) return;
-  for (size_t i = 0; i < g_pools.size(); i++) if (g_pools[i] == p) { g_pools.erase(g_pools.begin() + i); break; }
-  (void)hipFree(p->base); (void)hipFree(p->bits);
-  delete p;
-}
-
 struct MpcHandle {
   MpcParams params;
   int device = 0;
   int64_t max_batch = 0;
   int64_t ws_stride = 0;   /* reals (double, or float for MPC_PRECISION_F32) per wavefront tile of the workspace */
   bool staging = true;
-  int lds_lanes = 0;       /* instances per workgroup of the LDS-resident kernel (0: N too large for it, or MPC_LDS=0) */
   int64_t wave_max_batch = 0;   /* launches up to this size run one instance per wavefront (mpc_solve_wave_kernel); 0: never */
-  int64_t wave_whole_max = 16;  /* ... and up to this size an instance gets the whole wave (v_readlane) even where 16 lanes would do */
-  int64_t lds_max_batch = 0;   /* launches up to this size take the LDS-resident kernel: lds_lanes x number of CUs */
   bool mixed = false;      /* two phases per solve: fp32 up to MpcParams.mixed_switch_mu, then fp64 to tol (f32_finish on an F32 handle,
                             * f64_f32_start on an F64 handle) */
   int64_t ws_stride_f32 = 0, ws_stride_f64 = 0;   /* reals per wavefront tile of either record layout */
-  bool occ2 = false;       /* fp32: MPC_F32_OCC=2 selects the build held to 256 registers (two waves per SIMD, ~110 spill reloads per
-                            * pass); the unconstrained build (296 registers, one wave per SIMD) measured 7 % faster on the final code */
   int64_t io_stride = 0;   /* leading dimension of the handle's own staging arrays */
   void *ws = nullptr;
   hipStream_t stream = nullptr;
@@ -1055,27 +924,17 @@ struct MpcHandle {
   int64_t st_B = 0;
   hipEvent_t st_ev = nullptr;
   bool stats_pending = false;
-  int inst_per_lane = 1;      /* MPC_INSTANCES_PER_LANE: waves = ceil(B / 64 / inst_per_lane) */
-  int refill_min = 16, refill_wait = 8;   /* hand-over policy of the persistent kernel (MpcPhase), MPC_REFILL_MIN / MPC_REFILL_WAIT */
-  int refill_floor = 0, refill_floor_f32 = 0;   /* MPC_REFILL_FLOOR / MPC_REFILL_FLOOR_F32 (the fp32 phase of a mixed solve) */
   int compact_gap = 0;        /* MpcParams.lane_compact, or MPC_LANE_COMPACT in the environment (measurement aid): see MpcPhase.compact_gap */
   bool compact_env = false;
-  int compact_cooldown = 2;   /* MPC_LANE_COMPACT_COOLDOWN */
   int64_t compact_min_batch = 8192;   /* smaller launches are latency-bound: the moves cost more than the lines they save */
-  int finish_div = 1;         /* mixed precision: the fp64 phase runs ceil(waves / finish_div) waves whose lanes take the promoted
-                               * instances in turn (MPC_FINISH_DIV) */
-  int finish_refill_min = 16, finish_refill_wait = 8;   /* its hand-over policy (MPC_FINISH_REFILL_MIN / _WAIT) */
   /* multi-phase solve: second workspace, two parked-instance lists and two sets of scalars (allocated on first use) */
-  int n_cuts = 0;             /* MpcParams.pass_cut + pass_cut_next[], or MPC_PASS_CUT=a,b,c,d in the environment (none = single launch) */
+  int n_cuts = 0;             /* MpcParams.pass_cut + pass_cut_next[] (none = single launch) */
   int cuts[kMaxCuts] = {0, 0, 0, 0};
-  int64_t two_phase_min = 8192;
   void *ws2 = nullptr;
   double *d_park = nullptr;   /* [2][PARK_ROWS][io_stride] */
   void *d_piter = nullptr;    /* mixed precision: the promoted iterates, [io_stride / 64][N-1][IT_SZ of the fp32 record][64] floats */
-  int promote_cap = 0;        /* MPC_PROMOTE_CAP (measurement aid; 0 = Solver::kPromoteIterCap) */
-  bool promote_buffer = false, promote_env = false;   /* MpcParams.f32_phase_refill (MPC_PROMOTE_BUFFER in the environment overrides: measurement aid) */
+  bool promote_buffer = false;   /* MpcParams.f32_phase_refill */
   int32_t *d_list = nullptr;  /* [2][2][io_stride]: instance, source column */
-  MpcTilePool *pool = nullptr;   /* MPC_TILE_POOL=1 */
   /* deferred tails (MpcParams.tail_cut > 0; allocated on first use): see "tail slices" below */
   struct TailSlot {                /* one per batch whose stragglers may be outstanding (ring of tail_ring) */
     int64_t batch_id = 0;          /* 0: never used */
@@ -1102,10 +961,9 @@ struct MpcHandle {
   bool tail_ready = false;
   bool tail_double = true;     /* the solver of the tail slices: fp64, or fp32 on a pure MPC_PRECISION_F32 handle */
   int tail_ring = 0, tail_waves = 256, tail_priority = 0, slice_passes = 16;
-  /* a slice's grid: a lane per survivor (they are the long chains: most use the slice's whole budget) and one per fresh_div fresh
-   * entries (an instance just over the cut needs a few more passes, so a lane works off several of them in turn) */
-  int fresh_div = 4;
-  int64_t tail_cap = 0, surv_cap = 0, tail_min_batch = 4096;
+  /* (a slice's grid: a lane per survivor -- they are the long chains: most use the slice's whole budget -- and one per
+   * kSliceFreshDiv fresh entries: an instance just over the cut needs a few more passes, so a lane works off several in turn) */
+  int64_t tail_cap = 0, surv_cap = 0;
   hipStream_t tail_stream = nullptr;
   MpcTailQ fq_dev[kFreshRing] = {}, surv_dev[2] = {};   /* device storage of the fresh queues and the two survivor lists */
   int32_t *d_tcount = nullptr;   /* [kFreshRing + 2 + 6 kSliceRing]: counts of the fresh queues, of the survivor lists, slice work and exit counters, slice tallies */
@@ -1138,11 +996,9 @@ struct MpcHandle {
    * cuts of 16 ... 32 within 5 % of each other, 20 best; few 0 / 2 / 4 / 8: 43.4 / 43.8 / 44.7 / 44.8 M solves/s).  The arithmetic
    * of an instance does not depend on where it is carried on, so these change timing only.  auto_share: running mean of the
    * share of a batch that was handed over, in 1/65536 (mpc_tail_info). */
-  int64_t hold_batches = 0;
-  int tail_few = 4, tail_few_from = 8;        /* MPC_TAIL_FEW / MPC_TAIL_FEW_FROM (see MpcPhase.tail_few) */
+  int tail_few = 4;                           /* MPC_TAIL_FEW (see MpcPhase.tail_few) */
   int auto_cut = 20, auto_base = 20;
   int64_t auto_share = -1;
-  int64_t auto_lo = 983, auto_hi = 5243;      /* 1.5 % and 8 % of a batch, in 1/65536 (MPC_TAIL_AUTO_LO / _HI) */
   int64_t batch_seq = 0;         /* id of the most recent batch (every solve call counts) */
   int64_t n_deferred = 0;        /* deferring batches so far: batch k of them uses slot k % tail_ring and fresh queue k % kFreshRing */
   double *d_tel = nullptr;       /* mpc_telemetry_batch_host: device staging, grown on demand */
@@ -1152,29 +1008,17 @@ struct MpcHandle {
   bool timed = false;
 };
 
-/* the cut schedule of the multi-phase solve: MpcParams.pass_cut, pass_cut_next[0..2] (a zero ends the list), overridden
- * by MPC_PASS_CUT=a[,b[,c[,d]]] in the environment */
 static void set_wave_limit(MpcHandle *h, const MpcParams *p) {
   h->wave_max_batch = p->wave_max_batch == 0 ? 1024 : (p->wave_max_batch < 0 ? 0 : p->wave_max_batch);
   if (const char *e = getenv("MPC_WAVE_MAX_BATCH")) h->wave_max_batch = atoll(e);      /* (A/B measurements) */
-  if (const char *e = getenv("MPC_WAVE_WHOLE_MAX")) h->wave_whole_max = atoll(e);
   if (p->f64_f32_start == MPC_F32_START_ON || (p->precision == MPC_PRECISION_F32 && p->f32_finish != 0)) h->wave_max_batch = 0;
 }
 
+/* the cut schedule of the multi-phase solve: MpcParams.pass_cut, pass_cut_next[0..2] (a zero ends the list) */
 static void set_cuts(MpcHandle *h, const MpcParams *p) {
   h->n_cuts = 0;
   const int32_t given[kMaxCuts] = {p->pass_cut, p->pass_cut_next[0], p->pass_cut_next[1], p->pass_cut_next[2]};
   for (int q = 0; q < kMaxCuts && given[q] > 0; q++) h->cuts[h->n_cuts++] = given[q];
-  if (const char *e = getenv("MPC_PASS_CUT")) {
-    h->n_cuts = 0;
-    for (const char *c = e; *c && h->n_cuts < kMaxCuts;) {
-      const int v = atoi(c);
-      if (v <= 0) break;
-      h->cuts[h->n_cuts++] = v;
-      while (*c && *c != ',') ++c;
-      if (*c == ',') ++c;
-    }
-  }
 }
 
 /* two phases per solve (fp32 iterations, fp64 finish)?  F32 handles: f32_finish; F64 handles: f64_f32_start = 1, or 2
@@ -1208,24 +1052,6 @@ static int validate_params(const MpcParams *p) {
 
 extern "C" int mpc_abi_version(void) { return MPC_ABI_VERSION; }
 
-/* state of the handle's tile pool: per XCD (free tiles now, tiles in the pool, claims so far, highest tile number used + 1) */
-extern "C" int mpc_debug_tile_pool(MpcHandle *h, int64_t *out32) {
-  if (!h || !out32) return MPC_ERR_INVALID;
-  for (int q = 0; q < 32; q++) out32[q] = 0;
-  if (!h->pool) { g_last_error = "no tile pool on this handle (MPC_TILE_POOL=1 at mpc_create)"; return MPC_ERR_UNSUPPORTED; }
-  MPC_ON_DEVICE(h);
-  MPC_HIP_CHECK(hipDeviceSynchronize());
-  std::vector<unsigned long long> bits((size_t)h->pool->words * 8);
-  MPC_HIP_CHECK(hipMemcpy(bits.data(), h->pool->bits, bits.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  for (int x = 0; x < 8; x++) {
-    const unsigned long long *b = bits.data() + (size_t)x * h->pool->words;
-    int64_t fr = 0;
-    for (int t = 0; t < h->pool->tiles; t++) fr += (b[t / 64] >> (t % 64)) & 1ull;
-    out32[4 * x + 0] = fr; out32[4 * x + 1] = h->pool->tiles;
-    out32[4 * x + 2] = (int64_t)b[h->pool->words - 2]; out32[4 * x + 3] = (int64_t)b[h->pool->words - 1];
-  }
-  return MPC_OK;
-}
 extern "C" const char *mpc_last_error(void) { return g_last_error.c_str(); }
 
 extern "C" int mpc_create(const MpcParams *p, int device, int64_t max_batch, MpcHandle **out) {
@@ -1263,45 +1089,17 @@ extern "C" int mpc_create(const MpcParams *p, int device, int64_t max_batch, Mpc
   h->staging = true;
   if (const char *e = getenv("MPC_STAGING")) h->staging = atoi(e) != 0;
   const bool f32 = p->precision == MPC_PRECISION_F32;
-  if (const char *e = getenv("MPC_F32_OCC")) h->occ2 = atoi(e) == 2;
-  if (f32) {
-    MPC_CREATE_CHECK(hipFuncSetAttribute((const void *)mpc_solve_kernel<true, float, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
-    MPC_CREATE_CHECK(hipFuncSetAttribute((const void *)mpc_solve_kernel<true, float, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
-  } else MPC_CREATE_CHECK(hipFuncSetAttribute((const void *)mpc_solve_kernel<true, double, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
+  if (f32) MPC_CREATE_CHECK(hipFuncSetAttribute((const void *)mpc_solve_kernel<true, float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
+  else MPC_CREATE_CHECK(hipFuncSetAttribute((const void *)mpc_solve_kernel<true, double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
   h->ws_stride = mpc::workspace_fields_per_instance(p->N, f32, p->initial_state_rows != 0) * 64;   /* reals per wavefront tile */
   h->ws_stride_f32 = mpc::workspace_fields_per_instance(p->N, true, p->initial_state_rows != 0) * 64;
   h->ws_stride_f64 = mpc::workspace_fields_per_instance(p->N, false, p->initial_state_rows != 0) * 64;
   h->mixed = wants_mixed(p, max_batch);
-  /* MPC_MIXED=0/1 overrides the parameter for every handle of the process: how the whole parity suite was run with the fp32
-   * start forced on (tools/r03_session.sh p); a measurement aid, not an interface */
-  if (const char *e = getenv("MPC_MIXED")) h->mixed = atoi(e) != 0;
   if (h->mixed) {
-    MPC_CREATE_CHECK(hipFuncSetAttribute((const void *)mpc_solve_kernel<true, double, 1, float, float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
-    MPC_CREATE_CHECK(hipFuncSetAttribute((const void *)mpc_solve_kernel<true, float, 1, double, double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
-    MPC_CREATE_CHECK(hipFuncSetAttribute((const void *)mpc_solve_kernel<true, double, 1, double, float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
-    MPC_CREATE_CHECK(hipFuncSetAttribute((const void *)mpc_solve_kernel<true, float, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
-  }
-  {
-    /* LDS-resident kernel: as many instances per workgroup as 160 KB hold (32, 16 or 8); one workgroup per CU */
-    const int64_t per_inst = mpc::workspace_fields_per_instance(p->N, f32, p->initial_state_rows != 0) * (int64_t)(f32 ? sizeof(float) : sizeof(double));
-    for (int lanes : {32, 16, 8})
-      if (lanes * per_inst <= kLdsPerCu) { h->lds_lanes = lanes; break; }
-    /* Measured on MI355X (tools/batch_sweep.py, same box, B = 1 ... 16 384): the LDS-resident kernel is 5-9 % SLOWER than the
-     * streaming kernel at every size -- a lone wave pays ~12 cycles of issue per ds_write_b64 for the 44 fields a stage
-     * stores per iteration, where the streaming kernel's global stores are fire-and-forget, and the stage step is bound by
-     * its dependent fp64 chain, not by the record's latency.  So it is opt-in: MPC_LDS=1. */
-    const char *e_lds = getenv("MPC_LDS");
-    if (!(e_lds && atoi(e_lds) == 1)) h->lds_lanes = 0;
-    h->lds_max_batch = (int64_t)h->lds_lanes * prop.multiProcessorCount;
-    const void *fn = nullptr;
-    switch (h->lds_lanes) {
-      case 32: fn = f32 ? (const void *)mpc_solve_lds_kernel<float, 32> : (const void *)mpc_solve_lds_kernel<double, 32>; break;
-      case 16: fn = f32 ? (const void *)mpc_solve_lds_kernel<float, 16> : (const void *)mpc_solve_lds_kernel<double, 16>; break;
-      case 8: fn = f32 ? (const void *)mpc_solve_lds_kernel<float, 8> : (const void *)mpc_solve_lds_kernel<double, 8>; break;
-      default: break;
-    }
-    if (fn) MPC_CREATE_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
-    if (const char *e = getenv("MPC_LDS_MAX_BATCH")) h->lds_max_batch = atoll(e);
+    MPC_CREATE_CHECK(hipFuncSetAttribute((const void *)mpc_solve_kernel<true, double, float, float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
+    MPC_CREATE_CHECK(hipFuncSetAttribute((const void *)mpc_solve_kernel<true, float, double, double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
+    MPC_CREATE_CHECK(hipFuncSetAttribute((const void *)mpc_solve_kernel<true, double, double, float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
+    MPC_CREATE_CHECK(hipFuncSetAttribute((const void *)mpc_solve_kernel<true, float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
   }
   /* Small launches run ONE INSTANCE PER WAVEFRONT, or per 16 / 32 of its lanes (mpc_solve_wave_kernel): the lane kernel puts 64
    * instances into a wave, which is bound by the instructions it issues -- one MPC::solve() 0.68 ms; with the sweeps shared
@@ -1325,33 +1123,9 @@ extern "C" int mpc_create(const MpcParams *p, int device, int64_t max_batch, Mpc
   if ((e = hipMalloc((void **)&h->d_stats, kStatWords * sizeof(unsigned long long))) != hipSuccess) return fail(e, "hipMalloc");
   if ((e = hipEventCreateWithFlags(&h->ev_stats, hipEventDisableTiming)) != hipSuccess) return fail(e, "hipEventCreate");
   set_cuts(h, p);
-  if (const char *ep = getenv("MPC_TILE_POOL")) {
-    if (atoi(ep) > 0) {
-      /* tiles per XCD: its wave slots for this kernel (CUs / 8 XCDs x 4 SIMDs x waves per SIMD) and a margin */
-      /* (a partition mode that exposes fewer XCDs than 8 only makes the pools larger than needed; a wave that finds its
-       * pool empty keeps the tile of the handle's own workspace) */
-      const int per_xcd = (prop.multiProcessorCount + 7) / 8 * 4 * ((f32 && h->occ2) ? 2 : 1);
-      int extra = 16;
-      if (const char *ex = getenv("MPC_TILE_POOL_EXTRA")) extra = atoi(ex);
-      h->pool = pool_acquire(device, (size_t)h->ws_stride * (f32 ? sizeof(float) : sizeof(double)), per_xcd + (extra > 0 ? extra : 0));
-      if (!h->pool) { g_last_error = "hipMalloc(tile pool)"; mpc_destroy(h); return MPC_ERR_HIP; }
-    }
-  }
-  if (const char *e3 = getenv("MPC_PHASE_MIN_BATCH")) { h->two_phase_min = atoll(e3); if (h->two_phase_min < 1) h->two_phase_min = 1; }
-  if (const char *e4 = getenv("MPC_REFILL_MIN")) { h->refill_min = atoi(e4); if (h->refill_min < 1) h->refill_min = 1; }
-  if (const char *e5 = getenv("MPC_REFILL_WAIT")) { h->refill_wait = atoi(e5); if (h->refill_wait < 0) h->refill_wait = 0; }
-  if (const char *e2 = getenv("MPC_INSTANCES_PER_LANE")) { h->inst_per_lane = atoi(e2); if (h->inst_per_lane < 1) h->inst_per_lane = 1; }
   h->compact_gap = p->lane_compact >= 0 ? p->lane_compact : (p->N >= 15 ? 1 : 2);
   if (const char *e9 = getenv("MPC_LANE_COMPACT")) { h->compact_gap = atoi(e9); h->compact_env = true; if (h->compact_gap < 0) h->compact_gap = 0; }
-  if (const char *e10 = getenv("MPC_LANE_COMPACT_COOLDOWN")) { h->compact_cooldown = atoi(e10); if (h->compact_cooldown < 0) h->compact_cooldown = 0; }
   h->promote_buffer = p->f32_phase_refill != 0;
-  if (const char *e11 = getenv("MPC_PROMOTE_BUFFER")) { h->promote_buffer = atoi(e11) != 0; h->promote_env = true; }
-  if (const char *e12 = getenv("MPC_REFILL_FLOOR")) h->refill_floor = atoi(e12);
-  if (const char *e13 = getenv("MPC_REFILL_FLOOR_F32")) h->refill_floor_f32 = atoi(e13);
-  if (const char *e15 = getenv("MPC_PROMOTE_CAP")) h->promote_cap = atoi(e15);
-  if (const char *e6 = getenv("MPC_FINISH_DIV")) { h->finish_div = atoi(e6); if (h->finish_div < 1) h->finish_div = 1; }
-  if (const char *e7 = getenv("MPC_FINISH_REFILL_MIN")) { h->finish_refill_min = atoi(e7); if (h->finish_refill_min < 1) h->finish_refill_min = 1; }
-  if (const char *e8 = getenv("MPC_FINISH_REFILL_WAIT")) { h->finish_refill_wait = atoi(e8); if (h->finish_refill_wait < 0) h->finish_refill_wait = 0; }
   *out = h;
   return MPC_OK;
 }
@@ -1362,7 +1136,7 @@ extern "C" int mpc_set_params(MpcHandle *h, const MpcParams *p) {
   if (!h) return MPC_ERR_INVALID;
   int rc = validate_params(p);
   if (rc != MPC_OK) return rc;
-  if (wants_mixed(p, h->max_batch) != h->mixed && !getenv("MPC_MIXED")) {
+  if (wants_mixed(p, h->max_batch) != h->mixed) {
     g_last_error = "f32_finish / f64_f32_start cannot change on a live handle (they decide the workspaces)"; return MPC_ERR_INVALID;
   }
   if (p->N != h->params.N || p->precision != h->params.precision || (p->initial_state_rows != 0) != (h->params.initial_state_rows != 0)) {
@@ -1382,7 +1156,7 @@ extern "C" int mpc_set_params(MpcHandle *h, const MpcParams *p) {
   set_cuts(h, p);
   set_wave_limit(h, p);
   if (!h->compact_env) h->compact_gap = p->lane_compact >= 0 ? p->lane_compact : (p->N >= 15 ? 1 : 2);
-  if (!h->promote_env) h->promote_buffer = p->f32_phase_refill != 0;
+  h->promote_buffer = p->f32_phase_refill != 0;
   return MPC_OK;
 }
 
@@ -1403,7 +1177,6 @@ extern "C" void mpc_destroy(MpcHandle *h) {
   if (h->d_counter) (void)hipFree(h->d_counter);
   if (h->ws2) (void)hipFree(h->ws2);
   if (h->soc_ws) (void)hipFree(h->soc_ws);
-  pool_release(h->pool);
   if (h->d_park) (void)hipFree(h->d_park);
   if (h->d_list) (void)hipFree(h->d_list);
   if (h->d_piter) (void)hipFree(h->d_piter);
@@ -1451,26 +1224,6 @@ static int soc_alloc(MpcHandle *h, void **buf, int64_t waves) {
   return MPC_OK;
 }
 
-template <class R, int LANES>
-static int launch_lds_n(MpcHandle *h, int64_t B, int64_t ld, int64_t ldo, const R *state, const R *coeffs, const R *yaw_lo,
-                        const R *yaw_hi, const R *weights, R *out, R *traj, int32_t *status, int32_t *iters, hipStream_t s) {
-  const size_t lds = (size_t)mpc::workspace_fields_per_instance(h->params.N, sizeof(R) == 4, h->params.initial_state_rows != 0) * sizeof(R) * LANES;
-  const unsigned grid = (unsigned)((B + LANES - 1) / LANES);
-  hipLaunchKernelGGL((mpc_solve_lds_kernel<R, LANES>), dim3(grid), dim3(kBlock), lds, s, h->params, B, ld, ldo, state, coeffs, yaw_lo, yaw_hi,
-                     weights, out, traj, status, iters);
-  MPC_HIP_CHECK(hipGetLastError());
-  return MPC_OK;
-}
-template <class R>
-static int launch_lds(MpcHandle *h, int64_t B, int64_t ld, int64_t ldo, const R *state, const R *coeffs, const R *yaw_lo,
-                      const R *yaw_hi, const R *weights, R *out, R *traj, int32_t *status, int32_t *iters, hipStream_t s) {
-  switch (h->lds_lanes) {
-    case 32: return launch_lds_n<R, 32>(h, B, ld, ldo, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters, s);
-    case 16: return launch_lds_n<R, 16>(h, B, ld, ldo, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters, s);
-    default: return launch_lds_n<R, 8>(h, B, ld, ldo, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters, s);
-  }
-}
-
 /* ---- deferred tails: queues, tail slices, the pump, waiting for a batch -------------------------------------------------
  * A launch with a cut hands its stragglers to the FRESH QUEUE of its batch.  They are carried on by TAIL SLICES
  * (mpc_tail_slice_kernel) on the handle's own high-priority stream: slice k reads the survivors slice k-1 left and the fresh
@@ -1504,19 +1257,12 @@ static int tail_prepare(MpcHandle *h) {
    * instance until it is solved, and the solve calls stop deferring while the list is more than half full. */
   int64_t sc = 8 * h->tail_cap;
   if (sc < 16384) sc = 16384;
-  if (const char *e = getenv("MPC_TAIL_SURVIVORS")) { sc = atoll(e); if (sc < 64) sc = 64; }
   h->surv_cap = (sc + 63) / 64 * 64;
   if (const char *e = getenv("MPC_TAIL_WAVES")) { h->tail_waves = atoi(e); if (h->tail_waves < 1) h->tail_waves = 1; }
-  if (const char *e = getenv("MPC_TAIL_MIN_BATCH")) { h->tail_min_batch = atoll(e); if (h->tail_min_batch < 1) h->tail_min_batch = 1; }
   if (const char *e = getenv("MPC_SLICE_PASSES")) { h->slice_passes = atoi(e); if (h->slice_passes < 1) h->slice_passes = 1; }
-  if (const char *e = getenv("MPC_TAIL_HOLD_BATCHES")) h->hold_batches = atoll(e);
   if (const char *e = getenv("MPC_TAIL_FEW")) { h->tail_few = atoi(e); if (h->tail_few < 0) h->tail_few = 0; }
-  if (const char *e = getenv("MPC_TAIL_FEW_FROM")) { h->tail_few_from = atoi(e); if (h->tail_few_from < 1) h->tail_few_from = 1; }
-  if (const char *e = getenv("MPC_SLICE_FRESH_DIV")) { h->fresh_div = atoi(e); if (h->fresh_div < 1) h->fresh_div = 1; }
   h->auto_cut = h->auto_base = P.N <= 12 ? 20 : 24;
   if (const char *e = getenv("MPC_TAIL_AUTO_CUT")) { h->auto_cut = atoi(e); if (h->auto_cut < 4) h->auto_cut = 4; }
-  if (const char *e = getenv("MPC_TAIL_AUTO_LO")) h->auto_lo = atoll(e);
-  if (const char *e = getenv("MPC_TAIL_AUTO_HI")) h->auto_hi = atoll(e);
   /* The tail stream's priority: high (MPC_TAIL_PRIORITY=low|normal|high to measure the others).  A slice is a few dozen waves that
    * must find free SIMDs on a device the launches keep full: at normal priority a slice at N = 25 waited 6-12 ms for its 1.8 ms of
    * work (p90 of the retirement interval 15-30 ms), the stragglers' backlog grew until every buffer set was taken, and the long
@@ -1611,7 +1357,7 @@ static int tail_launch_slice(MpcHandle *h, bool force) {
     A.src[j] = h->fq_dev[best]; A.fresh_slot[j] = F.slot; A.fresh_batch[j] = F.batch_id;
     F.state = 2; F.slice = k;
     h->slice_abs[kr][h->slice_nabs[kr]++] = MpcHandle::Absorbed{best, F.slot, F.batch_id};
-    est += (h->fresh_avg + h->fresh_div - 1) / h->fresh_div;
+    est += (h->fresh_avg + kSliceFreshDiv - 1) / kSliceFreshDiv;
   }
   A.budget = h->slice_passes; A.ring = h->tail_ring;
   h->h_res[kr].count[28] = 0;
@@ -1627,17 +1373,15 @@ static int tail_launch_slice(MpcHandle *h, bool force) {
   if (soc) { const int rc = soc_alloc(h, &h->soc_tail, h->tail_waves); if (rc != MPC_OK) return rc; }
   A.soc_ws = h->soc_tail;
   if (soc && io32)
-    hipLaunchKernelGGL((mpc_tail_slice_kernel<true, double, 1, float, true>), dim3((unsigned)waves), dim3(kBlock), staging_lds_bytes<double>(), ts, h->params, A, (double *)h->tail_ws, tail_stride);
+    hipLaunchKernelGGL((mpc_tail_slice_kernel<true, double, float, true>), dim3((unsigned)waves), dim3(kBlock), staging_lds_bytes<double>(), ts, h->params, A, (double *)h->tail_ws, tail_stride);
   else if (soc)
-    hipLaunchKernelGGL((mpc_tail_slice_kernel<true, double, 1, double, true>), dim3((unsigned)waves), dim3(kBlock), staging_lds_bytes<double>(), ts, h->params, A, (double *)h->tail_ws, tail_stride);
-  else if (f32 && h->occ2)
-    hipLaunchKernelGGL((mpc_tail_slice_kernel<true, float, 2>), dim3((unsigned)waves), dim3(kBlock), staging_lds_bytes<float>(), ts, h->params, A, (float *)h->tail_ws, tail_stride);
+    hipLaunchKernelGGL((mpc_tail_slice_kernel<true, double, double, true>), dim3((unsigned)waves), dim3(kBlock), staging_lds_bytes<double>(), ts, h->params, A, (double *)h->tail_ws, tail_stride);
   else if (f32)
-    hipLaunchKernelGGL((mpc_tail_slice_kernel<true, float, 1>), dim3((unsigned)waves), dim3(kBlock), staging_lds_bytes<float>(), ts, h->params, A, (float *)h->tail_ws, tail_stride);
+    hipLaunchKernelGGL((mpc_tail_slice_kernel<true, float>), dim3((unsigned)waves), dim3(kBlock), staging_lds_bytes<float>(), ts, h->params, A, (float *)h->tail_ws, tail_stride);
   else if (io32)       /* the fp64 phase of a mixed-precision solve: fp32 arrays at the ABI */
-    hipLaunchKernelGGL((mpc_tail_slice_kernel<true, double, 1, float>), dim3((unsigned)waves), dim3(kBlock), staging_lds_bytes<double>(), ts, h->params, A, (double *)h->tail_ws, tail_stride);
+    hipLaunchKernelGGL((mpc_tail_slice_kernel<true, double, float>), dim3((unsigned)waves), dim3(kBlock), staging_lds_bytes<double>(), ts, h->params, A, (double *)h->tail_ws, tail_stride);
   else
-    hipLaunchKernelGGL((mpc_tail_slice_kernel<true, double, 1>), dim3((unsigned)waves), dim3(kBlock), staging_lds_bytes<double>(), ts, h->params, A, (double *)h->tail_ws, tail_stride);
+    hipLaunchKernelGGL((mpc_tail_slice_kernel<true, double>), dim3((unsigned)waves), dim3(kBlock), staging_lds_bytes<double>(), ts, h->params, A, (double *)h->tail_ws, tail_stride);
   MPC_HIP_CHECK(hipGetLastError());
   /* (what the pump reads when the slice has completed -- the survivors it left, what each absorbed batch handed over, the final
    * flags -- the slice's last wave writes into pinned host memory itself) */
@@ -1693,8 +1437,8 @@ static int tail_retire(MpcHandle *h, bool block, int *n_retired) {
          * distribution of iteration counts (weight sweeps: mean 16-18 iterations, a fat tail) -- the slices would do the launches'
          * work; one that sends next to nothing can come back towards the handle's base value */
         if (h->params.tail_cut < 0) {
-          if (h->auto_share > h->auto_hi && h->auto_cut < h->auto_base + 40) h->auto_cut += 2;
-          else if (h->auto_share < h->auto_lo && h->auto_cut > h->auto_base) --h->auto_cut;
+          if (h->auto_share > kAutoShareHi && h->auto_cut < h->auto_base + 40) h->auto_cut += 2;
+          else if (h->auto_share < kAutoShareLo && h->auto_cut > h->auto_base) --h->auto_cut;
         }
       }
       h->fresh_avg = (3 * h->fresh_avg + c + 3) / 4;
@@ -1725,10 +1469,6 @@ static int tail_pump(MpcHandle *h, bool block) {
   int n = 0;
   int rc = tail_retire(h, block && h->n_slice_done < h->n_slice, &n);
   if (rc != MPC_OK) return rc;
-  /* (measurement aid: MPC_TAIL_HOLD_BATCHES=n keeps the slices back until n batches have deferred, so that the launches can be
-   * timed with and without slices beside them; a blocking call releases them) */
-  if (!block && h->hold_batches > 0 && h->n_deferred < h->hold_batches) return MPC_OK;
-  h->hold_batches = 0;
   for (int turn = 0; turn < 2 && h->n_slice - h->n_slice_done < 2; turn++) {
     const bool in_flight = h->n_slice_done < h->n_slice;
     const bool filled = tail_has_filled(h);
@@ -1914,13 +1654,11 @@ static int launch_mixed(MpcHandle *h, int64_t B, int64_t ld, int64_t ldo, const 
   memset(&T, 0, sizeof(T));
   T.take = cb; T.n_out = cb + 1; T.zero_next = zero_next;
   T.out_inst = h->d_list; T.out_src = h->d_list + h->io_stride; T.out_park = h->d_park; T.ld_park = h->io_stride;
-  T.refill_min = h->refill_min; T.refill_wait = h->refill_wait;
+  T.refill_min = kRefillMin; T.refill_wait = kRefillWait;
   T.promote_out = 1;
-  T.promote_cap = h->promote_cap;
   T.p_iter = h->promote_buffer ? h->d_piter : nullptr;
-  T.refill_floor = h->refill_floor_f32;
-  T.compact_gap = (T.p_iter && B >= h->compact_min_batch) ? h->compact_gap : 0; T.compact_cooldown = h->compact_cooldown;
-  hipLaunchKernelGGL((mpc_solve_kernel<true, float, 1, RIO, RIO>), dim3(waves), dim3(kBlock), staging_lds_bytes<float>(), s, h->params, B, ld, ldo, state,
+  T.compact_gap = (T.p_iter && B >= h->compact_min_batch) ? h->compact_gap : 0; T.compact_cooldown = kCompactCooldown;
+  hipLaunchKernelGGL((mpc_solve_kernel<true, float, RIO, RIO>), dim3(waves), dim3(kBlock), staging_lds_bytes<float>(), s, h->params, B, ld, ldo, state,
                      coeffs, yaw_lo, yaw_hi, weights, out, traj, status, it_out, ws32, h->ws_stride_f32, T);
   MPC_HIP_CHECK(hipGetLastError());
   MpcPhase U;
@@ -1931,10 +1669,9 @@ static int launch_mixed(MpcHandle *h, int64_t B, int64_t ld, int64_t ldo, const 
   U.src_ws = ws32; U.src_tile_reals = h->ws_stride_f32;
   U.resume = 1; U.promote_in = 1;
   U.p_iter = h->promote_buffer ? h->d_piter : nullptr;
-  U.refill_min = h->finish_refill_min; U.refill_wait = h->finish_refill_wait;
+  U.refill_min = kRefillMin; U.refill_wait = kRefillWait;
   U.compact_gap = B >= h->compact_min_batch ? h->compact_gap : 0;
-  U.compact_cooldown = h->compact_cooldown;
-  const unsigned waves2 = (waves + (unsigned)h->finish_div - 1) / (unsigned)h->finish_div;
+  U.compact_cooldown = kCompactCooldown;
   /* deferred tails: the fp64 phase hands its stragglers over (the fp32 phase's chains end at kPromoteIterCap anyway) */
   /* (no early hand-over of a wave's last lanes here: the waves of this phase are partly filled by construction) */
   U.tail_cut = tail.tail_cut; U.t_slot = tail.t_slot; U.t_batch = tail.t_batch; U.tq = tail.tq; U.tail_few = 0; U.tail_few_from = tail.tail_few_from;
@@ -1943,10 +1680,10 @@ static int launch_mixed(MpcHandle *h, int64_t B, int64_t ld, int64_t ldo, const 
     const int rc = soc_alloc(h, &h->soc_ws, tiles);
     if (rc != MPC_OK) return rc;
     U.soc_ws = h->soc_ws;
-    hipLaunchKernelGGL((mpc_solve_kernel<true, double, 1, RIO, float, true>), dim3(waves2), dim3(kBlock), staging_lds_bytes<double>(), s, h->params, B, ld, ldo, state,
+    hipLaunchKernelGGL((mpc_solve_kernel<true, double, RIO, float, true>), dim3(waves), dim3(kBlock), staging_lds_bytes<double>(), s, h->params, B, ld, ldo, state,
                        coeffs, yaw_lo, yaw_hi, weights, out, traj, status, it_out, ws64, h->ws_stride_f64, U);
   } else
-    hipLaunchKernelGGL((mpc_solve_kernel<true, double, 1, RIO, float>), dim3(waves2), dim3(kBlock), staging_lds_bytes<double>(), s, h->params, B, ld, ldo, state,
+    hipLaunchKernelGGL((mpc_solve_kernel<true, double, RIO, float>), dim3(waves), dim3(kBlock), staging_lds_bytes<double>(), s, h->params, B, ld, ldo, state,
                        coeffs, yaw_lo, yaw_hi, weights, out, traj, status, it_out, ws64, h->ws_stride_f64, U);
   MPC_HIP_CHECK(hipGetLastError());
   MPC_HIP_CHECK(hipEventRecord(h->ev1, s));
@@ -1978,16 +1715,12 @@ static int launch_solve(MpcHandle *h, int64_t B, int64_t ld, int64_t ldo, const 
   if (!state || !coeffs || !yaw_lo || !yaw_hi || !out || !status) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
   MPC_ON_DEVICE(h);   /* workspace, lazy allocations and a NULL stream all belong to the handle's device */
   hipStream_t s = (hipStream_t)stream_;   /* NULL = HIP's default (null) stream, exactly as passed */
-  /* waves: one lane per instance, or fewer waves whose lanes take several instances in turn (instances_per_lane) */
-  const int64_t waves_full = (B + kBlock - 1) / kBlock;
-  int64_t waves = (waves_full + h->inst_per_lane - 1) / h->inst_per_lane;
-  if (waves < 1) waves = 1;
-  /* MpcParams.max_soc > 0 on an fp64 handle: the SOC builds of the kernels (the LDS-resident one has none: those launches take the
-   * lane kernel; the mixed-precision launch decides for its fp64 phase itself) */
+  /* waves: one lane per instance */
+  const int64_t waves = (B + kBlock - 1) / kBlock;
+  /* MpcParams.max_soc > 0 on an fp64 handle: the SOC builds of the kernels (the mixed-precision launch decides for its fp64 phase
+   * itself) */
   const bool soc = sizeof(R) == 8 && h->params.max_soc > 0;
-  const bool lds_path = !soc && h->lds_lanes > 0 && B <= h->lds_max_batch;
-  bool defer = may_defer && h->params.tail_cut != 0 && B >= h->tail_min_batch && (h->mixed || !lds_path) &&
-               !(h->wave_max_batch > 0 && B <= h->wave_max_batch);
+  bool defer = may_defer && h->params.tail_cut != 0 && B >= kTailMinBatch && !(h->wave_max_batch > 0 && B <= h->wave_max_batch);
   MpcHandle::BatchRec *rec = nullptr;
   { const int rc = batch_rec(h, h->batch_seq, &rec); if (rc != MPC_OK) return rc; }
   rec->id = 0;                                      /* (valid once the launch has been issued) */
@@ -2015,10 +1748,10 @@ static int launch_solve(MpcHandle *h, int64_t B, int64_t ld, int64_t ldo, const 
     /* (its count is zero again: the slice's last wave has reset it) */
     if (F.state == 2) MPC_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream_, h->slice_ev[F.slice % kSliceRing], 0));
   }
-  const int n_cuts = (!defer && h->inst_per_lane == 1 && B >= h->two_phase_min) ? h->n_cuts : 0;
+  const int n_cuts = (!defer && B >= kPassCutMinBatch) ? h->n_cuts : 0;
   auto tail_fields = [&](MpcPhase &T) {
     T.tail_cut = defer ? (h->params.tail_cut > 0 ? h->params.tail_cut : h->auto_cut) : 0; T.t_slot = slot_index; T.t_batch = h->batch_seq;
-    if (defer) { T.tq = h->fq_dev[fq_index]; T.tail_few = h->tail_few; T.tail_few_from = h->tail_few_from; }
+    if (defer) { T.tq = h->fq_dev[fq_index]; T.tail_few = h->tail_few; T.tail_few_from = kTailFewFrom; }
   };
   /* behind the launch: the batch's record (what mpc_tail_wait / _poll / _stream_wait resolve its id with) */
   int32_t *cb = h->d_counter + (h->counter_seq % kCounterRing) * kCounterInts;
@@ -2063,7 +1796,7 @@ static int launch_solve(MpcHandle *h, int64_t B, int64_t ld, int64_t ldo, const 
      * a launch of a few instances takes the whole wave anyway (its cross-lane reads are v_readlane instead of ds_bpermute) */
     const int64_t per = (int64_t)mpc::workspace_fields_per_instance(h->params.N, sizeof(R) == 4, h->params.initial_state_rows != 0) * (int64_t)sizeof(R);
     int lpi = h->params.N - 1 <= 16 ? 16 : (h->params.N - 1 <= 32 ? 32 : 64);
-    if (B <= h->wave_whole_max) lpi = 64;
+    if (B <= kWaveWholeMax) lpi = 64;
     if (const char *e = getenv("MPC_WAVE_LPI")) lpi = atoi(e) == 16 ? 16 : (atoi(e) == 32 ? 32 : 64);
     if (lpi < h->params.N - 1) lpi = 64;
     int32_t *it_w = iters ? iters : h->d_iters;
@@ -2098,41 +1831,26 @@ static int launch_solve(MpcHandle *h, int64_t B, int64_t ld, int64_t ldo, const 
     if (with_stats) stats_later(iters ? iters : h->d_iters);
     return MPC_OK;
   }
-  if (lds_path) {
-    --h->counter_seq;                              /* (this path uses no counters: the block stays clean for the next call) */
-    MPC_HIP_CHECK(hipEventRecord(h->ev0, s));
-    const int rc = launch_lds<R>(h, B, ld, ldo, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters ? iters : h->d_iters, s);
-    if (rc != MPC_OK) return rc;
-    MPC_HIP_CHECK(hipEventRecord(h->ev1, s));
-    h->timed = true;
-    { const int rt = tail_done(); if (rt != MPC_OK) return rt; }
-    if (with_stats) stats_later(iters ? iters : h->d_iters);
-    return MPC_OK;
-  }
   int32_t *it_out = iters ? iters : h->d_iters;
   if (soc) { const int rc = soc_alloc(h, &h->soc_ws, h->io_stride / 64); if (rc != MPC_OK) return rc; }
   MPC_HIP_CHECK(hipEventRecord(h->ev0, s));
   auto launch = [&](unsigned grid, void *wsp, const MpcPhase &tp) {
-    constexpr int kOcc2 = sizeof(R) == 4 ? 2 : 1;
     if constexpr (sizeof(R) == 8) {
       if (soc) {
         if (h->staging)
-          hipLaunchKernelGGL((mpc_solve_kernel<true, R, 1, R, R, true>), dim3(grid), dim3(kBlock), staging_lds_bytes<R>(), s, h->params, B, ld, ldo, state, coeffs,
+          hipLaunchKernelGGL((mpc_solve_kernel<true, R, R, R, true>), dim3(grid), dim3(kBlock), staging_lds_bytes<R>(), s, h->params, B, ld, ldo, state, coeffs,
                              yaw_lo, yaw_hi, weights, out, traj, status, it_out, (R *)wsp, h->ws_stride, tp);
         else
-          hipLaunchKernelGGL((mpc_solve_kernel<false, R, 1, R, R, true>), dim3(grid), dim3(kBlock), 0, s, h->params, B, ld, ldo, state, coeffs,
+          hipLaunchKernelGGL((mpc_solve_kernel<false, R, R, R, true>), dim3(grid), dim3(kBlock), 0, s, h->params, B, ld, ldo, state, coeffs,
                              yaw_lo, yaw_hi, weights, out, traj, status, it_out, (R *)wsp, h->ws_stride, tp);
         return;
       }
     }
-    if (h->staging && h->occ2)
-      hipLaunchKernelGGL((mpc_solve_kernel<true, R, kOcc2>), dim3(grid), dim3(kBlock), staging_lds_bytes<R>(), s, h->params, B, ld, ldo, state, coeffs,
-                         yaw_lo, yaw_hi, weights, out, traj, status, it_out, (R *)wsp, h->ws_stride, tp);
-    else if (h->staging)
-      hipLaunchKernelGGL((mpc_solve_kernel<true, R, 1>), dim3(grid), dim3(kBlock), staging_lds_bytes<R>(), s, h->params, B, ld, ldo, state, coeffs,
+    if (h->staging)
+      hipLaunchKernelGGL((mpc_solve_kernel<true, R>), dim3(grid), dim3(kBlock), staging_lds_bytes<R>(), s, h->params, B, ld, ldo, state, coeffs,
                          yaw_lo, yaw_hi, weights, out, traj, status, it_out, (R *)wsp, h->ws_stride, tp);
     else
-      hipLaunchKernelGGL((mpc_solve_kernel<false, R, 1>), dim3(grid), dim3(kBlock), 0, s, h->params, B, ld, ldo, state, coeffs,
+      hipLaunchKernelGGL((mpc_solve_kernel<false, R>), dim3(grid), dim3(kBlock), 0, s, h->params, B, ld, ldo, state, coeffs,
                          yaw_lo, yaw_hi, weights, out, traj, status, it_out, (R *)wsp, h->ws_stride, tp);
   };
   /* phase p takes from counter [2p], parks into list p & 1 and counts its parked instances in [2p + 1]; phase p > 0
@@ -2155,13 +1873,10 @@ static int launch_solve(MpcHandle *h, int64_t B, int64_t ld, int64_t ldo, const 
     T.src_ws = rd ? h->ws2 : h->ws;
     T.pass_cut = p < n_cuts ? h->cuts[p] : 0;
     T.resume = p > 0;
-    T.refill_min = h->refill_min; T.refill_wait = h->refill_wait; T.refill_floor = h->refill_floor;
-    T.compact_cooldown = h->compact_cooldown;
+    T.refill_min = kRefillMin; T.refill_wait = kRefillWait;
+    T.compact_cooldown = kCompactCooldown;
     T.compact_gap = (n_cuts == 0 && B >= h->compact_min_batch) ? h->compact_gap : 0;     /* (a phase that parks keeps iterates in its columns) */
     tail_fields(T);
-    const bool pooled = h->pool && n_cuts == 0;      /* a parked iterate stays in its column: phases keep their own tiles */
-    T.pool_bits = pooled ? h->pool->bits : nullptr; T.pool_base = pooled ? h->pool->base : nullptr;
-    T.pool_tiles = pooled ? h->pool->tiles : 0; T.pool_words = pooled ? h->pool->words : 0;
     T.soc_ws = h->soc_ws;
     launch((unsigned)waves, wr ? h->ws2 : h->ws, T);
     MPC_HIP_CHECK(hipGetLastError());

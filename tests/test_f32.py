@@ -263,28 +263,15 @@ def test_f32_gpu_weight_sweep_matches_oracle(pkg, host_twin, golden_dir, waypoin
 
 @pytest.mark.gpu
 def test_f32_pure_gpu_weight_sweep_matches_oracle(pkg, host_twin, golden_dir, waypoints):
-    """f32_finish = 0 on the device: the pure fp32 solver, both builds of the kernel (one and two waves per SIMD) bitwise equal,
-    all instances against the fp64 HIP path at the pure mode's tolerances."""
+    """f32_finish = 0 on the device: the pure fp32 solver, all instances against the fp64 HIP path at the pure mode's
+    tolerances."""
     import torch
     params = _f32_params(pkg, golden_dir, finish=0)
     p64 = params.copy(); p64.precision = pkg.PRECISION_F64
     B = 16384
     b = pkg.scenarios.lake_track_batch(B, params, waypoints, seed=53)
     w = pkg.scenarios.weight_sweep(B, params, seed=54, velocity_weights=(1.0, 100.0))
-    res = {}
-    old = os.environ.get("MPC_F32_OCC")
-    try:
-        for occ in ("2", "1"):
-            os.environ["MPC_F32_OCC"] = occ
-            res[occ] = _gpu_solve(pkg, params, b, w, torch.float32)
-    finally:
-        if old is None:
-            os.environ.pop("MPC_F32_OCC", None)
-        else:
-            os.environ["MPC_F32_OCC"] = old
-    for k in ("out", "traj", "status", "iters"):
-        assert np.array_equal(res["2"][k], res["1"][k]), k
-    r32 = res["2"]
+    r32 = _gpu_solve(pkg, params, b, w, torch.float32)
     r64 = _gpu_solve(pkg, p64, b, w, torch.float64)
     _check_f32(r32, r64, "HIP fp32 vs HIP fp64", B, pure=True)
     rt = twin_solve_f32(host_twin, params, {k: b[k][..., :2048] for k in ("state", "coeffs", "yaw_lo", "yaw_hi")}, weights=w[:, :2048], want_traj=False)

@@ -504,90 +504,49 @@ def test_staged_and_plain_kernels_are_bitwise_identical(pkg, golden_dir, waypoin
             os.environ["MPC_STAGING"] = old
 
 
-def test_lds_resident_kernel_is_bitwise_identical(pkg, golden_dir, waypoints, torch_dev):
-    """With MPC_LDS=1, launches of up to (instances per workgroup) x (number of CUs) instances keep the N-step variables of
-    every instance in LDS (mpc::LdsWorkspace, no workspace in HBM).  Same solver, same arithmetic: against the streaming
-    kernel (the default; MPC_LDS=0) on the same batch not a bit may change -- fp64 and fp32, all three LDS packings
-    (32 / 16 / 8 instances per workgroup: N = 10, 25, 40), ragged sizes down to B = 1."""
-    import torch
-    params = pkg.params_from_json(os.path.join(golden_dir, "config-fast.json"))
-    old = os.environ.get("MPC_LDS")
-    try:
-        for N, dt, B in ((10, 0.1, 1), (10, 0.1, 2000 + 13), (25, 0.05, 777), (40, 0.025, 130)):
-            for prec in (pkg.PRECISION_F64, pkg.PRECISION_F32):
-                q = params.copy(); q.N = N; q.dt = dt; q.precision = prec
-                q.f32_finish = 0; q.f64_f32_start = 0  # the LDS-resident kernel is a variant of the single-phase solve
-                b = pkg.scenarios.lake_track_batch(B, q, waypoints, seed=79)
-                tdt = torch.float32 if prec == pkg.PRECISION_F32 else torch.float64
-                t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(torch_dev, dtype=tdt)
-                res = {}
-                for lds in ("1", "0"):
-                    os.environ["MPC_LDS"] = lds
-                    with pkg.BatchedMPC(q, B, device=0) as mpc:
-                        r = mpc.solve_torch(t(b["state"]), t(b["coeffs"]), t(b["yaw_lo"]), t(b["yaw_hi"]), want_traj=True)
-                        torch.cuda.synchronize()
-                        res[lds] = {k: v.cpu().numpy() for k, v in r.items()}
-                        st = mpc.stats()
-                        assert st.batch == B and st.iter_sum == int(res[lds]["iters"].sum())
-                for key in ("out", "traj", "status", "iters"):
-                    assert np.array_equal(res["1"][key], res["0"][key]), (N, prec, key)
-                if prec == pkg.PRECISION_F64:
-                    assert (res["1"]["status"] == 0).all()
-    finally:
-        if old is None:
-            os.environ.pop("MPC_LDS", None)
-        else:
-            os.environ["MPC_LDS"] = old
-
-
 def test_multi_phase_solve_is_bitwise_identical(pkg, golden_dir, waypoints, torch_dev):
     """Parking unfinished instances after a number of passes and finishing them, re-packed, in further launches (up to
-    four cuts, MPC_PASS_CUT=a,b,c,d or MpcParams.pass_cut / pass_cut_next) must not change a single bit: the same
-    arithmetic on the same state, only in another lane."""
+    four cuts, MpcParams.pass_cut / pass_cut_next) must not change a single bit: the same arithmetic on the same state, only
+    in another lane."""
     params = pkg.params_from_json(os.path.join(golden_dir, "config-fast.json"))
-    old = os.environ.get("MPC_PASS_CUT")
-    try:
-        for N, dt, B in ((10, 0.1, 16384 + 11), (25, 0.05, 8192)):
-            q = params.copy(); q.N = N; q.dt = dt; q.f64_f32_start = 0     # cut schedules re-pack the single-phase solve
-            b = pkg.scenarios.lake_track_batch(B, q, waypoints, seed=78)
-            res = {}
-            for cut in ("0", "12", "5", "4,4,4,4", "3,9", "16,16,32"):
-                os.environ["MPC_PASS_CUT"] = cut
-                res[cut] = gpu_solve(pkg, q, b, torch_dev)
-            for cut in res:
-                for key in ("out", "traj", "status", "iters"):
-                    assert np.array_equal(res[cut][key], res["0"][key]), (N, cut, key)
-            assert (res["0"]["status"] == 0).mean() > 0.999 and res["0"]["iters"].max() > 14   # some instances did get parked
-        os.environ.pop("MPC_PASS_CUT", None)
-        # the heavy-tailed case the schedule is made for: per-instance weights, cuts given through MpcParams, both precisions
-        import torch
-        B = 16384
-        b = pkg.scenarios.lake_track_batch(B, params, waypoints, seed=79)
-        w = pkg.scenarios.weight_sweep(B, params, seed=80)
-        for prec, dt_ in ((pkg.PRECISION_F64, torch.float64), (pkg.PRECISION_F32, torch.float32)):
-            res = {}
-            for cuts in ((0, 0, 0, 0), (16, 16, 32, 0), (8, 8, 8, 8)):
-                q = params.copy(); q.precision = prec
-                q.f32_finish = 0                       # cut schedules re-pack the single-phase solve (the mixed mode has its own two phases)
-                q.pass_cut = cuts[0]
-                for k in range(3):
-                    q.pass_cut_next[k] = cuts[1 + k]
-                t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(torch_dev, dtype=dt_)
-                with pkg.BatchedMPC(q, B, device=0) as mpc:
-                    r = mpc.solve_torch(t(b["state"]), t(b["coeffs"]), t(b["yaw_lo"]), t(b["yaw_hi"]), weights=t(w), want_traj=True)
-                    torch.cuda.synchronize()
-                    st = mpc.stats()
-                    res[cuts] = {k: v.cpu().numpy() for k, v in r.items()}
-                    assert st.batch == B and st.n_success == int((res[cuts]["status"] == 0).sum())
-            for cuts in res:
-                for key in ("out", "traj", "status", "iters"):
-                    assert np.array_equal(res[cuts][key], res[(0, 0, 0, 0)][key]), (prec, cuts, key)
-            assert res[(0, 0, 0, 0)]["iters"].max() > 60     # instances that go through every phase
-    finally:
-        if old is None:
-            os.environ.pop("MPC_PASS_CUT", None)
-        else:
-            os.environ["MPC_PASS_CUT"] = old
+    for N, dt, B in ((10, 0.1, 16384 + 11), (25, 0.05, 8192)):
+        q = params.copy(); q.N = N; q.dt = dt; q.f64_f32_start = 0     # cut schedules re-pack the single-phase solve
+        b = pkg.scenarios.lake_track_batch(B, q, waypoints, seed=78)
+        res = {}
+        for cut in ((0,), (12,), (5,), (4, 4, 4, 4), (3, 9), (16, 16, 32)):
+            qc = q.copy()
+            qc.pass_cut = cut[0]
+            for k in range(3):
+                qc.pass_cut_next[k] = cut[1 + k] if 1 + k < len(cut) else 0
+            res[cut] = gpu_solve(pkg, qc, b, torch_dev)
+        for cut in res:
+            for key in ("out", "traj", "status", "iters"):
+                assert np.array_equal(res[cut][key], res[(0,)][key]), (N, cut, key)
+        assert (res[(0,)]["status"] == 0).mean() > 0.999 and res[(0,)]["iters"].max() > 14   # some instances did get parked
+    # the heavy-tailed case the schedule is made for: per-instance weights, cuts given through MpcParams, both precisions
+    import torch
+    B = 16384
+    b = pkg.scenarios.lake_track_batch(B, params, waypoints, seed=79)
+    w = pkg.scenarios.weight_sweep(B, params, seed=80)
+    for prec, dt_ in ((pkg.PRECISION_F64, torch.float64), (pkg.PRECISION_F32, torch.float32)):
+        res = {}
+        for cuts in ((0, 0, 0, 0), (16, 16, 32, 0), (8, 8, 8, 8)):
+            q = params.copy(); q.precision = prec
+            q.f32_finish = 0                       # cut schedules re-pack the single-phase solve (the mixed mode has its own two phases)
+            q.pass_cut = cuts[0]
+            for k in range(3):
+                q.pass_cut_next[k] = cuts[1 + k]
+            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(torch_dev, dtype=dt_)
+            with pkg.BatchedMPC(q, B, device=0) as mpc:
+                r = mpc.solve_torch(t(b["state"]), t(b["coeffs"]), t(b["yaw_lo"]), t(b["yaw_hi"]), weights=t(w), want_traj=True)
+                torch.cuda.synchronize()
+                st = mpc.stats()
+                res[cuts] = {k: v.cpu().numpy() for k, v in r.items()}
+                assert st.batch == B and st.n_success == int((res[cuts]["status"] == 0).sum())
+        for cuts in res:
+            for key in ("out", "traj", "status", "iters"):
+                assert np.array_equal(res[cuts][key], res[(0, 0, 0, 0)][key]), (prec, cuts, key)
+        assert res[(0, 0, 0, 0)]["iters"].max() > 60     # instances that go through every phase
 
 
 def test_lane_compaction_is_bitwise_identical(pkg, golden_dir, waypoints, torch_dev):
@@ -693,54 +652,6 @@ def test_f32_phase_refill_is_bitwise_identical(pkg, golden_dir, waypoints, torch
         for r in seen[1:]:
             for key in ("out", "traj", "status", "iters"):
                 assert np.array_equal(r[key], seen[0][key]), key
-
-
-def test_tile_pool_is_bitwise_identical_and_used(pkg, golden_dir, waypoints, torch_dev):
-    """MPC_TILE_POOL=1: waves take their workspace tile from a per-XCD pool shared by all handles instead of their
-    handle's own workspace.  Three handles on three streams, several rounds without a pause in between (so tiles change
-    hands between launches that are running): every launch must give the plain path's results bit for bit, every tile must
-    be back in the pool afterwards, and every wave must have got one."""
-    import torch
-    import ctypes as C
-    params = pkg.params_from_json(os.path.join(golden_dir, "config-fast.json"))
-    old = os.environ.get("MPC_TILE_POOL")
-    try:
-        for prec, dt_, B, sweep in ((pkg.PRECISION_F64, torch.float64, 32768 + 70, False), (pkg.PRECISION_F32, torch.float32, 16384, True)):
-            q = params.copy(); q.precision = prec
-            q.f32_finish = 0                           # the pool serves the single-phase launches
-            b = pkg.scenarios.lake_track_batch(B, q, waypoints, seed=7)
-            w = pkg.scenarios.weight_sweep(B, q, seed=8) if sweep else None
-            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(torch_dev, dtype=dt_)
-            ins = (t(b["state"]), t(b["coeffs"]), t(b["yaw_lo"]), t(b["yaw_hi"]))
-            wt = t(w) if w is not None else None
-            os.environ.pop("MPC_TILE_POOL", None)
-            with pkg.BatchedMPC(q, B, device=0) as mpc:
-                ref = {k: v.cpu().numpy() for k, v in mpc.solve_torch(*ins, weights=wt, want_traj=True).items()}
-            os.environ["MPC_TILE_POOL"] = "1"
-            hs = [pkg.BatchedMPC(q, B, device=0) for _ in range(3)]
-            streams = [torch.cuda.Stream(device=torch_dev) for _ in hs]
-            rounds, outs = 4, []
-            for _ in range(rounds):
-                for h, s_ in zip(hs, streams):
-                    with torch.cuda.stream(s_):
-                        outs.append(h.solve_torch(*ins, weights=wt, want_traj=True))
-            torch.cuda.synchronize()
-            for o in outs:
-                for key in ("out", "traj", "status", "iters"):
-                    assert np.array_equal(o[key].cpu().numpy(), ref[key]), (prec, key)
-            st = np.zeros(32, dtype=np.int64)
-            assert pkg.library().mpc_debug_tile_pool(hs[0]._h, C.c_void_p(st.ctypes.data)) == 0
-            st = st.reshape(8, 4)
-            assert (st[:, 0] == st[:, 1]).all(), st                       # every tile is back
-            assert st[:, 2].sum() == rounds * len(hs) * ((B + 63) // 64), st   # every wave got one (no wave fell back)
-            assert (st[:, 3] <= st[:, 1]).all() and (st[:, 3] > 0).all(), st
-            for h in hs:
-                h.close()
-    finally:
-        if old is None:
-            os.environ.pop("MPC_TILE_POOL", None)
-        else:
-            os.environ["MPC_TILE_POOL"] = old
 
 
 def test_garbage_inputs_get_a_status_and_stay_contained(pkg, host_twin, golden_dir, waypoints, torch_dev):

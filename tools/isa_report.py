@@ -10,7 +10,7 @@ subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-
                        "-I" + ROOT + "/carnd-mpc-project_amd/csrc", "--cuda-device-only", "-S", "-o", s_path,
                        ROOT + "/carnd-mpc-project_amd/csrc/mpc_solver.hip"] + os.environ.get("EXTRA", "").split(), stderr=subprocess.DEVNULL)
 txt = open(s_path).read()
-KERNEL = os.environ.get("KERNEL", "_ZN12_GLOBAL__N_116mpc_solve_kernelILb1EdLi1E")   # <STAGING=true, double, OCC=1>; fp32: ...ILb1EfLi2E
+KERNEL = os.environ.get("KERNEL", "_ZN12_GLOBAL__N_116mpc_solve_kernelILb1EdddLb0E")   # <STAGING=true, double, double, double, SOC=false>; fp32: ...ILb1EfffLb0E
 m = re.search(r"^" + KERNEL + r".*?s_endpgm", txt, re.S | re.M)
 k = m.group(0).split("\n")
 meta = re.findall(r"; (NumVgprs|NumAgprs|TotalNumVgprs|ScratchSize|codeLenInByte|Occupancy)[:=]? *=? *(\d+)", txt[m.end():m.end() + 12000])

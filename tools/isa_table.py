@@ -9,12 +9,12 @@ subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-
                        ROOT + "/carnd-mpc-project_amd/csrc/mpc_solver.hip"], stderr=subprocess.DEVNULL)
 txt = open(sp).read()
 T = {"d": "double", "f": "float"}
-print("| kernel <staging, solver reals, waves/SIMD, ABI reals[, source reals]> | VGPR + AGPR | scratch | waves/SIMD | code |")
+print("| kernel <staging, solver reals, ABI reals[, source reals], SOC> | VGPR + AGPR | scratch | waves/SIMD | code |")
 print("|---|---|---|---|---|")
-for m in re.finditer(r"^(_ZN12_GLOBAL__N_1\d+mpc_(solve|tail_slice)_kernelILb([01])E([df])Li(\d)E([df])([df])?EE\w*):", txt, re.M):
-    K, kind, stg, r, occ, rio, rsrc = m.groups()
+for m in re.finditer(r"^(_ZN12_GLOBAL__N_1\d+mpc_(solve|tail_slice)_kernelILb([01])E([df])([df])([df])?Lb([01])EEE\w*):", txt, re.M):
+    K, kind, stg, r, rio, rsrc, soc = m.groups()
     mm = re.search(r"^" + re.escape(K) + r":.*?s_endpgm", txt, re.S | re.M)
     meta = dict(re.findall(r"; (NumVgprs|NumAgprs|ScratchSize|codeLenInByte|Occupancy)[:=]? *=? *(\d+)", txt[mm.end():mm.end() + 12000])[:5])
-    name = "mpc_%s_kernel<%s, %s, %s, %s%s>" % (kind, "true" if stg == "1" else "false", T[r], occ, T[rio], ", " + T[rsrc] if rsrc else "")
+    name = "mpc_%s_kernel<%s, %s, %s%s, %s>" % (kind, "true" if stg == "1" else "false", T[r], T[rio], ", " + T[rsrc] if rsrc else "", "true" if soc == "1" else "false")
     print("| `%s` | %s + %s = %d | %s B | %s | %.1f KB |" % (name, meta["NumVgprs"], meta["NumAgprs"], int(meta["NumVgprs"]) + int(meta["NumAgprs"]),
                                                           meta["ScratchSize"], meta["Occupancy"], int(meta["codeLenInByte"]) / 1024))

@@ -18,8 +18,8 @@ for config, over, B in (("config-fast.json", {}, 256), ("config-stable.json", di
     ins = (t(b["state"]), t(b["coeffs"]), t(b["yaw_lo"]), t(b["yaw_hi"]))
     res = {}
     for mode in ("lane", "wave"):
-        if mode == "wave": os.environ["MPC_WAVE_MAX_BATCH"] = "1024"; os.environ["MPC_WAVE_WHOLE_MAX"] = "0"      # (lanes per instance by the horizon: 16 / 32)
-        else: os.environ["MPC_WAVE_MAX_BATCH"] = "0"
+        if mode == "wave": os.environ["MPC_WAVE_MAX_BATCH"] = "1024"; os.environ["MPC_WAVE_LPI"] = "16" if p.N - 1 <= 16 else "32"   # (lanes per instance by the horizon)
+        else: os.environ["MPC_WAVE_MAX_BATCH"] = "0"; os.environ.pop("MPC_WAVE_LPI", None)
         with pkg.BatchedMPC(p, B, device=0) as mpc:
             r = mpc.solve_torch(*ins, want_traj=True); torch.cuda.synchronize()
             res[mode] = {k: v.cpu().numpy() for k, v in r.items()}
