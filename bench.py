@@ -13,6 +13,11 @@ trajectories requested, drawn as SURVEY.md section 8d says (rejecting only a com
 batch's per-instance results are gathered to rank 0 (RCCL).  Rank 0 prints ONE JSON line of at most 2 KB on stdout; everything
 measured (every leg in full) goes to bench_full.json beside this file and to stderr.
 
+A plain run measures the headline alone: set-up, warm-up, the K timed batches, --dump-outputs, the line.  `--full` adds
+everything else, each in runs of its own after the timed batches: `strict_value`, the launch alone on the device
+(roofline.kernel_ms_alone), host_path, the CPU baselines with the parity against the oracle, and the extra legs (other
+populations and BASELINE.json configs, one child process each); --no-legs / --no-cpu-baseline / --no-host-leg trim it.
+
 What is timed.  Steps are pipelined the way a serving loop runs them: `--inflight` handles on separate streams, stragglers
 deferred to the handles' tail slices (MpcParams.tail_cut), results gathered once a batch is final.  A batch of the survey
 population is final 50-150 ms after its launch (its slowest instance runs to the iteration cap), a hundred batch periods.
@@ -57,6 +62,8 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure everything beyond the headline, each in runs "
+                    "of its own: strict_value, the launch alone, host_path, the CPU baselines and the parity against the oracle, the extra legs")
     ap.add_argument("--batch", type=int, default=65536, help="instances per GPU (weak scaling)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
     ap.add_argument("--global-batch", type=int, default=0, help="--scaling strong: total instances, split evenly over the GPUs")
@@ -99,11 +106,11 @@ def parse_args(argv=None):
     ap.add_argument("--outstanding", type=int, default=0, help="buffer sets = batches that may be outstanding (launched, or waiting for their stragglers); "
                     "0 = min(256, batches in flight x tail ring)")
     ap.add_argument("--leg-tail-cut", type=int, default=None, help="override the tail cut of a leg that defers (measurement aid)")
-    ap.add_argument("--no-legs", action="store_true", help="skip the extra legs of the default run (the unfiltered population of the "
+    ap.add_argument("--no-legs", action="store_true", help="skip the extra legs of --full (the unfiltered population of the "
                     "headline workload and the other BASELINE.json configs)")
     ap.add_argument("--leg-inflight", type=int, default=0, help="batches in flight of the extra legs (0: each leg's own, or the library's advice)")
-    ap.add_argument("--leg", default="", help="run ONE extra leg of the default run alone in this process and print its JSON line (what the default "
-                    "run starts as child processes): " + ", ".join(LEGS))
+    ap.add_argument("--leg", default="", help="run ONE extra leg of --full alone in this process and print its JSON line (what --full "
+                    "starts as child processes): " + ", ".join(LEGS))
     ap.add_argument("--leg-steps", type=int, default=20, help="timed steps of an extra leg that does not set its own")
     ap.add_argument("--no-leg-tails", dest="leg_tails", action="store_false", help="run the extra legs without deferred tails")
     ap.add_argument("--population", choices=("filtered", "survey", "unfiltered"), default="survey",
@@ -456,10 +463,10 @@ class Pipeline:
             h.close()
 
 
-def timed_run(pipe, steps, warmup, sync_all, lockstep=False):
+def timed_run(pipe, steps, warmup, sync_all, lockstep=False, strict=True):
     """-> dict: `steady_s` = host time between the moment batch number P became final and the moment batch P + steps did (P >=
     warmup batches final before the clock starts, batches issued behind the timed ones all along: the primed pipeline);
-    `strict_s` = the same number of batches from an empty device to an empty device, nothing issued behind them.
+    `strict_s` (strict=True) = the same number of batches from an empty device to an empty device, nothing issued behind them.
     lockstep (several ranks: every rank must issue the same number of batches, their gathers are collectives): P and the number
     of batches issued behind the timed ones are fixed in advance -- as many as may be outstanding -- instead of following the
     finals."""
@@ -495,6 +502,9 @@ def timed_run(pipe, steps, warmup, sync_all, lockstep=False):
         pipe.run_until(lambda p: p.n_issued >= total)
     pipe.drain()
     sync_all()
+    steady["kernel_ms"] = kms
+    if not strict:
+        return steady
     t0 = time.perf_counter()
     first = pipe.n_issued
     pipe.run_until(lambda p: p.n_issued >= first + steps)
@@ -524,7 +534,7 @@ def summarize(pkg, np, pipe, B, steps, elapsed):
     return r, status, iters, outs
 
 
-# The extra legs of the default run: name -> (description, keyword arguments of run_leg).  tail_cut -1 = MPC_TAIL_AUTO.
+# The extra legs of --full: name -> (description, keyword arguments of run_leg).  tail_cut -1 = MPC_TAIL_AUTO.
 LEGS = {
     "filtered": ("the headline workload (configs[2]) drawn with the generator's own rejection sampling (instances the reference's road model does "
                  "not hold for are redrawn: yaw on its bound, waypoint windows that double back, fits beyond Config::maxFitError) -- rounds 1-3's headline; "
@@ -604,7 +614,7 @@ def run_leg(pkg, torch, np, args, dev, local_rank, golden, wp, sync_all, name, c
 
 
 def extra_legs(args):
-    """The other populations the driver-timed line reports: the headline workload drawn with SURVEY.md
+    """The other populations a --full line reports: the headline workload drawn with SURVEY.md
     8d's own rejection only, and BASELINE.json configs[1], [3] (one GPU's share) and [4] (one GPU's share).  Each leg runs in a
     child process of its own (`bench.py --leg NAME`): the mapping of a process's streams onto the hardware queues depends on
     every stream it has created before, and legs run one after the other in one process measured up to 30 % below the same
@@ -764,9 +774,9 @@ def main():
     # HIP events on the stream the kernel is launched on: torch's current stream, whose handle is what
     # solve_torch passes to mpc_solve_batch_device (a NULL handle is HIP's null stream = torch's default)
     # (a handle's first call allocates lazily -- second workspace, tail queues: at least one untimed step per handle)
-    tr = timed_run(pipe, args.steps, max(args.warmup, pipe.nfl), sync_all, lockstep=dist is not None)
+    tr = timed_run(pipe, args.steps, max(args.warmup, pipe.nfl), sync_all, lockstep=dist is not None, strict=args.full)
     dumped = dump_outputs(pipe, args.dump_outputs) if args.dump_outputs and rank == 0 else None
-    elapsed, strict = tr["steady_s"], tr["strict_s"]
+    elapsed, strict = tr["steady_s"], tr.get("strict_s", 0.0)
     if dist is not None:
         tt = torch.tensor([elapsed, strict], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -776,9 +786,9 @@ def main():
     summary, status, iters_np, outs = summarize(pkg, np, pipe, B, args.steps, elapsed)
     out_np = outs["out"].cpu().numpy()
     last = pipe.last_slot()
-    # the same launch alone on the device (nothing else in flight), for reference
+    # --full: the same launch alone on the device (nothing else in flight), for reference
     iso = []
-    if stub is None:
+    if stub is None and args.full:
         for _ in range(3):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             with torch.cuda.stream(pipe.streams[0]):
@@ -826,7 +836,7 @@ def main():
         "vs_baseline": None, "dtype": dtype, "data": "synthetic",
         # the same number of batches from an empty device to an empty device, nothing issued behind them: carries the whole
         # latency of the last batch's slowest instance (a function of --steps)
-        "strict_value": total_solves / strict, "strict_ms_per_step": 1e3 * strict / args.steps,
+        "strict_value": total_solves / strict if strict else None, "strict_ms_per_step": 1e3 * strict / args.steps if strict else None,
         "timing": dict({k: tr[k] for k in ("first_timed_batch", "batches_in_the_window", "batches_issued_before_the_clock", "batches_outstanding_at_the_end")},
                        definition="primed pipeline: the clock runs from the moment batch number first_timed_batch became final (in issue order) to the "
                                   "moment `steps` more had, with later batches issued behind them all along; strict_value: empty device to empty device"),
@@ -911,7 +921,8 @@ def main():
                        "valu_tflops": flops_per_step / step_s / 1e12,
                        "valu_frac": valu_frac, "valu_peak_tflops": VALU_PEAK_TFLOPS[dtype]}
 
-    if world == 1 and stub is None and not args.no_host_leg:
+    extras = args.full and world == 1 and stub is None            # --full's measurements beyond the headline, one GPU
+    if extras and not args.no_host_leg:
         # PCIe-inclusive: the same batch from pageable host arrays through mpc_solve_batch_host (fp64 entry point)
         if not f32:
             hs = []
@@ -935,16 +946,16 @@ def main():
                                 "b1_note": "one MPC::solve() per telemetry message is what the reference does (mpc_main.cpp:167); includes the ctypes call; launches of at most 64 instances run one instance per wavefront (mpc_solve_wave_kernel)"}
     # IPOPT's own stopping rule (polish = 0) on the same batch, once: what the device returns then (compared with the oracle below)
     out_p0 = None
-    if world == 1 and stub is None and not args.no_cpu_baseline and not f32:
+    if extras and not args.no_cpu_baseline and not f32:
         p0 = params.copy(); p0.polish = 0; p0.tail_cut = 0
         with pkg.BatchedMPC(p0, B, device=local_rank) as m0:
             r0 = m0.solve_torch(*tensors, weights=d_w, want_traj=False)
             torch.cuda.synchronize(dev)
             out_p0 = (r0["out"].cpu().numpy(), r0["status"].cpu().numpy())
     pipe.close()
-    if world == 1 and stub is None and not args.no_legs:
+    if extras and not args.no_legs:
         res["legs"] = extra_legs(args)
-    if world == 1 and stub is None and not args.no_cpu_baseline:
+    if extras and not args.no_cpu_baseline:
         one, allc, parity = cpu_baseline_legs(args, batch, w_np, over, status, out_np, out_p0, args.cpu_seconds)
         res["cpu_baseline"] = one
         res["cpu_baseline_all_cores"] = allc
@@ -957,8 +968,8 @@ def main():
 
 def emit(res, json_fd, args):
     """Everything goes to bench_full.json (beside this file; `--full-json PATH` elsewhere) and to stderr; stdout gets ONE line of at
-    most 2 KB: the contract's keys, the roofline and the baselines in short, and every leg as [solves/s, success, maxiter,
-    linesearch, acceptable]."""
+    most 2 KB: the contract's keys, the roofline and, with --full, the baselines in short and every leg as [solves/s, success,
+    maxiter, linesearch, acceptable]."""
     full = json.dumps(res)
     path = args.full_json or os.path.join(ROOT, "bench_full.json")
     try:

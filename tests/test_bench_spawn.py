@@ -75,6 +75,24 @@ def test_bench_dump_outputs_repeatable_and_steps_exact(tmp_path):
     assert (dumps[0]["status.npy"] == 0).all() and (dumps[0]["iters.npy"] > 0).all()
 
 
+def test_bench_full_is_opt_in(tmp_path):
+    """A plain run times the headline and nothing else; --full adds the measurements that take runs of their own (with the
+    stub: the same batches timed from an empty device, strict_value) and dumps what the plain run dumps."""
+    import numpy as np
+    lines, dumps = [], []
+    for k, extra in enumerate(([], ["--full"])):
+        d = tmp_path / ("dump%d" % k)
+        r, _ = _run(["--gpus", "1", "--steps", "4", "--warmup", "1", "--batch", "64", "--stub", "host_twin", "--dump-outputs", str(d),
+                     "--full-json", str(tmp_path / ("full%d.json" % k))] + extra)
+        lines.append(r)
+        dumps.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+    assert lines[0]["strict_value"] is None and lines[1]["strict_value"] > 0
+    assert lines[0]["steps"] == lines[1]["steps"] == 4 and lines[0]["value"] > 0
+    assert sorted(dumps[0]) == sorted(dumps[1]) == ["iters.npy", "out.npy", "status.npy", "traj.npy"]
+    for f, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][f], equal_nan=True), f
+
+
 def test_bench_dump_outputs_sample_under_the_cap(tmp_path):
     """Beyond the size cap the same seeded instances are taken from every array, and their indices are written too."""
     import numpy as np

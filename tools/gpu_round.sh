@@ -16,7 +16,7 @@ timeout -k 10 900 python -m pytest tests -m gpu -q > $OUT/${TAG}_pytest_gpu.log 
 tail -3 $OUT/${TAG}_pytest_gpu.log
 fi
 echo "== bench" | tee -a $OUT/${TAG}_progress.log
-timeout -k 10 600 python bench.py $BENCH_ARGS > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench exit=$?" | tee -a $OUT/${TAG}_progress.log
+timeout -k 10 600 python bench.py --full $BENCH_ARGS > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench exit=$?" | tee -a $OUT/${TAG}_progress.log
 cat $OUT/${TAG}_bench.json
 echo "== rocprofv3 kernel trace" | tee -a $OUT/${TAG}_progress.log
 cd /tmp && export TMPDIR=/tmp
