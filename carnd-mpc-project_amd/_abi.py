@@ -75,7 +75,7 @@ EXPORTS = ["mpc_params_default", "mpc_params_load_json", "mpc_create", "mpc_set_
            "mpc_telemetry_batch_device", "mpc_rollout_batch_device", "mpc_debug_math_ext",
            "mpc_solve_batch_device_f32", "mpc_wire_parse", "mpc_wire_format_steer", "mpc_wire_format_manual",
            "mpc_wire_telemetry_batch_host", "mpc_telemetry_batch_host", "mpc_handle_device",
-           "mpc_run_batch_host", "mpc_last_batch_id", "mpc_tail_poll", "mpc_tail_wait", "mpc_tail_stream_wait", "mpc_tail_flush", "mpc_tail_pending", "mpc_tail_info", "mpc_solve_batch_host_f32", "mpc_inflight_advice"]
+           "mpc_run_batch_host", "mpc_last_batch_id", "mpc_tail_poll", "mpc_tail_wait", "mpc_tail_stream_wait", "mpc_tail_flush", "mpc_tail_pending", "mpc_tail_info", "mpc_solve_batch_host_f32", "mpc_inflight_advice", "mpc_take_order_info"]
 
 _lib = None
 
@@ -143,6 +143,7 @@ def library():
     L.mpc_tail_flush.argtypes = [C.c_void_p]
     L.mpc_tail_pending.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.mpc_tail_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    L.mpc_take_order_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.mpc_wire_parse.argtypes = [C.c_char_p, C.c_int64, C.POINTER(MpcWireTelemetry)]
     L.mpc_wire_format_steer.argtypes = [C.c_double, C.c_double, C.c_char_p, C.c_int64]
     L.mpc_wire_format_steer.restype = C.c_int64

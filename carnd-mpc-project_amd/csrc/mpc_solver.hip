@@ -19,6 +19,7 @@
 
 #include "mpc_core.h"
 #include "mpc_run_core.h"
+#include "mpc_take_key.h"
 
 namespace {
 
@@ -56,7 +57,9 @@ struct DeviceGuard {
 constexpr int kBlock = 64; /* one wavefront per workgroup: lanes never synchronise */
 constexpr int64_t kLdsPerCu = 160 * 1024;
 constexpr int kMaxCuts = 4;         /* cuts of the multi-phase solve: up to 5 launches per batch */
-constexpr int kCounterInts = 16;    /* two counters per phase */
+constexpr int kPhaseCounterInts = 16;   /* two counters per phase */
+constexpr int kCounterInts = kPhaseCounterInts + mpc::kTakeBins;   /* ... and behind them the take-order key's instances per bin (a block is zeroed by one wave) */
+static_assert(kCounterInts <= 64, "a counter block is zeroed by the lanes of one wave");
 constexpr int kCounterRing = 32;    /* counter blocks: solve call n uses block n % 32 and zeroes block (n + 16) % 32 for its next user */
 constexpr int kParkRows = 47;       /* Solver::PARK_N */
 constexpr int kFinPromote = -2, kFinScratch = -3;   /* a lane that waits to hand its instance to the fp64 phase (promoted / to be solved from scratch) */
@@ -176,7 +179,51 @@ struct MpcPhase {
   /* SOC builds (MpcParams.max_soc > 0): the SOC records, [wave of this launch][N-1][SOC_SZ / G][64][G] reals.  A correction lives
    * within one line search of one lane, so they go with the launch's wave number, not with the workspace tile. */
   void *soc_ws;
+  /* Take order (first phase only; nullptr = position p of the counter is instance p).  mpc_take_key_kernel has sorted the launch's
+   * instances into mpc::kTakeBins bins of predicted work: ord_cnt[b] instances in bin b, their indices in ord_list[b * ord_ld ..].
+   * Position p of the counter is then the p-th instance of the bins laid end to end, so that the 64 instances of a wave need about
+   * the same number of passes and the wave lives for about their mean instead of the worst of 64 unrelated draws. */
+  const int32_t *ord_cnt, *ord_list;
+  int64_t ord_ld;
 };
+
+/* The take-order key of every instance of a launch (csrc/mpc_take_key.h) and the bins' lists: one thread per instance, a wave
+ * appends its instances to the bins' lists.  No LDS and few registers: its waves fit beside the resident waves of a bulk
+ * launch.  cnt[] is zero on entry (it lives in the launch's counter block). */
+template <class R>
+__global__ __launch_bounds__(kBlock) void mpc_take_key_kernel(const float horizon_s, const int64_t B, const int64_t ld, const R *__restrict__ state,
+                                                           const R *__restrict__ coeffs, const R *__restrict__ yaw_lo, const R *__restrict__ yaw_hi,
+                                                           const int reverse, int32_t *__restrict__ cnt, int32_t *__restrict__ list, const int64_t ld_list) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  int b = -1;
+  if (i < B) {
+    R st[6], cf[MPC_NCOEF];
+    float f[mpc::kTakeFeats];
+#pragma unroll
+    for (int q = 0; q < 6; q++) st[q] = state[q * ld + i];
+#pragma unroll
+    for (int q = 0; q < MPC_NCOEF; q++) cf[q] = coeffs[q * ld + i];
+    mpc::take_key_features<R>(horizon_s, st, cf, yaw_lo[i], yaw_hi[i], f);
+    b = mpc::take_key_bin(f);
+    if (reverse) b = mpc::kTakeBins - 1 - b;
+  }
+  /* A wave appends its instances with ONE round of atomics: lane k adds the wave's number of instances of bin k and every lane
+   * reads the base of its own bin from it.  (One atomic per bin in turn, each waiting for the one before, made this kernel last
+   * 200 us on a device that a bulk launch keeps full -- as long as the ordered launch saves.) */
+  const unsigned lane = threadIdx.x & 63u;
+  static_assert(mpc::kTakeBins <= 64, "a lane per bin");
+  int n_mine = 0, rank = 0;
+#pragma unroll
+  for (int k = 0; k < mpc::kTakeBins; ++k) {
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(b == k);
+    if (lane == (unsigned)k) n_mine = __builtin_popcountll(m);
+    if (b == k) rank = __builtin_popcountll(m & ((1ull << lane) - 1ull));
+  }
+  int base = 0;
+  if (n_mine > 0) base = atomicAdd(&cnt[lane], n_mine);
+  const int64_t at = (int64_t)__shfl(base, b < 0 ? 0 : b, 64) + rank;
+  if (b >= 0 && at < ld_list) list[(int64_t)b * ld_list + at] = (int32_t)i;
+}
 
 /* Copies between queue entries and a lane's workspace column.  Loads first, then stores, a stage (or 16 rows) at a time: written as
  * `dst[..] = src[..]` in one loop the compiler must assume that a store aliases the next load and waits for every load before the
@@ -307,6 +354,19 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
           exhausted = !more;
           if (more) {
             i = T.resume ? (int64_t)T.in_inst[pos] : pos;
+            if (__builtin_expect(T.ord_list != nullptr, 0)) {      /* (placed out of line: the code around the take stays where it was) */
+              /* the bins laid end to end: which bin holds position pos (the counts are the same for every lane: scalar loads) */
+              int64_t off = pos;
+              int b = 0;
+#pragma unroll 1
+              for (; b < mpc::kTakeBins - 1; ++b) {
+                const int64_t c = (int64_t)T.ord_cnt[b];
+                if (off < c) break;
+                off -= c;
+              }
+              i = (int64_t)T.ord_list[(int64_t)b * T.ord_ld + (off < T.ord_ld ? off : 0)];
+              if ((uint64_t)i >= (uint64_t)B) i = pos;     /* (cannot happen: the lists hold 0 .. B-1 once each; results never go out of bounds) */
+            }
             R st[6], cf[MPC_NCOEF], w[MPC_NW];
 #pragma unroll
             for (int q = 0; q < 6; q++) st[q] = (R)state[q * ld + i];
@@ -927,6 +987,13 @@ struct MpcHandle {
   int compact_gap = 0;        /* MpcParams.lane_compact, or MPC_LANE_COMPACT in the environment (measurement aid): see MpcPhase.compact_gap */
   bool compact_env = false;
   int64_t compact_min_batch = 8192;   /* smaller launches are latency-bound: the moves cost more than the lines they save */
+  /* take order (see MpcPhase.ord_list): 1 = hardest bin first, 2 = easiest bin first, 0 = off; MPC_TAKE_ORDER in the environment
+   * (measurement aid).  Applied to single-phase fp64 launches of the solve entry points from take_order_min_batch instances,
+   * N < 15, no per-instance weights, no SOC: the cases tools/take_order_model.py and the benchmark have measured. */
+  int take_order = 1;
+  int64_t take_order_min_batch = 8192;
+  int32_t *d_take_list = nullptr;     /* [mpc::kTakeBins][io_stride] (allocated on first use) */
+  int64_t n_take_ordered = 0;         /* launches taken in key order so far (mpc_take_order_info) */
   /* multi-phase solve: second workspace, two parked-instance lists and two sets of scalars (allocated on first use) */
   int n_cuts = 0;             /* MpcParams.pass_cut + pass_cut_next[] (none = single launch) */
   int cuts[kMaxCuts] = {0, 0, 0, 0};
@@ -1125,6 +1192,7 @@ extern "C" int mpc_create(const MpcParams *p, int device, int64_t max_batch, Mpc
   set_cuts(h, p);
   h->compact_gap = p->lane_compact >= 0 ? p->lane_compact : (p->N >= 15 ? 1 : 2);
   if (const char *e9 = getenv("MPC_LANE_COMPACT")) { h->compact_gap = atoi(e9); h->compact_env = true; if (h->compact_gap < 0) h->compact_gap = 0; }
+  if (const char *e10 = getenv("MPC_TAKE_ORDER")) { h->take_order = atoi(e10); if (h->take_order < 0 || h->take_order > 2) h->take_order = 0; }
   h->promote_buffer = p->f32_phase_refill != 0;
   *out = h;
   return MPC_OK;
@@ -1179,6 +1247,7 @@ extern "C" void mpc_destroy(MpcHandle *h) {
   if (h->soc_ws) (void)hipFree(h->soc_ws);
   if (h->d_park) (void)hipFree(h->d_park);
   if (h->d_list) (void)hipFree(h->d_list);
+  if (h->d_take_list) (void)hipFree(h->d_take_list);
   if (h->d_piter) (void)hipFree(h->d_piter);
   if (h->d_tel) (void)hipFree(h->d_tel);
   if (h->tail_ready) (void)tail_drain(h);         /* stragglers still queued are finished: their batches' arrays may be read afterwards */
@@ -1581,6 +1650,12 @@ extern "C" int mpc_tail_stream_wait(MpcHandle *h, int64_t batch_id, void *stream
 /* counters of the handle's tail machinery: out[0] batches deferred so far, [1] tail slices so far, [2] ring, [3] capacity of a
  * batch's fresh queue, [4] waves per slice (upper bound), [5] 1 if the tail stream has high priority, [6] tail streams (1),
  * [7] batches that ran without deferral because the survivors' list was filling up, [8] passes per slice, [9] survivors now */
+extern "C" int mpc_take_order_info(const MpcHandle *h, int64_t *out) {
+  if (!h || !out) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
+  out[0] = h->n_take_ordered; out[1] = h->take_order;
+  return MPC_OK;
+}
+
 extern "C" int mpc_tail_info(const MpcHandle *h, int64_t *out) {
   if (!h || !out) return MPC_ERR_INVALID;
   out[0] = h->n_deferred; out[1] = h->n_slice; out[2] = h->tail_ring; out[3] = h->tail_cap; out[4] = h->tail_waves;
@@ -1695,7 +1770,8 @@ static int launch_mixed(MpcHandle *h, int64_t B, int64_t ld, int64_t ldo, const 
 template <class R>
 static int launch_solve(MpcHandle *h, int64_t B, int64_t ld, int64_t ldo, const R *state, const R *coeffs,
                         const R *yaw_lo, const R *yaw_hi, const R *weights, R *out, R *traj,
-                        int32_t *status, int32_t *iters, void *stream_, bool with_stats = true, bool may_defer = false) {
+                        int32_t *status, int32_t *iters, void *stream_, bool with_stats = true, bool may_defer = false,
+                        bool may_order = false) {
   if (!h) { g_last_error = "NULL handle"; return MPC_ERR_INVALID; }
   if ((h->params.precision == MPC_PRECISION_F32) != (sizeof(R) == 4)) {
     g_last_error = "this handle was created with the other precision: fp64 handles take the double entry points, "
@@ -1833,7 +1909,17 @@ static int launch_solve(MpcHandle *h, int64_t B, int64_t ld, int64_t ldo, const 
   }
   int32_t *it_out = iters ? iters : h->d_iters;
   if (soc) { const int rc = soc_alloc(h, &h->soc_ws, h->io_stride / 64); if (rc != MPC_OK) return rc; }
+  /* take order: the key kernel goes ahead of the launch on its stream; its counts live behind the phase counters of the block */
+  const bool ordered = may_order && h->take_order != 0 && sizeof(R) == 8 && n_cuts == 0 && !soc && !weights && h->params.N < 15 &&
+                       B >= h->take_order_min_batch;
+  if (ordered && !h->d_take_list) MPC_HIP_CHECK(hipMalloc((void **)&h->d_take_list, sizeof(int32_t) * mpc::kTakeBins * h->io_stride));
   MPC_HIP_CHECK(hipEventRecord(h->ev0, s));
+  if (ordered) {
+    hipLaunchKernelGGL((mpc_take_key_kernel<R>), dim3((unsigned)waves), dim3(kBlock), 0, s, (float)(h->params.N * h->params.dt), B, ld, state, coeffs,
+                       yaw_lo, yaw_hi, h->take_order == 2 ? 1 : 0, cb + kPhaseCounterInts, h->d_take_list, h->io_stride);
+    MPC_HIP_CHECK(hipGetLastError());
+    ++h->n_take_ordered;
+  }
   auto launch = [&](unsigned grid, void *wsp, const MpcPhase &tp) {
     if constexpr (sizeof(R) == 8) {
       if (soc) {
@@ -1878,6 +1964,7 @@ static int launch_solve(MpcHandle *h, int64_t B, int64_t ld, int64_t ldo, const 
     T.compact_gap = (n_cuts == 0 && B >= h->compact_min_batch) ? h->compact_gap : 0;     /* (a phase that parks keeps iterates in its columns) */
     tail_fields(T);
     T.soc_ws = h->soc_ws;
+    if (ordered) { T.ord_cnt = cb + kPhaseCounterInts; T.ord_list = h->d_take_list; T.ord_ld = h->io_stride; }
     launch((unsigned)waves, wr ? h->ws2 : h->ws, T);
     MPC_HIP_CHECK(hipGetLastError());
   }
@@ -1893,7 +1980,7 @@ extern "C" int mpc_solve_batch_device(MpcHandle *h, int64_t B, int64_t ld, const
                                       const double *coeffs, const double *yaw_lo, const double *yaw_hi,
                                       const double *weights, double *out, double *traj, int32_t *status,
                                       int32_t *iters, void *stream_) {
-  return launch_solve<double>(h, B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters, stream_, true, true);
+  return launch_solve<double>(h, B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters, stream_, true, true, true);
 }
 
 /* MPC_PRECISION_F32: the same solve with fp32 inputs, outputs and workspace (handle created with precision F32) */
@@ -2118,7 +2205,7 @@ static int solve_host(MpcHandle *h, int64_t B, int64_t ld, const R *state, const
   R *d_o = d_oblk, *d_t = d_o + MPC_NOUT * L;
   int32_t *d_st = (int32_t *)(d_o + (out_rows - kIntRows) * L), *d_it = d_st + L;
   int rc = launch_solve<R>(h, B, L, L, di, di + 6 * L, di + 11 * L, di + 12 * L, weights ? di + 13 * L : nullptr, d_o,
-                           traj ? d_t : nullptr, d_st, d_it, (void *)s);
+                           traj ? d_t : nullptr, d_st, d_it, (void *)s, true, false, true);
   if (rc != MPC_OK) return rc;
   MPC_HIP_CHECK(hipMemcpyAsync(ho, d_o, sizeof(R) * out_rows * L, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipStreamSynchronize(s));

@@ -224,6 +224,11 @@ class BatchedMPC:
                 "batches_not_deferred_survivors_full": int(a[7]), "passes_per_slice": int(a[8]), "survivors": int(a[9]),
                 "tail_cut_in_use": int(a[10]), "deferred_share": (int(a[11]) / 65536.0 if a[11] >= 0 else None), "queue_overflows": int(a[12])}
 
+    def take_order_info(self):
+        a = (C.c_int64 * 2)()
+        check(library().mpc_take_order_info(self._h, a), "mpc_take_order_info")
+        return {"launches_in_key_order": int(a[0]), "mode": int(a[1])}
+
     def synchronize(self):
         check(library().mpc_synchronize(self._h), "mpc_synchronize")
 

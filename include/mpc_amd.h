@@ -404,6 +404,10 @@ int mpc_tail_pending(MpcHandle *h, int64_t batch_id, int64_t *n);   /* waits for
  * running mean of the deferred share of a batch in 1/65536 (-1: none retired yet), batches that handed over more than their fresh
  * queue holds (the rest finished in the launch; MPC_TAIL_AUTO then raises its cut) */
 int mpc_tail_info(const MpcHandle *h, int64_t *out13);
+/* Take order: large single-phase fp64 launches of the solve entry points take their instances bin by bin of
+ * predicted work instead of in index order; results do not depend on it.  out2: launches so far that were taken in key order, and
+ * the mode (1 = hardest bin first, 2 = easiest first, 0 = off: MPC_TAKE_ORDER in the environment at mpc_create, a measurement aid). */
+int mpc_take_order_info(const MpcHandle *h, int64_t *out2);
 int mpc_synchronize(MpcHandle *h);
 /* Statistics of the most recent mpc_solve_batch_* call: gathered when asked for, from the status / iters arrays that call
  * wrote (they must still be there); waits for that call's launch. */
