@@ -68,6 +68,15 @@ class MpcBatchStats(C.Structure):
                 ("kernel_ms", C.c_double)]
 
 
+WARM_REC = 22    # MPC_WARM_REC: reals per stage of a warm buffer (s 6, u 2, lam 6, z_L 4, z_U 4)
+
+
+class MpcWarmOpts(C.Structure):
+    """Mirror of ``struct MpcWarmOpts`` (include/mpc_amd.h)."""
+    _fields_ = [("size", C.c_int32), ("shift", C.c_int32), ("mu_init", C.c_double), ("bound_push", C.c_double),
+                ("duals", C.c_int32), ("reserved", C.c_int32)]
+
+
 # every symbol include/mpc_amd.h declares (checked by tests/test_abi.py)
 EXPORTS = ["mpc_params_default", "mpc_params_load_json", "mpc_create", "mpc_set_params", "mpc_destroy",
            "mpc_last_error", "mpc_abi_version", "mpc_solve_batch_device", "mpc_solve_batch_host",
@@ -75,7 +84,9 @@ EXPORTS = ["mpc_params_default", "mpc_params_load_json", "mpc_create", "mpc_set_
            "mpc_telemetry_batch_device", "mpc_rollout_batch_device", "mpc_debug_math_ext",
            "mpc_solve_batch_device_f32", "mpc_wire_parse", "mpc_wire_format_steer", "mpc_wire_format_manual",
            "mpc_wire_telemetry_batch_host", "mpc_telemetry_batch_host", "mpc_handle_device",
-           "mpc_run_batch_host", "mpc_last_batch_id", "mpc_tail_poll", "mpc_tail_wait", "mpc_tail_stream_wait", "mpc_tail_flush", "mpc_tail_pending", "mpc_tail_info", "mpc_solve_batch_host_f32", "mpc_inflight_advice", "mpc_take_order_info"]
+           "mpc_run_batch_host", "mpc_last_batch_id", "mpc_tail_poll", "mpc_tail_wait", "mpc_tail_stream_wait", "mpc_tail_flush", "mpc_tail_pending", "mpc_tail_info", "mpc_solve_batch_host_f32", "mpc_inflight_advice", "mpc_take_order_info",
+           "mpc_warm_rows", "mpc_warm_opts_default", "mpc_solve_batch_device_warm", "mpc_solve_batch_host_warm",
+           "mpc_rollout_batch_device_warm"]
 
 _lib = None
 
@@ -144,6 +155,15 @@ def library():
     L.mpc_tail_pending.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.mpc_tail_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.mpc_take_order_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    L.mpc_warm_rows.argtypes = [C.c_int]
+    L.mpc_warm_rows.restype = C.c_int64
+    L.mpc_warm_opts_default.argtypes = [C.POINTER(MpcWarmOpts)]
+    # handle, B, ld, state .. weights, warm_in, warm_status, warm_out, ld_warm, opts, out, traj, status, iters[, stream]
+    L.mpc_solve_batch_device_warm.argtypes = ([C.c_void_p, C.c_int64, C.c_int64] + [DP] * 8 + [C.c_int64, C.POINTER(MpcWarmOpts)] +
+                                              [DP] * 4 + [C.c_void_p])
+    L.mpc_solve_batch_host_warm.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [DP] * 8 + [C.c_int64, C.POINTER(MpcWarmOpts)] + [DP] * 4
+    L.mpc_rollout_batch_device_warm.argtypes = ([C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 5 + [C.POINTER(MpcWarmOpts)] +
+                                                [DP] * 3 + [C.c_void_p])
     L.mpc_wire_parse.argtypes = [C.c_char_p, C.c_int64, C.POINTER(MpcWireTelemetry)]
     L.mpc_wire_format_steer.argtypes = [C.c_double, C.c_double, C.c_char_p, C.c_int64]
     L.mpc_wire_format_steer.restype = C.c_int64
@@ -166,6 +186,37 @@ def params_default():
     p = MpcParams()
     check(library().mpc_params_default(C.byref(p)), "mpc_params_default")
     return p
+
+
+def warm_rows(N):
+    """mpc_warm_rows: rows of a warm buffer for horizon N, (N-1) * WARM_REC."""
+    r = int(library().mpc_warm_rows(int(N)))
+    if r < 0:
+        raise MpcError("mpc_warm_rows(%d): N out of range" % N)
+    return r
+
+
+def warm_opts_default(**overrides):
+    """mpc_warm_opts_default, with keyword overrides (shift=0, mu_init=1e-6 ...)."""
+    o = MpcWarmOpts()
+    check(library().mpc_warm_opts_default(C.byref(o)), "mpc_warm_opts_default")
+    for k, v in overrides.items():
+        setattr(o, k, v)
+    return o
+
+
+def warm_to_vars(warm, state, N):
+    """One instance's warm column ((N-1) * WARM_REC values) and its state [6] as the reference's decision vector of 8N-2
+    entries in the order of MPC.cpp:56-63: x, y, psi, v, cte, epsi (N each; index 0 is the given state), delta, a (N-1 each)."""
+    import numpy as np
+    rec = np.asarray(warm, dtype=np.float64).reshape(N - 1, WARM_REC)
+    v = np.empty(8 * N - 2)
+    for q in range(6):
+        v[q * N] = state[q]
+        v[q * N + 1:(q + 1) * N] = rec[:, q]
+    v[6 * N:7 * N - 1] = rec[:, 6]
+    v[7 * N - 1:] = rec[:, 7]
+    return v
 
 
 def inflight_advice(params, B):

@@ -2224,6 +2224,102 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
     }
   }
 
+  /* ------------------------------------------------------------------ */
+  /* warm start (opt-in: the mpc_*_warm entry points of mpc_amd.h)        */
+  /* ------------------------------------------------------------------ */
+  /* Only the INITIAL ITERATE changes.  setup() has decided the branch outcomes of the objective and the objective scaling at the
+   * reference's start point (the state at index 0, zeros elsewhere: what CppAD's tape and IPOPT's gradient-based scaling see in
+   * MPC.cpp:207-292) and is not touched, so a warm solve works on the same NLP as a cold one and ends at that NLP's solution.  The
+   * reference cannot warm start: a non-zero xi would record another tape.  These four functions are the only place that knows the
+   * warm rules; the kernels and the test-only CPU build call them and nothing else.  fp64 solver only.
+   *
+   * warm_point: iterate slot 0 from the final iterate of an earlier solve, get(k, f) = field f (Layout<double>: s 6, u 2, lam 6,
+   * z_L 4, z_U 4) of the record of stage k.  W.shift: record k takes the earlier record k+1, the last one is repeated (the next
+   * step of a closed loop).  psi, v, delta, a are moved inside the relaxed bounds by W.bound_push (the rule of pushed()); the bound
+   * duals are kept and floored at mu0 / (kappa_sigma slack) -- the lower end of the band IPOPT's own safeguard (W&B eq. 16) would
+   * put them in -- or re-derived as mu0 / slack (W.duals = 1).  The direction fields are zeroed as start_point() does.
+   * Returns false -- the caller then starts cold -- for a record that is no iterate of this NLP: a value that is not finite, a
+   * bounded quantity outside its relaxed bounds, a negative dual. */
+  MPC_HD R warm_mu(const MpcWarmOpts &W) const { return mpc_min(IC::mu_init, mpc_max((R)W.mu_init, tol / R(10.0))); }
+  template <class Get> MPC_HD bool warm_point(Get get, const MpcWarmOpts &W) {
+    static_assert(sizeof(R) == 8 && IT_SZ == MPC_WARM_REC, "the warm record is the fp64 iterate record");
+    const R mu0 = warm_mu(W), kp = (R)W.bound_push;
+    const R lo[4] = {yl, vl, dl, al}, hi[4] = {yu, vu, du, au};
+    const R zero[D_N] = {};
+    bool ok = true;
+    for (int k = 0; k < M; ++k) {
+      const int ks = (W.shift && k + 1 < M) ? k + 1 : k;
+      R rec[IT_SZ];
+      MPC_UNROLL
+      for (int f = 0; f < IT_SZ; f++) rec[f] = get(ks, f);
+      MPC_UNROLL
+      for (int f = 0; f < IT_SZ; f++) ok = ok && mpc_abs(rec[f]) <= IC::huge;      /* (false for a NaN) */
+      MPC_UNROLL
+      for (int b = 0; b < 4; b++) {
+        const int fx = b < 2 ? F_S + 2 + b : F_U + b - 2;
+        const R x = rec[fx];
+        ok = ok && x >= lo[b] && x <= hi[b] && rec[F_ZL + b] >= R(0.0) && rec[F_ZU + b] >= R(0.0);
+        const R pl = mpc_min(kp * mpc_max(R(1.0), mpc_abs(lo[b])), kp * (hi[b] - lo[b]));
+        const R pu = mpc_min(kp * mpc_max(R(1.0), mpc_abs(hi[b])), kp * (hi[b] - lo[b]));
+        const R xp = mpc_min(mpc_max(x, lo[b] + pl), hi[b] - pu);
+        rec[fx] = xp;
+        const R zl0 = mu0 / (xp - lo[b]), zu0 = mu0 / (hi[b] - xp);
+        rec[F_ZL + b] = W.duals ? zl0 : mpc_max(rec[F_ZL + b], zl0 * IC::inv_kappa_sigma);
+        rec[F_ZU + b] = W.duals ? zu0 : mpc_max(rec[F_ZU + b], zu0 * IC::inv_kappa_sigma);
+      }
+      ws.template store_run<0, IT_SZ>(k, IT0, rec);
+      ws.template store_run<F_D, D_N>(k, 0, zero);
+    }
+    return ok;
+  }
+  /* begin(false) -- no least-squares multiplier estimate: the multipliers came along -- with the warm barrier parameter */
+  MPC_HD void begin_warm(const MpcWarmOpts &W) {
+    begin(false);
+    mu = warm_mu(W); tau = mpc_max(IC::tau_min, R(1.0) - mu);
+  }
+  /* the final iterate in the record layout warm_point() reads: put(k, f, value) */
+  template <class Put> MPC_HD void warm_store(Put put) const {
+    const int I = it(cur);
+    for (int k = 0; k < M; ++k) {
+      R rec[IT_SZ];
+      MPC_UNROLL
+      for (int f = 0; f < IT_SZ; f++) rec[f] = ws.it(k, I, f);
+      MPC_UNROLL
+      for (int f = 0; f < IT_SZ; f++) put(k, f, rec[f]);
+    }
+  }
+  /* One instance, warm where `warm` says so: the warm attempt; whatever it ends in but SUCCESS -- and a record warm_point() refuses
+   * -- is followed by the complete cold solve (least-squares start, then the one restart: solve()).  The iterations add up.
+   * warm = false is solve() itself.  One loop with one step() (the sweeps are force-inlined: a second call site would double the
+   * code); attempt = -1 marks the warm attempt, as in the lane kernel, which drives the same sequence through its own state. */
+  template <class Get> MPC_HD int solve_warm(bool warm, Get get, const MpcWarmOpts &W) {
+    int it_total = 0, attempt = 0;
+    if (warm) {
+      warm = warm_point(get, W);
+      if (!warm) start_point();
+    }
+    if (warm) { begin_warm(W); attempt = -1; }
+    else begin(true);
+    for (;;) {
+      const int r = step();
+      if (r == MPC_RUNNING) continue;
+      if (attempt < 0 && r != MPC_STATUS_SUCCESS) {
+        attempt = 0; it_total += iters;
+        start_point();
+        begin(true);
+        continue;
+      }
+      if (r == MPC_STATUS_LINESEARCH && attempt == 0 && !no_restart) {
+        attempt = 1; it_total += iters;
+        start_point();
+        begin(false);
+        continue;
+      }
+      iters += it_total;
+      return r;
+    }
+  }
+
   /* The state of an unfinished instance between two passes with phase == PH_DIR (everything else lives in the
    * current iterate slot of the workspace or is recomputed by setup()): 36 values through an accessor a(q). */
   enum { PARK_N = 47 };

@@ -187,6 +187,19 @@ struct MpcPhase {
   int64_t ord_ld;
 };
 
+/* What the WARM build of mpc_solve_kernel gets on top (the mpc_*_warm entry points): the warm buffers, [(N-1) * MPC_WARM_REC][ld_warm]
+ * doubles addressed by INSTANCE at both ends -- quantity-major, so neighbouring lanes coalesce like every other array at the ABI, and
+ * lane compaction may move an instance between the two.  warm_in may be warm_out and warm_status may be the launch's own status
+ * array: a lane reads its instance's column (and its status) when it takes the instance and writes them when it has finished it, so
+ * none of these pointers is __restrict__.  A type of its own: the other builds' kernel arguments are what they were. */
+struct MpcPhaseWarm : MpcPhase {
+  const double *warm_in;          /* nullptr: every instance starts cold */
+  const int32_t *warm_status;     /* nullptr: every column of warm_in is valid */
+  double *warm_out;               /* nullptr: nothing is written */
+  int64_t ld_warm;
+  MpcWarmOpts wopts;
+};
+
 /* The take-order key of every instance of a launch (csrc/mpc_take_key.h) and the bins' lists: one thread per instance, a wave
  * appends its instances to the bins' lists.  No LDS and few registers: its waves fit beside the resident waves of a bulk
  * launch.  cnt[] is zero on entry (it lives in the launch's counter block). */
@@ -258,14 +271,15 @@ template <class RIO, class R> struct OutRef {
 /* RIO: the type of the arrays at the ABI (inputs, outputs); R: the solver's.  They differ only in the fp64 phase of a
  * mixed-precision solve on an MPC_PRECISION_F32 handle (RIO = float, R = double).  RSRC: the reals of the workspace a
  * promote_in phase takes its iterates from. */
-template <bool STAGING, class R, class RIO = R, class RSRC = RIO, bool SOC = false>
+template <bool STAGING, class R, class RIO = R, class RSRC = RIO, bool SOC = false, bool WARM = false>
 __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
     const MpcParams P, const int64_t B, const int64_t ld, const int64_t ldo, const RIO *__restrict__ state,
     const RIO *__restrict__ coeffs, const RIO *__restrict__ yaw_lo, const RIO *__restrict__ yaw_hi,
     const RIO *__restrict__ weights, RIO *__restrict__ out, RIO *__restrict__ traj,
     int32_t *__restrict__ status, int32_t *__restrict__ iters, R *__restrict__ wsbase,
-    const int64_t tile_reals, const MpcPhase T) {
+    const int64_t tile_reals, const std::conditional_t<WARM, MpcPhaseWarm, MpcPhase> T) {
   extern __shared__ double smem[];
+  static_assert(!WARM || (sizeof(R) == 8 && std::is_same<R, RIO>::value && std::is_same<R, RSRC>::value && !SOC), "warm start: the plain fp64 solve only");
   using WS = std::conditional_t<SOC, mpc::TiledSocWorkspace<STAGING, R>, mpc::TiledWorkspace<STAGING, R>>;
   using SV = mpc::Solver<WS, R, 0, SOC>;
   using FL = mpc::Fields<R>;
@@ -343,6 +357,14 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
           const int64_t l = ldo;
           S.unpack([o, l](int q) { return OutRef<RIO, R>{o + q * l}; }, [t, l](int q) { return OutRef<RIO, R>{t + q * l}; }, traj != nullptr,
                    (R)yaw_lo[i], (R)yaw_hi[i]);
+          if constexpr (WARM) {
+            /* the final iterate, whatever the status (the caller's next solve looks at the status) */
+            if (T.warm_out) {
+              double *wo = T.warm_out + i;
+              const int64_t lw = T.ld_warm;
+              S.warm_store([wo, lw](int k, int f, R v) { wo[(int64_t)(k * MPC_WARM_REC + f) * lw] = v; });
+            }
+          }
           status[i] = fin_status;
           if (iters) iters[i] = S.iters + it_total;
           fin = false;
@@ -380,8 +402,26 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
               for (int q = 0; q < MPC_NW; q++) w[q] = (R)P.weights[q];
             }
             const bool from_scratch = T.promote_in && T.in_park[pos + 35 * T.ld_park] != 0.0;   /* the fp32 phase gave up on it */
-            const int s0 = S.setup(st, cf, (R)yaw_lo[i], (R)yaw_hi[i], w, !T.resume || from_scratch);
-            if (T.promote_in && s0 != MPC_STATUS_SUCCESS) {
+            bool warm = false, warm_cand = false;   /* WARM: this instance has a valid column in warm_in / starts from it */
+            if constexpr (WARM) warm_cand = T.warm_in != nullptr && (T.warm_status == nullptr || T.warm_status[i] == MPC_STATUS_SUCCESS);
+            const int s0 = S.setup(st, cf, (R)yaw_lo[i], (R)yaw_hi[i], w, (!T.resume || from_scratch) && !warm_cand);
+            if constexpr (WARM) {
+              if (warm_cand) {
+                if (s0 == MPC_STATUS_SUCCESS) {
+                  const double *wi = T.warm_in + i;
+                  const int64_t lw = T.ld_warm;
+                  warm = S.warm_point([wi, lw](int k, int f) -> R { return wi[(int64_t)(k * MPC_WARM_REC + f) * lw]; }, T.wopts);
+                }
+                if (!warm) S.start_point();     /* set-up left slot 0 to the warm point, and the column holds no iterate of this NLP */
+              }
+            }
+            if constexpr (WARM) {
+              /* attempt -1: should the warm attempt end in anything but SUCCESS, the instance is solved again the way a cold solve
+               * starts -- the convention of an iterate handed over by the fp32 phase, below */
+              if (warm) { S.begin_warm(T.wopts); attempt = -1; it_total = 0; passes = 0; have = true; }
+            }
+            if (warm) {
+            } else if (T.promote_in && s0 != MPC_STATUS_SUCCESS) {
               /* a start state that the fp32 set-up let through (outside the relaxed bounds by less than the fp32 spacing) and this
                * solver's set-up rejects: the verdict of the single-phase solve, the start point reported */
               S.start_point();
@@ -840,6 +880,55 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_wave_kernel(
   }
 }
 
+/* The same with a warm start (the mpc_*_warm entry points; see MpcPhaseWarm for the buffers): a kernel of its own, so that the cold
+ * launches are what they were.  Every lane of the group reads the instance's column of warm_in (Solver::solve_warm: the warm
+ * attempt, then the complete cold solve if that does not end in SUCCESS); the group's first lane writes warm_out. */
+template <class R, int LPI>
+__global__ __launch_bounds__(kBlock, 1) void mpc_solve_wave_warm_kernel(
+    const MpcParams P, const int64_t B, const int64_t ld, const int64_t ldo, const R *__restrict__ state,
+    const R *__restrict__ coeffs, const R *__restrict__ yaw_lo, const R *__restrict__ yaw_hi,
+    const R *__restrict__ weights, R *__restrict__ out, R *__restrict__ traj,
+    int32_t *status, int32_t *__restrict__ iters, const double *warm_in, const int32_t *warm_status, double *warm_out,
+    const int64_t ld_warm, const MpcWarmOpts wopts) {
+  extern __shared__ double smem[];
+  constexpr int G = 64 / LPI;
+  using WS = mpc::LdsWorkspace<R, G>;
+  using SV = mpc::Solver<WS, R, LPI, false>;
+  const int group = threadIdx.x / LPI;
+  const int64_t i = (int64_t)blockIdx.x * G + group;
+  if (i >= B) return;
+  WS ws;
+  ws.base = (typename WS::lreal *)smem;
+  ws.lane = group;
+  SV S(P, ws);
+  S.wlane = threadIdx.x % LPI; S.wbase = group * LPI;
+  R st[6], cf[MPC_NCOEF], w[MPC_NW];
+#pragma unroll
+  for (int q = 0; q < 6; q++) st[q] = state[q * ld + i];
+#pragma unroll
+  for (int q = 0; q < MPC_NCOEF; q++) cf[q] = coeffs[q * ld + i];
+#pragma unroll
+  for (int q = 0; q < MPC_NW; q++) w[q] = weights ? weights[q * ld + i] : (R)P.weights[q];
+  const bool warm = warm_in != nullptr && (warm_status == nullptr || warm_status[i] == MPC_STATUS_SUCCESS);
+  int r = S.setup(st, cf, yaw_lo[i], yaw_hi[i], w, true);
+  if (r == MPC_STATUS_SUCCESS) {
+    const double *wi = warm_in + i;
+    r = S.solve_warm(warm, [wi, ld_warm](int k, int f) -> R { return wi[(int64_t)(k * MPC_WARM_REC + f) * ld_warm]; }, wopts);
+  }
+  if (S.wlane == 0) {
+    R *o = out + i;
+    R *t = traj ? traj + i : nullptr;
+    const int64_t l = ldo;
+    S.unpack([o, l](int q) -> R & { return o[q * l]; }, [t, l](int q) -> R & { return t[q * l]; }, traj != nullptr, yaw_lo[i], yaw_hi[i]);
+    if (warm_out) {
+      double *wo = warm_out + i;
+      S.warm_store([wo, ld_warm](int k, int f, R v) { wo[(int64_t)(k * MPC_WARM_REC + f) * ld_warm] = v; });
+    }
+    status[i] = r;
+    if (iters) iters[i] = S.iters;
+  }
+}
+
 /* MPC::run pre-processing, one instance per lane (mpc_run_core.h).  rows of `pre`: state 0..5, coeffs 6..10,
  * yaw_lo 11, yaw_hi 12, max_yaw_change 13, target_speed 14 */
 template <bool TELEMETRY>
@@ -1068,6 +1157,10 @@ struct MpcHandle {
   int64_t auto_share = -1;
   int64_t batch_seq = 0;         /* id of the most recent batch (every solve call counts) */
   int64_t n_deferred = 0;        /* deferring batches so far: batch k of them uses slot k % tail_ring and fresh queue k % kFreshRing */
+  /* warm start (allocated on first use): the rollout's warm buffer, [mpc_warm_rows(N)][io_stride] doubles, and the device side of the
+   * host entry point's warm_in / warm_out (one block, read and written in place) with the status the warm data came with */
+  double *d_warm = nullptr, *d_warm_io = nullptr;
+  int32_t *d_warm_st = nullptr;
   double *d_tel = nullptr;       /* mpc_telemetry_batch_host: device staging, grown on demand */
   size_t tel_bytes = 0;
   /* last call */
@@ -1250,6 +1343,9 @@ extern "C" void mpc_destroy(MpcHandle *h) {
   if (h->d_take_list) (void)hipFree(h->d_take_list);
   if (h->d_piter) (void)hipFree(h->d_piter);
   if (h->d_tel) (void)hipFree(h->d_tel);
+  if (h->d_warm) (void)hipFree(h->d_warm);
+  if (h->d_warm_io) (void)hipFree(h->d_warm_io);
+  if (h->d_warm_st) (void)hipFree(h->d_warm_st);
   if (h->tail_ready) (void)tail_drain(h);         /* stragglers still queued are finished: their batches' arrays may be read afterwards */
   if (h->tail_stream) (void)hipStreamSynchronize(h->tail_stream);
   for (void *q : {(void *)h->d_tcount, (void *)h->d_remaining, h->tail_ws, h->soc_tail, (void *)h->surv_dev[0].park, h->surv_dev[0].iter,
@@ -1983,6 +2079,120 @@ extern "C" int mpc_solve_batch_device(MpcHandle *h, int64_t B, int64_t ld, const
   return launch_solve<double>(h, B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters, stream_, true, true, true);
 }
 
+/* ---- warm start ---------------------------------------------------------------------------------------------------------- */
+extern "C" int64_t mpc_warm_rows(int N) { return (N < 3 || N > MPC_MAX_N) ? (int64_t)MPC_ERR_INVALID : (int64_t)(N - 1) * MPC_WARM_REC; }
+
+extern "C" int mpc_warm_opts_default(MpcWarmOpts *o) {
+  if (!o) return MPC_ERR_INVALID;
+  memset(o, 0, sizeof(*o));
+  /* DESIGN.md section 6i has the grid these come from: the fewest iterations among the settings without a status difference or a
+   * fork against the oracle on either population -- the previous solution as it is, not moved on by a stage */
+  o->size = (int32_t)sizeof(MpcWarmOpts); o->shift = 0; o->mu_init = 1e-6; o->bound_push = 1e-6; o->duals = 0;
+  return MPC_OK;
+}
+
+/* what every warm entry point checks before it touches anything; *W: the options in effect */
+static int warm_check(MpcHandle *h, const MpcWarmOpts *opts, MpcWarmOpts *W) {
+  if (!h) { g_last_error = "NULL handle"; return MPC_ERR_INVALID; }
+  if (h->params.precision != MPC_PRECISION_F64) { g_last_error = "warm start: fp64 handles only (this one was created with MPC_PRECISION_F32)"; return MPC_ERR_INVALID; }
+  if (h->mixed) {
+    g_last_error = "warm start is not available on a handle whose solve starts in fp32 (two launches): create it with MpcParams.f64_f32_start = 0";
+    return MPC_ERR_UNSUPPORTED;
+  }
+  if (h->params.max_soc > 0) { g_last_error = "warm start is not available with the second-order correction: set MpcParams.max_soc = 0"; return MPC_ERR_UNSUPPORTED; }
+  (void)mpc_warm_opts_default(W);
+  if (opts) {
+    if (opts->size != (int32_t)sizeof(MpcWarmOpts)) { g_last_error = "MpcWarmOpts.size mismatch (fill it with mpc_warm_opts_default)"; return MPC_ERR_INVALID; }
+    if ((opts->shift != 0 && opts->shift != 1) || (opts->duals != 0 && opts->duals != 1) || !(opts->mu_init > 0 && opts->mu_init <= 0.1) ||
+        !(opts->bound_push > 0 && opts->bound_push <= 1e-2)) {
+      g_last_error = "MpcWarmOpts: shift and duals are 0 or 1, 0 < mu_init <= 0.1, 0 < bound_push <= 1e-2"; return MPC_ERR_INVALID;
+    }
+    *W = *opts;
+  }
+  return MPC_OK;
+}
+
+/* One launch, all arrays on the device: the wave kernel up to wave_max_batch instances, else the WARM build of the lane kernel --
+ * a single phase, no deferred tails, no pass cuts, no take order.  with_stats as in launch_solve. */
+static int launch_warm(MpcHandle *h, int64_t B, int64_t ld, int64_t ldo, const double *state, const double *coeffs, const double *yaw_lo,
+                       const double *yaw_hi, const double *weights, const double *warm_in, const int32_t *warm_status, double *warm_out,
+                       int64_t ld_warm, const MpcWarmOpts &W, double *out, double *traj, int32_t *status, int32_t *iters, void *stream_,
+                       bool with_stats) {
+  using R = double;
+  if (B < 0 || ld < B || ldo < B) { g_last_error = "ld < B"; return MPC_ERR_INVALID; }
+  if ((warm_in || warm_out) && ld_warm < B) { g_last_error = "ld_warm < B"; return MPC_ERR_INVALID; }
+  if (B > h->max_batch) { g_last_error = "B exceeds the handle's max_batch"; return MPC_ERR_INVALID; }
+  h->last_B = B; h->timed = false; h->have_stats = false; h->stats_pending = false;
+  ++h->batch_seq;
+  if (B == 0) {
+    if (!h->brec) h->brec = new MpcHandle::BatchRec[MpcHandle::kBatchRecs];
+    MpcHandle::BatchRec &R0 = h->brec[h->batch_seq % MpcHandle::kBatchRecs];
+    R0.id = h->batch_seq; R0.kind = 2;
+    return MPC_OK;
+  }
+  if (!state || !coeffs || !yaw_lo || !yaw_hi || !out || !status) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
+  MPC_ON_DEVICE(h);
+  hipStream_t s = (hipStream_t)stream_;
+  MpcHandle::BatchRec *rec = nullptr;
+  { const int rc = batch_rec(h, h->batch_seq, &rec); if (rc != MPC_OK) return rc; }
+  rec->id = 0;
+  int32_t *it_out = iters ? iters : h->d_iters;
+  MPC_HIP_CHECK(hipEventRecord(h->ev0, s));
+  if (h->wave_max_batch > 0 && B <= h->wave_max_batch) {
+    /* lanes per instance as in launch_solve */
+    const int64_t per = (int64_t)mpc::workspace_fields_per_instance(h->params.N, false, h->params.initial_state_rows != 0) * (int64_t)sizeof(R);
+    int lpi = h->params.N - 1 <= 16 ? 16 : (h->params.N - 1 <= 32 ? 32 : 64);
+    if (B <= kWaveWholeMax) lpi = 64;
+    if (const char *e = getenv("MPC_WAVE_LPI")) lpi = atoi(e) == 16 ? 16 : (atoi(e) == 32 ? 32 : 64);
+    if (lpi < h->params.N - 1) lpi = 64;
+    if (lpi == 16)
+      hipLaunchKernelGGL((mpc_solve_wave_warm_kernel<R, 16>), dim3((unsigned)((B + 3) / 4)), dim3(kBlock), (size_t)(4 * per), s, h->params, B, ld, ldo, state, coeffs,
+                         yaw_lo, yaw_hi, weights, out, traj, status, it_out, warm_in, warm_status, warm_out, ld_warm, W);
+    else if (lpi == 32)
+      hipLaunchKernelGGL((mpc_solve_wave_warm_kernel<R, 32>), dim3((unsigned)((B + 1) / 2)), dim3(kBlock), (size_t)(2 * per), s, h->params, B, ld, ldo, state, coeffs,
+                         yaw_lo, yaw_hi, weights, out, traj, status, it_out, warm_in, warm_status, warm_out, ld_warm, W);
+    else
+      hipLaunchKernelGGL((mpc_solve_wave_warm_kernel<R, 64>), dim3((unsigned)B), dim3(kBlock), (size_t)per, s, h->params, B, ld, ldo, state, coeffs,
+                         yaw_lo, yaw_hi, weights, out, traj, status, it_out, warm_in, warm_status, warm_out, ld_warm, W);
+  } else {
+    int32_t *cb = h->d_counter + (h->counter_seq % kCounterRing) * kCounterInts;
+    int32_t *zero_next = h->d_counter + ((h->counter_seq + kCounterRing / 2) % kCounterRing) * kCounterInts;
+    ++h->counter_seq;
+    MpcPhaseWarm T;
+    memset(&T, 0, sizeof(T));
+    T.take = cb; T.n_out = cb + 1; T.zero_next = zero_next; T.ld_park = h->io_stride;
+    T.refill_min = kRefillMin; T.refill_wait = kRefillWait;
+    T.compact_cooldown = kCompactCooldown;
+    T.compact_gap = B >= h->compact_min_batch ? h->compact_gap : 0;
+    T.t_batch = h->batch_seq;
+    T.warm_in = warm_in; T.warm_status = warm_status; T.warm_out = warm_out; T.ld_warm = ld_warm; T.wopts = W;
+    const unsigned grid = (unsigned)((B + kBlock - 1) / kBlock);
+    if (h->staging)
+      hipLaunchKernelGGL((mpc_solve_kernel<true, R, R, R, false, true>), dim3(grid), dim3(kBlock), staging_lds_bytes<R>(), s, h->params, B, ld, ldo, state, coeffs,
+                         yaw_lo, yaw_hi, weights, out, traj, status, it_out, (R *)h->ws, h->ws_stride, T);
+    else
+      hipLaunchKernelGGL((mpc_solve_kernel<false, R, R, R, false, true>), dim3(grid), dim3(kBlock), 0, s, h->params, B, ld, ldo, state, coeffs,
+                         yaw_lo, yaw_hi, weights, out, traj, status, it_out, (R *)h->ws, h->ws_stride, T);
+  }
+  MPC_HIP_CHECK(hipGetLastError());
+  MPC_HIP_CHECK(hipEventRecord(h->ev1, s));
+  h->timed = true;
+  rec->id = h->batch_seq; rec->kind = 0; rec->slot = 0;
+  MPC_HIP_CHECK(hipEventRecord(rec->ev, s));
+  if (with_stats) { h->st_status = status; h->st_iters = it_out; h->st_B = B; h->st_ev = rec->ev; h->stats_pending = true; }
+  return MPC_OK;
+}
+
+extern "C" int mpc_solve_batch_device_warm(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
+                                           const double *yaw_lo, const double *yaw_hi, const double *weights, const double *warm_in,
+                                           const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts,
+                                           double *out, double *traj, int32_t *status, int32_t *iters, void *stream_) {
+  MpcWarmOpts W;
+  const int rc = warm_check(h, opts, &W);
+  if (rc != MPC_OK) return rc;
+  return launch_warm(h, B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, warm_in, warm_status, warm_out, ld_warm, W, out, traj, status, iters, stream_, true);
+}
+
 /* MPC_PRECISION_F32: the same solve with fp32 inputs, outputs and workspace (handle created with precision F32) */
 extern "C" int mpc_solve_batch_device_f32(MpcHandle *h, int64_t B, int64_t ld, const float *state,
                                           const float *coeffs, const float *yaw_lo, const float *yaw_hi,
@@ -2148,6 +2358,39 @@ extern "C" int mpc_rollout_batch_device(MpcHandle *h, int64_t B, int64_t ld, int
   return record_stats(h, B, status, iters, s);   /* worst status per instance, iterations summed over the steps */
 }
 
+/* the rollout with every step after the first warm-started from the step before (the handle keeps the buffer) */
+extern "C" int mpc_rollout_batch_device_warm(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
+                                             const double *yaw_lo, const double *yaw_hi, const double *weights, const MpcWarmOpts *opts,
+                                             double *hist, int32_t *status, int32_t *iters, void *stream_) {
+  MpcWarmOpts W;
+  { const int rc = warm_check(h, opts, &W); if (rc != MPC_OK) return rc; }
+  if (B < 0 || ld < B || B > h->max_batch) { g_last_error = "bad B/ld"; return MPC_ERR_INVALID; }
+  if (steps < 1) { g_last_error = "steps < 1"; return MPC_ERR_INVALID; }
+  if (B == 0) { h->last_B = 0; return MPC_OK; }
+  if (!state || !coeffs || !yaw_lo || !yaw_hi || !status) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
+  MPC_ON_DEVICE(h);
+  if (!hist && (!h->d_run9 || h->run9_ld < ld)) {
+    if (h->d_run9) MPC_HIP_CHECK(hipFree(h->d_run9));
+    h->d_run9 = nullptr;
+    MPC_HIP_CHECK(hipMalloc((void **)&h->d_run9, sizeof(double) * 9 * ld));
+    h->run9_ld = ld;
+  }
+  if (!h->d_rstat) MPC_HIP_CHECK(hipMalloc((void **)&h->d_rstat, sizeof(int32_t) * h->io_stride));
+  if (!h->d_warm) MPC_HIP_CHECK(hipMalloc((void **)&h->d_warm, sizeof(double) * (size_t)mpc_warm_rows(h->params.N) * (size_t)h->io_stride));
+  hipStream_t s = (hipStream_t)stream_;
+  const unsigned grid = (unsigned)((B + 255) / 256);
+  for (int t = 0; t < steps; t++) {
+    double *o9 = hist ? hist + (int64_t)t * 9 * ld : h->d_run9;
+    /* in place: a lane reads its car's column and its previous status (d_rstat) before it writes either */
+    int rc = launch_warm(h, B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, t == 0 ? nullptr : h->d_warm, h->d_rstat, h->d_warm, h->io_stride, W,
+                         o9, nullptr, h->d_rstat, h->d_iters, stream_, false);
+    if (rc != MPC_OK) return rc;
+    hipLaunchKernelGGL(mpc_rollout_step_kernel, dim3(grid), dim3(256), 0, s, B, ld, t == 0, o9, state, h->d_rstat, h->d_iters, status, iters);
+    MPC_HIP_CHECK(hipGetLastError());
+  }
+  return record_stats(h, B, status, iters, s);
+}
+
 extern "C" int mpc_synchronize(MpcHandle *h) {
   if (!h) return MPC_ERR_INVALID;
   MPC_ON_DEVICE(h);
@@ -2171,9 +2414,13 @@ static void for_rows(int n_rows, size_t row_bytes, Fn fn) {
 }
 
 /* host pointers: one copy in, the launch(es), one copy out, on the handle's own stream; R = the handle's precision */
+/* (warm: the host arrays of mpc_solve_batch_host_warm and the options in effect; fp64 handles only) */
+struct HostWarm {
+  const double *in; const int32_t *in_status; double *out; int64_t ld; MpcWarmOpts W;
+};
 template <class R>
 static int solve_host(MpcHandle *h, int64_t B, int64_t ld, const R *state, const R *coeffs, const R *yaw_lo, const R *yaw_hi,
-                      const R *weights, R *out, R *traj, int32_t *status, int32_t *iters) {
+                      const R *weights, R *out, R *traj, int32_t *status, int32_t *iters, const HostWarm *warm = nullptr) {
   if (!h) { g_last_error = "NULL handle"; return MPC_ERR_INVALID; }
   if ((h->params.precision == MPC_PRECISION_F32) != (sizeof(R) == 4)) {
     g_last_error = "this handle was created with the other precision (mpc_solve_batch_host for fp64 handles, mpc_solve_batch_host_f32 for MPC_PRECISION_F32)";
@@ -2204,9 +2451,28 @@ static int solve_host(MpcHandle *h, int64_t B, int64_t ld, const R *state, const
   MPC_HIP_CHECK(hipMemcpyAsync(di, hi, sizeof(R) * in_rows * L, hipMemcpyHostToDevice, s));
   R *d_o = d_oblk, *d_t = d_o + MPC_NOUT * L;
   int32_t *d_st = (int32_t *)(d_o + (out_rows - kIntRows) * L), *d_it = d_st + L;
-  int rc = launch_solve<R>(h, B, L, L, di, di + 6 * L, di + 11 * L, di + 12 * L, weights ? di + 13 * L : nullptr, d_o,
-                           traj ? d_t : nullptr, d_st, d_it, (void *)s, true, false, true);
-  if (rc != MPC_OK) return rc;
+  int rc = MPC_OK;
+  if constexpr (sizeof(R) == 8) {
+    if (warm) {
+      /* the warm buffer goes through a device block of its own, rows of the handle's stride, read and written in place */
+      const int64_t rows = mpc_warm_rows(N);
+      if ((warm->in || warm->out) && warm->ld < B) { g_last_error = "ld_warm < B"; return MPC_ERR_INVALID; }
+      if ((warm->in || warm->out) && !h->d_warm_io) MPC_HIP_CHECK(hipMalloc((void **)&h->d_warm_io, sizeof(double) * (size_t)rows * (size_t)S));
+      if (warm->in && warm->in_status && !h->d_warm_st) MPC_HIP_CHECK(hipMalloc((void **)&h->d_warm_st, sizeof(int32_t) * S));
+      if (warm->in) MPC_HIP_CHECK(hipMemcpy2DAsync(h->d_warm_io, sizeof(double) * S, warm->in, sizeof(double) * warm->ld, sizeof(double) * B, rows, hipMemcpyHostToDevice, s));
+      if (warm->in && warm->in_status) MPC_HIP_CHECK(hipMemcpyAsync(h->d_warm_st, warm->in_status, sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
+      rc = launch_warm(h, B, L, L, di, di + 6 * L, di + 11 * L, di + 12 * L, weights ? di + 13 * L : nullptr, warm->in ? h->d_warm_io : nullptr,
+                       (warm->in && warm->in_status) ? h->d_warm_st : nullptr, warm->out ? h->d_warm_io : nullptr, S, warm->W, d_o, traj ? d_t : nullptr,
+                       d_st, d_it, (void *)s, true);
+      if (rc != MPC_OK) return rc;
+      if (warm->out) MPC_HIP_CHECK(hipMemcpy2DAsync(warm->out, sizeof(double) * warm->ld, h->d_warm_io, sizeof(double) * S, sizeof(double) * B, rows, hipMemcpyDeviceToHost, s));
+    }
+  }
+  if (!warm) {
+    rc = launch_solve<R>(h, B, L, L, di, di + 6 * L, di + 11 * L, di + 12 * L, weights ? di + 13 * L : nullptr, d_o,
+                         traj ? d_t : nullptr, d_st, d_it, (void *)s, true, false, true);
+    if (rc != MPC_OK) return rc;
+  }
   MPC_HIP_CHECK(hipMemcpyAsync(ho, d_o, sizeof(R) * out_rows * L, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipStreamSynchronize(s));
   for_rows(MPC_NOUT + (traj ? 2 * N : 0), sizeof(R) * B, [=](int q) {
@@ -2224,6 +2490,16 @@ extern "C" int mpc_solve_batch_host(MpcHandle *h, int64_t B, int64_t ld, const d
                                     const double *weights, double *out, double *traj, int32_t *status,
                                     int32_t *iters) {
   return solve_host<double>(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters);
+}
+
+extern "C" int mpc_solve_batch_host_warm(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
+                                         const double *yaw_lo, const double *yaw_hi, const double *weights, const double *warm_in,
+                                         const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts,
+                                         double *out, double *traj, int32_t *status, int32_t *iters) {
+  HostWarm hw{warm_in, warm_status, warm_out, ld_warm, {}};
+  const int rc = warm_check(h, opts, &hw.W);
+  if (rc != MPC_OK) return rc;
+  return solve_host<double>(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters, &hw);
 }
 
 extern "C" int mpc_solve_batch_host_f32(MpcHandle *h, int64_t B, int64_t ld, const float *state,

@@ -68,10 +68,20 @@ class BatchedMPC:
         }
         return out
 
-    def solve_torch(self, state, coeffs, yaw_lo, yaw_hi, weights=None, want_traj=False, outputs=None, stream=None):
+    def warm_rows(self):
+        """Rows of this handle's warm buffers: (N-1) * WARM_REC."""
+        return _abi.warm_rows(self.N)
+
+    def solve_torch(self, state, coeffs, yaw_lo, yaw_hi, weights=None, want_traj=False, outputs=None, stream=None,
+                    warm=None, warm_status=None, want_warm=False, warm_opts=None):
         """state [6,B], coeffs [5,B], yaw_lo/hi [B], weights [12,B] or None: CUDA tensors, float64 (float32 for a
         handle created with precision F32).  Asynchronous on ``stream`` (default: torch's current stream).  Returns the
-        dict of output tensors."""
+        dict of output tensors.
+
+        Warm start (opt-in, fp64 handles; mpc_solve_batch_device_warm): ``warm`` [warm_rows(), B] is the "warm" tensor an
+        earlier call returned and ``warm_status`` [B] int32 that call's status (None: every column is valid); with
+        ``want_warm`` (implied by ``warm``) the result holds "warm", the final primal-dual iterate -- written in place when
+        ``outputs`` carries the same tensor.  ``warm_opts``: an MpcWarmOpts (None: the library's defaults)."""
         import torch
         B = state.shape[1]
         dt = self._dtype()
@@ -88,6 +98,22 @@ class BatchedMPC:
             outputs = self.alloc_outputs(B, state.device, want_traj)
         s = stream if stream is not None else torch.cuda.current_stream(state.device)
         traj = outputs.get("traj")
+        if warm is not None or want_warm:
+            rows = self.warm_rows()
+            if warm is not None and (warm.dtype != torch.float64 or not warm.is_cuda or not warm.is_contiguous() or tuple(warm.shape) != (rows, B)):
+                raise ValueError("warm must be a contiguous float64 CUDA tensor of shape (%d, B)" % rows)
+            if warm_status is not None and (warm_status.dtype != torch.int32 or not warm_status.is_cuda or tuple(warm_status.shape) != (B,)):
+                raise ValueError("warm_status must be an int32 CUDA tensor of shape (B,)")
+            if outputs.get("warm") is None:
+                outputs["warm"] = torch.empty((rows, B), dtype=torch.float64, device=state.device)
+            check(library().mpc_solve_batch_device_warm(
+                self._h, B, B, state.data_ptr(), coeffs.data_ptr(), yaw_lo.data_ptr(), yaw_hi.data_ptr(),
+                weights.data_ptr() if weights is not None else None, warm.data_ptr() if warm is not None else None,
+                warm_status.data_ptr() if warm_status is not None else None, outputs["warm"].data_ptr(), B,
+                C.byref(warm_opts) if warm_opts is not None else None, outputs["out"].data_ptr(),
+                traj.data_ptr() if traj is not None else None, outputs["status"].data_ptr(), outputs["iters"].data_ptr(),
+                C.c_void_p(s.cuda_stream)), "mpc_solve_batch_device_warm")
+            return outputs
         fn = library().mpc_solve_batch_device_f32 if self.f32 else library().mpc_solve_batch_device
         check(fn(self._h, B, B, state.data_ptr(), coeffs.data_ptr(), yaw_lo.data_ptr(), yaw_hi.data_ptr(),
                  weights.data_ptr() if weights is not None else None, outputs["out"].data_ptr(),
@@ -153,9 +179,12 @@ class BatchedMPC:
             C.c_void_p(s.cuda_stream)), "mpc_telemetry_batch_device")
         return res
 
-    def rollout_torch(self, state, coeffs, yaw_lo, yaw_hi, steps, weights=None, want_hist=True, stream=None):
+    def rollout_torch(self, state, coeffs, yaw_lo, yaw_hi, steps, weights=None, want_hist=True, stream=None, warm_start=False,
+                      warm_opts=None):
         """Closed loop of src/test.cpp:79-111 for a batch: `steps` cold-started solves, each fed with the previous
-        step-1 state.  `state` [6,B] is advanced in place.  Returns hist [steps,9,B], worst status, summed iters."""
+        step-1 state.  `state` [6,B] is advanced in place.  Returns hist [steps,9,B], worst status, summed iters.
+        ``warm_start``: every step after the first starts from the solution of the step before
+        (mpc_rollout_batch_device_warm; same NLP, fewer iterations)."""
         import torch
         B = state.shape[1]
         dev = state.device
@@ -166,6 +195,13 @@ class BatchedMPC:
                "status": torch.empty((B,), dtype=torch.int32, device=dev),
                "iters": torch.empty((B,), dtype=torch.int32, device=dev)}
         s = stream if stream is not None else torch.cuda.current_stream(dev)
+        if warm_start:
+            check(library().mpc_rollout_batch_device_warm(
+                self._h, B, B, int(steps), state.data_ptr(), coeffs.data_ptr(), yaw_lo.data_ptr(), yaw_hi.data_ptr(),
+                weights.data_ptr() if weights is not None else None, C.byref(warm_opts) if warm_opts is not None else None,
+                res["hist"].data_ptr() if want_hist else None, res["status"].data_ptr(), res["iters"].data_ptr(),
+                C.c_void_p(s.cuda_stream)), "mpc_rollout_batch_device_warm")
+            return res
         check(library().mpc_rollout_batch_device(
             self._h, B, B, int(steps), state.data_ptr(), coeffs.data_ptr(), yaw_lo.data_ptr(), yaw_hi.data_ptr(),
             weights.data_ptr() if weights is not None else None, res["hist"].data_ptr() if want_hist else None,
@@ -189,6 +225,29 @@ class BatchedMPC:
         fn = library().mpc_solve_batch_host_f32 if self.f32 else library().mpc_solve_batch_host
         check(fn(self._h, B, B, p(state), p(coeffs), p(yaw_lo), p(yaw_hi), p(weights), p(out), p(traj), p(status), p(iters)), "mpc_solve_batch_host")
         return {"out": out, "status": status, "iters": iters, "traj": traj}
+
+    def solve_numpy_warm(self, state, coeffs, yaw_lo, yaw_hi, warm=None, warm_status=None, weights=None, want_traj=False, warm_opts=None):
+        """Host arrays through mpc_solve_batch_host_warm (fp64 handles): like solve_numpy, with "warm" [warm_rows(), B] in the
+        result; ``warm`` / ``warm_status``: that array and the status of an earlier call."""
+        f = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+        state, coeffs, yaw_lo, yaw_hi = f(state), f(coeffs), f(yaw_lo), f(yaw_hi)
+        B = state.shape[1]
+        rows = self.warm_rows()
+        if warm is not None:
+            warm = f(warm)
+            assert warm.shape == (rows, B)
+        if warm_status is not None:
+            warm_status = np.ascontiguousarray(warm_status, dtype=np.int32)
+        if weights is not None:
+            weights = f(weights)
+        out = np.empty((_abi.NOUT, B)); status = np.empty(B, dtype=np.int32); iters = np.empty(B, dtype=np.int32)
+        traj = np.empty((2 * self.N, B)) if want_traj else None
+        wout = np.empty((rows, B))
+        p = lambda a: a.ctypes.data if a is not None else None
+        check(library().mpc_solve_batch_host_warm(self._h, B, B, p(state), p(coeffs), p(yaw_lo), p(yaw_hi), p(weights), p(warm), p(warm_status),
+                                                  p(wout), B, C.byref(warm_opts) if warm_opts is not None else None, p(out), p(traj),
+                                                  p(status), p(iters)), "mpc_solve_batch_host_warm")
+        return {"out": out, "status": status, "iters": iters, "traj": traj, "warm": wout}
 
     # -- deferred tails (MpcParams.tail_cut > 0, include/mpc_amd.h) -------------
     def last_batch_id(self):

@@ -341,6 +341,60 @@ int mpc_telemetry_batch_host(MpcHandle *h, int64_t B, int64_t ld, int npts, cons
 int mpc_rollout_batch_device(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
                              const double *yaw_lo, const double *yaw_hi, const double *weights, double *hist,
                              int32_t *status, int32_t *iters, void *stream);
+
+/* ---- warm start (opt-in) -----------------------------------------------------------
+ * In a closed loop the problem of step t+1 is the problem of step t with its horizon moved on by one stage: the previous
+ * solution is almost the answer.  The warm entry points take the final primal-dual iterate of an earlier solve as the INITIAL
+ * ITERATE of this one.  Nothing else changes: the NLP is the reference's, with the branch outcomes of FG_eval and IPOPT's
+ * objective scaling decided at the reference's start point (the state at index 0, zeros elsewhere) exactly as in a cold solve,
+ * so a warm solve converges to the same NLP's solution and the cold solve stays the yardstick.  (The reference cannot warm start:
+ * with a non-zero xi, CppAD would record another tape.  That is deliberately not imitated.)
+ *
+ * The warm buffer, [mpc_warm_rows(N)][ld_warm] doubles, quantity-major like every array here: row k * MPC_WARM_REC + f is field
+ * f of the record of stage k = 0 .. N-2,
+ *   f  0..5   x, y, psi, v, cte, epsi at index k+1      = vars[x_start + k+1] ... vars[epsi_start + k+1] (MPC.cpp:56-63)
+ *   f  6..7   delta, a at index k                       = vars[delta_start + k], vars[a_start + k]
+ *   f  8..13  multipliers of the model rows of index k+1 (constraints[1 + x_start + k+1] ..., MPC.cpp:116-152), the solver's sign
+ *   f 14..17  duals of the lower bounds of psi_{k+1}, v_{k+1}, delta_k, a_k
+ *   f 18..21  duals of their upper bounds
+ * (the variables of index 0 are the given state).  Rules:
+ *   - an instance is warm-started only where warm_status (the status array of the solve that wrote warm_in) says
+ *     MPC_STATUS_SUCCESS; every other instance starts cold, bitwise the cold solve.  warm_status = NULL: every instance is valid;
+ *   - a record that is no iterate of this NLP (not-a-number, a bounded quantity outside its bounds) starts cold as well, and a warm
+ *     attempt that ends in anything but MPC_STATUS_SUCCESS is followed by the COMPLETE cold solve (least-squares multiplier start,
+ *     then the one restart): a warm start never loses an instance, `iters` adds both up;
+ *   - warm_in = NULL is a cold solve that still writes warm_out: how a loop starts, and the way to the full primal-dual solution;
+ *     warm_out = NULL writes nothing; warm_in == warm_out and warm_status == status are allowed (in-place loops);
+ *   - fp64 handles only (MPC_ERR_INVALID otherwise).  MPC_ERR_UNSUPPORTED, never a silent cold solve, on a handle whose solve is
+ *     the two-launch mixed-precision one (set f64_f32_start = 0) and with max_soc > 0 (set max_soc = 0).  No deferred tails, pass
+ *     cuts or take order: one launch per call. */
+#define MPC_WARM_REC 22
+typedef struct MpcWarmOpts {
+  int32_t size;        /* sizeof(MpcWarmOpts) */
+  int32_t shift;       /* 1: record k starts from the previous record k+1 (the last one repeated): the next step of a closed loop;
+                        * 0: as it is: the same problem again, or a loop whose steps are short against the horizon */
+  double mu_init;      /* barrier parameter the warm attempt starts with (a cold solve: 0.1), in [tol / 10, 0.1] */
+  double bound_push;   /* psi, v, delta, a are moved at least this far (relative, like IPOPT's bound_push) inside their bounds */
+  int32_t duals;       /* bound duals: 0 = kept, floored at mu_init / (1e10 slack); 1 = re-derived as mu_init / slack */
+  int32_t reserved;
+} MpcWarmOpts;
+int64_t mpc_warm_rows(int N);                       /* (N-1) * MPC_WARM_REC, or MPC_ERR_INVALID */
+int mpc_warm_opts_default(MpcWarmOpts *o);
+/* opts = NULL: the defaults */
+int mpc_solve_batch_device_warm(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
+                                const double *yaw_lo, const double *yaw_hi, const double *weights, const double *warm_in,
+                                const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts,
+                                double *out, double *traj, int32_t *status, int32_t *iters, void *stream);
+int mpc_solve_batch_host_warm(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
+                              const double *yaw_lo, const double *yaw_hi, const double *weights, const double *warm_in,
+                              const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts,
+                              double *out, double *traj, int32_t *status, int32_t *iters);
+/* The rollout above with step 1 cold and every later step warm-started from the step before (cars whose previous step did not
+ * succeed start cold).  The warm buffer lives in the handle: mpc_warm_rows(N) * 8 bytes per instance of the handle's capacity,
+ * allocated by the first call. */
+int mpc_rollout_batch_device_warm(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
+                                  const double *yaw_lo, const double *yaw_hi, const double *weights, const MpcWarmOpts *opts,
+                                  double *hist, int32_t *status, int32_t *iters, void *stream);
 /* ---- the wire side of the handler (src/mpc_main.cpp:26-36, 81-222, DATA.md:5-16) --------
  * Everything between the bytes of a simulator frame and the bytes of the reply; the WebSocket server itself is out of
  * scope.  See csrc/mpc_wire.cpp. */

@@ -264,10 +264,15 @@ class MPC {                                                            /* MPC.h:
   int handleN = 0, handleFp32Start = 0;
   Vehicle vehicle;
   RoadGeometry roadGeometry;
+  /* warm start of solve() (setWarmStart): the previous solve's final iterate and its status */
+  bool warmStart = false, haveWarm = false;
+  std::vector<double> warmBuf;
+  int32_t warmStatus = 0, lastIters = 0;
 
   void ensure(int64_t B) {
     const MpcParams p = Config::snapshot();
     if (handle && (B > capacity || p.N != handleN || p.f64_f32_start != handleFp32Start)) { mpc_destroy(handle); handle = nullptr; }
+    if (p.N != handleN) haveWarm = false;
     if (!handle) {
       capacity = B < 1 ? 1 : B; handleN = p.N; handleFp32Start = p.f64_f32_start;
       int rc = mpc_create(&p, -1, capacity, &handle);
@@ -282,6 +287,19 @@ class MPC {                                                            /* MPC.h:
   virtual ~MPC() { if (handle) mpc_destroy(handle); }
 
   RoadGeometry &road() { return roadGeometry; }
+
+  /* New: closed loops.  With setWarmStart(true), solve() starts from the solution of the solve() before it, moved on by one
+   * stage (mpc_solve_batch_host_warm with the library's default MpcWarmOpts): the same NLP, so the same answer within the solver's
+   * tolerance, in about half the iterations when the states follow each other as in src/test.cpp:79-111.  A previous solve
+   * that did not succeed, and a warm attempt that does not, fall back to the cold solve inside the library.  Off by default (every
+   * solve then starts at the reference's zero start point).  Switching it on, a change of Config::N and resetWarmStart() forget the
+   * stored solution.  Needs a handle whose solve is one launch: Config::fp32Start = 0 at horizons of MPC_F32_START_AUTO_N or
+   * more, Config::maxSoc = 0; the library refuses otherwise and solve() throws.  run() always starts cold (it re-fits the road in
+   * a new vehicle frame every call). */
+  void setWarmStart(bool on) { if (on != warmStart) haveWarm = false; warmStart = on; }
+  bool getWarmStart() const { return warmStart; }
+  void resetWarmStart() { haveWarm = false; }
+  int lastIterations() const { return (int)lastIters; }   /* interior-point iterations of the latest solve() */
 
   /* MPC::solve, MPC.h:42-43 / MPC.cpp:183-325.  `state` = {x,y,psi,v,cte,epsi}; target_velocity and dir
    * are accepted and ignored exactly as FG_eval ignores them.  Returns
@@ -299,8 +317,16 @@ class MPC {                                                            /* MPC.h:
     std::vector<double> traj(2 * N);
     int32_t status = 0, iters = 0;
     const double ylo = Config::yawLow, yhi = Config::yawHigh;
-    int rc = mpc_solve_batch_host(handle, 1, 1, st, cf, &ylo, &yhi, NULL, out, traj.data(), &status, &iters);
+    int rc;
+    if (warmStart) {
+      const int64_t rows = mpc_warm_rows(N);
+      if ((int64_t)warmBuf.size() != rows) { warmBuf.assign((size_t)rows, 0.0); haveWarm = false; }
+      rc = mpc_solve_batch_host_warm(handle, 1, 1, st, cf, &ylo, &yhi, NULL, haveWarm ? warmBuf.data() : NULL, haveWarm ? &warmStatus : NULL,
+                                     warmBuf.data(), 1, NULL, out, traj.data(), &status, &iters);
+      haveWarm = rc == MPC_OK; warmStatus = status;
+    } else rc = mpc_solve_batch_host(handle, 1, 1, st, cf, &ylo, &yhi, NULL, out, traj.data(), &status, &iters);
     if (rc != MPC_OK) throw std::string("mpc_solve_batch_host failed: ") + mpc_last_error();
+    lastIters = iters;
     if (status != MPC_STATUS_SUCCESS) {
 #ifdef EXIT_ON_IPOPT_FAILURE
       throw std::string("Ipopt failed with ") + std::to_string(status);
