@@ -1041,6 +1041,10 @@ __global__ void mpc_debug_math_kernel(int64_t n, const double *x, double *sn, do
 
 }  // namespace
 
+/* ---- host side from here on ---------------------------------------------------------------------------------------------------- */
+#include <optional>
+#include <type_traits>
+
 struct MpcHandle {
   MpcParams params;
   int device = 0;
@@ -1063,8 +1067,8 @@ struct MpcHandle {
   hipEvent_t ev_stats = nullptr;
   bool have_stats = false;
   double *d_run = nullptr;    /* run(): pre[15] rows */
-  double *d_run9 = nullptr;   /* run(): solve()'s 9 rows, caller's leading dimension */
-  int64_t run9_ld = 0;
+  double *d_run9 = nullptr;   /* run(), rollout: solve()'s 9 rows, caller's leading dimension (grown on demand) */
+  size_t run9_bytes = 0;
   int32_t *d_status = nullptr, *d_iters = nullptr, *d_rstat = nullptr, *d_counter = nullptr;
   int64_t counter_seq = 0;    /* solve calls that used a counter block so far */
   /* statistics are gathered when mpc_get_stats asks for them (a kernel per batch on the launch stream costs the serving loop a
@@ -1168,6 +1172,36 @@ struct MpcHandle {
   bool timed = false;
 };
 
+#define MPC_TRY(expr)                                                                    \
+  do {                                                                                   \
+    const int rc_ = (expr);                                                              \
+    if (rc_ != MPC_OK) return rc_;                                                       \
+  } while (0)
+
+/* the handle's lazy device allocations: made by the first call that needs them, kept (mpc_destroy frees whatever exists) */
+template <class T>
+static int ensure_dev(T **p, size_t bytes) {
+  if (!*p) MPC_HIP_CHECK(hipMalloc((void **)p, bytes));
+  return MPC_OK;
+}
+/* ... and the ones that follow the caller's sizes: *have bytes now, at least `need` afterwards */
+template <class T>
+static int grow_dev(T **p, size_t *have, size_t need) {
+  if (*p && *have >= need) return MPC_OK;
+  if (*p) MPC_HIP_CHECK(hipFree(*p));
+  *p = nullptr; *have = 0;
+  MPC_HIP_CHECK(hipMalloc((void **)p, need));
+  *have = need;
+  return MPC_OK;
+}
+
+/* what the entry points with a batch of their own check first (the solve entry points: solve_begin) */
+static int check_batch(const MpcHandle *h, int64_t B, int64_t ld) {
+  if (!h) { g_last_error = "NULL handle"; return MPC_ERR_INVALID; }
+  if (B < 0 || ld < B || B > h->max_batch) { g_last_error = "bad B/ld"; return MPC_ERR_INVALID; }
+  return MPC_OK;
+}
+
 static void set_wave_limit(MpcHandle *h, const MpcParams *p) {
   h->wave_max_batch = p->wave_max_batch == 0 ? 1024 : (p->wave_max_batch < 0 ? 0 : p->wave_max_batch);
   if (const char *e = getenv("MPC_WAVE_MAX_BATCH")) h->wave_max_batch = atoll(e);      /* (A/B measurements) */
@@ -1249,18 +1283,16 @@ extern "C" int mpc_create(const MpcParams *p, int device, int64_t max_batch, Mpc
   h->staging = true;
   if (const char *e = getenv("MPC_STAGING")) h->staging = atoi(e) != 0;
   const bool f32 = p->precision == MPC_PRECISION_F32;
-  if (f32) MPC_CREATE_CHECK(hipFuncSetAttribute((const void *)mpc_solve_kernel<true, float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
-  else MPC_CREATE_CHECK(hipFuncSetAttribute((const void *)mpc_solve_kernel<true, double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
+  h->mixed = wants_mixed(p, max_batch);
+  /* the staging builds this handle may launch: its own precision's, and the phases of a mixed-precision solve */
+  const void *const staged[] = {f32 ? (const void *)mpc_solve_kernel<true, float> : (const void *)mpc_solve_kernel<true, double>,
+                                (const void *)mpc_solve_kernel<true, double, float, float>, (const void *)mpc_solve_kernel<true, float, double, double>,
+                                (const void *)mpc_solve_kernel<true, double, double, float>};
+  for (int q = 0; q < (h->mixed ? 4 : 1); q++)
+    MPC_CREATE_CHECK(hipFuncSetAttribute(staged[q], hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
   h->ws_stride = mpc::workspace_fields_per_instance(p->N, f32, p->initial_state_rows != 0) * 64;   /* reals per wavefront tile */
   h->ws_stride_f32 = mpc::workspace_fields_per_instance(p->N, true, p->initial_state_rows != 0) * 64;
   h->ws_stride_f64 = mpc::workspace_fields_per_instance(p->N, false, p->initial_state_rows != 0) * 64;
-  h->mixed = wants_mixed(p, max_batch);
-  if (h->mixed) {
-    MPC_CREATE_CHECK(hipFuncSetAttribute((const void *)mpc_solve_kernel<true, double, float, float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
-    MPC_CREATE_CHECK(hipFuncSetAttribute((const void *)mpc_solve_kernel<true, float, double, double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
-    MPC_CREATE_CHECK(hipFuncSetAttribute((const void *)mpc_solve_kernel<true, double, double, float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
-    MPC_CREATE_CHECK(hipFuncSetAttribute((const void *)mpc_solve_kernel<true, float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
-  }
   /* Small launches run ONE INSTANCE PER WAVEFRONT, or per 16 / 32 of its lanes (mpc_solve_wave_kernel): the lane kernel puts 64
    * instances into a wave, which is bound by the instructions it issues -- one MPC::solve() 0.68 ms; with the sweeps shared
    * between the lanes 0.30 ms, bitwise the same results (MpcParams.wave_max_batch: default 1 024 instances). */
@@ -1384,9 +1416,7 @@ static int record_stats(MpcHandle *h, int64_t B, const int32_t *status, const in
 
 /* The SOC records of `waves` wavefront tiles (fp64 solver), allocated once: N cannot change on a live handle */
 static int soc_alloc(MpcHandle *h, void **buf, int64_t waves) {
-  if (*buf) return MPC_OK;
-  MPC_HIP_CHECK(hipMalloc(buf, sizeof(double) * (size_t)waves * (size_t)mpc::soc_fields_per_instance(h->params.N) * 64u));
-  return MPC_OK;
+  return ensure_dev(buf, sizeof(double) * (size_t)waves * (size_t)mpc::soc_fields_per_instance(h->params.N) * 64u);
 }
 
 /* ---- deferred tails: queues, tail slices, the pump, waiting for a batch -------------------------------------------------
@@ -1401,9 +1431,8 @@ static int tail_alloc_queue(MpcHandle *h, MpcTailQ &Q, int64_t cap, int32_t *cou
   const size_t real_bytes = f32 ? sizeof(float) : sizeof(double);
   const size_t it_sz = f32 ? (size_t)mpc::Fields<float>::IT_SZ : (size_t)mpc::Fields<double>::IT_SZ;
   Q.cap = (int32_t)cap; Q.count = count;
-  if (!Q.park) MPC_HIP_CHECK(hipMalloc((void **)&Q.park, sizeof(double) * (size_t)kTailRows * (size_t)cap));
-  if (!Q.iter) MPC_HIP_CHECK(hipMalloc(&Q.iter, (size_t)(cap / 64) * (size_t)(h->params.N - 1) * it_sz * 64 * real_bytes));
-  return MPC_OK;
+  MPC_TRY(ensure_dev(&Q.park, sizeof(double) * (size_t)kTailRows * (size_t)cap));
+  return ensure_dev(&Q.iter, (size_t)(cap / 64) * (size_t)(h->params.N - 1) * it_sz * 64 * real_bytes);
 }
 
 static int tail_prepare(MpcHandle *h) {
@@ -1443,24 +1472,20 @@ static int tail_prepare(MpcHandle *h) {
    * below (a plain hipMemset runs on the null stream, which neither the caller's stream nor the tail stream waits for -- on a
    * device that other handles keep full its fill kernel can start after the launch that follows this call) */
   const int n_counts = kFreshRing + 2 + 6 * kSliceRing;
-  if (!h->d_tcount) MPC_HIP_CHECK(hipMalloc((void **)&h->d_tcount, sizeof(int32_t) * n_counts));
+  MPC_TRY(ensure_dev(&h->d_tcount, sizeof(int32_t) * n_counts));
   MPC_HIP_CHECK(hipMemsetAsync(h->d_tcount, 0, sizeof(int32_t) * n_counts, h->tail_stream));
-  if (!h->d_remaining) MPC_HIP_CHECK(hipMalloc((void **)&h->d_remaining, sizeof(int32_t) * kTailMaxRing));
+  MPC_TRY(ensure_dev(&h->d_remaining, sizeof(int32_t) * kTailMaxRing));
   MPC_HIP_CHECK(hipMemsetAsync(h->d_remaining, 0, sizeof(int32_t) * kTailMaxRing, h->tail_stream));
   if (!h->h_final) MPC_HIP_CHECK(hipHostMalloc((void **)&h->h_final, sizeof(long long) * kTailMaxRing, hipHostMallocDefault));
   if (!h->h_res) MPC_HIP_CHECK(hipHostMalloc((void **)&h->h_res, sizeof(MpcHandle::SliceRes) * kSliceRing, hipHostMallocDefault));
   memset(h->h_final, 0, sizeof(long long) * kTailMaxRing);
   memset(h->h_res, 0, sizeof(MpcHandle::SliceRes) * kSliceRing);
   for (int q = 0; q < kFreshRing; q++) {
-    const int rc = tail_alloc_queue(h, h->fq_dev[q], h->tail_cap, h->d_tcount + q);
-    if (rc != MPC_OK) return rc;
+    MPC_TRY(tail_alloc_queue(h, h->fq_dev[q], h->tail_cap, h->d_tcount + q));
     if (!h->fq[q].bulk) MPC_HIP_CHECK(hipEventCreateWithFlags(&h->fq[q].bulk, hipEventDisableTiming));
   }
-  for (int q = 0; q < 2; q++) {
-    const int rc = tail_alloc_queue(h, h->surv_dev[q], h->surv_cap, h->d_tcount + kFreshRing + q);
-    if (rc != MPC_OK) return rc;
-  }
-  if (!h->tail_ws) MPC_HIP_CHECK(hipMalloc((void **)&h->tail_ws, (size_t)tail_stride * (size_t)h->tail_waves * real_bytes));
+  for (int q = 0; q < 2; q++) MPC_TRY(tail_alloc_queue(h, h->surv_dev[q], h->surv_cap, h->d_tcount + kFreshRing + q));
+  MPC_TRY(ensure_dev(&h->tail_ws, (size_t)tail_stride * (size_t)h->tail_waves * real_bytes));
   for (int q = 0; q < kSliceRing; q++)
     if (!h->slice_ev[q]) MPC_HIP_CHECK(hipEventCreateWithFlags(&h->slice_ev[q], hipEventDisableTiming));
   MPC_HIP_CHECK(hipStreamSynchronize(h->tail_stream));
@@ -1535,18 +1560,17 @@ static int tail_launch_slice(MpcHandle *h, bool force) {
   const bool f32 = !h->tail_double, io32 = h->params.precision == MPC_PRECISION_F32;
   const int64_t tail_stride = f32 ? h->ws_stride_f32 : h->ws_stride_f64;
   const bool soc = !f32 && h->params.max_soc > 0;     /* (the slice solves under the parameters it is launched with) */
-  if (soc) { const int rc = soc_alloc(h, &h->soc_tail, h->tail_waves); if (rc != MPC_OK) return rc; }
+  if (soc) MPC_TRY(soc_alloc(h, &h->soc_tail, h->tail_waves));
   A.soc_ws = h->soc_tail;
-  if (soc && io32)
-    hipLaunchKernelGGL((mpc_tail_slice_kernel<true, double, float, true>), dim3((unsigned)waves), dim3(kBlock), staging_lds_bytes<double>(), ts, h->params, A, (double *)h->tail_ws, tail_stride);
-  else if (soc)
-    hipLaunchKernelGGL((mpc_tail_slice_kernel<true, double, double, true>), dim3((unsigned)waves), dim3(kBlock), staging_lds_bytes<double>(), ts, h->params, A, (double *)h->tail_ws, tail_stride);
-  else if (f32)
-    hipLaunchKernelGGL((mpc_tail_slice_kernel<true, float>), dim3((unsigned)waves), dim3(kBlock), staging_lds_bytes<float>(), ts, h->params, A, (float *)h->tail_ws, tail_stride);
-  else if (io32)       /* the fp64 phase of a mixed-precision solve: fp32 arrays at the ABI */
-    hipLaunchKernelGGL((mpc_tail_slice_kernel<true, double, float>), dim3((unsigned)waves), dim3(kBlock), staging_lds_bytes<double>(), ts, h->params, A, (double *)h->tail_ws, tail_stride);
-  else
-    hipLaunchKernelGGL((mpc_tail_slice_kernel<true, double>), dim3((unsigned)waves), dim3(kBlock), staging_lds_bytes<double>(), ts, h->params, A, (double *)h->tail_ws, tail_stride);
+  auto go = [&](auto kernel, auto r) {       /* (r: a value of the solver's reals) */
+    using R = decltype(r);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)waves), dim3(kBlock), staging_lds_bytes<R>(), ts, h->params, A, (R *)h->tail_ws, tail_stride);
+  };
+  if (soc && io32) go(mpc_tail_slice_kernel<true, double, float, true>, double{});
+  else if (soc) go(mpc_tail_slice_kernel<true, double, double, true>, double{});
+  else if (f32) go(mpc_tail_slice_kernel<true, float>, float{});
+  else if (io32) go(mpc_tail_slice_kernel<true, double, float>, double{});      /* the fp64 phase of a mixed-precision solve: fp32 arrays at the ABI */
+  else go(mpc_tail_slice_kernel<true, double>, double{});
   MPC_HIP_CHECK(hipGetLastError());
   /* (what the pump reads when the slice has completed -- the survivors it left, what each absorbed batch handed over, the final
    * flags -- the slice's last wave writes into pinned host memory itself) */
@@ -1797,84 +1821,206 @@ extern "C" int mpc_tail_pending(MpcHandle *h, int64_t batch_id, int64_t *n) {
   return MPC_OK;
 }
 
+/* ---- the solve call: one description of it, one way to the device ----------------------------------------------------------
+ * What a solve call works on, all arrays on the device: ld = leading dimension of the inputs, ldo = of out / traj.  Host side
+ * only: launch_kernel is the one place that spells it out as kernel arguments. */
+template <class R>
+struct SolveIO {
+  int64_t B, ld, ldo;
+  const R *state, *coeffs, *yaw_lo, *yaw_hi, *weights;
+  R *out, *traj;
+  int32_t *status, *iters;
+};
+/* ... and what a warm call brings on top: the warm buffers (see MpcPhaseWarm) and the options in effect (warm_check) */
+struct WarmIO {
+  const double *warm_in; const int32_t *warm_status; double *warm_out; int64_t ld_warm; MpcWarmOpts opts;
+};
+/* ... and where a deferring launch hands its stragglers: its batch's slot of the ring and its fresh queue */
+struct TailPlace {
+  bool defer = false;
+  int slot = 0, fq = 0;
+};
+struct CounterBlocks { int32_t *cb, *zero_next; };
+
+/* `extra`: what the kernel takes behind the solve arguments */
+template <class K, class R, class... Extra>
+static int launch_kernel(K kernel, unsigned grid, size_t lds, hipStream_t s, const MpcHandle *h, const SolveIO<R> &io, Extra... extra) {
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, h->params, io.B, io.ld, io.ldo, io.state, io.coeffs, io.yaw_lo, io.yaw_hi,
+                     io.weights, io.out, io.traj, io.status, io.iters, extra...);
+  MPC_HIP_CHECK(hipGetLastError());
+  return MPC_OK;
+}
+
+template <int V> using Int = std::integral_constant<int, V>;
+/* f(std::true_type) or f(std::false_type): a run-time switch as a template argument */
+template <class F>
+static int with_bool(bool b, F f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+/* Every phase's switches are off unless it sets them; the hand-over and compaction policies are the same for all */
+static MpcPhase phase_defaults(const MpcHandle *h, int64_t B) {
+  MpcPhase T;
+  memset(&T, 0, sizeof(T));
+  T.ld_park = h->io_stride;
+  T.refill_min = kRefillMin; T.refill_wait = kRefillWait;
+  T.compact_gap = B >= h->compact_min_batch ? h->compact_gap : 0; T.compact_cooldown = kCompactCooldown;
+  return T;
+}
+
+/* The counter block of a solve call that takes its work from counters (the wave path does not, and leaves the ring alone): call n
+ * uses block n % kCounterRing, and its first launch zeroes the block half a ring ahead for a later call */
+static CounterBlocks take_counters(MpcHandle *h) {
+  const int64_t n = h->counter_seq++;
+  return {h->d_counter + (n % kCounterRing) * kCounterInts, h->d_counter + ((n + kCounterRing / 2) % kCounterRing) * kCounterInts};
+}
+
+/* Lanes per instance on the wave path: a lane per stage -- 16 up to N = 17 (four instances per wavefront), 32 up to N = 33, else
+ * the whole wave; a launch of a few instances takes the whole wave anyway (its cross-lane reads are v_readlane instead of
+ * ds_bpermute).  MPC_WAVE_LPI in the environment overrides both (measurement aid, read per call). */
+static int wave_lpi(const MpcHandle *h, int64_t B) {
+  const int stages = h->params.N - 1;
+  int lpi = stages <= 16 ? 16 : (stages <= 32 ? 32 : 64);
+  if (B <= kWaveWholeMax) lpi = 64;
+  if (const char *e = getenv("MPC_WAVE_LPI")) lpi = atoi(e) == 16 ? 16 : (atoi(e) == 32 ? 32 : 64);
+  if (lpi < stages) lpi = 64;
+  return lpi;
+}
+
+/* The wave path: 64 / LPI instances per wavefront, each with its stage records in LDS (the SOC build: and its SOC records behind
+ * them).  Plain, SOC (fp64, max_soc > 0) or warm (fp64). */
+template <class R>
+static int launch_wave(MpcHandle *h, const SolveIO<R> &io, hipStream_t s, bool soc, const WarmIO *warm) {
+  const size_t per = (size_t)mpc::workspace_fields_per_instance(h->params.N, sizeof(R) == 4, h->params.initial_state_rows != 0) * sizeof(R);
+  auto go = [&](auto lpi) {
+    constexpr int LPI = decltype(lpi)::value, G = 64 / LPI;
+    const unsigned grid = (unsigned)((io.B + G - 1) / G);
+    if constexpr (sizeof(R) == 8) {
+      if (warm)
+        return launch_kernel(mpc_solve_wave_warm_kernel<R, LPI>, grid, G * per, s, h, io, warm->warm_in, warm->warm_status, warm->warm_out,
+                             warm->ld_warm, warm->opts);
+      if (soc)
+        return launch_kernel(mpc_solve_wave_kernel<R, LPI, true>, grid, G * (per + (size_t)mpc::soc_fields_per_instance(h->params.N) * sizeof(R)), s, h, io);
+    }
+    return launch_kernel(mpc_solve_wave_kernel<R, LPI>, grid, G * per, s, h, io);
+  };
+  switch (wave_lpi(h, io.B)) {
+    case 16: return go(Int<16>{});
+    case 32: return go(Int<32>{});
+    default: return go(Int<64>{});
+  }
+}
+
+/* The lane kernel (an instance per lane; `ws`: the workspace of the phase).  single: the build that MPC_STAGING, max_soc on an fp64
+ * handle and a warm call select.  The two phases of a mixed-precision solve are builds of their own: the fp32 solver, and the fp64
+ * solver that takes its iterates from fp32 records -- whatever RIO, the type at the ABI, is. */
+enum class LaneBuild { single, mixed_f32, mixed_f64 };
+template <class RIO>
+static int launch_lanes(MpcHandle *h, LaneBuild build, const SolveIO<RIO> &io, hipStream_t s, void *ws, bool soc, const MpcPhase &T,
+                        const WarmIO *warm = nullptr) {
+  const unsigned grid = (unsigned)((io.B + kBlock - 1) / kBlock);
+  /* (r, rsrc: values of the solver's reals and of the reals its resumed iterates come in) */
+  auto go = [&](auto staging, auto r, auto rsrc, auto soc_build, auto warm_build, int64_t tile_reals, const auto &phase) {
+    using R = decltype(r);
+    constexpr bool STAGING = decltype(staging)::value;
+    return launch_kernel(mpc_solve_kernel<STAGING, R, RIO, decltype(rsrc), decltype(soc_build)::value, decltype(warm_build)::value>, grid,
+                         STAGING ? staging_lds_bytes<R>() : 0, s, h, io, (R *)ws, tile_reals, phase);
+  };
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  if (build == LaneBuild::mixed_f32) return go(yes, float{}, RIO{}, no, no, h->ws_stride_f32, T);
+  if (build == LaneBuild::mixed_f64) return with_bool(soc, [&](auto soc_build) { return go(yes, double{}, float{}, soc_build, no, h->ws_stride_f64, T); });
+  return with_bool(h->staging, [&](auto staging) {
+    if constexpr (sizeof(RIO) == 8) {
+      if (warm) return go(staging, RIO{}, RIO{}, no, yes, h->ws_stride, MpcPhaseWarm{T, warm->warm_in, warm->warm_status, warm->warm_out, warm->ld_warm, warm->opts});
+      if (soc) return go(staging, RIO{}, RIO{}, yes, no, h->ws_stride, T);
+    }
+    return go(staging, RIO{}, RIO{}, no, no, h->ws_stride, T);
+  });
+}
+
+/* the tail fields of a phase that may hand instances over (defer = false: the batch's id only) */
+static void tail_fields(const MpcHandle *h, const TailPlace &tp, MpcPhase &T) {
+  T.tail_cut = tp.defer ? (h->params.tail_cut > 0 ? h->params.tail_cut : h->auto_cut) : 0; T.t_slot = tp.slot; T.t_batch = h->batch_seq;
+  if (tp.defer) { T.tq = h->fq_dev[tp.fq]; T.tail_few = h->tail_few; T.tail_few_from = kTailFewFrom; }
+}
+
 /* Mixed precision across phases: phase 0 = the fp32 solver on the handle's fp32 workspace, parking every instance at
  * MPC_PROMOTE; phase 1 = the fp64 solver resuming all of them on the fp64 workspace.  RIO is the handle's own precision
  * (the type at the ABI).  Instances the fp32 phase finishes itself (rejected at set-up, not-a-number, iteration cap) are
  * final after phase 0. */
 template <class RIO>
-static int launch_mixed(MpcHandle *h, int64_t B, int64_t ld, int64_t ldo, const RIO *state, const RIO *coeffs, const RIO *yaw_lo,
-                        const RIO *yaw_hi, const RIO *weights, RIO *out, RIO *traj, int32_t *status, int32_t *iters, hipStream_t s,
-                        const MpcPhase &tail, int32_t *cb, int32_t *zero_next) {
-  const int64_t tiles = h->io_stride / 64;
+static int launch_mixed(MpcHandle *h, const SolveIO<RIO> &io, hipStream_t s, const TailPlace &tp) {
+  const int64_t S = h->io_stride, tiles = S / 64, B = io.B;
+  const bool soc = h->params.max_soc > 0;     /* the fp64 phase honours MpcParams.max_soc (the fp32 phase never corrects) */
   /* h->ws holds the handle's own layout; the phases need one workspace of each (each allocation on its own: a failure
    * leaves the handle usable for a retry, and mpc_destroy frees whatever exists) */
-  if (!h->ws2) {
-    const size_t other = sizeof(RIO) == 4 ? (size_t)h->ws_stride_f64 * tiles * sizeof(double) : (size_t)h->ws_stride_f32 * tiles * sizeof(float);
-    MPC_HIP_CHECK(hipMalloc((void **)&h->ws2, other));
-  }
-  if (!h->d_park) MPC_HIP_CHECK(hipMalloc((void **)&h->d_park, sizeof(double) * 2 * kParkRows * h->io_stride));
-  if (!h->d_list) MPC_HIP_CHECK(hipMalloc((void **)&h->d_list, sizeof(int32_t) * 4 * h->io_stride));
-  if (!h->d_piter && h->promote_buffer)
-    MPC_HIP_CHECK(hipMalloc(&h->d_piter, sizeof(float) * (size_t)h->io_stride * (size_t)(h->params.N - 1) * mpc::Fields<float>::IT_SZ));
-  float *ws32 = sizeof(RIO) == 4 ? (float *)h->ws : (float *)h->ws2;
-  double *ws64 = sizeof(RIO) == 4 ? (double *)h->ws2 : (double *)h->ws;
-  int32_t *it_out = iters ? iters : h->d_iters;
+  MPC_TRY(ensure_dev(&h->ws2, sizeof(RIO) == 4 ? (size_t)h->ws_stride_f64 * tiles * sizeof(double) : (size_t)h->ws_stride_f32 * tiles * sizeof(float)));
+  MPC_TRY(ensure_dev(&h->d_park, sizeof(double) * 2 * kParkRows * S));
+  MPC_TRY(ensure_dev(&h->d_list, sizeof(int32_t) * 4 * S));
+  if (h->promote_buffer) MPC_TRY(ensure_dev(&h->d_piter, sizeof(float) * (size_t)S * (size_t)(h->params.N - 1) * mpc::Fields<float>::IT_SZ));
+  if (soc) MPC_TRY(soc_alloc(h, &h->soc_ws, tiles));
+  void *ws32 = sizeof(RIO) == 4 ? h->ws : h->ws2, *ws64 = sizeof(RIO) == 4 ? h->ws2 : h->ws;
+  const CounterBlocks C = take_counters(h);
   MPC_HIP_CHECK(hipEventRecord(h->ev0, s));
-  const unsigned waves = (unsigned)((B + kBlock - 1) / kBlock);
-  MpcPhase T;
-  memset(&T, 0, sizeof(T));
-  T.take = cb; T.n_out = cb + 1; T.zero_next = zero_next;
-  T.out_inst = h->d_list; T.out_src = h->d_list + h->io_stride; T.out_park = h->d_park; T.ld_park = h->io_stride;
-  T.refill_min = kRefillMin; T.refill_wait = kRefillWait;
+  MpcPhase T = phase_defaults(h, B);
+  T.take = C.cb; T.n_out = C.cb + 1; T.zero_next = C.zero_next;
+  T.out_inst = h->d_list; T.out_src = h->d_list + S; T.out_park = h->d_park;
   T.promote_out = 1;
   T.p_iter = h->promote_buffer ? h->d_piter : nullptr;
-  T.compact_gap = (T.p_iter && B >= h->compact_min_batch) ? h->compact_gap : 0; T.compact_cooldown = kCompactCooldown;
-  hipLaunchKernelGGL((mpc_solve_kernel<true, float, RIO, RIO>), dim3(waves), dim3(kBlock), staging_lds_bytes<float>(), s, h->params, B, ld, ldo, state,
-                     coeffs, yaw_lo, yaw_hi, weights, out, traj, status, it_out, ws32, h->ws_stride_f32, T);
-  MPC_HIP_CHECK(hipGetLastError());
-  MpcPhase U;
-  memset(&U, 0, sizeof(U));
-  U.take = cb + 2; U.n_out = cb + 3; U.n_in = cb + 1;
-  U.in_inst = h->d_list; U.in_src = h->d_list + h->io_stride; U.in_park = h->d_park; U.ld_park = h->io_stride;
-  U.out_inst = h->d_list + 2 * h->io_stride; U.out_src = h->d_list + 3 * h->io_stride; U.out_park = h->d_park + (int64_t)kParkRows * h->io_stride;
+  if (!T.p_iter) T.compact_gap = 0;      /* (without the buffer a handed-over instance keeps its iterate in its column) */
+  MPC_TRY(launch_lanes(h, LaneBuild::mixed_f32, io, s, ws32, false, T));
+  MpcPhase U = phase_defaults(h, B);
+  U.take = C.cb + 2; U.n_out = C.cb + 3; U.n_in = C.cb + 1;
+  U.in_inst = h->d_list; U.in_src = h->d_list + S; U.in_park = h->d_park;
+  U.out_inst = h->d_list + 2 * S; U.out_src = h->d_list + 3 * S; U.out_park = h->d_park + (int64_t)kParkRows * S;
   U.src_ws = ws32; U.src_tile_reals = h->ws_stride_f32;
   U.resume = 1; U.promote_in = 1;
-  U.p_iter = h->promote_buffer ? h->d_piter : nullptr;
-  U.refill_min = kRefillMin; U.refill_wait = kRefillWait;
-  U.compact_gap = B >= h->compact_min_batch ? h->compact_gap : 0;
-  U.compact_cooldown = kCompactCooldown;
+  U.p_iter = T.p_iter;
   /* deferred tails: the fp64 phase hands its stragglers over (the fp32 phase's chains end at kPromoteIterCap anyway) */
   /* (no early hand-over of a wave's last lanes here: the waves of this phase are partly filled by construction) */
-  U.tail_cut = tail.tail_cut; U.t_slot = tail.t_slot; U.t_batch = tail.t_batch; U.tq = tail.tq; U.tail_few = 0; U.tail_few_from = tail.tail_few_from;
-  if (h->params.max_soc > 0) {
-    /* the fp64 phase honours MpcParams.max_soc (the fp32 phase never corrects) */
-    const int rc = soc_alloc(h, &h->soc_ws, tiles);
-    if (rc != MPC_OK) return rc;
-    U.soc_ws = h->soc_ws;
-    hipLaunchKernelGGL((mpc_solve_kernel<true, double, RIO, float, true>), dim3(waves), dim3(kBlock), staging_lds_bytes<double>(), s, h->params, B, ld, ldo, state,
-                       coeffs, yaw_lo, yaw_hi, weights, out, traj, status, it_out, ws64, h->ws_stride_f64, U);
-  } else
-    hipLaunchKernelGGL((mpc_solve_kernel<true, double, RIO, float>), dim3(waves), dim3(kBlock), staging_lds_bytes<double>(), s, h->params, B, ld, ldo, state,
-                       coeffs, yaw_lo, yaw_hi, weights, out, traj, status, it_out, ws64, h->ws_stride_f64, U);
-  MPC_HIP_CHECK(hipGetLastError());
-  MPC_HIP_CHECK(hipEventRecord(h->ev1, s));
-  h->timed = true;
+  tail_fields(h, tp, U); U.tail_few = 0;
+  if (soc) U.soc_ws = h->soc_ws;
+  return launch_lanes(h, LaneBuild::mixed_f64, io, s, ws64, soc, U);
+}
+
+/* A launch that wants to defer: brings the tail machinery up, turns the pump and claims the batch's slot and fresh queue -- or
+ * decides against (tp.defer = false) */
+static int tail_claim(MpcHandle *h, hipStream_t s, TailPlace &tp) {
+  MPC_TRY(tail_prepare(h));
+  MPC_TRY(tail_pump(h, false));
+  /* the survivors' list is filling up (stragglers arrive faster than the slices finish them): this batch keeps its own */
+  if (2 * h->surv_last > h->surv_cap) {
+    tp.defer = false; ++h->n_throttled;
+    if (h->params.tail_cut < 0 && h->auto_cut < h->auto_base + 40) h->auto_cut += 2;
+    return MPC_OK;
+  }
+  tp.slot = (int)(h->n_deferred % h->tail_ring);
+  tp.fq = (int)(h->n_deferred % kFreshRing);
+  /* the slot is taken again: the batch it held must be final (only if the ring is shorter than the stragglers' latency) */
+  for (int guard = 0; h->tslot[tp.slot].batch_id != 0 && !h->tslot[tp.slot].final_; guard++) {
+    if (guard > (1 << 22)) { g_last_error = "deferred tails: no progress"; return MPC_ERR_HIP; }
+    MPC_TRY(tail_pump(h, true));
+  }
+  /* the fresh queue is taken again: the slice that absorbed its previous batch must have read it */
+  MpcHandle::FreshQ &F = h->fq[tp.fq];
+  if (F.state == 1) MPC_TRY(tail_launch_slice(h, true));
+  /* (its count is zero again: the slice's last wave has reset it) */
+  if (F.state == 2) MPC_HIP_CHECK(hipStreamWaitEvent(s, h->slice_ev[F.slice % kSliceRing], 0));
   return MPC_OK;
 }
 
-/* the launch; ld = leading dimension of the inputs, ldo = of out/traj */
+/* What every solve call starts with: the checks, the batch's id (every call counts, an empty one too), the handle's device (`guard`
+ * lives in the caller: as long as the call) and the batch's record.  *rec stays NULL for an empty batch: nothing is left to do. */
 template <class R>
-static int launch_solve(MpcHandle *h, int64_t B, int64_t ld, int64_t ldo, const R *state, const R *coeffs,
-                        const R *yaw_lo, const R *yaw_hi, const R *weights, R *out, R *traj,
-                        int32_t *status, int32_t *iters, void *stream_, bool with_stats = true, bool may_defer = false,
-                        bool may_order = false) {
+static int solve_begin(MpcHandle *h, const SolveIO<R> &io, const WarmIO *warm, std::optional<DeviceGuard> &guard, MpcHandle::BatchRec **rec) {
   if (!h) { g_last_error = "NULL handle"; return MPC_ERR_INVALID; }
   if ((h->params.precision == MPC_PRECISION_F32) != (sizeof(R) == 4)) {
     g_last_error = "this handle was created with the other precision: fp64 handles take the double entry points, "
                    "MPC_PRECISION_F32 handles mpc_solve_batch_device_f32";
     return MPC_ERR_INVALID;
   }
-  if (B < 0 || ld < B || ldo < B) { g_last_error = "ld < B"; return MPC_ERR_INVALID; }
+  const int64_t B = io.B;
+  if (B < 0 || io.ld < B || io.ldo < B) { g_last_error = "ld < B"; return MPC_ERR_INVALID; }
+  if (warm && (warm->warm_in || warm->warm_out) && warm->ld_warm < B) { g_last_error = "ld_warm < B"; return MPC_ERR_INVALID; }
   if (B > h->max_batch) { g_last_error = "B exceeds the handle's max_batch"; return MPC_ERR_INVALID; }
   h->last_B = B; h->timed = false; h->have_stats = false; h->stats_pending = false;
   ++h->batch_seq;
@@ -1884,199 +2030,118 @@ static int launch_solve(MpcHandle *h, int64_t B, int64_t ld, int64_t ldo, const 
     R0.id = h->batch_seq; R0.kind = 2;
     return MPC_OK;
   }
-  if (!state || !coeffs || !yaw_lo || !yaw_hi || !out || !status) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
-  MPC_ON_DEVICE(h);   /* workspace, lazy allocations and a NULL stream all belong to the handle's device */
+  if (!io.state || !io.coeffs || !io.yaw_lo || !io.yaw_hi || !io.out || !io.status) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
+  guard.emplace(h->device);    /* workspace, lazy allocations and a NULL stream all belong to the handle's device */
+  if (guard->err != hipSuccess) { g_last_error = std::string("hipSetDevice: ") + hipGetErrorString(guard->err); return MPC_ERR_HIP; }
+  MPC_TRY(batch_rec(h, h->batch_seq, rec));
+  (*rec)->id = 0;              /* (valid once the launch has been issued) */
+  return MPC_OK;
+}
+
+/* ... and ends with, behind its last launch: the events, the batch's record (what mpc_tail_wait / _poll / _stream_wait resolve its
+ * id with), the hand-over bookkeeping of a deferring batch, and what mpc_get_stats will gather if asked */
+template <class R>
+static int solve_end(MpcHandle *h, const SolveIO<R> &io, hipStream_t s, MpcHandle::BatchRec *rec, const TailPlace &tp, bool with_stats) {
+  MPC_HIP_CHECK(hipEventRecord(h->ev1, s));
+  h->timed = true;
+  rec->id = h->batch_seq; rec->kind = tp.defer ? 1 : 0; rec->slot = tp.slot;
+  MPC_HIP_CHECK(hipEventRecord(rec->ev, s));
+  if (tp.defer) {
+    MpcHandle::FreshQ &F = h->fq[tp.fq];
+    F.batch_id = h->batch_seq; F.slot = tp.slot; F.state = 1; F.slice = -1;
+    MPC_HIP_CHECK(hipEventRecord(F.bulk, s));
+    MpcHandle::TailSlot &S = h->tslot[tp.slot];
+    S.batch_id = h->batch_seq; S.final_ = false; S.deferred = -1; S.B = io.B;
+    ++h->n_not_final;
+    ++h->n_deferred;
+    MPC_TRY(tail_pump(h, false));
+  }
+  if (with_stats) { h->st_status = io.status; h->st_iters = io.iters; h->st_B = io.B; h->st_ev = rec->ev; h->stats_pending = true; }
+  return MPC_OK;
+}
+
+/* The launch, for every entry point.  with_stats: mpc_get_stats may ask about this call.  may_defer: the caller can wait for the
+ * batch's stragglers (mpc_tail_wait).  may_order: the take order may be applied.  warm: a warm call (warm_check has passed: an
+ * fp64 handle, not mixed, no SOC) -- a single phase of the WARM build, or the warm wave kernel; it never defers, cuts or orders. */
+template <class R>
+static int launch_solve(MpcHandle *h, const SolveIO<R> &call, void *stream_, bool with_stats = true, bool may_defer = false,
+                        bool may_order = false, const WarmIO *warm = nullptr) {
+  std::optional<DeviceGuard> guard;
+  MpcHandle::BatchRec *rec = nullptr;
+  MPC_TRY(solve_begin(h, call, warm, guard, &rec));
+  if (!rec) return MPC_OK;
+  SolveIO<R> io = call;
+  if (!io.iters) io.iters = h->d_iters;
+  const int64_t B = io.B;
   hipStream_t s = (hipStream_t)stream_;   /* NULL = HIP's default (null) stream, exactly as passed */
-  /* waves: one lane per instance */
-  const int64_t waves = (B + kBlock - 1) / kBlock;
+  if (warm) may_defer = may_order = false;
   /* MpcParams.max_soc > 0 on an fp64 handle: the SOC builds of the kernels (the mixed-precision launch decides for its fp64 phase
    * itself) */
   const bool soc = sizeof(R) == 8 && h->params.max_soc > 0;
-  bool defer = may_defer && h->params.tail_cut != 0 && B >= kTailMinBatch && !(h->wave_max_batch > 0 && B <= h->wave_max_batch);
-  MpcHandle::BatchRec *rec = nullptr;
-  { const int rc = batch_rec(h, h->batch_seq, &rec); if (rc != MPC_OK) return rc; }
-  rec->id = 0;                                      /* (valid once the launch has been issued) */
-  int slot_index = 0, fq_index = 0;
-  if (defer) {
-    int rc = tail_prepare(h);
-    if (rc != MPC_OK) return rc;
-    rc = tail_pump(h, false);
-    if (rc != MPC_OK) return rc;
-    /* the survivors' list is filling up (stragglers arrive faster than the slices finish them): this batch keeps its own */
-    if (2 * h->surv_last > h->surv_cap) { defer = false; ++h->n_throttled; if (h->params.tail_cut < 0 && h->auto_cut < h->auto_base + 40) h->auto_cut += 2; }
-  }
-  if (defer) {
-    slot_index = (int)(h->n_deferred % h->tail_ring);
-    fq_index = (int)(h->n_deferred % kFreshRing);
-    /* the slot is taken again: the batch it held must be final (only if the ring is shorter than the stragglers' latency) */
-    for (int guard = 0; h->tslot[slot_index].batch_id != 0 && !h->tslot[slot_index].final_; guard++) {
-      if (guard > (1 << 22)) { g_last_error = "deferred tails: no progress"; return MPC_ERR_HIP; }
-      const int rc = tail_pump(h, true);
-      if (rc != MPC_OK) return rc;
-    }
-    /* the fresh queue is taken again: the slice that absorbed its previous batch must have read it */
-    MpcHandle::FreshQ &F = h->fq[fq_index];
-    if (F.state == 1) { const int rc = tail_launch_slice(h, true); if (rc != MPC_OK) return rc; }
-    /* (its count is zero again: the slice's last wave has reset it) */
-    if (F.state == 2) MPC_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream_, h->slice_ev[F.slice % kSliceRing], 0));
-  }
-  const int n_cuts = (!defer && B >= kPassCutMinBatch) ? h->n_cuts : 0;
-  auto tail_fields = [&](MpcPhase &T) {
-    T.tail_cut = defer ? (h->params.tail_cut > 0 ? h->params.tail_cut : h->auto_cut) : 0; T.t_slot = slot_index; T.t_batch = h->batch_seq;
-    if (defer) { T.tq = h->fq_dev[fq_index]; T.tail_few = h->tail_few; T.tail_few_from = kTailFewFrom; }
-  };
-  /* behind the launch: the batch's record (what mpc_tail_wait / _poll / _stream_wait resolve its id with) */
-  int32_t *cb = h->d_counter + (h->counter_seq % kCounterRing) * kCounterInts;
-  int32_t *zero_next = h->d_counter + ((h->counter_seq + kCounterRing / 2) % kCounterRing) * kCounterInts;
-  ++h->counter_seq;
-  auto stats_later = [&](const int32_t *it_arr) { h->st_status = status; h->st_iters = it_arr; h->st_B = B; h->st_ev = rec->ev; h->stats_pending = true; };
-  auto tail_done = [&]() -> int {
-    rec->id = h->batch_seq; rec->kind = defer ? 1 : 0; rec->slot = slot_index;
-    MPC_HIP_CHECK(hipEventRecord(rec->ev, s));
-    if (!defer) return MPC_OK;
-    MpcHandle::FreshQ &F = h->fq[fq_index];
-    F.batch_id = h->batch_seq; F.slot = slot_index; F.state = 1; F.slice = -1;
-    MPC_HIP_CHECK(hipEventRecord(F.bulk, s));
-    MpcHandle::TailSlot &S = h->tslot[slot_index];
-    S.batch_id = h->batch_seq; S.final_ = false; S.deferred = -1; S.B = B;
-    ++h->n_not_final;
-    ++h->n_deferred;
-    return tail_pump(h, false);
-  };
-  const bool wave_path = h->wave_max_batch > 0 && B <= h->wave_max_batch;
-  if (h->mixed && !wave_path) {
-    MpcPhase TT;
-    memset(&TT, 0, sizeof(TT));
-    tail_fields(TT);
-    const int rc = launch_mixed<R>(h, B, ld, ldo, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters, s, TT, cb, zero_next);
-    if (rc != MPC_OK) return rc;
-    const int rt = tail_done();
-    if (rt != MPC_OK) return rt;
-    if (with_stats) stats_later(iters ? iters : h->d_iters);
-    return MPC_OK;
-  }
-  if (n_cuts > 0) {
-    const size_t ws_bytes = (size_t)h->ws_stride * (size_t)(h->io_stride / 64) * sizeof(R);
-    if (!h->ws2) MPC_HIP_CHECK(hipMalloc((void **)&h->ws2, ws_bytes));
-    if (!h->d_park) MPC_HIP_CHECK(hipMalloc((void **)&h->d_park, sizeof(double) * 2 * kParkRows * h->io_stride));
-    if (!h->d_list) MPC_HIP_CHECK(hipMalloc((void **)&h->d_list, sizeof(int32_t) * 4 * h->io_stride));
-  }
-  if (h->wave_max_batch > 0 && B <= h->wave_max_batch) {
-    --h->counter_seq;                              /* (this path uses no counters: the block stays clean for the next call) */
+  const bool wave_path = h->wave_max_batch > 0 && B <= h->wave_max_batch;      /* (comes first: set_wave_limit decides which handles have it) */
+  TailPlace tp;
+  tp.defer = may_defer && h->params.tail_cut != 0 && B >= kTailMinBatch && !wave_path;
+  if (tp.defer) MPC_TRY(tail_claim(h, s, tp));
+  if (wave_path) {
     MPC_HIP_CHECK(hipEventRecord(h->ev0, s));
-    /* lanes per instance: a lane per stage -- 16 up to N = 17 (four instances per wavefront), 32 up to N = 33, else the whole wave;
-     * a launch of a few instances takes the whole wave anyway (its cross-lane reads are v_readlane instead of ds_bpermute) */
-    const int64_t per = (int64_t)mpc::workspace_fields_per_instance(h->params.N, sizeof(R) == 4, h->params.initial_state_rows != 0) * (int64_t)sizeof(R);
-    int lpi = h->params.N - 1 <= 16 ? 16 : (h->params.N - 1 <= 32 ? 32 : 64);
-    if (B <= kWaveWholeMax) lpi = 64;
-    if (const char *e = getenv("MPC_WAVE_LPI")) lpi = atoi(e) == 16 ? 16 : (atoi(e) == 32 ? 32 : 64);
-    if (lpi < h->params.N - 1) lpi = 64;
-    int32_t *it_w = iters ? iters : h->d_iters;
-    if constexpr (sizeof(R) == 8) {
-      if (soc) {
-        const int64_t ps = per + mpc::soc_fields_per_instance(h->params.N) * (int64_t)sizeof(R);   /* the SOC records behind the stage records */
-        if (lpi == 16)
-          hipLaunchKernelGGL((mpc_solve_wave_kernel<R, 16, true>), dim3((unsigned)((B + 3) / 4)), dim3(kBlock), (size_t)(4 * ps), s, h->params, B, ld, ldo, state, coeffs, yaw_lo, yaw_hi,
-                             weights, out, traj, status, it_w);
-        else if (lpi == 32)
-          hipLaunchKernelGGL((mpc_solve_wave_kernel<R, 32, true>), dim3((unsigned)((B + 1) / 2)), dim3(kBlock), (size_t)(2 * ps), s, h->params, B, ld, ldo, state, coeffs, yaw_lo, yaw_hi,
-                             weights, out, traj, status, it_w);
-        else
-          hipLaunchKernelGGL((mpc_solve_wave_kernel<R, 64, true>), dim3((unsigned)B), dim3(kBlock), (size_t)ps, s, h->params, B, ld, ldo, state, coeffs, yaw_lo, yaw_hi,
-                             weights, out, traj, status, it_w);
-        lpi = 0;
-      }
+    MPC_TRY(launch_wave(h, io, s, soc, warm));
+  } else if (h->mixed) {
+    MPC_TRY(launch_mixed(h, io, s, tp));
+  } else {
+    const int64_t S = h->io_stride;
+    const int n_cuts = (!warm && !tp.defer && B >= kPassCutMinBatch) ? h->n_cuts : 0;
+    if (n_cuts > 0) {
+      MPC_TRY(ensure_dev(&h->ws2, (size_t)h->ws_stride * (size_t)(S / 64) * sizeof(R)));
+      MPC_TRY(ensure_dev(&h->d_park, sizeof(double) * 2 * kParkRows * S));
+      MPC_TRY(ensure_dev(&h->d_list, sizeof(int32_t) * 4 * S));
     }
-    if (lpi == 16)
-      hipLaunchKernelGGL((mpc_solve_wave_kernel<R, 16>), dim3((unsigned)((B + 3) / 4)), dim3(kBlock), (size_t)(4 * per), s, h->params, B, ld, ldo, state, coeffs, yaw_lo, yaw_hi,
-                         weights, out, traj, status, it_w);
-    else if (lpi == 32)
-      hipLaunchKernelGGL((mpc_solve_wave_kernel<R, 32>), dim3((unsigned)((B + 1) / 2)), dim3(kBlock), (size_t)(2 * per), s, h->params, B, ld, ldo, state, coeffs, yaw_lo, yaw_hi,
-                         weights, out, traj, status, it_w);
-    else if (lpi == 64)
-      hipLaunchKernelGGL((mpc_solve_wave_kernel<R, 64>), dim3((unsigned)B), dim3(kBlock), (size_t)per, s, h->params, B, ld, ldo, state, coeffs, yaw_lo, yaw_hi,
-                         weights, out, traj, status, it_w);
-    MPC_HIP_CHECK(hipGetLastError());
-    MPC_HIP_CHECK(hipEventRecord(h->ev1, s));
-    h->timed = true;
-    { const int rt = tail_done(); if (rt != MPC_OK) return rt; }
-    if (with_stats) stats_later(iters ? iters : h->d_iters);
-    return MPC_OK;
-  }
-  int32_t *it_out = iters ? iters : h->d_iters;
-  if (soc) { const int rc = soc_alloc(h, &h->soc_ws, h->io_stride / 64); if (rc != MPC_OK) return rc; }
-  /* take order: the key kernel goes ahead of the launch on its stream; its counts live behind the phase counters of the block */
-  const bool ordered = may_order && h->take_order != 0 && sizeof(R) == 8 && n_cuts == 0 && !soc && !weights && h->params.N < 15 &&
-                       B >= h->take_order_min_batch;
-  if (ordered && !h->d_take_list) MPC_HIP_CHECK(hipMalloc((void **)&h->d_take_list, sizeof(int32_t) * mpc::kTakeBins * h->io_stride));
-  MPC_HIP_CHECK(hipEventRecord(h->ev0, s));
-  if (ordered) {
-    hipLaunchKernelGGL((mpc_take_key_kernel<R>), dim3((unsigned)waves), dim3(kBlock), 0, s, (float)(h->params.N * h->params.dt), B, ld, state, coeffs,
-                       yaw_lo, yaw_hi, h->take_order == 2 ? 1 : 0, cb + kPhaseCounterInts, h->d_take_list, h->io_stride);
-    MPC_HIP_CHECK(hipGetLastError());
-    ++h->n_take_ordered;
-  }
-  auto launch = [&](unsigned grid, void *wsp, const MpcPhase &tp) {
-    if constexpr (sizeof(R) == 8) {
-      if (soc) {
-        if (h->staging)
-          hipLaunchKernelGGL((mpc_solve_kernel<true, R, R, R, true>), dim3(grid), dim3(kBlock), staging_lds_bytes<R>(), s, h->params, B, ld, ldo, state, coeffs,
-                             yaw_lo, yaw_hi, weights, out, traj, status, it_out, (R *)wsp, h->ws_stride, tp);
-        else
-          hipLaunchKernelGGL((mpc_solve_kernel<false, R, R, R, true>), dim3(grid), dim3(kBlock), 0, s, h->params, B, ld, ldo, state, coeffs,
-                             yaw_lo, yaw_hi, weights, out, traj, status, it_out, (R *)wsp, h->ws_stride, tp);
-        return;
-      }
+    if (soc) MPC_TRY(soc_alloc(h, &h->soc_ws, S / 64));
+    /* take order: the key kernel goes ahead of the launch on its stream; its counts live behind the phase counters of the block */
+    const bool ordered = may_order && h->take_order != 0 && sizeof(R) == 8 && n_cuts == 0 && !soc && !io.weights && h->params.N < 15 &&
+                         B >= h->take_order_min_batch;
+    if (ordered) MPC_TRY(ensure_dev(&h->d_take_list, sizeof(int32_t) * mpc::kTakeBins * S));
+    const CounterBlocks C = take_counters(h);
+    MPC_HIP_CHECK(hipEventRecord(h->ev0, s));
+    if (ordered) {
+      hipLaunchKernelGGL((mpc_take_key_kernel<R>), dim3((unsigned)((B + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, (float)(h->params.N * h->params.dt), B,
+                         io.ld, io.state, io.coeffs, io.yaw_lo, io.yaw_hi, h->take_order == 2 ? 1 : 0, C.cb + kPhaseCounterInts, h->d_take_list, S);
+      MPC_HIP_CHECK(hipGetLastError());
+      ++h->n_take_ordered;
     }
-    if (h->staging)
-      hipLaunchKernelGGL((mpc_solve_kernel<true, R>), dim3(grid), dim3(kBlock), staging_lds_bytes<R>(), s, h->params, B, ld, ldo, state, coeffs,
-                         yaw_lo, yaw_hi, weights, out, traj, status, it_out, (R *)wsp, h->ws_stride, tp);
-    else
-      hipLaunchKernelGGL((mpc_solve_kernel<false, R>), dim3(grid), dim3(kBlock), 0, s, h->params, B, ld, ldo, state, coeffs,
-                         yaw_lo, yaw_hi, weights, out, traj, status, it_out, (R *)wsp, h->ws_stride, tp);
-  };
-  /* phase p takes from counter [2p], parks into list p & 1 and counts its parked instances in [2p + 1]; phase p > 0
-   * reads list (p - 1) & 1 and the workspace of phase p - 1; every phase has the grid of the first (see MpcPhase) */
-  for (int p = 0; p <= n_cuts; ++p) {
-    MpcPhase T;
-    memset(&T, 0, sizeof(T));          /* every switch a phase does not set is off */
-    const int wr = p & 1, rd = wr ^ 1;
-    T.take = cb + 2 * p;
-    T.n_out = cb + 2 * p + 1;
-    T.n_in = p > 0 ? cb + 2 * (p - 1) + 1 : nullptr;
-    T.zero_next = p == 0 ? zero_next : nullptr;
-    T.out_inst = h->d_list ? h->d_list + (int64_t)(2 * wr) * h->io_stride : nullptr;
-    T.out_src = h->d_list ? h->d_list + (int64_t)(2 * wr + 1) * h->io_stride : nullptr;
-    T.in_inst = h->d_list ? h->d_list + (int64_t)(2 * rd) * h->io_stride : nullptr;
-    T.in_src = h->d_list ? h->d_list + (int64_t)(2 * rd + 1) * h->io_stride : nullptr;
-    T.out_park = h->d_park ? h->d_park + (int64_t)wr * kParkRows * h->io_stride : nullptr;
-    T.in_park = h->d_park ? h->d_park + (int64_t)rd * kParkRows * h->io_stride : nullptr;
-    T.ld_park = h->io_stride;
-    T.src_ws = rd ? h->ws2 : h->ws;
-    T.pass_cut = p < n_cuts ? h->cuts[p] : 0;
-    T.resume = p > 0;
-    T.refill_min = kRefillMin; T.refill_wait = kRefillWait;
-    T.compact_cooldown = kCompactCooldown;
-    T.compact_gap = (n_cuts == 0 && B >= h->compact_min_batch) ? h->compact_gap : 0;     /* (a phase that parks keeps iterates in its columns) */
-    tail_fields(T);
-    T.soc_ws = h->soc_ws;
-    if (ordered) { T.ord_cnt = cb + kPhaseCounterInts; T.ord_list = h->d_take_list; T.ord_ld = h->io_stride; }
-    launch((unsigned)waves, wr ? h->ws2 : h->ws, T);
-    MPC_HIP_CHECK(hipGetLastError());
+    /* phase p takes from counter [2p], parks into list p & 1 and counts its parked instances in [2p + 1]; phase p > 0
+     * reads list (p - 1) & 1 and the workspace of phase p - 1; every phase has the grid of the first (see MpcPhase) */
+    for (int p = 0; p <= n_cuts; ++p) {
+      MpcPhase T = phase_defaults(h, B);
+      const int wr = p & 1, rd = wr ^ 1;
+      T.take = C.cb + 2 * p;
+      T.n_out = C.cb + 2 * p + 1;
+      T.n_in = p > 0 ? C.cb + 2 * (p - 1) + 1 : nullptr;
+      T.zero_next = p == 0 ? C.zero_next : nullptr;
+      if (!warm) {
+        if (h->d_list) {
+          T.out_inst = h->d_list + (int64_t)(2 * wr) * S; T.out_src = h->d_list + (int64_t)(2 * wr + 1) * S;
+          T.in_inst = h->d_list + (int64_t)(2 * rd) * S; T.in_src = h->d_list + (int64_t)(2 * rd + 1) * S;
+        }
+        if (h->d_park) { T.out_park = h->d_park + (int64_t)wr * kParkRows * S; T.in_park = h->d_park + (int64_t)rd * kParkRows * S; }
+        T.src_ws = rd ? h->ws2 : h->ws;
+        T.soc_ws = h->soc_ws;
+      }
+      T.pass_cut = p < n_cuts ? h->cuts[p] : 0;
+      T.resume = p > 0;
+      if (n_cuts > 0) T.compact_gap = 0;     /* (a phase that parks keeps iterates in its columns) */
+      tail_fields(h, tp, T);
+      if (ordered) { T.ord_cnt = C.cb + kPhaseCounterInts; T.ord_list = h->d_take_list; T.ord_ld = S; }
+      MPC_TRY(launch_lanes(h, LaneBuild::single, io, s, wr ? h->ws2 : h->ws, soc, T, warm));
+    }
   }
-  MPC_HIP_CHECK(hipGetLastError());
-  MPC_HIP_CHECK(hipEventRecord(h->ev1, s));
-  h->timed = true;
-  { const int rt = tail_done(); if (rt != MPC_OK) return rt; }
-  if (with_stats) stats_later(it_out);
-  return MPC_OK;
+  return solve_end(h, io, s, rec, tp, with_stats);
 }
 
 extern "C" int mpc_solve_batch_device(MpcHandle *h, int64_t B, int64_t ld, const double *state,
                                       const double *coeffs, const double *yaw_lo, const double *yaw_hi,
                                       const double *weights, double *out, double *traj, int32_t *status,
                                       int32_t *iters, void *stream_) {
-  return launch_solve<double>(h, B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters, stream_, true, true, true);
+  return launch_solve<double>(h, {B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters}, stream_, true, true, true);
 }
 
 /* ---- warm start ---------------------------------------------------------------------------------------------------------- */
@@ -2112,85 +2177,13 @@ static int warm_check(MpcHandle *h, const MpcWarmOpts *opts, MpcWarmOpts *W) {
   return MPC_OK;
 }
 
-/* One launch, all arrays on the device: the wave kernel up to wave_max_batch instances, else the WARM build of the lane kernel --
- * a single phase, no deferred tails, no pass cuts, no take order.  with_stats as in launch_solve. */
-static int launch_warm(MpcHandle *h, int64_t B, int64_t ld, int64_t ldo, const double *state, const double *coeffs, const double *yaw_lo,
-                       const double *yaw_hi, const double *weights, const double *warm_in, const int32_t *warm_status, double *warm_out,
-                       int64_t ld_warm, const MpcWarmOpts &W, double *out, double *traj, int32_t *status, int32_t *iters, void *stream_,
-                       bool with_stats) {
-  using R = double;
-  if (B < 0 || ld < B || ldo < B) { g_last_error = "ld < B"; return MPC_ERR_INVALID; }
-  if ((warm_in || warm_out) && ld_warm < B) { g_last_error = "ld_warm < B"; return MPC_ERR_INVALID; }
-  if (B > h->max_batch) { g_last_error = "B exceeds the handle's max_batch"; return MPC_ERR_INVALID; }
-  h->last_B = B; h->timed = false; h->have_stats = false; h->stats_pending = false;
-  ++h->batch_seq;
-  if (B == 0) {
-    if (!h->brec) h->brec = new MpcHandle::BatchRec[MpcHandle::kBatchRecs];
-    MpcHandle::BatchRec &R0 = h->brec[h->batch_seq % MpcHandle::kBatchRecs];
-    R0.id = h->batch_seq; R0.kind = 2;
-    return MPC_OK;
-  }
-  if (!state || !coeffs || !yaw_lo || !yaw_hi || !out || !status) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
-  MPC_ON_DEVICE(h);
-  hipStream_t s = (hipStream_t)stream_;
-  MpcHandle::BatchRec *rec = nullptr;
-  { const int rc = batch_rec(h, h->batch_seq, &rec); if (rc != MPC_OK) return rc; }
-  rec->id = 0;
-  int32_t *it_out = iters ? iters : h->d_iters;
-  MPC_HIP_CHECK(hipEventRecord(h->ev0, s));
-  if (h->wave_max_batch > 0 && B <= h->wave_max_batch) {
-    /* lanes per instance as in launch_solve */
-    const int64_t per = (int64_t)mpc::workspace_fields_per_instance(h->params.N, false, h->params.initial_state_rows != 0) * (int64_t)sizeof(R);
-    int lpi = h->params.N - 1 <= 16 ? 16 : (h->params.N - 1 <= 32 ? 32 : 64);
-    if (B <= kWaveWholeMax) lpi = 64;
-    if (const char *e = getenv("MPC_WAVE_LPI")) lpi = atoi(e) == 16 ? 16 : (atoi(e) == 32 ? 32 : 64);
-    if (lpi < h->params.N - 1) lpi = 64;
-    if (lpi == 16)
-      hipLaunchKernelGGL((mpc_solve_wave_warm_kernel<R, 16>), dim3((unsigned)((B + 3) / 4)), dim3(kBlock), (size_t)(4 * per), s, h->params, B, ld, ldo, state, coeffs,
-                         yaw_lo, yaw_hi, weights, out, traj, status, it_out, warm_in, warm_status, warm_out, ld_warm, W);
-    else if (lpi == 32)
-      hipLaunchKernelGGL((mpc_solve_wave_warm_kernel<R, 32>), dim3((unsigned)((B + 1) / 2)), dim3(kBlock), (size_t)(2 * per), s, h->params, B, ld, ldo, state, coeffs,
-                         yaw_lo, yaw_hi, weights, out, traj, status, it_out, warm_in, warm_status, warm_out, ld_warm, W);
-    else
-      hipLaunchKernelGGL((mpc_solve_wave_warm_kernel<R, 64>), dim3((unsigned)B), dim3(kBlock), (size_t)per, s, h->params, B, ld, ldo, state, coeffs,
-                         yaw_lo, yaw_hi, weights, out, traj, status, it_out, warm_in, warm_status, warm_out, ld_warm, W);
-  } else {
-    int32_t *cb = h->d_counter + (h->counter_seq % kCounterRing) * kCounterInts;
-    int32_t *zero_next = h->d_counter + ((h->counter_seq + kCounterRing / 2) % kCounterRing) * kCounterInts;
-    ++h->counter_seq;
-    MpcPhaseWarm T;
-    memset(&T, 0, sizeof(T));
-    T.take = cb; T.n_out = cb + 1; T.zero_next = zero_next; T.ld_park = h->io_stride;
-    T.refill_min = kRefillMin; T.refill_wait = kRefillWait;
-    T.compact_cooldown = kCompactCooldown;
-    T.compact_gap = B >= h->compact_min_batch ? h->compact_gap : 0;
-    T.t_batch = h->batch_seq;
-    T.warm_in = warm_in; T.warm_status = warm_status; T.warm_out = warm_out; T.ld_warm = ld_warm; T.wopts = W;
-    const unsigned grid = (unsigned)((B + kBlock - 1) / kBlock);
-    if (h->staging)
-      hipLaunchKernelGGL((mpc_solve_kernel<true, R, R, R, false, true>), dim3(grid), dim3(kBlock), staging_lds_bytes<R>(), s, h->params, B, ld, ldo, state, coeffs,
-                         yaw_lo, yaw_hi, weights, out, traj, status, it_out, (R *)h->ws, h->ws_stride, T);
-    else
-      hipLaunchKernelGGL((mpc_solve_kernel<false, R, R, R, false, true>), dim3(grid), dim3(kBlock), 0, s, h->params, B, ld, ldo, state, coeffs,
-                         yaw_lo, yaw_hi, weights, out, traj, status, it_out, (R *)h->ws, h->ws_stride, T);
-  }
-  MPC_HIP_CHECK(hipGetLastError());
-  MPC_HIP_CHECK(hipEventRecord(h->ev1, s));
-  h->timed = true;
-  rec->id = h->batch_seq; rec->kind = 0; rec->slot = 0;
-  MPC_HIP_CHECK(hipEventRecord(rec->ev, s));
-  if (with_stats) { h->st_status = status; h->st_iters = it_out; h->st_B = B; h->st_ev = rec->ev; h->stats_pending = true; }
-  return MPC_OK;
-}
-
 extern "C" int mpc_solve_batch_device_warm(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
                                            const double *yaw_lo, const double *yaw_hi, const double *weights, const double *warm_in,
                                            const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts,
                                            double *out, double *traj, int32_t *status, int32_t *iters, void *stream_) {
-  MpcWarmOpts W;
-  const int rc = warm_check(h, opts, &W);
-  if (rc != MPC_OK) return rc;
-  return launch_warm(h, B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, warm_in, warm_status, warm_out, ld_warm, W, out, traj, status, iters, stream_, true);
+  WarmIO warm{warm_in, warm_status, warm_out, ld_warm, {}};
+  MPC_TRY(warm_check(h, opts, &warm.opts));
+  return launch_solve<double>(h, {B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters}, stream_, true, false, false, &warm);
 }
 
 /* MPC_PRECISION_F32: the same solve with fp32 inputs, outputs and workspace (handle created with precision F32) */
@@ -2198,15 +2191,14 @@ extern "C" int mpc_solve_batch_device_f32(MpcHandle *h, int64_t B, int64_t ld, c
                                           const float *coeffs, const float *yaw_lo, const float *yaw_hi,
                                           const float *weights, float *out, float *traj, int32_t *status,
                                           int32_t *iters, void *stream_) {
-  return launch_solve<float>(h, B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters, stream_, true, true);
+  return launch_solve<float>(h, {B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters}, stream_, true, true);
 }
 
 /* run() for a batch; `tel` selects the telemetry rows as input (with latency compensation) and `cmd` the reply */
 static int run_impl(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, bool tel, double extra, double *ptsx,
                     double *ptsy, double *out8, double *cmd, double *traj, int32_t *status, int32_t *iters, double *pre,
                     void *stream_) {
-  if (!h) { g_last_error = "NULL handle"; return MPC_ERR_INVALID; }
-  if (B < 0 || ld < B || B > h->max_batch) { g_last_error = "bad B/ld"; return MPC_ERR_INVALID; }
+  MPC_TRY(check_batch(h, B, ld));
   if (npts < 3 || npts > mpc::RUN_MAX_PTS) { g_last_error = "npts must be 3..8"; return MPC_ERR_INVALID; }
   if (B == 0) { h->last_B = 0; return MPC_OK; }
   if (!pose || !ptsx || !ptsy || !(out8 || cmd) || !status) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
@@ -2216,21 +2208,15 @@ static int run_impl(MpcHandle *h, int64_t B, int64_t ld, int npts, const double 
   if (h->params.max_fit_order > 5) { g_last_error = "run(): max_fit_order > 5 is not built (fit orders 2..4)"; return MPC_ERR_UNSUPPORTED; }
   MPC_ON_DEVICE(h);
   const int64_t S = h->io_stride;
-  if (!h->d_run) MPC_HIP_CHECK(hipMalloc((void **)&h->d_run, sizeof(double) * 15 * S));
-  if (!h->d_run9 || h->run9_ld < ld) {       /* solve()'s 9 rows, with the caller's leading dimension (traj shares it) */
-    if (h->d_run9) MPC_HIP_CHECK(hipFree(h->d_run9));
-    h->d_run9 = nullptr;
-    MPC_HIP_CHECK(hipMalloc((void **)&h->d_run9, sizeof(double) * 9 * ld));
-    h->run9_ld = ld;
-  }
+  MPC_TRY(ensure_dev(&h->d_run, sizeof(double) * 15 * S));
+  MPC_TRY(grow_dev(&h->d_run9, &h->run9_bytes, sizeof(double) * 9 * ld));       /* solve()'s 9 rows, with the caller's leading dimension (traj shares it) */
   hipStream_t s = (hipStream_t)stream_;
   double *d_pre = h->d_run;
   const unsigned grid = (unsigned)((B + 255) / 256);
   if (tel) hipLaunchKernelGGL(mpc_run_pre_kernel<true>, dim3(grid), dim3(256), 0, s, h->params, B, ld, npts, pose, extra, ptsx, ptsy, d_pre, S);
   else hipLaunchKernelGGL(mpc_run_pre_kernel<false>, dim3(grid), dim3(256), 0, s, h->params, B, ld, npts, pose, 0.0, ptsx, ptsy, d_pre, S);
   MPC_HIP_CHECK(hipGetLastError());
-  int rc = launch_solve<double>(h, B, S, ld, d_pre, d_pre + 6 * S, d_pre + 11 * S, d_pre + 12 * S, nullptr, h->d_run9, traj, status, iters, stream_);
-  if (rc != MPC_OK) return rc;
+  MPC_TRY(launch_solve<double>(h, {B, S, ld, d_pre, d_pre + 6 * S, d_pre + 11 * S, d_pre + 12 * S, nullptr, h->d_run9, traj, status, iters}, stream_));
   hipLaunchKernelGGL(mpc_run_post_kernel, dim3(grid), dim3(256), 0, s, h->params, B, d_pre, S, h->d_run9, ld, out8, cmd, ld);
   MPC_HIP_CHECK(hipGetLastError());
   if (pre) MPC_HIP_CHECK(hipMemcpy2DAsync(pre, sizeof(double) * ld, d_pre, sizeof(double) * S, sizeof(double) * B, 15, hipMemcpyDeviceToDevice, s));
@@ -2258,20 +2244,13 @@ extern "C" void mpc_internal_set_error(const char *msg) { g_last_error = msg ? m
  * mpc_telemetry_batch_device with leading dimension ld; the waypoint arrays are inputs only here. */
 extern "C" int mpc_telemetry_batch_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
                                         const double *ptsx, const double *ptsy, double *cmd, int32_t *status) {
-  if (!h) { g_last_error = "NULL handle"; return MPC_ERR_INVALID; }
-  if (B < 0 || ld < B || B > h->max_batch) { g_last_error = "bad B/ld"; return MPC_ERR_INVALID; }
+  MPC_TRY(check_batch(h, B, ld));
   if (npts < 3 || npts > mpc::RUN_MAX_PTS) { g_last_error = "npts must be 3..8"; return MPC_ERR_INVALID; }
   if (B == 0) { h->last_B = 0; return MPC_OK; }
   if (!tel || !ptsx || !ptsy || !cmd || !status) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
   MPC_ON_DEVICE(h);
   const int64_t rows = 6 + 2 * npts, L = (B + 7) / 8 * 8;
-  const size_t need = sizeof(double) * (size_t)((rows + 2) * L) + sizeof(int32_t) * (size_t)L;
-  if (h->tel_bytes < need) {
-    if (h->d_tel) MPC_HIP_CHECK(hipFree(h->d_tel));
-    h->d_tel = nullptr; h->tel_bytes = 0;
-    MPC_HIP_CHECK(hipMalloc((void **)&h->d_tel, need));
-    h->tel_bytes = need;
-  }
+  MPC_TRY(grow_dev(&h->d_tel, &h->tel_bytes, sizeof(double) * (size_t)((rows + 2) * L) + sizeof(int32_t) * (size_t)L));
   double *d = h->d_tel, *d_cmd = d + rows * L;
   int32_t *d_st = (int32_t *)(d_cmd + 2 * L);
   hipStream_t s = h->stream;
@@ -2291,8 +2270,7 @@ extern "C" int mpc_telemetry_batch_host(MpcHandle *h, int64_t B, int64_t ld, int
  * like the reference does (MPC.cpp:329; mpc_main.cpp:189-190 relies on it). */
 extern "C" int mpc_run_batch_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx, double *ptsy,
                                   double *out8, double *traj, int32_t *status, int32_t *iters, double *pre) {
-  if (!h) { g_last_error = "NULL handle"; return MPC_ERR_INVALID; }
-  if (B < 0 || ld < B || B > h->max_batch) { g_last_error = "bad B/ld"; return MPC_ERR_INVALID; }
+  MPC_TRY(check_batch(h, B, ld));
   if (npts < 3 || npts > mpc::RUN_MAX_PTS) { g_last_error = "npts must be 3..8"; return MPC_ERR_INVALID; }
   if (h->params.precision != MPC_PRECISION_F64) { g_last_error = "run() entry points are fp64 only"; return MPC_ERR_INVALID; }
   if (B == 0) { h->last_B = 0; return MPC_OK; }
@@ -2301,13 +2279,7 @@ extern "C" int mpc_run_batch_host(MpcHandle *h, int64_t B, int64_t ld, int npts,
   const int N = h->params.N;
   const int64_t L = (B + 7) / 8 * 8;
   const int64_t in_rows = 6 + 2 * npts, out_rows = 8 + 2 * N + 15;
-  const size_t need = sizeof(double) * (size_t)((in_rows + out_rows) * L) + sizeof(int32_t) * (size_t)(2 * L);
-  if (h->tel_bytes < need) {
-    if (h->d_tel) MPC_HIP_CHECK(hipFree(h->d_tel));
-    h->d_tel = nullptr; h->tel_bytes = 0;
-    MPC_HIP_CHECK(hipMalloc((void **)&h->d_tel, need));
-    h->tel_bytes = need;
-  }
+  MPC_TRY(grow_dev(&h->d_tel, &h->tel_bytes, sizeof(double) * (size_t)((in_rows + out_rows) * L) + sizeof(int32_t) * (size_t)(2 * L)));
   double *d = h->d_tel, *d_px = d + 6 * L, *d_py = d_px + (int64_t)npts * L, *d_o8 = d + in_rows * L, *d_tr = d_o8 + 8 * L, *d_pre = d_tr + 2 * (int64_t)N * L;
   int32_t *d_st = (int32_t *)(d_pre + 15 * L), *d_it = d_st + L;
   hipStream_t s = h->stream;
@@ -2330,65 +2302,45 @@ extern "C" int mpc_run_batch_host(MpcHandle *h, int64_t B, int64_t ld, int npts,
 /* the device a handle lives on (mpc_create's `device`, resolved) */
 extern "C" int mpc_handle_device(const MpcHandle *h) { return h ? h->device : MPC_ERR_INVALID; }
 
-extern "C" int mpc_rollout_batch_device(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
-                                        const double *yaw_lo, const double *yaw_hi, const double *weights, double *hist,
-                                        int32_t *status, int32_t *iters, void *stream_) {
-  if (!h) { g_last_error = "NULL handle"; return MPC_ERR_INVALID; }
-  if (B < 0 || ld < B || B > h->max_batch) { g_last_error = "bad B/ld"; return MPC_ERR_INVALID; }
+/* The rollout: `steps` solves, each followed by the step kernel.  W != NULL: every step after the first is warm-started from the step
+ * before (the handle keeps the buffer). */
+static int rollout_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs, const double *yaw_lo,
+                        const double *yaw_hi, const double *weights, const MpcWarmOpts *W, double *hist, int32_t *status, int32_t *iters,
+                        void *stream_) {
+  MPC_TRY(check_batch(h, B, ld));
   if (steps < 1) { g_last_error = "steps < 1"; return MPC_ERR_INVALID; }
   if (B == 0) { h->last_B = 0; return MPC_OK; }
   if (!state || !coeffs || !yaw_lo || !yaw_hi || !status) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
   MPC_ON_DEVICE(h);
-  if (!hist && (!h->d_run9 || h->run9_ld < ld)) {
-    if (h->d_run9) MPC_HIP_CHECK(hipFree(h->d_run9));
-    h->d_run9 = nullptr;
-    MPC_HIP_CHECK(hipMalloc((void **)&h->d_run9, sizeof(double) * 9 * ld));
-    h->run9_ld = ld;
-  }
-  if (!h->d_rstat) MPC_HIP_CHECK(hipMalloc((void **)&h->d_rstat, sizeof(int32_t) * h->io_stride));
+  if (!hist) MPC_TRY(grow_dev(&h->d_run9, &h->run9_bytes, sizeof(double) * 9 * ld));
+  MPC_TRY(ensure_dev(&h->d_rstat, sizeof(int32_t) * h->io_stride));
+  if (W) MPC_TRY(ensure_dev(&h->d_warm, sizeof(double) * (size_t)mpc_warm_rows(h->params.N) * (size_t)h->io_stride));
   hipStream_t s = (hipStream_t)stream_;
   const unsigned grid = (unsigned)((B + 255) / 256);
   for (int t = 0; t < steps; t++) {
     double *o9 = hist ? hist + (int64_t)t * 9 * ld : h->d_run9;
-    int rc = launch_solve<double>(h, B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, o9, nullptr, h->d_rstat, h->d_iters, stream_, false);
-    if (rc != MPC_OK) return rc;
+    /* (warm, in place: a lane reads its car's column and its previous status (d_rstat) before it writes either) */
+    const WarmIO warm{t == 0 ? nullptr : h->d_warm, h->d_rstat, h->d_warm, h->io_stride, W ? *W : MpcWarmOpts{}};
+    MPC_TRY(launch_solve<double>(h, {B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, o9, nullptr, h->d_rstat, h->d_iters}, stream_, false, false, false,
+                                 W ? &warm : nullptr));
     hipLaunchKernelGGL(mpc_rollout_step_kernel, dim3(grid), dim3(256), 0, s, B, ld, t == 0, o9, state, h->d_rstat, h->d_iters, status, iters);
     MPC_HIP_CHECK(hipGetLastError());
   }
   return record_stats(h, B, status, iters, s);   /* worst status per instance, iterations summed over the steps */
 }
 
-/* the rollout with every step after the first warm-started from the step before (the handle keeps the buffer) */
+extern "C" int mpc_rollout_batch_device(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
+                                        const double *yaw_lo, const double *yaw_hi, const double *weights, double *hist,
+                                        int32_t *status, int32_t *iters, void *stream_) {
+  return rollout_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, nullptr, hist, status, iters, stream_);
+}
+
 extern "C" int mpc_rollout_batch_device_warm(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
                                              const double *yaw_lo, const double *yaw_hi, const double *weights, const MpcWarmOpts *opts,
                                              double *hist, int32_t *status, int32_t *iters, void *stream_) {
   MpcWarmOpts W;
-  { const int rc = warm_check(h, opts, &W); if (rc != MPC_OK) return rc; }
-  if (B < 0 || ld < B || B > h->max_batch) { g_last_error = "bad B/ld"; return MPC_ERR_INVALID; }
-  if (steps < 1) { g_last_error = "steps < 1"; return MPC_ERR_INVALID; }
-  if (B == 0) { h->last_B = 0; return MPC_OK; }
-  if (!state || !coeffs || !yaw_lo || !yaw_hi || !status) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
-  MPC_ON_DEVICE(h);
-  if (!hist && (!h->d_run9 || h->run9_ld < ld)) {
-    if (h->d_run9) MPC_HIP_CHECK(hipFree(h->d_run9));
-    h->d_run9 = nullptr;
-    MPC_HIP_CHECK(hipMalloc((void **)&h->d_run9, sizeof(double) * 9 * ld));
-    h->run9_ld = ld;
-  }
-  if (!h->d_rstat) MPC_HIP_CHECK(hipMalloc((void **)&h->d_rstat, sizeof(int32_t) * h->io_stride));
-  if (!h->d_warm) MPC_HIP_CHECK(hipMalloc((void **)&h->d_warm, sizeof(double) * (size_t)mpc_warm_rows(h->params.N) * (size_t)h->io_stride));
-  hipStream_t s = (hipStream_t)stream_;
-  const unsigned grid = (unsigned)((B + 255) / 256);
-  for (int t = 0; t < steps; t++) {
-    double *o9 = hist ? hist + (int64_t)t * 9 * ld : h->d_run9;
-    /* in place: a lane reads its car's column and its previous status (d_rstat) before it writes either */
-    int rc = launch_warm(h, B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, t == 0 ? nullptr : h->d_warm, h->d_rstat, h->d_warm, h->io_stride, W,
-                         o9, nullptr, h->d_rstat, h->d_iters, stream_, false);
-    if (rc != MPC_OK) return rc;
-    hipLaunchKernelGGL(mpc_rollout_step_kernel, dim3(grid), dim3(256), 0, s, B, ld, t == 0, o9, state, h->d_rstat, h->d_iters, status, iters);
-    MPC_HIP_CHECK(hipGetLastError());
-  }
-  return record_stats(h, B, status, iters, s);
+  MPC_TRY(warm_check(h, opts, &W));
+  return rollout_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, &W, hist, status, iters, stream_);
 }
 
 extern "C" int mpc_synchronize(MpcHandle *h) {
@@ -2415,18 +2367,15 @@ static void for_rows(int n_rows, size_t row_bytes, Fn fn) {
 
 /* host pointers: one copy in, the launch(es), one copy out, on the handle's own stream; R = the handle's precision */
 /* (warm: the host arrays of mpc_solve_batch_host_warm and the options in effect; fp64 handles only) */
-struct HostWarm {
-  const double *in; const int32_t *in_status; double *out; int64_t ld; MpcWarmOpts W;
-};
 template <class R>
 static int solve_host(MpcHandle *h, int64_t B, int64_t ld, const R *state, const R *coeffs, const R *yaw_lo, const R *yaw_hi,
-                      const R *weights, R *out, R *traj, int32_t *status, int32_t *iters, const HostWarm *warm = nullptr) {
+                      const R *weights, R *out, R *traj, int32_t *status, int32_t *iters, const WarmIO *warm = nullptr) {
   if (!h) { g_last_error = "NULL handle"; return MPC_ERR_INVALID; }
   if ((h->params.precision == MPC_PRECISION_F32) != (sizeof(R) == 4)) {
     g_last_error = "this handle was created with the other precision (mpc_solve_batch_host for fp64 handles, mpc_solve_batch_host_f32 for MPC_PRECISION_F32)";
     return MPC_ERR_INVALID;
   }
-  if (B < 0 || ld < B || B > h->max_batch) { g_last_error = "bad B/ld"; return MPC_ERR_INVALID; }
+  MPC_TRY(check_batch(h, B, ld));
   if (B == 0) { h->last_B = 0; h->have_stats = false; return MPC_OK; }
   if (!state || !coeffs || !yaw_lo || !yaw_hi || !out || !status) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
   MPC_ON_DEVICE(h);
@@ -2435,7 +2384,7 @@ static int solve_host(MpcHandle *h, int64_t B, int64_t ld, const R *state, const
   constexpr int kInRows = 6 + MPC_NCOEF + 2 + MPC_NW;              /* 25 */
   constexpr int kIntRows = sizeof(R) == 8 ? 1 : 2;                 /* status and iters: 2 x int32 per instance */
   const int kOutRows = MPC_NOUT + 2 * N + kIntRows;                /* out, traj, status|iters (N is fixed per handle) */
-  if (!h->d_io) MPC_HIP_CHECK(hipMalloc((void **)&h->d_io, sizeof(R) * (kInRows + kOutRows) * S));
+  MPC_TRY(ensure_dev(&h->d_io, sizeof(R) * (kInRows + kOutRows) * S));
   if (!h->h_io) MPC_HIP_CHECK(hipHostMalloc((void **)&h->h_io, sizeof(R) * (kInRows + kOutRows) * S, hipHostMallocDefault));
   /* rows packed with leading dimension L (B rounded up to 16: 64-byte rows), so each direction is ONE copy */
   const int64_t L = (B + 15) / 16 * 16;
@@ -2451,28 +2400,27 @@ static int solve_host(MpcHandle *h, int64_t B, int64_t ld, const R *state, const
   MPC_HIP_CHECK(hipMemcpyAsync(di, hi, sizeof(R) * in_rows * L, hipMemcpyHostToDevice, s));
   R *d_o = d_oblk, *d_t = d_o + MPC_NOUT * L;
   int32_t *d_st = (int32_t *)(d_o + (out_rows - kIntRows) * L), *d_it = d_st + L;
-  int rc = MPC_OK;
-  if constexpr (sizeof(R) == 8) {
-    if (warm) {
-      /* the warm buffer goes through a device block of its own, rows of the handle's stride, read and written in place */
-      const int64_t rows = mpc_warm_rows(N);
-      if ((warm->in || warm->out) && warm->ld < B) { g_last_error = "ld_warm < B"; return MPC_ERR_INVALID; }
-      if ((warm->in || warm->out) && !h->d_warm_io) MPC_HIP_CHECK(hipMalloc((void **)&h->d_warm_io, sizeof(double) * (size_t)rows * (size_t)S));
-      if (warm->in && warm->in_status && !h->d_warm_st) MPC_HIP_CHECK(hipMalloc((void **)&h->d_warm_st, sizeof(int32_t) * S));
-      if (warm->in) MPC_HIP_CHECK(hipMemcpy2DAsync(h->d_warm_io, sizeof(double) * S, warm->in, sizeof(double) * warm->ld, sizeof(double) * B, rows, hipMemcpyHostToDevice, s));
-      if (warm->in && warm->in_status) MPC_HIP_CHECK(hipMemcpyAsync(h->d_warm_st, warm->in_status, sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
-      rc = launch_warm(h, B, L, L, di, di + 6 * L, di + 11 * L, di + 12 * L, weights ? di + 13 * L : nullptr, warm->in ? h->d_warm_io : nullptr,
-                       (warm->in && warm->in_status) ? h->d_warm_st : nullptr, warm->out ? h->d_warm_io : nullptr, S, warm->W, d_o, traj ? d_t : nullptr,
-                       d_st, d_it, (void *)s, true);
-      if (rc != MPC_OK) return rc;
-      if (warm->out) MPC_HIP_CHECK(hipMemcpy2DAsync(warm->out, sizeof(double) * warm->ld, h->d_warm_io, sizeof(double) * S, sizeof(double) * B, rows, hipMemcpyDeviceToHost, s));
+  /* the warm buffer goes through a device block of its own, rows of the handle's stride, read and written in place */
+  const int64_t warm_rows = mpc_warm_rows(N);
+  WarmIO dw{nullptr, nullptr, nullptr, S, {}};
+  if (warm) {
+    if ((warm->warm_in || warm->warm_out) && warm->ld_warm < B) { g_last_error = "ld_warm < B"; return MPC_ERR_INVALID; }
+    dw.opts = warm->opts;
+    if (warm->warm_in || warm->warm_out) MPC_TRY(ensure_dev(&h->d_warm_io, sizeof(double) * (size_t)warm_rows * (size_t)S));
+    if (warm->warm_in && warm->warm_status) MPC_TRY(ensure_dev(&h->d_warm_st, sizeof(int32_t) * S));
+    if (warm->warm_in) {
+      MPC_HIP_CHECK(hipMemcpy2DAsync(h->d_warm_io, sizeof(double) * S, warm->warm_in, sizeof(double) * warm->ld_warm, sizeof(double) * B, warm_rows, hipMemcpyHostToDevice, s));
+      dw.warm_in = h->d_warm_io;
+      if (warm->warm_status) {
+        MPC_HIP_CHECK(hipMemcpyAsync(h->d_warm_st, warm->warm_status, sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
+        dw.warm_status = h->d_warm_st;
+      }
     }
+    if (warm->warm_out) dw.warm_out = h->d_warm_io;
   }
-  if (!warm) {
-    rc = launch_solve<R>(h, B, L, L, di, di + 6 * L, di + 11 * L, di + 12 * L, weights ? di + 13 * L : nullptr, d_o,
-                         traj ? d_t : nullptr, d_st, d_it, (void *)s, true, false, true);
-    if (rc != MPC_OK) return rc;
-  }
+  MPC_TRY(launch_solve<R>(h, {B, L, L, di, di + 6 * L, di + 11 * L, di + 12 * L, weights ? di + 13 * L : nullptr, d_o, traj ? d_t : nullptr, d_st, d_it},
+                          (void *)s, true, false, true, warm ? &dw : nullptr));
+  if (dw.warm_out) MPC_HIP_CHECK(hipMemcpy2DAsync(warm->warm_out, sizeof(double) * warm->ld_warm, h->d_warm_io, sizeof(double) * S, sizeof(double) * B, warm_rows, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipMemcpyAsync(ho, d_o, sizeof(R) * out_rows * L, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipStreamSynchronize(s));
   for_rows(MPC_NOUT + (traj ? 2 * N : 0), sizeof(R) * B, [=](int q) {
@@ -2496,9 +2444,8 @@ extern "C" int mpc_solve_batch_host_warm(MpcHandle *h, int64_t B, int64_t ld, co
                                          const double *yaw_lo, const double *yaw_hi, const double *weights, const double *warm_in,
                                          const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts,
                                          double *out, double *traj, int32_t *status, int32_t *iters) {
-  HostWarm hw{warm_in, warm_status, warm_out, ld_warm, {}};
-  const int rc = warm_check(h, opts, &hw.W);
-  if (rc != MPC_OK) return rc;
+  WarmIO hw{warm_in, warm_status, warm_out, ld_warm, {}};
+  MPC_TRY(warm_check(h, opts, &hw.opts));
   return solve_host<double>(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters, &hw);
 }
 

@@ -181,6 +181,78 @@ def test_in_place_buffers(pkg, golden_dir, waypoints, torch_dev):
         assert np.array_equal(got[8192][k][..., -cars:], got[cars][k][..., (np.arange(8192) % cars)[-cars:]], equal_nan=True), k
 
 
+def _three_solves_ld16(pkg, params, b, B, dev):
+    """On a fresh handle, through the C ABI with ld = ld_warm = 16 > B: the cold solve, the cold solve through the warm entry point
+    (warm_in = NULL, warm_out given) and one warm solve started from that result in place (warm_in is warm_out, warm_status is
+    status).  Every output array starts as a sentinel.  Returns the arrays of the three calls as numpy, all 16 columns."""
+    import torch
+    ld, F, I = 16, -7777.25, -12345
+    rows = pkg.warm_rows(params.N)
+
+    def inp(a):
+        a = np.atleast_2d(np.asarray(a, dtype=np.float64))
+        wide = np.zeros((a.shape[0], ld)); wide[:, :B] = a
+        return _t(wide, dev)
+    ff = lambda r: torch.full((r, ld), F, dtype=torch.float64, device=dev)
+    ii = lambda: torch.full((ld,), I, dtype=torch.int32, device=dev)
+    state, coeffs, ylo, yhi = inp(b["state"]), inp(b["coeffs"]), inp(b["yaw_lo"]), inp(b["yaw_hi"])
+    lib = pkg.library()
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    got = []
+
+    def fetch(**k):
+        torch.cuda.synchronize()
+        got.append({n: v.cpu().numpy().copy() for n, v in k.items()})
+    with pkg.BatchedMPC(params, B, device=0) as mpc:
+        out, traj, status, iters = ff(9), ff(2 * params.N), ii(), ii()
+        assert lib.mpc_solve_batch_device(mpc._h, B, ld, state.data_ptr(), coeffs.data_ptr(), ylo.data_ptr(), yhi.data_ptr(), None, out.data_ptr(),
+                                          traj.data_ptr(), status.data_ptr(), iters.data_ptr(), stream) == 0, lib.mpc_last_error()
+        fetch(out=out, traj=traj, status=status, iters=iters)
+        out, traj, status, iters, warm = ff(9), ff(2 * params.N), ii(), ii(), ff(rows)
+        assert lib.mpc_solve_batch_device_warm(mpc._h, B, ld, state.data_ptr(), coeffs.data_ptr(), ylo.data_ptr(), yhi.data_ptr(), None, None, None,
+                                               warm.data_ptr(), ld, None, out.data_ptr(), traj.data_ptr(), status.data_ptr(), iters.data_ptr(),
+                                               stream) == 0, lib.mpc_last_error()
+        fetch(out=out, traj=traj, status=status, iters=iters, warm=warm)
+        nxt = out[:6].clone().contiguous()                       # (columns from B on are never read)
+        out, traj, iters = ff(9), ff(2 * params.N), ii()
+        assert lib.mpc_solve_batch_device_warm(mpc._h, B, ld, nxt.data_ptr(), coeffs.data_ptr(), ylo.data_ptr(), yhi.data_ptr(), None, warm.data_ptr(),
+                                               status.data_ptr(), warm.data_ptr(), ld, None, out.data_ptr(), traj.data_ptr(), status.data_ptr(),
+                                               iters.data_ptr(), stream) == 0, lib.mpc_last_error()
+        fetch(out=out, traj=traj, status=status, iters=iters, warm=warm)
+    return got, F, I
+
+
+@pytest.mark.parametrize("lpi", [16, 32, 64])
+def test_wave_groups_with_a_ragged_batch(pkg, golden_dir, waypoints, torch_dev, monkeypatch, lpi):
+    """B = 7 with 16, 32 and 64 lanes per instance (MPC_WAVE_LPI overrides the whole-wave rule of small launches): the last wavefront of
+    the 16- and 32-lane launches holds groups without an instance, and the warm wave kernel runs at every group size.  The cold solve,
+    the cold solve through the warm entry point and a warm solve in place are BITWISE the lane kernel's in out, traj, status, iters and
+    the warm buffer, and with ld = 16 nothing from column 7 on is written by either kernel."""
+    params = pkg.params_from_json(os.path.join(golden_dir, "config-fast.json"))
+    params.f64_f32_start = 0
+    assert params.N == 10
+    B = 7
+    b = pkg.scenarios.lake_track_batch(B, params, waypoints, stream=3, filtered="survey")
+    monkeypatch.setenv("MPC_WAVE_LPI", str(lpi))
+    res = {}
+    for mode, limit in (("lane", "0"), ("wave", "1024")):
+        monkeypatch.setenv("MPC_WAVE_MAX_BATCH", limit)       # (read when the handle is created)
+        res[mode], F, I = _three_solves_ld16(pkg, params, b, B, torch_dev)
+    names = ("cold", "cold through the warm entry point", "warm in place")
+    for name, lane, wave in zip(names, res["lane"], res["wave"]):
+        assert sorted(lane) == sorted(wave) and ("warm" in lane) == (name != "cold")
+        for k in lane:
+            for mode, a in (("lane", lane[k]), ("wave", wave[k])):
+                assert (a[..., B:] == (I if a.dtype == np.int32 else F)).all(), (lpi, name, mode, k, "written beyond column B - 1")
+            assert np.array_equal(lane[k][..., :B], wave[k][..., :B], equal_nan=True), (lpi, name, k)
+        assert (lane["status"][:B] != I).all() and (lane["iters"][:B] != I).all(), (lpi, name)
+    # the warm entry point without a warm start is the cold solve, and the warm solve is another solve (it starts from the next state)
+    cold, viaw, warm = res["wave"]
+    for k in ("out", "traj", "status", "iters"):
+        assert np.array_equal(cold[k], viaw[k], equal_nan=True), (lpi, k)
+    assert not np.array_equal(warm["out"][:, :B], viaw["out"][:, :B])
+
+
 def test_host_entry_point_and_fallbacks(pkg, warm_twin, golden_dir, waypoints, torch_dev):
     """mpc_solve_batch_host_warm: the device entry point's results; invalid columns and garbage end as the cold solve does."""
     from warm_helpers import garbage_warm
