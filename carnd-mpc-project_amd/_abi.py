@@ -86,7 +86,8 @@ EXPORTS = ["mpc_params_default", "mpc_params_load_json", "mpc_create", "mpc_set_
            "mpc_wire_telemetry_batch_host", "mpc_telemetry_batch_host", "mpc_handle_device",
            "mpc_run_batch_host", "mpc_last_batch_id", "mpc_tail_poll", "mpc_tail_wait", "mpc_tail_stream_wait", "mpc_tail_flush", "mpc_tail_pending", "mpc_tail_info", "mpc_solve_batch_host_f32", "mpc_inflight_advice", "mpc_take_order_info",
            "mpc_warm_rows", "mpc_warm_opts_default", "mpc_solve_batch_device_warm", "mpc_solve_batch_host_warm",
-           "mpc_rollout_batch_device_warm"]
+           "mpc_rollout_batch_device_warm", "mpc_run_batch_device_warm", "mpc_run_batch_host_warm",
+           "mpc_telemetry_batch_device_warm", "mpc_telemetry_batch_host_warm", "mpc_wire_telemetry_batch_host_warm"]
 
 _lib = None
 
@@ -164,6 +165,14 @@ def library():
     L.mpc_solve_batch_host_warm.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [DP] * 8 + [C.c_int64, C.POINTER(MpcWarmOpts)] + [DP] * 4
     L.mpc_rollout_batch_device_warm.argtypes = ([C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 5 + [C.POINTER(MpcWarmOpts)] +
                                                 [DP] * 3 + [C.c_void_p])
+    # the run() path: the cold arguments up to ptsy, then warm_in, warm_status, warm_out, ld_warm, opts, then the cold outputs
+    WARM = [DP] * 3 + [C.c_int64, C.POINTER(MpcWarmOpts)]
+    L.mpc_run_batch_device_warm.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 3 + WARM + [DP] * 5 + [C.c_void_p]
+    L.mpc_run_batch_host_warm.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 3 + WARM + [DP] * 5
+    L.mpc_telemetry_batch_device_warm.argtypes = ([C.c_void_p, C.c_int64, C.c_int64, C.c_int, DP, C.c_double] + [DP] * 2 + WARM + [DP] * 3 +
+                                                  [C.c_void_p])
+    L.mpc_telemetry_batch_host_warm.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, DP, C.c_double] + [DP] * 2 + WARM + [DP] * 2
+    L.mpc_wire_telemetry_batch_host_warm.argtypes = [C.c_void_p, C.c_int64, C.POINTER(MpcWireTelemetry), DP, C.c_double] + WARM + [DP, DP]
     L.mpc_wire_parse.argtypes = [C.c_char_p, C.c_int64, C.POINTER(MpcWireTelemetry)]
     L.mpc_wire_format_steer.argtypes = [C.c_double, C.c_double, C.c_char_p, C.c_int64]
     L.mpc_wire_format_steer.restype = C.c_int64

@@ -2655,6 +2655,24 @@ MPC_HD void convert_iterate_record(Get get, Put put) {
   for (int b = 0; b < 4; b++) { put(FD::F_ZL + b, (RD)get(FS::F_ZL + b)); put(FD::F_ZU + b, (RD)get(FS::F_ZU + b)); }
 }
 
+/* The `get` of Solver::warm_point() / solve_warm() for one instance's column of a warm buffer (include/mpc_amd.h: row
+ * k * MPC_WARM_REC + f, rows `ld` doubles apart), and the one place that knows the rule of the run() path: every run() problem
+ * starts at (0, 0, 0, v, cte, epsi) in its own vehicle frame, so the previous call's record is taken as it is -- except that the psi
+ * box moves with the fit (run_pre), and warm_point() refuses a psi outside it.  psi (field 2) is therefore projected into
+ * [psi_lo, psi_hi], the caller's box of THIS problem; the push inside the relaxed bounds, the floor on the duals and every refusal
+ * stay warm_point()'s.  Comparisons, not fmin / fmax: a not-a-number stays one and is refused.  (-inf, +inf) -- the entry points
+ * whose caller poses the psi box itself -- reads the column as it is.  Nothing is written. */
+struct WarmColumn {
+  const double *col;
+  int64_t ld;
+  double psi_lo, psi_hi;
+  MPC_HD double operator()(int k, int f) const {
+    double v = col[(int64_t)(k * MPC_WARM_REC + f) * ld];
+    if (f == Layout<double>::F_S + 2) v = v < psi_lo ? psi_lo : (v > psi_hi ? psi_hi : v);
+    return v;
+  }
+};
+
 /* One instance, end to end (used by the test-only host build; the device kernel
  * drives Solver directly so that outputs go straight to their HBM arrays). */
 template <class WS, class R>

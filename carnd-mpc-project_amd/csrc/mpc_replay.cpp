@@ -4,7 +4,7 @@
  * Stands where the reference's uWS server stands (src/mpc_main.cpp:81-222), without the socket: frames are read from
  * stdin, one per line, exactly as the simulator sends them (`42["telemetry",{...}]`); the replies the reference would
  * send (`42["steer",{...}]`, `42["manual",{}]`) are written to stdout, one per line, nothing for frames it ignores.
- *     mpc_replay <config.json> [--cars B] [--extra-latency seconds] [--tcp PORT]
+ *     mpc_replay <config.json> [--cars B] [--extra-latency seconds] [--tcp PORT] [--warm]
  * With --tcp PORT the frames come from ONE TCP connection on 127.0.0.1:PORT instead of stdin (newline-delimited text, not
  * the WebSocket protocol: a relay in front of the simulator would strip that), and the replies go back on the same socket.
  * With --cars B the input is B interleaved connections: line i belongs to car i mod B, and each group of B lines is
@@ -14,6 +14,9 @@
  * group are written, in car order, once the whole group has been read: a last group with fewer than B frames is flushed at
  * end of input (with --tcp: when the peer closes its side).  The handler's running mean of its own compute time
  * (:158,:178) is replaced by the constant --extra-latency (default 0) so that a replay is reproducible.
+ * With --warm every car's solve starts from the solution of that car's previous message (mpc_wire_telemetry_batch_host_warm: one
+ * warm buffer column and one status per car; a car's first message, and one after a solve that did not succeed, start cold).
+ * Without it nothing of that exists and the output is what it always was.
  */
 #include <arpa/inet.h>
 #include <netinet/in.h>
@@ -30,16 +33,18 @@
 #include "mpc_amd.h"
 
 int main(int argc, char **argv) {
-  if (argc < 2) { fprintf(stderr, "usage: mpc_replay <config.json> [--cars B] [--extra-latency s] [--tcp PORT]\n"); return 2; }
+  if (argc < 2) { fprintf(stderr, "usage: mpc_replay <config.json> [--cars B] [--extra-latency s] [--tcp PORT] [--warm]\n"); return 2; }
   int64_t cars = 1;
   double extra = 0.0;
   int tcp_port = 0;
+  bool warm_start = false;
   for (int i = 2; i < argc; i += 2) {
     const bool has_value = i + 1 < argc;
-    if (has_value && !strcmp(argv[i], "--cars")) cars = atoll(argv[i + 1]);
+    if (!strcmp(argv[i], "--warm")) { warm_start = true; i--; }
+    else if (has_value && !strcmp(argv[i], "--cars")) cars = atoll(argv[i + 1]);
     else if (has_value && !strcmp(argv[i], "--extra-latency")) extra = atof(argv[i + 1]);
     else if (has_value && !strcmp(argv[i], "--tcp")) tcp_port = atoi(argv[i + 1]);
-    else { fprintf(stderr, "mpc_replay: unknown or incomplete option '%s'\nusage: mpc_replay <config.json> [--cars B] [--extra-latency s] [--tcp PORT]\n", argv[i]); return 2; }
+    else { fprintf(stderr, "mpc_replay: unknown or incomplete option '%s'\nusage: mpc_replay <config.json> [--cars B] [--extra-latency s] [--tcp PORT] [--warm]\n", argv[i]); return 2; }
   }
   if (cars < 1) { fprintf(stderr, "mpc_replay: --cars must be >= 1\n"); return 2; }
   /* frame source / reply sink: stdin/stdout, or one TCP connection */
@@ -82,6 +87,10 @@ int main(int argc, char **argv) {
   if (mpc_create(&p, -1, cars, &h) != MPC_OK) { fprintf(stderr, "mpc_create: %s\n", mpc_last_error()); return 1; }
   std::vector<double> prev((size_t)cars, 0.0), cmd((size_t)(2 * cars));
   std::vector<int32_t> status((size_t)cars);
+  /* --warm: column c of `warm` and wstat[c] belong to car c (any status but success: the car starts cold) */
+  const int64_t warm_rows = warm_start ? mpc_warm_rows(p.N) : 0;
+  std::vector<double> warm((size_t)(warm_rows * cars));
+  std::vector<int32_t> wstat((size_t)cars, MPC_STATUS_MAXITER);
   std::vector<MpcWireTelemetry> tel;
   std::vector<int64_t> who;                       /* car of each telemetry frame of the current group */
   std::vector<std::string> replies;
@@ -95,7 +104,24 @@ int main(int argc, char **argv) {
       for (size_t k = 0; k < tel.size(); k++) pt[k] = prev[(size_t)who[k]];
       std::vector<double> c(2 * tel.size());
       std::vector<int32_t> st(tel.size());
-      if (mpc_wire_telemetry_batch_host(h, (int64_t)tel.size(), tel.data(), pt.data(), extra, c.data(), st.data()) != MPC_OK) {
+      if (warm_start) {
+        /* the group's cars may be a subset: their columns packed, solved in place, and put back */
+        const int64_t nb = (int64_t)tel.size();
+        std::vector<double> w((size_t)(warm_rows * nb));
+        std::vector<int32_t> ws((size_t)nb);
+        for (int64_t k = 0; k < nb; k++) {
+          ws[(size_t)k] = wstat[(size_t)who[k]];
+          for (int64_t r = 0; r < warm_rows; r++) w[(size_t)(r * nb + k)] = warm[(size_t)(r * cars + who[k])];
+        }
+        if (mpc_wire_telemetry_batch_host_warm(h, nb, tel.data(), pt.data(), extra, w.data(), ws.data(), w.data(), nb, nullptr, c.data(), st.data()) != MPC_OK) {
+          fprintf(stderr, "mpc_wire_telemetry_batch_host_warm: %s\n", mpc_last_error());
+          return 1;
+        }
+        for (int64_t k = 0; k < nb; k++) {
+          wstat[(size_t)who[k]] = st[(size_t)k];
+          for (int64_t r = 0; r < warm_rows; r++) warm[(size_t)(r * cars + who[k])] = w[(size_t)(r * nb + k)];
+        }
+      } else if (mpc_wire_telemetry_batch_host(h, (int64_t)tel.size(), tel.data(), pt.data(), extra, c.data(), st.data()) != MPC_OK) {
         fprintf(stderr, "mpc_wire_telemetry_batch_host: %s\n", mpc_last_error());
         return 1;
       }

@@ -198,6 +198,7 @@ struct MpcPhaseWarm : MpcPhase {
   double *warm_out;               /* nullptr: nothing is written */
   int64_t ld_warm;
   MpcWarmOpts wopts;
+  int32_t psi_box;                /* the run() path: psi of the records is projected into the instance's [yaw_lo, yaw_hi] (mpc::WarmColumn) */
 };
 
 /* The take-order key of every instance of a launch (csrc/mpc_take_key.h) and the bins' lists: one thread per instance, a wave
@@ -408,9 +409,8 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
             if constexpr (WARM) {
               if (warm_cand) {
                 if (s0 == MPC_STATUS_SUCCESS) {
-                  const double *wi = T.warm_in + i;
-                  const int64_t lw = T.ld_warm;
-                  warm = S.warm_point([wi, lw](int k, int f) -> R { return wi[(int64_t)(k * MPC_WARM_REC + f) * lw]; }, T.wopts);
+                  const bool box = T.psi_box != 0;
+                  warm = S.warm_point(mpc::WarmColumn{T.warm_in + i, T.ld_warm, box ? (double)yaw_lo[i] : -HUGE_VAL, box ? (double)yaw_hi[i] : HUGE_VAL}, T.wopts);
                 }
                 if (!warm) S.start_point();     /* set-up left slot 0 to the warm point, and the column holds no iterate of this NLP */
               }
@@ -889,7 +889,7 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_wave_warm_kernel(
     const R *__restrict__ coeffs, const R *__restrict__ yaw_lo, const R *__restrict__ yaw_hi,
     const R *__restrict__ weights, R *__restrict__ out, R *__restrict__ traj,
     int32_t *status, int32_t *__restrict__ iters, const double *warm_in, const int32_t *warm_status, double *warm_out,
-    const int64_t ld_warm, const MpcWarmOpts wopts) {
+    const int64_t ld_warm, const MpcWarmOpts wopts, const int psi_box) {
   extern __shared__ double smem[];
   constexpr int G = 64 / LPI;
   using WS = mpc::LdsWorkspace<R, G>;
@@ -912,8 +912,8 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_wave_warm_kernel(
   const bool warm = warm_in != nullptr && (warm_status == nullptr || warm_status[i] == MPC_STATUS_SUCCESS);
   int r = S.setup(st, cf, yaw_lo[i], yaw_hi[i], w, true);
   if (r == MPC_STATUS_SUCCESS) {
-    const double *wi = warm_in + i;
-    r = S.solve_warm(warm, [wi, ld_warm](int k, int f) -> R { return wi[(int64_t)(k * MPC_WARM_REC + f) * ld_warm]; }, wopts);
+    /* (psi_box: the run() path, see mpc::WarmColumn) */
+    r = S.solve_warm(warm, mpc::WarmColumn{warm_in + i, ld_warm, psi_box ? (double)yaw_lo[i] : -HUGE_VAL, psi_box ? (double)yaw_hi[i] : HUGE_VAL}, wopts);
   }
   if (S.wlane == 0) {
     R *o = out + i;
@@ -1834,6 +1834,7 @@ struct SolveIO {
 /* ... and what a warm call brings on top: the warm buffers (see MpcPhaseWarm) and the options in effect (warm_check) */
 struct WarmIO {
   const double *warm_in; const int32_t *warm_status; double *warm_out; int64_t ld_warm; MpcWarmOpts opts;
+  bool psi_box = false;   /* the run() path: the records' psi goes into this call's psi box first (mpc::WarmColumn) */
 };
 /* ... and where a deferring launch hands its stragglers: its batch's slot of the ring and its fresh queue */
 struct TailPlace {
@@ -1896,7 +1897,7 @@ static int launch_wave(MpcHandle *h, const SolveIO<R> &io, hipStream_t s, bool s
     if constexpr (sizeof(R) == 8) {
       if (warm)
         return launch_kernel(mpc_solve_wave_warm_kernel<R, LPI>, grid, G * per, s, h, io, warm->warm_in, warm->warm_status, warm->warm_out,
-                             warm->ld_warm, warm->opts);
+                             warm->ld_warm, warm->opts, warm->psi_box ? 1 : 0);
       if (soc)
         return launch_kernel(mpc_solve_wave_kernel<R, LPI, true>, grid, G * (per + (size_t)mpc::soc_fields_per_instance(h->params.N) * sizeof(R)), s, h, io);
     }
@@ -1930,7 +1931,7 @@ static int launch_lanes(MpcHandle *h, LaneBuild build, const SolveIO<RIO> &io, h
   if (build == LaneBuild::mixed_f64) return with_bool(soc, [&](auto soc_build) { return go(yes, double{}, float{}, soc_build, no, h->ws_stride_f64, T); });
   return with_bool(h->staging, [&](auto staging) {
     if constexpr (sizeof(RIO) == 8) {
-      if (warm) return go(staging, RIO{}, RIO{}, no, yes, h->ws_stride, MpcPhaseWarm{T, warm->warm_in, warm->warm_status, warm->warm_out, warm->ld_warm, warm->opts});
+      if (warm) return go(staging, RIO{}, RIO{}, no, yes, h->ws_stride, MpcPhaseWarm{T, warm->warm_in, warm->warm_status, warm->warm_out, warm->ld_warm, warm->opts, warm->psi_box ? 1 : 0});
       if (soc) return go(staging, RIO{}, RIO{}, yes, no, h->ws_stride, T);
     }
     return go(staging, RIO{}, RIO{}, no, no, h->ws_stride, T);
@@ -2194,11 +2195,14 @@ extern "C" int mpc_solve_batch_device_f32(MpcHandle *h, int64_t B, int64_t ld, c
   return launch_solve<float>(h, {B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters}, stream_, true, true);
 }
 
-/* run() for a batch; `tel` selects the telemetry rows as input (with latency compensation) and `cmd` the reply */
+/* run() for a batch; `tel` selects the telemetry rows as input (with latency compensation) and `cmd` the reply.  warm: a warm call
+ * (warm_check has passed) -- the same three kernels, the solve started from the previous call's records with their psi projected
+ * into the box run_pre derives for this call (mpc::WarmColumn). */
 static int run_impl(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, bool tel, double extra, double *ptsx,
                     double *ptsy, double *out8, double *cmd, double *traj, int32_t *status, int32_t *iters, double *pre,
-                    void *stream_) {
+                    void *stream_, const WarmIO *warm = nullptr) {
   MPC_TRY(check_batch(h, B, ld));
+  if (warm && (warm->warm_in || warm->warm_out) && warm->ld_warm < B) { g_last_error = "ld_warm < B"; return MPC_ERR_INVALID; }
   if (npts < 3 || npts > mpc::RUN_MAX_PTS) { g_last_error = "npts must be 3..8"; return MPC_ERR_INVALID; }
   if (B == 0) { h->last_B = 0; return MPC_OK; }
   if (!pose || !ptsx || !ptsy || !(out8 || cmd) || !status) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
@@ -2216,7 +2220,8 @@ static int run_impl(MpcHandle *h, int64_t B, int64_t ld, int npts, const double 
   if (tel) hipLaunchKernelGGL(mpc_run_pre_kernel<true>, dim3(grid), dim3(256), 0, s, h->params, B, ld, npts, pose, extra, ptsx, ptsy, d_pre, S);
   else hipLaunchKernelGGL(mpc_run_pre_kernel<false>, dim3(grid), dim3(256), 0, s, h->params, B, ld, npts, pose, 0.0, ptsx, ptsy, d_pre, S);
   MPC_HIP_CHECK(hipGetLastError());
-  MPC_TRY(launch_solve<double>(h, {B, S, ld, d_pre, d_pre + 6 * S, d_pre + 11 * S, d_pre + 12 * S, nullptr, h->d_run9, traj, status, iters}, stream_));
+  MPC_TRY(launch_solve<double>(h, {B, S, ld, d_pre, d_pre + 6 * S, d_pre + 11 * S, d_pre + 12 * S, nullptr, h->d_run9, traj, status, iters}, stream_, true, false,
+                               false, warm));
   hipLaunchKernelGGL(mpc_run_post_kernel, dim3(grid), dim3(256), 0, s, h->params, B, d_pre, S, h->d_run9, ld, out8, cmd, ld);
   MPC_HIP_CHECK(hipGetLastError());
   if (pre) MPC_HIP_CHECK(hipMemcpy2DAsync(pre, sizeof(double) * ld, d_pre, sizeof(double) * S, sizeof(double) * B, 15, hipMemcpyDeviceToDevice, s));
@@ -2236,14 +2241,68 @@ extern "C" int mpc_telemetry_batch_device(MpcHandle *h, int64_t B, int64_t ld, i
   return run_impl(h, B, ld, npts, tel, true, extra_latency, ptsx, ptsy, out8, cmd, nullptr, status, nullptr, nullptr, stream_);
 }
 
+/* run() and the telemetry handler, warm-started from the previous call (include/mpc_amd.h, "warm start on the run() path") */
+static WarmIO run_warm_io(const double *warm_in, const int32_t *warm_status, double *warm_out, int64_t ld_warm) {
+  WarmIO w{warm_in, warm_status, warm_out, ld_warm, {}};
+  w.psi_box = true;
+  return w;
+}
+
+extern "C" int mpc_run_batch_device_warm(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx,
+                                         double *ptsy, const double *warm_in, const int32_t *warm_status, double *warm_out,
+                                         int64_t ld_warm, const MpcWarmOpts *opts, double *out8, double *traj, int32_t *status,
+                                         int32_t *iters, double *pre, void *stream_) {
+  WarmIO warm = run_warm_io(warm_in, warm_status, warm_out, ld_warm);
+  MPC_TRY(warm_check(h, opts, &warm.opts));
+  if (B > 0 && !out8) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
+  return run_impl(h, B, ld, npts, pose, false, 0.0, ptsx, ptsy, out8, nullptr, traj, status, iters, pre, stream_, &warm);
+}
+
+extern "C" int mpc_telemetry_batch_device_warm(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
+                                               double *ptsx, double *ptsy, const double *warm_in, const int32_t *warm_status,
+                                               double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts, double *cmd, double *out8,
+                                               int32_t *status, void *stream_) {
+  WarmIO warm = run_warm_io(warm_in, warm_status, warm_out, ld_warm);
+  MPC_TRY(warm_check(h, opts, &warm.opts));
+  if (B > 0 && !cmd) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
+  return run_impl(h, B, ld, npts, tel, true, extra_latency, ptsx, ptsy, out8, cmd, nullptr, status, nullptr, nullptr, stream_, &warm);
+}
+
+/* The host arrays of a warm call (`hw`) on the device: the warm buffer goes through a device block of its own, rows of the handle's
+ * stride, read and written in place, with the status it came with beside it.  *dw: what the launch gets. */
+static int warm_host_in(MpcHandle *h, int64_t B, const WarmIO &hw, hipStream_t s, WarmIO *dw) {
+  const int64_t S = h->io_stride, warm_rows = mpc_warm_rows(h->params.N);
+  *dw = WarmIO{nullptr, nullptr, nullptr, S, hw.opts};
+  dw->psi_box = hw.psi_box;
+  if ((hw.warm_in || hw.warm_out) && hw.ld_warm < B) { g_last_error = "ld_warm < B"; return MPC_ERR_INVALID; }
+  if (hw.warm_in || hw.warm_out) MPC_TRY(ensure_dev(&h->d_warm_io, sizeof(double) * (size_t)warm_rows * (size_t)S));
+  if (hw.warm_in && hw.warm_status) MPC_TRY(ensure_dev(&h->d_warm_st, sizeof(int32_t) * S));
+  if (hw.warm_in) {
+    MPC_HIP_CHECK(hipMemcpy2DAsync(h->d_warm_io, sizeof(double) * S, hw.warm_in, sizeof(double) * hw.ld_warm, sizeof(double) * B, warm_rows, hipMemcpyHostToDevice, s));
+    dw->warm_in = h->d_warm_io;
+    if (hw.warm_status) {
+      MPC_HIP_CHECK(hipMemcpyAsync(h->d_warm_st, hw.warm_status, sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
+      dw->warm_status = h->d_warm_st;
+    }
+  }
+  if (hw.warm_out) dw->warm_out = h->d_warm_io;
+  return MPC_OK;
+}
+static int warm_host_out(MpcHandle *h, int64_t B, const WarmIO &hw, hipStream_t s) {
+  if (!hw.warm_out) return MPC_OK;
+  MPC_HIP_CHECK(hipMemcpy2DAsync(hw.warm_out, sizeof(double) * hw.ld_warm, h->d_warm_io, sizeof(double) * h->io_stride, sizeof(double) * B,
+                                 mpc_warm_rows(h->params.N), hipMemcpyDeviceToHost, s));
+  return MPC_OK;
+}
+
 /* used by the other translation units of the library (mpc_wire.cpp): the error text of this thread */
 extern "C" void mpc_internal_set_error(const char *msg) { g_last_error = msg ? msg : ""; }
 
 /* The telemetry handler for host arrays: one copy in, the kernels, one copy out, on the handle's own device and stream
  * (whatever the caller's current device is), staging kept on the handle.  rows of `tel`, `ptsx`, `ptsy` as in
  * mpc_telemetry_batch_device with leading dimension ld; the waypoint arrays are inputs only here. */
-extern "C" int mpc_telemetry_batch_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
-                                        const double *ptsx, const double *ptsy, double *cmd, int32_t *status) {
+static int telemetry_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency, const double *ptsx,
+                          const double *ptsy, double *cmd, int32_t *status, const WarmIO *warm) {
   MPC_TRY(check_batch(h, B, ld));
   if (npts < 3 || npts > mpc::RUN_MAX_PTS) { g_last_error = "npts must be 3..8"; return MPC_ERR_INVALID; }
   if (B == 0) { h->last_B = 0; return MPC_OK; }
@@ -2257,19 +2316,35 @@ extern "C" int mpc_telemetry_batch_host(MpcHandle *h, int64_t B, int64_t ld, int
   MPC_HIP_CHECK(hipMemcpy2DAsync(d, sizeof(double) * L, tel, sizeof(double) * ld, sizeof(double) * B, 6, hipMemcpyHostToDevice, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(d + 6 * L, sizeof(double) * L, ptsx, sizeof(double) * ld, sizeof(double) * B, npts, hipMemcpyHostToDevice, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(d + (6 + npts) * L, sizeof(double) * L, ptsy, sizeof(double) * ld, sizeof(double) * B, npts, hipMemcpyHostToDevice, s));
-  const int rc = mpc_telemetry_batch_device(h, B, L, npts, d, extra_latency, d + 6 * L, d + (6 + npts) * L, d_cmd, nullptr, d_st, (void *)s);
-  if (rc != MPC_OK) return rc;
+  WarmIO dw{};
+  if (warm) MPC_TRY(warm_host_in(h, B, *warm, s, &dw));
+  MPC_TRY(run_impl(h, B, L, npts, d, true, extra_latency, d + 6 * L, d + (6 + npts) * L, nullptr, d_cmd, nullptr, d_st, nullptr, nullptr, (void *)s,
+                   warm ? &dw : nullptr));
+  if (warm) MPC_TRY(warm_host_out(h, B, *warm, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(cmd, sizeof(double) * ld, d_cmd, sizeof(double) * L, sizeof(double) * B, 2, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipMemcpyAsync(status, d_st, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipStreamSynchronize(s));
   return MPC_OK;
 }
 
+extern "C" int mpc_telemetry_batch_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
+                                        const double *ptsx, const double *ptsy, double *cmd, int32_t *status) {
+  return telemetry_host(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, cmd, status, nullptr);
+}
+
+extern "C" int mpc_telemetry_batch_host_warm(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
+                                             const double *ptsx, const double *ptsy, const double *warm_in, const int32_t *warm_status,
+                                             double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts, double *cmd, int32_t *status) {
+  WarmIO hw = run_warm_io(warm_in, warm_status, warm_out, ld_warm);
+  MPC_TRY(warm_check(h, opts, &hw.opts));
+  return telemetry_host(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, cmd, status, &hw);
+}
+
 /* MPC::run() for host arrays (the drop-in's B = 1 case, include/mpc_drop_in.hpp): one copy in, the three kernels of
  * mpc_run_batch_device on the handle's own device and stream, one copy out; synchronises.  ptsx / ptsy are transformed in place
  * like the reference does (MPC.cpp:329; mpc_main.cpp:189-190 relies on it). */
-extern "C" int mpc_run_batch_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx, double *ptsy,
-                                  double *out8, double *traj, int32_t *status, int32_t *iters, double *pre) {
+static int run_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx, double *ptsy, double *out8,
+                    double *traj, int32_t *status, int32_t *iters, double *pre, const WarmIO *warm) {
   MPC_TRY(check_batch(h, B, ld));
   if (npts < 3 || npts > mpc::RUN_MAX_PTS) { g_last_error = "npts must be 3..8"; return MPC_ERR_INVALID; }
   if (h->params.precision != MPC_PRECISION_F64) { g_last_error = "run() entry points are fp64 only"; return MPC_ERR_INVALID; }
@@ -2286,8 +2361,10 @@ extern "C" int mpc_run_batch_host(MpcHandle *h, int64_t B, int64_t ld, int npts,
   MPC_HIP_CHECK(hipMemcpy2DAsync(d, sizeof(double) * L, pose, sizeof(double) * ld, sizeof(double) * B, 6, hipMemcpyHostToDevice, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(d_px, sizeof(double) * L, ptsx, sizeof(double) * ld, sizeof(double) * B, npts, hipMemcpyHostToDevice, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(d_py, sizeof(double) * L, ptsy, sizeof(double) * ld, sizeof(double) * B, npts, hipMemcpyHostToDevice, s));
-  const int rc = mpc_run_batch_device(h, B, L, npts, d, d_px, d_py, d_o8, traj ? d_tr : nullptr, d_st, d_it, d_pre, (void *)s);
-  if (rc != MPC_OK) return rc;
+  WarmIO dw{};
+  if (warm) MPC_TRY(warm_host_in(h, B, *warm, s, &dw));
+  MPC_TRY(run_impl(h, B, L, npts, d, false, 0.0, d_px, d_py, d_o8, nullptr, traj ? d_tr : nullptr, d_st, d_it, d_pre, (void *)s, warm ? &dw : nullptr));
+  if (warm) MPC_TRY(warm_host_out(h, B, *warm, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(ptsx, sizeof(double) * ld, d_px, sizeof(double) * L, sizeof(double) * B, npts, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(ptsy, sizeof(double) * ld, d_py, sizeof(double) * L, sizeof(double) * B, npts, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(out8, sizeof(double) * ld, d_o8, sizeof(double) * L, sizeof(double) * B, 8, hipMemcpyDeviceToHost, s));
@@ -2297,6 +2374,19 @@ extern "C" int mpc_run_batch_host(MpcHandle *h, int64_t B, int64_t ld, int npts,
   if (iters) MPC_HIP_CHECK(hipMemcpyAsync(iters, d_it, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipStreamSynchronize(s));
   return MPC_OK;
+}
+
+extern "C" int mpc_run_batch_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx, double *ptsy,
+                                  double *out8, double *traj, int32_t *status, int32_t *iters, double *pre) {
+  return run_host(h, B, ld, npts, pose, ptsx, ptsy, out8, traj, status, iters, pre, nullptr);
+}
+
+extern "C" int mpc_run_batch_host_warm(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx, double *ptsy,
+                                       const double *warm_in, const int32_t *warm_status, double *warm_out, int64_t ld_warm,
+                                       const MpcWarmOpts *opts, double *out8, double *traj, int32_t *status, int32_t *iters, double *pre) {
+  WarmIO hw = run_warm_io(warm_in, warm_status, warm_out, ld_warm);
+  MPC_TRY(warm_check(h, opts, &hw.opts));
+  return run_host(h, B, ld, npts, pose, ptsx, ptsy, out8, traj, status, iters, pre, &hw);
 }
 
 /* the device a handle lives on (mpc_create's `device`, resolved) */
@@ -2401,26 +2491,11 @@ static int solve_host(MpcHandle *h, int64_t B, int64_t ld, const R *state, const
   R *d_o = d_oblk, *d_t = d_o + MPC_NOUT * L;
   int32_t *d_st = (int32_t *)(d_o + (out_rows - kIntRows) * L), *d_it = d_st + L;
   /* the warm buffer goes through a device block of its own, rows of the handle's stride, read and written in place */
-  const int64_t warm_rows = mpc_warm_rows(N);
   WarmIO dw{nullptr, nullptr, nullptr, S, {}};
-  if (warm) {
-    if ((warm->warm_in || warm->warm_out) && warm->ld_warm < B) { g_last_error = "ld_warm < B"; return MPC_ERR_INVALID; }
-    dw.opts = warm->opts;
-    if (warm->warm_in || warm->warm_out) MPC_TRY(ensure_dev(&h->d_warm_io, sizeof(double) * (size_t)warm_rows * (size_t)S));
-    if (warm->warm_in && warm->warm_status) MPC_TRY(ensure_dev(&h->d_warm_st, sizeof(int32_t) * S));
-    if (warm->warm_in) {
-      MPC_HIP_CHECK(hipMemcpy2DAsync(h->d_warm_io, sizeof(double) * S, warm->warm_in, sizeof(double) * warm->ld_warm, sizeof(double) * B, warm_rows, hipMemcpyHostToDevice, s));
-      dw.warm_in = h->d_warm_io;
-      if (warm->warm_status) {
-        MPC_HIP_CHECK(hipMemcpyAsync(h->d_warm_st, warm->warm_status, sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
-        dw.warm_status = h->d_warm_st;
-      }
-    }
-    if (warm->warm_out) dw.warm_out = h->d_warm_io;
-  }
+  if (warm) MPC_TRY(warm_host_in(h, B, *warm, s, &dw));
   MPC_TRY(launch_solve<R>(h, {B, L, L, di, di + 6 * L, di + 11 * L, di + 12 * L, weights ? di + 13 * L : nullptr, d_o, traj ? d_t : nullptr, d_st, d_it},
                           (void *)s, true, false, true, warm ? &dw : nullptr));
-  if (dw.warm_out) MPC_HIP_CHECK(hipMemcpy2DAsync(warm->warm_out, sizeof(double) * warm->ld_warm, h->d_warm_io, sizeof(double) * S, sizeof(double) * B, warm_rows, hipMemcpyDeviceToHost, s));
+  if (warm) MPC_TRY(warm_host_out(h, B, *warm, s));
   MPC_HIP_CHECK(hipMemcpyAsync(ho, d_o, sizeof(R) * out_rows * L, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipStreamSynchronize(s));
   for_rows(MPC_NOUT + (traj ? 2 * N : 0), sizeof(R) * B, [=](int q) {

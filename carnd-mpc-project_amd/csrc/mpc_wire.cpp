@@ -131,8 +131,12 @@ extern "C" int64_t mpc_wire_format_manual(char *buf, int64_t cap) {
  * is the mean handler time the reference adds to Config::lookahead (:158).  cmd is [2][B]: steering_angle row, throttle
  * row.  Runs on the handle's own device and stream (mpc_telemetry_batch_host), whatever the caller's current device. */
 extern "C" void mpc_internal_set_error(const char *msg);
-extern "C" int mpc_wire_telemetry_batch_host(MpcHandle *h, int64_t B, const MpcWireTelemetry *tel, const double *prev_throttle,
-                                             double extra_latency, double *cmd, int32_t *status) {
+/* (warm: the buffers and options of mpc_wire_telemetry_batch_host_warm, handed on to mpc_telemetry_batch_host_warm) */
+struct WireWarm {
+  const double *warm_in; const int32_t *warm_status; double *warm_out; int64_t ld_warm; const MpcWarmOpts *opts;
+};
+static int wire_telemetry(MpcHandle *h, int64_t B, const MpcWireTelemetry *tel, const double *prev_throttle, double extra_latency,
+                          double *cmd, int32_t *status, const WireWarm *warm) {
   if (!h || B < 0 || (B > 0 && (!tel || !cmd || !status))) { mpc_internal_set_error("mpc_wire_telemetry_batch_host: NULL argument or B < 0"); return MPC_ERR_INVALID; }
   if (B == 0) return MPC_OK;
   const int npts = tel[0].npts;
@@ -149,5 +153,23 @@ extern "C" int mpc_wire_telemetry_batch_host(MpcHandle *h, int64_t B, const MpcW
     host[4 * B + i] = t.steering_angle; host[5 * B + i] = prev_throttle ? prev_throttle[i] : 0.0;
     for (int q = 0; q < npts; q++) { host[(6 + q) * B + i] = t.ptsx[q]; host[(6 + npts + q) * B + i] = t.ptsy[q]; }
   }
+  if (warm)
+    return mpc_telemetry_batch_host_warm(h, B, B, npts, host.data(), extra_latency, host.data() + 6 * B, host.data() + (6 + npts) * B, warm->warm_in,
+                                         warm->warm_status, warm->warm_out, warm->ld_warm, warm->opts, cmd, status);
   return mpc_telemetry_batch_host(h, B, B, npts, host.data(), extra_latency, host.data() + 6 * B, host.data() + (6 + npts) * B, cmd, status);
+}
+
+extern "C" int mpc_wire_telemetry_batch_host(MpcHandle *h, int64_t B, const MpcWireTelemetry *tel, const double *prev_throttle,
+                                             double extra_latency, double *cmd, int32_t *status) {
+  return wire_telemetry(h, B, tel, prev_throttle, extra_latency, cmd, status, nullptr);
+}
+
+/* The same, each connection warm-started from its own previous message (mpc_telemetry_batch_host_warm; the warm arguments are that
+ * entry point's, column i belonging to connection i). */
+extern "C" int mpc_wire_telemetry_batch_host_warm(MpcHandle *h, int64_t B, const MpcWireTelemetry *tel, const double *prev_throttle,
+                                                  double extra_latency, const double *warm_in, const int32_t *warm_status,
+                                                  double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts, double *cmd,
+                                                  int32_t *status) {
+  const WireWarm w{warm_in, warm_status, warm_out, ld_warm, opts};
+  return wire_telemetry(h, B, tel, prev_throttle, extra_latency, cmd, status, &w);
 }

@@ -395,6 +395,28 @@ int mpc_solve_batch_host_warm(MpcHandle *h, int64_t B, int64_t ld, const double 
 int mpc_rollout_batch_device_warm(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
                                   const double *yaw_lo, const double *yaw_hi, const double *weights, const MpcWarmOpts *opts,
                                   double *hist, int32_t *status, int32_t *iters, void *stream);
+/* Warm start on the run() path: what a telemetry handler calls once per message (mpc_main.cpp).  Every run() problem starts at
+ * (0, 0, 0, v, cte, epsi) in its own vehicle frame, and from one message to the next the solution looks almost the same in that
+ * frame, so the previous call's records are taken as they are, unshifted by default -- with one change: the psi box moves with the
+ * road fit (MPC.cpp:345-352), so psi (field 2 of every record) is projected into the [yaw_lo, yaw_hi] this call derives before the
+ * rules above see it (a not-a-number stays one and is refused).  warm_in is only read.  The library remembers no poses: a rigid
+ * re-framing of the records was measured and does not beat this.  Each entry point is its cold form plus
+ * warm_in, warm_status, warm_out, ld_warm, opts, with every convention of mpc_solve_batch_device_warm (NULL warm_in: a cold call
+ * that writes warm_out, bitwise the cold entry point; in-place buffers; the refusals). */
+int mpc_run_batch_device_warm(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx, double *ptsy,
+                              const double *warm_in, const int32_t *warm_status, double *warm_out, int64_t ld_warm,
+                              const MpcWarmOpts *opts, double *out8, double *traj, int32_t *status, int32_t *iters, double *pre,
+                              void *stream);
+int mpc_run_batch_host_warm(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx, double *ptsy,
+                            const double *warm_in, const int32_t *warm_status, double *warm_out, int64_t ld_warm,
+                            const MpcWarmOpts *opts, double *out8, double *traj, int32_t *status, int32_t *iters, double *pre);
+int mpc_telemetry_batch_device_warm(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
+                                    double *ptsx, double *ptsy, const double *warm_in, const int32_t *warm_status, double *warm_out,
+                                    int64_t ld_warm, const MpcWarmOpts *opts, double *cmd, double *out8, int32_t *status,
+                                    void *stream);
+int mpc_telemetry_batch_host_warm(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
+                                  const double *ptsx, const double *ptsy, const double *warm_in, const int32_t *warm_status,
+                                  double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts, double *cmd, int32_t *status);
 /* ---- the wire side of the handler (src/mpc_main.cpp:26-36, 81-222, DATA.md:5-16) --------
  * Everything between the bytes of a simulator frame and the bytes of the reply; the WebSocket server itself is out of
  * scope.  See csrc/mpc_wire.cpp. */
@@ -417,6 +439,10 @@ int64_t mpc_wire_format_manual(char *buf, int64_t cap);
  * prev_throttle[B] or NULL: throttle of each connection's previous reply; cmd [2][B]: steering_angle row, throttle row. */
 int mpc_wire_telemetry_batch_host(MpcHandle *h, int64_t B, const MpcWireTelemetry *tel, const double *prev_throttle,
                                   double extra_latency, double *cmd, int32_t *status);
+/* The same through mpc_telemetry_batch_host_warm: column i of the warm buffers belongs to connection i. */
+int mpc_wire_telemetry_batch_host_warm(MpcHandle *h, int64_t B, const MpcWireTelemetry *tel, const double *prev_throttle,
+                                       double extra_latency, const double *warm_in, const int32_t *warm_status, double *warm_out,
+                                       int64_t ld_warm, const MpcWarmOpts *opts, double *cmd, int32_t *status);
 /* ---- deferred tails (MpcParams.tail_cut > 0) ----------------------------------------------------------------
  * A launch lasts as long as its slowest instance; on heavy-tailed workloads one 200-iteration straggler prices 65 536
  * solves.  With tail_cut = n the launch of mpc_solve_batch_device(_f32) hands every instance that is still running after

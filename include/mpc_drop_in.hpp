@@ -268,11 +268,16 @@ class MPC {                                                            /* MPC.h:
   bool warmStart = false, haveWarm = false;
   std::vector<double> warmBuf;
   int32_t warmStatus = 0, lastIters = 0;
+  /* ... and of run(): a buffer and status of its own, because run()'s records live in the vehicle frame of its previous call
+   * and solve()'s in the frame of the road polynomial */
+  bool haveRunWarm = false;
+  std::vector<double> runWarmBuf;
+  int32_t runWarmStatus = 0;
 
   void ensure(int64_t B) {
     const MpcParams p = Config::snapshot();
     if (handle && (B > capacity || p.N != handleN || p.f64_f32_start != handleFp32Start)) { mpc_destroy(handle); handle = nullptr; }
-    if (p.N != handleN) haveWarm = false;
+    if (p.N != handleN) haveWarm = haveRunWarm = false;
     if (!handle) {
       capacity = B < 1 ? 1 : B; handleN = p.N; handleFp32Start = p.f64_f32_start;
       int rc = mpc_create(&p, -1, capacity, &handle);
@@ -294,12 +299,15 @@ class MPC {                                                            /* MPC.h:
    * that did not succeed, and a warm attempt that does not, fall back to the cold solve inside the library.  Off by default (every
    * solve then starts at the reference's zero start point).  Switching it on, a change of Config::N and resetWarmStart() forget the
    * stored solution.  Needs a handle whose solve is one launch: Config::fp32Start = 0 at horizons of MPC_F32_START_AUTO_N or
-   * more, Config::maxSoc = 0; the library refuses otherwise and solve() throws.  run() always starts cold (it re-fits the road in
-   * a new vehicle frame every call). */
-  void setWarmStart(bool on) { if (on != warmStart) haveWarm = false; warmStart = on; }
+   * more, Config::maxSoc = 0; the library refuses otherwise and solve() / run() throw.
+   * run() -- what a telemetry handler calls once per message -- warm-starts too, from the run() before it
+   * (mpc_run_batch_host_warm): every run() problem starts at (0, 0, 0, v, cte, epsi) in its own vehicle frame, so the previous
+   * records are taken as they are, their psi projected into the psi box of the new fit.  It keeps a stored solution of its own
+   * (the two live in different frames), forgotten under the same conditions. */
+  void setWarmStart(bool on) { if (on != warmStart) haveWarm = haveRunWarm = false; warmStart = on; }
   bool getWarmStart() const { return warmStart; }
-  void resetWarmStart() { haveWarm = false; }
-  int lastIterations() const { return (int)lastIters; }   /* interior-point iterations of the latest solve() */
+  void resetWarmStart() { haveWarm = haveRunWarm = false; }
+  int lastIterations() const { return (int)lastIters; }   /* interior-point iterations of the latest solve() or run() */
 
   /* MPC::solve, MPC.h:42-43 / MPC.cpp:183-325.  `state` = {x,y,psi,v,cte,epsi}; target_velocity and dir
    * are accepted and ignored exactly as FG_eval ignores them.  Returns
@@ -350,8 +358,16 @@ class MPC {                                                            /* MPC.h:
     double out8[8], pre[15];
     std::vector<double> traj(2 * N);
     int32_t status = 0, iters = 0;
-    const int rc = mpc_run_batch_host(handle, 1, 1, npts, pose, ptsx.data(), ptsy.data(), out8, traj.data(), &status, &iters, pre);
+    int rc;
+    if (warmStart) {
+      const int64_t rows = mpc_warm_rows(N);
+      if ((int64_t)runWarmBuf.size() != rows) { runWarmBuf.assign((size_t)rows, 0.0); haveRunWarm = false; }
+      rc = mpc_run_batch_host_warm(handle, 1, 1, npts, pose, ptsx.data(), ptsy.data(), haveRunWarm ? runWarmBuf.data() : NULL,
+                                   haveRunWarm ? &runWarmStatus : NULL, runWarmBuf.data(), 1, NULL, out8, traj.data(), &status, &iters, pre);
+      haveRunWarm = rc == MPC_OK; runWarmStatus = status;
+    } else rc = mpc_run_batch_host(handle, 1, 1, npts, pose, ptsx.data(), ptsy.data(), out8, traj.data(), &status, &iters, pre);
     if (rc != MPC_OK) throw std::string("mpc_run_batch_host failed: ") + mpc_last_error();
+    lastIters = iters;
     vehicle = veh;
     int nc = MPC_NCOEF;
     while (nc > 3 && pre[6 + nc - 1] == 0.0) --nc;                      /* the fit's order (the rows are zero padded) */
