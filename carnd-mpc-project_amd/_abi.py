@@ -87,7 +87,8 @@ EXPORTS = ["mpc_params_default", "mpc_params_load_json", "mpc_create", "mpc_set_
            "mpc_run_batch_host", "mpc_last_batch_id", "mpc_tail_poll", "mpc_tail_wait", "mpc_tail_stream_wait", "mpc_tail_flush", "mpc_tail_pending", "mpc_tail_info", "mpc_solve_batch_host_f32", "mpc_inflight_advice", "mpc_take_order_info",
            "mpc_warm_rows", "mpc_warm_opts_default", "mpc_solve_batch_device_warm", "mpc_solve_batch_host_warm",
            "mpc_rollout_batch_device_warm", "mpc_run_batch_device_warm", "mpc_run_batch_host_warm",
-           "mpc_telemetry_batch_device_warm", "mpc_telemetry_batch_host_warm", "mpc_wire_telemetry_batch_host_warm"]
+           "mpc_telemetry_batch_device_warm", "mpc_telemetry_batch_host_warm", "mpc_wire_telemetry_batch_host_warm",
+           "mpc_rollout_batch_device_fused", "mpc_rollout_fused_info"]
 
 _lib = None
 
@@ -165,6 +166,10 @@ def library():
     L.mpc_solve_batch_host_warm.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [DP] * 8 + [C.c_int64, C.POINTER(MpcWarmOpts)] + [DP] * 4
     L.mpc_rollout_batch_device_warm.argtypes = ([C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 5 + [C.POINTER(MpcWarmOpts)] +
                                                 [DP] * 3 + [C.c_void_p])
+    # handle, B, ld, steps, state .. weights, warm_start, opts, hist, status, iters, stream
+    L.mpc_rollout_batch_device_fused.argtypes = ([C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 5 + [C.c_int, C.POINTER(MpcWarmOpts)] +
+                                                 [DP] * 3 + [C.c_void_p])
+    L.mpc_rollout_fused_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     # the run() path: the cold arguments up to ptsy, then warm_in, warm_status, warm_out, ld_warm, opts, then the cold outputs
     WARM = [DP] * 3 + [C.c_int64, C.POINTER(MpcWarmOpts)]
     L.mpc_run_batch_device_warm.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 3 + WARM + [DP] * 5 + [C.c_void_p]

@@ -2673,6 +2673,24 @@ struct WarmColumn {
   }
 };
 
+/* One car of a closed-loop rollout (mpc_rollout_batch_device*, the loop of src/test.cpp:79-111) between two of its solves: what the
+ * next solve starts from, what the call reports per car, and which steps may start warm.  The fused rollout (the ROLL builds of the
+ * lane kernel) and the test-only CPU build tests/rollout_twin go through this and nothing else; mpc_rollout_step_kernel states the
+ * same rule for the stepwise loop, a launch per step. */
+struct RolloutCar {
+  /* the next state: rows 0..5 of solve()'s 9-vector {x1, y1, psi1, v1, cte1, epsi1}, as they were written (out9(q) reads, state(q, v) writes) */
+  template <class Get, class Put> MPC_HD static void next_state(Get out9, Put state) {
+    MPC_UNROLL
+    for (int q = 0; q < 6; q++) state(q, out9(q));
+  }
+  /* the car's status: the first step assigns, later steps keep the larger code */
+  MPC_HD static int32_t fold_status(int step, int32_t so_far, int32_t s) { return step == 0 ? s : (s > so_far ? s : so_far); }
+  /* the car's iterations: summed over its steps */
+  MPC_HD static int32_t sum_iters(int step, int32_t so_far, int32_t it) { return (step == 0 ? 0 : so_far) + it; }
+  /* step `step` (0-based) of a warm rollout starts from the step before if that one succeeded; the first step is always cold */
+  MPC_HD static bool starts_warm(int step, int32_t prev_status) { return step > 0 && prev_status == MPC_STATUS_SUCCESS; }
+};
+
 /* One instance, end to end (used by the test-only host build; the device kernel
  * drives Solver directly so that outputs go straight to their HBM arrays). */
 template <class WS, class R>

@@ -201,6 +201,19 @@ struct MpcPhaseWarm : MpcPhase {
   int32_t psi_box;                /* the run() path: psi of the records is projected into the instance's [yaw_lo, yaw_hi] (mpc::WarmColumn) */
 };
 
+/* What the ROLL builds of mpc_solve_kernel get on top (mpc_rollout_batch_device_fused): a lane keeps the car it has taken for `steps`
+ * solves.  Everything the launch writes AND reads again goes through the pointers below -- the car's state, its status and its
+ * iterations here, its warm column (warm_in == warm_out) in MpcPhaseWarm -- and none of them is const or __restrict__: the lane that
+ * has written a value is the one that reads it back, in program order.  The kernel's own state / out / status / iters arguments are
+ * not dereferenced in these builds.  A type of its own: the other builds' kernel arguments are what they were. */
+struct MpcPhaseRoll : MpcPhaseWarm {
+  int32_t steps;
+  double *hist;                   /* [steps][9][ldo], or the handle's 9 scratch rows with hist_step = 0 */
+  int64_t hist_step;              /* doubles from one step's 9 rows to the next */
+  double *state;                  /* [6][ld]: read at every step, the next state written in place */
+  int32_t *status, *iters;        /* per car: worst status, summed iterations (iters may be nullptr) */
+};
+
 /* The take-order key of every instance of a launch (csrc/mpc_take_key.h) and the bins' lists: one thread per instance, a wave
  * appends its instances to the bins' lists.  No LDS and few registers: its waves fit beside the resident waves of a bulk
  * launch.  cnt[] is zero on entry (it lives in the launch's counter block). */
@@ -272,15 +285,25 @@ template <class RIO, class R> struct OutRef {
 /* RIO: the type of the arrays at the ABI (inputs, outputs); R: the solver's.  They differ only in the fp64 phase of a
  * mixed-precision solve on an MPC_PRECISION_F32 handle (RIO = float, R = double).  RSRC: the reals of the workspace a
  * promote_in phase takes its iterates from. */
-template <bool STAGING, class R, class RIO = R, class RSRC = RIO, bool SOC = false, bool WARM = false>
+/* ROLL (mpc_rollout_batch_device_fused): a lane keeps the car it has taken for T.steps solves.  At the hand-over point a finished
+ * solve of step t goes to row block t of T.hist, its rows 0..5 become the car's state, status and iterations are folded into the
+ * car's (mpc::RolloutCar), and -- WARM -- the final iterate goes to the car's warm column; with steps left the lane then takes the
+ * SAME car again instead of asking the counter: set-up from the state it has just stored and a cold start, or, WARM and the step
+ * succeeded, warm_point() on its own column and begin_warm() -- the code the take runs for a fresh instance.  Step 0 is cold.
+ * Exit: a lane with steps left holds its car as `have` (solving) or `fin` (a finished or rejected step waiting for the hand-over),
+ * so the wave stays; every pass advances a solve (bounded by max_iter and the one restart), a step (a car has T.steps of them)
+ * or consumes the counter.  These builds are launched without lane compaction, cuts and deferred tails (the step index lives in
+ * the lane's registers and does not travel). */
+template <bool STAGING, class R, class RIO = R, class RSRC = RIO, bool SOC = false, bool WARM = false, bool ROLL = false>
 __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
     const MpcParams P, const int64_t B, const int64_t ld, const int64_t ldo, const RIO *__restrict__ state,
     const RIO *__restrict__ coeffs, const RIO *__restrict__ yaw_lo, const RIO *__restrict__ yaw_hi,
     const RIO *__restrict__ weights, RIO *__restrict__ out, RIO *__restrict__ traj,
     int32_t *__restrict__ status, int32_t *__restrict__ iters, R *__restrict__ wsbase,
-    const int64_t tile_reals, const std::conditional_t<WARM, MpcPhaseWarm, MpcPhase> T) {
+    const int64_t tile_reals, const std::conditional_t<ROLL, MpcPhaseRoll, std::conditional_t<WARM, MpcPhaseWarm, MpcPhase>> T) {
   extern __shared__ double smem[];
   static_assert(!WARM || (sizeof(R) == 8 && std::is_same<R, RIO>::value && std::is_same<R, RSRC>::value && !SOC), "warm start: the plain fp64 solve only");
+  static_assert(!ROLL || (sizeof(R) == 8 && std::is_same<R, RIO>::value && std::is_same<R, RSRC>::value && !SOC), "fused rollout: the plain fp64 solve only");
   using WS = std::conditional_t<SOC, mpc::TiledSocWorkspace<STAGING, R>, mpc::TiledWorkspace<STAGING, R>>;
   using SV = mpc::Solver<WS, R, 0, SOC>;
   using FL = mpc::Fields<R>;
@@ -298,8 +321,9 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
   bool queue_full = false;                       /* deferred tails: the batch's queue slot has no room left */
   bool col_busy = false;                         /* this lane's column holds a parked iterate */
   int attempt = 0, it_total = 0, passes = 0, fin_status = 0, waited = 0, cooldown = 0;
+  int step = 0;                                  /* ROLL: solves of car i finished so far */
   const int64_t n_work = T.resume ? (int64_t)*T.n_in : B;
-  (void)col_busy; (void)cooldown;
+  (void)col_busy; (void)cooldown; (void)step;
   for (;;) {
 #if defined(__HIP_DEVICE_COMPILE__)
     /* ---- lane compaction, part 1: is it worth it now?  (see MpcPhase.compact_gap) ---- */
@@ -352,6 +376,35 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
           }
           fin = false;
         }
+        bool again = false, again_warm = false;   /* ROLL: this lane goes on with the next step of its car / and may start it warm */
+        if constexpr (ROLL) {
+          if (fin) {
+            using Car = mpc::RolloutCar;
+            double *o = T.hist + (int64_t)step * T.hist_step + i;
+            const int64_t l = ldo;
+            S.unpack([o, l](int q) { return OutRef<RIO, R>{o + q * l}; }, [](int) { return OutRef<RIO, R>{nullptr}; }, false, (R)yaw_lo[i], (R)yaw_hi[i]);
+            double *sp = T.state + i;
+            const int64_t ls = ld;
+            Car::next_state([o, l](int q) { return o[q * l]; }, [sp, ls](int q, double v) { sp[q * ls] = v; });
+            int32_t worst = 0, sum = 0;
+            if (step > 0) worst = T.status[i];
+            T.status[i] = Car::fold_status(step, worst, fin_status);
+            if (T.iters) {
+              if (step > 0) sum = T.iters[i];
+              T.iters[i] = Car::sum_iters(step, sum, S.iters + it_total);
+            }
+            if constexpr (WARM) {
+              double *wo = T.warm_out + i;
+              const int64_t lw = T.ld_warm;
+              S.warm_store([wo, lw](int k, int f, R v) { wo[(int64_t)(k * MPC_WARM_REC + f) * lw] = v; });
+            }
+            ++step;
+            again = step < T.steps;
+            again_warm = WARM && again && Car::starts_warm(step, fin_status);
+            if (!again) step = 0;                  /* the car is done: the lane is free for whatever the counter still has */
+            fin = false;
+          }
+        }
         if (fin) {
           RIO *o = out + i;
           RIO *t = traj ? traj + i : nullptr;
@@ -371,13 +424,16 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
           fin = false;
         }
         bool exhausted = false;
-        if (!have && more) {
-          const int64_t pos = (int64_t)atomicAdd(T.take, 1);
-          more = pos < n_work;
-          exhausted = !more;
-          if (more) {
-            i = T.resume ? (int64_t)T.in_inst[pos] : pos;
-            if (__builtin_expect(T.ord_list != nullptr, 0)) {      /* (placed out of line: the code around the take stays where it was) */
+        if ((!have && more) || again) {
+          int64_t pos = i;                         /* (ROLL, the same car again: the counter is not asked) */
+          if (!again) {
+            pos = (int64_t)atomicAdd(T.take, 1);
+            more = pos < n_work;
+            exhausted = !more;
+          }
+          if (more || again) {
+            if (!again) i = T.resume ? (int64_t)T.in_inst[pos] : pos;
+            if (__builtin_expect(T.ord_list != nullptr && !again, 0)) {     /* (placed out of line: the code around the take stays where it was) */
               /* the bins laid end to end: which bin holds position pos (the counts are the same for every lane: scalar loads) */
               int64_t off = pos;
               int b = 0;
@@ -391,8 +447,14 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
               if ((uint64_t)i >= (uint64_t)B) i = pos;     /* (cannot happen: the lists hold 0 .. B-1 once each; results never go out of bounds) */
             }
             R st[6], cf[MPC_NCOEF], w[MPC_NW];
+            if constexpr (ROLL) {
+              /* the car's state as it stands: the start state, or the six doubles this lane stored at the step before */
 #pragma unroll
-            for (int q = 0; q < 6; q++) st[q] = (R)state[q * ld + i];
+              for (int q = 0; q < 6; q++) st[q] = (R)T.state[q * ld + i];
+            } else {
+#pragma unroll
+              for (int q = 0; q < 6; q++) st[q] = (R)state[q * ld + i];
+            }
 #pragma unroll
             for (int q = 0; q < MPC_NCOEF; q++) cf[q] = (R)coeffs[q * ld + i];
             if (weights) {
@@ -404,7 +466,8 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
             }
             const bool from_scratch = T.promote_in && T.in_park[pos + 35 * T.ld_park] != 0.0;   /* the fp32 phase gave up on it */
             bool warm = false, warm_cand = false;   /* WARM: this instance has a valid column in warm_in / starts from it */
-            if constexpr (WARM) warm_cand = T.warm_in != nullptr && (T.warm_status == nullptr || T.warm_status[i] == MPC_STATUS_SUCCESS);
+            if constexpr (WARM && ROLL) warm_cand = again_warm;   /* (the column this lane stored when it finished the step before) */
+            else if constexpr (WARM) warm_cand = T.warm_in != nullptr && (T.warm_status == nullptr || T.warm_status[i] == MPC_STATUS_SUCCESS);
             const int s0 = S.setup(st, cf, (R)yaw_lo[i], (R)yaw_hi[i], w, (!T.resume || from_scratch) && !warm_cand);
             if constexpr (WARM) {
               if (warm_cand) {
@@ -1165,6 +1228,7 @@ struct MpcHandle {
    * host entry point's warm_in / warm_out (one block, read and written in place) with the status the warm data came with */
   double *d_warm = nullptr, *d_warm_io = nullptr;
   int32_t *d_warm_st = nullptr;
+  int64_t n_roll_fused = 0, n_roll_stepwise = 0;   /* mpc_rollout_batch_device_fused calls that ran the fused kernel / the stepwise loop (mpc_rollout_fused_info) */
   double *d_tel = nullptr;       /* mpc_telemetry_batch_host: device staging, grown on demand */
   size_t tel_bytes = 0;
   /* last call */
@@ -2392,15 +2456,22 @@ extern "C" int mpc_run_batch_host_warm(MpcHandle *h, int64_t B, int64_t ld, int 
 /* the device a handle lives on (mpc_create's `device`, resolved) */
 extern "C" int mpc_handle_device(const MpcHandle *h) { return h ? h->device : MPC_ERR_INVALID; }
 
+/* what the rollout entry points check before they touch anything (an empty batch may come with NULL arrays) */
+static int rollout_args(const MpcHandle *h, int64_t B, int64_t ld, int steps, const double *state, const double *coeffs, const double *yaw_lo,
+                        const double *yaw_hi, const int32_t *status) {
+  MPC_TRY(check_batch(h, B, ld));
+  if (steps < 1) { g_last_error = "steps < 1"; return MPC_ERR_INVALID; }
+  if (B > 0 && (!state || !coeffs || !yaw_lo || !yaw_hi || !status)) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
+  return MPC_OK;
+}
+
 /* The rollout: `steps` solves, each followed by the step kernel.  W != NULL: every step after the first is warm-started from the step
  * before (the handle keeps the buffer). */
 static int rollout_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs, const double *yaw_lo,
                         const double *yaw_hi, const double *weights, const MpcWarmOpts *W, double *hist, int32_t *status, int32_t *iters,
                         void *stream_) {
-  MPC_TRY(check_batch(h, B, ld));
-  if (steps < 1) { g_last_error = "steps < 1"; return MPC_ERR_INVALID; }
+  MPC_TRY(rollout_args(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, status));
   if (B == 0) { h->last_B = 0; return MPC_OK; }
-  if (!state || !coeffs || !yaw_lo || !yaw_hi || !status) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
   MPC_ON_DEVICE(h);
   if (!hist) MPC_TRY(grow_dev(&h->d_run9, &h->run9_bytes, sizeof(double) * 9 * ld));
   MPC_TRY(ensure_dev(&h->d_rstat, sizeof(int32_t) * h->io_stride));
@@ -2431,6 +2502,65 @@ extern "C" int mpc_rollout_batch_device_warm(MpcHandle *h, int64_t B, int64_t ld
   MpcWarmOpts W;
   MPC_TRY(warm_check(h, opts, &W));
   return rollout_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, &W, hist, status, iters, stream_);
+}
+
+/* The rollout in one launch: the ROLL build of the lane kernel, a lane per car for all `steps` solves (see mpc_solve_kernel).  One
+ * rule decides: fused == stepwise on every handle.  The fused kernel is the single-phase fp64 lane kernel, so it runs where the
+ * stepwise loop would launch exactly that at every step (an fp64 handle, no fp32 start, no SOC, B above the wave limit); everywhere
+ * else -- and for an fp32 handle, which the loop refuses -- the call IS the stepwise loop.  W != NULL: warm (warm_check has passed). */
+static int rollout_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs, const double *yaw_lo,
+                              const double *yaw_hi, const double *weights, const MpcWarmOpts *W, double *hist, int32_t *status,
+                              int32_t *iters, void *stream_) {
+  MPC_TRY(rollout_args(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, status));
+  const bool wave_path = h->wave_max_batch > 0 && B <= h->wave_max_batch;
+  if (B == 0 || h->params.precision != MPC_PRECISION_F64 || h->mixed || h->params.max_soc > 0 || wave_path) {
+    MPC_TRY(rollout_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, W, hist, status, iters, stream_));
+    ++h->n_roll_stepwise;
+    return MPC_OK;
+  }
+  MPC_ON_DEVICE(h);
+  if (!hist) MPC_TRY(grow_dev(&h->d_run9, &h->run9_bytes, sizeof(double) * 9 * ld));
+  if (W) MPC_TRY(ensure_dev(&h->d_warm, sizeof(double) * (size_t)mpc_warm_rows(h->params.N) * (size_t)h->io_stride));
+  double *o9 = hist ? hist : h->d_run9;          /* (no history: every car's 9 rows go to its own column of the scratch rows) */
+  const SolveIO<double> io{B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, o9, nullptr, status, iters ? iters : h->d_iters};
+  std::optional<DeviceGuard> guard;
+  MpcHandle::BatchRec *rec = nullptr;
+  MPC_TRY(solve_begin(h, io, nullptr, guard, &rec));
+  hipStream_t s = (hipStream_t)stream_;
+  const CounterBlocks C = take_counters(h);
+  MPC_HIP_CHECK(hipEventRecord(h->ev0, s));
+  MpcPhase T = phase_defaults(h, B);
+  T.take = C.cb; T.n_out = C.cb + 1; T.zero_next = C.zero_next;
+  T.compact_gap = 0;                             /* (the step index does not travel with a moved instance) */
+  const TailPlace tp;
+  tail_fields(h, tp, T);
+  double *warm = W ? h->d_warm : nullptr;
+  const MpcPhaseRoll R{MpcPhaseWarm{T, warm, nullptr, warm, h->io_stride, W ? *W : MpcWarmOpts{}, 0}, steps, o9, hist ? 9 * ld : 0, state, status, iters};
+  const unsigned grid = (unsigned)((B + kBlock - 1) / kBlock);
+  MPC_TRY(with_bool(h->staging, [&](auto staging) {
+    return with_bool(W != nullptr, [&](auto warm_build) {
+      constexpr bool STAGING = decltype(staging)::value;
+      return launch_kernel(mpc_solve_kernel<STAGING, double, double, double, false, decltype(warm_build)::value, true>, grid,
+                           STAGING ? staging_lds_bytes<double>() : 0, s, h, io, (double *)h->ws, h->ws_stride, R);
+    });
+  }));
+  MPC_TRY(solve_end(h, io, s, rec, tp, false));
+  ++h->n_roll_fused;
+  return record_stats(h, B, status, iters, s);   /* as the stepwise loop: worst status per instance, iterations summed over the steps */
+}
+
+extern "C" int mpc_rollout_batch_device_fused(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
+                                              const double *yaw_lo, const double *yaw_hi, const double *weights, int warm_start,
+                                              const MpcWarmOpts *opts, double *hist, int32_t *status, int32_t *iters, void *stream_) {
+  MpcWarmOpts W;
+  if (warm_start) MPC_TRY(warm_check(h, opts, &W));
+  return rollout_fused_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, warm_start ? &W : nullptr, hist, status, iters, stream_);
+}
+
+extern "C" int mpc_rollout_fused_info(const MpcHandle *h, int64_t *out2) {
+  if (!h || !out2) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
+  out2[0] = h->n_roll_fused; out2[1] = h->n_roll_stepwise;
+  return MPC_OK;
 }
 
 extern "C" int mpc_synchronize(MpcHandle *h) {

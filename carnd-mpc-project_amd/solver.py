@@ -232,11 +232,13 @@ class BatchedMPC:
         return res
 
     def rollout_torch(self, state, coeffs, yaw_lo, yaw_hi, steps, weights=None, want_hist=True, stream=None, warm_start=False,
-                      warm_opts=None):
+                      warm_opts=None, fused=False):
         """Closed loop of src/test.cpp:79-111 for a batch: `steps` cold-started solves, each fed with the previous
         step-1 state.  `state` [6,B] is advanced in place.  Returns hist [steps,9,B], worst status, summed iters.
         ``warm_start``: every step after the first starts from the solution of the step before
-        (mpc_rollout_batch_device_warm; same NLP, fewer iterations)."""
+        (mpc_rollout_batch_device_warm; same NLP, fewer iterations).
+        ``fused``: the same rollout in one launch, every car advancing on its own (mpc_rollout_batch_device_fused; bitwise the
+        same results, rollout_fused_info() tells whether the fused kernel or the stepwise loop ran)."""
         import torch
         B = state.shape[1]
         dev = state.device
@@ -247,6 +249,13 @@ class BatchedMPC:
                "status": torch.empty((B,), dtype=torch.int32, device=dev),
                "iters": torch.empty((B,), dtype=torch.int32, device=dev)}
         s = stream if stream is not None else torch.cuda.current_stream(dev)
+        if fused:
+            check(library().mpc_rollout_batch_device_fused(
+                self._h, B, B, int(steps), state.data_ptr(), coeffs.data_ptr(), yaw_lo.data_ptr(), yaw_hi.data_ptr(),
+                weights.data_ptr() if weights is not None else None, 1 if warm_start else 0,
+                C.byref(warm_opts) if warm_opts is not None else None, res["hist"].data_ptr() if want_hist else None,
+                res["status"].data_ptr(), res["iters"].data_ptr(), C.c_void_p(s.cuda_stream)), "mpc_rollout_batch_device_fused")
+            return res
         if warm_start:
             check(library().mpc_rollout_batch_device_warm(
                 self._h, B, B, int(steps), state.data_ptr(), coeffs.data_ptr(), yaw_lo.data_ptr(), yaw_hi.data_ptr(),
@@ -339,6 +348,11 @@ class BatchedMPC:
         a = (C.c_int64 * 2)()
         check(library().mpc_take_order_info(self._h, a), "mpc_take_order_info")
         return {"launches_in_key_order": int(a[0]), "mode": int(a[1])}
+
+    def rollout_fused_info(self):
+        a = (C.c_int64 * 2)()
+        check(library().mpc_rollout_fused_info(self._h, a), "mpc_rollout_fused_info")
+        return {"fused_launches": int(a[0]), "stepwise_loops": int(a[1])}
 
     def synchronize(self):
         check(library().mpc_synchronize(self._h), "mpc_synchronize")

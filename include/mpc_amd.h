@@ -395,6 +395,18 @@ int mpc_solve_batch_host_warm(MpcHandle *h, int64_t B, int64_t ld, const double 
 int mpc_rollout_batch_device_warm(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
                                   const double *yaw_lo, const double *yaw_hi, const double *weights, const MpcWarmOpts *opts,
                                   double *hist, int32_t *status, int32_t *iters, void *stream);
+/* The rollout of mpc_rollout_batch_device (warm_start = 0) or mpc_rollout_batch_device_warm (warm_start = 1; opts as there,
+ * NULL = defaults) in ONE launch: a lane keeps its car for all `steps` solves and starts the next one as soon as its own is done,
+ * instead of every car waiting at every step for the slowest car of that step.
+ * Arguments, outputs, status / iters conventions and refusals are those of the stepwise entry points;
+ * every array this call writes (state, hist, status, iters) holds BITWISE what the stepwise call writes.
+ * The one launch serves fp64 handles whose solve is a single launch of the lane kernel (no fp32 start, max_soc = 0) for batches
+ * above the wave limit; on every other handle and size the call runs the stepwise loop itself (mpc_rollout_fused_info tells). */
+int mpc_rollout_batch_device_fused(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
+                                   const double *yaw_lo, const double *yaw_hi, const double *weights, int warm_start,
+                                   const MpcWarmOpts *opts, double *hist, int32_t *status, int32_t *iters, void *stream);
+/* out2: calls so far that ran the fused kernel, calls that ran the stepwise loop instead */
+int mpc_rollout_fused_info(const MpcHandle *h, int64_t *out2);
 /* Warm start on the run() path: what a telemetry handler calls once per message (mpc_main.cpp).  Every run() problem starts at
  * (0, 0, 0, v, cte, epsi) in its own vehicle frame, and from one message to the next the solution looks almost the same in that
  * frame, so the previous call's records are taken as they are, unshifted by default -- with one change: the psi box moves with the
