@@ -68,6 +68,10 @@ class MpcBatchStats(C.Structure):
                 ("kernel_ms", C.c_double)]
 
 
+NMODEL = 6       # MPC_NMODEL: rows of a model array, [NMODEL][ld] (the mpc_*_model entry points), in the order of MODEL_ROWS
+MODEL_DT, MODEL_LF, MODEL_MAX_STEERING, MODEL_MAX_ACCELERATION, MODEL_MAX_DECELERATION, MODEL_MAX_SPEED = range(6)
+MODEL_ROWS = ("dt", "Lf", "max_steering", "max_acceleration", "max_deceleration", "max_speed")   # the MpcParams fields, row by row
+
 WARM_REC = 22    # MPC_WARM_REC: reals per stage of a warm buffer (s 6, u 2, lam 6, z_L 4, z_U 4)
 
 
@@ -88,7 +92,8 @@ EXPORTS = ["mpc_params_default", "mpc_params_load_json", "mpc_create", "mpc_set_
            "mpc_warm_rows", "mpc_warm_opts_default", "mpc_solve_batch_device_warm", "mpc_solve_batch_host_warm",
            "mpc_rollout_batch_device_warm", "mpc_run_batch_device_warm", "mpc_run_batch_host_warm",
            "mpc_telemetry_batch_device_warm", "mpc_telemetry_batch_host_warm", "mpc_wire_telemetry_batch_host_warm",
-           "mpc_rollout_batch_device_fused", "mpc_rollout_fused_info"]
+           "mpc_rollout_batch_device_fused", "mpc_rollout_fused_info",
+           "mpc_solve_batch_device_model", "mpc_solve_batch_host_model", "mpc_rollout_batch_device_model"]
 
 _lib = None
 
@@ -170,6 +175,10 @@ def library():
     L.mpc_rollout_batch_device_fused.argtypes = ([C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 5 + [C.c_int, C.POINTER(MpcWarmOpts)] +
                                                  [DP] * 3 + [C.c_void_p])
     L.mpc_rollout_fused_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    # the entry points without _model, with `model` behind `weights`
+    L.mpc_solve_batch_device_model.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [DP] * 10 + [C.c_void_p]
+    L.mpc_solve_batch_host_model.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [DP] * 10
+    L.mpc_rollout_batch_device_model.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 9 + [C.c_void_p]
     # the run() path: the cold arguments up to ptsy, then warm_in, warm_status, warm_out, ld_warm, opts, then the cold outputs
     WARM = [DP] * 3 + [C.c_int64, C.POINTER(MpcWarmOpts)]
     L.mpc_run_batch_device_warm.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 3 + WARM + [DP] * 5 + [C.c_void_p]

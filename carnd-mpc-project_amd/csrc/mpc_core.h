@@ -658,6 +658,31 @@ MPC_HD double speed_target(const MpcParams &P, double angle, double maxv) {
   return fmin(P.steer_speeds[last], maxv);
 }
 
+/* The six values of the vehicle model that an instance may bring along (rows of model [MPC_NMODEL][ld], include/mpc_amd.h): the
+ * time step, the wheelbase and the four limits, in the units of the MpcParams fields of the same names.  Solver::setup() and
+ * Solver::unpack() are the only places of the solve that read them, and they read them as fields of these names: of the handle's
+ * MpcParams itself (the existing signatures -- each field read where it is used, as before there was a choice, so the kernels
+ * without per-instance values are instruction for instruction what they were) or of this struct, filled from the instance's column
+ * (ModelVals::column, setup_model() / unpack_model()). */
+struct ModelVals {
+  double dt, Lf, max_steering, max_acceleration, max_deceleration, max_speed;
+  MPC_HD static ModelVals of(const MpcParams &P) { return ModelVals{P.dt, P.Lf, P.max_steering, P.max_acceleration, P.max_deceleration, P.max_speed}; }
+  /* Column `get(row)` of a model array.  A usable column holds six finite values with dt > 0, Lf > 0, max_speed > 0 and
+   * max_steering > 0 -- what mpc_create asks of the same MpcParams fields -- and max_acceleration > 0 > max_deceleration: the start
+   * point a = 0 of every solve lies strictly inside the acceleration box (mpc_create does not look at these two; a handle's
+   * parameters come from a config file, a column from arithmetic on arrays).  Anything else: `ok` is false and the values are the
+   * handle's, so that the start point such an instance is reported with (MPC_STATUS_INFEASIBLE) holds no not-a-number. */
+  template <class Get> MPC_HD static ModelVals column(const MpcParams &P, Get get, bool &ok) {
+    const ModelVals m{get(MPC_MODEL_DT), get(MPC_MODEL_LF), get(MPC_MODEL_MAX_STEERING), get(MPC_MODEL_MAX_ACCELERATION),
+                      get(MPC_MODEL_MAX_DECELERATION), get(MPC_MODEL_MAX_SPEED)};
+    /* (comparisons that a not-a-number fails) */
+    ok = m.dt > 0.0 && m.dt < HUGE_VAL && m.Lf > 0.0 && m.Lf < HUGE_VAL && m.max_steering > 0.0 && m.max_steering < HUGE_VAL &&
+         m.max_acceleration > 0.0 && m.max_acceleration < HUGE_VAL && m.max_deceleration < 0.0 && m.max_deceleration > -HUGE_VAL &&
+         m.max_speed > 0.0 && m.max_speed < HUGE_VAL;
+    return ok ? m : of(P);
+  }
+};
+
 /* what a trial-point evaluation returns */
 template <class R>
 struct Eval {
@@ -2110,20 +2135,33 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
   /* ------------------------------------------------------------------ */
   MPC_HD int setup(const R *state6, const R *coef5, R yaw_lo, R yaw_hi, const R *w12,
                    bool write_start = true) {
+    return setup_vals(P, state6, coef5, yaw_lo, yaw_hi, w12, write_start);
+  }
+  /* The same for an instance that brings its own model values: `model(row)` reads its column of model [MPC_NMODEL][ld].  A column
+   * that ModelVals::column refuses ends as MPC_STATUS_INFEASIBLE with the start point of the handle's own values. */
+  template <class Get>
+  MPC_HD int setup_model(Get model, const R *state6, const R *coef5, R yaw_lo, R yaw_hi, const R *w12, bool write_start = true) {
+    bool ok;
+    const ModelVals m = ModelVals::column(P, model, ok);
+    const int s = setup_vals(m, state6, coef5, yaw_lo, yaw_hi, w12, write_start);
+    return ok ? s : MPC_STATUS_INFEASIBLE;
+  }
+  template <class MV>
+  MPC_HD int setup_vals(const MV &m, const R *state6, const R *coef5, R yaw_lo, R yaw_hi, const R *w12, bool write_start) {
     MPC_UNROLL
     for (int i = 0; i < 6; i++) st[i] = state6[i];
     MPC_UNROLL
     for (int i = 0; i < MPC_NCOEF; i++) coef[i] = coef5[i];
-    M = P.N - 1; dt = (R)P.dt; iLf = (R)(1.0 / P.Lf); dtLf = (R)(P.dt / P.Lf);
+    M = P.N - 1; dt = (R)m.dt; iLf = (R)(1.0 / m.Lf); dtLf = (R)(m.dt / m.Lf);
     /* IPOPT's bound_relax_factor (default 1e-8, untouched by MPC.cpp:160-179): every finite variable bound is moved
      * outwards by factor * max(1, |bound|) before the solve; the start point is pushed inside the RELAXED bounds and
      * the returned point is projected back into the caller's (unpack).  This is what makes a solve that starts ON a
      * bound well posed: the psi_0 of a closed loop whose heading has reached yawHigh (test.cpp:79-111). */
     const double rf = P.bound_relax_factor;
     yl = (R)((double)yaw_lo - rf * fmax(1.0, fabs((double)yaw_lo))); yu = (R)((double)yaw_hi + rf * fmax(1.0, fabs((double)yaw_hi)));
-    vu = (R)(P.max_speed + rf * fmax(1.0, P.max_speed)); vl = -vu;
-    du = (R)(P.max_steering + rf * fmax(1.0, P.max_steering)); dl = -du;
-    al = (R)(P.max_deceleration - rf * fmax(1.0, fabs(P.max_deceleration))); au = (R)(P.max_acceleration + rf * fmax(1.0, fabs(P.max_acceleration)));
+    vu = (R)(m.max_speed + rf * fmax(1.0, m.max_speed)); vl = -vu;
+    du = (R)(m.max_steering + rf * fmax(1.0, m.max_steering)); dl = -du;
+    al = (R)(m.max_deceleration - rf * fmax(1.0, fabs(m.max_deceleration))); au = (R)(m.max_acceleration + rf * fmax(1.0, fabs(m.max_acceleration)));
     fth0 = fth1 = fth2 = fth3 = fph0 = fph1 = fph2 = fph3 = R(0.0);
     lsm = false; cur = 0; iters = 0; n_reg = 0; nf = 0; E.f = R(0.0);
     /* fp32: its own tolerance; the outputs cannot stop moving below the noise of an fp32 step */
@@ -2138,14 +2176,14 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
     wc = (0.0 < P.cte_panic) ? w12[0] : w12[11];
     we = (0.0 > P.epsi_panic) ? w12[10] : w12[1];
     wv = w12[2]; wd = w12[3]; wdd = w12[4];
-    vref = (R)speed_target(P, 0.0, P.max_speed);
+    vref = (R)speed_target(P, 0.0, m.max_speed);
     /* i = 0 terms: constants of the objective (their variables are fixed), MPC.cpp:71-92 */
 #if !MPC_S0_VARIABLE
     R wc0, we0, vref0;
 #endif
     wc0 = ((double)mpc_abs(st[4]) < P.cte_panic) ? w12[0] : w12[11];
     we0 = ((double)mpc_abs(st[5]) > P.epsi_panic) ? w12[10] : w12[1];
-    vref0 = (R)speed_target(P, (double)st[2], P.max_speed);
+    vref0 = (R)speed_target(P, (double)st[2], m.max_speed);
 #if MPC_S0_VARIABLE
     wneg0 = (st[3] < R(0.0)) ? w12[9] : R(0.0);
     s0_rows = P.initial_state_rows != 0;
@@ -2620,6 +2658,17 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
    * honor_original_bounds (IPOPT 3.12 default "yes") the returned point is projected into the bounds the user gave */
   template <class OutF, class TrajF>
   MPC_HD void unpack(OutF out, TrajF traj, bool want_traj, R yaw_lo, R yaw_hi) const {
+    unpack_vals(P, out, traj, want_traj, yaw_lo, yaw_hi);
+  }
+  /* The same for an instance with its own model values: its unrelaxed limits are read from its column again here, at the hand-over
+   * point, instead of being carried through the iteration (a refused column: the handle's, as in setup_model) */
+  template <class Get, class OutF, class TrajF>
+  MPC_HD void unpack_model(Get model, OutF out, TrajF traj, bool want_traj, R yaw_lo, R yaw_hi) const {
+    bool ok;
+    unpack_vals(ModelVals::column(P, model, ok), out, traj, want_traj, yaw_lo, yaw_hi);
+  }
+  template <class MV, class OutF, class TrajF>
+  MPC_HD void unpack_vals(const MV &m, OutF out, TrajF traj, bool want_traj, R yaw_lo, R yaw_hi) const {
     const int I = it(cur);
     MPC_UNROLL
     for (int i = 0; i < 6; i++) out(i) = ws.it(0, I, F_S + i);
@@ -2629,9 +2678,9 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
       const R psi1 = ws.it(0, I, F_S + 2), v1 = ws.it(0, I, F_S + 3), d0 = ws.it(0, I, F_U + 0), a0 = ws.it(0, I, F_U + 1);
       /* written so that a NaN passes through unchanged */
       out(2) = psi1 < yaw_lo ? yaw_lo : (psi1 > yaw_hi ? yaw_hi : psi1);
-      out(3) = v1 < (R)-P.max_speed ? (R)-P.max_speed : (v1 > (R)P.max_speed ? (R)P.max_speed : v1);
-      out(6) = d0 < (R)-P.max_steering ? (R)-P.max_steering : (d0 > (R)P.max_steering ? (R)P.max_steering : d0);
-      out(7) = a0 < (R)P.max_deceleration ? (R)P.max_deceleration : (a0 > (R)P.max_acceleration ? (R)P.max_acceleration : a0);
+      out(3) = v1 < (R)-m.max_speed ? (R)-m.max_speed : (v1 > (R)m.max_speed ? (R)m.max_speed : v1);
+      out(6) = d0 < (R)-m.max_steering ? (R)-m.max_steering : (d0 > (R)m.max_steering ? (R)m.max_steering : d0);
+      out(7) = a0 < (R)m.max_deceleration ? (R)m.max_deceleration : (a0 > (R)m.max_acceleration ? (R)m.max_acceleration : a0);
     }
     out(8) = E.f + cost0;
     if (want_traj) {

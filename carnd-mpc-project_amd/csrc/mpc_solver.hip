@@ -201,6 +201,15 @@ struct MpcPhaseWarm : MpcPhase {
   int32_t psi_box;                /* the run() path: psi of the records is projected into the instance's [yaw_lo, yaw_hi] (mpc::WarmColumn) */
 };
 
+/* What the MODEL builds of mpc_solve_kernel get on top (the mpc_*_model entry points): the model values of every instance,
+ * [MPC_NMODEL][ld] doubles addressed by INSTANCE like the inputs -- a lane reads its instance's six values wherever it runs set-up
+ * for it (the take, an instance that lane compaction has moved) and when it writes the instance out, so the column follows the
+ * instance from lane to lane.  These builds are launched as one single phase without cuts and deferred tails (a parked or deferred
+ * instance would have to carry its column along).  A type of its own: the other builds' kernel arguments are what they were. */
+struct MpcPhaseModel : MpcPhase {
+  const double *model;
+};
+
 /* What the ROLL builds of mpc_solve_kernel get on top (mpc_rollout_batch_device_fused): a lane keeps the car it has taken for `steps`
  * solves.  Everything the launch writes AND reads again goes through the pointers below -- the car's state, its status and its
  * iterations here, its warm column (warm_in == warm_out) in MpcPhaseWarm -- and none of them is const or __restrict__: the lane that
@@ -294,16 +303,20 @@ template <class RIO, class R> struct OutRef {
  * so the wave stays; every pass advances a solve (bounded by max_iter and the one restart), a step (a car has T.steps of them)
  * or consumes the counter.  These builds are launched without lane compaction, cuts and deferred tails (the step index lives in
  * the lane's registers and does not travel). */
-template <bool STAGING, class R, class RIO = R, class RSRC = RIO, bool SOC = false, bool WARM = false, bool ROLL = false>
+/* MODEL (the mpc_*_model entry points): every set-up and the hand-over read dt, Lf and the four limits from the instance's column of
+ * T.model instead of P (Solver::setup_model / unpack_model), by instance index and outside the sweeps; nothing else differs. */
+template <bool STAGING, class R, class RIO = R, class RSRC = RIO, bool SOC = false, bool WARM = false, bool ROLL = false, bool MODEL = false>
 __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
     const MpcParams P, const int64_t B, const int64_t ld, const int64_t ldo, const RIO *__restrict__ state,
     const RIO *__restrict__ coeffs, const RIO *__restrict__ yaw_lo, const RIO *__restrict__ yaw_hi,
     const RIO *__restrict__ weights, RIO *__restrict__ out, RIO *__restrict__ traj,
     int32_t *__restrict__ status, int32_t *__restrict__ iters, R *__restrict__ wsbase,
-    const int64_t tile_reals, const std::conditional_t<ROLL, MpcPhaseRoll, std::conditional_t<WARM, MpcPhaseWarm, MpcPhase>> T) {
+    const int64_t tile_reals,
+    const std::conditional_t<ROLL, MpcPhaseRoll, std::conditional_t<WARM, MpcPhaseWarm, std::conditional_t<MODEL, MpcPhaseModel, MpcPhase>>> T) {
   extern __shared__ double smem[];
   static_assert(!WARM || (sizeof(R) == 8 && std::is_same<R, RIO>::value && std::is_same<R, RSRC>::value && !SOC), "warm start: the plain fp64 solve only");
   static_assert(!ROLL || (sizeof(R) == 8 && std::is_same<R, RIO>::value && std::is_same<R, RSRC>::value && !SOC), "fused rollout: the plain fp64 solve only");
+  static_assert(!MODEL || (sizeof(R) == 8 && std::is_same<R, RIO>::value && std::is_same<R, RSRC>::value && !WARM && !ROLL), "per-instance model values: the cold fp64 solve only");
   using WS = std::conditional_t<SOC, mpc::TiledSocWorkspace<STAGING, R>, mpc::TiledWorkspace<STAGING, R>>;
   using SV = mpc::Solver<WS, R, 0, SOC>;
   using FL = mpc::Fields<R>;
@@ -409,8 +422,15 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
           RIO *o = out + i;
           RIO *t = traj ? traj + i : nullptr;
           const int64_t l = ldo;
-          S.unpack([o, l](int q) { return OutRef<RIO, R>{o + q * l}; }, [t, l](int q) { return OutRef<RIO, R>{t + q * l}; }, traj != nullptr,
-                   (R)yaw_lo[i], (R)yaw_hi[i]);
+          if constexpr (MODEL) {
+            const double *mc = T.model + i;
+            const int64_t lm = ld;
+            S.unpack_model([mc, lm](int q) { return mc[q * lm]; }, [o, l](int q) { return OutRef<RIO, R>{o + q * l}; },
+                           [t, l](int q) { return OutRef<RIO, R>{t + q * l}; }, traj != nullptr, (R)yaw_lo[i], (R)yaw_hi[i]);
+          } else {
+            S.unpack([o, l](int q) { return OutRef<RIO, R>{o + q * l}; }, [t, l](int q) { return OutRef<RIO, R>{t + q * l}; }, traj != nullptr,
+                     (R)yaw_lo[i], (R)yaw_hi[i]);
+          }
           if constexpr (WARM) {
             /* the final iterate, whatever the status (the caller's next solve looks at the status) */
             if (T.warm_out) {
@@ -468,7 +488,12 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
             bool warm = false, warm_cand = false;   /* WARM: this instance has a valid column in warm_in / starts from it */
             if constexpr (WARM && ROLL) warm_cand = again_warm;   /* (the column this lane stored when it finished the step before) */
             else if constexpr (WARM) warm_cand = T.warm_in != nullptr && (T.warm_status == nullptr || T.warm_status[i] == MPC_STATUS_SUCCESS);
-            const int s0 = S.setup(st, cf, (R)yaw_lo[i], (R)yaw_hi[i], w, (!T.resume || from_scratch) && !warm_cand);
+            int s0;
+            if constexpr (MODEL) {
+              const double *mc = T.model + i;
+              const int64_t lm = ld;
+              s0 = S.setup_model([mc, lm](int q) { return mc[q * lm]; }, st, cf, (R)yaw_lo[i], (R)yaw_hi[i], w, (!T.resume || from_scratch) && !warm_cand);
+            } else s0 = S.setup(st, cf, (R)yaw_lo[i], (R)yaw_hi[i], w, (!T.resume || from_scratch) && !warm_cand);
             if constexpr (WARM) {
               if (warm_cand) {
                 if (s0 == MPC_STATUS_SUCCESS) {
@@ -591,7 +616,11 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
 #pragma unroll
             for (int q = 0; q < MPC_NW; q++) w[q] = (R)P.weights[q];
           }
-          (void)S.setup(st, cf, (R)yaw_lo[i], (R)yaw_hi[i], w, false);
+          if constexpr (MODEL) {      /* the instance has changed lanes: its column comes with it */
+            const double *mc = T.model + i;
+            const int64_t lm = ld;
+            (void)S.setup_model([mc, lm](int q) { return mc[q * lm]; }, st, cf, (R)yaw_lo[i], (R)yaw_hi[i], w, false);
+          } else (void)S.setup(st, cf, (R)yaw_lo[i], (R)yaw_hi[i], w, false);
           S.unpark([mb, src](int q) -> R { return mb[q * 64 + src]; }, attempt, it_total);
           const int I = S.cur ? FL::IT1 : FL::IT0;
           WS wsrc = ws;
@@ -1227,6 +1256,7 @@ struct MpcHandle {
   /* warm start (allocated on first use): the rollout's warm buffer, [mpc_warm_rows(N)][io_stride] doubles, and the device side of the
    * host entry point's warm_in / warm_out (one block, read and written in place) with the status the warm data came with */
   double *d_warm = nullptr, *d_warm_io = nullptr;
+  double *d_model = nullptr;      /* the device side of mpc_solve_batch_host_model's model array (allocated on first use) */
   int32_t *d_warm_st = nullptr;
   int64_t n_roll_fused = 0, n_roll_stepwise = 0;   /* mpc_rollout_batch_device_fused calls that ran the fused kernel / the stepwise loop (mpc_rollout_fused_info) */
   double *d_tel = nullptr;       /* mpc_telemetry_batch_host: device staging, grown on demand */
@@ -1440,6 +1470,7 @@ extern "C" void mpc_destroy(MpcHandle *h) {
   if (h->d_piter) (void)hipFree(h->d_piter);
   if (h->d_tel) (void)hipFree(h->d_tel);
   if (h->d_warm) (void)hipFree(h->d_warm);
+  if (h->d_model) (void)hipFree(h->d_model);
   if (h->d_warm_io) (void)hipFree(h->d_warm_io);
   if (h->d_warm_st) (void)hipFree(h->d_warm_st);
   if (h->tail_ready) (void)tail_drain(h);         /* stragglers still queued are finished: their batches' arrays may be read afterwards */
@@ -1894,6 +1925,7 @@ struct SolveIO {
   const R *state, *coeffs, *yaw_lo, *yaw_hi, *weights;
   R *out, *traj;
   int32_t *status, *iters;
+  const double *model = nullptr;   /* a model call (the mpc_*_model entry points, fp64 handles): [MPC_NMODEL][ld], see MpcPhaseModel */
 };
 /* ... and what a warm call brings on top: the warm buffers (see MpcPhaseWarm) and the options in effect (warm_check) */
 struct WarmIO {
@@ -1975,7 +2007,7 @@ static int launch_wave(MpcHandle *h, const SolveIO<R> &io, hipStream_t s, bool s
 }
 
 /* The lane kernel (an instance per lane; `ws`: the workspace of the phase).  single: the build that MPC_STAGING, max_soc on an fp64
- * handle and a warm call select.  The two phases of a mixed-precision solve are builds of their own: the fp32 solver, and the fp64
+ * handle, a warm call and a model call (io.model; with or without SOC) select.  The two phases of a mixed-precision solve are builds of their own: the fp32 solver, and the fp64
  * solver that takes its iterates from fp32 records -- whatever RIO, the type at the ABI, is. */
 enum class LaneBuild { single, mixed_f32, mixed_f64 };
 template <class RIO>
@@ -1983,22 +2015,24 @@ static int launch_lanes(MpcHandle *h, LaneBuild build, const SolveIO<RIO> &io, h
                         const WarmIO *warm = nullptr) {
   const unsigned grid = (unsigned)((io.B + kBlock - 1) / kBlock);
   /* (r, rsrc: values of the solver's reals and of the reals its resumed iterates come in) */
-  auto go = [&](auto staging, auto r, auto rsrc, auto soc_build, auto warm_build, int64_t tile_reals, const auto &phase) {
+  auto go = [&](auto staging, auto r, auto rsrc, auto soc_build, auto warm_build, int64_t tile_reals, const auto &phase, auto model_build) {
     using R = decltype(r);
     constexpr bool STAGING = decltype(staging)::value;
-    return launch_kernel(mpc_solve_kernel<STAGING, R, RIO, decltype(rsrc), decltype(soc_build)::value, decltype(warm_build)::value>, grid,
-                         STAGING ? staging_lds_bytes<R>() : 0, s, h, io, (R *)ws, tile_reals, phase);
+    return launch_kernel(mpc_solve_kernel<STAGING, R, RIO, decltype(rsrc), decltype(soc_build)::value, decltype(warm_build)::value, false,
+                                          decltype(model_build)::value>,
+                         grid, STAGING ? staging_lds_bytes<R>() : 0, s, h, io, (R *)ws, tile_reals, phase);
   };
   constexpr std::true_type yes{};
   constexpr std::false_type no{};
-  if (build == LaneBuild::mixed_f32) return go(yes, float{}, RIO{}, no, no, h->ws_stride_f32, T);
-  if (build == LaneBuild::mixed_f64) return with_bool(soc, [&](auto soc_build) { return go(yes, double{}, float{}, soc_build, no, h->ws_stride_f64, T); });
+  if (build == LaneBuild::mixed_f32) return go(yes, float{}, RIO{}, no, no, h->ws_stride_f32, T, no);
+  if (build == LaneBuild::mixed_f64) return with_bool(soc, [&](auto soc_build) { return go(yes, double{}, float{}, soc_build, no, h->ws_stride_f64, T, no); });
   return with_bool(h->staging, [&](auto staging) {
     if constexpr (sizeof(RIO) == 8) {
-      if (warm) return go(staging, RIO{}, RIO{}, no, yes, h->ws_stride, MpcPhaseWarm{T, warm->warm_in, warm->warm_status, warm->warm_out, warm->ld_warm, warm->opts, warm->psi_box ? 1 : 0});
-      if (soc) return go(staging, RIO{}, RIO{}, yes, no, h->ws_stride, T);
+      if (io.model) return with_bool(soc, [&](auto soc_build) { return go(staging, RIO{}, RIO{}, soc_build, no, h->ws_stride, MpcPhaseModel{T, io.model}, yes); });
+      if (warm) return go(staging, RIO{}, RIO{}, no, yes, h->ws_stride, MpcPhaseWarm{T, warm->warm_in, warm->warm_status, warm->warm_out, warm->ld_warm, warm->opts, warm->psi_box ? 1 : 0}, no);
+      if (soc) return go(staging, RIO{}, RIO{}, yes, no, h->ws_stride, T, no);
     }
-    return go(staging, RIO{}, RIO{}, no, no, h->ws_stride, T);
+    return go(staging, RIO{}, RIO{}, no, no, h->ws_stride, T, no);
   });
 }
 
@@ -2127,7 +2161,10 @@ static int solve_end(MpcHandle *h, const SolveIO<R> &io, hipStream_t s, MpcHandl
 
 /* The launch, for every entry point.  with_stats: mpc_get_stats may ask about this call.  may_defer: the caller can wait for the
  * batch's stragglers (mpc_tail_wait).  may_order: the take order may be applied.  warm: a warm call (warm_check has passed: an
- * fp64 handle, not mixed, no SOC) -- a single phase of the WARM build, or the warm wave kernel; it never defers, cuts or orders. */
+ * fp64 handle, not mixed, no SOC) -- a single phase of the WARM build, or the warm wave kernel; it never defers, cuts or orders.
+ * call.model: a model call (model_check has passed: an fp64 handle) -- ONE launch of the MODEL build of the single-phase fp64 lane
+ * kernel on h->ws at every B, also on a handle whose ordinary solve starts in fp32 (on an fp64 handle h->ws has the fp64 layout):
+ * no wave path, no mixed-precision launch, and it never defers, cuts or orders either. */
 template <class R>
 static int launch_solve(MpcHandle *h, const SolveIO<R> &call, void *stream_, bool with_stats = true, bool may_defer = false,
                         bool may_order = false, const WarmIO *warm = nullptr) {
@@ -2139,22 +2176,23 @@ static int launch_solve(MpcHandle *h, const SolveIO<R> &call, void *stream_, boo
   if (!io.iters) io.iters = h->d_iters;
   const int64_t B = io.B;
   hipStream_t s = (hipStream_t)stream_;   /* NULL = HIP's default (null) stream, exactly as passed */
-  if (warm) may_defer = may_order = false;
+  const bool model = io.model != nullptr;
+  if (warm || model) may_defer = may_order = false;
   /* MpcParams.max_soc > 0 on an fp64 handle: the SOC builds of the kernels (the mixed-precision launch decides for its fp64 phase
    * itself) */
   const bool soc = sizeof(R) == 8 && h->params.max_soc > 0;
-  const bool wave_path = h->wave_max_batch > 0 && B <= h->wave_max_batch;      /* (comes first: set_wave_limit decides which handles have it) */
+  const bool wave_path = !model && h->wave_max_batch > 0 && B <= h->wave_max_batch;      /* (comes first: set_wave_limit decides which handles have it) */
   TailPlace tp;
   tp.defer = may_defer && h->params.tail_cut != 0 && B >= kTailMinBatch && !wave_path;
   if (tp.defer) MPC_TRY(tail_claim(h, s, tp));
   if (wave_path) {
     MPC_HIP_CHECK(hipEventRecord(h->ev0, s));
     MPC_TRY(launch_wave(h, io, s, soc, warm));
-  } else if (h->mixed) {
+  } else if (h->mixed && !model) {
     MPC_TRY(launch_mixed(h, io, s, tp));
   } else {
     const int64_t S = h->io_stride;
-    const int n_cuts = (!warm && !tp.defer && B >= kPassCutMinBatch) ? h->n_cuts : 0;
+    const int n_cuts = (!warm && !model && !tp.defer && B >= kPassCutMinBatch) ? h->n_cuts : 0;
     if (n_cuts > 0) {
       MPC_TRY(ensure_dev(&h->ws2, (size_t)h->ws_stride * (size_t)(S / 64) * sizeof(R)));
       MPC_TRY(ensure_dev(&h->d_park, sizeof(double) * 2 * kParkRows * S));
@@ -2207,6 +2245,24 @@ extern "C" int mpc_solve_batch_device(MpcHandle *h, int64_t B, int64_t ld, const
                                       const double *weights, double *out, double *traj, int32_t *status,
                                       int32_t *iters, void *stream_) {
   return launch_solve<double>(h, {B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters}, stream_, true, true, true);
+}
+
+/* ---- per-instance model values -------------------------------------------------------------------------------------------- */
+/* what every model entry point checks before it touches anything (model != NULL) */
+static int model_check(const MpcHandle *h) {
+  if (!h) { g_last_error = "NULL handle"; return MPC_ERR_INVALID; }
+  if (h->params.precision != MPC_PRECISION_F64) { g_last_error = "per-instance model values: fp64 handles only (this one was created with MPC_PRECISION_F32)"; return MPC_ERR_INVALID; }
+  return MPC_OK;
+}
+
+extern "C" int mpc_solve_batch_device_model(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
+                                            const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
+                                            double *out, double *traj, int32_t *status, int32_t *iters, void *stream_) {
+  if (!model) return mpc_solve_batch_device(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters, stream_);
+  MPC_TRY(model_check(h));
+  SolveIO<double> io{B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters};
+  io.model = model;
+  return launch_solve<double>(h, io, stream_, true, false, false);
 }
 
 /* ---- warm start ---------------------------------------------------------------------------------------------------------- */
@@ -2466,10 +2522,10 @@ static int rollout_args(const MpcHandle *h, int64_t B, int64_t ld, int steps, co
 }
 
 /* The rollout: `steps` solves, each followed by the step kernel.  W != NULL: every step after the first is warm-started from the step
- * before (the handle keeps the buffer). */
+ * before (the handle keeps the buffer).  model != NULL (cold only): mpc_rollout_batch_device_model. */
 static int rollout_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs, const double *yaw_lo,
                         const double *yaw_hi, const double *weights, const MpcWarmOpts *W, double *hist, int32_t *status, int32_t *iters,
-                        void *stream_) {
+                        void *stream_, const double *model = nullptr) {
   MPC_TRY(rollout_args(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, status));
   if (B == 0) { h->last_B = 0; return MPC_OK; }
   MPC_ON_DEVICE(h);
@@ -2482,8 +2538,9 @@ static int rollout_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *
     double *o9 = hist ? hist + (int64_t)t * 9 * ld : h->d_run9;
     /* (warm, in place: a lane reads its car's column and its previous status (d_rstat) before it writes either) */
     const WarmIO warm{t == 0 ? nullptr : h->d_warm, h->d_rstat, h->d_warm, h->io_stride, W ? *W : MpcWarmOpts{}};
-    MPC_TRY(launch_solve<double>(h, {B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, o9, nullptr, h->d_rstat, h->d_iters}, stream_, false, false, false,
-                                 W ? &warm : nullptr));
+    SolveIO<double> io{B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, o9, nullptr, h->d_rstat, h->d_iters};
+    io.model = model;            /* (a model rollout: the cars' columns go to every step) */
+    MPC_TRY(launch_solve<double>(h, io, stream_, false, false, false, W ? &warm : nullptr));
     hipLaunchKernelGGL(mpc_rollout_step_kernel, dim3(grid), dim3(256), 0, s, B, ld, t == 0, o9, state, h->d_rstat, h->d_iters, status, iters);
     MPC_HIP_CHECK(hipGetLastError());
   }
@@ -2494,6 +2551,14 @@ extern "C" int mpc_rollout_batch_device(MpcHandle *h, int64_t B, int64_t ld, int
                                         const double *yaw_lo, const double *yaw_hi, const double *weights, double *hist,
                                         int32_t *status, int32_t *iters, void *stream_) {
   return rollout_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, nullptr, hist, status, iters, stream_);
+}
+
+extern "C" int mpc_rollout_batch_device_model(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
+                                              const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
+                                              double *hist, int32_t *status, int32_t *iters, void *stream_) {
+  if (!model) return mpc_rollout_batch_device(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, hist, status, iters, stream_);
+  MPC_TRY(model_check(h));
+  return rollout_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, nullptr, hist, status, iters, stream_, model);
 }
 
 extern "C" int mpc_rollout_batch_device_warm(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
@@ -2586,10 +2651,12 @@ static void for_rows(int n_rows, size_t row_bytes, Fn fn) {
 }
 
 /* host pointers: one copy in, the launch(es), one copy out, on the handle's own stream; R = the handle's precision */
-/* (warm: the host arrays of mpc_solve_batch_host_warm and the options in effect; fp64 handles only) */
+/* (warm: the host arrays of mpc_solve_batch_host_warm and the options in effect; model: the host array of mpc_solve_batch_host_model,
+ * which goes through a device block of its own, rows packed like the inputs; both fp64 handles only) */
 template <class R>
 static int solve_host(MpcHandle *h, int64_t B, int64_t ld, const R *state, const R *coeffs, const R *yaw_lo, const R *yaw_hi,
-                      const R *weights, R *out, R *traj, int32_t *status, int32_t *iters, const WarmIO *warm = nullptr) {
+                      const R *weights, R *out, R *traj, int32_t *status, int32_t *iters, const WarmIO *warm = nullptr,
+                      const double *model = nullptr) {
   if (!h) { g_last_error = "NULL handle"; return MPC_ERR_INVALID; }
   if ((h->params.precision == MPC_PRECISION_F32) != (sizeof(R) == 4)) {
     g_last_error = "this handle was created with the other precision (mpc_solve_batch_host for fp64 handles, mpc_solve_batch_host_f32 for MPC_PRECISION_F32)";
@@ -2623,8 +2690,13 @@ static int solve_host(MpcHandle *h, int64_t B, int64_t ld, const R *state, const
   /* the warm buffer goes through a device block of its own, rows of the handle's stride, read and written in place */
   WarmIO dw{nullptr, nullptr, nullptr, S, {}};
   if (warm) MPC_TRY(warm_host_in(h, B, *warm, s, &dw));
-  MPC_TRY(launch_solve<R>(h, {B, L, L, di, di + 6 * L, di + 11 * L, di + 12 * L, weights ? di + 13 * L : nullptr, d_o, traj ? d_t : nullptr, d_st, d_it},
-                          (void *)s, true, false, true, warm ? &dw : nullptr));
+  SolveIO<R> io{B, L, L, di, di + 6 * L, di + 11 * L, di + 12 * L, weights ? di + 13 * L : nullptr, d_o, traj ? d_t : nullptr, d_st, d_it};
+  if (model) {
+    MPC_TRY(ensure_dev(&h->d_model, sizeof(double) * MPC_NMODEL * (size_t)S));
+    MPC_HIP_CHECK(hipMemcpy2DAsync(h->d_model, sizeof(double) * L, model, sizeof(double) * ld, sizeof(double) * B, MPC_NMODEL, hipMemcpyHostToDevice, s));
+    io.model = h->d_model;
+  }
+  MPC_TRY(launch_solve<R>(h, io, (void *)s, true, false, true, warm ? &dw : nullptr));
   if (warm) MPC_TRY(warm_host_out(h, B, *warm, s));
   MPC_HIP_CHECK(hipMemcpyAsync(ho, d_o, sizeof(R) * out_rows * L, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipStreamSynchronize(s));
@@ -2643,6 +2715,14 @@ extern "C" int mpc_solve_batch_host(MpcHandle *h, int64_t B, int64_t ld, const d
                                     const double *weights, double *out, double *traj, int32_t *status,
                                     int32_t *iters) {
   return solve_host<double>(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters);
+}
+
+extern "C" int mpc_solve_batch_host_model(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
+                                          const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
+                                          double *out, double *traj, int32_t *status, int32_t *iters) {
+  if (!model) return mpc_solve_batch_host(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters);
+  MPC_TRY(model_check(h));
+  return solve_host<double>(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters, nullptr, model);
 }
 
 extern "C" int mpc_solve_batch_host_warm(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,

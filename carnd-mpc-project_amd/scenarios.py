@@ -223,5 +223,13 @@ def weight_sweep(B, params, seed=DEFAULT_SEED, velocity_weights=(1.0, 100.0)):
     return np.ascontiguousarray(w)
 
 
+def model_rows(params, B):
+    """The uniform model array [6, B] of a parameter set: dt, Lf, max_steering, max_acceleration, max_deceleration, max_speed in
+    every column (rows _abi.MODEL_*) -- what a model call (solve_torch(model=...)) solves when nothing is varied; overwrite the
+    rows to sweep."""
+    col = np.array([getattr(params, name) for name in _abi.MODEL_ROWS], dtype=np.float64)
+    return np.ascontiguousarray(np.tile(col[:, None], (1, int(B))))
+
+
 def golden_dir():
     return os.path.join(_abi.ROOT, "tests", "golden")

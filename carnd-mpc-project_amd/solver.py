@@ -73,7 +73,7 @@ class BatchedMPC:
         return _abi.warm_rows(self.N)
 
     def solve_torch(self, state, coeffs, yaw_lo, yaw_hi, weights=None, want_traj=False, outputs=None, stream=None,
-                    warm=None, warm_status=None, want_warm=False, warm_opts=None):
+                    warm=None, warm_status=None, want_warm=False, warm_opts=None, model=None):
         """state [6,B], coeffs [5,B], yaw_lo/hi [B], weights [12,B] or None: CUDA tensors, float64 (float32 for a
         handle created with precision F32).  Asynchronous on ``stream`` (default: torch's current stream).  Returns the
         dict of output tensors.
@@ -81,7 +81,12 @@ class BatchedMPC:
         Warm start (opt-in, fp64 handles; mpc_solve_batch_device_warm): ``warm`` [warm_rows(), B] is the "warm" tensor an
         earlier call returned and ``warm_status`` [B] int32 that call's status (None: every column is valid); with
         ``want_warm`` (implied by ``warm``) the result holds "warm", the final primal-dual iterate -- written in place when
-        ``outputs`` carries the same tensor.  ``warm_opts``: an MpcWarmOpts (None: the library's defaults)."""
+        ``outputs`` carries the same tensor.  ``warm_opts``: an MpcWarmOpts (None: the library's defaults).
+
+        ``model`` [6, B] float64 (fp64 handles; mpc_solve_batch_device_model): dt, Lf, max_steering, max_acceleration,
+        max_deceleration and max_speed of every instance (rows _abi.MODEL_*, scenarios.model_rows gives a handle's own) -- one
+        launch of the single-phase fp64 solver whatever the handle's dispatch; an unusable column ends INFEASIBLE.  Not
+        together with a warm start."""
         import torch
         B = state.shape[1]
         dt = self._dtype()
@@ -98,6 +103,16 @@ class BatchedMPC:
             outputs = self.alloc_outputs(B, state.device, want_traj)
         s = stream if stream is not None else torch.cuda.current_stream(state.device)
         traj = outputs.get("traj")
+        if model is not None:
+            if warm is not None or want_warm:
+                raise ValueError("model and a warm start cannot be combined")
+            self._check_model(model, B)
+            check(library().mpc_solve_batch_device_model(
+                self._h, B, B, state.data_ptr(), coeffs.data_ptr(), yaw_lo.data_ptr(), yaw_hi.data_ptr(),
+                weights.data_ptr() if weights is not None else None, model.data_ptr(), outputs["out"].data_ptr(),
+                traj.data_ptr() if traj is not None else None, outputs["status"].data_ptr(), outputs["iters"].data_ptr(),
+                C.c_void_p(s.cuda_stream)), "mpc_solve_batch_device_model")
+            return outputs
         if warm is not None or want_warm:
             rows = self.warm_rows()
             if warm is not None and (warm.dtype != torch.float64 or not warm.is_cuda or not warm.is_contiguous() or tuple(warm.shape) != (rows, B)):
@@ -120,6 +135,12 @@ class BatchedMPC:
                  traj.data_ptr() if traj is not None else None, outputs["status"].data_ptr(),
                  outputs["iters"].data_ptr(), C.c_void_p(s.cuda_stream)), "mpc_solve_batch_device")
         return outputs
+
+    @staticmethod
+    def _check_model(model, B):
+        import torch
+        if model.dtype != torch.float64 or not model.is_cuda or not model.is_contiguous() or tuple(model.shape) != (_abi.NMODEL, B):
+            raise ValueError("model must be a contiguous float64 CUDA tensor of shape (%d, B)" % _abi.NMODEL)
 
     def _warm_args(self, res, B, device, warm, warm_status, warm_out):
         """The warm arguments of a run()-path call (checked); the "warm" tensor of the result is `warm_out` if given (in-place
@@ -232,13 +253,15 @@ class BatchedMPC:
         return res
 
     def rollout_torch(self, state, coeffs, yaw_lo, yaw_hi, steps, weights=None, want_hist=True, stream=None, warm_start=False,
-                      warm_opts=None, fused=False):
+                      warm_opts=None, fused=False, model=None):
         """Closed loop of src/test.cpp:79-111 for a batch: `steps` cold-started solves, each fed with the previous
         step-1 state.  `state` [6,B] is advanced in place.  Returns hist [steps,9,B], worst status, summed iters.
         ``warm_start``: every step after the first starts from the solution of the step before
         (mpc_rollout_batch_device_warm; same NLP, fewer iterations).
         ``fused``: the same rollout in one launch, every car advancing on its own (mpc_rollout_batch_device_fused; bitwise the
-        same results, rollout_fused_info() tells whether the fused kernel or the stepwise loop ran)."""
+        same results, rollout_fused_info() tells whether the fused kernel or the stepwise loop ran).
+        ``model`` [6, B]: every car's own dt, Lf and limits, as in solve_torch (mpc_rollout_batch_device_model: the stepwise cold
+        loop; not together with ``warm_start`` or ``fused``)."""
         import torch
         B = state.shape[1]
         dev = state.device
@@ -249,6 +272,15 @@ class BatchedMPC:
                "status": torch.empty((B,), dtype=torch.int32, device=dev),
                "iters": torch.empty((B,), dtype=torch.int32, device=dev)}
         s = stream if stream is not None else torch.cuda.current_stream(dev)
+        if model is not None:
+            if warm_start or fused:
+                raise ValueError("a model rollout is the stepwise cold loop: warm_start and fused are not available")
+            self._check_model(model, B)
+            check(library().mpc_rollout_batch_device_model(
+                self._h, B, B, int(steps), state.data_ptr(), coeffs.data_ptr(), yaw_lo.data_ptr(), yaw_hi.data_ptr(),
+                weights.data_ptr() if weights is not None else None, model.data_ptr(), res["hist"].data_ptr() if want_hist else None,
+                res["status"].data_ptr(), res["iters"].data_ptr(), C.c_void_p(s.cuda_stream)), "mpc_rollout_batch_device_model")
+            return res
         if fused:
             check(library().mpc_rollout_batch_device_fused(
                 self._h, B, B, int(steps), state.data_ptr(), coeffs.data_ptr(), yaw_lo.data_ptr(), yaw_hi.data_ptr(),
@@ -270,8 +302,9 @@ class BatchedMPC:
         return res
 
     # -- host path (numpy arrays; copies through PCIe) ------------------------
-    def solve_numpy(self, state, coeffs, yaw_lo, yaw_hi, weights=None, want_traj=False):
-        """Host arrays through mpc_solve_batch_host (float64), or mpc_solve_batch_host_f32 for an MPC_PRECISION_F32 handle."""
+    def solve_numpy(self, state, coeffs, yaw_lo, yaw_hi, weights=None, want_traj=False, model=None):
+        """Host arrays through mpc_solve_batch_host (float64), or mpc_solve_batch_host_f32 for an MPC_PRECISION_F32 handle.
+        ``model`` [6, B] float64: per-instance dt, Lf and limits as in solve_torch (mpc_solve_batch_host_model, fp64 handles)."""
         dt = np.float32 if self.f32 else np.float64
         f = lambda a: np.ascontiguousarray(np.asarray(a, dtype=dt))
         state, coeffs, yaw_lo, yaw_hi = f(state), f(coeffs), f(yaw_lo), f(yaw_hi)
@@ -283,6 +316,12 @@ class BatchedMPC:
         out = np.empty((_abi.NOUT, B), dtype=dt); status = np.empty(B, dtype=np.int32); iters = np.empty(B, dtype=np.int32)
         traj = np.empty((2 * self.N, B), dtype=dt) if want_traj else None
         p = lambda a: a.ctypes.data if a is not None else None
+        if model is not None:
+            model = np.ascontiguousarray(np.asarray(model, dtype=np.float64))
+            assert model.shape == (_abi.NMODEL, B)
+            check(library().mpc_solve_batch_host_model(self._h, B, B, p(state), p(coeffs), p(yaw_lo), p(yaw_hi), p(weights), p(model), p(out),
+                                                       p(traj), p(status), p(iters)), "mpc_solve_batch_host_model")
+            return {"out": out, "status": status, "iters": iters, "traj": traj}
         fn = library().mpc_solve_batch_host_f32 if self.f32 else library().mpc_solve_batch_host
         check(fn(self._h, B, B, p(state), p(coeffs), p(yaw_lo), p(yaw_hi), p(weights), p(out), p(traj), p(status), p(iters)), "mpc_solve_batch_host")
         return {"out": out, "status": status, "iters": iters, "traj": traj}

@@ -37,6 +37,9 @@ extern "C" {
 #define MPC_NOUT 9     /* x1,y1,psi1,v1,cte1,epsi1,delta0,a0,cost (MPC.cpp:322-324) */
 #define MPC_MAX_N 64   /* largest horizon the kernels are sized for */
 #define MPC_MAX_SOC 16 /* largest MpcParams.max_soc */
+#define MPC_NMODEL 6   /* model values an instance may bring along (the mpc_*_model entry points) */
+enum { MPC_MODEL_DT = 0, MPC_MODEL_LF, MPC_MODEL_MAX_STEERING, MPC_MODEL_MAX_ACCELERATION,
+       MPC_MODEL_MAX_DECELERATION, MPC_MODEL_MAX_SPEED };      /* rows of model [6][ld], units of MpcParams */
 
 /* return codes */
 enum {
@@ -429,6 +432,37 @@ int mpc_telemetry_batch_device_warm(MpcHandle *h, int64_t B, int64_t ld, int npt
 int mpc_telemetry_batch_host_warm(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
                                   const double *ptsx, const double *ptsy, const double *warm_in, const int32_t *warm_status,
                                   double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts, double *cmd, int32_t *status);
+/* ---- per-instance model values (dt, Lf, limits) ----------------------------------------------------------------------------
+ * A batch whose instances differ in the time step, the wheelbase or the actuator and speed limits -- a dt study, a fleet of
+ * different vehicles, randomised limits over many closed loops -- in one launch on one handle.  Each entry point is the one
+ * without `_model` plus `model`, [MPC_NMODEL][ld] doubles addressed like `weights` (rows MPC_MODEL_*, in the units of the MpcParams
+ * fields of the same names).
+ * model == NULL: the call IS the entry point without `_model`, with every convention it has (deferred tails, take order, the
+ *   wave path), bitwise.
+ * model != NULL: instance i is solved with dt, Lf, max_steering, max_acceleration, max_deceleration and max_speed of its column.
+ *   Everything else is the handle's: N, the weights (unless `weights` is given), the panic thresholds, the speed tables, every
+ *   solver control and max_soc.  The speed target is computeSpeedTarget(0, max_speed_i) on the handle's tables; the relaxed bounds
+ *   of the solve and the projection of honor_original_bounds use the instance's limits.
+ * Dispatch: a model call is always ONE launch of the single-phase fp64 lane kernel, at every B -- no wave path, no deferred
+ *   tails (no instance is ever MPC_STATUS_PENDING), no pass cuts, no take order.  A handle whose ordinary solve starts in fp32
+ *   (f64_f32_start = 1, or AUTO at N >= 15: the library's default parameters at N = 25) is served the same way on its fp64
+ *   workspace; such a call is never refused, allocates nothing, and its results are bitwise those of a handle created with
+ *   f64_f32_start = 0.  max_soc > 0 is honoured.  MPC_PRECISION_F32 handles: MPC_ERR_INVALID with a message.
+ * A column that is not usable -- a non-finite value, dt <= 0, Lf <= 0, max_steering <= 0, max_speed <= 0 (what mpc_create refuses
+ *   in MpcParams), max_acceleration <= 0 or max_deceleration >= 0 (the start point a = 0 must lie inside the box) -- ends that
+ *   instance with MPC_STATUS_INFEASIBLE and the start point in `out`, as an infeasible start does, with no not-a-number; the
+ *   batch goes on.  A state with |v| beyond the instance's own relaxed speed limit is MPC_STATUS_INFEASIBLE as ever.
+ * The rollout is the stepwise cold loop of mpc_rollout_batch_device with `model` passed to every step.  The run() / telemetry
+ * entry points read Lf and the limits of their pre- and post-processing from the handle and have no such form. */
+int mpc_solve_batch_device_model(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
+                                 const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
+                                 double *out, double *traj, int32_t *status, int32_t *iters, void *stream);
+int mpc_solve_batch_host_model(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
+                               const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
+                               double *out, double *traj, int32_t *status, int32_t *iters);
+int mpc_rollout_batch_device_model(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
+                                   const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
+                                   double *hist, int32_t *status, int32_t *iters, void *stream);
 /* ---- the wire side of the handler (src/mpc_main.cpp:26-36, 81-222, DATA.md:5-16) --------
  * Everything between the bytes of a simulator frame and the bytes of the reply; the WebSocket server itself is out of
  * scope.  See csrc/mpc_wire.cpp. */

@@ -1,0 +1,138 @@
+"""Per-instance model values (include/mpc_amd.h, "per-instance model values": dt, Lf and the four limits of every instance in
+model [6][ld]), checked without a GPU: the CPU build tests/model_twin calls the same Solver::setup_model / unpack_model as the MODEL
+builds of the lane kernel.  The yardstick is the oracle solving every instance with its own OrcConfig."""
+import ctypes as C
+import os
+import re
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+from helpers import twin_solve
+from model_helpers import INFEASIBLE, assert_matches_oracle, load_model_twin, oracle_model_solve, population, twin_model_solve
+
+KEYS = ("out", "traj", "status", "iters")
+# what the oracle does on the stated population (193 instances, lake_track_batch seed 77, rows default_rng(5)):
+# converged / INFEASIBLE (|v| above the instance's own speed limit); nothing else occurs
+ORACLE_COUNTS = {"config-fast.json": (176, 17), "config-stable.json": (166, 27)}
+
+
+@pytest.fixture(scope="module")
+def model_twin():
+    """TEST-ONLY CPU build of the per-instance model values (tests/model_twin)."""
+    return load_model_twin()
+
+
+@pytest.mark.parametrize("cfgname", sorted(ORACLE_COUNTS))
+def test_population_against_the_oracle(pkg, model_twin, golden_dir, waypoints, cfgname):
+    params = pkg.params_from_json(os.path.join(golden_dir, cfgname))
+    b, model = population(pkg, params, waypoints)
+    ref = oracle_model_solve(cfgname, b, model)
+    assert ((ref["status"] == 0).sum(), (ref["status"] == INFEASIBLE).sum()) == ORACLE_COUNTS[cfgname] and ref["iters"].max() <= 25
+    got = twin_model_solve(model_twin, params, b, model)
+    assert_matches_oracle(got, ref, what=cfgname)
+    # the rows matter: the uniform solve gives another steering angle nearly everywhere
+    uni = twin_model_solve(model_twin, params, b, pkg.scenarios.model_rows(params, 193))
+    assert (np.abs(uni["out"][6] - got["out"][6]) > 1e-4).sum() >= 150
+
+
+def test_model_rows(pkg, golden_dir):
+    params = pkg.params_from_json(os.path.join(golden_dir, "config-fast.json"))
+    m = pkg.scenarios.model_rows(params, 5)
+    assert m.shape == (6, 5) and m.dtype == np.float64 and m.flags.c_contiguous
+    assert m[:, 3].tolist() == [params.dt, params.Lf, params.max_steering, params.max_acceleration, params.max_deceleration, params.max_speed]
+
+
+@pytest.mark.parametrize("cfgname", sorted(ORACLE_COUNTS))
+def test_uniform_rows_are_the_plain_solve_bitwise(pkg, model_twin, host_twin, golden_dir, waypoints, cfgname):
+    params = pkg.params_from_json(os.path.join(golden_dir, cfgname))
+    b, _ = population(pkg, params, waypoints)
+    plain = twin_solve(host_twin, params, b)
+    got = twin_model_solve(model_twin, params, b, pkg.scenarios.model_rows(params, 193))
+    for k in KEYS:
+        assert np.array_equal(plain[k], got[k], equal_nan=True), k
+
+
+@pytest.mark.parametrize("max_soc", [0, 4])
+def test_uniform_rows_are_the_plain_solve_bitwise_on_the_hard_instances(pkg, model_twin, host_twin, golden_dir, max_soc):
+    d = np.load(os.path.join(golden_dir, "soc_instances.npz"))
+    for pop, over in (("n10", {}), ("n25", dict(N=25, dt=0.05))):
+        params = pkg.params_from_json(os.path.join(golden_dir, "config-fast.json" if pop == "n10" else "config-stable.json"), **over)
+        params.max_soc = max_soc
+        b = {k: np.ascontiguousarray(d["%s_%s" % (pop, k)]) for k in ("state", "coeffs", "yaw_lo", "yaw_hi")}
+        B = b["state"].shape[1]
+        plain = twin_solve(host_twin, params, b)
+        got = twin_model_solve(model_twin, params, b, pkg.scenarios.model_rows(params, B))
+        assert (plain["status"] != 0).any() or plain["iters"].max() > 25      # (they are hard)
+        for k in KEYS:
+            assert np.array_equal(plain[k], got[k], equal_nan=True), (pop, k)
+
+
+def test_spoilt_columns(pkg, model_twin, golden_dir, waypoints):
+    """A column that cannot be used -- not-a-number, dt = 0, Lf < 0, max_deceleration > 0, and the other values the header names --
+    ends its instance INFEASIBLE with finite outputs; the neighbours are bitwise what they are without the spoilt columns."""
+    params = pkg.params_from_json(os.path.join(golden_dir, "config-fast.json"))
+    b, model = population(pkg, params, waypoints)
+    clean = twin_model_solve(model_twin, params, b, model)
+    spoilt = model.copy()
+    # (instances the clean solve converges on)
+    at = [int(i) for i in np.where(clean["status"] == 0)[0][[3, 20, 47, 64, 90, 101, 120, 133, 150]]]
+    spoilt[2, at[0]] = np.nan
+    spoilt[0, at[1]] = 0.0
+    spoilt[1, at[2]] = -2.67
+    spoilt[4, at[3]] = 5.0
+    spoilt[5, at[4]] = np.inf
+    spoilt[3, at[5]] = 0.0
+    spoilt[5, at[6]] = -40.0
+    spoilt[2, at[7]] = -0.4
+    spoilt[:, at[8]] = np.nan
+    got = twin_model_solve(model_twin, params, b, spoilt)
+    assert (got["status"][at] == INFEASIBLE).all(), got["status"][at]
+    assert np.isfinite(got["out"]).all() and np.isfinite(got["traj"]).all()
+    rest = np.setdiff1d(np.arange(193), at)
+    for k in KEYS:
+        assert np.array_equal(got[k][..., rest], clean[k][..., rest]), k
+
+
+def _c_prototype(header, name):
+    m = re.search(r"\bint\s+%s\s*\(([^;]*?)\)\s*;" % name, header, re.S)
+    assert m, name
+    return [re.sub(r"\s+", " ", a).strip() for a in m.group(1).split(",")]
+
+
+def test_model_abi(pkg):
+    """The three symbols exist with the header's signatures, MPC_NMODEL == 6 and the rows in the stated order, the ABI version is
+    unchanged, and a NULL handle is refused (with and without a model array)."""
+    from carnd_mpc_project_amd import _abi
+    lib = pkg.library()
+    assert lib.mpc_abi_version() == 5 and _abi.NMODEL == 6
+    header = open(os.path.join(_abi.ROOT, "include", "mpc_amd.h")).read()
+    solve = ["MpcHandle *h", "int64_t B", "int64_t ld", "const double *state", "const double *coeffs", "const double *yaw_lo",
+             "const double *yaw_hi", "const double *weights", "const double *model", "double *out", "double *traj", "int32_t *status",
+             "int32_t *iters"]
+    assert _c_prototype(header, "mpc_solve_batch_device_model") == solve + ["void *stream"]
+    assert _c_prototype(header, "mpc_solve_batch_host_model") == solve
+    assert _c_prototype(header, "mpc_rollout_batch_device_model") == (
+        ["MpcHandle *h", "int64_t B", "int64_t ld", "int steps", "double *state"] + solve[4:9] +
+        ["double *hist", "int32_t *status", "int32_t *iters", "void *stream"])
+    # the same argument lists with `model` taken out are the entry points a NULL model forwards to
+    for name in ("mpc_solve_batch_device", "mpc_solve_batch_host", "mpc_rollout_batch_device"):
+        assert [a for a in _c_prototype(header, name + "_model") if a != "const double *model"] == _c_prototype(header, name)
+        assert len(getattr(lib, name + "_model").argtypes) == len(getattr(lib, name).argtypes) + 1
+    src = ('#include <stdio.h>\n#include "mpc_amd.h"\nint main(){printf("%d %d %d %d %d %d %d %d %zu\\n", MPC_NMODEL, MPC_MODEL_DT, MPC_MODEL_LF, '
+           'MPC_MODEL_MAX_STEERING, MPC_MODEL_MAX_ACCELERATION, MPC_MODEL_MAX_DECELERATION, MPC_MODEL_MAX_SPEED, MPC_ABI_VERSION, sizeof(MpcParams));return 0;}\n')
+    with tempfile.TemporaryDirectory() as d:
+        open(os.path.join(d, "p.c"), "w").write(src)
+        subprocess.check_call(["gcc", "-I", os.path.join(_abi.ROOT, "include"), "-o", os.path.join(d, "p"), os.path.join(d, "p.c")])
+        out = [int(x) for x in subprocess.check_output([os.path.join(d, "p")]).split()]
+    assert out == [6, 0, 1, 2, 3, 4, 5, 5, C.sizeof(pkg.MpcParams)]
+    assert _abi.MODEL_ROWS == ("dt", "Lf", "max_steering", "max_acceleration", "max_deceleration", "max_speed")
+    one = np.zeros(9); st = np.zeros(1, dtype=np.int32); m = np.ones((6, 1))
+    p = lambda a: a.ctypes.data
+    for model in (p(m), None):
+        assert lib.mpc_solve_batch_device_model(None, 1, 1, p(one), p(one), p(one), p(one), None, model, p(one), None, p(st), None, None) == -1
+        assert lib.mpc_solve_batch_host_model(None, 1, 1, p(one), p(one), p(one), p(one), None, model, p(one), None, p(st), None) == -1
+        assert lib.mpc_rollout_batch_device_model(None, 1, 1, 2, p(one), p(one), p(one), p(one), None, model, None, p(st), None, None) == -1
+        assert lib.mpc_last_error()
