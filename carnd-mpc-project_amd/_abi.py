@@ -93,7 +93,9 @@ EXPORTS = ["mpc_params_default", "mpc_params_load_json", "mpc_create", "mpc_set_
            "mpc_rollout_batch_device_warm", "mpc_run_batch_device_warm", "mpc_run_batch_host_warm",
            "mpc_telemetry_batch_device_warm", "mpc_telemetry_batch_host_warm", "mpc_wire_telemetry_batch_host_warm",
            "mpc_rollout_batch_device_fused", "mpc_rollout_fused_info",
-           "mpc_solve_batch_device_model", "mpc_solve_batch_host_model", "mpc_rollout_batch_device_model"]
+           "mpc_solve_batch_device_model", "mpc_solve_batch_host_model", "mpc_rollout_batch_device_model",
+           "mpc_solve_batch_device_warm_model", "mpc_solve_batch_host_warm_model", "mpc_rollout_batch_device_warm_model",
+           "mpc_rollout_batch_device_fused_model"]
 
 _lib = None
 
@@ -179,6 +181,15 @@ def library():
     L.mpc_solve_batch_device_model.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [DP] * 10 + [C.c_void_p]
     L.mpc_solve_batch_host_model.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [DP] * 10
     L.mpc_rollout_batch_device_model.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 9 + [C.c_void_p]
+    # ... and the warm / fused ones likewise
+    L.mpc_solve_batch_device_warm_model.argtypes = ([C.c_void_p, C.c_int64, C.c_int64] + [DP] * 9 + [C.c_int64, C.POINTER(MpcWarmOpts)] +
+                                                    [DP] * 4 + [C.c_void_p])
+    L.mpc_solve_batch_host_warm_model.argtypes = ([C.c_void_p, C.c_int64, C.c_int64] + [DP] * 9 + [C.c_int64, C.POINTER(MpcWarmOpts)] +
+                                                  [DP] * 4)
+    L.mpc_rollout_batch_device_warm_model.argtypes = ([C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 6 + [C.POINTER(MpcWarmOpts)] +
+                                                      [DP] * 3 + [C.c_void_p])
+    L.mpc_rollout_batch_device_fused_model.argtypes = ([C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 6 +
+                                                       [C.c_int, C.POINTER(MpcWarmOpts)] + [DP] * 3 + [C.c_void_p])
     # the run() path: the cold arguments up to ptsy, then warm_in, warm_status, warm_out, ld_warm, opts, then the cold outputs
     WARM = [DP] * 3 + [C.c_int64, C.POINTER(MpcWarmOpts)]
     L.mpc_run_batch_device_warm.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 3 + WARM + [DP] * 5 + [C.c_void_p]

@@ -223,6 +223,16 @@ struct MpcPhaseRoll : MpcPhaseWarm {
   int32_t *status, *iters;        /* per car: worst status, summed iterations (iters may be nullptr) */
 };
 
+/* What the WARM+MODEL and ROLL+MODEL builds get (the mpc_*_warm_model entry points, mpc_rollout_batch_device_fused_model): the warm
+ * or rollout arguments and the instances' columns, read as in MpcPhaseModel.  Types of their own once more: the kernel arguments of
+ * every other build are what they were. */
+struct MpcPhaseWarmModel : MpcPhaseWarm {
+  const double *model;
+};
+struct MpcPhaseRollModel : MpcPhaseRoll {
+  const double *model;
+};
+
 /* The take-order key of every instance of a launch (csrc/mpc_take_key.h) and the bins' lists: one thread per instance, a wave
  * appends its instances to the bins' lists.  No LDS and few registers: its waves fit beside the resident waves of a bulk
  * launch.  cnt[] is zero on entry (it lives in the launch's counter block). */
@@ -304,7 +314,14 @@ template <class RIO, class R> struct OutRef {
  * or consumes the counter.  These builds are launched without lane compaction, cuts and deferred tails (the step index lives in
  * the lane's registers and does not travel). */
 /* MODEL (the mpc_*_model entry points): every set-up and the hand-over read dt, Lf and the four limits from the instance's column of
- * T.model instead of P (Solver::setup_model / unpack_model), by instance index and outside the sweeps; nothing else differs. */
+ * T.model instead of P (Solver::setup_model / unpack_model), by instance index and outside the sweeps; nothing else differs.
+ * With WARM: warm_point() judges a record against the relaxed box that setup_model has just set from the column, and the cold solve
+ * that follows a refused record or a failed warm attempt starts from the solver's own members -- no set-up in between.  With ROLL:
+ * the car taken again is set up from its column like a fresh one, and the hand-over of a step projects into the column's limits. */
+template <bool ROLL, bool WARM, bool MODEL>
+using MpcPhaseOf = std::conditional_t<ROLL, std::conditional_t<MODEL, MpcPhaseRollModel, MpcPhaseRoll>,
+                                      std::conditional_t<WARM, std::conditional_t<MODEL, MpcPhaseWarmModel, MpcPhaseWarm>,
+                                                         std::conditional_t<MODEL, MpcPhaseModel, MpcPhase>>>;
 template <bool STAGING, class R, class RIO = R, class RSRC = RIO, bool SOC = false, bool WARM = false, bool ROLL = false, bool MODEL = false>
 __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
     const MpcParams P, const int64_t B, const int64_t ld, const int64_t ldo, const RIO *__restrict__ state,
@@ -312,11 +329,11 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
     const RIO *__restrict__ weights, RIO *__restrict__ out, RIO *__restrict__ traj,
     int32_t *__restrict__ status, int32_t *__restrict__ iters, R *__restrict__ wsbase,
     const int64_t tile_reals,
-    const std::conditional_t<ROLL, MpcPhaseRoll, std::conditional_t<WARM, MpcPhaseWarm, std::conditional_t<MODEL, MpcPhaseModel, MpcPhase>>> T) {
+    const MpcPhaseOf<ROLL, WARM, MODEL> T) {
   extern __shared__ double smem[];
   static_assert(!WARM || (sizeof(R) == 8 && std::is_same<R, RIO>::value && std::is_same<R, RSRC>::value && !SOC), "warm start: the plain fp64 solve only");
   static_assert(!ROLL || (sizeof(R) == 8 && std::is_same<R, RIO>::value && std::is_same<R, RSRC>::value && !SOC), "fused rollout: the plain fp64 solve only");
-  static_assert(!MODEL || (sizeof(R) == 8 && std::is_same<R, RIO>::value && std::is_same<R, RSRC>::value && !WARM && !ROLL), "per-instance model values: the cold fp64 solve only");
+  static_assert(!MODEL || (sizeof(R) == 8 && std::is_same<R, RIO>::value && std::is_same<R, RSRC>::value), "per-instance model values: the fp64 solve only");
   using WS = std::conditional_t<SOC, mpc::TiledSocWorkspace<STAGING, R>, mpc::TiledWorkspace<STAGING, R>>;
   using SV = mpc::Solver<WS, R, 0, SOC>;
   using FL = mpc::Fields<R>;
@@ -395,7 +412,12 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
             using Car = mpc::RolloutCar;
             double *o = T.hist + (int64_t)step * T.hist_step + i;
             const int64_t l = ldo;
-            S.unpack([o, l](int q) { return OutRef<RIO, R>{o + q * l}; }, [](int) { return OutRef<RIO, R>{nullptr}; }, false, (R)yaw_lo[i], (R)yaw_hi[i]);
+            if constexpr (MODEL) {             /* the car's own limits, from its column */
+              const double *mc = T.model + i;
+              const int64_t lm = ld;
+              S.unpack_model([mc, lm](int q) { return mc[q * lm]; }, [o, l](int q) { return OutRef<RIO, R>{o + q * l}; },
+                             [](int) { return OutRef<RIO, R>{nullptr}; }, false, (R)yaw_lo[i], (R)yaw_hi[i]);
+            } else S.unpack([o, l](int q) { return OutRef<RIO, R>{o + q * l}; }, [](int) { return OutRef<RIO, R>{nullptr}; }, false, (R)yaw_lo[i], (R)yaw_hi[i]);
             double *sp = T.state + i;
             const int64_t ls = ld;
             Car::next_state([o, l](int q) { return o[q * l]; }, [sp, ls](int q, double v) { sp[q * ls] = v; });
@@ -2028,6 +2050,9 @@ static int launch_lanes(MpcHandle *h, LaneBuild build, const SolveIO<RIO> &io, h
   if (build == LaneBuild::mixed_f64) return with_bool(soc, [&](auto soc_build) { return go(yes, double{}, float{}, soc_build, no, h->ws_stride_f64, T, no); });
   return with_bool(h->staging, [&](auto staging) {
     if constexpr (sizeof(RIO) == 8) {
+      if (io.model && warm)
+        return go(staging, RIO{}, RIO{}, no, yes, h->ws_stride,
+                  MpcPhaseWarmModel{MpcPhaseWarm{T, warm->warm_in, warm->warm_status, warm->warm_out, warm->ld_warm, warm->opts, warm->psi_box ? 1 : 0}, io.model}, yes);
       if (io.model) return with_bool(soc, [&](auto soc_build) { return go(staging, RIO{}, RIO{}, soc_build, no, h->ws_stride, MpcPhaseModel{T, io.model}, yes); });
       if (warm) return go(staging, RIO{}, RIO{}, no, yes, h->ws_stride, MpcPhaseWarm{T, warm->warm_in, warm->warm_status, warm->warm_out, warm->ld_warm, warm->opts, warm->psi_box ? 1 : 0}, no);
       if (soc) return go(staging, RIO{}, RIO{}, yes, no, h->ws_stride, T, no);
@@ -2164,7 +2189,8 @@ static int solve_end(MpcHandle *h, const SolveIO<R> &io, hipStream_t s, MpcHandl
  * fp64 handle, not mixed, no SOC) -- a single phase of the WARM build, or the warm wave kernel; it never defers, cuts or orders.
  * call.model: a model call (model_check has passed: an fp64 handle) -- ONE launch of the MODEL build of the single-phase fp64 lane
  * kernel on h->ws at every B, also on a handle whose ordinary solve starts in fp32 (on an fp64 handle h->ws has the fp64 layout):
- * no wave path, no mixed-precision launch, and it never defers, cuts or orders either. */
+ * no wave path, no mixed-precision launch, and it never defers, cuts or orders either.  warm and call.model together (warm_model_check
+ * has passed: an fp64 handle, no SOC): the same one launch, of the WARM+MODEL build -- lane compaction included, as for a warm call. */
 template <class R>
 static int launch_solve(MpcHandle *h, const SolveIO<R> &call, void *stream_, bool with_stats = true, bool may_defer = false,
                         bool may_order = false, const WarmIO *warm = nullptr) {
@@ -2277,14 +2303,8 @@ extern "C" int mpc_warm_opts_default(MpcWarmOpts *o) {
   return MPC_OK;
 }
 
-/* what every warm entry point checks before it touches anything; *W: the options in effect */
-static int warm_check(MpcHandle *h, const MpcWarmOpts *opts, MpcWarmOpts *W) {
-  if (!h) { g_last_error = "NULL handle"; return MPC_ERR_INVALID; }
-  if (h->params.precision != MPC_PRECISION_F64) { g_last_error = "warm start: fp64 handles only (this one was created with MPC_PRECISION_F32)"; return MPC_ERR_INVALID; }
-  if (h->mixed) {
-    g_last_error = "warm start is not available on a handle whose solve starts in fp32 (two launches): create it with MpcParams.f64_f32_start = 0";
-    return MPC_ERR_UNSUPPORTED;
-  }
+/* the part of a warm entry point's checks that does not depend on how the handle solves: no SOC, and the options; *W: those in effect */
+static int warm_opts_check(MpcHandle *h, const MpcWarmOpts *opts, MpcWarmOpts *W) {
   if (h->params.max_soc > 0) { g_last_error = "warm start is not available with the second-order correction: set MpcParams.max_soc = 0"; return MPC_ERR_UNSUPPORTED; }
   (void)mpc_warm_opts_default(W);
   if (opts) {
@@ -2298,6 +2318,24 @@ static int warm_check(MpcHandle *h, const MpcWarmOpts *opts, MpcWarmOpts *W) {
   return MPC_OK;
 }
 
+/* what every warm entry point checks before it touches anything; *W: the options in effect */
+static int warm_check(MpcHandle *h, const MpcWarmOpts *opts, MpcWarmOpts *W) {
+  if (!h) { g_last_error = "NULL handle"; return MPC_ERR_INVALID; }
+  if (h->params.precision != MPC_PRECISION_F64) { g_last_error = "warm start: fp64 handles only (this one was created with MPC_PRECISION_F32)"; return MPC_ERR_INVALID; }
+  if (h->mixed) {
+    g_last_error = "warm start is not available on a handle whose solve starts in fp32 (two launches): create it with MpcParams.f64_f32_start = 0";
+    return MPC_ERR_UNSUPPORTED;
+  }
+  return warm_opts_check(h, opts, W);
+}
+/* ... and a warm call with per-instance model values (model != NULL): the model rule decides which handles are accepted -- every fp64
+ * handle, also one whose ordinary solve starts in fp32, because a model call is the single-phase fp64 launch on every handle -- and
+ * the warm rule the rest */
+static int warm_model_check(MpcHandle *h, const MpcWarmOpts *opts, MpcWarmOpts *W) {
+  MPC_TRY(model_check(h));
+  return warm_opts_check(h, opts, W);
+}
+
 extern "C" int mpc_solve_batch_device_warm(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
                                            const double *yaw_lo, const double *yaw_hi, const double *weights, const double *warm_in,
                                            const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts,
@@ -2305,6 +2343,21 @@ extern "C" int mpc_solve_batch_device_warm(MpcHandle *h, int64_t B, int64_t ld, 
   WarmIO warm{warm_in, warm_status, warm_out, ld_warm, {}};
   MPC_TRY(warm_check(h, opts, &warm.opts));
   return launch_solve<double>(h, {B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters}, stream_, true, false, false, &warm);
+}
+
+extern "C" int mpc_solve_batch_device_warm_model(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
+                                                 const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
+                                                 const double *warm_in, const int32_t *warm_status, double *warm_out, int64_t ld_warm,
+                                                 const MpcWarmOpts *opts, double *out, double *traj, int32_t *status, int32_t *iters,
+                                                 void *stream_) {
+  if (!model)
+    return mpc_solve_batch_device_warm(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, warm_in, warm_status, warm_out, ld_warm, opts, out, traj,
+                                       status, iters, stream_);
+  WarmIO warm{warm_in, warm_status, warm_out, ld_warm, {}};
+  MPC_TRY(warm_model_check(h, opts, &warm.opts));
+  SolveIO<double> io{B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters};
+  io.model = model;
+  return launch_solve<double>(h, io, stream_, true, false, false, &warm);
 }
 
 /* MPC_PRECISION_F32: the same solve with fp32 inputs, outputs and workspace (handle created with precision F32) */
@@ -2522,7 +2575,7 @@ static int rollout_args(const MpcHandle *h, int64_t B, int64_t ld, int steps, co
 }
 
 /* The rollout: `steps` solves, each followed by the step kernel.  W != NULL: every step after the first is warm-started from the step
- * before (the handle keeps the buffer).  model != NULL (cold only): mpc_rollout_batch_device_model. */
+ * before (the handle keeps the buffer).  model != NULL: the cars' columns go to every step (model_check has passed), cold or warm. */
 static int rollout_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs, const double *yaw_lo,
                         const double *yaw_hi, const double *weights, const MpcWarmOpts *W, double *hist, int32_t *status, int32_t *iters,
                         void *stream_, const double *model = nullptr) {
@@ -2569,17 +2622,29 @@ extern "C" int mpc_rollout_batch_device_warm(MpcHandle *h, int64_t B, int64_t ld
   return rollout_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, &W, hist, status, iters, stream_);
 }
 
+extern "C" int mpc_rollout_batch_device_warm_model(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
+                                                   const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
+                                                   const MpcWarmOpts *opts, double *hist, int32_t *status, int32_t *iters, void *stream_) {
+  if (!model) return mpc_rollout_batch_device_warm(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, opts, hist, status, iters, stream_);
+  MpcWarmOpts W;
+  MPC_TRY(warm_model_check(h, opts, &W));
+  return rollout_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, &W, hist, status, iters, stream_, model);
+}
+
 /* The rollout in one launch: the ROLL build of the lane kernel, a lane per car for all `steps` solves (see mpc_solve_kernel).  One
  * rule decides: fused == stepwise on every handle.  The fused kernel is the single-phase fp64 lane kernel, so it runs where the
  * stepwise loop would launch exactly that at every step (an fp64 handle, no fp32 start, no SOC, B above the wave limit); everywhere
- * else -- and for an fp32 handle, which the loop refuses -- the call IS the stepwise loop.  W != NULL: warm (warm_check has passed). */
+ * else -- and for an fp32 handle, which the loop refuses -- the call IS the stepwise loop.  W != NULL: warm (warm_check has passed).
+ * model != NULL (model_check has passed: an fp64 handle): the stepwise model loop launches the single-phase fp64 lane kernel at every B
+ * and on a handle whose ordinary solve starts in fp32 as well, so the one launch -- the ROLL+MODEL builds -- runs at every B >= 1 of
+ * every handle without SOC; with SOC (a cold call; a warm one has been refused) the call is the stepwise model loop. */
 static int rollout_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs, const double *yaw_lo,
                               const double *yaw_hi, const double *weights, const MpcWarmOpts *W, double *hist, int32_t *status,
-                              int32_t *iters, void *stream_) {
+                              int32_t *iters, void *stream_, const double *model = nullptr) {
   MPC_TRY(rollout_args(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, status));
-  const bool wave_path = h->wave_max_batch > 0 && B <= h->wave_max_batch;
-  if (B == 0 || h->params.precision != MPC_PRECISION_F64 || h->mixed || h->params.max_soc > 0 || wave_path) {
-    MPC_TRY(rollout_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, W, hist, status, iters, stream_));
+  const bool wave_path = !model && h->wave_max_batch > 0 && B <= h->wave_max_batch;
+  if (B == 0 || h->params.precision != MPC_PRECISION_F64 || (h->mixed && !model) || h->params.max_soc > 0 || wave_path) {
+    MPC_TRY(rollout_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, W, hist, status, iters, stream_, model));
     ++h->n_roll_stepwise;
     return MPC_OK;
   }
@@ -2605,8 +2670,12 @@ static int rollout_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, do
   MPC_TRY(with_bool(h->staging, [&](auto staging) {
     return with_bool(W != nullptr, [&](auto warm_build) {
       constexpr bool STAGING = decltype(staging)::value;
-      return launch_kernel(mpc_solve_kernel<STAGING, double, double, double, false, decltype(warm_build)::value, true>, grid,
-                           STAGING ? staging_lds_bytes<double>() : 0, s, h, io, (double *)h->ws, h->ws_stride, R);
+      constexpr bool WARM = decltype(warm_build)::value;
+      const size_t lds = STAGING ? staging_lds_bytes<double>() : 0;
+      if (model)
+        return launch_kernel(mpc_solve_kernel<STAGING, double, double, double, false, WARM, true, true>, grid, lds, s, h, io, (double *)h->ws,
+                             h->ws_stride, MpcPhaseRollModel{R, model});
+      return launch_kernel(mpc_solve_kernel<STAGING, double, double, double, false, WARM, true>, grid, lds, s, h, io, (double *)h->ws, h->ws_stride, R);
     });
   }));
   MPC_TRY(solve_end(h, io, s, rec, tp, false));
@@ -2620,6 +2689,18 @@ extern "C" int mpc_rollout_batch_device_fused(MpcHandle *h, int64_t B, int64_t l
   MpcWarmOpts W;
   if (warm_start) MPC_TRY(warm_check(h, opts, &W));
   return rollout_fused_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, warm_start ? &W : nullptr, hist, status, iters, stream_);
+}
+
+extern "C" int mpc_rollout_batch_device_fused_model(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
+                                                    const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
+                                                    int warm_start, const MpcWarmOpts *opts, double *hist, int32_t *status, int32_t *iters,
+                                                    void *stream_) {
+  if (!model)
+    return mpc_rollout_batch_device_fused(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, warm_start, opts, hist, status, iters, stream_);
+  MpcWarmOpts W;
+  if (warm_start) MPC_TRY(warm_model_check(h, opts, &W));
+  else MPC_TRY(model_check(h));
+  return rollout_fused_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, warm_start ? &W : nullptr, hist, status, iters, stream_, model);
 }
 
 extern "C" int mpc_rollout_fused_info(const MpcHandle *h, int64_t *out2) {
@@ -2732,6 +2813,18 @@ extern "C" int mpc_solve_batch_host_warm(MpcHandle *h, int64_t B, int64_t ld, co
   WarmIO hw{warm_in, warm_status, warm_out, ld_warm, {}};
   MPC_TRY(warm_check(h, opts, &hw.opts));
   return solve_host<double>(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters, &hw);
+}
+
+extern "C" int mpc_solve_batch_host_warm_model(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
+                                               const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
+                                               const double *warm_in, const int32_t *warm_status, double *warm_out, int64_t ld_warm,
+                                               const MpcWarmOpts *opts, double *out, double *traj, int32_t *status, int32_t *iters) {
+  if (!model)
+    return mpc_solve_batch_host_warm(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, warm_in, warm_status, warm_out, ld_warm, opts, out, traj,
+                                     status, iters);
+  WarmIO hw{warm_in, warm_status, warm_out, ld_warm, {}};
+  MPC_TRY(warm_model_check(h, opts, &hw.opts));
+  return solve_host<double>(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters, &hw, model);
 }
 
 extern "C" int mpc_solve_batch_host_f32(MpcHandle *h, int64_t B, int64_t ld, const float *state,

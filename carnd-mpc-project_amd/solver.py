@@ -85,8 +85,8 @@ class BatchedMPC:
 
         ``model`` [6, B] float64 (fp64 handles; mpc_solve_batch_device_model): dt, Lf, max_steering, max_acceleration,
         max_deceleration and max_speed of every instance (rows _abi.MODEL_*, scenarios.model_rows gives a handle's own) -- one
-        launch of the single-phase fp64 solver whatever the handle's dispatch; an unusable column ends INFEASIBLE.  Not
-        together with a warm start."""
+        launch of the single-phase fp64 solver whatever the handle's dispatch; an unusable column ends INFEASIBLE.  Together
+        with the warm arguments: mpc_solve_batch_device_warm_model -- a record is judged against the instance's own limits."""
         import torch
         B = state.shape[1]
         dt = self._dtype()
@@ -104,9 +104,8 @@ class BatchedMPC:
         s = stream if stream is not None else torch.cuda.current_stream(state.device)
         traj = outputs.get("traj")
         if model is not None:
-            if warm is not None or want_warm:
-                raise ValueError("model and a warm start cannot be combined")
             self._check_model(model, B)
+        if model is not None and not (warm is not None or want_warm):
             check(library().mpc_solve_batch_device_model(
                 self._h, B, B, state.data_ptr(), coeffs.data_ptr(), yaw_lo.data_ptr(), yaw_hi.data_ptr(),
                 weights.data_ptr() if weights is not None else None, model.data_ptr(), outputs["out"].data_ptr(),
@@ -121,13 +120,16 @@ class BatchedMPC:
                 raise ValueError("warm_status must be an int32 CUDA tensor of shape (B,)")
             if outputs.get("warm") is None:
                 outputs["warm"] = torch.empty((rows, B), dtype=torch.float64, device=state.device)
-            check(library().mpc_solve_batch_device_warm(
-                self._h, B, B, state.data_ptr(), coeffs.data_ptr(), yaw_lo.data_ptr(), yaw_hi.data_ptr(),
-                weights.data_ptr() if weights is not None else None, warm.data_ptr() if warm is not None else None,
-                warm_status.data_ptr() if warm_status is not None else None, outputs["warm"].data_ptr(), B,
-                C.byref(warm_opts) if warm_opts is not None else None, outputs["out"].data_ptr(),
-                traj.data_ptr() if traj is not None else None, outputs["status"].data_ptr(), outputs["iters"].data_ptr(),
-                C.c_void_p(s.cuda_stream)), "mpc_solve_batch_device_warm")
+            head = (self._h, B, B, state.data_ptr(), coeffs.data_ptr(), yaw_lo.data_ptr(), yaw_hi.data_ptr(),
+                    weights.data_ptr() if weights is not None else None)
+            tail = (warm.data_ptr() if warm is not None else None, warm_status.data_ptr() if warm_status is not None else None,
+                    outputs["warm"].data_ptr(), B, C.byref(warm_opts) if warm_opts is not None else None, outputs["out"].data_ptr(),
+                    traj.data_ptr() if traj is not None else None, outputs["status"].data_ptr(), outputs["iters"].data_ptr(),
+                    C.c_void_p(s.cuda_stream))
+            if model is not None:
+                check(library().mpc_solve_batch_device_warm_model(*head, model.data_ptr(), *tail), "mpc_solve_batch_device_warm_model")
+            else:
+                check(library().mpc_solve_batch_device_warm(*head, *tail), "mpc_solve_batch_device_warm")
             return outputs
         fn = library().mpc_solve_batch_device_f32 if self.f32 else library().mpc_solve_batch_device
         check(fn(self._h, B, B, state.data_ptr(), coeffs.data_ptr(), yaw_lo.data_ptr(), yaw_hi.data_ptr(),
@@ -260,8 +262,8 @@ class BatchedMPC:
         (mpc_rollout_batch_device_warm; same NLP, fewer iterations).
         ``fused``: the same rollout in one launch, every car advancing on its own (mpc_rollout_batch_device_fused; bitwise the
         same results, rollout_fused_info() tells whether the fused kernel or the stepwise loop ran).
-        ``model`` [6, B]: every car's own dt, Lf and limits, as in solve_torch (mpc_rollout_batch_device_model: the stepwise cold
-        loop; not together with ``warm_start`` or ``fused``)."""
+        ``model`` [6, B]: every car's own dt, Lf and limits, as in solve_torch -- with every combination of ``warm_start`` and
+        ``fused`` (mpc_rollout_batch_device_model, _warm_model, _fused_model)."""
         import torch
         B = state.shape[1]
         dev = state.device
@@ -273,9 +275,18 @@ class BatchedMPC:
                "iters": torch.empty((B,), dtype=torch.int32, device=dev)}
         s = stream if stream is not None else torch.cuda.current_stream(dev)
         if model is not None:
-            if warm_start or fused:
-                raise ValueError("a model rollout is the stepwise cold loop: warm_start and fused are not available")
             self._check_model(model, B)
+            head = (self._h, B, B, int(steps), state.data_ptr(), coeffs.data_ptr(), yaw_lo.data_ptr(), yaw_hi.data_ptr(),
+                    weights.data_ptr() if weights is not None else None, model.data_ptr())
+            tail = (res["hist"].data_ptr() if want_hist else None, res["status"].data_ptr(), res["iters"].data_ptr(), C.c_void_p(s.cuda_stream))
+            opts = C.byref(warm_opts) if warm_opts is not None else None
+            if fused:
+                check(library().mpc_rollout_batch_device_fused_model(*head, 1 if warm_start else 0, opts, *tail),
+                      "mpc_rollout_batch_device_fused_model")
+                return res
+            if warm_start:
+                check(library().mpc_rollout_batch_device_warm_model(*head, opts, *tail), "mpc_rollout_batch_device_warm_model")
+                return res
             check(library().mpc_rollout_batch_device_model(
                 self._h, B, B, int(steps), state.data_ptr(), coeffs.data_ptr(), yaw_lo.data_ptr(), yaw_hi.data_ptr(),
                 weights.data_ptr() if weights is not None else None, model.data_ptr(), res["hist"].data_ptr() if want_hist else None,
@@ -326,9 +337,11 @@ class BatchedMPC:
         check(fn(self._h, B, B, p(state), p(coeffs), p(yaw_lo), p(yaw_hi), p(weights), p(out), p(traj), p(status), p(iters)), "mpc_solve_batch_host")
         return {"out": out, "status": status, "iters": iters, "traj": traj}
 
-    def solve_numpy_warm(self, state, coeffs, yaw_lo, yaw_hi, warm=None, warm_status=None, weights=None, want_traj=False, warm_opts=None):
+    def solve_numpy_warm(self, state, coeffs, yaw_lo, yaw_hi, warm=None, warm_status=None, weights=None, want_traj=False, warm_opts=None,
+                         model=None):
         """Host arrays through mpc_solve_batch_host_warm (fp64 handles): like solve_numpy, with "warm" [warm_rows(), B] in the
-        result; ``warm`` / ``warm_status``: that array and the status of an earlier call."""
+        result; ``warm`` / ``warm_status``: that array and the status of an earlier call.  ``model`` [6, B]: as in solve_numpy
+        (mpc_solve_batch_host_warm_model)."""
         f = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64))
         state, coeffs, yaw_lo, yaw_hi = f(state), f(coeffs), f(yaw_lo), f(yaw_hi)
         B = state.shape[1]
@@ -344,9 +357,14 @@ class BatchedMPC:
         traj = np.empty((2 * self.N, B)) if want_traj else None
         wout = np.empty((rows, B))
         p = lambda a: a.ctypes.data if a is not None else None
-        check(library().mpc_solve_batch_host_warm(self._h, B, B, p(state), p(coeffs), p(yaw_lo), p(yaw_hi), p(weights), p(warm), p(warm_status),
-                                                  p(wout), B, C.byref(warm_opts) if warm_opts is not None else None, p(out), p(traj),
-                                                  p(status), p(iters)), "mpc_solve_batch_host_warm")
+        head = (self._h, B, B, p(state), p(coeffs), p(yaw_lo), p(yaw_hi), p(weights))
+        tail = (p(warm), p(warm_status), p(wout), B, C.byref(warm_opts) if warm_opts is not None else None, p(out), p(traj), p(status), p(iters))
+        if model is not None:
+            model = f(model)
+            assert model.shape == (_abi.NMODEL, B)
+            check(library().mpc_solve_batch_host_warm_model(*head, p(model), *tail), "mpc_solve_batch_host_warm_model")
+        else:
+            check(library().mpc_solve_batch_host_warm(*head, *tail), "mpc_solve_batch_host_warm")
         return {"out": out, "status": status, "iters": iters, "traj": traj, "warm": wout}
 
     # -- deferred tails (MpcParams.tail_cut > 0, include/mpc_amd.h) -------------

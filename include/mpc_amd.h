@@ -452,7 +452,8 @@ int mpc_telemetry_batch_host_warm(MpcHandle *h, int64_t B, int64_t ld, int npts,
  *   in MpcParams), max_acceleration <= 0 or max_deceleration >= 0 (the start point a = 0 must lie inside the box) -- ends that
  *   instance with MPC_STATUS_INFEASIBLE and the start point in `out`, as an infeasible start does, with no not-a-number; the
  *   batch goes on.  A state with |v| beyond the instance's own relaxed speed limit is MPC_STATUS_INFEASIBLE as ever.
- * The rollout is the stepwise cold loop of mpc_rollout_batch_device with `model` passed to every step.  The run() / telemetry
+ * The rollout is the stepwise cold loop of mpc_rollout_batch_device with `model` passed to every step (warm and in one launch:
+ * the next section).  The run() / telemetry
  * entry points read Lf and the limits of their pre- and post-processing from the handle and have no such form. */
 int mpc_solve_batch_device_model(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
                                  const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
@@ -463,6 +464,53 @@ int mpc_solve_batch_host_model(MpcHandle *h, int64_t B, int64_t ld, const double
 int mpc_rollout_batch_device_model(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
                                    const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
                                    double *hist, int32_t *status, int32_t *iters, void *stream);
+/* ---- warm start and the one-launch rollout with per-instance model values ----------------------------------------------------
+ * Each entry point is the one of the same name without `_model` plus `model` directly behind `weights`, [MPC_NMODEL][ld] addressed
+ * like `weights`, exactly as in mpc_solve_batch_device_model.
+ * model == NULL: the call IS the entry point without `_model`, bitwise, with every convention that one has (the wave path and its
+ *   refusals included).
+ * model != NULL, what a call solves with: every convention of the warm entry points holds -- only columns whose warm_status is
+ *   MPC_STATUS_SUCCESS start warm; a refused record, or a warm attempt that does not end in SUCCESS, is followed by the complete cold
+ *   solve and `iters` adds both up; warm_in = NULL is a cold call that writes warm_out, bitwise mpc_solve_batch_device_model; warm_in
+ *   may be warm_out and warm_status may be status -- and so does every convention of the model entry points: the six values of
+ *   instance i come from its column, everything else from the handle, and an unusable column ends MPC_STATUS_INFEASIBLE with finite
+ *   outputs and a finite record in warm_out.
+ * model != NULL, the box a record is checked against: the instance's own relaxed box, the one the solve itself uses (relaxed limits
+ *   of ITS max_speed, max_steering, max_acceleration, max_deceleration).  A record may therefore have been written under another
+ *   column than the one it is handed to: if it still fits it starts warm, if it does not (a delta beyond a narrowed max_steering)
+ *   the instance starts cold and is bitwise the cold model solve, iterations included.  shift = 1 moves a record by one stage, which
+ *   is that instance's own dt.
+ * Dispatch: a warm model call is always ONE launch of the single-phase fp64 lane kernel, at every B -- no wave path, no deferred
+ *   tails, no pass cuts, no take order, as for a model call; lane compaction applies as for a warm call and changes no result.
+ * Accepted handles: the model rule.  Every fp64 handle, also one whose ordinary solve starts in fp32 (f64_f32_start = 1, or AUTO
+ *   at N >= 15): it is served on its fp64 workspace, nothing is allocated for that, and the results are bitwise those of a handle
+ *   created with f64_f32_start = 0.  (The warm entry points without `_model` refuse such a handle because their solve would be the
+ *   two-launch one; here it never is, so nothing is silently cold.)
+ * Refusals: an MPC_PRECISION_F32 handle gets MPC_ERR_INVALID with the model message; max_soc > 0 together with a warm start gets
+ *   MPC_ERR_UNSUPPORTED, as for every warm call.
+ * mpc_rollout_batch_device_warm_model: the stepwise loop of mpc_rollout_batch_device_warm with `model` passed to every step.
+ * mpc_rollout_batch_device_fused_model: writes bitwise what mpc_rollout_batch_device_model writes (warm_start = 0) or what
+ *   mpc_rollout_batch_device_warm_model writes (warm_start = 1), into state, hist, status and iters.  The stepwise model loop
+ *   launches the lane kernel at every B, so the one launch runs at every B >= 1 on every fp64 handle with max_soc = 0; a cold call
+ *   with max_soc > 0 runs the stepwise loop itself.  mpc_rollout_fused_info counts both kinds, as for the call without `_model`.
+ *   A car whose step ends MPC_STATUS_INFEASIBLE (an unusable column, a speed beyond its own limit) behaves as in the stepwise
+ *   loop: the start point is that step's "solution", the next state is taken from it, and the next step starts cold. */
+int mpc_solve_batch_device_warm_model(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
+                                      const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
+                                      const double *warm_in, const int32_t *warm_status, double *warm_out, int64_t ld_warm,
+                                      const MpcWarmOpts *opts, double *out, double *traj, int32_t *status, int32_t *iters,
+                                      void *stream);
+int mpc_solve_batch_host_warm_model(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
+                                    const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
+                                    const double *warm_in, const int32_t *warm_status, double *warm_out, int64_t ld_warm,
+                                    const MpcWarmOpts *opts, double *out, double *traj, int32_t *status, int32_t *iters);
+int mpc_rollout_batch_device_warm_model(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
+                                        const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
+                                        const MpcWarmOpts *opts, double *hist, int32_t *status, int32_t *iters, void *stream);
+int mpc_rollout_batch_device_fused_model(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
+                                         const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
+                                         int warm_start, const MpcWarmOpts *opts, double *hist, int32_t *status, int32_t *iters,
+                                         void *stream);
 /* ---- the wire side of the handler (src/mpc_main.cpp:26-36, 81-222, DATA.md:5-16) --------
  * Everything between the bytes of a simulator frame and the bytes of the reply; the WebSocket server itself is out of
  * scope.  See csrc/mpc_wire.cpp. */
