@@ -95,7 +95,10 @@ EXPORTS = ["mpc_params_default", "mpc_params_load_json", "mpc_create", "mpc_set_
            "mpc_rollout_batch_device_fused", "mpc_rollout_fused_info",
            "mpc_solve_batch_device_model", "mpc_solve_batch_host_model", "mpc_rollout_batch_device_model",
            "mpc_solve_batch_device_warm_model", "mpc_solve_batch_host_warm_model", "mpc_rollout_batch_device_warm_model",
-           "mpc_rollout_batch_device_fused_model"]
+           "mpc_rollout_batch_device_fused_model",
+           "mpc_run_batch_device_model", "mpc_run_batch_host_model", "mpc_telemetry_batch_device_model", "mpc_telemetry_batch_host_model",
+           "mpc_run_batch_device_warm_model", "mpc_run_batch_host_warm_model", "mpc_telemetry_batch_device_warm_model",
+           "mpc_telemetry_batch_host_warm_model", "mpc_wire_telemetry_batch_host_model", "mpc_wire_telemetry_batch_host_warm_model"]
 
 _lib = None
 
@@ -198,6 +201,18 @@ def library():
                                                   [C.c_void_p])
     L.mpc_telemetry_batch_host_warm.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, DP, C.c_double] + [DP] * 2 + WARM + [DP] * 2
     L.mpc_wire_telemetry_batch_host_warm.argtypes = [C.c_void_p, C.c_int64, C.POINTER(MpcWireTelemetry), DP, C.c_double] + WARM + [DP, DP]
+    # the run() path with per-instance model values: `model` directly behind ptsy (wire forms: behind extra_latency)
+    L.mpc_run_batch_device_model.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 9 + [C.c_void_p]
+    L.mpc_run_batch_host_model.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 9
+    L.mpc_telemetry_batch_device_model.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, DP, C.c_double] + [DP] * 6 + [C.c_void_p]
+    L.mpc_telemetry_batch_host_model.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, DP, C.c_double] + [DP] * 5
+    L.mpc_run_batch_device_warm_model.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 4 + WARM + [DP] * 5 + [C.c_void_p]
+    L.mpc_run_batch_host_warm_model.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 4 + WARM + [DP] * 5
+    L.mpc_telemetry_batch_device_warm_model.argtypes = ([C.c_void_p, C.c_int64, C.c_int64, C.c_int, DP, C.c_double] + [DP] * 3 + WARM + [DP] * 3 +
+                                                        [C.c_void_p])
+    L.mpc_telemetry_batch_host_warm_model.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, DP, C.c_double] + [DP] * 3 + WARM + [DP] * 2
+    L.mpc_wire_telemetry_batch_host_model.argtypes = [C.c_void_p, C.c_int64, C.POINTER(MpcWireTelemetry), DP, C.c_double, DP, DP, DP]
+    L.mpc_wire_telemetry_batch_host_warm_model.argtypes = [C.c_void_p, C.c_int64, C.POINTER(MpcWireTelemetry), DP, C.c_double, DP] + WARM + [DP, DP]
     L.mpc_wire_parse.argtypes = [C.c_char_p, C.c_int64, C.POINTER(MpcWireTelemetry)]
     L.mpc_wire_format_steer.argtypes = [C.c_double, C.c_double, C.c_char_p, C.c_int64]
     L.mpc_wire_format_steer.restype = C.c_int64

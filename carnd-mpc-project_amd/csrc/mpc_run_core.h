@@ -13,6 +13,8 @@
 #ifndef MPC_RUN_CORE_H
 #define MPC_RUN_CORE_H
 
+#include <type_traits>
+
 #include "mpc_core.h"
 
 namespace mpc {
@@ -101,9 +103,25 @@ struct RunPre {
   int ncoef;
 };
 
+/* Where the functions below read the six model values (dt, Lf and the four limits; only Lf and the limits occur here): `m`, a
+ * template argument like Solver::setup_vals' -- the handle's MpcParams itself for the entry points without per-instance values
+ * (their kernels pass P twice and each field is read from P where it is used, so they are instruction for instruction what they
+ * were; the signatures without `m` are the same call for host code) or an instance's mpc::ModelVals (the mpc_run_*_model / mpc_telemetry_*_model entry points; a column that
+ * ModelVals::column refuses has become the handle's values there).  Everything else -- the tables, max_fit_*, latency_ms,
+ * lookahead, steer_adj_*, the weights -- is the handle's on every path. */
+/* (MV = MpcParams: the values are read through P itself -- a second reference to the same parameter block moved a scalar load in
+ * mpc_run_pre_kernel) */
+template <class MV>
+MPC_HD const MV &run_model_of(const MpcParams &P, const MV &m) {
+  if constexpr (std::is_same<MV, MpcParams>::value) return P;
+  else return m;
+}
+
 /* The pre-solve half of MPC::run.  pose = {x, y, psi, v, steering, acceleration}; px/py hold the n global
  * waypoints on entry and the vehicle-frame waypoints on return (the reference transforms them in place). */
-MPC_HD void run_pre(const MpcParams &P, const double *pose, double *px, double *py, int n, RunPre &R) {
+template <class MV>
+MPC_HD void run_pre(const MpcParams &P, const MV &m_, const double *pose, double *px, double *py, int n, RunPre &R) {
+  const MV &m = run_model_of(P, m_);
   double sn, cs;
   fsincos(pose[2], &sn, &cs);
   MPC_UNROLL
@@ -147,28 +165,36 @@ MPC_HD void run_pre(const MpcParams &P, const double *pose, double *px, double *
   const double dir = back - 0.0;                                                  /* computeOrientationChange(0, back) */
   R.max_yaw_change = (road_orientation(c, back, dir) - road_orientation(c, 0.0, dir)) * (back - front) / back;   /* :339 */
   const double max_speed = table_lookup(P.yaw_changes, P.n_yaw_changes, P.yaw_change_speeds, P.n_yaw_change_speeds,
-                                        R.max_yaw_change, P.max_speed);           /* :340 */
+                                        R.max_yaw_change, m.max_speed);           /* :340 */
   R.target_speed = table_lookup(P.steers, P.n_steers, P.steer_speeds, P.n_steer_speeds, pose[4], max_speed);   /* :342 */
   if (R.max_yaw_change < 0.0) { R.yaw_lo = R.max_yaw_change; R.yaw_hi = 0.1; }   /* :345-352 */
   else { R.yaw_lo = -0.1; R.yaw_hi = R.max_yaw_change; }
   R.state[0] = 0.0; R.state[1] = 0.0; R.state[2] = 0.0; R.state[3] = pose[3]; R.state[4] = cte; R.state[5] = epsi;   /* :355-356 */
 }
+MPC_HD void run_pre(const MpcParams &P, const double *pose, double *px, double *py, int n, RunPre &R) { run_pre(P, P, pose, px, py, n, R); }
 
 /* The post-solve half (MPC.cpp:360-381): result9 -> {x1,y1,psi1,v1,steer in [-1,1],accel,cte1,epsi1} */
-MPC_HD void run_post(const MpcParams &P, double max_yaw_change, double target_speed, double v0, const double *r9, double *o8) {
+template <class MV>
+MPC_HD void run_post(const MpcParams &P, const MV &m_, double max_yaw_change, double target_speed, double v0, const double *r9, double *o8) {
+  const MV &m = run_model_of(P, m_);
   double steer = r9[6];
   if (fabs(max_yaw_change) > P.steer_adj_thresh) steer += P.steer_adj_ratio * max_yaw_change;
   const double accel = fmin(r9[7], target_speed - v0);
-  double sv = steer / P.max_steering;
+  double sv = steer / m.max_steering;
   sv = sv < -1.0 ? -1.0 : (sv > 1.0 ? 1.0 : sv);
   o8[0] = r9[0]; o8[1] = r9[1]; o8[2] = r9[2]; o8[3] = r9[3]; o8[4] = sv; o8[5] = accel; o8[6] = r9[4]; o8[7] = r9[5];
+}
+MPC_HD void run_post(const MpcParams &P, double max_yaw_change, double target_speed, double v0, const double *r9, double *o8) {
+  run_post(P, P, max_yaw_change, target_speed, v0, r9, o8);
 }
 
 /* ---- N2: the telemetry handler around run(), src/mpc_main.cpp:126-159 and :171-174 ------------------ */
 /* tel = {x, y, psi (rad, any range), speed (mph), steering_angle (simulator sign), previous throttle command};
  * extra = the handler's mean solve time added to Config::lookahead (mpc_main.cpp:158).
  * -> pose {x,y,psi,v,steering,acceleration} after latency compensation (Vehicle::update + Vehicle::move) */
-MPC_HD void telemetry_to_pose(const MpcParams &P, const double *tel, double extra, double *pose) {
+template <class MV>
+MPC_HD void telemetry_to_pose(const MpcParams &P, const MV &m_, const double *tel, double extra, double *pose) {
+  const MV &m = run_model_of(P, m_);
   double psi = tel[2];
   while (psi >= M_PI) psi -= 2.0 * M_PI;                 /* normalizeAngle, mpc_main.cpp:127 */
   while (psi < -M_PI) psi += 2.0 * M_PI;
@@ -183,22 +209,25 @@ MPC_HD void telemetry_to_pose(const MpcParams &P, const double *tel, double extr
     fsincos(psi, &sn, &cs);
     pose[0] = tel[0] + dist * cs;
     pose[1] = tel[1] + dist * sn;
-    pose[2] = psi + steer * dist / P.Lf;                 /* Vehicle::length = Config::Lf, mpc_main.cpp:155 */
+    pose[2] = psi + steer * dist / m.Lf;                 /* Vehicle::length = Config::Lf, mpc_main.cpp:155 */
     pose[3] = v + acc * dtm;                             /* not clamped: Vehicle.cpp:156 is overwritten at :167 */
   }
 }
+MPC_HD void telemetry_to_pose(const MpcParams &P, const double *tel, double extra, double *pose) { telemetry_to_pose(P, P, tel, extra, pose); }
 /* Vehicle::computeThrottle (Vehicle.cpp:81-103) */
-MPC_HD double compute_throttle(const MpcParams &P, double accel, double target) {
-  const double keep = target / P.max_speed;
-  if (accel >= 0.0) return accel < 0.001 ? keep : fmin(1.0, keep + (1.0 - keep) * accel / P.max_acceleration);
+template <class MV>
+MPC_HD double compute_throttle(const MV &m, double accel, double target) {
+  const double keep = target / m.max_speed;
+  if (accel >= 0.0) return accel < 0.001 ? keep : fmin(1.0, keep + (1.0 - keep) * accel / m.max_acceleration);
   if (accel <= -15.0) return -1.0;
   const double base = accel < -10.0 ? 0.95 : (accel < -5.0 ? 0.9 : 0.85);
-  return -base - (1.0 - base) * accel / P.max_deceleration;
+  return -base - (1.0 - base) * accel / m.max_deceleration;
 }
 /* mpc_main.cpp:171-174: run()'s result -> the command sent back to the simulator */
-MPC_HD void command_from_run(const MpcParams &P, const double *o8, double *steer_cmd, double *throttle_cmd) {
+template <class MV>
+MPC_HD void command_from_run(const MV &m, const double *o8, double *steer_cmd, double *throttle_cmd) {
   *steer_cmd = -o8[4];
-  *throttle_cmd = compute_throttle(P, o8[5], o8[3]);
+  *throttle_cmd = compute_throttle(m, o8[5], o8[3]);
 }
 
 }  // namespace mpc

@@ -202,12 +202,13 @@ struct MpcPhaseWarm : MpcPhase {
 };
 
 /* What the MODEL builds of mpc_solve_kernel get on top (the mpc_*_model entry points): the model values of every instance,
- * [MPC_NMODEL][ld] doubles addressed by INSTANCE like the inputs -- a lane reads its instance's six values wherever it runs set-up
+ * [MPC_NMODEL][ld_model] doubles addressed by INSTANCE like the inputs -- a lane reads its instance's six values wherever it runs set-up
  * for it (the take, an instance that lane compaction has moved) and when it writes the instance out, so the column follows the
  * instance from lane to lane.  These builds are launched as one single phase without cuts and deferred tails (a parked or deferred
  * instance would have to carry its column along).  A type of its own: the other builds' kernel arguments are what they were. */
 struct MpcPhaseModel : MpcPhase {
   const double *model;
+  int64_t ld_model;               /* its own leading dimension: run() solves from the handle's rows, the columns stay the caller's */
 };
 
 /* What the ROLL builds of mpc_solve_kernel get on top (mpc_rollout_batch_device_fused): a lane keeps the car it has taken for `steps`
@@ -228,9 +229,10 @@ struct MpcPhaseRoll : MpcPhaseWarm {
  * every other build are what they were. */
 struct MpcPhaseWarmModel : MpcPhaseWarm {
   const double *model;
+  int64_t ld_model;
 };
 struct MpcPhaseRollModel : MpcPhaseRoll {
-  const double *model;
+  const double *model;            /* (leading dimension ld: a rollout has one for all its arrays) */
 };
 
 /* The take-order key of every instance of a launch (csrc/mpc_take_key.h) and the bins' lists: one thread per instance, a wave
@@ -414,7 +416,8 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
             const int64_t l = ldo;
             if constexpr (MODEL) {             /* the car's own limits, from its column */
               const double *mc = T.model + i;
-              const int64_t lm = ld;
+              int64_t lm = ld;
+              if constexpr (!ROLL) lm = T.ld_model;
               S.unpack_model([mc, lm](int q) { return mc[q * lm]; }, [o, l](int q) { return OutRef<RIO, R>{o + q * l}; },
                              [](int) { return OutRef<RIO, R>{nullptr}; }, false, (R)yaw_lo[i], (R)yaw_hi[i]);
             } else S.unpack([o, l](int q) { return OutRef<RIO, R>{o + q * l}; }, [](int) { return OutRef<RIO, R>{nullptr}; }, false, (R)yaw_lo[i], (R)yaw_hi[i]);
@@ -446,7 +449,8 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
           const int64_t l = ldo;
           if constexpr (MODEL) {
             const double *mc = T.model + i;
-            const int64_t lm = ld;
+            int64_t lm = ld;
+            if constexpr (!ROLL) lm = T.ld_model;
             S.unpack_model([mc, lm](int q) { return mc[q * lm]; }, [o, l](int q) { return OutRef<RIO, R>{o + q * l}; },
                            [t, l](int q) { return OutRef<RIO, R>{t + q * l}; }, traj != nullptr, (R)yaw_lo[i], (R)yaw_hi[i]);
           } else {
@@ -513,7 +517,8 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
             int s0;
             if constexpr (MODEL) {
               const double *mc = T.model + i;
-              const int64_t lm = ld;
+              int64_t lm = ld;
+              if constexpr (!ROLL) lm = T.ld_model;
               s0 = S.setup_model([mc, lm](int q) { return mc[q * lm]; }, st, cf, (R)yaw_lo[i], (R)yaw_hi[i], w, (!T.resume || from_scratch) && !warm_cand);
             } else s0 = S.setup(st, cf, (R)yaw_lo[i], (R)yaw_hi[i], w, (!T.resume || from_scratch) && !warm_cand);
             if constexpr (WARM) {
@@ -640,7 +645,8 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
           }
           if constexpr (MODEL) {      /* the instance has changed lanes: its column comes with it */
             const double *mc = T.model + i;
-            const int64_t lm = ld;
+            int64_t lm = ld;
+            if constexpr (!ROLL) lm = T.ld_model;
             (void)S.setup_model([mc, lm](int q) { return mc[q * lm]; }, st, cf, (R)yaw_lo[i], (R)yaw_hi[i], w, false);
           } else (void)S.setup(st, cf, (R)yaw_lo[i], (R)yaw_hi[i], w, false);
           S.unpark([mb, src](int q) -> R { return mb[q * 64 + src]; }, attempt, it_total);
@@ -955,13 +961,22 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_tail_slice_kernel(const MpcPara
  * 3.7 KB per instance at N = 10 in fp64); every lane of the group
  * runs the solver's state machine on them -- the decisions are wave-uniform -- and the sweeps share their work between the
  * lanes (mpc::Solver<WS, R, true>: backward_wave, forward_wave and the wave form of costate_trial in mpc_core.h). */
-template <class R, int LPI, bool SOC = false>
+/* MODEL (the mpc_run_*_model / mpc_telemetry_*_model entry points): one more kernel argument, the instances' columns (WaveModel);
+ * every lane of a group reads the group's column once, Solver::setup_model / unpack_model take the place of setup / unpack, and the
+ * group's first lane writes as before.  The builds without it have the arguments they had (`Model` is empty). */
+struct WaveModel {
+  const double *model;            /* [MPC_NMODEL][ld], addressed by instance */
+  int64_t ld;
+};
+template <class R, int LPI, bool SOC = false, bool MODEL = false, class... Model>
 __global__ __launch_bounds__(kBlock, 1) void mpc_solve_wave_kernel(
     const MpcParams P, const int64_t B, const int64_t ld, const int64_t ldo, const R *__restrict__ state,
     const R *__restrict__ coeffs, const R *__restrict__ yaw_lo, const R *__restrict__ yaw_hi,
     const R *__restrict__ weights, R *__restrict__ out, R *__restrict__ traj,
-    int32_t *__restrict__ status, int32_t *__restrict__ iters) {
+    int32_t *__restrict__ status, int32_t *__restrict__ iters, const Model... model) {
   extern __shared__ double smem[];
+  static_assert(sizeof...(Model) == (MODEL ? 1 : 0), "the MODEL builds take one WaveModel");
+  static_assert(!MODEL || sizeof(R) == 8, "per-instance model values: the fp64 solve only");
   constexpr int G = 64 / LPI;                       /* instances per wavefront: each on LPI neighbouring lanes */
   using WS = std::conditional_t<SOC, mpc::LdsSocWorkspace<R, G>, mpc::LdsWorkspace<R, G>>;
   using SV = mpc::Solver<WS, R, LPI, SOC>;
@@ -982,13 +997,26 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_wave_kernel(
   for (int q = 0; q < MPC_NCOEF; q++) cf[q] = coeffs[q * ld + i];
 #pragma unroll
   for (int q = 0; q < MPC_NW; q++) w[q] = weights ? weights[q * ld + i] : (R)P.weights[q];
-  int r = S.setup(st, cf, yaw_lo[i], yaw_hi[i], w, true);
+  /* (MODEL: the group's column, read once; a column that cannot be used ends INFEASIBLE, mpc::ModelVals::column) */
+  [[maybe_unused]] double mv[MPC_NMODEL];
+  if constexpr (MODEL) {
+    const WaveModel &W = (model, ...);
+#pragma unroll
+    for (int q = 0; q < MPC_NMODEL; q++) mv[q] = W.model[q * W.ld + i];
+  }
+  [[maybe_unused]] const auto col = [&mv](int q) { return mv[q]; };
+  int r;
+  if constexpr (MODEL) r = S.setup_model(col, st, cf, yaw_lo[i], yaw_hi[i], w, true);
+  else r = S.setup(st, cf, yaw_lo[i], yaw_hi[i], w, true);
   if (r == MPC_STATUS_SUCCESS) r = S.solve();
   if (S.wlane == 0) {
     R *o = out + i;
     R *t = traj ? traj + i : nullptr;
     const int64_t l = ldo;
-    S.unpack([o, l](int q) -> R & { return o[q * l]; }, [t, l](int q) -> R & { return t[q * l]; }, traj != nullptr, yaw_lo[i], yaw_hi[i]);
+    const auto fo = [o, l](int q) -> R & { return o[q * l]; };
+    const auto ft = [t, l](int q) -> R & { return t[q * l]; };
+    if constexpr (MODEL) S.unpack_model(col, fo, ft, traj != nullptr, yaw_lo[i], yaw_hi[i]);
+    else S.unpack(fo, ft, traj != nullptr, yaw_lo[i], yaw_hi[i]);
     status[i] = r;
     if (iters) iters[i] = S.iters;
   }
@@ -997,14 +1025,18 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_wave_kernel(
 /* The same with a warm start (the mpc_*_warm entry points; see MpcPhaseWarm for the buffers): a kernel of its own, so that the cold
  * launches are what they were.  Every lane of the group reads the instance's column of warm_in (Solver::solve_warm: the warm
  * attempt, then the complete cold solve if that does not end in SUCCESS); the group's first lane writes warm_out. */
-template <class R, int LPI>
+/* MODEL: as in mpc_solve_wave_kernel.  Solver::warm_point judges the record against the relaxed box that setup_model has just set
+ * from the column -- the instance's own -- and the cold solve behind a refused record starts from the solver's own members. */
+template <class R, int LPI, bool MODEL = false, class... Model>
 __global__ __launch_bounds__(kBlock, 1) void mpc_solve_wave_warm_kernel(
     const MpcParams P, const int64_t B, const int64_t ld, const int64_t ldo, const R *__restrict__ state,
     const R *__restrict__ coeffs, const R *__restrict__ yaw_lo, const R *__restrict__ yaw_hi,
     const R *__restrict__ weights, R *__restrict__ out, R *__restrict__ traj,
     int32_t *status, int32_t *__restrict__ iters, const double *warm_in, const int32_t *warm_status, double *warm_out,
-    const int64_t ld_warm, const MpcWarmOpts wopts, const int psi_box) {
+    const int64_t ld_warm, const MpcWarmOpts wopts, const int psi_box, const Model... model) {
   extern __shared__ double smem[];
+  static_assert(sizeof...(Model) == (MODEL ? 1 : 0), "the MODEL builds take one WaveModel");
+  static_assert(!MODEL || sizeof(R) == 8, "per-instance model values: the fp64 solve only");
   constexpr int G = 64 / LPI;
   using WS = mpc::LdsWorkspace<R, G>;
   using SV = mpc::Solver<WS, R, LPI, false>;
@@ -1024,7 +1056,16 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_wave_warm_kernel(
 #pragma unroll
   for (int q = 0; q < MPC_NW; q++) w[q] = weights ? weights[q * ld + i] : (R)P.weights[q];
   const bool warm = warm_in != nullptr && (warm_status == nullptr || warm_status[i] == MPC_STATUS_SUCCESS);
-  int r = S.setup(st, cf, yaw_lo[i], yaw_hi[i], w, true);
+  [[maybe_unused]] double mv[MPC_NMODEL];
+  if constexpr (MODEL) {
+    const WaveModel &W = (model, ...);
+#pragma unroll
+    for (int q = 0; q < MPC_NMODEL; q++) mv[q] = W.model[q * W.ld + i];
+  }
+  [[maybe_unused]] const auto col = [&mv](int q) { return mv[q]; };
+  int r;
+  if constexpr (MODEL) r = S.setup_model(col, st, cf, yaw_lo[i], yaw_hi[i], w, true);
+  else r = S.setup(st, cf, yaw_lo[i], yaw_hi[i], w, true);
   if (r == MPC_STATUS_SUCCESS) {
     /* (psi_box: the run() path, see mpc::WarmColumn) */
     r = S.solve_warm(warm, mpc::WarmColumn{warm_in + i, ld_warm, psi_box ? (double)yaw_lo[i] : -HUGE_VAL, psi_box ? (double)yaw_hi[i] : HUGE_VAL}, wopts);
@@ -1033,7 +1074,10 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_wave_warm_kernel(
     R *o = out + i;
     R *t = traj ? traj + i : nullptr;
     const int64_t l = ldo;
-    S.unpack([o, l](int q) -> R & { return o[q * l]; }, [t, l](int q) -> R & { return t[q * l]; }, traj != nullptr, yaw_lo[i], yaw_hi[i]);
+    const auto fo = [o, l](int q) -> R & { return o[q * l]; };
+    const auto ft = [t, l](int q) -> R & { return t[q * l]; };
+    if constexpr (MODEL) S.unpack_model(col, fo, ft, traj != nullptr, yaw_lo[i], yaw_hi[i]);
+    else S.unpack(fo, ft, traj != nullptr, yaw_lo[i], yaw_hi[i]);
     if (warm_out) {
       double *wo = warm_out + i;
       S.warm_store([wo, ld_warm](int k, int f, R v) { wo[(int64_t)(k * MPC_WARM_REC + f) * ld_warm] = v; });
@@ -1058,12 +1102,12 @@ __global__ __launch_bounds__(256) void mpc_run_pre_kernel(const MpcParams P, int
     double t6[6];
 #pragma unroll
     for (int q = 0; q < 6; q++) t6[q] = po[q];
-    mpc::telemetry_to_pose(P, t6, extra, po);
+    mpc::telemetry_to_pose(P, P, t6, extra, po);
   }
 #pragma unroll
   for (int q = 0; q < mpc::RUN_MAX_PTS; q++) { px[q] = q < npts ? ptsx[q * ld + i] : 0.0; py[q] = q < npts ? ptsy[q * ld + i] : 0.0; }
   mpc::RunPre R;
-  mpc::run_pre(P, po, px, py, npts, R);
+  mpc::run_pre(P, P, po, px, py, npts, R);
 #pragma unroll
   for (int q = 0; q < mpc::RUN_MAX_PTS; q++) if (q < npts) { ptsx[q * ld + i] = px[q]; ptsy[q * ld + i] = py[q]; }
 #pragma unroll
@@ -1081,7 +1125,7 @@ __global__ __launch_bounds__(256) void mpc_run_post_kernel(const MpcParams P, in
   double r9[9], o8[8];
 #pragma unroll
   for (int q = 0; q < 9; q++) r9[q] = out9[q * ld9 + i];
-  mpc::run_post(P, pre[13 * ldp + i], pre[14 * ldp + i], pre[3 * ldp + i], r9, o8);
+  mpc::run_post(P, P, pre[13 * ldp + i], pre[14 * ldp + i], pre[3 * ldp + i], r9, o8);
   if (out8) {
 #pragma unroll
     for (int q = 0; q < 8; q++) out8[q * ld + i] = o8[q];
@@ -1089,6 +1133,67 @@ __global__ __launch_bounds__(256) void mpc_run_post_kernel(const MpcParams P, in
   if (cmd) {         /* the reply of the telemetry handler (mpc_main.cpp:171-174) */
     double sc, tc;
     mpc::command_from_run(P, o8, &sc, &tc);
+    cmd[i] = sc; cmd[ld + i] = tc;
+  }
+}
+
+/* The same two kernels for instances that bring their own model values (the mpc_run_*_model / mpc_telemetry_*_model entry points):
+ * a lane reads its instance's column of model [MPC_NMODEL][ldm] once and hands it to mpc_run_core.h as mpc::ModelVals -- Lf in the
+ * latency compensation, max_speed as the cap of the speed tables, max_steering in the normalisation, max_speed and the two
+ * acceleration limits in the throttle.  A column that cannot be used: the handle's values (mpc::ModelVals::column); the solve in
+ * between reports the instance INFEASIBLE.  Kernels of their own: the two above have the arguments and the code they had. */
+template <bool TELEMETRY>
+__global__ __launch_bounds__(256) void mpc_run_pre_model_kernel(const MpcParams P, int64_t B, int64_t ld, int npts,
+                                                                const double *__restrict__ pose, double extra, double *__restrict__ ptsx,
+                                                                double *__restrict__ ptsy, double *__restrict__ pre, int64_t ldp,
+                                                                const double *__restrict__ model, int64_t ldm) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B) return;
+  bool ok;
+  const double *mc = model + i;
+  const mpc::ModelVals m = mpc::ModelVals::column(P, [mc, ldm](int q) { return mc[q * ldm]; }, ok);
+  double po[6], px[mpc::RUN_MAX_PTS], py[mpc::RUN_MAX_PTS];
+#pragma unroll
+  for (int q = 0; q < 6; q++) po[q] = pose[q * ld + i];
+  if (TELEMETRY) {
+    double t6[6];
+#pragma unroll
+    for (int q = 0; q < 6; q++) t6[q] = po[q];
+    mpc::telemetry_to_pose(P, m, t6, extra, po);
+  }
+#pragma unroll
+  for (int q = 0; q < mpc::RUN_MAX_PTS; q++) { px[q] = q < npts ? ptsx[q * ld + i] : 0.0; py[q] = q < npts ? ptsy[q * ld + i] : 0.0; }
+  mpc::RunPre R;
+  mpc::run_pre(P, m, po, px, py, npts, R);
+#pragma unroll
+  for (int q = 0; q < mpc::RUN_MAX_PTS; q++) if (q < npts) { ptsx[q * ld + i] = px[q]; ptsy[q * ld + i] = py[q]; }
+#pragma unroll
+  for (int q = 0; q < 6; q++) pre[q * ldp + i] = R.state[q];
+#pragma unroll
+  for (int q = 0; q < 5; q++) pre[(6 + q) * ldp + i] = R.coef[q];
+  pre[11 * ldp + i] = R.yaw_lo; pre[12 * ldp + i] = R.yaw_hi; pre[13 * ldp + i] = R.max_yaw_change; pre[14 * ldp + i] = R.target_speed;
+}
+
+__global__ __launch_bounds__(256) void mpc_run_post_model_kernel(const MpcParams P, int64_t B, const double *__restrict__ pre, int64_t ldp,
+                                                                 const double *__restrict__ out9, int64_t ld9, double *__restrict__ out8,
+                                                                 double *__restrict__ cmd, int64_t ld, const double *__restrict__ model,
+                                                                 int64_t ldm) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B) return;
+  bool ok;
+  const double *mc = model + i;
+  const mpc::ModelVals m = mpc::ModelVals::column(P, [mc, ldm](int q) { return mc[q * ldm]; }, ok);
+  double r9[9], o8[8];
+#pragma unroll
+  for (int q = 0; q < 9; q++) r9[q] = out9[q * ld9 + i];
+  mpc::run_post(P, m, pre[13 * ldp + i], pre[14 * ldp + i], pre[3 * ldp + i], r9, o8);
+  if (out8) {
+#pragma unroll
+    for (int q = 0; q < 8; q++) out8[q * ld + i] = o8[q];
+  }
+  if (cmd) {
+    double sc, tc;
+    mpc::command_from_run(m, o8, &sc, &tc);
     cmd[i] = sc; cmd[ld + i] = tc;
   }
 }
@@ -1947,7 +2052,10 @@ struct SolveIO {
   const R *state, *coeffs, *yaw_lo, *yaw_hi, *weights;
   R *out, *traj;
   int32_t *status, *iters;
-  const double *model = nullptr;   /* a model call (the mpc_*_model entry points, fp64 handles): [MPC_NMODEL][ld], see MpcPhaseModel */
+  const double *model = nullptr;   /* a model call (the mpc_*_model entry points, fp64 handles): [MPC_NMODEL][ld_model], see MpcPhaseModel */
+  int64_t ld_model = 0;            /* (its own: run() solves from the handle's rows at the handle's stride, the columns stay where the caller has them) */
+  bool model_wave = false;         /* a model call of the run() / telemetry entry points: the wave MODEL kernels up to wave_max_batch */
+  void set_model(const double *m, int64_t l, bool wave = false) { model = m; ld_model = l; model_wave = wave; }
 };
 /* ... and what a warm call brings on top: the warm buffers (see MpcPhaseWarm) and the options in effect (warm_check) */
 struct WarmIO {
@@ -2005,7 +2113,7 @@ static int wave_lpi(const MpcHandle *h, int64_t B) {
 }
 
 /* The wave path: 64 / LPI instances per wavefront, each with its stage records in LDS (the SOC build: and its SOC records behind
- * them).  Plain, SOC (fp64, max_soc > 0) or warm (fp64). */
+ * them).  Plain, SOC (fp64, max_soc > 0) or warm (fp64); io.model: the MODEL builds of the three (fp64). */
 template <class R>
 static int launch_wave(MpcHandle *h, const SolveIO<R> &io, hipStream_t s, bool soc, const WarmIO *warm) {
   const size_t per = (size_t)mpc::workspace_fields_per_instance(h->params.N, sizeof(R) == 4, h->params.initial_state_rows != 0) * sizeof(R);
@@ -2013,11 +2121,19 @@ static int launch_wave(MpcHandle *h, const SolveIO<R> &io, hipStream_t s, bool s
     constexpr int LPI = decltype(lpi)::value, G = 64 / LPI;
     const unsigned grid = (unsigned)((io.B + G - 1) / G);
     if constexpr (sizeof(R) == 8) {
+      const size_t per_soc = per + (size_t)mpc::soc_fields_per_instance(h->params.N) * sizeof(R);
+      if (io.model) {
+        const WaveModel wm{io.model, io.ld_model};
+        if (warm)
+          return launch_kernel(mpc_solve_wave_warm_kernel<R, LPI, true, WaveModel>, grid, G * per, s, h, io, warm->warm_in, warm->warm_status,
+                               warm->warm_out, warm->ld_warm, warm->opts, warm->psi_box ? 1 : 0, wm);
+        if (soc) return launch_kernel(mpc_solve_wave_kernel<R, LPI, true, true, WaveModel>, grid, G * per_soc, s, h, io, wm);
+        return launch_kernel(mpc_solve_wave_kernel<R, LPI, false, true, WaveModel>, grid, G * per, s, h, io, wm);
+      }
       if (warm)
         return launch_kernel(mpc_solve_wave_warm_kernel<R, LPI>, grid, G * per, s, h, io, warm->warm_in, warm->warm_status, warm->warm_out,
                              warm->ld_warm, warm->opts, warm->psi_box ? 1 : 0);
-      if (soc)
-        return launch_kernel(mpc_solve_wave_kernel<R, LPI, true>, grid, G * (per + (size_t)mpc::soc_fields_per_instance(h->params.N) * sizeof(R)), s, h, io);
+      if (soc) return launch_kernel(mpc_solve_wave_kernel<R, LPI, true>, grid, G * per_soc, s, h, io);
     }
     return launch_kernel(mpc_solve_wave_kernel<R, LPI>, grid, G * per, s, h, io);
   };
@@ -2052,8 +2168,8 @@ static int launch_lanes(MpcHandle *h, LaneBuild build, const SolveIO<RIO> &io, h
     if constexpr (sizeof(RIO) == 8) {
       if (io.model && warm)
         return go(staging, RIO{}, RIO{}, no, yes, h->ws_stride,
-                  MpcPhaseWarmModel{MpcPhaseWarm{T, warm->warm_in, warm->warm_status, warm->warm_out, warm->ld_warm, warm->opts, warm->psi_box ? 1 : 0}, io.model}, yes);
-      if (io.model) return with_bool(soc, [&](auto soc_build) { return go(staging, RIO{}, RIO{}, soc_build, no, h->ws_stride, MpcPhaseModel{T, io.model}, yes); });
+                  MpcPhaseWarmModel{MpcPhaseWarm{T, warm->warm_in, warm->warm_status, warm->warm_out, warm->ld_warm, warm->opts, warm->psi_box ? 1 : 0}, io.model, io.ld_model}, yes);
+      if (io.model) return with_bool(soc, [&](auto soc_build) { return go(staging, RIO{}, RIO{}, soc_build, no, h->ws_stride, MpcPhaseModel{T, io.model, io.ld_model}, yes); });
       if (warm) return go(staging, RIO{}, RIO{}, no, yes, h->ws_stride, MpcPhaseWarm{T, warm->warm_in, warm->warm_status, warm->warm_out, warm->ld_warm, warm->opts, warm->psi_box ? 1 : 0}, no);
       if (soc) return go(staging, RIO{}, RIO{}, yes, no, h->ws_stride, T, no);
     }
@@ -2190,7 +2306,9 @@ static int solve_end(MpcHandle *h, const SolveIO<R> &io, hipStream_t s, MpcHandl
  * call.model: a model call (model_check has passed: an fp64 handle) -- ONE launch of the MODEL build of the single-phase fp64 lane
  * kernel on h->ws at every B, also on a handle whose ordinary solve starts in fp32 (on an fp64 handle h->ws has the fp64 layout):
  * no wave path, no mixed-precision launch, and it never defers, cuts or orders either.  warm and call.model together (warm_model_check
- * has passed: an fp64 handle, no SOC): the same one launch, of the WARM+MODEL build -- lane compaction included, as for a warm call. */
+ * has passed: an fp64 handle, no SOC): the same one launch, of the WARM+MODEL build -- lane compaction included, as for a warm call.
+ * call.model_wave (the run() / telemetry model entry points, where the small batch is the rule): up to wave_max_batch the one launch
+ * is the wave kernel's MODEL build instead -- cold, SOC or warm, launch_wave's own choice of lanes per instance and LDS. */
 template <class R>
 static int launch_solve(MpcHandle *h, const SolveIO<R> &call, void *stream_, bool with_stats = true, bool may_defer = false,
                         bool may_order = false, const WarmIO *warm = nullptr) {
@@ -2207,7 +2325,7 @@ static int launch_solve(MpcHandle *h, const SolveIO<R> &call, void *stream_, boo
   /* MpcParams.max_soc > 0 on an fp64 handle: the SOC builds of the kernels (the mixed-precision launch decides for its fp64 phase
    * itself) */
   const bool soc = sizeof(R) == 8 && h->params.max_soc > 0;
-  const bool wave_path = !model && h->wave_max_batch > 0 && B <= h->wave_max_batch;      /* (comes first: set_wave_limit decides which handles have it) */
+  const bool wave_path = (!model || io.model_wave) && h->wave_max_batch > 0 && B <= h->wave_max_batch;      /* (comes first: set_wave_limit decides which handles have it) */
   TailPlace tp;
   tp.defer = may_defer && h->params.tail_cut != 0 && B >= kTailMinBatch && !wave_path;
   if (tp.defer) MPC_TRY(tail_claim(h, s, tp));
@@ -2287,7 +2405,7 @@ extern "C" int mpc_solve_batch_device_model(MpcHandle *h, int64_t B, int64_t ld,
   if (!model) return mpc_solve_batch_device(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters, stream_);
   MPC_TRY(model_check(h));
   SolveIO<double> io{B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters};
-  io.model = model;
+  io.set_model(model, ld);
   return launch_solve<double>(h, io, stream_, true, false, false);
 }
 
@@ -2356,7 +2474,7 @@ extern "C" int mpc_solve_batch_device_warm_model(MpcHandle *h, int64_t B, int64_
   WarmIO warm{warm_in, warm_status, warm_out, ld_warm, {}};
   MPC_TRY(warm_model_check(h, opts, &warm.opts));
   SolveIO<double> io{B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters};
-  io.model = model;
+  io.set_model(model, ld);
   return launch_solve<double>(h, io, stream_, true, false, false, &warm);
 }
 
@@ -2370,10 +2488,12 @@ extern "C" int mpc_solve_batch_device_f32(MpcHandle *h, int64_t B, int64_t ld, c
 
 /* run() for a batch; `tel` selects the telemetry rows as input (with latency compensation) and `cmd` the reply.  warm: a warm call
  * (warm_check has passed) -- the same three kernels, the solve started from the previous call's records with their psi projected
- * into the box run_pre derives for this call (mpc::WarmColumn). */
+ * into the box run_pre derives for this call (mpc::WarmColumn).  model (device, [MPC_NMODEL][ld]; model_check has passed): the MODEL
+ * forms of the pre and post kernels, and a model solve between them that reads its inputs from the handle's rows at the handle's
+ * stride and the columns from the caller's array at the caller's ld (SolveIO::ld_model) -- the array is not copied. */
 static int run_impl(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, bool tel, double extra, double *ptsx,
                     double *ptsy, double *out8, double *cmd, double *traj, int32_t *status, int32_t *iters, double *pre,
-                    void *stream_, const WarmIO *warm = nullptr) {
+                    void *stream_, const WarmIO *warm = nullptr, const double *model = nullptr) {
   MPC_TRY(check_batch(h, B, ld));
   if (warm && (warm->warm_in || warm->warm_out) && warm->ld_warm < B) { g_last_error = "ld_warm < B"; return MPC_ERR_INVALID; }
   if (npts < 3 || npts > mpc::RUN_MAX_PTS) { g_last_error = "npts must be 3..8"; return MPC_ERR_INVALID; }
@@ -2390,12 +2510,16 @@ static int run_impl(MpcHandle *h, int64_t B, int64_t ld, int npts, const double 
   hipStream_t s = (hipStream_t)stream_;
   double *d_pre = h->d_run;
   const unsigned grid = (unsigned)((B + 255) / 256);
-  if (tel) hipLaunchKernelGGL(mpc_run_pre_kernel<true>, dim3(grid), dim3(256), 0, s, h->params, B, ld, npts, pose, extra, ptsx, ptsy, d_pre, S);
+  if (model && tel) hipLaunchKernelGGL(mpc_run_pre_model_kernel<true>, dim3(grid), dim3(256), 0, s, h->params, B, ld, npts, pose, extra, ptsx, ptsy, d_pre, S, model, ld);
+  else if (model) hipLaunchKernelGGL(mpc_run_pre_model_kernel<false>, dim3(grid), dim3(256), 0, s, h->params, B, ld, npts, pose, 0.0, ptsx, ptsy, d_pre, S, model, ld);
+  else if (tel) hipLaunchKernelGGL(mpc_run_pre_kernel<true>, dim3(grid), dim3(256), 0, s, h->params, B, ld, npts, pose, extra, ptsx, ptsy, d_pre, S);
   else hipLaunchKernelGGL(mpc_run_pre_kernel<false>, dim3(grid), dim3(256), 0, s, h->params, B, ld, npts, pose, 0.0, ptsx, ptsy, d_pre, S);
   MPC_HIP_CHECK(hipGetLastError());
-  MPC_TRY(launch_solve<double>(h, {B, S, ld, d_pre, d_pre + 6 * S, d_pre + 11 * S, d_pre + 12 * S, nullptr, h->d_run9, traj, status, iters}, stream_, true, false,
-                               false, warm));
-  hipLaunchKernelGGL(mpc_run_post_kernel, dim3(grid), dim3(256), 0, s, h->params, B, d_pre, S, h->d_run9, ld, out8, cmd, ld);
+  SolveIO<double> io{B, S, ld, d_pre, d_pre + 6 * S, d_pre + 11 * S, d_pre + 12 * S, nullptr, h->d_run9, traj, status, iters};
+  if (model) io.set_model(model, ld, true);
+  MPC_TRY(launch_solve<double>(h, io, stream_, true, false, false, warm));
+  if (model) hipLaunchKernelGGL(mpc_run_post_model_kernel, dim3(grid), dim3(256), 0, s, h->params, B, d_pre, S, h->d_run9, ld, out8, cmd, ld, model, ld);
+  else hipLaunchKernelGGL(mpc_run_post_kernel, dim3(grid), dim3(256), 0, s, h->params, B, d_pre, S, h->d_run9, ld, out8, cmd, ld);
   MPC_HIP_CHECK(hipGetLastError());
   if (pre) MPC_HIP_CHECK(hipMemcpy2DAsync(pre, sizeof(double) * ld, d_pre, sizeof(double) * S, sizeof(double) * B, 15, hipMemcpyDeviceToDevice, s));
   return MPC_OK;
@@ -2441,6 +2565,52 @@ extern "C" int mpc_telemetry_batch_device_warm(MpcHandle *h, int64_t B, int64_t 
   return run_impl(h, B, ld, npts, tel, true, extra_latency, ptsx, ptsy, out8, cmd, nullptr, status, nullptr, nullptr, stream_, &warm);
 }
 
+/* ... and with per-instance model values (include/mpc_amd.h, "per-instance model values on the run() path"); model == NULL: the
+ * entry point without _model.  The handles: model_check / warm_model_check, as for the mpc_solve_*_model entry points. */
+extern "C" int mpc_run_batch_device_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx, double *ptsy,
+                                          const double *model, double *out8, double *traj, int32_t *status, int32_t *iters, double *pre,
+                                          void *stream_) {
+  if (!model) return mpc_run_batch_device(h, B, ld, npts, pose, ptsx, ptsy, out8, traj, status, iters, pre, stream_);
+  MPC_TRY(model_check(h));
+  if (B > 0 && !out8) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
+  return run_impl(h, B, ld, npts, pose, false, 0.0, ptsx, ptsy, out8, nullptr, traj, status, iters, pre, stream_, nullptr, model);
+}
+
+extern "C" int mpc_telemetry_batch_device_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
+                                                double *ptsx, double *ptsy, const double *model, double *cmd, double *out8, int32_t *status,
+                                                void *stream_) {
+  if (!model) return mpc_telemetry_batch_device(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, cmd, out8, status, stream_);
+  MPC_TRY(model_check(h));
+  if (B > 0 && !cmd) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
+  return run_impl(h, B, ld, npts, tel, true, extra_latency, ptsx, ptsy, out8, cmd, nullptr, status, nullptr, nullptr, stream_, nullptr, model);
+}
+
+extern "C" int mpc_run_batch_device_warm_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx,
+                                               double *ptsy, const double *model, const double *warm_in, const int32_t *warm_status,
+                                               double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts, double *out8, double *traj,
+                                               int32_t *status, int32_t *iters, double *pre, void *stream_) {
+  if (!model)
+    return mpc_run_batch_device_warm(h, B, ld, npts, pose, ptsx, ptsy, warm_in, warm_status, warm_out, ld_warm, opts, out8, traj, status, iters, pre,
+                                     stream_);
+  WarmIO warm = run_warm_io(warm_in, warm_status, warm_out, ld_warm);
+  MPC_TRY(warm_model_check(h, opts, &warm.opts));
+  if (B > 0 && !out8) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
+  return run_impl(h, B, ld, npts, pose, false, 0.0, ptsx, ptsy, out8, nullptr, traj, status, iters, pre, stream_, &warm, model);
+}
+
+extern "C" int mpc_telemetry_batch_device_warm_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
+                                                     double *ptsx, double *ptsy, const double *model, const double *warm_in,
+                                                     const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts,
+                                                     double *cmd, double *out8, int32_t *status, void *stream_) {
+  if (!model)
+    return mpc_telemetry_batch_device_warm(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, warm_in, warm_status, warm_out, ld_warm, opts, cmd, out8,
+                                           status, stream_);
+  WarmIO warm = run_warm_io(warm_in, warm_status, warm_out, ld_warm);
+  MPC_TRY(warm_model_check(h, opts, &warm.opts));
+  if (B > 0 && !cmd) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
+  return run_impl(h, B, ld, npts, tel, true, extra_latency, ptsx, ptsy, out8, cmd, nullptr, status, nullptr, nullptr, stream_, &warm, model);
+}
+
 /* The host arrays of a warm call (`hw`) on the device: the warm buffer goes through a device block of its own, rows of the handle's
  * stride, read and written in place, with the status it came with beside it.  *dw: what the launch gets. */
 static int warm_host_in(MpcHandle *h, int64_t B, const WarmIO &hw, hipStream_t s, WarmIO *dw) {
@@ -2473,26 +2643,28 @@ extern "C" void mpc_internal_set_error(const char *msg) { g_last_error = msg ? m
 
 /* The telemetry handler for host arrays: one copy in, the kernels, one copy out, on the handle's own device and stream
  * (whatever the caller's current device is), staging kept on the handle.  rows of `tel`, `ptsx`, `ptsy` as in
- * mpc_telemetry_batch_device with leading dimension ld; the waypoint arrays are inputs only here. */
+ * mpc_telemetry_batch_device with leading dimension ld; the waypoint arrays are inputs only here.  model (host, [MPC_NMODEL][ld];
+ * model_check has passed): six more rows of the staging block, copied in with the other inputs. */
 static int telemetry_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency, const double *ptsx,
-                          const double *ptsy, double *cmd, int32_t *status, const WarmIO *warm) {
+                          const double *ptsy, double *cmd, int32_t *status, const WarmIO *warm, const double *model = nullptr) {
   MPC_TRY(check_batch(h, B, ld));
   if (npts < 3 || npts > mpc::RUN_MAX_PTS) { g_last_error = "npts must be 3..8"; return MPC_ERR_INVALID; }
   if (B == 0) { h->last_B = 0; return MPC_OK; }
   if (!tel || !ptsx || !ptsy || !cmd || !status) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
   MPC_ON_DEVICE(h);
-  const int64_t rows = 6 + 2 * npts, L = (B + 7) / 8 * 8;
-  MPC_TRY(grow_dev(&h->d_tel, &h->tel_bytes, sizeof(double) * (size_t)((rows + 2) * L) + sizeof(int32_t) * (size_t)L));
-  double *d = h->d_tel, *d_cmd = d + rows * L;
-  int32_t *d_st = (int32_t *)(d_cmd + 2 * L);
+  const int64_t rows = 6 + 2 * npts, L = (B + 7) / 8 * 8, model_rows = model ? MPC_NMODEL : 0;
+  MPC_TRY(grow_dev(&h->d_tel, &h->tel_bytes, sizeof(double) * (size_t)((rows + 2 + model_rows) * L) + sizeof(int32_t) * (size_t)L));
+  double *d = h->d_tel, *d_cmd = d + rows * L, *d_model = d_cmd + 2 * L;
+  int32_t *d_st = (int32_t *)(d_model + model_rows * L);
   hipStream_t s = h->stream;
   MPC_HIP_CHECK(hipMemcpy2DAsync(d, sizeof(double) * L, tel, sizeof(double) * ld, sizeof(double) * B, 6, hipMemcpyHostToDevice, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(d + 6 * L, sizeof(double) * L, ptsx, sizeof(double) * ld, sizeof(double) * B, npts, hipMemcpyHostToDevice, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(d + (6 + npts) * L, sizeof(double) * L, ptsy, sizeof(double) * ld, sizeof(double) * B, npts, hipMemcpyHostToDevice, s));
+  if (model) MPC_HIP_CHECK(hipMemcpy2DAsync(d_model, sizeof(double) * L, model, sizeof(double) * ld, sizeof(double) * B, MPC_NMODEL, hipMemcpyHostToDevice, s));
   WarmIO dw{};
   if (warm) MPC_TRY(warm_host_in(h, B, *warm, s, &dw));
   MPC_TRY(run_impl(h, B, L, npts, d, true, extra_latency, d + 6 * L, d + (6 + npts) * L, nullptr, d_cmd, nullptr, d_st, nullptr, nullptr, (void *)s,
-                   warm ? &dw : nullptr));
+                   warm ? &dw : nullptr, model ? d_model : nullptr));
   if (warm) MPC_TRY(warm_host_out(h, B, *warm, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(cmd, sizeof(double) * ld, d_cmd, sizeof(double) * L, sizeof(double) * B, 2, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipMemcpyAsync(status, d_st, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
@@ -2513,11 +2685,29 @@ extern "C" int mpc_telemetry_batch_host_warm(MpcHandle *h, int64_t B, int64_t ld
   return telemetry_host(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, cmd, status, &hw);
 }
 
+extern "C" int mpc_telemetry_batch_host_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
+                                              const double *ptsx, const double *ptsy, const double *model, double *cmd, int32_t *status) {
+  if (!model) return mpc_telemetry_batch_host(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, cmd, status);
+  MPC_TRY(model_check(h));
+  return telemetry_host(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, cmd, status, nullptr, model);
+}
+
+extern "C" int mpc_telemetry_batch_host_warm_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
+                                                   const double *ptsx, const double *ptsy, const double *model, const double *warm_in,
+                                                   const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts,
+                                                   double *cmd, int32_t *status) {
+  if (!model)
+    return mpc_telemetry_batch_host_warm(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, warm_in, warm_status, warm_out, ld_warm, opts, cmd, status);
+  WarmIO hw = run_warm_io(warm_in, warm_status, warm_out, ld_warm);
+  MPC_TRY(warm_model_check(h, opts, &hw.opts));
+  return telemetry_host(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, cmd, status, &hw, model);
+}
+
 /* MPC::run() for host arrays (the drop-in's B = 1 case, include/mpc_drop_in.hpp): one copy in, the three kernels of
  * mpc_run_batch_device on the handle's own device and stream, one copy out; synchronises.  ptsx / ptsy are transformed in place
- * like the reference does (MPC.cpp:329; mpc_main.cpp:189-190 relies on it). */
+ * like the reference does (MPC.cpp:329; mpc_main.cpp:189-190 relies on it).  model: as in telemetry_host. */
 static int run_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx, double *ptsy, double *out8,
-                    double *traj, int32_t *status, int32_t *iters, double *pre, const WarmIO *warm) {
+                    double *traj, int32_t *status, int32_t *iters, double *pre, const WarmIO *warm, const double *model = nullptr) {
   MPC_TRY(check_batch(h, B, ld));
   if (npts < 3 || npts > mpc::RUN_MAX_PTS) { g_last_error = "npts must be 3..8"; return MPC_ERR_INVALID; }
   if (h->params.precision != MPC_PRECISION_F64) { g_last_error = "run() entry points are fp64 only"; return MPC_ERR_INVALID; }
@@ -2526,17 +2716,20 @@ static int run_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const double 
   MPC_ON_DEVICE(h);
   const int N = h->params.N;
   const int64_t L = (B + 7) / 8 * 8;
-  const int64_t in_rows = 6 + 2 * npts, out_rows = 8 + 2 * N + 15;
-  MPC_TRY(grow_dev(&h->d_tel, &h->tel_bytes, sizeof(double) * (size_t)((in_rows + out_rows) * L) + sizeof(int32_t) * (size_t)(2 * L)));
+  const int64_t in_rows = 6 + 2 * npts, out_rows = 8 + 2 * N + 15, model_rows = model ? MPC_NMODEL : 0;
+  MPC_TRY(grow_dev(&h->d_tel, &h->tel_bytes, sizeof(double) * (size_t)((in_rows + out_rows + model_rows) * L) + sizeof(int32_t) * (size_t)(2 * L)));
   double *d = h->d_tel, *d_px = d + 6 * L, *d_py = d_px + (int64_t)npts * L, *d_o8 = d + in_rows * L, *d_tr = d_o8 + 8 * L, *d_pre = d_tr + 2 * (int64_t)N * L;
-  int32_t *d_st = (int32_t *)(d_pre + 15 * L), *d_it = d_st + L;
+  double *d_model = d_pre + 15 * L;
+  int32_t *d_st = (int32_t *)(d_model + model_rows * L), *d_it = d_st + L;
   hipStream_t s = h->stream;
   MPC_HIP_CHECK(hipMemcpy2DAsync(d, sizeof(double) * L, pose, sizeof(double) * ld, sizeof(double) * B, 6, hipMemcpyHostToDevice, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(d_px, sizeof(double) * L, ptsx, sizeof(double) * ld, sizeof(double) * B, npts, hipMemcpyHostToDevice, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(d_py, sizeof(double) * L, ptsy, sizeof(double) * ld, sizeof(double) * B, npts, hipMemcpyHostToDevice, s));
+  if (model) MPC_HIP_CHECK(hipMemcpy2DAsync(d_model, sizeof(double) * L, model, sizeof(double) * ld, sizeof(double) * B, MPC_NMODEL, hipMemcpyHostToDevice, s));
   WarmIO dw{};
   if (warm) MPC_TRY(warm_host_in(h, B, *warm, s, &dw));
-  MPC_TRY(run_impl(h, B, L, npts, d, false, 0.0, d_px, d_py, d_o8, nullptr, traj ? d_tr : nullptr, d_st, d_it, d_pre, (void *)s, warm ? &dw : nullptr));
+  MPC_TRY(run_impl(h, B, L, npts, d, false, 0.0, d_px, d_py, d_o8, nullptr, traj ? d_tr : nullptr, d_st, d_it, d_pre, (void *)s, warm ? &dw : nullptr,
+                   model ? d_model : nullptr));
   if (warm) MPC_TRY(warm_host_out(h, B, *warm, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(ptsx, sizeof(double) * ld, d_px, sizeof(double) * L, sizeof(double) * B, npts, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(ptsy, sizeof(double) * ld, d_py, sizeof(double) * L, sizeof(double) * B, npts, hipMemcpyDeviceToHost, s));
@@ -2560,6 +2753,24 @@ extern "C" int mpc_run_batch_host_warm(MpcHandle *h, int64_t B, int64_t ld, int 
   WarmIO hw = run_warm_io(warm_in, warm_status, warm_out, ld_warm);
   MPC_TRY(warm_check(h, opts, &hw.opts));
   return run_host(h, B, ld, npts, pose, ptsx, ptsy, out8, traj, status, iters, pre, &hw);
+}
+
+extern "C" int mpc_run_batch_host_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx, double *ptsy,
+                                        const double *model, double *out8, double *traj, int32_t *status, int32_t *iters, double *pre) {
+  if (!model) return mpc_run_batch_host(h, B, ld, npts, pose, ptsx, ptsy, out8, traj, status, iters, pre);
+  MPC_TRY(model_check(h));
+  return run_host(h, B, ld, npts, pose, ptsx, ptsy, out8, traj, status, iters, pre, nullptr, model);
+}
+
+extern "C" int mpc_run_batch_host_warm_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx, double *ptsy,
+                                             const double *model, const double *warm_in, const int32_t *warm_status, double *warm_out,
+                                             int64_t ld_warm, const MpcWarmOpts *opts, double *out8, double *traj, int32_t *status,
+                                             int32_t *iters, double *pre) {
+  if (!model)
+    return mpc_run_batch_host_warm(h, B, ld, npts, pose, ptsx, ptsy, warm_in, warm_status, warm_out, ld_warm, opts, out8, traj, status, iters, pre);
+  WarmIO hw = run_warm_io(warm_in, warm_status, warm_out, ld_warm);
+  MPC_TRY(warm_model_check(h, opts, &hw.opts));
+  return run_host(h, B, ld, npts, pose, ptsx, ptsy, out8, traj, status, iters, pre, &hw, model);
 }
 
 /* the device a handle lives on (mpc_create's `device`, resolved) */
@@ -2592,7 +2803,7 @@ static int rollout_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *
     /* (warm, in place: a lane reads its car's column and its previous status (d_rstat) before it writes either) */
     const WarmIO warm{t == 0 ? nullptr : h->d_warm, h->d_rstat, h->d_warm, h->io_stride, W ? *W : MpcWarmOpts{}};
     SolveIO<double> io{B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, o9, nullptr, h->d_rstat, h->d_iters};
-    io.model = model;            /* (a model rollout: the cars' columns go to every step) */
+    if (model) io.set_model(model, ld);   /* (a model rollout: the cars' columns go to every step) */
     MPC_TRY(launch_solve<double>(h, io, stream_, false, false, false, W ? &warm : nullptr));
     hipLaunchKernelGGL(mpc_rollout_step_kernel, dim3(grid), dim3(256), 0, s, B, ld, t == 0, o9, state, h->d_rstat, h->d_iters, status, iters);
     MPC_HIP_CHECK(hipGetLastError());
@@ -2775,7 +2986,7 @@ static int solve_host(MpcHandle *h, int64_t B, int64_t ld, const R *state, const
   if (model) {
     MPC_TRY(ensure_dev(&h->d_model, sizeof(double) * MPC_NMODEL * (size_t)S));
     MPC_HIP_CHECK(hipMemcpy2DAsync(h->d_model, sizeof(double) * L, model, sizeof(double) * ld, sizeof(double) * B, MPC_NMODEL, hipMemcpyHostToDevice, s));
-    io.model = h->d_model;
+    io.set_model(h->d_model, L);
   }
   MPC_TRY(launch_solve<R>(h, io, (void *)s, true, false, true, warm ? &dw : nullptr));
   if (warm) MPC_TRY(warm_host_out(h, B, *warm, s));

@@ -136,7 +136,7 @@ struct WireWarm {
   const double *warm_in; const int32_t *warm_status; double *warm_out; int64_t ld_warm; const MpcWarmOpts *opts;
 };
 static int wire_telemetry(MpcHandle *h, int64_t B, const MpcWireTelemetry *tel, const double *prev_throttle, double extra_latency,
-                          double *cmd, int32_t *status, const WireWarm *warm) {
+                          double *cmd, int32_t *status, const WireWarm *warm, const double *model = nullptr) {
   if (!h || B < 0 || (B > 0 && (!tel || !cmd || !status))) { mpc_internal_set_error("mpc_wire_telemetry_batch_host: NULL argument or B < 0"); return MPC_ERR_INVALID; }
   if (B == 0) return MPC_OK;
   const int npts = tel[0].npts;
@@ -153,10 +153,11 @@ static int wire_telemetry(MpcHandle *h, int64_t B, const MpcWireTelemetry *tel, 
     host[4 * B + i] = t.steering_angle; host[5 * B + i] = prev_throttle ? prev_throttle[i] : 0.0;
     for (int q = 0; q < npts; q++) { host[(6 + q) * B + i] = t.ptsx[q]; host[(6 + npts + q) * B + i] = t.ptsy[q]; }
   }
+  /* (model [MPC_NMODEL][B]: column i belongs to connection i, like every row above; NULL: the entry points without _model) */
   if (warm)
-    return mpc_telemetry_batch_host_warm(h, B, B, npts, host.data(), extra_latency, host.data() + 6 * B, host.data() + (6 + npts) * B, warm->warm_in,
-                                         warm->warm_status, warm->warm_out, warm->ld_warm, warm->opts, cmd, status);
-  return mpc_telemetry_batch_host(h, B, B, npts, host.data(), extra_latency, host.data() + 6 * B, host.data() + (6 + npts) * B, cmd, status);
+    return mpc_telemetry_batch_host_warm_model(h, B, B, npts, host.data(), extra_latency, host.data() + 6 * B, host.data() + (6 + npts) * B, model,
+                                               warm->warm_in, warm->warm_status, warm->warm_out, warm->ld_warm, warm->opts, cmd, status);
+  return mpc_telemetry_batch_host_model(h, B, B, npts, host.data(), extra_latency, host.data() + 6 * B, host.data() + (6 + npts) * B, model, cmd, status);
 }
 
 extern "C" int mpc_wire_telemetry_batch_host(MpcHandle *h, int64_t B, const MpcWireTelemetry *tel, const double *prev_throttle,
@@ -172,4 +173,19 @@ extern "C" int mpc_wire_telemetry_batch_host_warm(MpcHandle *h, int64_t B, const
                                                   int32_t *status) {
   const WireWarm w{warm_in, warm_status, warm_out, ld_warm, opts};
   return wire_telemetry(h, B, tel, prev_throttle, extra_latency, cmd, status, &w);
+}
+
+/* The two above for connections that bring their own vehicle (mpc_telemetry_batch_host_model / _host_warm_model): model is
+ * [MPC_NMODEL][B], column i belonging to connection i; model == NULL: the entry point without _model. */
+extern "C" int mpc_wire_telemetry_batch_host_model(MpcHandle *h, int64_t B, const MpcWireTelemetry *tel, const double *prev_throttle,
+                                                   double extra_latency, const double *model, double *cmd, int32_t *status) {
+  return wire_telemetry(h, B, tel, prev_throttle, extra_latency, cmd, status, nullptr, model);
+}
+
+extern "C" int mpc_wire_telemetry_batch_host_warm_model(MpcHandle *h, int64_t B, const MpcWireTelemetry *tel, const double *prev_throttle,
+                                                        double extra_latency, const double *model, const double *warm_in,
+                                                        const int32_t *warm_status, double *warm_out, int64_t ld_warm,
+                                                        const MpcWarmOpts *opts, double *cmd, int32_t *status) {
+  const WireWarm w{warm_in, warm_status, warm_out, ld_warm, opts};
+  return wire_telemetry(h, B, tel, prev_throttle, extra_latency, cmd, status, &w, model);
 }

@@ -160,7 +160,7 @@ class BatchedMPC:
                 res["warm"].data_ptr(), B)
 
     def run_torch(self, pose, ptsx, ptsy, want_traj=False, want_pre=False, stream=None, warm=None, warm_status=None, want_warm=False,
-                  warm_opts=None, warm_out=None, status_out=None):
+                  warm_opts=None, warm_out=None, status_out=None, model=None):
         """MPC::run() for a batch on the device (src/control/MPC.cpp:327-382): pose [6,B] = x,y,psi,v,steering,
         acceleration; ptsx/ptsy [npts,B] global waypoints, overwritten with the vehicle-frame waypoints as the
         reference does.  Returns out8 [8,B] = {x1,y1,psi1,v1,steer in [-1,1],accel,cte1,epsi1} etc.
@@ -168,7 +168,10 @@ class BatchedMPC:
         Warm start from the previous call (opt-in, mpc_run_batch_device_warm): ``warm`` / ``warm_status`` are the "warm" and
         "status" tensors that call returned, as in solve_torch; ``want_warm`` (implied by ``warm``) puts "warm" into the result.
         ``warm_out`` / ``status_out``: tensors to write them into -- the ones passed as ``warm`` / ``warm_status`` for a loop in
-        place."""
+        place.
+
+        ``model`` [6, B] float64 as in solve_torch (mpc_run_batch_device_model, _warm_model; fp64 handles): every car's own dt, Lf
+        and limits, in the solve and in run()'s pre- and post-processing (the speed-table cap, the steering normalisation)."""
         import torch
         B = pose.shape[1]
         npts = ptsx.shape[0]
@@ -182,13 +185,27 @@ class BatchedMPC:
                "traj": torch.empty((2 * self.N, B), dtype=torch.float64, device=dev) if want_traj else None,
                "pre": torch.empty((15, B), dtype=torch.float64, device=dev) if want_pre else None}
         s = stream if stream is not None else torch.cuda.current_stream(dev)
+        if model is not None:
+            self._check_model(model, B)
+        outs = (res["out8"].data_ptr(), res["traj"].data_ptr() if want_traj else None, res["status"].data_ptr(), res["iters"].data_ptr(),
+                res["pre"].data_ptr() if want_pre else None, C.c_void_p(s.cuda_stream))
         if warm is not None or want_warm or warm_out is not None:
             w_in, w_st, w_out, ld_warm = self._warm_args(res, B, dev, warm, warm_status, warm_out)
+            opts = C.byref(warm_opts) if warm_opts is not None else None
+            if model is not None:
+                check(library().mpc_run_batch_device_warm_model(
+                    self._h, B, B, int(npts), pose.data_ptr(), ptsx.data_ptr(), ptsy.data_ptr(), model.data_ptr(), w_in, w_st, w_out, ld_warm,
+                    opts, *outs), "mpc_run_batch_device_warm_model")
+                return res
             check(library().mpc_run_batch_device_warm(
                 self._h, B, B, int(npts), pose.data_ptr(), ptsx.data_ptr(), ptsy.data_ptr(), w_in, w_st, w_out, ld_warm,
                 C.byref(warm_opts) if warm_opts is not None else None, res["out8"].data_ptr(),
                 res["traj"].data_ptr() if want_traj else None, res["status"].data_ptr(), res["iters"].data_ptr(),
                 res["pre"].data_ptr() if want_pre else None, C.c_void_p(s.cuda_stream)), "mpc_run_batch_device_warm")
+            return res
+        if model is not None:
+            check(library().mpc_run_batch_device_model(self._h, B, B, int(npts), pose.data_ptr(), ptsx.data_ptr(), ptsy.data_ptr(),
+                                                       model.data_ptr(), *outs), "mpc_run_batch_device_model")
             return res
         check(library().mpc_run_batch_device(
             self._h, B, B, int(npts), pose.data_ptr(), ptsx.data_ptr(), ptsy.data_ptr(), res["out8"].data_ptr(),
@@ -196,10 +213,11 @@ class BatchedMPC:
             res["pre"].data_ptr() if want_pre else None, C.c_void_p(s.cuda_stream)), "mpc_run_batch_device")
         return res
 
-    def run_numpy(self, pose, ptsx, ptsy, want_traj=False, warm=None, warm_status=None, want_warm=False, warm_opts=None):
+    def run_numpy(self, pose, ptsx, ptsy, want_traj=False, warm=None, warm_status=None, want_warm=False, warm_opts=None, model=None):
         """MPC::run() for host arrays (mpc_run_batch_host; B = 1 is what include/mpc_drop_in.hpp's MPC::run calls): pose [6,B],
         ptsx / ptsy [npts,B] global waypoints.  Returns out8, status, iters, pre [15,B], the vehicle-frame waypoints and traj.
-        ``warm`` / ``warm_status`` / ``want_warm`` / ``warm_opts``: mpc_run_batch_host_warm, as in run_torch ("warm" in the result)."""
+        ``warm`` / ``warm_status`` / ``want_warm`` / ``warm_opts``: mpc_run_batch_host_warm, as in run_torch ("warm" in the result).
+        ``model`` [6, B]: per-instance dt, Lf and limits as in run_torch (mpc_run_batch_host_model, _host_warm_model)."""
         import numpy as np
         f = lambda a: np.ascontiguousarray(a, dtype=np.float64)
         pose, px, py = f(pose), f(ptsx).copy(), f(ptsy).copy()
@@ -207,6 +225,10 @@ class BatchedMPC:
         out8 = np.empty((8, B)); pre = np.empty((15, B)); status = np.empty(B, dtype=np.int32); iters = np.empty(B, dtype=np.int32)
         traj = np.empty((2 * self.N, B)) if want_traj else None
         p = lambda a: a.ctypes.data if a is not None else None
+        if model is not None:
+            model = f(model)
+            if model.shape != (_abi.NMODEL, B):
+                raise ValueError("model must have shape (%d, B)" % _abi.NMODEL)
         if warm is not None or want_warm:
             rows = self.warm_rows()
             if warm is not None:
@@ -215,20 +237,30 @@ class BatchedMPC:
             if warm_status is not None:
                 warm_status = np.ascontiguousarray(warm_status, dtype=np.int32)
             wout = np.empty((rows, B))
+            if model is not None:
+                check(library().mpc_run_batch_host_warm_model(self._h, B, B, int(npts), p(pose), p(px), p(py), p(model), p(warm), p(warm_status),
+                                                              p(wout), B, C.byref(warm_opts) if warm_opts is not None else None, p(out8),
+                                                              p(traj), p(status), p(iters), p(pre)), "mpc_run_batch_host_warm_model")
+                return {"out8": out8, "status": status, "iters": iters, "pre": pre, "ptsx": px, "ptsy": py, "traj": traj, "warm": wout}
             check(library().mpc_run_batch_host_warm(self._h, B, B, int(npts), p(pose), p(px), p(py), p(warm), p(warm_status), p(wout), B,
                                                     C.byref(warm_opts) if warm_opts is not None else None, p(out8), p(traj), p(status),
                                                     p(iters), p(pre)), "mpc_run_batch_host_warm")
             return {"out8": out8, "status": status, "iters": iters, "pre": pre, "ptsx": px, "ptsy": py, "traj": traj, "warm": wout}
+        if model is not None:
+            check(library().mpc_run_batch_host_model(self._h, B, B, int(npts), p(pose), p(px), p(py), p(model), p(out8), p(traj), p(status),
+                                                     p(iters), p(pre)), "mpc_run_batch_host_model")
+            return {"out8": out8, "status": status, "iters": iters, "pre": pre, "ptsx": px, "ptsy": py, "traj": traj}
         check(library().mpc_run_batch_host(self._h, B, B, int(npts), p(pose), p(px), p(py), p(out8), p(traj), p(status), p(iters), p(pre)),
               "mpc_run_batch_host")
         return {"out8": out8, "status": status, "iters": iters, "pre": pre, "ptsx": px, "ptsy": py, "traj": traj}
 
     def telemetry_torch(self, tel, ptsx, ptsy, extra_latency=0.0, want_out8=False, stream=None, warm=None, warm_status=None,
-                        want_warm=False, warm_opts=None, warm_out=None, status_out=None):
+                        want_warm=False, warm_opts=None, warm_out=None, status_out=None, model=None):
         """The telemetry handler around run() (src/mpc_main.cpp:126-174) for a batch: tel [6,B] = x, y, psi,
         speed [mph], steering_angle (simulator sign), previous throttle.  Returns cmd [2,B] = (steering_angle,
         throttle) of the reply, status, and optionally run()'s 8-vector.  The warm arguments are run_torch's
-        (mpc_telemetry_batch_device_warm)."""
+        (mpc_telemetry_batch_device_warm).  ``model`` [6, B] as in run_torch (mpc_telemetry_batch_device_model, _warm_model): each
+        car's own Lf in the latency compensation and its own limits in the steering normalisation and the throttle."""
         import torch
         B = tel.shape[1]
         npts = ptsx.shape[0]
@@ -240,13 +272,26 @@ class BatchedMPC:
                "status": status_out if status_out is not None else torch.empty((B,), dtype=torch.int32, device=dev),
                "out8": torch.empty((8, B), dtype=torch.float64, device=dev) if want_out8 else None}
         s = stream if stream is not None else torch.cuda.current_stream(dev)
+        if model is not None:
+            self._check_model(model, B)
+        outs = (res["cmd"].data_ptr(), res["out8"].data_ptr() if want_out8 else None, res["status"].data_ptr(), C.c_void_p(s.cuda_stream))
         if warm is not None or want_warm or warm_out is not None:
             w_in, w_st, w_out, ld_warm = self._warm_args(res, B, dev, warm, warm_status, warm_out)
+            if model is not None:
+                check(library().mpc_telemetry_batch_device_warm_model(
+                    self._h, B, B, int(npts), tel.data_ptr(), float(extra_latency), ptsx.data_ptr(), ptsy.data_ptr(), model.data_ptr(), w_in,
+                    w_st, w_out, ld_warm, C.byref(warm_opts) if warm_opts is not None else None, *outs), "mpc_telemetry_batch_device_warm_model")
+                return res
             check(library().mpc_telemetry_batch_device_warm(
                 self._h, B, B, int(npts), tel.data_ptr(), float(extra_latency), ptsx.data_ptr(), ptsy.data_ptr(), w_in, w_st, w_out,
                 ld_warm, C.byref(warm_opts) if warm_opts is not None else None, res["cmd"].data_ptr(),
                 res["out8"].data_ptr() if want_out8 else None, res["status"].data_ptr(), C.c_void_p(s.cuda_stream)),
                 "mpc_telemetry_batch_device_warm")
+            return res
+        if model is not None:
+            check(library().mpc_telemetry_batch_device_model(
+                self._h, B, B, int(npts), tel.data_ptr(), float(extra_latency), ptsx.data_ptr(), ptsy.data_ptr(), model.data_ptr(), *outs),
+                "mpc_telemetry_batch_device_model")
             return res
         check(library().mpc_telemetry_batch_device(
             self._h, B, B, int(npts), tel.data_ptr(), float(extra_latency), ptsx.data_ptr(), ptsy.data_ptr(),

@@ -453,8 +453,7 @@ int mpc_telemetry_batch_host_warm(MpcHandle *h, int64_t B, int64_t ld, int npts,
  *   instance with MPC_STATUS_INFEASIBLE and the start point in `out`, as an infeasible start does, with no not-a-number; the
  *   batch goes on.  A state with |v| beyond the instance's own relaxed speed limit is MPC_STATUS_INFEASIBLE as ever.
  * The rollout is the stepwise cold loop of mpc_rollout_batch_device with `model` passed to every step (warm and in one launch:
- * the next section).  The run() / telemetry
- * entry points read Lf and the limits of their pre- and post-processing from the handle and have no such form. */
+ * the next section; run() and the telemetry handler: the section after that). */
 int mpc_solve_batch_device_model(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
                                  const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
                                  double *out, double *traj, int32_t *status, int32_t *iters, void *stream);
@@ -511,6 +510,62 @@ int mpc_rollout_batch_device_fused_model(MpcHandle *h, int64_t B, int64_t ld, in
                                          const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
                                          int warm_start, const MpcWarmOpts *opts, double *hist, int32_t *status, int32_t *iters,
                                          void *stream);
+/* ---- per-instance model values on the run() path: a fleet of different vehicles behind one handler ----------------------------
+ * Each entry point is the one of the same name without `_model` plus `model`, [MPC_NMODEL][ld] doubles addressed with the call's
+ * ld (rows MPC_MODEL_*), directly behind `ptsy`; the wire forms further down take it as [MPC_NMODEL][B] directly behind
+ * `extra_latency`.  Host forms: a host array, copied in with the other inputs.
+ * model == NULL: the call IS the entry point without `_model`, bitwise, with all of its conventions and refusals.
+ * model != NULL, what instance i is processed with: the six values of its column in the solve (as in mpc_solve_batch_device_model;
+ *   dt enters only there) and, around it, in the five places of MPC::run() and the handler that read them --
+ *     max_speed         the cap of the two speed tables: pre[14] (target speed) is what the instance's own max_speed gives
+ *                       (the only row of `pre` that depends on the column: pre[11..13] come from the fit); the `keep` term of
+ *                       computeThrottle
+ *     max_steering      the normalisation of the steering value in out8[4] / cmd[0]
+ *     Lf                the heading of the latency compensation (telemetry forms)
+ *     max_acceleration, max_deceleration   computeThrottle (telemetry forms)
+ *   Everything else is the handle's: the speed tables themselves, max_fit_order / max_fit_error, latency_ms, lookahead,
+ *   steer_adj_*, the weights, N, every solver control and max_soc.
+ * A column that is not usable (the rule of the section above): the handle's values take its place in the pre- and post-processing as
+ *   in the solve, the instance ends MPC_STATUS_INFEASIBLE, out8, cmd, pre and warm_out hold no not-a-number, and the batch goes on.
+ *   A car faster than its own (relaxed) speed limit is MPC_STATUS_INFEASIBLE as ever.
+ * Dispatch: ONE solve launch between the pre and the post kernel -- the wave kernel's MODEL build (an instance per wavefront, or per
+ *   16 / 32 of its lanes) when B <= wave_max_batch (0 means 1 024, below 0 never), cold, with max_soc > 0, and warm; above it the
+ *   lane kernel's MODEL build, as for every model call.  No deferred tails, no pass cuts, no take order.  Both write the same bits.
+ *   (mpc_solve_*_model and mpc_rollout_*_model are not changed by this: the lane kernel at every B.)
+ * Accepted handles: the model rule.  Every fp64 handle, also one whose ordinary solve starts in fp32 (served on its fp64 workspace,
+ *   bitwise a handle created with f64_f32_start = 0) -- for the warm forms too, which without `_model` refuse such a handle.
+ * Refusals: an MPC_PRECISION_F32 handle gets MPC_ERR_INVALID with the model message; max_soc > 0 together with a warm form gets
+ *   MPC_ERR_UNSUPPORTED, as every warm call does (the cold forms honour max_soc); npts outside 3..8, ld < B and ld_warm < B get
+ *   MPC_ERR_INVALID as without `_model`.
+ * Warm forms: every rule of mpc_solve_batch_device_warm_model (a record is checked against the instance's own relaxed box; one that
+ *   no longer fits -- written under a column with a wider max_steering, say -- starts that instance cold, bitwise the cold model
+ *   call) and the one extra rule of the run() path: psi of the record is projected into this call's [yaw_lo, yaw_hi] first. */
+int mpc_run_batch_device_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx, double *ptsy,
+                               const double *model, double *out8, double *traj, int32_t *status, int32_t *iters, double *pre,
+                               void *stream);
+int mpc_run_batch_host_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx, double *ptsy,
+                             const double *model, double *out8, double *traj, int32_t *status, int32_t *iters, double *pre);
+int mpc_telemetry_batch_device_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
+                                     double *ptsx, double *ptsy, const double *model, double *cmd, double *out8, int32_t *status,
+                                     void *stream);
+int mpc_telemetry_batch_host_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
+                                   const double *ptsx, const double *ptsy, const double *model, double *cmd, int32_t *status);
+int mpc_run_batch_device_warm_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx, double *ptsy,
+                                    const double *model, const double *warm_in, const int32_t *warm_status, double *warm_out,
+                                    int64_t ld_warm, const MpcWarmOpts *opts, double *out8, double *traj, int32_t *status,
+                                    int32_t *iters, double *pre, void *stream);
+int mpc_run_batch_host_warm_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx, double *ptsy,
+                                  const double *model, const double *warm_in, const int32_t *warm_status, double *warm_out,
+                                  int64_t ld_warm, const MpcWarmOpts *opts, double *out8, double *traj, int32_t *status,
+                                  int32_t *iters, double *pre);
+int mpc_telemetry_batch_device_warm_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
+                                          double *ptsx, double *ptsy, const double *model, const double *warm_in,
+                                          const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts,
+                                          double *cmd, double *out8, int32_t *status, void *stream);
+int mpc_telemetry_batch_host_warm_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
+                                        const double *ptsx, const double *ptsy, const double *model, const double *warm_in,
+                                        const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts,
+                                        double *cmd, int32_t *status);
 /* ---- the wire side of the handler (src/mpc_main.cpp:26-36, 81-222, DATA.md:5-16) --------
  * Everything between the bytes of a simulator frame and the bytes of the reply; the WebSocket server itself is out of
  * scope.  See csrc/mpc_wire.cpp. */
@@ -537,6 +592,14 @@ int mpc_wire_telemetry_batch_host(MpcHandle *h, int64_t B, const MpcWireTelemetr
 int mpc_wire_telemetry_batch_host_warm(MpcHandle *h, int64_t B, const MpcWireTelemetry *tel, const double *prev_throttle,
                                        double extra_latency, const double *warm_in, const int32_t *warm_status, double *warm_out,
                                        int64_t ld_warm, const MpcWarmOpts *opts, double *cmd, int32_t *status);
+/* The two above for connections with vehicles of their own (mpc_telemetry_batch_host_model / _host_warm_model): model is
+ * [MPC_NMODEL][B], column i belonging to connection i; NULL: the entry point without `_model`. */
+int mpc_wire_telemetry_batch_host_model(MpcHandle *h, int64_t B, const MpcWireTelemetry *tel, const double *prev_throttle,
+                                        double extra_latency, const double *model, double *cmd, int32_t *status);
+int mpc_wire_telemetry_batch_host_warm_model(MpcHandle *h, int64_t B, const MpcWireTelemetry *tel, const double *prev_throttle,
+                                             double extra_latency, const double *model, const double *warm_in,
+                                             const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts,
+                                             double *cmd, int32_t *status);
 /* ---- deferred tails (MpcParams.tail_cut > 0) ----------------------------------------------------------------
  * A launch lasts as long as its slowest instance; on heavy-tailed workloads one 200-iteration straggler prices 65 536
  * solves.  With tail_cut = n the launch of mpc_solve_batch_device(_f32) hands every instance that is still running after
