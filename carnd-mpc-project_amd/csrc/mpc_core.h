@@ -35,9 +35,11 @@
  * fully coalesced line.  (See DESIGN.md for why this beats one instance per
  * wavefront for 6x6 blocks, and for the traffic accounting.)
  *
- * The same header compiles with g++ for tests/host_twin.cpp, a test-only CPU
- * build used to debug the algorithm in the GPU-less build container; the
- * shipped library contains the HIP build only.
+ * The same header compiles with g++ for tests/host_twin, the one test-only CPU
+ * build (host_twin.cpp and instance_twin.cpp, one library), which runs the
+ * per-instance driver at the end of this file -- what the wave kernels run --
+ * against the oracle on a machine without a GPU; the shipped library contains
+ * the HIP build only.
  */
 #ifndef MPC_CORE_H
 #define MPC_CORE_H
@@ -2724,7 +2726,7 @@ struct WarmColumn {
 
 /* One car of a closed-loop rollout (mpc_rollout_batch_device*, the loop of src/test.cpp:79-111) between two of its solves: what the
  * next solve starts from, what the call reports per car, and which steps may start warm.  The fused rollout (the ROLL builds of the
- * lane kernel) and the test-only CPU build tests/rollout_twin go through this and nothing else; mpc_rollout_step_kernel states the
+ * lane kernel) and the test-only CPU build tests/host_twin go through this and nothing else; mpc_rollout_step_kernel states the
  * same rule for the stepwise loop, a launch per step. */
 struct RolloutCar {
   /* the next state: rows 0..5 of solve()'s 9-vector {x1, y1, psi1, v1, cte1, epsi1}, as they were written (out9(q) reads, state(q, v) writes) */
@@ -2740,18 +2742,88 @@ struct RolloutCar {
   MPC_HD static bool starts_warm(int step, int32_t prev_status) { return step > 0 && prev_status == MPC_STATUS_SUCCESS; }
 };
 
-/* One instance, end to end (used by the test-only host build; the device kernel
- * drives Solver directly so that outputs go straight to their HBM arrays). */
+/* ---- one instance, end to end ------------------------------------------------------------------------------------------------
+ * The sequence every caller with a Solver object per instance runs: gather_instance, instance_solve and -- by whoever writes the
+ * instance out: the group's first lane in the wave kernels -- instance_store.  The wave kernels (mpc_solve_wave_kernel), the
+ * test-only CPU build (tests/host_twin) and solve_instance below are uses of these three and spell nothing of it out themselves;
+ * the lane kernel drives Solver::step through a state machine of its own.  Two arguments say which form a call takes, by type:
+ *   col   NoColumn: the handle's model values (setup / unpack); or the getter of the instance's column (setup_model / unpack_model)
+ *   warm  NoWarm: solve(); or a WarmStart (solve_warm, then warm_store) */
+struct NoColumn {};
+struct NoWarm {};
+struct WarmStart {
+  bool warm;                      /* start from `column`; false: cold, as solve() */
+  WarmColumn column;
+  const MpcWarmOpts *opts;
+  double *out;                    /* the instance's column of warm_out, rows ld_out doubles apart; nullptr: nothing is written */
+  int64_t ld_out;
+};
+/* What a warm call brings (the mpc_*_warm entry points): the warm buffers, [(N-1) * MPC_WARM_REC][ld_warm] doubles addressed by
+ * INSTANCE at both ends, the options in effect and the rule of the run() path (psi_box: mpc::WarmColumn).  warm_in may be warm_out
+ * and warm_status may be the call's own status array, so none of the pointers is __restrict__: instance() reads the status the
+ * column came with, before anything of the instance is written. */
+struct WarmCall {
+  const double *warm_in;          /* nullptr: every instance starts cold */
+  const int32_t *warm_status;     /* nullptr: every column of warm_in is valid */
+  double *warm_out;               /* nullptr: nothing is written */
+  int64_t ld_warm;
+  MpcWarmOpts wopts;
+  int32_t psi_box;                /* the run() path: psi of the records is projected into the instance's [yaw_lo, yaw_hi] */
+  MPC_HD WarmStart instance(int64_t i, double yaw_lo, double yaw_hi) const {
+    const bool warm = warm_in != nullptr && (warm_status == nullptr || warm_status[i] == MPC_STATUS_SUCCESS);
+    return WarmStart{warm, WarmColumn{warm_in + i, ld_warm, psi_box ? yaw_lo : -HUGE_VAL, psi_box ? yaw_hi : HUGE_VAL}, &wopts,
+                     warm_out ? warm_out + i : nullptr, ld_warm};
+  }
+};
+
+/* instance i of quantity-major arrays with leading dimension ld; weights == nullptr: the handle's */
+template <class R, class RIO>
+MPC_HD void gather_instance(const MpcParams &P, int64_t i, int64_t ld, const RIO *state, const RIO *coeffs, const RIO *weights, R *st,
+                            R *cf, R *w) {
+  MPC_UNROLL
+  for (int q = 0; q < 6; q++) st[q] = (R)state[q * ld + i];
+  MPC_UNROLL
+  for (int q = 0; q < MPC_NCOEF; q++) cf[q] = (R)coeffs[q * ld + i];
+  MPC_UNROLL
+  for (int q = 0; q < MPC_NW; q++) w[q] = weights ? (R)weights[q * ld + i] : (R)P.weights[q];
+}
+
+/* set-up and solve; returns the status */
+template <class SV, class Col, class Warm, class R>
+MPC_HD int instance_solve(SV &S, Col col, const Warm &warm, const R *st, const R *cf, R yaw_lo, R yaw_hi, const R *w) {
+  int r;
+  if constexpr (std::is_same<Col, NoColumn>::value) r = S.setup(st, cf, yaw_lo, yaw_hi, w, true);
+  else r = S.setup_model(col, st, cf, yaw_lo, yaw_hi, w, true);
+  if (r != MPC_STATUS_SUCCESS) return r;
+  if constexpr (std::is_same<Warm, NoWarm>::value) return S.solve();
+  else return S.solve_warm(warm.warm, warm.column, *warm.opts);
+}
+
+/* the hand-over through the caller's accessors (Solver::unpack), the final iterate whatever the status; returns the iterations */
+template <class SV, class Col, class Warm, class OutF, class TrajF, class R>
+MPC_HD int instance_store(const SV &S, Col col, const Warm &warm, OutF out, TrajF traj, bool want_traj, R yaw_lo, R yaw_hi) {
+  if constexpr (std::is_same<Col, NoColumn>::value) S.unpack(out, traj, want_traj, yaw_lo, yaw_hi);
+  else S.unpack_model(col, out, traj, want_traj, yaw_lo, yaw_hi);
+  if constexpr (!std::is_same<Warm, NoWarm>::value) {
+    if (warm.out) {
+      double *wo = warm.out;
+      const int64_t lw = warm.ld_out;
+      S.warm_store([wo, lw](int k, int f, R v) { wo[(int64_t)(k * MPC_WARM_REC + f) * lw] = v; });
+    }
+  }
+  return S.iters;
+}
+
 template <class WS, class R>
 MPC_HD int solve_instance(const MpcParams &P, WS ws, const R *state6, const R *coef5, R yaw_lo,
                           R yaw_hi, const R *w12, R *out9, R *traj2N, int *iters_out) {
   Solver<WS, R> S(P, ws);
-  int status = S.setup(state6, coef5, yaw_lo, yaw_hi, w12);
-  if (status == MPC_STATUS_SUCCESS) status = S.solve();
+  const int status = instance_solve(S, NoColumn{}, NoWarm{}, state6, coef5, yaw_lo, yaw_hi, w12);
   R *o = out9;
   R *t = traj2N;
-  S.unpack([o](int i) -> R & { return o[i]; }, [t](int i) -> R & { return t[i]; }, traj2N != nullptr, yaw_lo, yaw_hi);
-  if (iters_out) *iters_out = S.iters;
+  const int it = instance_store(S, NoColumn{}, NoWarm{}, [o](int i) -> R & { return o[i]; }, [t](int i) -> R & { return t[i]; },
+                                traj2N != nullptr, yaw_lo, yaw_hi);
+  if (iters_out) *iters_out = it;
   return status;
 }
 

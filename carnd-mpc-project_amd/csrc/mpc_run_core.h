@@ -21,6 +21,19 @@ namespace mpc {
 
 enum : int { RUN_MAX_PTS = 8 };
 
+/* Rows of `pre` [RUN_PRE_ROWS][ld], what the pre-solve half hands to the solve and to the post-solve half (and to the caller who
+ * asks for it): the solve's inputs first, in the order a solve call takes them */
+enum : int {
+  RUN_PRE_STATE = 0,              /* 6 rows */
+  RUN_PRE_COEFFS = 6,             /* MPC_NCOEF rows */
+  RUN_PRE_YAW_LO = 11,
+  RUN_PRE_YAW_HI = 12,
+  RUN_PRE_MAX_YAW_CHANGE = 13,
+  RUN_PRE_TARGET_SPEED = 14,
+  RUN_PRE_ROWS = 15
+};
+static_assert(RUN_PRE_COEFFS + MPC_NCOEF == RUN_PRE_YAW_LO, "the rows of pre");
+
 /* least squares min ||A c - y|| with A[i][j] = x_i^j, i < n <= 8, j < NC, by Householder QR (the
  * factorisation Eigen's householderQr() performs in utils.cpp:24-26); everything unrolled */
 template <int NC>
@@ -171,6 +184,7 @@ MPC_HD void run_pre(const MpcParams &P, const MV &m_, const double *pose, double
   else { R.yaw_lo = -0.1; R.yaw_hi = R.max_yaw_change; }
   R.state[0] = 0.0; R.state[1] = 0.0; R.state[2] = 0.0; R.state[3] = pose[3]; R.state[4] = cte; R.state[5] = epsi;   /* :355-356 */
 }
+
 MPC_HD void run_pre(const MpcParams &P, const double *pose, double *px, double *py, int n, RunPre &R) { run_pre(P, P, pose, px, py, n, R); }
 
 /* The post-solve half (MPC.cpp:360-381): result9 -> {x1,y1,psi1,v1,steer in [-1,1],accel,cte1,epsi1} */
@@ -228,6 +242,70 @@ template <class MV>
 MPC_HD void command_from_run(const MV &m, const double *o8, double *steer_cmd, double *throttle_cmd) {
   *steer_cmd = -o8[4];
   *throttle_cmd = compute_throttle(m, o8[5], o8[3]);
+}
+
+
+/* ---- one instance of a batch, as the run() kernels and the test-only CPU build (tests/host_twin) run it ----------------------
+ * MV as above: the handle's MpcParams (pass P twice) or the instance's ModelVals (model_vals_of). */
+/* instance i's column of model [MPC_NMODEL][ld]; a column that cannot be used: the handle's values (the solve reports it INFEASIBLE) */
+MPC_HD ModelVals model_vals_of(const MpcParams &P, const double *model, int64_t ld, int64_t i) {
+  bool ok;
+  const double *mc = model + i;
+  return ModelVals::column(P, [mc, ld](int q) { return mc[q * ld]; }, ok);
+}
+
+/* pose [6][ld] (TELEMETRY: the simulator's telemetry rows, latency compensation first, mpc_main.cpp:126-159) and the waypoints
+ * ptsx / ptsy [npts][ld], which become the vehicle-frame ones in place -> pre [RUN_PRE_ROWS][ldp].  Returns the fit's coefficient count. */
+template <bool TELEMETRY, class MV>
+MPC_HD int run_pre_instance(const MpcParams &P, const MV &m, int64_t i, int64_t ld, int npts, const double *pose, double extra,
+                            double *ptsx, double *ptsy, double *pre, int64_t ldp) {
+  double po[6], px[RUN_MAX_PTS], py[RUN_MAX_PTS];
+  MPC_UNROLL
+  for (int q = 0; q < 6; q++) po[q] = pose[q * ld + i];
+  if (TELEMETRY) {
+    double t6[6];
+    MPC_UNROLL
+    for (int q = 0; q < 6; q++) t6[q] = po[q];
+    telemetry_to_pose(P, m, t6, extra, po);
+  }
+  MPC_UNROLL
+  for (int q = 0; q < RUN_MAX_PTS; q++) {
+    /* (no load under a condition: the rows past npts read the last row that exists and count as 0.0 -- with conditional loads
+     * mpc_run_pre_kernel needs 188 VGPRs instead of 168 and loses a wave of occupancy) */
+    const int row = q < npts ? q : npts - 1;
+    const double x = ptsx[row * ld + i], y = ptsy[row * ld + i];
+    px[q] = q < npts ? x : 0.0; py[q] = q < npts ? y : 0.0;
+  }
+  RunPre R;
+  run_pre(P, m, po, px, py, npts, R);
+  MPC_UNROLL
+  for (int q = 0; q < RUN_MAX_PTS; q++) if (q < npts) { ptsx[q * ld + i] = px[q]; ptsy[q * ld + i] = py[q]; }
+  MPC_UNROLL
+  for (int q = 0; q < 6; q++) pre[(RUN_PRE_STATE + q) * ldp + i] = R.state[q];
+  MPC_UNROLL
+  for (int q = 0; q < MPC_NCOEF; q++) pre[(RUN_PRE_COEFFS + q) * ldp + i] = R.coef[q];
+  pre[RUN_PRE_YAW_LO * ldp + i] = R.yaw_lo; pre[RUN_PRE_YAW_HI * ldp + i] = R.yaw_hi;
+  pre[RUN_PRE_MAX_YAW_CHANGE * ldp + i] = R.max_yaw_change; pre[RUN_PRE_TARGET_SPEED * ldp + i] = R.target_speed;
+  return R.ncoef;
+}
+
+/* pre and solve()'s vector out9 [9][ld9] -> out8 [8][ld] and / or cmd [2][ld], the reply of the telemetry handler (either may be nullptr) */
+template <class MV>
+MPC_HD void run_post_instance(const MpcParams &P, const MV &m, int64_t i, const double *pre, int64_t ldp, const double *out9, int64_t ld9,
+                              double *out8, double *cmd, int64_t ld) {
+  double r9[9], o8[8];
+  MPC_UNROLL
+  for (int q = 0; q < 9; q++) r9[q] = out9[q * ld9 + i];
+  run_post(P, m, pre[RUN_PRE_MAX_YAW_CHANGE * ldp + i], pre[RUN_PRE_TARGET_SPEED * ldp + i], pre[(RUN_PRE_STATE + 3) * ldp + i], r9, o8);
+  if (out8) {
+    MPC_UNROLL
+    for (int q = 0; q < 8; q++) out8[q * ld + i] = o8[q];
+  }
+  if (cmd) {
+    double sc, tc;
+    command_from_run(run_model_of(P, m), o8, &sc, &tc);
+    cmd[i] = sc; cmd[ld + i] = tc;
+  }
 }
 
 }  // namespace mpc

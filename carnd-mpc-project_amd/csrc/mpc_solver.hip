@@ -15,6 +15,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 #include "mpc_core.h"
@@ -187,36 +188,29 @@ struct MpcPhase {
   int64_t ord_ld;
 };
 
-/* What the WARM build of mpc_solve_kernel gets on top (the mpc_*_warm entry points): the warm buffers, [(N-1) * MPC_WARM_REC][ld_warm]
- * doubles addressed by INSTANCE at both ends -- quantity-major, so neighbouring lanes coalesce like every other array at the ABI, and
- * lane compaction may move an instance between the two.  warm_in may be warm_out and warm_status may be the launch's own status
- * array: a lane reads its instance's column (and its status) when it takes the instance and writes them when it has finished it, so
- * none of these pointers is __restrict__.  A type of its own: the other builds' kernel arguments are what they were. */
-struct MpcPhaseWarm : MpcPhase {
-  const double *warm_in;          /* nullptr: every instance starts cold */
-  const int32_t *warm_status;     /* nullptr: every column of warm_in is valid */
-  double *warm_out;               /* nullptr: nothing is written */
-  int64_t ld_warm;
-  MpcWarmOpts wopts;
-  int32_t psi_box;                /* the run() path: psi of the records is projected into the instance's [yaw_lo, yaw_hi] (mpc::WarmColumn) */
-};
-
-/* What the MODEL builds of mpc_solve_kernel get on top (the mpc_*_model entry points): the model values of every instance,
- * [MPC_NMODEL][ld_model] doubles addressed by INSTANCE like the inputs -- a lane reads its instance's six values wherever it runs set-up
- * for it (the take, an instance that lane compaction has moved) and when it writes the instance out, so the column follows the
- * instance from lane to lane.  These builds are launched as one single phase without cuts and deferred tails (a parked or deferred
- * instance would have to carry its column along).  A type of its own: the other builds' kernel arguments are what they were. */
-struct MpcPhaseModel : MpcPhase {
+/* What a build of mpc_solve_kernel gets on top of MpcPhase is composed of three parts, and MpcPhaseOf<ROLL, WARM, MODEL> inherits
+ * exactly the parts its build reads; MpcPhaseOf<false, false, false> is MpcPhase itself, so the kernel arguments of the builds
+ * without any of them are what they were.
+ *
+ * WARM (the mpc_*_warm entry points; the warm rollouts): mpc::WarmCall, the warm buffers addressed by INSTANCE at both ends --
+ * quantity-major, so neighbouring lanes coalesce like every other array at the ABI, and lane compaction may move an instance between
+ * the two.  A lane reads its instance's column (and its status) when it takes the instance and writes them when it has finished it.
+ *
+ * MODEL (the mpc_*_model entry points): the model values of every instance, [MPC_NMODEL][ld_model] doubles addressed by INSTANCE
+ * like the inputs -- a lane reads its instance's six values wherever it runs set-up for it (the take, an instance that lane
+ * compaction has moved) and when it writes the instance out, so the column follows the instance from lane to lane.  These builds
+ * are launched as one single phase without cuts and deferred tails (a parked or deferred instance would have to carry its column
+ * along).  Also the last argument of the MODEL builds of the wave kernel and of the run() kernels. */
+struct MpcModelPart {
   const double *model;
-  int64_t ld_model;               /* its own leading dimension: run() solves from the handle's rows, the columns stay the caller's */
+  int64_t ld_model;               /* its own leading dimension: run() solves from the handle's rows, the columns stay the caller's (a rollout: ld) */
 };
 
-/* What the ROLL builds of mpc_solve_kernel get on top (mpc_rollout_batch_device_fused): a lane keeps the car it has taken for `steps`
- * solves.  Everything the launch writes AND reads again goes through the pointers below -- the car's state, its status and its
- * iterations here, its warm column (warm_in == warm_out) in MpcPhaseWarm -- and none of them is const or __restrict__: the lane that
- * has written a value is the one that reads it back, in program order.  The kernel's own state / out / status / iters arguments are
- * not dereferenced in these builds.  A type of its own: the other builds' kernel arguments are what they were. */
-struct MpcPhaseRoll : MpcPhaseWarm {
+/* ROLL (mpc_rollout_batch_device_fused): a lane keeps the car it has taken for `steps` solves.  Everything the launch writes AND
+ * reads again goes through the pointers below -- the car's state, its status and its iterations here, its warm column (warm_in ==
+ * warm_out) in the warm part -- and none of them is const or __restrict__: the lane that has written a value is the one that reads
+ * it back, in program order.  The kernel's own state / out / status / iters arguments are not dereferenced in these builds. */
+struct MpcRollPart {
   int32_t steps;
   double *hist;                   /* [steps][9][ldo], or the handle's 9 scratch rows with hist_step = 0 */
   int64_t hist_step;              /* doubles from one step's 9 rows to the next */
@@ -224,16 +218,22 @@ struct MpcPhaseRoll : MpcPhaseWarm {
   int32_t *status, *iters;        /* per car: worst status, summed iterations (iters may be nullptr) */
 };
 
-/* What the WARM+MODEL and ROLL+MODEL builds get (the mpc_*_warm_model entry points, mpc_rollout_batch_device_fused_model): the warm
- * or rollout arguments and the instances' columns, read as in MpcPhaseModel.  Types of their own once more: the kernel arguments of
- * every other build are what they were. */
-struct MpcPhaseWarmModel : MpcPhaseWarm {
-  const double *model;
-  int64_t ld_model;
-};
-struct MpcPhaseRollModel : MpcPhaseRoll {
-  const double *model;            /* (leading dimension ld: a rollout has one for all its arrays) */
-};
+template <bool ON, class Part> struct MpcPartIf : Part {};
+template <class Part> struct MpcPartIf<false, Part> {};
+template <bool ROLL, bool WARM, bool MODEL>
+struct MpcPhaseParts : MpcPhase, MpcPartIf<WARM, mpc::WarmCall>, MpcPartIf<ROLL, MpcRollPart>, MpcPartIf<MODEL, MpcModelPart> {};
+template <bool ROLL, bool WARM, bool MODEL>
+using MpcPhaseOf = std::conditional_t<ROLL || WARM || MODEL, MpcPhaseParts<ROLL, WARM, MODEL>, MpcPhase>;
+/* a phase's value from its parts: those the build does not inherit are left out */
+template <bool ROLL, bool WARM, bool MODEL>
+static MpcPhaseOf<ROLL, WARM, MODEL> phase_of(const MpcPhase &T, const mpc::WarmCall &warm, const MpcRollPart &roll, const MpcModelPart &model) {
+  MpcPhaseOf<ROLL, WARM, MODEL> X;
+  static_cast<MpcPhase &>(X) = T;
+  if constexpr (WARM) static_cast<mpc::WarmCall &>(X) = warm;
+  if constexpr (ROLL) static_cast<MpcRollPart &>(X) = roll;
+  if constexpr (MODEL) static_cast<MpcModelPart &>(X) = model;
+  return X;
+}
 
 /* The take-order key of every instance of a launch (csrc/mpc_take_key.h) and the bins' lists: one thread per instance, a wave
  * appends its instances to the bins' lists.  No LDS and few registers: its waves fit beside the resident waves of a bulk
@@ -320,10 +320,6 @@ template <class RIO, class R> struct OutRef {
  * With WARM: warm_point() judges a record against the relaxed box that setup_model has just set from the column, and the cold solve
  * that follows a refused record or a failed warm attempt starts from the solver's own members -- no set-up in between.  With ROLL:
  * the car taken again is set up from its column like a fresh one, and the hand-over of a step projects into the column's limits. */
-template <bool ROLL, bool WARM, bool MODEL>
-using MpcPhaseOf = std::conditional_t<ROLL, std::conditional_t<MODEL, MpcPhaseRollModel, MpcPhaseRoll>,
-                                      std::conditional_t<WARM, std::conditional_t<MODEL, MpcPhaseWarmModel, MpcPhaseWarm>,
-                                                         std::conditional_t<MODEL, MpcPhaseModel, MpcPhase>>>;
 template <bool STAGING, class R, class RIO = R, class RSRC = RIO, bool SOC = false, bool WARM = false, bool ROLL = false, bool MODEL = false>
 __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
     const MpcParams P, const int64_t B, const int64_t ld, const int64_t ldo, const RIO *__restrict__ state,
@@ -961,21 +957,26 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_tail_slice_kernel(const MpcPara
  * 3.7 KB per instance at N = 10 in fp64); every lane of the group
  * runs the solver's state machine on them -- the decisions are wave-uniform -- and the sweeps share their work between the
  * lanes (mpc::Solver<WS, R, true>: backward_wave, forward_wave and the wave form of costate_trial in mpc_core.h). */
-/* MODEL (the mpc_run_*_model / mpc_telemetry_*_model entry points): one more kernel argument, the instances' columns (WaveModel);
- * every lane of a group reads the group's column once, Solver::setup_model / unpack_model take the place of setup / unpack, and the
- * group's first lane writes as before.  The builds without it have the arguments they had (`Model` is empty). */
-struct WaveModel {
-  const double *model;            /* [MPC_NMODEL][ld], addressed by instance */
-  int64_t ld;
-};
-template <class R, int LPI, bool SOC = false, bool MODEL = false, class... Model>
+/* The body is the per-instance driver of mpc_core.h: gather_instance, instance_solve by every lane of the group, instance_store by
+ * the group's first lane.
+ * WARM (the mpc_*_warm entry points): every lane of the group reads the instance's column of warm_in (Solver::solve_warm: the warm
+ * attempt, then the complete cold solve if that does not end in SUCCESS); the first lane writes warm_out.
+ * MODEL (the mpc_run_*_model / mpc_telemetry_*_model entry points): every lane of the group reads the group's column once, and
+ * Solver::setup_model / unpack_model take the place of setup / unpack; warm_point judges a record against the relaxed box that
+ * setup_model has just set from the column.
+ * `Extra`: what the WARM and MODEL builds take behind the solve arguments, one struct each in this order (mpc::WarmCall,
+ * MpcModelPart); a build that is neither has the arguments it had. */
+template <bool WARM> struct WaveStatusPtr { typedef int32_t *__restrict__ type; };
+template <> struct WaveStatusPtr<true> { typedef int32_t *type; };      /* (warm_status may be the call's own status array) */
+template <class R, int LPI, bool SOC = false, bool WARM = false, bool MODEL = false, class... Extra>
 __global__ __launch_bounds__(kBlock, 1) void mpc_solve_wave_kernel(
     const MpcParams P, const int64_t B, const int64_t ld, const int64_t ldo, const R *__restrict__ state,
     const R *__restrict__ coeffs, const R *__restrict__ yaw_lo, const R *__restrict__ yaw_hi,
     const R *__restrict__ weights, R *__restrict__ out, R *__restrict__ traj,
-    int32_t *__restrict__ status, int32_t *__restrict__ iters, const Model... model) {
+    typename WaveStatusPtr<WARM>::type status, int32_t *__restrict__ iters, const Extra... extra) {
   extern __shared__ double smem[];
-  static_assert(sizeof...(Model) == (MODEL ? 1 : 0), "the MODEL builds take one WaveModel");
+  static_assert(sizeof...(Extra) == (WARM ? 1 : 0) + (MODEL ? 1 : 0), "the WARM builds take a WarmCall, the MODEL builds an MpcModelPart");
+  static_assert(!WARM || (sizeof(R) == 8 && !SOC), "warm start: the plain fp64 solve only");
   static_assert(!MODEL || sizeof(R) == 8, "per-instance model values: the fp64 solve only");
   constexpr int G = 64 / LPI;                       /* instances per wavefront: each on LPI neighbouring lanes */
   using WS = std::conditional_t<SOC, mpc::LdsSocWorkspace<R, G>, mpc::LdsWorkspace<R, G>>;
@@ -991,211 +992,65 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_wave_kernel(
   SV S(P, ws);
   S.wlane = threadIdx.x % LPI; S.wbase = group * LPI;
   R st[6], cf[MPC_NCOEF], w[MPC_NW];
-#pragma unroll
-  for (int q = 0; q < 6; q++) st[q] = state[q * ld + i];
-#pragma unroll
-  for (int q = 0; q < MPC_NCOEF; q++) cf[q] = coeffs[q * ld + i];
-#pragma unroll
-  for (int q = 0; q < MPC_NW; q++) w[q] = weights ? weights[q * ld + i] : (R)P.weights[q];
+  mpc::gather_instance(P, i, ld, state, coeffs, weights, st, cf, w);
+  const R ylo = yaw_lo[i], yhi = yaw_hi[i];
+  const auto warm = [&] {
+    if constexpr (WARM) return std::get<0>(std::tie(extra...)).instance(i, (double)ylo, (double)yhi);
+    else return mpc::NoWarm{};
+  }();
   /* (MODEL: the group's column, read once; a column that cannot be used ends INFEASIBLE, mpc::ModelVals::column) */
   [[maybe_unused]] double mv[MPC_NMODEL];
-  if constexpr (MODEL) {
-    const WaveModel &W = (model, ...);
+  const auto col = [&] {
+    if constexpr (MODEL) {
+      const MpcModelPart &W = std::get<sizeof...(Extra) - 1>(std::tie(extra...));
 #pragma unroll
-    for (int q = 0; q < MPC_NMODEL; q++) mv[q] = W.model[q * W.ld + i];
-  }
-  [[maybe_unused]] const auto col = [&mv](int q) { return mv[q]; };
-  int r;
-  if constexpr (MODEL) r = S.setup_model(col, st, cf, yaw_lo[i], yaw_hi[i], w, true);
-  else r = S.setup(st, cf, yaw_lo[i], yaw_hi[i], w, true);
-  if (r == MPC_STATUS_SUCCESS) r = S.solve();
+      for (int q = 0; q < MPC_NMODEL; q++) mv[q] = W.model[q * W.ld_model + i];
+      return [&mv](int q) { return mv[q]; };
+    } else return mpc::NoColumn{};
+  }();
+  const int r = mpc::instance_solve(S, col, warm, st, cf, ylo, yhi, w);
   if (S.wlane == 0) {
     R *o = out + i;
     R *t = traj ? traj + i : nullptr;
     const int64_t l = ldo;
-    const auto fo = [o, l](int q) -> R & { return o[q * l]; };
-    const auto ft = [t, l](int q) -> R & { return t[q * l]; };
-    if constexpr (MODEL) S.unpack_model(col, fo, ft, traj != nullptr, yaw_lo[i], yaw_hi[i]);
-    else S.unpack(fo, ft, traj != nullptr, yaw_lo[i], yaw_hi[i]);
+    const int it = mpc::instance_store(S, col, warm, [o, l](int q) -> R & { return o[q * l]; }, [t, l](int q) -> R & { return t[q * l]; },
+                                       traj != nullptr, ylo, yhi);
     status[i] = r;
-    if (iters) iters[i] = S.iters;
+    if (iters) iters[i] = it;
   }
 }
 
-/* The same with a warm start (the mpc_*_warm entry points; see MpcPhaseWarm for the buffers): a kernel of its own, so that the cold
- * launches are what they were.  Every lane of the group reads the instance's column of warm_in (Solver::solve_warm: the warm
- * attempt, then the complete cold solve if that does not end in SUCCESS); the group's first lane writes warm_out. */
-/* MODEL: as in mpc_solve_wave_kernel.  Solver::warm_point judges the record against the relaxed box that setup_model has just set
- * from the column -- the instance's own -- and the cold solve behind a refused record starts from the solver's own members. */
-template <class R, int LPI, bool MODEL = false, class... Model>
-__global__ __launch_bounds__(kBlock, 1) void mpc_solve_wave_warm_kernel(
-    const MpcParams P, const int64_t B, const int64_t ld, const int64_t ldo, const R *__restrict__ state,
-    const R *__restrict__ coeffs, const R *__restrict__ yaw_lo, const R *__restrict__ yaw_hi,
-    const R *__restrict__ weights, R *__restrict__ out, R *__restrict__ traj,
-    int32_t *status, int32_t *__restrict__ iters, const double *warm_in, const int32_t *warm_status, double *warm_out,
-    const int64_t ld_warm, const MpcWarmOpts wopts, const int psi_box, const Model... model) {
-  extern __shared__ double smem[];
-  static_assert(sizeof...(Model) == (MODEL ? 1 : 0), "the MODEL builds take one WaveModel");
-  static_assert(!MODEL || sizeof(R) == 8, "per-instance model values: the fp64 solve only");
-  constexpr int G = 64 / LPI;
-  using WS = mpc::LdsWorkspace<R, G>;
-  using SV = mpc::Solver<WS, R, LPI, false>;
-  const int group = threadIdx.x / LPI;
-  const int64_t i = (int64_t)blockIdx.x * G + group;
-  if (i >= B) return;
-  WS ws;
-  ws.base = (typename WS::lreal *)smem;
-  ws.lane = group;
-  SV S(P, ws);
-  S.wlane = threadIdx.x % LPI; S.wbase = group * LPI;
-  R st[6], cf[MPC_NCOEF], w[MPC_NW];
-#pragma unroll
-  for (int q = 0; q < 6; q++) st[q] = state[q * ld + i];
-#pragma unroll
-  for (int q = 0; q < MPC_NCOEF; q++) cf[q] = coeffs[q * ld + i];
-#pragma unroll
-  for (int q = 0; q < MPC_NW; q++) w[q] = weights ? weights[q * ld + i] : (R)P.weights[q];
-  const bool warm = warm_in != nullptr && (warm_status == nullptr || warm_status[i] == MPC_STATUS_SUCCESS);
-  [[maybe_unused]] double mv[MPC_NMODEL];
-  if constexpr (MODEL) {
-    const WaveModel &W = (model, ...);
-#pragma unroll
-    for (int q = 0; q < MPC_NMODEL; q++) mv[q] = W.model[q * W.ld + i];
-  }
-  [[maybe_unused]] const auto col = [&mv](int q) { return mv[q]; };
-  int r;
-  if constexpr (MODEL) r = S.setup_model(col, st, cf, yaw_lo[i], yaw_hi[i], w, true);
-  else r = S.setup(st, cf, yaw_lo[i], yaw_hi[i], w, true);
-  if (r == MPC_STATUS_SUCCESS) {
-    /* (psi_box: the run() path, see mpc::WarmColumn) */
-    r = S.solve_warm(warm, mpc::WarmColumn{warm_in + i, ld_warm, psi_box ? (double)yaw_lo[i] : -HUGE_VAL, psi_box ? (double)yaw_hi[i] : HUGE_VAL}, wopts);
-  }
-  if (S.wlane == 0) {
-    R *o = out + i;
-    R *t = traj ? traj + i : nullptr;
-    const int64_t l = ldo;
-    const auto fo = [o, l](int q) -> R & { return o[q * l]; };
-    const auto ft = [t, l](int q) -> R & { return t[q * l]; };
-    if constexpr (MODEL) S.unpack_model(col, fo, ft, traj != nullptr, yaw_lo[i], yaw_hi[i]);
-    else S.unpack(fo, ft, traj != nullptr, yaw_lo[i], yaw_hi[i]);
-    if (warm_out) {
-      double *wo = warm_out + i;
-      S.warm_store([wo, ld_warm](int k, int f, R v) { wo[(int64_t)(k * MPC_WARM_REC + f) * ld_warm] = v; });
-    }
-    status[i] = r;
-    if (iters) iters[i] = S.iters;
-  }
-}
-
-/* MPC::run pre-processing, one instance per lane (mpc_run_core.h).  rows of `pre`: state 0..5, coeffs 6..10,
- * yaw_lo 11, yaw_hi 12, max_yaw_change 13, target_speed 14 */
-template <bool TELEMETRY>
+/* MPC::run pre- and post-processing, one instance per lane: mpc::run_pre_instance / run_post_instance of mpc_run_core.h (the rows of
+ * `pre`: mpc::RUN_PRE_*).  MODEL (the mpc_run_*_model / mpc_telemetry_*_model entry points): one more kernel argument, and a lane
+ * reads its instance's column of it once and hands it to mpc_run_core.h as mpc::ModelVals -- Lf in the latency compensation,
+ * max_speed as the cap of the speed tables, max_steering in the normalisation, max_speed and the two acceleration limits in the
+ * throttle.  A column that cannot be used: the handle's values (mpc::ModelVals::column); the solve in between reports the instance
+ * INFEASIBLE.  The builds without it have the arguments they had (`Model` is empty) and read every value from P. */
+template <bool TELEMETRY, bool MODEL, class... Model>
 __global__ __launch_bounds__(256) void mpc_run_pre_kernel(const MpcParams P, int64_t B, int64_t ld, int npts,
                                                           const double *__restrict__ pose, double extra, double *__restrict__ ptsx,
-                                                          double *__restrict__ ptsy, double *__restrict__ pre, int64_t ldp) {
+                                                          double *__restrict__ ptsy, double *__restrict__ pre, int64_t ldp,
+                                                          const Model... model) {
+  static_assert(sizeof...(Model) == (MODEL ? 1 : 0), "the MODEL builds take one MpcModelPart");
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B) return;
-  double po[6], px[mpc::RUN_MAX_PTS], py[mpc::RUN_MAX_PTS];
-#pragma unroll
-  for (int q = 0; q < 6; q++) po[q] = pose[q * ld + i];
-  if (TELEMETRY) {   /* rows are the simulator's telemetry: latency compensation first (mpc_main.cpp:126-159) */
-    double t6[6];
-#pragma unroll
-    for (int q = 0; q < 6; q++) t6[q] = po[q];
-    mpc::telemetry_to_pose(P, P, t6, extra, po);
-  }
-#pragma unroll
-  for (int q = 0; q < mpc::RUN_MAX_PTS; q++) { px[q] = q < npts ? ptsx[q * ld + i] : 0.0; py[q] = q < npts ? ptsy[q * ld + i] : 0.0; }
-  mpc::RunPre R;
-  mpc::run_pre(P, P, po, px, py, npts, R);
-#pragma unroll
-  for (int q = 0; q < mpc::RUN_MAX_PTS; q++) if (q < npts) { ptsx[q * ld + i] = px[q]; ptsy[q * ld + i] = py[q]; }
-#pragma unroll
-  for (int q = 0; q < 6; q++) pre[q * ldp + i] = R.state[q];
-#pragma unroll
-  for (int q = 0; q < 5; q++) pre[(6 + q) * ldp + i] = R.coef[q];
-  pre[11 * ldp + i] = R.yaw_lo; pre[12 * ldp + i] = R.yaw_hi; pre[13 * ldp + i] = R.max_yaw_change; pre[14 * ldp + i] = R.target_speed;
+  if constexpr (MODEL) {
+    const MpcModelPart &W = (model, ...);
+    mpc::run_pre_instance<TELEMETRY>(P, mpc::model_vals_of(P, W.model, W.ld_model, i), i, ld, npts, pose, extra, ptsx, ptsy, pre, ldp);
+  } else mpc::run_pre_instance<TELEMETRY>(P, P, i, ld, npts, pose, extra, ptsx, ptsy, pre, ldp);
 }
 
+template <bool MODEL, class... Model>
 __global__ __launch_bounds__(256) void mpc_run_post_kernel(const MpcParams P, int64_t B, const double *__restrict__ pre, int64_t ldp,
                                                            const double *__restrict__ out9, int64_t ld9, double *__restrict__ out8,
-                                                           double *__restrict__ cmd, int64_t ld) {
+                                                           double *__restrict__ cmd, int64_t ld, const Model... model) {
+  static_assert(sizeof...(Model) == (MODEL ? 1 : 0), "the MODEL builds take one MpcModelPart");
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B) return;
-  double r9[9], o8[8];
-#pragma unroll
-  for (int q = 0; q < 9; q++) r9[q] = out9[q * ld9 + i];
-  mpc::run_post(P, P, pre[13 * ldp + i], pre[14 * ldp + i], pre[3 * ldp + i], r9, o8);
-  if (out8) {
-#pragma unroll
-    for (int q = 0; q < 8; q++) out8[q * ld + i] = o8[q];
-  }
-  if (cmd) {         /* the reply of the telemetry handler (mpc_main.cpp:171-174) */
-    double sc, tc;
-    mpc::command_from_run(P, o8, &sc, &tc);
-    cmd[i] = sc; cmd[ld + i] = tc;
-  }
-}
-
-/* The same two kernels for instances that bring their own model values (the mpc_run_*_model / mpc_telemetry_*_model entry points):
- * a lane reads its instance's column of model [MPC_NMODEL][ldm] once and hands it to mpc_run_core.h as mpc::ModelVals -- Lf in the
- * latency compensation, max_speed as the cap of the speed tables, max_steering in the normalisation, max_speed and the two
- * acceleration limits in the throttle.  A column that cannot be used: the handle's values (mpc::ModelVals::column); the solve in
- * between reports the instance INFEASIBLE.  Kernels of their own: the two above have the arguments and the code they had. */
-template <bool TELEMETRY>
-__global__ __launch_bounds__(256) void mpc_run_pre_model_kernel(const MpcParams P, int64_t B, int64_t ld, int npts,
-                                                                const double *__restrict__ pose, double extra, double *__restrict__ ptsx,
-                                                                double *__restrict__ ptsy, double *__restrict__ pre, int64_t ldp,
-                                                                const double *__restrict__ model, int64_t ldm) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B) return;
-  bool ok;
-  const double *mc = model + i;
-  const mpc::ModelVals m = mpc::ModelVals::column(P, [mc, ldm](int q) { return mc[q * ldm]; }, ok);
-  double po[6], px[mpc::RUN_MAX_PTS], py[mpc::RUN_MAX_PTS];
-#pragma unroll
-  for (int q = 0; q < 6; q++) po[q] = pose[q * ld + i];
-  if (TELEMETRY) {
-    double t6[6];
-#pragma unroll
-    for (int q = 0; q < 6; q++) t6[q] = po[q];
-    mpc::telemetry_to_pose(P, m, t6, extra, po);
-  }
-#pragma unroll
-  for (int q = 0; q < mpc::RUN_MAX_PTS; q++) { px[q] = q < npts ? ptsx[q * ld + i] : 0.0; py[q] = q < npts ? ptsy[q * ld + i] : 0.0; }
-  mpc::RunPre R;
-  mpc::run_pre(P, m, po, px, py, npts, R);
-#pragma unroll
-  for (int q = 0; q < mpc::RUN_MAX_PTS; q++) if (q < npts) { ptsx[q * ld + i] = px[q]; ptsy[q * ld + i] = py[q]; }
-#pragma unroll
-  for (int q = 0; q < 6; q++) pre[q * ldp + i] = R.state[q];
-#pragma unroll
-  for (int q = 0; q < 5; q++) pre[(6 + q) * ldp + i] = R.coef[q];
-  pre[11 * ldp + i] = R.yaw_lo; pre[12 * ldp + i] = R.yaw_hi; pre[13 * ldp + i] = R.max_yaw_change; pre[14 * ldp + i] = R.target_speed;
-}
-
-__global__ __launch_bounds__(256) void mpc_run_post_model_kernel(const MpcParams P, int64_t B, const double *__restrict__ pre, int64_t ldp,
-                                                                 const double *__restrict__ out9, int64_t ld9, double *__restrict__ out8,
-                                                                 double *__restrict__ cmd, int64_t ld, const double *__restrict__ model,
-                                                                 int64_t ldm) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B) return;
-  bool ok;
-  const double *mc = model + i;
-  const mpc::ModelVals m = mpc::ModelVals::column(P, [mc, ldm](int q) { return mc[q * ldm]; }, ok);
-  double r9[9], o8[8];
-#pragma unroll
-  for (int q = 0; q < 9; q++) r9[q] = out9[q * ld9 + i];
-  mpc::run_post(P, m, pre[13 * ldp + i], pre[14 * ldp + i], pre[3 * ldp + i], r9, o8);
-  if (out8) {
-#pragma unroll
-    for (int q = 0; q < 8; q++) out8[q * ld + i] = o8[q];
-  }
-  if (cmd) {
-    double sc, tc;
-    mpc::command_from_run(m, o8, &sc, &tc);
-    cmd[i] = sc; cmd[ld + i] = tc;
-  }
+  if constexpr (MODEL) {
+    const MpcModelPart &W = (model, ...);
+    mpc::run_post_instance(P, mpc::model_vals_of(P, W.model, W.ld_model, i), i, pre, ldp, out9, ld9, out8, cmd, ld);
+  } else mpc::run_post_instance(P, P, i, pre, ldp, out9, ld9, out8, cmd, ld);
 }
 
 /* rollout bookkeeping: next state <- solve()'s step-1 rows; worst status and summed iterations per instance */
@@ -2052,16 +1907,13 @@ struct SolveIO {
   const R *state, *coeffs, *yaw_lo, *yaw_hi, *weights;
   R *out, *traj;
   int32_t *status, *iters;
-  const double *model = nullptr;   /* a model call (the mpc_*_model entry points, fp64 handles): [MPC_NMODEL][ld_model], see MpcPhaseModel */
+  const double *model = nullptr;   /* a model call (the mpc_*_model entry points, fp64 handles): [MPC_NMODEL][ld_model], see MpcModelPart */
   int64_t ld_model = 0;            /* (its own: run() solves from the handle's rows at the handle's stride, the columns stay where the caller has them) */
   bool model_wave = false;         /* a model call of the run() / telemetry entry points: the wave MODEL kernels up to wave_max_batch */
   void set_model(const double *m, int64_t l, bool wave = false) { model = m; ld_model = l; model_wave = wave; }
 };
-/* ... and what a warm call brings on top: the warm buffers (see MpcPhaseWarm) and the options in effect (warm_check) */
-struct WarmIO {
-  const double *warm_in; const int32_t *warm_status; double *warm_out; int64_t ld_warm; MpcWarmOpts opts;
-  bool psi_box = false;   /* the run() path: the records' psi goes into this call's psi box first (mpc::WarmColumn) */
-};
+/* ... and what a warm call brings on top: the warm buffers and the options in effect (warm_check), as the kernels take them */
+using WarmIO = mpc::WarmCall;
 /* ... and where a deferring launch hands its stragglers: its batch's slot of the ring and its fresh queue */
 struct TailPlace {
   bool defer = false;
@@ -2122,17 +1974,11 @@ static int launch_wave(MpcHandle *h, const SolveIO<R> &io, hipStream_t s, bool s
     const unsigned grid = (unsigned)((io.B + G - 1) / G);
     if constexpr (sizeof(R) == 8) {
       const size_t per_soc = per + (size_t)mpc::soc_fields_per_instance(h->params.N) * sizeof(R);
-      if (io.model) {
-        const WaveModel wm{io.model, io.ld_model};
-        if (warm)
-          return launch_kernel(mpc_solve_wave_warm_kernel<R, LPI, true, WaveModel>, grid, G * per, s, h, io, warm->warm_in, warm->warm_status,
-                               warm->warm_out, warm->ld_warm, warm->opts, warm->psi_box ? 1 : 0, wm);
-        if (soc) return launch_kernel(mpc_solve_wave_kernel<R, LPI, true, true, WaveModel>, grid, G * per_soc, s, h, io, wm);
-        return launch_kernel(mpc_solve_wave_kernel<R, LPI, false, true, WaveModel>, grid, G * per, s, h, io, wm);
-      }
-      if (warm)
-        return launch_kernel(mpc_solve_wave_warm_kernel<R, LPI>, grid, G * per, s, h, io, warm->warm_in, warm->warm_status, warm->warm_out,
-                             warm->ld_warm, warm->opts, warm->psi_box ? 1 : 0);
+      const MpcModelPart wm{io.model, io.ld_model};
+      if (io.model && warm) return launch_kernel(mpc_solve_wave_kernel<R, LPI, false, true, true, WarmIO, MpcModelPart>, grid, G * per, s, h, io, *warm, wm);
+      if (io.model && soc) return launch_kernel(mpc_solve_wave_kernel<R, LPI, true, false, true, MpcModelPart>, grid, G * per_soc, s, h, io, wm);
+      if (io.model) return launch_kernel(mpc_solve_wave_kernel<R, LPI, false, false, true, MpcModelPart>, grid, G * per, s, h, io, wm);
+      if (warm) return launch_kernel(mpc_solve_wave_kernel<R, LPI, false, true, false, WarmIO>, grid, G * per, s, h, io, *warm);
       if (soc) return launch_kernel(mpc_solve_wave_kernel<R, LPI, true>, grid, G * per_soc, s, h, io);
     }
     return launch_kernel(mpc_solve_wave_kernel<R, LPI>, grid, G * per, s, h, io);
@@ -2153,27 +1999,25 @@ static int launch_lanes(MpcHandle *h, LaneBuild build, const SolveIO<RIO> &io, h
                         const WarmIO *warm = nullptr) {
   const unsigned grid = (unsigned)((io.B + kBlock - 1) / kBlock);
   /* (r, rsrc: values of the solver's reals and of the reals its resumed iterates come in) */
-  auto go = [&](auto staging, auto r, auto rsrc, auto soc_build, auto warm_build, int64_t tile_reals, const auto &phase, auto model_build) {
+  auto go = [&](auto staging, auto r, auto rsrc, auto soc_build, auto warm_build, int64_t tile_reals, auto model_build) {
     using R = decltype(r);
-    constexpr bool STAGING = decltype(staging)::value;
-    return launch_kernel(mpc_solve_kernel<STAGING, R, RIO, decltype(rsrc), decltype(soc_build)::value, decltype(warm_build)::value, false,
-                                          decltype(model_build)::value>,
-                         grid, STAGING ? staging_lds_bytes<R>() : 0, s, h, io, (R *)ws, tile_reals, phase);
+    constexpr bool STAGING = decltype(staging)::value, WARM = decltype(warm_build)::value, MODEL = decltype(model_build)::value;
+    return launch_kernel(mpc_solve_kernel<STAGING, R, RIO, decltype(rsrc), decltype(soc_build)::value, WARM, false, MODEL>, grid,
+                         STAGING ? staging_lds_bytes<R>() : 0, s, h, io, (R *)ws, tile_reals,
+                         phase_of<false, WARM, MODEL>(T, warm ? *warm : WarmIO{}, {}, {io.model, io.ld_model}));
   };
   constexpr std::true_type yes{};
   constexpr std::false_type no{};
-  if (build == LaneBuild::mixed_f32) return go(yes, float{}, RIO{}, no, no, h->ws_stride_f32, T, no);
-  if (build == LaneBuild::mixed_f64) return with_bool(soc, [&](auto soc_build) { return go(yes, double{}, float{}, soc_build, no, h->ws_stride_f64, T, no); });
+  if (build == LaneBuild::mixed_f32) return go(yes, float{}, RIO{}, no, no, h->ws_stride_f32, no);
+  if (build == LaneBuild::mixed_f64) return with_bool(soc, [&](auto soc_build) { return go(yes, double{}, float{}, soc_build, no, h->ws_stride_f64, no); });
   return with_bool(h->staging, [&](auto staging) {
     if constexpr (sizeof(RIO) == 8) {
-      if (io.model && warm)
-        return go(staging, RIO{}, RIO{}, no, yes, h->ws_stride,
-                  MpcPhaseWarmModel{MpcPhaseWarm{T, warm->warm_in, warm->warm_status, warm->warm_out, warm->ld_warm, warm->opts, warm->psi_box ? 1 : 0}, io.model, io.ld_model}, yes);
-      if (io.model) return with_bool(soc, [&](auto soc_build) { return go(staging, RIO{}, RIO{}, soc_build, no, h->ws_stride, MpcPhaseModel{T, io.model, io.ld_model}, yes); });
-      if (warm) return go(staging, RIO{}, RIO{}, no, yes, h->ws_stride, MpcPhaseWarm{T, warm->warm_in, warm->warm_status, warm->warm_out, warm->ld_warm, warm->opts, warm->psi_box ? 1 : 0}, no);
-      if (soc) return go(staging, RIO{}, RIO{}, yes, no, h->ws_stride, T, no);
+      if (io.model && warm) return go(staging, RIO{}, RIO{}, no, yes, h->ws_stride, yes);
+      if (io.model) return with_bool(soc, [&](auto soc_build) { return go(staging, RIO{}, RIO{}, soc_build, no, h->ws_stride, yes); });
+      if (warm) return go(staging, RIO{}, RIO{}, no, yes, h->ws_stride, no);
+      if (soc) return go(staging, RIO{}, RIO{}, yes, no, h->ws_stride, no);
     }
-    return go(staging, RIO{}, RIO{}, no, no, h->ws_stride, T, no);
+    return go(staging, RIO{}, RIO{}, no, no, h->ws_stride, no);
   });
 }
 
@@ -2459,7 +2303,7 @@ extern "C" int mpc_solve_batch_device_warm(MpcHandle *h, int64_t B, int64_t ld, 
                                            const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts,
                                            double *out, double *traj, int32_t *status, int32_t *iters, void *stream_) {
   WarmIO warm{warm_in, warm_status, warm_out, ld_warm, {}};
-  MPC_TRY(warm_check(h, opts, &warm.opts));
+  MPC_TRY(warm_check(h, opts, &warm.wopts));
   return launch_solve<double>(h, {B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters}, stream_, true, false, false, &warm);
 }
 
@@ -2472,7 +2316,7 @@ extern "C" int mpc_solve_batch_device_warm_model(MpcHandle *h, int64_t B, int64_
     return mpc_solve_batch_device_warm(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, warm_in, warm_status, warm_out, ld_warm, opts, out, traj,
                                        status, iters, stream_);
   WarmIO warm{warm_in, warm_status, warm_out, ld_warm, {}};
-  MPC_TRY(warm_model_check(h, opts, &warm.opts));
+  MPC_TRY(warm_model_check(h, opts, &warm.wopts));
   SolveIO<double> io{B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters};
   io.set_model(model, ld);
   return launch_solve<double>(h, io, stream_, true, false, false, &warm);
@@ -2505,23 +2349,32 @@ static int run_impl(MpcHandle *h, int64_t B, int64_t ld, int npts, const double 
   if (h->params.max_fit_order > 5) { g_last_error = "run(): max_fit_order > 5 is not built (fit orders 2..4)"; return MPC_ERR_UNSUPPORTED; }
   MPC_ON_DEVICE(h);
   const int64_t S = h->io_stride;
-  MPC_TRY(ensure_dev(&h->d_run, sizeof(double) * 15 * S));
+  MPC_TRY(ensure_dev(&h->d_run, sizeof(double) * mpc::RUN_PRE_ROWS * S));
   MPC_TRY(grow_dev(&h->d_run9, &h->run9_bytes, sizeof(double) * 9 * ld));       /* solve()'s 9 rows, with the caller's leading dimension (traj shares it) */
   hipStream_t s = (hipStream_t)stream_;
   double *d_pre = h->d_run;
   const unsigned grid = (unsigned)((B + 255) / 256);
-  if (model && tel) hipLaunchKernelGGL(mpc_run_pre_model_kernel<true>, dim3(grid), dim3(256), 0, s, h->params, B, ld, npts, pose, extra, ptsx, ptsy, d_pre, S, model, ld);
-  else if (model) hipLaunchKernelGGL(mpc_run_pre_model_kernel<false>, dim3(grid), dim3(256), 0, s, h->params, B, ld, npts, pose, 0.0, ptsx, ptsy, d_pre, S, model, ld);
-  else if (tel) hipLaunchKernelGGL(mpc_run_pre_kernel<true>, dim3(grid), dim3(256), 0, s, h->params, B, ld, npts, pose, extra, ptsx, ptsy, d_pre, S);
-  else hipLaunchKernelGGL(mpc_run_pre_kernel<false>, dim3(grid), dim3(256), 0, s, h->params, B, ld, npts, pose, 0.0, ptsx, ptsy, d_pre, S);
+  /* the two kernels around the solve: f(MODEL build or not, the argument the MODEL builds take behind the others) */
+  const auto around = [&](auto f) { return model ? f(std::true_type{}, MpcModelPart{model, ld}) : f(std::false_type{}); };
+  around([&](auto model_build, auto... mp) {
+    return with_bool(tel, [&](auto telemetry) {
+      hipLaunchKernelGGL((mpc_run_pre_kernel<decltype(telemetry)::value, decltype(model_build)::value, decltype(mp)...>), dim3(grid), dim3(256), 0, s,
+                         h->params, B, ld, npts, pose, tel ? extra : 0.0, ptsx, ptsy, d_pre, S, mp...);
+      return MPC_OK;
+    });
+  });
   MPC_HIP_CHECK(hipGetLastError());
-  SolveIO<double> io{B, S, ld, d_pre, d_pre + 6 * S, d_pre + 11 * S, d_pre + 12 * S, nullptr, h->d_run9, traj, status, iters};
+  SolveIO<double> io{B, S, ld, d_pre + mpc::RUN_PRE_STATE * S, d_pre + mpc::RUN_PRE_COEFFS * S, d_pre + mpc::RUN_PRE_YAW_LO * S,
+                     d_pre + mpc::RUN_PRE_YAW_HI * S, nullptr, h->d_run9, traj, status, iters};
   if (model) io.set_model(model, ld, true);
   MPC_TRY(launch_solve<double>(h, io, stream_, true, false, false, warm));
-  if (model) hipLaunchKernelGGL(mpc_run_post_model_kernel, dim3(grid), dim3(256), 0, s, h->params, B, d_pre, S, h->d_run9, ld, out8, cmd, ld, model, ld);
-  else hipLaunchKernelGGL(mpc_run_post_kernel, dim3(grid), dim3(256), 0, s, h->params, B, d_pre, S, h->d_run9, ld, out8, cmd, ld);
+  around([&](auto model_build, auto... mp) {
+    hipLaunchKernelGGL((mpc_run_post_kernel<decltype(model_build)::value, decltype(mp)...>), dim3(grid), dim3(256), 0, s, h->params, B, d_pre, S,
+                       h->d_run9, ld, out8, cmd, ld, mp...);
+    return MPC_OK;
+  });
   MPC_HIP_CHECK(hipGetLastError());
-  if (pre) MPC_HIP_CHECK(hipMemcpy2DAsync(pre, sizeof(double) * ld, d_pre, sizeof(double) * S, sizeof(double) * B, 15, hipMemcpyDeviceToDevice, s));
+  if (pre) MPC_HIP_CHECK(hipMemcpy2DAsync(pre, sizeof(double) * ld, d_pre, sizeof(double) * S, sizeof(double) * B, mpc::RUN_PRE_ROWS, hipMemcpyDeviceToDevice, s));
   return MPC_OK;
 }
 
@@ -2541,7 +2394,7 @@ extern "C" int mpc_telemetry_batch_device(MpcHandle *h, int64_t B, int64_t ld, i
 /* run() and the telemetry handler, warm-started from the previous call (include/mpc_amd.h, "warm start on the run() path") */
 static WarmIO run_warm_io(const double *warm_in, const int32_t *warm_status, double *warm_out, int64_t ld_warm) {
   WarmIO w{warm_in, warm_status, warm_out, ld_warm, {}};
-  w.psi_box = true;
+  w.psi_box = 1;
   return w;
 }
 
@@ -2550,7 +2403,7 @@ extern "C" int mpc_run_batch_device_warm(MpcHandle *h, int64_t B, int64_t ld, in
                                          int64_t ld_warm, const MpcWarmOpts *opts, double *out8, double *traj, int32_t *status,
                                          int32_t *iters, double *pre, void *stream_) {
   WarmIO warm = run_warm_io(warm_in, warm_status, warm_out, ld_warm);
-  MPC_TRY(warm_check(h, opts, &warm.opts));
+  MPC_TRY(warm_check(h, opts, &warm.wopts));
   if (B > 0 && !out8) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
   return run_impl(h, B, ld, npts, pose, false, 0.0, ptsx, ptsy, out8, nullptr, traj, status, iters, pre, stream_, &warm);
 }
@@ -2560,7 +2413,7 @@ extern "C" int mpc_telemetry_batch_device_warm(MpcHandle *h, int64_t B, int64_t 
                                                double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts, double *cmd, double *out8,
                                                int32_t *status, void *stream_) {
   WarmIO warm = run_warm_io(warm_in, warm_status, warm_out, ld_warm);
-  MPC_TRY(warm_check(h, opts, &warm.opts));
+  MPC_TRY(warm_check(h, opts, &warm.wopts));
   if (B > 0 && !cmd) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
   return run_impl(h, B, ld, npts, tel, true, extra_latency, ptsx, ptsy, out8, cmd, nullptr, status, nullptr, nullptr, stream_, &warm);
 }
@@ -2593,7 +2446,7 @@ extern "C" int mpc_run_batch_device_warm_model(MpcHandle *h, int64_t B, int64_t 
     return mpc_run_batch_device_warm(h, B, ld, npts, pose, ptsx, ptsy, warm_in, warm_status, warm_out, ld_warm, opts, out8, traj, status, iters, pre,
                                      stream_);
   WarmIO warm = run_warm_io(warm_in, warm_status, warm_out, ld_warm);
-  MPC_TRY(warm_model_check(h, opts, &warm.opts));
+  MPC_TRY(warm_model_check(h, opts, &warm.wopts));
   if (B > 0 && !out8) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
   return run_impl(h, B, ld, npts, pose, false, 0.0, ptsx, ptsy, out8, nullptr, traj, status, iters, pre, stream_, &warm, model);
 }
@@ -2606,7 +2459,7 @@ extern "C" int mpc_telemetry_batch_device_warm_model(MpcHandle *h, int64_t B, in
     return mpc_telemetry_batch_device_warm(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, warm_in, warm_status, warm_out, ld_warm, opts, cmd, out8,
                                            status, stream_);
   WarmIO warm = run_warm_io(warm_in, warm_status, warm_out, ld_warm);
-  MPC_TRY(warm_model_check(h, opts, &warm.opts));
+  MPC_TRY(warm_model_check(h, opts, &warm.wopts));
   if (B > 0 && !cmd) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
   return run_impl(h, B, ld, npts, tel, true, extra_latency, ptsx, ptsy, out8, cmd, nullptr, status, nullptr, nullptr, stream_, &warm, model);
 }
@@ -2615,7 +2468,7 @@ extern "C" int mpc_telemetry_batch_device_warm_model(MpcHandle *h, int64_t B, in
  * stride, read and written in place, with the status it came with beside it.  *dw: what the launch gets. */
 static int warm_host_in(MpcHandle *h, int64_t B, const WarmIO &hw, hipStream_t s, WarmIO *dw) {
   const int64_t S = h->io_stride, warm_rows = mpc_warm_rows(h->params.N);
-  *dw = WarmIO{nullptr, nullptr, nullptr, S, hw.opts};
+  *dw = WarmIO{nullptr, nullptr, nullptr, S, hw.wopts};
   dw->psi_box = hw.psi_box;
   if ((hw.warm_in || hw.warm_out) && hw.ld_warm < B) { g_last_error = "ld_warm < B"; return MPC_ERR_INVALID; }
   if (hw.warm_in || hw.warm_out) MPC_TRY(ensure_dev(&h->d_warm_io, sizeof(double) * (size_t)warm_rows * (size_t)S));
@@ -2681,7 +2534,7 @@ extern "C" int mpc_telemetry_batch_host_warm(MpcHandle *h, int64_t B, int64_t ld
                                              const double *ptsx, const double *ptsy, const double *warm_in, const int32_t *warm_status,
                                              double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts, double *cmd, int32_t *status) {
   WarmIO hw = run_warm_io(warm_in, warm_status, warm_out, ld_warm);
-  MPC_TRY(warm_check(h, opts, &hw.opts));
+  MPC_TRY(warm_check(h, opts, &hw.wopts));
   return telemetry_host(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, cmd, status, &hw);
 }
 
@@ -2699,7 +2552,7 @@ extern "C" int mpc_telemetry_batch_host_warm_model(MpcHandle *h, int64_t B, int6
   if (!model)
     return mpc_telemetry_batch_host_warm(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, warm_in, warm_status, warm_out, ld_warm, opts, cmd, status);
   WarmIO hw = run_warm_io(warm_in, warm_status, warm_out, ld_warm);
-  MPC_TRY(warm_model_check(h, opts, &hw.opts));
+  MPC_TRY(warm_model_check(h, opts, &hw.wopts));
   return telemetry_host(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, cmd, status, &hw, model);
 }
 
@@ -2716,10 +2569,10 @@ static int run_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const double 
   MPC_ON_DEVICE(h);
   const int N = h->params.N;
   const int64_t L = (B + 7) / 8 * 8;
-  const int64_t in_rows = 6 + 2 * npts, out_rows = 8 + 2 * N + 15, model_rows = model ? MPC_NMODEL : 0;
+  const int64_t in_rows = 6 + 2 * npts, out_rows = 8 + 2 * N + mpc::RUN_PRE_ROWS, model_rows = model ? MPC_NMODEL : 0;
   MPC_TRY(grow_dev(&h->d_tel, &h->tel_bytes, sizeof(double) * (size_t)((in_rows + out_rows + model_rows) * L) + sizeof(int32_t) * (size_t)(2 * L)));
   double *d = h->d_tel, *d_px = d + 6 * L, *d_py = d_px + (int64_t)npts * L, *d_o8 = d + in_rows * L, *d_tr = d_o8 + 8 * L, *d_pre = d_tr + 2 * (int64_t)N * L;
-  double *d_model = d_pre + 15 * L;
+  double *d_model = d_pre + mpc::RUN_PRE_ROWS * L;
   int32_t *d_st = (int32_t *)(d_model + model_rows * L), *d_it = d_st + L;
   hipStream_t s = h->stream;
   MPC_HIP_CHECK(hipMemcpy2DAsync(d, sizeof(double) * L, pose, sizeof(double) * ld, sizeof(double) * B, 6, hipMemcpyHostToDevice, s));
@@ -2735,7 +2588,7 @@ static int run_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const double 
   MPC_HIP_CHECK(hipMemcpy2DAsync(ptsy, sizeof(double) * ld, d_py, sizeof(double) * L, sizeof(double) * B, npts, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(out8, sizeof(double) * ld, d_o8, sizeof(double) * L, sizeof(double) * B, 8, hipMemcpyDeviceToHost, s));
   if (traj) MPC_HIP_CHECK(hipMemcpy2DAsync(traj, sizeof(double) * ld, d_tr, sizeof(double) * L, sizeof(double) * B, 2 * N, hipMemcpyDeviceToHost, s));
-  if (pre) MPC_HIP_CHECK(hipMemcpy2DAsync(pre, sizeof(double) * ld, d_pre, sizeof(double) * L, sizeof(double) * B, 15, hipMemcpyDeviceToHost, s));
+  if (pre) MPC_HIP_CHECK(hipMemcpy2DAsync(pre, sizeof(double) * ld, d_pre, sizeof(double) * L, sizeof(double) * B, mpc::RUN_PRE_ROWS, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipMemcpyAsync(status, d_st, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
   if (iters) MPC_HIP_CHECK(hipMemcpyAsync(iters, d_it, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipStreamSynchronize(s));
@@ -2751,7 +2604,7 @@ extern "C" int mpc_run_batch_host_warm(MpcHandle *h, int64_t B, int64_t ld, int 
                                        const double *warm_in, const int32_t *warm_status, double *warm_out, int64_t ld_warm,
                                        const MpcWarmOpts *opts, double *out8, double *traj, int32_t *status, int32_t *iters, double *pre) {
   WarmIO hw = run_warm_io(warm_in, warm_status, warm_out, ld_warm);
-  MPC_TRY(warm_check(h, opts, &hw.opts));
+  MPC_TRY(warm_check(h, opts, &hw.wopts));
   return run_host(h, B, ld, npts, pose, ptsx, ptsy, out8, traj, status, iters, pre, &hw);
 }
 
@@ -2769,7 +2622,7 @@ extern "C" int mpc_run_batch_host_warm_model(MpcHandle *h, int64_t B, int64_t ld
   if (!model)
     return mpc_run_batch_host_warm(h, B, ld, npts, pose, ptsx, ptsy, warm_in, warm_status, warm_out, ld_warm, opts, out8, traj, status, iters, pre);
   WarmIO hw = run_warm_io(warm_in, warm_status, warm_out, ld_warm);
-  MPC_TRY(warm_model_check(h, opts, &hw.opts));
+  MPC_TRY(warm_model_check(h, opts, &hw.wopts));
   return run_host(h, B, ld, npts, pose, ptsx, ptsy, out8, traj, status, iters, pre, &hw, model);
 }
 
@@ -2876,17 +2729,16 @@ static int rollout_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, do
   const TailPlace tp;
   tail_fields(h, tp, T);
   double *warm = W ? h->d_warm : nullptr;
-  const MpcPhaseRoll R{MpcPhaseWarm{T, warm, nullptr, warm, h->io_stride, W ? *W : MpcWarmOpts{}, 0}, steps, o9, hist ? 9 * ld : 0, state, status, iters};
+  const WarmIO wc{warm, nullptr, warm, h->io_stride, W ? *W : MpcWarmOpts{}, 0};
+  const MpcRollPart roll{steps, o9, hist ? 9 * ld : 0, state, status, iters};
   const unsigned grid = (unsigned)((B + kBlock - 1) / kBlock);
   MPC_TRY(with_bool(h->staging, [&](auto staging) {
     return with_bool(W != nullptr, [&](auto warm_build) {
-      constexpr bool STAGING = decltype(staging)::value;
-      constexpr bool WARM = decltype(warm_build)::value;
-      const size_t lds = STAGING ? staging_lds_bytes<double>() : 0;
-      if (model)
-        return launch_kernel(mpc_solve_kernel<STAGING, double, double, double, false, WARM, true, true>, grid, lds, s, h, io, (double *)h->ws,
-                             h->ws_stride, MpcPhaseRollModel{R, model});
-      return launch_kernel(mpc_solve_kernel<STAGING, double, double, double, false, WARM, true>, grid, lds, s, h, io, (double *)h->ws, h->ws_stride, R);
+      return with_bool(model != nullptr, [&](auto model_build) {
+        constexpr bool STAGING = decltype(staging)::value, WARM = decltype(warm_build)::value, MODEL = decltype(model_build)::value;
+        return launch_kernel(mpc_solve_kernel<STAGING, double, double, double, false, WARM, true, MODEL>, grid, STAGING ? staging_lds_bytes<double>() : 0,
+                             s, h, io, (double *)h->ws, h->ws_stride, phase_of<true, WARM, MODEL>(T, wc, roll, {model, ld}));
+      });
     });
   }));
   MPC_TRY(solve_end(h, io, s, rec, tp, false));
@@ -3022,7 +2874,7 @@ extern "C" int mpc_solve_batch_host_warm(MpcHandle *h, int64_t B, int64_t ld, co
                                          const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts,
                                          double *out, double *traj, int32_t *status, int32_t *iters) {
   WarmIO hw{warm_in, warm_status, warm_out, ld_warm, {}};
-  MPC_TRY(warm_check(h, opts, &hw.opts));
+  MPC_TRY(warm_check(h, opts, &hw.wopts));
   return solve_host<double>(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters, &hw);
 }
 
@@ -3034,7 +2886,7 @@ extern "C" int mpc_solve_batch_host_warm_model(MpcHandle *h, int64_t B, int64_t 
     return mpc_solve_batch_host_warm(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, warm_in, warm_status, warm_out, ld_warm, opts, out, traj,
                                      status, iters);
   WarmIO hw{warm_in, warm_status, warm_out, ld_warm, {}};
-  MPC_TRY(warm_model_check(h, opts, &hw.opts));
+  MPC_TRY(warm_model_check(h, opts, &hw.wopts));
   return solve_host<double>(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters, &hw, model);
 }
 

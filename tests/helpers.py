@@ -2,6 +2,7 @@
 import ctypes as C
 import json
 import os
+import subprocess
 
 import numpy as np
 
@@ -77,6 +78,13 @@ F32PURE_TOL_COST_REL = 1e-4
 
 def vp(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def load_twin():
+    """The TEST-ONLY CPU build of the device headers, tests/host_twin: one library for every twin_* helper of the test suite."""
+    d = os.path.join(ROOT, "tests", "host_twin")
+    subprocess.check_call(["make", "-s", "-C", d])
+    return C.CDLL(os.path.join(d, "libhost_twin.so"))
 
 
 def twin_solve(twin, params, batch, weights=None, want_traj=True):

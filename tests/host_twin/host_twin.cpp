@@ -24,9 +24,7 @@ static int twin_solve(const MpcParams *p, int64_t B, int64_t ld, const R *state,
   for (int64_t i = 0; i < B; i++) {
     R st[6], cf[MPC_NCOEF], w[MPC_NW], o9[9];
     std::vector<R> tr(2 * N);
-    for (int q = 0; q < 6; q++) st[q] = state[q * ld + i];
-    for (int q = 0; q < MPC_NCOEF; q++) cf[q] = coeffs[q * ld + i];
-    for (int q = 0; q < MPC_NW; q++) w[q] = weights ? weights[q * ld + i] : (R)p->weights[q];
+    mpc::gather_instance(*p, i, ld, state, coeffs, weights, st, cf, w);
     mpc::HostWorkspace<R> ws{wsbuf.data()};
     int it = 0;
     int s = mpc::solve_instance<mpc::HostWorkspace<R>, R>(*p, ws, st, cf, yaw_lo[i], yaw_hi[i], w, o9, traj ? tr.data() : nullptr, &it);
@@ -63,21 +61,13 @@ extern "C" void mpc_host_twin_math2(int64_t n, const double *x, double *at, doub
 }
 
 /* MPC::run pre/post-processing of the device header, one instance at a time (struct-of-arrays I/O like the ABI):
- * pose[6][ld], pts[npts][ld] in/out, pre[15][ld] = state6 coeffs5 yaw_lo yaw_hi max_yaw_change target_speed */
+ * pose[6][ld], pts[npts][ld] in/out, pre[RUN_PRE_ROWS][ld] (the rows: mpc_run_core.h) */
 extern "C" int mpc_host_twin_run_pre(const MpcParams *p, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx,
                                      double *ptsy, double *pre, int32_t *ncoef) {
   if (npts < 3 || npts > mpc::RUN_MAX_PTS) return MPC_ERR_INVALID;
   for (int64_t i = 0; i < B; i++) {
-    double po[6], px[mpc::RUN_MAX_PTS] = {0}, py[mpc::RUN_MAX_PTS] = {0};
-    for (int q = 0; q < 6; q++) po[q] = pose[q * ld + i];
-    for (int q = 0; q < npts; q++) { px[q] = ptsx[q * ld + i]; py[q] = ptsy[q * ld + i]; }
-    mpc::RunPre R;
-    mpc::run_pre(*p, po, px, py, npts, R);
-    for (int q = 0; q < npts; q++) { ptsx[q * ld + i] = px[q]; ptsy[q * ld + i] = py[q]; }
-    for (int q = 0; q < 6; q++) pre[q * ld + i] = R.state[q];
-    for (int q = 0; q < 5; q++) pre[(6 + q) * ld + i] = R.coef[q];
-    pre[11 * ld + i] = R.yaw_lo; pre[12 * ld + i] = R.yaw_hi; pre[13 * ld + i] = R.max_yaw_change; pre[14 * ld + i] = R.target_speed;
-    if (ncoef) ncoef[i] = R.ncoef;
+    const int nc = mpc::run_pre_instance<false>(*p, *p, i, ld, npts, pose, 0.0, ptsx, ptsy, pre, ld);
+    if (ncoef) ncoef[i] = nc;
   }
   return MPC_OK;
 }
@@ -109,9 +99,7 @@ static int solve_parked_t(const MpcParams *p, int64_t B, int64_t ld, int pass_cu
   for (int64_t i = 0; i < B; i++) {
     R st[6], cf[MPC_NCOEF], w[MPC_NW];
     double park[SV::PARK_N];
-    for (int q = 0; q < 6; q++) st[q] = state[q * ld + i];
-    for (int q = 0; q < MPC_NCOEF; q++) cf[q] = coeffs[q * ld + i];
-    for (int q = 0; q < MPC_NW; q++) w[q] = weights ? weights[q * ld + i] : (R)p->weights[q];
+    mpc::gather_instance(*p, i, ld, state, coeffs, weights, st, cf, w);
     SV A(*p, mpc::HostWorkspace<R>{wsA.data()});
     int s = A.setup(st, cf, yaw_lo[i], yaw_hi[i], w), attempt = 0, it_total = 0, passes = 0;
     SV *fin = &A;
@@ -293,9 +281,7 @@ static int traffic_t(const MpcParams *p, int64_t B, int64_t ld, const R *state, 
   std::vector<R> wsbuf((size_t)mpc::workspace_fields_per_instance(p->N, sizeof(R) == 4, true));
   for (int64_t i = 0; i < B; i++) {
     R st[6], cf[MPC_NCOEF], w[MPC_NW];
-    for (int q = 0; q < 6; q++) st[q] = state[q * ld + i];
-    for (int q = 0; q < MPC_NCOEF; q++) cf[q] = coeffs[q * ld + i];
-    for (int q = 0; q < MPC_NW; q++) w[q] = weights ? weights[q * ld + i] : (R)p->weights[q];
+    mpc::gather_instance(*p, i, ld, state, coeffs, weights, st, cf, w);
     TrafficCount c;
     SV S(*p, WS(wsbuf.data(), &c));
     int s = S.setup(st, cf, yaw_lo[i], yaw_hi[i], w), attempt = 0, it_total = 0;

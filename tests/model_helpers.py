@@ -1,24 +1,17 @@
-"""Helpers of the per-instance model tests (test infrastructure): the TEST-ONLY CPU build tests/model_twin, the population both test
+"""Helpers of the per-instance model tests (test infrastructure): the TEST-ONLY CPU build (mpc_twin_solve of tests/host_twin), the population both test
 files use, and the oracle solving every instance with its own OrcConfig -- the yardstick of these tests."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 import oracle_lib as O
-from helpers import ROOT, TOL_ACCEL, TOL_STEER, TOL_TRAJ, vp
+from helpers import TOL_ACCEL, TOL_STEER, TOL_TRAJ, load_twin, vp
 
 MODEL_FIELDS = ("dt", "Lf", "max_steering", "max_acceleration", "max_deceleration", "max_speed")   # rows of a model array
 INFEASIBLE = 3   # MPC_STATUS_INFEASIBLE
 
 
-def load_model_twin():
-    d = os.path.join(ROOT, "tests", "model_twin")
-    subprocess.check_call(["make", "-s", "-C", d])
-    L = C.CDLL(os.path.join(d, "libmodel_twin.so"))
-    L.mpc_model_twin_solve.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 10
-    return L
+load_model_twin = load_twin
 
 
 def draw_rows(params, B, seed=5, dts=(0.05, 0.08, 0.1, 0.15)):
@@ -49,8 +42,8 @@ def twin_model_solve(twin, params, batch, model, weights=None, want_traj=True):
     out = np.zeros((9, B)); traj = np.zeros((2 * params.N, B)) if want_traj else None
     status = np.zeros(B, dtype=np.int32); iters = np.zeros(B, dtype=np.int32)
     w = f(weights) if weights is not None else None
-    rc = twin.mpc_model_twin_solve(C.byref(params), B, B, vp(st), vp(cf), vp(yl), vp(yh), vp(w), vp(md), vp(out), vp(traj), vp(status),
-                                   vp(iters))
+    rc = twin.mpc_twin_solve(C.byref(params), C.c_int64(B), C.c_int64(B), vp(st), vp(cf), vp(yl), vp(yh), vp(w), vp(md), None, None, None,
+                             C.c_int64(0), None, C.c_int(0), vp(out), vp(traj), vp(status), vp(iters))
     assert rc == 0
     return {"out": out, "traj": traj, "status": status, "iters": iters}
 

@@ -1,23 +1,18 @@
 """Helpers of the tests of warm starts and closed loops with per-instance model values (test infrastructure): the TEST-ONLY CPU build
-tests/model_loop_twin, the loops both test files run, and the oracle's own cold loop of one car with its own OrcConfig."""
+(mpc_twin_solve and mpc_twin_rollout of tests/host_twin), the loops both test files run, and the oracle's own cold loop of one car with its own OrcConfig."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 import oracle_lib as O
-from helpers import ROOT, TOL_ACCEL, TOL_STEER, TOL_TRAJ, vp
+from helpers import TOL_ACCEL, TOL_STEER, TOL_TRAJ, load_twin, vp
 from model_helpers import MODEL_FIELDS
 
 MODES = {"cold": (False, {}), "warm": (True, {}), "warm_shift1": (True, {"shift": 1})}
 WARM_REC = 22
 
 
-def load_model_loop_twin():
-    d = os.path.join(ROOT, "tests", "model_loop_twin")
-    subprocess.check_call(["make", "-s", "-C", d])
-    return C.CDLL(os.path.join(d, "libmodel_loop_twin.so"))
+load_model_loop_twin = load_twin
 
 
 def twin_warm_model_solve(twin, params, batch, model, opts, warm=None, warm_status=None, inplace=False, weights=None, want_traj=False):
@@ -39,8 +34,8 @@ def twin_warm_model_solve(twin, params, batch, model, opts, warm=None, warm_stat
     elif warm_status is not None:
         warm_status = np.ascontiguousarray(warm_status, dtype=np.int32)
     w = f(weights) if weights is not None else None
-    rc = twin.mpc_model_loop_twin_solve(C.byref(params), C.c_int64(B), C.c_int64(B), vp(st), vp(cf), vp(yl), vp(yh), vp(w), vp(md), vp(warm),
-                                        vp(warm_status), vp(wout), C.c_int64(B), C.byref(opts), vp(out), vp(traj), vp(status), vp(iters))
+    rc = twin.mpc_twin_solve(C.byref(params), C.c_int64(B), C.c_int64(B), vp(st), vp(cf), vp(yl), vp(yh), vp(w), vp(md), vp(warm),
+                             vp(warm_status), vp(wout), C.c_int64(B), C.byref(opts), C.c_int(0), vp(out), vp(traj), vp(status), vp(iters))
     assert rc == 0
     return {"out": out, "traj": traj, "status": status, "iters": iters, "warm": wout}
 
@@ -72,8 +67,8 @@ def twin_model_rollout(twin, params, sc, model, steps, opts, warm_start, weights
     w = f(weights) if weights is not None else None
     hist = np.zeros((steps, 9, B)); status = np.full(B, -99, dtype=np.int32); iters = np.full(B, -99, dtype=np.int32)
     sst = np.zeros((steps, B), dtype=np.int32); sit = np.zeros((steps, B), dtype=np.int32)
-    rc = twin.mpc_model_loop_twin_rollout(C.byref(params), C.c_int64(B), C.c_int64(B), C.c_int(steps), vp(st), vp(cf), vp(yl), vp(yh), vp(w),
-                                          vp(md), C.c_int(1 if warm_start else 0), C.byref(opts), vp(hist), vp(status), vp(iters), vp(sst), vp(sit))
+    rc = twin.mpc_twin_rollout(C.byref(params), C.c_int64(B), C.c_int64(B), C.c_int(steps), vp(st), vp(cf), vp(yl), vp(yh), vp(w),
+                               vp(md), C.c_int(1 if warm_start else 0), C.byref(opts), vp(hist), vp(status), vp(iters), vp(sst), vp(sit))
     assert rc == 0
     return {"hist": hist, "state": st, "status": status, "iters": iters, "step_status": sst, "step_iters": sit}
 

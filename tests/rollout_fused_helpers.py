@@ -1,17 +1,12 @@
-"""Helpers of the fused-rollout tests (test infrastructure): the TEST-ONLY CPU build of one car's whole loop (tests/rollout_twin)."""
+"""Helpers of the fused-rollout tests (test infrastructure): the TEST-ONLY CPU build of one car's whole loop (mpc_twin_rollout of
+tests/host_twin)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-from helpers import ROOT, vp
+from helpers import load_twin, vp
 
-
-def load_rollout_twin():
-    d = os.path.join(ROOT, "tests", "rollout_twin")
-    subprocess.check_call(["make", "-s", "-C", d])
-    return C.CDLL(os.path.join(d, "librollout_twin.so"))
+load_rollout_twin = load_twin
 
 
 def twin_rollout(twin, params, sc, steps, opts, warm_start, weights=None):
@@ -23,7 +18,7 @@ def twin_rollout(twin, params, sc, steps, opts, warm_start, weights=None):
     w = f(weights) if weights is not None else None
     hist = np.zeros((steps, 9, B)); status = np.full(B, -99, dtype=np.int32); iters = np.full(B, -99, dtype=np.int32)
     sst = np.zeros((steps, B), dtype=np.int32); sit = np.zeros((steps, B), dtype=np.int32)
-    rc = twin.mpc_rollout_twin(C.byref(params), C.c_int64(B), C.c_int64(B), C.c_int(steps), vp(st), vp(cf), vp(yl), vp(yh), vp(w),
-                               C.c_int(1 if warm_start else 0), C.byref(opts), vp(hist), vp(status), vp(iters), vp(sst), vp(sit))
+    rc = twin.mpc_twin_rollout(C.byref(params), C.c_int64(B), C.c_int64(B), C.c_int(steps), vp(st), vp(cf), vp(yl), vp(yh), vp(w),
+                               None, C.c_int(1 if warm_start else 0), C.byref(opts), vp(hist), vp(status), vp(iters), vp(sst), vp(sit))
     assert rc == 0
     return {"hist": hist, "state": st, "status": status, "iters": iters, "step_status": sst, "step_iters": sit}

@@ -1,14 +1,12 @@
 """Helpers of the tests of run() and the telemetry handler with per-instance model values (test infrastructure): the TEST-ONLY CPU
-build tests/run_model_twin, the stated population -- 48 lake-track cars, each with a column of its own --, and the oracle's mpc_run /
+build (mpc_twin_run of tests/host_twin), the stated population -- 48 lake-track cars, each with a column of its own --, and the oracle's mpc_run /
 telemetry_handler with a per-car OrcConfig: the yardstick of these tests."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 import oracle_lib as O
-from helpers import ROOT, TOL_ACCEL, TOL_STEER, TOL_TRAJ, vp
+from helpers import TOL_ACCEL, TOL_STEER, TOL_TRAJ, load_twin, vp
 from model_helpers import MODEL_FIELDS, draw_rows
 
 NPTS = 6
@@ -18,10 +16,7 @@ EXTRA_LATENCY = 0.02
 INFEASIBLE = 3               # MPC_STATUS_INFEASIBLE
 
 
-def load_run_model_twin():
-    d = os.path.join(ROOT, "tests", "run_model_twin")
-    subprocess.check_call(["make", "-s", "-C", d])
-    return C.CDLL(os.path.join(d, "librun_model_twin.so"))
+load_run_model_twin = load_twin
 
 
 def fleet(pkg, params, waypoints, B=FLEET_B):
@@ -42,7 +37,7 @@ def uniform_model(params, B):
 
 
 def twin_run_model(twin, params, pose, ptsx, ptsy, model, opts, warm=None, warm_status=None, tel=False, extra=0.0):
-    """tests/run_model_twin with the arguments of mpc_run_batch_host_warm_model (tel: of mpc_telemetry_batch_host_warm_model, `pose` =
+    """mpc_twin_run with the arguments of mpc_run_batch_host_warm_model (tel: of mpc_telemetry_batch_host_warm_model, `pose` =
     the telemetry rows) -> out8, cmd, status, iters, pre, warm and the vehicle-frame waypoints."""
     f = lambda a: np.ascontiguousarray(a, dtype=np.float64)
     pose, px, py, md = f(pose), f(ptsx).copy(), f(ptsy).copy(), f(model)
@@ -56,9 +51,9 @@ def twin_run_model(twin, params, pose, ptsx, ptsy, model, opts, warm=None, warm_
         assert warm.shape == (rows, B)
     if warm_status is not None:
         warm_status = np.ascontiguousarray(warm_status, dtype=np.int32)
-    rc = twin.mpc_run_model_twin_run(C.byref(params), C.c_int64(B), C.c_int64(B), C.c_int(npts), vp(pose), C.c_int(1 if tel else 0), C.c_double(extra),
-                                     vp(px), vp(py), vp(md), vp(warm), vp(warm_status), vp(wout), C.c_int64(B), C.byref(opts), vp(out8), vp(cmd),
-                                     vp(status), vp(iters), vp(pre))
+    rc = twin.mpc_twin_run(C.byref(params), C.c_int64(B), C.c_int64(B), C.c_int(npts), vp(pose), C.c_int(1 if tel else 0), C.c_double(extra),
+                           vp(px), vp(py), vp(md), vp(warm), vp(warm_status), vp(wout), C.c_int64(B), C.byref(opts), vp(out8), vp(cmd),
+                           vp(status), vp(iters), vp(pre))
     assert rc == 0
     return {"out8": out8, "cmd": cmd, "status": status, "iters": iters, "pre": pre, "warm": wout, "ptsx": px, "ptsy": py}
 

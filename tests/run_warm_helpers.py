@@ -1,4 +1,4 @@
-"""Helpers of the run()-path warm-start tests (test infrastructure): the TEST-ONLY CPU build tests/run_warm_twin, the closed
+"""Helpers of the run()-path warm-start tests (test infrastructure): the TEST-ONLY CPU build (mpc_twin_run and mpc_twin_solve of tests/host_twin), the closed
 loop of a telemetry handler (window rule, ideal plant) that both test files and the tools drive, and the oracle's cold mpc_run on
 every step's instance -- the comparison is solve by solve, so loop amplification and window flips cannot enter."""
 import ctypes as C
@@ -8,15 +8,10 @@ import subprocess
 import numpy as np
 
 import oracle_lib as O
-from helpers import ROOT, vp
+from helpers import ROOT, load_twin, vp
 
 NPTS = 6
-
-
-def load_run_warm_twin():
-    d = os.path.join(ROOT, "tests", "run_warm_twin")
-    subprocess.check_call(["make", "-s", "-C", d])
-    return C.CDLL(os.path.join(d, "librun_warm_twin.so"))
+load_run_warm_twin = load_twin
 
 
 def pick_window(wp, x, y, npts=NPTS):
@@ -41,10 +36,10 @@ def plant(pose, out8, max_steering):
 
 
 def twin_run(twin, params, pose, ptsx, ptsy, opts, warm=None, warm_status=None, tel=False, extra=0.0):
-    """tests/run_warm_twin with the arguments of mpc_run_batch_host_warm (tel: of mpc_telemetry_batch_host_warm, `pose` = the
+    """mpc_twin_run without per-instance model values, with the arguments of mpc_run_batch_host_warm (tel: of mpc_telemetry_batch_host_warm, `pose` = the
     telemetry rows) -> out8, cmd, status, iters, pre, warm."""
     f = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-    pose, px, py = f(pose), f(ptsx), f(ptsy)
+    pose, px, py = f(pose), f(ptsx).copy(), f(ptsy).copy()          # (the waypoints are transformed in place: the caller keeps its own)
     B, npts = pose.shape[1], px.shape[0]
     rows = (params.N - 1) * 22
     out8 = np.zeros((8, B)); cmd = np.zeros((2, B)); pre = np.zeros((15, B)); status = np.zeros(B, dtype=np.int32); iters = np.zeros(B, dtype=np.int32)
@@ -54,9 +49,9 @@ def twin_run(twin, params, pose, ptsx, ptsy, opts, warm=None, warm_status=None, 
         assert warm.shape == (rows, B)
     if warm_status is not None:
         warm_status = np.ascontiguousarray(warm_status, dtype=np.int32)
-    rc = twin.mpc_run_warm_twin_run(C.byref(params), C.c_int64(B), C.c_int64(B), C.c_int(npts), vp(pose), C.c_int(1 if tel else 0), C.c_double(extra),
-                                    vp(px), vp(py), vp(warm), vp(warm_status), vp(wout), C.c_int64(B), C.byref(opts), vp(out8), vp(cmd), vp(status),
-                                    vp(iters), vp(pre))
+    rc = twin.mpc_twin_run(C.byref(params), C.c_int64(B), C.c_int64(B), C.c_int(npts), vp(pose), C.c_int(1 if tel else 0), C.c_double(extra),
+                           vp(px), vp(py), None, vp(warm), vp(warm_status), vp(wout), C.c_int64(B), C.byref(opts), vp(out8), vp(cmd), vp(status),
+                           vp(iters), vp(pre))
     assert rc == 0
     return {"out8": out8, "cmd": cmd, "status": status, "iters": iters, "pre": pre, "warm": wout}
 
@@ -73,8 +68,8 @@ def twin_solve_box(twin, params, batch, opts, psi_box, warm=None, warm_status=No
         warm = f(warm)
     if warm_status is not None:
         warm_status = np.ascontiguousarray(warm_status, dtype=np.int32)
-    rc = twin.mpc_run_warm_twin_solve(C.byref(params), C.c_int64(B), C.c_int64(B), vp(st), vp(cf), vp(yl), vp(yh), C.c_int(1 if psi_box else 0), vp(warm),
-                                      vp(warm_status), vp(wout), C.c_int64(B), C.byref(opts), vp(out), vp(status), vp(iters))
+    rc = twin.mpc_twin_solve(C.byref(params), C.c_int64(B), C.c_int64(B), vp(st), vp(cf), vp(yl), vp(yh), None, None, vp(warm), vp(warm_status),
+                             vp(wout), C.c_int64(B), C.byref(opts), C.c_int(1 if psi_box else 0), vp(out), None, vp(status), vp(iters))
     assert rc == 0
     return {"out": out, "status": status, "iters": iters, "warm": wout}
 

@@ -1,6 +1,6 @@
 """Per-instance model values on the device (mpc_solve_batch_device_model, mpc_solve_batch_host_model, mpc_rollout_batch_device_model):
 the MODEL builds of the lane kernel against the oracle solving every instance with its own OrcConfig, against the CPU build of the
-same header (tests/model_twin) and against the plain entry points."""
+same header (tests/host_twin, mpc_twin_solve) and against the plain entry points."""
 import ctypes as C
 import os
 

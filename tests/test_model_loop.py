@@ -1,5 +1,5 @@
 """Warm starts and closed loops with per-instance model values (include/mpc_amd.h: mpc_solve_batch_*_warm_model,
-mpc_rollout_batch_device_warm_model, mpc_rollout_batch_device_fused_model), checked without a GPU: the CPU build tests/model_loop_twin
+mpc_rollout_batch_device_warm_model, mpc_rollout_batch_device_fused_model), checked without a GPU: the CPU build tests/host_twin (mpc_twin_solve / mpc_twin_rollout)
 calls the same Solver::setup_model / solve_warm / warm_store / unpack_model and mpc::RolloutCar as the WARM+MODEL and ROLL+MODEL builds
 of the lane kernel.  Yardsticks: the plain twins (uniform rows), the cold loop, and the oracle's own cold loop with one OrcConfig per
 car."""
@@ -22,7 +22,7 @@ CARS, STEPS = 193, 8
 
 @pytest.fixture(scope="module")
 def twin():
-    """TEST-ONLY CPU build of the warm model solve and the car-by-car model loop (tests/model_loop_twin)."""
+    """TEST-ONLY CPU build of the warm model solve and the car-by-car model loop (tests/host_twin, mpc_twin_solve / mpc_twin_rollout)."""
     return load_model_loop_twin()
 
 
@@ -87,7 +87,7 @@ def test_abi(pkg):
 
 @pytest.mark.parametrize("mode", list(MODES))
 def test_uniform_rows_are_the_plain_twins_bitwise(pkg, twin, fast, pop, mode):
-    """Rows equal to the handle's values: the car-by-car model loop is tests/rollout_twin and the closed loop of tests/warm_twin --
+    """Rows equal to the handle's values: the car-by-car model loop is tests/host_twin (mpc_twin_rollout) and the closed loop of tests/host_twin (mpc_twin_solve) --
     hist, state and every solve's status and iterations."""
     b, _ = pop
     warm_start, o = MODES[mode]

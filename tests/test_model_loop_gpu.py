@@ -1,7 +1,7 @@
 """Warm starts and closed loops with per-instance model values on the device (mpc_solve_batch_device_warm_model, _host_warm_model,
 mpc_rollout_batch_device_warm_model, mpc_rollout_batch_device_fused_model): the WARM+MODEL and ROLL+MODEL builds of the lane kernel
 against the cold model entry points, the oracle solving every instance with its own OrcConfig, the CPU build of the same header
-(tests/model_loop_twin) and the stepwise loops the fused call stands for.  Every output array holds sentinels before a call."""
+(tests/host_twin, mpc_twin_solve / mpc_twin_rollout) and the stepwise loops the fused call stands for.  Every output array holds sentinels before a call."""
 import ctypes as C
 import os
 

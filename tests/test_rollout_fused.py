@@ -1,6 +1,6 @@
 """The fused rollout (mpc_rollout_batch_device_fused) checked without a GPU: the rule one car follows between two of its solves
-(mpc::RolloutCar, csrc/mpc_core.h), run car by car by the CPU build tests/rollout_twin, against the step-by-step closed loops of
-tests/warm_twin; and the two symbols of the C ABI."""
+(mpc::RolloutCar, csrc/mpc_core.h), run car by car by the CPU build tests/host_twin (mpc_twin_rollout), against the step-by-step closed loops of
+tests/host_twin (mpc_twin_solve); and the two symbols of the C ABI."""
 import ctypes as C
 import os
 import re

@@ -1,7 +1,7 @@
-"""run() and the telemetry handler with per-instance model values, on the CPU: tests/run_model_twin -- the templated run_pre /
+"""run() and the telemetry handler with per-instance model values, on the CPU: tests/host_twin (mpc_twin_run) -- the templated run_pre /
 telemetry_to_pose / run_post / command_from_run of csrc/mpc_run_core.h around Solver::setup_model / solve_warm / unpack_model, built
 with g++ -- against the oracle's mpc_run / telemetry_handler with a per-car OrcConfig on the stated population (48 lake-track cars,
-seed 77, the columns of draw_rows seed 9), against tests/run_warm_twin for columns that repeat the handle's values, and on columns
+seed 77, the columns of draw_rows seed 9), against tests/host_twin (mpc_twin_run without a model array) for columns that repeat the handle's values, and on columns
 that cannot be used."""
 import os
 
@@ -51,7 +51,7 @@ def test_twin_follows_the_oracle_with_a_config_per_car(pkg, twin, golden_dir, wa
 
 @pytest.mark.parametrize("tel", [False, True])
 def test_uniform_columns_are_the_run_warm_twin_bitwise(pkg, twin, warm_twin, golden_dir, waypoints, tel):
-    """every column the handle's own values: bitwise tests/run_warm_twin (the functions without a model argument), cold and warm"""
+    """every column the handle's own values: bitwise tests/host_twin (mpc_twin_run without a model array), cold and warm"""
     params = pkg.params_from_json(os.path.join(golden_dir, "config-fast.json"))
     F = fleet(pkg, params, waypoints)
     opts = pkg.warm_opts_default()

@@ -1,7 +1,7 @@
 """run() and the telemetry handler with per-instance model values on the device (mpc_run_batch_device_model, mpc_telemetry_batch_device_model,
 their _warm_model, _host_model and _host_warm_model forms, the two wire forms, run_torch / run_numpy / telemetry_torch with
 ``model``): the MODEL forms of the pre and post kernels around the wave kernels' MODEL builds (B <= wave_max_batch) or the lane
-kernel's, against the oracle with a per-car OrcConfig, against the CPU build of the same functions (tests/run_model_twin), and the two
+kernel's, against the oracle with a per-car OrcConfig, against the CPU build of the same functions (tests/host_twin, mpc_twin_run), and the two
 paths against each other bit for bit.  N = 10, six waypoints per car."""
 import ctypes as C
 import os

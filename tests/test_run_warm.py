@@ -1,5 +1,5 @@
 """Warm start of run() and the telemetry handler from the previous call (include/mpc_amd.h, "warm start on the run() path"), checked
-without a GPU: the CPU build tests/run_warm_twin runs mpc_run_core.h around Solver::solve_warm with the warm column read through
+without a GPU: the CPU build tests/host_twin (mpc_twin_run without a model array) runs mpc_run_core.h around Solver::solve_warm with the warm column read through
 mpc::WarmColumn, exactly what the kernels do.  The yardstick is the oracle's COLD mpc_run on every step's own instance (pose and
 window as the loop under test met them), solve by solve."""
 import os
@@ -18,7 +18,7 @@ POPULATIONS = (("config-fast.json", 96, 20), ("config-stable.json", 64, 12))
 
 @pytest.fixture(scope="module")
 def twin():
-    """TEST-ONLY CPU build of run() with the warm start (tests/run_warm_twin)."""
+    """TEST-ONLY CPU build of run() with the warm start (tests/host_twin, mpc_twin_run without a model array)."""
     return load_run_warm_twin()
 
 

@@ -1,7 +1,7 @@
 """Warm start on the run() path on the device (mpc_run_batch_device_warm / _host_warm, mpc_telemetry_batch_device_warm / _host_warm,
 mpc_wire_telemetry_batch_host_warm, lib/mpc_replay --warm, MPC::run with setWarmStart): the warm wave kernel and the WARM build of
 the lane kernel, the warm column read through mpc::WarmColumn, against the oracle's cold mpc_run on every step's own instance and
-against the CPU build of the same functions (tests/run_warm_twin)."""
+against the CPU build of the same functions (tests/host_twin, mpc_twin_run without a model array)."""
 import ctypes as C
 import json
 import os

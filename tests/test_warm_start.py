@@ -1,4 +1,4 @@
-"""Warm start of the device solver (include/mpc_amd.h, "warm start"), checked without a GPU: the CPU build tests/warm_twin calls the
+"""Warm start of the device solver (include/mpc_amd.h, "warm start"), checked without a GPU: the CPU build tests/host_twin (mpc_twin_solve) calls the
 same Solver::warm_point / begin_warm / warm_store as the kernels.  The oracle's COLD solve is the yardstick throughout: a warm
 solve works on the same NLP (branch outcomes and objective scaling decided at the reference's start point) from another initial
 iterate."""
@@ -17,7 +17,7 @@ from warm_helpers import garbage_warm, golden_batches, load_warm_twin, twin_clos
 
 @pytest.fixture(scope="module")
 def warm_twin():
-    """TEST-ONLY CPU build of the warm start (tests/warm_twin)."""
+    """TEST-ONLY CPU build of the warm start (tests/host_twin, mpc_twin_solve)."""
     return load_warm_twin()
 
 

@@ -1,5 +1,5 @@
 """Warm start on the device (mpc_solve_batch_device_warm / _host_warm / mpc_rollout_batch_device_warm, MPC::setWarmStart): the WARM
-build of the lane kernel and the warm wave kernel against the CPU build of the same Solver functions (tests/warm_twin), the cold
+build of the lane kernel and the warm wave kernel against the CPU build of the same Solver functions (tests/host_twin, mpc_twin_solve), the cold
 entry points and the oracle's cold closed loops."""
 import ctypes as C
 import os

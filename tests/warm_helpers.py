@@ -1,18 +1,14 @@
-"""Helpers of the warm-start tests (test infrastructure): the TEST-ONLY CPU build of the warm start (tests/warm_twin) and the
-closed loops both test files run."""
+"""Helpers of the warm-start tests (test infrastructure): the TEST-ONLY CPU build of the warm start (mpc_twin_solve of
+tests/host_twin) and the closed loops both test files run."""
 import ctypes as C
 import os
 import subprocess
 
 import numpy as np
 
-from helpers import ROOT, vp
+from helpers import ROOT, load_twin, vp
 
-
-def load_warm_twin():
-    d = os.path.join(ROOT, "tests", "warm_twin")
-    subprocess.check_call(["make", "-s", "-C", d])
-    return C.CDLL(os.path.join(d, "libwarm_twin.so"))
+load_warm_twin = load_twin
 
 
 def twin_warm_solve(twin, params, batch, opts, warm=None, warm_status=None, want_warm=True, inplace=False):
@@ -31,8 +27,8 @@ def twin_warm_solve(twin, params, batch, opts, warm=None, warm_status=None, want
         status = warm_status
     elif warm_status is not None:
         warm_status = np.ascontiguousarray(warm_status, dtype=np.int32)
-    rc = twin.mpc_warm_twin_solve(C.byref(params), C.c_int64(B), C.c_int64(B), vp(st), vp(cf), vp(yl), vp(yh), None, vp(warm),
-                                  vp(warm_status), vp(wout), C.c_int64(B), C.byref(opts), vp(out), None, vp(status), vp(iters))
+    rc = twin.mpc_twin_solve(C.byref(params), C.c_int64(B), C.c_int64(B), vp(st), vp(cf), vp(yl), vp(yh), None, None, vp(warm),
+                             vp(warm_status), vp(wout), C.c_int64(B), C.byref(opts), C.c_int(0), vp(out), None, vp(status), vp(iters))
     assert rc == 0
     return {"out": out, "status": status, "iters": iters, "warm": wout}
 
