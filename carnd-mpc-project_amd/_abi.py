@@ -141,20 +141,10 @@ def library():
     L.mpc_destroy.restype = None
     L.mpc_last_error.restype = C.c_char_p
     L.mpc_abi_version.restype = C.c_int
-    L.mpc_solve_batch_device.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [DP] * 9 + [C.c_void_p]
-    L.mpc_solve_batch_host.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [DP] * 9
-    L.mpc_solve_batch_host_f32.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [DP] * 9
-    L.mpc_solve_batch_device_f32.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [DP] * 9 + [C.c_void_p]
     L.mpc_synchronize.argtypes = [C.c_void_p]
     L.mpc_get_stats.argtypes = [C.c_void_p, C.POINTER(MpcBatchStats)]
     L.mpc_debug_math.argtypes = [C.c_int, C.c_int64] + [C.c_void_p] * 4
     L.mpc_debug_math_ext.argtypes = [C.c_int, C.c_int64] + [C.c_void_p] * 6
-    L.mpc_run_batch_device.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 8 + [C.c_void_p]
-    L.mpc_run_batch_host.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [C.c_void_p] * 8
-    L.mpc_telemetry_batch_device.argtypes = ([C.c_void_p, C.c_int64, C.c_int64, C.c_int, DP, C.c_double] + [DP] * 5 +
-                                             [C.c_void_p])
-    L.mpc_rollout_batch_device.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 8 + [C.c_void_p]
-    L.mpc_telemetry_batch_host.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, DP, C.c_double] + [DP] * 4
     L.mpc_handle_device.argtypes = [C.c_void_p]
     L.mpc_inflight_advice.argtypes = [C.c_void_p, C.c_int64]
     L.mpc_inflight_advice.restype = C.c_int
@@ -170,55 +160,34 @@ def library():
     L.mpc_warm_rows.argtypes = [C.c_int]
     L.mpc_warm_rows.restype = C.c_int64
     L.mpc_warm_opts_default.argtypes = [C.POINTER(MpcWarmOpts)]
-    # handle, B, ld, state .. weights, warm_in, warm_status, warm_out, ld_warm, opts, out, traj, status, iters[, stream]
-    L.mpc_solve_batch_device_warm.argtypes = ([C.c_void_p, C.c_int64, C.c_int64] + [DP] * 8 + [C.c_int64, C.POINTER(MpcWarmOpts)] +
-                                              [DP] * 4 + [C.c_void_p])
-    L.mpc_solve_batch_host_warm.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [DP] * 8 + [C.c_int64, C.POINTER(MpcWarmOpts)] + [DP] * 4
-    L.mpc_rollout_batch_device_warm.argtypes = ([C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 5 + [C.POINTER(MpcWarmOpts)] +
-                                                [DP] * 3 + [C.c_void_p])
-    # handle, B, ld, steps, state .. weights, warm_start, opts, hist, status, iters, stream
-    L.mpc_rollout_batch_device_fused.argtypes = ([C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 5 + [C.c_int, C.POINTER(MpcWarmOpts)] +
-                                                 [DP] * 3 + [C.c_void_p])
     L.mpc_rollout_fused_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-    # the entry points without _model, with `model` behind `weights`
-    L.mpc_solve_batch_device_model.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [DP] * 10 + [C.c_void_p]
-    L.mpc_solve_batch_host_model.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [DP] * 10
-    L.mpc_rollout_batch_device_model.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 9 + [C.c_void_p]
-    # ... and the warm / fused ones likewise
-    L.mpc_solve_batch_device_warm_model.argtypes = ([C.c_void_p, C.c_int64, C.c_int64] + [DP] * 9 + [C.c_int64, C.POINTER(MpcWarmOpts)] +
-                                                    [DP] * 4 + [C.c_void_p])
-    L.mpc_solve_batch_host_warm_model.argtypes = ([C.c_void_p, C.c_int64, C.c_int64] + [DP] * 9 + [C.c_int64, C.POINTER(MpcWarmOpts)] +
-                                                  [DP] * 4)
-    L.mpc_rollout_batch_device_warm_model.argtypes = ([C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 6 + [C.POINTER(MpcWarmOpts)] +
-                                                      [DP] * 3 + [C.c_void_p])
-    L.mpc_rollout_batch_device_fused_model.argtypes = ([C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 6 +
-                                                       [C.c_int, C.POINTER(MpcWarmOpts)] + [DP] * 3 + [C.c_void_p])
-    # the run() path: the cold arguments up to ptsy, then warm_in, warm_status, warm_out, ld_warm, opts, then the cold outputs
-    WARM = [DP] * 3 + [C.c_int64, C.POINTER(MpcWarmOpts)]
-    L.mpc_run_batch_device_warm.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 3 + WARM + [DP] * 5 + [C.c_void_p]
-    L.mpc_run_batch_host_warm.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 3 + WARM + [DP] * 5
-    L.mpc_telemetry_batch_device_warm.argtypes = ([C.c_void_p, C.c_int64, C.c_int64, C.c_int, DP, C.c_double] + [DP] * 2 + WARM + [DP] * 3 +
-                                                  [C.c_void_p])
-    L.mpc_telemetry_batch_host_warm.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, DP, C.c_double] + [DP] * 2 + WARM + [DP] * 2
-    L.mpc_wire_telemetry_batch_host_warm.argtypes = [C.c_void_p, C.c_int64, C.POINTER(MpcWireTelemetry), DP, C.c_double] + WARM + [DP, DP]
-    # the run() path with per-instance model values: `model` directly behind ptsy (wire forms: behind extra_latency)
-    L.mpc_run_batch_device_model.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 9 + [C.c_void_p]
-    L.mpc_run_batch_host_model.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 9
-    L.mpc_telemetry_batch_device_model.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, DP, C.c_double] + [DP] * 6 + [C.c_void_p]
-    L.mpc_telemetry_batch_host_model.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, DP, C.c_double] + [DP] * 5
-    L.mpc_run_batch_device_warm_model.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 4 + WARM + [DP] * 5 + [C.c_void_p]
-    L.mpc_run_batch_host_warm_model.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [DP] * 4 + WARM + [DP] * 5
-    L.mpc_telemetry_batch_device_warm_model.argtypes = ([C.c_void_p, C.c_int64, C.c_int64, C.c_int, DP, C.c_double] + [DP] * 3 + WARM + [DP] * 3 +
-                                                        [C.c_void_p])
-    L.mpc_telemetry_batch_host_warm_model.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, DP, C.c_double] + [DP] * 3 + WARM + [DP] * 2
-    L.mpc_wire_telemetry_batch_host_model.argtypes = [C.c_void_p, C.c_int64, C.POINTER(MpcWireTelemetry), DP, C.c_double, DP, DP, DP]
-    L.mpc_wire_telemetry_batch_host_warm_model.argtypes = [C.c_void_p, C.c_int64, C.POINTER(MpcWireTelemetry), DP, C.c_double, DP] + WARM + [DP, DP]
+    # The batch entry points: one row per family -- (head, outs, stream or not) -- and the rule of include/mpc_amd.h for its four forms:
+    # _model puts `model` (one pointer) behind the head, _warm puts `warm` (warm_in, warm_status, warm_out, ld_warm, opts; the
+    # stepwise rollout: opts alone) behind that.  The fused rollout has two forms: its warm_start, opts pair leads its outs.
+    I64, OPTS = C.c_int64, C.POINTER(MpcWarmOpts)
+    H = [C.c_void_p, I64, I64]
+    WARM = [DP] * 3 + [I64, OPTS]
+    families = [("mpc_solve_batch_device", H + [DP] * 5, [DP] * 4, True, WARM),
+                ("mpc_solve_batch_host", H + [DP] * 5, [DP] * 4, False, WARM),
+                ("mpc_run_batch_device", H + [C.c_int] + [DP] * 3, [DP] * 5, True, WARM),
+                ("mpc_run_batch_host", H + [C.c_int] + [DP] * 3, [DP] * 5, False, WARM),
+                ("mpc_telemetry_batch_device", H + [C.c_int, DP, C.c_double] + [DP] * 2, [DP] * 3, True, WARM),
+                ("mpc_telemetry_batch_host", H + [C.c_int, DP, C.c_double] + [DP] * 2, [DP] * 2, False, WARM),
+                ("mpc_wire_telemetry_batch_host", [C.c_void_p, I64, C.POINTER(MpcWireTelemetry), DP, C.c_double], [DP] * 2, False, WARM),
+                ("mpc_rollout_batch_device", H + [C.c_int] + [DP] * 5, [DP] * 3, True, [OPTS]),
+                ("mpc_rollout_batch_device_fused", H + [C.c_int] + [DP] * 5, [C.c_int, OPTS] + [DP] * 3, True, None)]
+    for family, head, outs, stream, warm in families:
+        tail = outs + ([C.c_void_p] if stream else [])
+        for w_name, w in [("", [])] + ([("_warm", warm)] if warm else []):
+            for m_name, m in (("", []), ("_model", [DP])):
+                getattr(L, family + w_name + m_name).argtypes = head + m + w + tail
+    L.mpc_solve_batch_device_f32.argtypes = L.mpc_solve_batch_device.argtypes      # (the same pointers, to floats)
+    L.mpc_solve_batch_host_f32.argtypes = L.mpc_solve_batch_host.argtypes
     L.mpc_wire_parse.argtypes = [C.c_char_p, C.c_int64, C.POINTER(MpcWireTelemetry)]
     L.mpc_wire_format_steer.argtypes = [C.c_double, C.c_double, C.c_char_p, C.c_int64]
     L.mpc_wire_format_steer.restype = C.c_int64
     L.mpc_wire_format_manual.argtypes = [C.c_char_p, C.c_int64]
     L.mpc_wire_format_manual.restype = C.c_int64
-    L.mpc_wire_telemetry_batch_host.argtypes = [C.c_void_p, C.c_int64, C.POINTER(MpcWireTelemetry), DP, C.c_double, DP, DP]
     if L.mpc_abi_version() != ABI_VERSION:
         raise MpcError("ABI version mismatch between %s and the Python binding" % path)
     _lib = L

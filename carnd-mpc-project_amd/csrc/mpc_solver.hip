@@ -1907,13 +1907,22 @@ struct SolveIO {
   const R *state, *coeffs, *yaw_lo, *yaw_hi, *weights;
   R *out, *traj;
   int32_t *status, *iters;
-  const double *model = nullptr;   /* a model call (the mpc_*_model entry points, fp64 handles): [MPC_NMODEL][ld_model], see MpcModelPart */
-  int64_t ld_model = 0;            /* (its own: run() solves from the handle's rows at the handle's stride, the columns stay where the caller has them) */
-  bool model_wave = false;         /* a model call of the run() / telemetry entry points: the wave MODEL kernels up to wave_max_batch */
-  void set_model(const double *m, int64_t l, bool wave = false) { model = m; ld_model = l; model_wave = wave; }
 };
-/* ... and what a warm call brings on top: the warm buffers and the options in effect (warm_check), as the kernels take them */
+/* ... and what a warm call brings on top: the warm buffers and the options in effect, as the kernels take them */
 using WarmIO = mpc::WarmCall;
+/* What a call brings beyond its family's own arrays.  The entry points follow one rule (include/mpc_amd.h): the _model form puts
+ * `model` behind the family's inputs, the _warm form `warm_in, warm_status, warm_out, ld_warm, opts` behind that.  call_extras turns
+ * those arguments into this value and checks them against the handle; every family (the solve, run(), the telemetry handler, the
+ * rollouts; device and host arrays) takes one and serves the four forms with it. */
+struct CallExtras {
+  int refused = MPC_OK;            /* call_extras' verdict, its text in g_last_error: a family returns it before it touches anything */
+  bool warm = false;               /* a warm call: a _warm form, whichever arrays it brings -- with none it still runs the WARM build */
+  WarmIO w{};                      /* ... its buffers and the options in effect */
+  const double *model = nullptr;   /* a model call (fp64 handles): [MPC_NMODEL][ld_model], see MpcModelPart */
+  int64_t ld_model = 0;            /* 0: the ld of the solve's inputs.  (run() sets its own: it solves from the handle's rows at the handle's stride, the columns stay where the caller has them) */
+  bool model_wave = false;         /* a model call of the run() / telemetry entry points: the wave MODEL kernels up to wave_max_batch */
+  const WarmIO *warm_io() const { return warm ? &w : nullptr; }
+};
 /* ... and where a deferring launch hands its stragglers: its batch's slot of the ring and its fresh queue */
 struct TailPlace {
   bool defer = false;
@@ -1934,6 +1943,22 @@ template <int V> using Int = std::integral_constant<int, V>;
 /* f(std::true_type) or f(std::false_type): a run-time switch as a template argument */
 template <class F>
 static int with_bool(bool b, F f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+/* f(soc, warm, model): the builds of an fp64 solve kernel, all six of them -- plain, SOC, WARM, MODEL, MODEL+SOC, MODEL+WARM.  A warm
+ * call has no SOC (call_extras refuses it on a handle with max_soc > 0), so there is no SOC+WARM build. */
+template <class F>
+static int with_build(bool soc, bool warm, bool model, F f) {
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  if (warm) return model ? f(no, yes, yes) : f(no, yes, no);
+  if (soc) return model ? f(yes, no, yes) : f(yes, no, no);
+  return model ? f(no, no, yes) : f(no, no, no);
+}
+/* the argument a kernel takes only in the builds with ON: (*p) or nothing, for std::apply */
+template <bool ON, class T>
+static auto arg_if(const T *p) {
+  if constexpr (ON) return std::make_tuple(*p);
+  else return std::tuple<>{};
+}
 
 /* Every phase's switches are off unless it sets them; the hand-over and compaction policies are the same for all */
 static MpcPhase phase_defaults(const MpcHandle *h, int64_t B) {
@@ -1965,23 +1990,24 @@ static int wave_lpi(const MpcHandle *h, int64_t B) {
 }
 
 /* The wave path: 64 / LPI instances per wavefront, each with its stage records in LDS (the SOC build: and its SOC records behind
- * them).  Plain, SOC (fp64, max_soc > 0) or warm (fp64); io.model: the MODEL builds of the three (fp64). */
+ * them).  fp64: the build with_build picks for (soc, warm, model.model); fp32: plain. */
 template <class R>
-static int launch_wave(MpcHandle *h, const SolveIO<R> &io, hipStream_t s, bool soc, const WarmIO *warm) {
+static int launch_wave(MpcHandle *h, const SolveIO<R> &io, hipStream_t s, bool soc, const WarmIO *warm, const MpcModelPart &model) {
   const size_t per = (size_t)mpc::workspace_fields_per_instance(h->params.N, sizeof(R) == 4, h->params.initial_state_rows != 0) * sizeof(R);
   auto go = [&](auto lpi) {
     constexpr int LPI = decltype(lpi)::value, G = 64 / LPI;
     const unsigned grid = (unsigned)((io.B + G - 1) / G);
     if constexpr (sizeof(R) == 8) {
-      const size_t per_soc = per + (size_t)mpc::soc_fields_per_instance(h->params.N) * sizeof(R);
-      const MpcModelPart wm{io.model, io.ld_model};
-      if (io.model && warm) return launch_kernel(mpc_solve_wave_kernel<R, LPI, false, true, true, WarmIO, MpcModelPart>, grid, G * per, s, h, io, *warm, wm);
-      if (io.model && soc) return launch_kernel(mpc_solve_wave_kernel<R, LPI, true, false, true, MpcModelPart>, grid, G * per_soc, s, h, io, wm);
-      if (io.model) return launch_kernel(mpc_solve_wave_kernel<R, LPI, false, false, true, MpcModelPart>, grid, G * per, s, h, io, wm);
-      if (warm) return launch_kernel(mpc_solve_wave_kernel<R, LPI, false, true, false, WarmIO>, grid, G * per, s, h, io, *warm);
-      if (soc) return launch_kernel(mpc_solve_wave_kernel<R, LPI, true>, grid, G * per_soc, s, h, io);
+      return with_build(soc, warm != nullptr, model.model != nullptr, [&](auto soc_build, auto warm_build, auto model_build) {
+        constexpr bool SOC = decltype(soc_build)::value, WARM = decltype(warm_build)::value, MODEL = decltype(model_build)::value;
+        const size_t lds = G * (per + (SOC ? (size_t)mpc::soc_fields_per_instance(h->params.N) * sizeof(R) : 0));
+        return std::apply([&](auto... extra) {
+          return launch_kernel(mpc_solve_wave_kernel<R, LPI, SOC, WARM, MODEL, decltype(extra)...>, grid, lds, s, h, io, extra...);
+        }, std::tuple_cat(arg_if<WARM>(warm), arg_if<MODEL>(&model)));
+      });
+    } else {
+      return launch_kernel(mpc_solve_wave_kernel<R, LPI>, grid, G * per, s, h, io);
     }
-    return launch_kernel(mpc_solve_wave_kernel<R, LPI>, grid, G * per, s, h, io);
   };
   switch (wave_lpi(h, io.B)) {
     case 16: return go(Int<16>{});
@@ -1990,13 +2016,13 @@ static int launch_wave(MpcHandle *h, const SolveIO<R> &io, hipStream_t s, bool s
   }
 }
 
-/* The lane kernel (an instance per lane; `ws`: the workspace of the phase).  single: the build that MPC_STAGING, max_soc on an fp64
- * handle, a warm call and a model call (io.model; with or without SOC) select.  The two phases of a mixed-precision solve are builds of their own: the fp32 solver, and the fp64
- * solver that takes its iterates from fp32 records -- whatever RIO, the type at the ABI, is. */
+/* The lane kernel (an instance per lane; `ws`: the workspace of the phase).  single: the build that MPC_STAGING and, on an fp64
+ * handle, with_build select: max_soc, a warm call, a model call (model.model).  The two phases of a mixed-precision solve are builds of
+ * their own: the fp32 solver, and the fp64 solver that takes its iterates from fp32 records -- whatever RIO, the type at the ABI, is. */
 enum class LaneBuild { single, mixed_f32, mixed_f64 };
 template <class RIO>
 static int launch_lanes(MpcHandle *h, LaneBuild build, const SolveIO<RIO> &io, hipStream_t s, void *ws, bool soc, const MpcPhase &T,
-                        const WarmIO *warm = nullptr) {
+                        const WarmIO *warm = nullptr, const MpcModelPart &model = {}) {
   const unsigned grid = (unsigned)((io.B + kBlock - 1) / kBlock);
   /* (r, rsrc: values of the solver's reals and of the reals its resumed iterates come in) */
   auto go = [&](auto staging, auto r, auto rsrc, auto soc_build, auto warm_build, int64_t tile_reals, auto model_build) {
@@ -2004,7 +2030,7 @@ static int launch_lanes(MpcHandle *h, LaneBuild build, const SolveIO<RIO> &io, h
     constexpr bool STAGING = decltype(staging)::value, WARM = decltype(warm_build)::value, MODEL = decltype(model_build)::value;
     return launch_kernel(mpc_solve_kernel<STAGING, R, RIO, decltype(rsrc), decltype(soc_build)::value, WARM, false, MODEL>, grid,
                          STAGING ? staging_lds_bytes<R>() : 0, s, h, io, (R *)ws, tile_reals,
-                         phase_of<false, WARM, MODEL>(T, warm ? *warm : WarmIO{}, {}, {io.model, io.ld_model}));
+                         phase_of<false, WARM, MODEL>(T, warm ? *warm : WarmIO{}, {}, model));
   };
   constexpr std::true_type yes{};
   constexpr std::false_type no{};
@@ -2012,12 +2038,12 @@ static int launch_lanes(MpcHandle *h, LaneBuild build, const SolveIO<RIO> &io, h
   if (build == LaneBuild::mixed_f64) return with_bool(soc, [&](auto soc_build) { return go(yes, double{}, float{}, soc_build, no, h->ws_stride_f64, no); });
   return with_bool(h->staging, [&](auto staging) {
     if constexpr (sizeof(RIO) == 8) {
-      if (io.model && warm) return go(staging, RIO{}, RIO{}, no, yes, h->ws_stride, yes);
-      if (io.model) return with_bool(soc, [&](auto soc_build) { return go(staging, RIO{}, RIO{}, soc_build, no, h->ws_stride, yes); });
-      if (warm) return go(staging, RIO{}, RIO{}, no, yes, h->ws_stride, no);
-      if (soc) return go(staging, RIO{}, RIO{}, yes, no, h->ws_stride, no);
+      return with_build(soc, warm != nullptr, model.model != nullptr, [&](auto soc_build, auto warm_build, auto model_build) {
+        return go(staging, RIO{}, RIO{}, soc_build, warm_build, h->ws_stride, model_build);
+      });
+    } else {
+      return go(staging, RIO{}, RIO{}, no, no, h->ws_stride, no);
     }
-    return go(staging, RIO{}, RIO{}, no, no, h->ws_stride, no);
   });
 }
 
@@ -2144,18 +2170,63 @@ static int solve_end(MpcHandle *h, const SolveIO<R> &io, hipStream_t s, MpcHandl
   return MPC_OK;
 }
 
-/* The launch, for every entry point.  with_stats: mpc_get_stats may ask about this call.  may_defer: the caller can wait for the
- * batch's stragglers (mpc_tail_wait).  may_order: the take order may be applied.  warm: a warm call (warm_check has passed: an
- * fp64 handle, not mixed, no SOC) -- a single phase of the WARM build, or the warm wave kernel; it never defers, cuts or orders.
- * call.model: a model call (model_check has passed: an fp64 handle) -- ONE launch of the MODEL build of the single-phase fp64 lane
+/* ---- warm start and per-instance model values: options of every call -------------------------------------------------------- */
+extern "C" int64_t mpc_warm_rows(int N) { return (N < 3 || N > MPC_MAX_N) ? (int64_t)MPC_ERR_INVALID : (int64_t)(N - 1) * MPC_WARM_REC; }
+
+extern "C" int mpc_warm_opts_default(MpcWarmOpts *o) {
+  if (!o) return MPC_ERR_INVALID;
+  memset(o, 0, sizeof(*o));
+  /* DESIGN.md section 6i has the grid these come from: the fewest iterations among the settings without a status difference or a
+   * fork against the oracle on either population -- the previous solution as it is, not moved on by a stage */
+  o->size = (int32_t)sizeof(MpcWarmOpts); o->shift = 0; o->mu_init = 1e-6; o->bound_push = 1e-6; o->duals = 0;
+  return MPC_OK;
+}
+
+/* What an entry point's model and warm arguments come to, checked before anything is touched -- in this order: the handle; which
+ * handles are accepted; no SOC for a warm call; the options.  `warm`: the call came through a _warm form (the fused rollout:
+ * warm_start != 0).  The model rule decides which handles a model call is accepted on, warm or not -- every fp64 handle, also one
+ * whose ordinary solve starts in fp32, because a model call is the single-phase fp64 launch on every handle; a warm call without
+ * model needs an fp64 handle that does not start in fp32.  A call with neither is checked for its handle only. */
+static CallExtras call_extras(const MpcHandle *h, const double *model = nullptr, bool warm = false, const double *warm_in = nullptr,
+                              const int32_t *warm_status = nullptr, double *warm_out = nullptr, int64_t ld_warm = 0,
+                              const MpcWarmOpts *opts = nullptr) {
+  CallExtras x;
+  x.warm = warm; x.model = model;
+  x.w = WarmIO{warm_in, warm_status, warm_out, ld_warm, {}, 0};
+  const auto refuse = [&x](int rc, const char *why) { g_last_error = why; x.refused = rc; return x; };
+  if (!h) return refuse(MPC_ERR_INVALID, "NULL handle");
+  const bool f64 = h->params.precision == MPC_PRECISION_F64;
+  if (model && !f64) return refuse(MPC_ERR_INVALID, "per-instance model values: fp64 handles only (this one was created with MPC_PRECISION_F32)");
+  if (!warm) return x;
+  if (!model && !f64) return refuse(MPC_ERR_INVALID, "warm start: fp64 handles only (this one was created with MPC_PRECISION_F32)");
+  if (!model && h->mixed)
+    return refuse(MPC_ERR_UNSUPPORTED, "warm start is not available on a handle whose solve starts in fp32 (two launches): create it with MpcParams.f64_f32_start = 0");
+  if (h->params.max_soc > 0) return refuse(MPC_ERR_UNSUPPORTED, "warm start is not available with the second-order correction: set MpcParams.max_soc = 0");
+  (void)mpc_warm_opts_default(&x.w.wopts);
+  if (opts) {
+    if (opts->size != (int32_t)sizeof(MpcWarmOpts)) return refuse(MPC_ERR_INVALID, "MpcWarmOpts.size mismatch (fill it with mpc_warm_opts_default)");
+    if ((opts->shift != 0 && opts->shift != 1) || (opts->duals != 0 && opts->duals != 1) || !(opts->mu_init > 0 && opts->mu_init <= 0.1) ||
+        !(opts->bound_push > 0 && opts->bound_push <= 1e-2))
+      return refuse(MPC_ERR_INVALID, "MpcWarmOpts: shift and duals are 0 or 1, 0 < mu_init <= 0.1, 0 < bound_push <= 1e-2");
+    x.w.wopts = *opts;
+  }
+  return x;
+}
+
+/* The launch, for every entry point.  flags: kStats -- mpc_get_stats may ask about this call; kDefer -- the caller can wait for the
+ * batch's stragglers (mpc_tail_wait); kOrder -- the take order may be applied.  x.warm: a warm call (an fp64 handle, no SOC; without
+ * model: not mixed) -- a single phase of the WARM build, or the warm wave kernel; it never defers, cuts or orders.
+ * x.model: a model call (an fp64 handle) -- ONE launch of the MODEL build of the single-phase fp64 lane
  * kernel on h->ws at every B, also on a handle whose ordinary solve starts in fp32 (on an fp64 handle h->ws has the fp64 layout):
- * no wave path, no mixed-precision launch, and it never defers, cuts or orders either.  warm and call.model together (warm_model_check
- * has passed: an fp64 handle, no SOC): the same one launch, of the WARM+MODEL build -- lane compaction included, as for a warm call.
- * call.model_wave (the run() / telemetry model entry points, where the small batch is the rule): up to wave_max_batch the one launch
+ * no wave path, no mixed-precision launch, and it never defers, cuts or orders either.  x.warm and x.model together: the same one
+ * launch, of the WARM+MODEL build -- lane compaction included, as for a warm call.
+ * x.model_wave (the run() / telemetry model entry points, where the small batch is the rule): up to wave_max_batch the one launch
  * is the wave kernel's MODEL build instead -- cold, SOC or warm, launch_wave's own choice of lanes per instance and LDS. */
+enum SolveFlag : unsigned { kStats = 1u, kDefer = 2u, kOrder = 4u };
 template <class R>
-static int launch_solve(MpcHandle *h, const SolveIO<R> &call, void *stream_, bool with_stats = true, bool may_defer = false,
-                        bool may_order = false, const WarmIO *warm = nullptr) {
+static int launch_solve(MpcHandle *h, const SolveIO<R> &call, void *stream_, unsigned flags, const CallExtras &x) {
+  MPC_TRY(x.refused);
+  const WarmIO *warm = x.warm_io();
   std::optional<DeviceGuard> guard;
   MpcHandle::BatchRec *rec = nullptr;
   MPC_TRY(solve_begin(h, call, warm, guard, &rec));
@@ -2164,18 +2235,19 @@ static int launch_solve(MpcHandle *h, const SolveIO<R> &call, void *stream_, boo
   if (!io.iters) io.iters = h->d_iters;
   const int64_t B = io.B;
   hipStream_t s = (hipStream_t)stream_;   /* NULL = HIP's default (null) stream, exactly as passed */
-  const bool model = io.model != nullptr;
-  if (warm || model) may_defer = may_order = false;
+  const MpcModelPart mp{x.model, x.ld_model ? x.ld_model : io.ld};
+  const bool model = x.model != nullptr;
+  const bool may_defer = (flags & kDefer) && !warm && !model, may_order = (flags & kOrder) && !warm && !model;
   /* MpcParams.max_soc > 0 on an fp64 handle: the SOC builds of the kernels (the mixed-precision launch decides for its fp64 phase
    * itself) */
   const bool soc = sizeof(R) == 8 && h->params.max_soc > 0;
-  const bool wave_path = (!model || io.model_wave) && h->wave_max_batch > 0 && B <= h->wave_max_batch;      /* (comes first: set_wave_limit decides which handles have it) */
+  const bool wave_path = (!model || x.model_wave) && h->wave_max_batch > 0 && B <= h->wave_max_batch;      /* (comes first: set_wave_limit decides which handles have it) */
   TailPlace tp;
   tp.defer = may_defer && h->params.tail_cut != 0 && B >= kTailMinBatch && !wave_path;
   if (tp.defer) MPC_TRY(tail_claim(h, s, tp));
   if (wave_path) {
     MPC_HIP_CHECK(hipEventRecord(h->ev0, s));
-    MPC_TRY(launch_wave(h, io, s, soc, warm));
+    MPC_TRY(launch_wave(h, io, s, soc, warm, mp));
   } else if (h->mixed && !model) {
     MPC_TRY(launch_mixed(h, io, s, tp));
   } else {
@@ -2222,89 +2294,34 @@ static int launch_solve(MpcHandle *h, const SolveIO<R> &call, void *stream_, boo
       if (n_cuts > 0) T.compact_gap = 0;     /* (a phase that parks keeps iterates in its columns) */
       tail_fields(h, tp, T);
       if (ordered) { T.ord_cnt = C.cb + kPhaseCounterInts; T.ord_list = h->d_take_list; T.ord_ld = S; }
-      MPC_TRY(launch_lanes(h, LaneBuild::single, io, s, wr ? h->ws2 : h->ws, soc, T, warm));
+      MPC_TRY(launch_lanes(h, LaneBuild::single, io, s, wr ? h->ws2 : h->ws, soc, T, warm, mp));
     }
   }
-  return solve_end(h, io, s, rec, tp, with_stats);
+  return solve_end(h, io, s, rec, tp, (flags & kStats) != 0);
 }
 
+/* The solve on device arrays, fp64: the four forms.  Only the plain one may defer its stragglers and apply the take order. */
 extern "C" int mpc_solve_batch_device(MpcHandle *h, int64_t B, int64_t ld, const double *state,
                                       const double *coeffs, const double *yaw_lo, const double *yaw_hi,
                                       const double *weights, double *out, double *traj, int32_t *status,
                                       int32_t *iters, void *stream_) {
-  return launch_solve<double>(h, {B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters}, stream_, true, true, true);
-}
-
-/* ---- per-instance model values -------------------------------------------------------------------------------------------- */
-/* what every model entry point checks before it touches anything (model != NULL) */
-static int model_check(const MpcHandle *h) {
-  if (!h) { g_last_error = "NULL handle"; return MPC_ERR_INVALID; }
-  if (h->params.precision != MPC_PRECISION_F64) { g_last_error = "per-instance model values: fp64 handles only (this one was created with MPC_PRECISION_F32)"; return MPC_ERR_INVALID; }
-  return MPC_OK;
+  return launch_solve<double>(h, {B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters}, stream_, kStats | kDefer | kOrder,
+                              call_extras(h));
 }
 
 extern "C" int mpc_solve_batch_device_model(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
                                             const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
                                             double *out, double *traj, int32_t *status, int32_t *iters, void *stream_) {
-  if (!model) return mpc_solve_batch_device(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters, stream_);
-  MPC_TRY(model_check(h));
-  SolveIO<double> io{B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters};
-  io.set_model(model, ld);
-  return launch_solve<double>(h, io, stream_, true, false, false);
-}
-
-/* ---- warm start ---------------------------------------------------------------------------------------------------------- */
-extern "C" int64_t mpc_warm_rows(int N) { return (N < 3 || N > MPC_MAX_N) ? (int64_t)MPC_ERR_INVALID : (int64_t)(N - 1) * MPC_WARM_REC; }
-
-extern "C" int mpc_warm_opts_default(MpcWarmOpts *o) {
-  if (!o) return MPC_ERR_INVALID;
-  memset(o, 0, sizeof(*o));
-  /* DESIGN.md section 6i has the grid these come from: the fewest iterations among the settings without a status difference or a
-   * fork against the oracle on either population -- the previous solution as it is, not moved on by a stage */
-  o->size = (int32_t)sizeof(MpcWarmOpts); o->shift = 0; o->mu_init = 1e-6; o->bound_push = 1e-6; o->duals = 0;
-  return MPC_OK;
-}
-
-/* the part of a warm entry point's checks that does not depend on how the handle solves: no SOC, and the options; *W: those in effect */
-static int warm_opts_check(MpcHandle *h, const MpcWarmOpts *opts, MpcWarmOpts *W) {
-  if (h->params.max_soc > 0) { g_last_error = "warm start is not available with the second-order correction: set MpcParams.max_soc = 0"; return MPC_ERR_UNSUPPORTED; }
-  (void)mpc_warm_opts_default(W);
-  if (opts) {
-    if (opts->size != (int32_t)sizeof(MpcWarmOpts)) { g_last_error = "MpcWarmOpts.size mismatch (fill it with mpc_warm_opts_default)"; return MPC_ERR_INVALID; }
-    if ((opts->shift != 0 && opts->shift != 1) || (opts->duals != 0 && opts->duals != 1) || !(opts->mu_init > 0 && opts->mu_init <= 0.1) ||
-        !(opts->bound_push > 0 && opts->bound_push <= 1e-2)) {
-      g_last_error = "MpcWarmOpts: shift and duals are 0 or 1, 0 < mu_init <= 0.1, 0 < bound_push <= 1e-2"; return MPC_ERR_INVALID;
-    }
-    *W = *opts;
-  }
-  return MPC_OK;
-}
-
-/* what every warm entry point checks before it touches anything; *W: the options in effect */
-static int warm_check(MpcHandle *h, const MpcWarmOpts *opts, MpcWarmOpts *W) {
-  if (!h) { g_last_error = "NULL handle"; return MPC_ERR_INVALID; }
-  if (h->params.precision != MPC_PRECISION_F64) { g_last_error = "warm start: fp64 handles only (this one was created with MPC_PRECISION_F32)"; return MPC_ERR_INVALID; }
-  if (h->mixed) {
-    g_last_error = "warm start is not available on a handle whose solve starts in fp32 (two launches): create it with MpcParams.f64_f32_start = 0";
-    return MPC_ERR_UNSUPPORTED;
-  }
-  return warm_opts_check(h, opts, W);
-}
-/* ... and a warm call with per-instance model values (model != NULL): the model rule decides which handles are accepted -- every fp64
- * handle, also one whose ordinary solve starts in fp32, because a model call is the single-phase fp64 launch on every handle -- and
- * the warm rule the rest */
-static int warm_model_check(MpcHandle *h, const MpcWarmOpts *opts, MpcWarmOpts *W) {
-  MPC_TRY(model_check(h));
-  return warm_opts_check(h, opts, W);
+  return launch_solve<double>(h, {B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters}, stream_,
+                              model ? kStats : kStats | kDefer | kOrder, call_extras(h, model));
 }
 
 extern "C" int mpc_solve_batch_device_warm(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
                                            const double *yaw_lo, const double *yaw_hi, const double *weights, const double *warm_in,
                                            const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts,
                                            double *out, double *traj, int32_t *status, int32_t *iters, void *stream_) {
-  WarmIO warm{warm_in, warm_status, warm_out, ld_warm, {}};
-  MPC_TRY(warm_check(h, opts, &warm.wopts));
-  return launch_solve<double>(h, {B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters}, stream_, true, false, false, &warm);
+  return launch_solve<double>(h, {B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters}, stream_, kStats,
+                              call_extras(h, nullptr, true, warm_in, warm_status, warm_out, ld_warm, opts));
 }
 
 extern "C" int mpc_solve_batch_device_warm_model(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
@@ -2312,14 +2329,8 @@ extern "C" int mpc_solve_batch_device_warm_model(MpcHandle *h, int64_t B, int64_
                                                  const double *warm_in, const int32_t *warm_status, double *warm_out, int64_t ld_warm,
                                                  const MpcWarmOpts *opts, double *out, double *traj, int32_t *status, int32_t *iters,
                                                  void *stream_) {
-  if (!model)
-    return mpc_solve_batch_device_warm(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, warm_in, warm_status, warm_out, ld_warm, opts, out, traj,
-                                       status, iters, stream_);
-  WarmIO warm{warm_in, warm_status, warm_out, ld_warm, {}};
-  MPC_TRY(warm_model_check(h, opts, &warm.wopts));
-  SolveIO<double> io{B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters};
-  io.set_model(model, ld);
-  return launch_solve<double>(h, io, stream_, true, false, false, &warm);
+  return launch_solve<double>(h, {B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters}, stream_, kStats,
+                              call_extras(h, model, true, warm_in, warm_status, warm_out, ld_warm, opts));
 }
 
 /* MPC_PRECISION_F32: the same solve with fp32 inputs, outputs and workspace (handle created with precision F32) */
@@ -2327,22 +2338,24 @@ extern "C" int mpc_solve_batch_device_f32(MpcHandle *h, int64_t B, int64_t ld, c
                                           const float *coeffs, const float *yaw_lo, const float *yaw_hi,
                                           const float *weights, float *out, float *traj, int32_t *status,
                                           int32_t *iters, void *stream_) {
-  return launch_solve<float>(h, {B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters}, stream_, true, true);
+  return launch_solve<float>(h, {B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters}, stream_, kStats | kDefer, call_extras(h));
 }
 
-/* run() for a batch; `tel` selects the telemetry rows as input (with latency compensation) and `cmd` the reply.  warm: a warm call
- * (warm_check has passed) -- the same three kernels, the solve started from the previous call's records with their psi projected
- * into the box run_pre derives for this call (mpc::WarmColumn).  model (device, [MPC_NMODEL][ld]; model_check has passed): the MODEL
+/* run() for a batch; `tel` selects the telemetry rows as input (with latency compensation) and `cmd` the reply.  x.warm: the same
+ * three kernels, the solve started from the previous call's records with their psi projected
+ * into the box run_pre derives for this call (mpc::WarmColumn).  x.model (device, [MPC_NMODEL][ld]): the MODEL
  * forms of the pre and post kernels, and a model solve between them that reads its inputs from the handle's rows at the handle's
- * stride and the columns from the caller's array at the caller's ld (SolveIO::ld_model) -- the array is not copied. */
+ * stride and the columns from the caller's array at the caller's ld (CallExtras::ld_model) -- the array is not copied. */
 static int run_impl(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, bool tel, double extra, double *ptsx,
                     double *ptsy, double *out8, double *cmd, double *traj, int32_t *status, int32_t *iters, double *pre,
-                    void *stream_, const WarmIO *warm = nullptr, const double *model = nullptr) {
+                    void *stream_, CallExtras x) {
+  MPC_TRY(x.refused);
+  if (B > 0 && !(tel ? cmd : out8)) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
   MPC_TRY(check_batch(h, B, ld));
-  if (warm && (warm->warm_in || warm->warm_out) && warm->ld_warm < B) { g_last_error = "ld_warm < B"; return MPC_ERR_INVALID; }
+  if (x.warm && (x.w.warm_in || x.w.warm_out) && x.w.ld_warm < B) { g_last_error = "ld_warm < B"; return MPC_ERR_INVALID; }
   if (npts < 3 || npts > mpc::RUN_MAX_PTS) { g_last_error = "npts must be 3..8"; return MPC_ERR_INVALID; }
   if (B == 0) { h->last_B = 0; return MPC_OK; }
-  if (!pose || !ptsx || !ptsy || !(out8 || cmd) || !status) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
+  if (!pose || !ptsx || !ptsy || !status) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
   /* the tables MPC::run() looks up (Vehicle.cpp:34-79) must exist, and the fit is built for orders 2..4
    * (Config::maxFitOrder <= 5, as in every config-*.json; the reference would go on to higher orders) */
   if (h->params.n_yaw_change_speeds < 1 || h->params.n_steer_speeds < 1) { g_last_error = "run(): empty speed tables (load a config-*.json)"; return MPC_ERR_INVALID; }
@@ -2354,6 +2367,7 @@ static int run_impl(MpcHandle *h, int64_t B, int64_t ld, int npts, const double 
   hipStream_t s = (hipStream_t)stream_;
   double *d_pre = h->d_run;
   const unsigned grid = (unsigned)((B + 255) / 256);
+  const double *model = x.model;
   /* the two kernels around the solve: f(MODEL build or not, the argument the MODEL builds take behind the others) */
   const auto around = [&](auto f) { return model ? f(std::true_type{}, MpcModelPart{model, ld}) : f(std::false_type{}); };
   around([&](auto model_build, auto... mp) {
@@ -2364,10 +2378,9 @@ static int run_impl(MpcHandle *h, int64_t B, int64_t ld, int npts, const double 
     });
   });
   MPC_HIP_CHECK(hipGetLastError());
-  SolveIO<double> io{B, S, ld, d_pre + mpc::RUN_PRE_STATE * S, d_pre + mpc::RUN_PRE_COEFFS * S, d_pre + mpc::RUN_PRE_YAW_LO * S,
-                     d_pre + mpc::RUN_PRE_YAW_HI * S, nullptr, h->d_run9, traj, status, iters};
-  if (model) io.set_model(model, ld, true);
-  MPC_TRY(launch_solve<double>(h, io, stream_, true, false, false, warm));
+  x.w.psi_box = 1; x.ld_model = ld; x.model_wave = true;      /* the run() path's own */
+  MPC_TRY(launch_solve<double>(h, {B, S, ld, d_pre + mpc::RUN_PRE_STATE * S, d_pre + mpc::RUN_PRE_COEFFS * S, d_pre + mpc::RUN_PRE_YAW_LO * S,
+                                   d_pre + mpc::RUN_PRE_YAW_HI * S, nullptr, h->d_run9, traj, status, iters}, stream_, kStats, x));
   around([&](auto model_build, auto... mp) {
     hipLaunchKernelGGL((mpc_run_post_kernel<decltype(model_build)::value, decltype(mp)...>), dim3(grid), dim3(256), 0, s, h->params, B, d_pre, S,
                        h->d_run9, ld, out8, cmd, ld, mp...);
@@ -2378,115 +2391,89 @@ static int run_impl(MpcHandle *h, int64_t B, int64_t ld, int npts, const double 
   return MPC_OK;
 }
 
+/* run() and the telemetry handler on device arrays: the four forms of each (include/mpc_amd.h, "warm start on the run() path" and
+ * "per-instance model values on the run() path") */
 extern "C" int mpc_run_batch_device(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx,
                                     double *ptsy, double *out8, double *traj, int32_t *status, int32_t *iters,
                                     double *pre, void *stream_) {
-  if (h && B > 0 && !out8) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
-  return run_impl(h, B, ld, npts, pose, false, 0.0, ptsx, ptsy, out8, nullptr, traj, status, iters, pre, stream_);
+  return run_impl(h, B, ld, npts, pose, false, 0.0, ptsx, ptsy, out8, nullptr, traj, status, iters, pre, stream_, call_extras(h));
 }
 
 extern "C" int mpc_telemetry_batch_device(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
                                           double *ptsx, double *ptsy, double *cmd, double *out8, int32_t *status, void *stream_) {
-  if (h && B > 0 && !cmd) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
-  return run_impl(h, B, ld, npts, tel, true, extra_latency, ptsx, ptsy, out8, cmd, nullptr, status, nullptr, nullptr, stream_);
-}
-
-/* run() and the telemetry handler, warm-started from the previous call (include/mpc_amd.h, "warm start on the run() path") */
-static WarmIO run_warm_io(const double *warm_in, const int32_t *warm_status, double *warm_out, int64_t ld_warm) {
-  WarmIO w{warm_in, warm_status, warm_out, ld_warm, {}};
-  w.psi_box = 1;
-  return w;
+  return run_impl(h, B, ld, npts, tel, true, extra_latency, ptsx, ptsy, out8, cmd, nullptr, status, nullptr, nullptr, stream_, call_extras(h));
 }
 
 extern "C" int mpc_run_batch_device_warm(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx,
                                          double *ptsy, const double *warm_in, const int32_t *warm_status, double *warm_out,
                                          int64_t ld_warm, const MpcWarmOpts *opts, double *out8, double *traj, int32_t *status,
                                          int32_t *iters, double *pre, void *stream_) {
-  WarmIO warm = run_warm_io(warm_in, warm_status, warm_out, ld_warm);
-  MPC_TRY(warm_check(h, opts, &warm.wopts));
-  if (B > 0 && !out8) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
-  return run_impl(h, B, ld, npts, pose, false, 0.0, ptsx, ptsy, out8, nullptr, traj, status, iters, pre, stream_, &warm);
+  return run_impl(h, B, ld, npts, pose, false, 0.0, ptsx, ptsy, out8, nullptr, traj, status, iters, pre, stream_,
+                  call_extras(h, nullptr, true, warm_in, warm_status, warm_out, ld_warm, opts));
 }
 
 extern "C" int mpc_telemetry_batch_device_warm(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
                                                double *ptsx, double *ptsy, const double *warm_in, const int32_t *warm_status,
                                                double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts, double *cmd, double *out8,
                                                int32_t *status, void *stream_) {
-  WarmIO warm = run_warm_io(warm_in, warm_status, warm_out, ld_warm);
-  MPC_TRY(warm_check(h, opts, &warm.wopts));
-  if (B > 0 && !cmd) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
-  return run_impl(h, B, ld, npts, tel, true, extra_latency, ptsx, ptsy, out8, cmd, nullptr, status, nullptr, nullptr, stream_, &warm);
+  return run_impl(h, B, ld, npts, tel, true, extra_latency, ptsx, ptsy, out8, cmd, nullptr, status, nullptr, nullptr, stream_,
+                  call_extras(h, nullptr, true, warm_in, warm_status, warm_out, ld_warm, opts));
 }
 
-/* ... and with per-instance model values (include/mpc_amd.h, "per-instance model values on the run() path"); model == NULL: the
- * entry point without _model.  The handles: model_check / warm_model_check, as for the mpc_solve_*_model entry points. */
 extern "C" int mpc_run_batch_device_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx, double *ptsy,
                                           const double *model, double *out8, double *traj, int32_t *status, int32_t *iters, double *pre,
                                           void *stream_) {
-  if (!model) return mpc_run_batch_device(h, B, ld, npts, pose, ptsx, ptsy, out8, traj, status, iters, pre, stream_);
-  MPC_TRY(model_check(h));
-  if (B > 0 && !out8) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
-  return run_impl(h, B, ld, npts, pose, false, 0.0, ptsx, ptsy, out8, nullptr, traj, status, iters, pre, stream_, nullptr, model);
+  return run_impl(h, B, ld, npts, pose, false, 0.0, ptsx, ptsy, out8, nullptr, traj, status, iters, pre, stream_, call_extras(h, model));
 }
 
 extern "C" int mpc_telemetry_batch_device_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
                                                 double *ptsx, double *ptsy, const double *model, double *cmd, double *out8, int32_t *status,
                                                 void *stream_) {
-  if (!model) return mpc_telemetry_batch_device(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, cmd, out8, status, stream_);
-  MPC_TRY(model_check(h));
-  if (B > 0 && !cmd) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
-  return run_impl(h, B, ld, npts, tel, true, extra_latency, ptsx, ptsy, out8, cmd, nullptr, status, nullptr, nullptr, stream_, nullptr, model);
+  return run_impl(h, B, ld, npts, tel, true, extra_latency, ptsx, ptsy, out8, cmd, nullptr, status, nullptr, nullptr, stream_, call_extras(h, model));
 }
 
 extern "C" int mpc_run_batch_device_warm_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx,
                                                double *ptsy, const double *model, const double *warm_in, const int32_t *warm_status,
                                                double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts, double *out8, double *traj,
                                                int32_t *status, int32_t *iters, double *pre, void *stream_) {
-  if (!model)
-    return mpc_run_batch_device_warm(h, B, ld, npts, pose, ptsx, ptsy, warm_in, warm_status, warm_out, ld_warm, opts, out8, traj, status, iters, pre,
-                                     stream_);
-  WarmIO warm = run_warm_io(warm_in, warm_status, warm_out, ld_warm);
-  MPC_TRY(warm_model_check(h, opts, &warm.wopts));
-  if (B > 0 && !out8) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
-  return run_impl(h, B, ld, npts, pose, false, 0.0, ptsx, ptsy, out8, nullptr, traj, status, iters, pre, stream_, &warm, model);
+  return run_impl(h, B, ld, npts, pose, false, 0.0, ptsx, ptsy, out8, nullptr, traj, status, iters, pre, stream_,
+                  call_extras(h, model, true, warm_in, warm_status, warm_out, ld_warm, opts));
 }
 
 extern "C" int mpc_telemetry_batch_device_warm_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
                                                      double *ptsx, double *ptsy, const double *model, const double *warm_in,
                                                      const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts,
                                                      double *cmd, double *out8, int32_t *status, void *stream_) {
-  if (!model)
-    return mpc_telemetry_batch_device_warm(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, warm_in, warm_status, warm_out, ld_warm, opts, cmd, out8,
-                                           status, stream_);
-  WarmIO warm = run_warm_io(warm_in, warm_status, warm_out, ld_warm);
-  MPC_TRY(warm_model_check(h, opts, &warm.wopts));
-  if (B > 0 && !cmd) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
-  return run_impl(h, B, ld, npts, tel, true, extra_latency, ptsx, ptsy, out8, cmd, nullptr, status, nullptr, nullptr, stream_, &warm, model);
+  return run_impl(h, B, ld, npts, tel, true, extra_latency, ptsx, ptsy, out8, cmd, nullptr, status, nullptr, nullptr, stream_,
+                  call_extras(h, model, true, warm_in, warm_status, warm_out, ld_warm, opts));
 }
 
-/* The host arrays of a warm call (`hw`) on the device: the warm buffer goes through a device block of its own, rows of the handle's
- * stride, read and written in place, with the status it came with beside it.  *dw: what the launch gets. */
-static int warm_host_in(MpcHandle *h, int64_t B, const WarmIO &hw, hipStream_t s, WarmIO *dw) {
+/* A host-array call's extras (`hx`) on the device, *dx: what the launch gets.  The model columns are where the family has copied them
+ * (d_model; NULL: not a model call).  The warm buffer goes through a device block of its own, rows of the handle's stride, read and
+ * written in place, with the status it came with beside it. */
+static int host_extras_in(MpcHandle *h, int64_t B, const CallExtras &hx, const double *d_model, hipStream_t s, CallExtras *dx) {
   const int64_t S = h->io_stride, warm_rows = mpc_warm_rows(h->params.N);
-  *dw = WarmIO{nullptr, nullptr, nullptr, S, hw.wopts};
-  dw->psi_box = hw.psi_box;
+  const WarmIO &hw = hx.w;
+  dx->warm = hx.warm; dx->model = d_model;
+  dx->w = WarmIO{nullptr, nullptr, nullptr, S, hw.wopts, 0};
+  if (!hx.warm) return MPC_OK;
   if ((hw.warm_in || hw.warm_out) && hw.ld_warm < B) { g_last_error = "ld_warm < B"; return MPC_ERR_INVALID; }
   if (hw.warm_in || hw.warm_out) MPC_TRY(ensure_dev(&h->d_warm_io, sizeof(double) * (size_t)warm_rows * (size_t)S));
   if (hw.warm_in && hw.warm_status) MPC_TRY(ensure_dev(&h->d_warm_st, sizeof(int32_t) * S));
   if (hw.warm_in) {
     MPC_HIP_CHECK(hipMemcpy2DAsync(h->d_warm_io, sizeof(double) * S, hw.warm_in, sizeof(double) * hw.ld_warm, sizeof(double) * B, warm_rows, hipMemcpyHostToDevice, s));
-    dw->warm_in = h->d_warm_io;
+    dx->w.warm_in = h->d_warm_io;
     if (hw.warm_status) {
       MPC_HIP_CHECK(hipMemcpyAsync(h->d_warm_st, hw.warm_status, sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
-      dw->warm_status = h->d_warm_st;
+      dx->w.warm_status = h->d_warm_st;
     }
   }
-  if (hw.warm_out) dw->warm_out = h->d_warm_io;
+  if (hw.warm_out) dx->w.warm_out = h->d_warm_io;
   return MPC_OK;
 }
-static int warm_host_out(MpcHandle *h, int64_t B, const WarmIO &hw, hipStream_t s) {
-  if (!hw.warm_out) return MPC_OK;
-  MPC_HIP_CHECK(hipMemcpy2DAsync(hw.warm_out, sizeof(double) * hw.ld_warm, h->d_warm_io, sizeof(double) * h->io_stride, sizeof(double) * B,
+static int host_extras_out(MpcHandle *h, int64_t B, const CallExtras &hx, hipStream_t s) {
+  if (!hx.warm || !hx.w.warm_out) return MPC_OK;
+  MPC_HIP_CHECK(hipMemcpy2DAsync(hx.w.warm_out, sizeof(double) * hx.w.ld_warm, h->d_warm_io, sizeof(double) * h->io_stride, sizeof(double) * B,
                                  mpc_warm_rows(h->params.N), hipMemcpyDeviceToHost, s));
   return MPC_OK;
 }
@@ -2496,16 +2483,17 @@ extern "C" void mpc_internal_set_error(const char *msg) { g_last_error = msg ? m
 
 /* The telemetry handler for host arrays: one copy in, the kernels, one copy out, on the handle's own device and stream
  * (whatever the caller's current device is), staging kept on the handle.  rows of `tel`, `ptsx`, `ptsy` as in
- * mpc_telemetry_batch_device with leading dimension ld; the waypoint arrays are inputs only here.  model (host, [MPC_NMODEL][ld];
- * model_check has passed): six more rows of the staging block, copied in with the other inputs. */
+ * mpc_telemetry_batch_device with leading dimension ld; the waypoint arrays are inputs only here.  x.model (host, [MPC_NMODEL][ld]):
+ * six more rows of the staging block, copied in with the other inputs. */
 static int telemetry_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency, const double *ptsx,
-                          const double *ptsy, double *cmd, int32_t *status, const WarmIO *warm, const double *model = nullptr) {
+                          const double *ptsy, double *cmd, int32_t *status, const CallExtras &x) {
+  MPC_TRY(x.refused);
   MPC_TRY(check_batch(h, B, ld));
   if (npts < 3 || npts > mpc::RUN_MAX_PTS) { g_last_error = "npts must be 3..8"; return MPC_ERR_INVALID; }
   if (B == 0) { h->last_B = 0; return MPC_OK; }
   if (!tel || !ptsx || !ptsy || !cmd || !status) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
   MPC_ON_DEVICE(h);
-  const int64_t rows = 6 + 2 * npts, L = (B + 7) / 8 * 8, model_rows = model ? MPC_NMODEL : 0;
+  const int64_t rows = 6 + 2 * npts, L = (B + 7) / 8 * 8, model_rows = x.model ? MPC_NMODEL : 0;
   MPC_TRY(grow_dev(&h->d_tel, &h->tel_bytes, sizeof(double) * (size_t)((rows + 2 + model_rows) * L) + sizeof(int32_t) * (size_t)L));
   double *d = h->d_tel, *d_cmd = d + rows * L, *d_model = d_cmd + 2 * L;
   int32_t *d_st = (int32_t *)(d_model + model_rows * L);
@@ -2513,12 +2501,11 @@ static int telemetry_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const d
   MPC_HIP_CHECK(hipMemcpy2DAsync(d, sizeof(double) * L, tel, sizeof(double) * ld, sizeof(double) * B, 6, hipMemcpyHostToDevice, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(d + 6 * L, sizeof(double) * L, ptsx, sizeof(double) * ld, sizeof(double) * B, npts, hipMemcpyHostToDevice, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(d + (6 + npts) * L, sizeof(double) * L, ptsy, sizeof(double) * ld, sizeof(double) * B, npts, hipMemcpyHostToDevice, s));
-  if (model) MPC_HIP_CHECK(hipMemcpy2DAsync(d_model, sizeof(double) * L, model, sizeof(double) * ld, sizeof(double) * B, MPC_NMODEL, hipMemcpyHostToDevice, s));
-  WarmIO dw{};
-  if (warm) MPC_TRY(warm_host_in(h, B, *warm, s, &dw));
-  MPC_TRY(run_impl(h, B, L, npts, d, true, extra_latency, d + 6 * L, d + (6 + npts) * L, nullptr, d_cmd, nullptr, d_st, nullptr, nullptr, (void *)s,
-                   warm ? &dw : nullptr, model ? d_model : nullptr));
-  if (warm) MPC_TRY(warm_host_out(h, B, *warm, s));
+  if (x.model) MPC_HIP_CHECK(hipMemcpy2DAsync(d_model, sizeof(double) * L, x.model, sizeof(double) * ld, sizeof(double) * B, MPC_NMODEL, hipMemcpyHostToDevice, s));
+  CallExtras dx;
+  MPC_TRY(host_extras_in(h, B, x, x.model ? d_model : nullptr, s, &dx));
+  MPC_TRY(run_impl(h, B, L, npts, d, true, extra_latency, d + 6 * L, d + (6 + npts) * L, nullptr, d_cmd, nullptr, d_st, nullptr, nullptr, (void *)s, dx));
+  MPC_TRY(host_extras_out(h, B, x, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(cmd, sizeof(double) * ld, d_cmd, sizeof(double) * L, sizeof(double) * B, 2, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipMemcpyAsync(status, d_st, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipStreamSynchronize(s));
@@ -2527,40 +2514,35 @@ static int telemetry_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const d
 
 extern "C" int mpc_telemetry_batch_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
                                         const double *ptsx, const double *ptsy, double *cmd, int32_t *status) {
-  return telemetry_host(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, cmd, status, nullptr);
+  return telemetry_host(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, cmd, status, call_extras(h));
 }
 
 extern "C" int mpc_telemetry_batch_host_warm(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
                                              const double *ptsx, const double *ptsy, const double *warm_in, const int32_t *warm_status,
                                              double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts, double *cmd, int32_t *status) {
-  WarmIO hw = run_warm_io(warm_in, warm_status, warm_out, ld_warm);
-  MPC_TRY(warm_check(h, opts, &hw.wopts));
-  return telemetry_host(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, cmd, status, &hw);
+  return telemetry_host(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, cmd, status,
+                        call_extras(h, nullptr, true, warm_in, warm_status, warm_out, ld_warm, opts));
 }
 
 extern "C" int mpc_telemetry_batch_host_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
                                               const double *ptsx, const double *ptsy, const double *model, double *cmd, int32_t *status) {
-  if (!model) return mpc_telemetry_batch_host(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, cmd, status);
-  MPC_TRY(model_check(h));
-  return telemetry_host(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, cmd, status, nullptr, model);
+  return telemetry_host(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, cmd, status, call_extras(h, model));
 }
 
 extern "C" int mpc_telemetry_batch_host_warm_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
                                                    const double *ptsx, const double *ptsy, const double *model, const double *warm_in,
                                                    const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts,
                                                    double *cmd, int32_t *status) {
-  if (!model)
-    return mpc_telemetry_batch_host_warm(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, warm_in, warm_status, warm_out, ld_warm, opts, cmd, status);
-  WarmIO hw = run_warm_io(warm_in, warm_status, warm_out, ld_warm);
-  MPC_TRY(warm_model_check(h, opts, &hw.wopts));
-  return telemetry_host(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, cmd, status, &hw, model);
+  return telemetry_host(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, cmd, status,
+                        call_extras(h, model, true, warm_in, warm_status, warm_out, ld_warm, opts));
 }
 
 /* MPC::run() for host arrays (the drop-in's B = 1 case, include/mpc_drop_in.hpp): one copy in, the three kernels of
  * mpc_run_batch_device on the handle's own device and stream, one copy out; synchronises.  ptsx / ptsy are transformed in place
- * like the reference does (MPC.cpp:329; mpc_main.cpp:189-190 relies on it).  model: as in telemetry_host. */
+ * like the reference does (MPC.cpp:329; mpc_main.cpp:189-190 relies on it).  x.model: as in telemetry_host. */
 static int run_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx, double *ptsy, double *out8,
-                    double *traj, int32_t *status, int32_t *iters, double *pre, const WarmIO *warm, const double *model = nullptr) {
+                    double *traj, int32_t *status, int32_t *iters, double *pre, const CallExtras &x) {
+  MPC_TRY(x.refused);
   MPC_TRY(check_batch(h, B, ld));
   if (npts < 3 || npts > mpc::RUN_MAX_PTS) { g_last_error = "npts must be 3..8"; return MPC_ERR_INVALID; }
   if (h->params.precision != MPC_PRECISION_F64) { g_last_error = "run() entry points are fp64 only"; return MPC_ERR_INVALID; }
@@ -2569,7 +2551,7 @@ static int run_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const double 
   MPC_ON_DEVICE(h);
   const int N = h->params.N;
   const int64_t L = (B + 7) / 8 * 8;
-  const int64_t in_rows = 6 + 2 * npts, out_rows = 8 + 2 * N + mpc::RUN_PRE_ROWS, model_rows = model ? MPC_NMODEL : 0;
+  const int64_t in_rows = 6 + 2 * npts, out_rows = 8 + 2 * N + mpc::RUN_PRE_ROWS, model_rows = x.model ? MPC_NMODEL : 0;
   MPC_TRY(grow_dev(&h->d_tel, &h->tel_bytes, sizeof(double) * (size_t)((in_rows + out_rows + model_rows) * L) + sizeof(int32_t) * (size_t)(2 * L)));
   double *d = h->d_tel, *d_px = d + 6 * L, *d_py = d_px + (int64_t)npts * L, *d_o8 = d + in_rows * L, *d_tr = d_o8 + 8 * L, *d_pre = d_tr + 2 * (int64_t)N * L;
   double *d_model = d_pre + mpc::RUN_PRE_ROWS * L;
@@ -2578,12 +2560,11 @@ static int run_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const double 
   MPC_HIP_CHECK(hipMemcpy2DAsync(d, sizeof(double) * L, pose, sizeof(double) * ld, sizeof(double) * B, 6, hipMemcpyHostToDevice, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(d_px, sizeof(double) * L, ptsx, sizeof(double) * ld, sizeof(double) * B, npts, hipMemcpyHostToDevice, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(d_py, sizeof(double) * L, ptsy, sizeof(double) * ld, sizeof(double) * B, npts, hipMemcpyHostToDevice, s));
-  if (model) MPC_HIP_CHECK(hipMemcpy2DAsync(d_model, sizeof(double) * L, model, sizeof(double) * ld, sizeof(double) * B, MPC_NMODEL, hipMemcpyHostToDevice, s));
-  WarmIO dw{};
-  if (warm) MPC_TRY(warm_host_in(h, B, *warm, s, &dw));
-  MPC_TRY(run_impl(h, B, L, npts, d, false, 0.0, d_px, d_py, d_o8, nullptr, traj ? d_tr : nullptr, d_st, d_it, d_pre, (void *)s, warm ? &dw : nullptr,
-                   model ? d_model : nullptr));
-  if (warm) MPC_TRY(warm_host_out(h, B, *warm, s));
+  if (x.model) MPC_HIP_CHECK(hipMemcpy2DAsync(d_model, sizeof(double) * L, x.model, sizeof(double) * ld, sizeof(double) * B, MPC_NMODEL, hipMemcpyHostToDevice, s));
+  CallExtras dx;
+  MPC_TRY(host_extras_in(h, B, x, x.model ? d_model : nullptr, s, &dx));
+  MPC_TRY(run_impl(h, B, L, npts, d, false, 0.0, d_px, d_py, d_o8, nullptr, traj ? d_tr : nullptr, d_st, d_it, d_pre, (void *)s, dx));
+  MPC_TRY(host_extras_out(h, B, x, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(ptsx, sizeof(double) * ld, d_px, sizeof(double) * L, sizeof(double) * B, npts, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(ptsy, sizeof(double) * ld, d_py, sizeof(double) * L, sizeof(double) * B, npts, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(out8, sizeof(double) * ld, d_o8, sizeof(double) * L, sizeof(double) * B, 8, hipMemcpyDeviceToHost, s));
@@ -2597,33 +2578,27 @@ static int run_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const double 
 
 extern "C" int mpc_run_batch_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx, double *ptsy,
                                   double *out8, double *traj, int32_t *status, int32_t *iters, double *pre) {
-  return run_host(h, B, ld, npts, pose, ptsx, ptsy, out8, traj, status, iters, pre, nullptr);
+  return run_host(h, B, ld, npts, pose, ptsx, ptsy, out8, traj, status, iters, pre, call_extras(h));
 }
 
 extern "C" int mpc_run_batch_host_warm(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx, double *ptsy,
                                        const double *warm_in, const int32_t *warm_status, double *warm_out, int64_t ld_warm,
                                        const MpcWarmOpts *opts, double *out8, double *traj, int32_t *status, int32_t *iters, double *pre) {
-  WarmIO hw = run_warm_io(warm_in, warm_status, warm_out, ld_warm);
-  MPC_TRY(warm_check(h, opts, &hw.wopts));
-  return run_host(h, B, ld, npts, pose, ptsx, ptsy, out8, traj, status, iters, pre, &hw);
+  return run_host(h, B, ld, npts, pose, ptsx, ptsy, out8, traj, status, iters, pre,
+                  call_extras(h, nullptr, true, warm_in, warm_status, warm_out, ld_warm, opts));
 }
 
 extern "C" int mpc_run_batch_host_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx, double *ptsy,
                                         const double *model, double *out8, double *traj, int32_t *status, int32_t *iters, double *pre) {
-  if (!model) return mpc_run_batch_host(h, B, ld, npts, pose, ptsx, ptsy, out8, traj, status, iters, pre);
-  MPC_TRY(model_check(h));
-  return run_host(h, B, ld, npts, pose, ptsx, ptsy, out8, traj, status, iters, pre, nullptr, model);
+  return run_host(h, B, ld, npts, pose, ptsx, ptsy, out8, traj, status, iters, pre, call_extras(h, model));
 }
 
 extern "C" int mpc_run_batch_host_warm_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, double *ptsx, double *ptsy,
                                              const double *model, const double *warm_in, const int32_t *warm_status, double *warm_out,
                                              int64_t ld_warm, const MpcWarmOpts *opts, double *out8, double *traj, int32_t *status,
                                              int32_t *iters, double *pre) {
-  if (!model)
-    return mpc_run_batch_host_warm(h, B, ld, npts, pose, ptsx, ptsy, warm_in, warm_status, warm_out, ld_warm, opts, out8, traj, status, iters, pre);
-  WarmIO hw = run_warm_io(warm_in, warm_status, warm_out, ld_warm);
-  MPC_TRY(warm_model_check(h, opts, &hw.wopts));
-  return run_host(h, B, ld, npts, pose, ptsx, ptsy, out8, traj, status, iters, pre, &hw, model);
+  return run_host(h, B, ld, npts, pose, ptsx, ptsy, out8, traj, status, iters, pre,
+                  call_extras(h, model, true, warm_in, warm_status, warm_out, ld_warm, opts));
 }
 
 /* the device a handle lives on (mpc_create's `device`, resolved) */
@@ -2638,26 +2613,25 @@ static int rollout_args(const MpcHandle *h, int64_t B, int64_t ld, int steps, co
   return MPC_OK;
 }
 
-/* The rollout: `steps` solves, each followed by the step kernel.  W != NULL: every step after the first is warm-started from the step
- * before (the handle keeps the buffer).  model != NULL: the cars' columns go to every step (model_check has passed), cold or warm. */
+/* The rollout: `steps` solves, each followed by the step kernel.  x.warm: every step after the first is warm-started from the step
+ * before (the handle keeps the buffer; of x.w only the options count).  x.model: the cars' columns go to every step, cold or warm. */
 static int rollout_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs, const double *yaw_lo,
-                        const double *yaw_hi, const double *weights, const MpcWarmOpts *W, double *hist, int32_t *status, int32_t *iters,
-                        void *stream_, const double *model = nullptr) {
+                        const double *yaw_hi, const double *weights, double *hist, int32_t *status, int32_t *iters, void *stream_,
+                        CallExtras x) {
+  MPC_TRY(x.refused);
   MPC_TRY(rollout_args(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, status));
   if (B == 0) { h->last_B = 0; return MPC_OK; }
   MPC_ON_DEVICE(h);
   if (!hist) MPC_TRY(grow_dev(&h->d_run9, &h->run9_bytes, sizeof(double) * 9 * ld));
   MPC_TRY(ensure_dev(&h->d_rstat, sizeof(int32_t) * h->io_stride));
-  if (W) MPC_TRY(ensure_dev(&h->d_warm, sizeof(double) * (size_t)mpc_warm_rows(h->params.N) * (size_t)h->io_stride));
+  if (x.warm) MPC_TRY(ensure_dev(&h->d_warm, sizeof(double) * (size_t)mpc_warm_rows(h->params.N) * (size_t)h->io_stride));
   hipStream_t s = (hipStream_t)stream_;
   const unsigned grid = (unsigned)((B + 255) / 256);
   for (int t = 0; t < steps; t++) {
     double *o9 = hist ? hist + (int64_t)t * 9 * ld : h->d_run9;
     /* (warm, in place: a lane reads its car's column and its previous status (d_rstat) before it writes either) */
-    const WarmIO warm{t == 0 ? nullptr : h->d_warm, h->d_rstat, h->d_warm, h->io_stride, W ? *W : MpcWarmOpts{}};
-    SolveIO<double> io{B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, o9, nullptr, h->d_rstat, h->d_iters};
-    if (model) io.set_model(model, ld);   /* (a model rollout: the cars' columns go to every step) */
-    MPC_TRY(launch_solve<double>(h, io, stream_, false, false, false, W ? &warm : nullptr));
+    x.w = WarmIO{t == 0 ? nullptr : h->d_warm, h->d_rstat, h->d_warm, h->io_stride, x.w.wopts, 0};
+    MPC_TRY(launch_solve<double>(h, {B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, o9, nullptr, h->d_rstat, h->d_iters}, stream_, 0, x));
     hipLaunchKernelGGL(mpc_rollout_step_kernel, dim3(grid), dim3(256), 0, s, B, ld, t == 0, o9, state, h->d_rstat, h->d_iters, status, iters);
     MPC_HIP_CHECK(hipGetLastError());
   }
@@ -2667,54 +2641,51 @@ static int rollout_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *
 extern "C" int mpc_rollout_batch_device(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
                                         const double *yaw_lo, const double *yaw_hi, const double *weights, double *hist,
                                         int32_t *status, int32_t *iters, void *stream_) {
-  return rollout_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, nullptr, hist, status, iters, stream_);
+  return rollout_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, hist, status, iters, stream_, call_extras(h));
 }
 
 extern "C" int mpc_rollout_batch_device_model(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
                                               const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
                                               double *hist, int32_t *status, int32_t *iters, void *stream_) {
-  if (!model) return mpc_rollout_batch_device(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, hist, status, iters, stream_);
-  MPC_TRY(model_check(h));
-  return rollout_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, nullptr, hist, status, iters, stream_, model);
+  return rollout_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, hist, status, iters, stream_, call_extras(h, model));
 }
 
 extern "C" int mpc_rollout_batch_device_warm(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
                                              const double *yaw_lo, const double *yaw_hi, const double *weights, const MpcWarmOpts *opts,
                                              double *hist, int32_t *status, int32_t *iters, void *stream_) {
-  MpcWarmOpts W;
-  MPC_TRY(warm_check(h, opts, &W));
-  return rollout_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, &W, hist, status, iters, stream_);
+  return rollout_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, hist, status, iters, stream_,
+                      call_extras(h, nullptr, true, nullptr, nullptr, nullptr, 0, opts));
 }
 
 extern "C" int mpc_rollout_batch_device_warm_model(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
                                                    const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
                                                    const MpcWarmOpts *opts, double *hist, int32_t *status, int32_t *iters, void *stream_) {
-  if (!model) return mpc_rollout_batch_device_warm(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, opts, hist, status, iters, stream_);
-  MpcWarmOpts W;
-  MPC_TRY(warm_model_check(h, opts, &W));
-  return rollout_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, &W, hist, status, iters, stream_, model);
+  return rollout_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, hist, status, iters, stream_,
+                      call_extras(h, model, true, nullptr, nullptr, nullptr, 0, opts));
 }
 
 /* The rollout in one launch: the ROLL build of the lane kernel, a lane per car for all `steps` solves (see mpc_solve_kernel).  One
  * rule decides: fused == stepwise on every handle.  The fused kernel is the single-phase fp64 lane kernel, so it runs where the
  * stepwise loop would launch exactly that at every step (an fp64 handle, no fp32 start, no SOC, B above the wave limit); everywhere
- * else -- and for an fp32 handle, which the loop refuses -- the call IS the stepwise loop.  W != NULL: warm (warm_check has passed).
- * model != NULL (model_check has passed: an fp64 handle): the stepwise model loop launches the single-phase fp64 lane kernel at every B
+ * else -- and for an fp32 handle, which the loop refuses -- the call IS the stepwise loop.  x.warm: warm_start != 0.
+ * x.model (an fp64 handle): the stepwise model loop launches the single-phase fp64 lane kernel at every B
  * and on a handle whose ordinary solve starts in fp32 as well, so the one launch -- the ROLL+MODEL builds -- runs at every B >= 1 of
  * every handle without SOC; with SOC (a cold call; a warm one has been refused) the call is the stepwise model loop. */
 static int rollout_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs, const double *yaw_lo,
-                              const double *yaw_hi, const double *weights, const MpcWarmOpts *W, double *hist, int32_t *status,
-                              int32_t *iters, void *stream_, const double *model = nullptr) {
+                              const double *yaw_hi, const double *weights, double *hist, int32_t *status, int32_t *iters, void *stream_,
+                              const CallExtras &x) {
+  MPC_TRY(x.refused);
   MPC_TRY(rollout_args(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, status));
+  const double *model = x.model;
   const bool wave_path = !model && h->wave_max_batch > 0 && B <= h->wave_max_batch;
   if (B == 0 || h->params.precision != MPC_PRECISION_F64 || (h->mixed && !model) || h->params.max_soc > 0 || wave_path) {
-    MPC_TRY(rollout_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, W, hist, status, iters, stream_, model));
+    MPC_TRY(rollout_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, hist, status, iters, stream_, x));
     ++h->n_roll_stepwise;
     return MPC_OK;
   }
   MPC_ON_DEVICE(h);
   if (!hist) MPC_TRY(grow_dev(&h->d_run9, &h->run9_bytes, sizeof(double) * 9 * ld));
-  if (W) MPC_TRY(ensure_dev(&h->d_warm, sizeof(double) * (size_t)mpc_warm_rows(h->params.N) * (size_t)h->io_stride));
+  if (x.warm) MPC_TRY(ensure_dev(&h->d_warm, sizeof(double) * (size_t)mpc_warm_rows(h->params.N) * (size_t)h->io_stride));
   double *o9 = hist ? hist : h->d_run9;          /* (no history: every car's 9 rows go to its own column of the scratch rows) */
   const SolveIO<double> io{B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, o9, nullptr, status, iters ? iters : h->d_iters};
   std::optional<DeviceGuard> guard;
@@ -2728,17 +2699,15 @@ static int rollout_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, do
   T.compact_gap = 0;                             /* (the step index does not travel with a moved instance) */
   const TailPlace tp;
   tail_fields(h, tp, T);
-  double *warm = W ? h->d_warm : nullptr;
-  const WarmIO wc{warm, nullptr, warm, h->io_stride, W ? *W : MpcWarmOpts{}, 0};
+  double *warm = x.warm ? h->d_warm : nullptr;
+  const WarmIO wc{warm, nullptr, warm, h->io_stride, x.w.wopts, 0};
   const MpcRollPart roll{steps, o9, hist ? 9 * ld : 0, state, status, iters};
   const unsigned grid = (unsigned)((B + kBlock - 1) / kBlock);
   MPC_TRY(with_bool(h->staging, [&](auto staging) {
-    return with_bool(W != nullptr, [&](auto warm_build) {
-      return with_bool(model != nullptr, [&](auto model_build) {
-        constexpr bool STAGING = decltype(staging)::value, WARM = decltype(warm_build)::value, MODEL = decltype(model_build)::value;
-        return launch_kernel(mpc_solve_kernel<STAGING, double, double, double, false, WARM, true, MODEL>, grid, STAGING ? staging_lds_bytes<double>() : 0,
-                             s, h, io, (double *)h->ws, h->ws_stride, phase_of<true, WARM, MODEL>(T, wc, roll, {model, ld}));
-      });
+    return with_build(false, x.warm, model != nullptr, [&](auto, auto warm_build, auto model_build) {      /* (no SOC here: those handles loop) */
+      constexpr bool STAGING = decltype(staging)::value, WARM = decltype(warm_build)::value, MODEL = decltype(model_build)::value;
+      return launch_kernel(mpc_solve_kernel<STAGING, double, double, double, false, WARM, true, MODEL>, grid, STAGING ? staging_lds_bytes<double>() : 0,
+                           s, h, io, (double *)h->ws, h->ws_stride, phase_of<true, WARM, MODEL>(T, wc, roll, {model, ld}));
     });
   }));
   MPC_TRY(solve_end(h, io, s, rec, tp, false));
@@ -2749,21 +2718,16 @@ static int rollout_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, do
 extern "C" int mpc_rollout_batch_device_fused(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
                                               const double *yaw_lo, const double *yaw_hi, const double *weights, int warm_start,
                                               const MpcWarmOpts *opts, double *hist, int32_t *status, int32_t *iters, void *stream_) {
-  MpcWarmOpts W;
-  if (warm_start) MPC_TRY(warm_check(h, opts, &W));
-  return rollout_fused_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, warm_start ? &W : nullptr, hist, status, iters, stream_);
+  return rollout_fused_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, hist, status, iters, stream_,
+                            call_extras(h, nullptr, warm_start != 0, nullptr, nullptr, nullptr, 0, opts));
 }
 
 extern "C" int mpc_rollout_batch_device_fused_model(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
                                                     const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
                                                     int warm_start, const MpcWarmOpts *opts, double *hist, int32_t *status, int32_t *iters,
                                                     void *stream_) {
-  if (!model)
-    return mpc_rollout_batch_device_fused(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, warm_start, opts, hist, status, iters, stream_);
-  MpcWarmOpts W;
-  if (warm_start) MPC_TRY(warm_model_check(h, opts, &W));
-  else MPC_TRY(model_check(h));
-  return rollout_fused_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, warm_start ? &W : nullptr, hist, status, iters, stream_, model);
+  return rollout_fused_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, hist, status, iters, stream_,
+                            call_extras(h, model, warm_start != 0, nullptr, nullptr, nullptr, 0, opts));
 }
 
 extern "C" int mpc_rollout_fused_info(const MpcHandle *h, int64_t *out2) {
@@ -2795,13 +2759,12 @@ static void for_rows(int n_rows, size_t row_bytes, Fn fn) {
 }
 
 /* host pointers: one copy in, the launch(es), one copy out, on the handle's own stream; R = the handle's precision */
-/* (warm: the host arrays of mpc_solve_batch_host_warm and the options in effect; model: the host array of mpc_solve_batch_host_model,
+/* (x.warm: the host arrays of mpc_solve_batch_host_warm and the options in effect; x.model: the host array of mpc_solve_batch_host_model,
  * which goes through a device block of its own, rows packed like the inputs; both fp64 handles only) */
 template <class R>
 static int solve_host(MpcHandle *h, int64_t B, int64_t ld, const R *state, const R *coeffs, const R *yaw_lo, const R *yaw_hi,
-                      const R *weights, R *out, R *traj, int32_t *status, int32_t *iters, const WarmIO *warm = nullptr,
-                      const double *model = nullptr) {
-  if (!h) { g_last_error = "NULL handle"; return MPC_ERR_INVALID; }
+                      const R *weights, R *out, R *traj, int32_t *status, int32_t *iters, const CallExtras &x) {
+  MPC_TRY(x.refused);
   if ((h->params.precision == MPC_PRECISION_F32) != (sizeof(R) == 4)) {
     g_last_error = "this handle was created with the other precision (mpc_solve_batch_host for fp64 handles, mpc_solve_batch_host_f32 for MPC_PRECISION_F32)";
     return MPC_ERR_INVALID;
@@ -2831,17 +2794,16 @@ static int solve_host(MpcHandle *h, int64_t B, int64_t ld, const R *state, const
   MPC_HIP_CHECK(hipMemcpyAsync(di, hi, sizeof(R) * in_rows * L, hipMemcpyHostToDevice, s));
   R *d_o = d_oblk, *d_t = d_o + MPC_NOUT * L;
   int32_t *d_st = (int32_t *)(d_o + (out_rows - kIntRows) * L), *d_it = d_st + L;
-  /* the warm buffer goes through a device block of its own, rows of the handle's stride, read and written in place */
-  WarmIO dw{nullptr, nullptr, nullptr, S, {}};
-  if (warm) MPC_TRY(warm_host_in(h, B, *warm, s, &dw));
-  SolveIO<R> io{B, L, L, di, di + 6 * L, di + 11 * L, di + 12 * L, weights ? di + 13 * L : nullptr, d_o, traj ? d_t : nullptr, d_st, d_it};
-  if (model) {
+  CallExtras dx;
+  MPC_TRY(host_extras_in(h, B, x, nullptr, s, &dx));
+  if (x.model) {
     MPC_TRY(ensure_dev(&h->d_model, sizeof(double) * MPC_NMODEL * (size_t)S));
-    MPC_HIP_CHECK(hipMemcpy2DAsync(h->d_model, sizeof(double) * L, model, sizeof(double) * ld, sizeof(double) * B, MPC_NMODEL, hipMemcpyHostToDevice, s));
-    io.set_model(h->d_model, L);
+    MPC_HIP_CHECK(hipMemcpy2DAsync(h->d_model, sizeof(double) * L, x.model, sizeof(double) * ld, sizeof(double) * B, MPC_NMODEL, hipMemcpyHostToDevice, s));
+    dx.model = h->d_model;
   }
-  MPC_TRY(launch_solve<R>(h, io, (void *)s, true, false, true, warm ? &dw : nullptr));
-  if (warm) MPC_TRY(warm_host_out(h, B, *warm, s));
+  MPC_TRY(launch_solve<R>(h, {B, L, L, di, di + 6 * L, di + 11 * L, di + 12 * L, weights ? di + 13 * L : nullptr, d_o, traj ? d_t : nullptr, d_st, d_it},
+                          (void *)s, kStats | kOrder, dx));
+  MPC_TRY(host_extras_out(h, B, x, s));
   MPC_HIP_CHECK(hipMemcpyAsync(ho, d_o, sizeof(R) * out_rows * L, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipStreamSynchronize(s));
   for_rows(MPC_NOUT + (traj ? 2 * N : 0), sizeof(R) * B, [=](int q) {
@@ -2858,43 +2820,36 @@ extern "C" int mpc_solve_batch_host(MpcHandle *h, int64_t B, int64_t ld, const d
                                     const double *coeffs, const double *yaw_lo, const double *yaw_hi,
                                     const double *weights, double *out, double *traj, int32_t *status,
                                     int32_t *iters) {
-  return solve_host<double>(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters);
+  return solve_host<double>(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters, call_extras(h));
 }
 
 extern "C" int mpc_solve_batch_host_model(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
                                           const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
                                           double *out, double *traj, int32_t *status, int32_t *iters) {
-  if (!model) return mpc_solve_batch_host(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters);
-  MPC_TRY(model_check(h));
-  return solve_host<double>(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters, nullptr, model);
+  return solve_host<double>(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters, call_extras(h, model));
 }
 
 extern "C" int mpc_solve_batch_host_warm(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
                                          const double *yaw_lo, const double *yaw_hi, const double *weights, const double *warm_in,
                                          const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts,
                                          double *out, double *traj, int32_t *status, int32_t *iters) {
-  WarmIO hw{warm_in, warm_status, warm_out, ld_warm, {}};
-  MPC_TRY(warm_check(h, opts, &hw.wopts));
-  return solve_host<double>(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters, &hw);
+  return solve_host<double>(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters,
+                            call_extras(h, nullptr, true, warm_in, warm_status, warm_out, ld_warm, opts));
 }
 
 extern "C" int mpc_solve_batch_host_warm_model(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
                                                const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
                                                const double *warm_in, const int32_t *warm_status, double *warm_out, int64_t ld_warm,
                                                const MpcWarmOpts *opts, double *out, double *traj, int32_t *status, int32_t *iters) {
-  if (!model)
-    return mpc_solve_batch_host_warm(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, warm_in, warm_status, warm_out, ld_warm, opts, out, traj,
-                                     status, iters);
-  WarmIO hw{warm_in, warm_status, warm_out, ld_warm, {}};
-  MPC_TRY(warm_model_check(h, opts, &hw.wopts));
-  return solve_host<double>(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters, &hw, model);
+  return solve_host<double>(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters,
+                            call_extras(h, model, true, warm_in, warm_status, warm_out, ld_warm, opts));
 }
 
 extern "C" int mpc_solve_batch_host_f32(MpcHandle *h, int64_t B, int64_t ld, const float *state,
                                         const float *coeffs, const float *yaw_lo, const float *yaw_hi,
                                         const float *weights, float *out, float *traj, int32_t *status,
                                         int32_t *iters) {
-  return solve_host<float>(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters);
+  return solve_host<float>(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters, call_extras(h));
 }
 
 extern "C" int mpc_get_stats(MpcHandle *h, MpcBatchStats *st) {

@@ -72,6 +72,15 @@ class BatchedMPC:
         """Rows of this handle's warm buffers: (N-1) * WARM_REC."""
         return _abi.warm_rows(self.N)
 
+    def _call(self, family, head, outs, model=None, warm=None):
+        """Call `family`'s entry point for this call, chosen by the rule of include/mpc_amd.h: the name is the family's, + "_warm"
+        for a warm call (`warm`: the values the _warm form takes -- warm_in, warm_status, warm_out, ld_warm, opts; the stepwise
+        rollout: opts alone), + "_model" with `model` (a pointer); the arguments are the handle, head, [model], warm, outs."""
+        name = family + ("_warm" if warm is not None else "") + ("_model" if model is not None else "")
+        rc = getattr(library(), name)(self._h, *head, *(() if model is None else (model,)), *(warm or ()), *outs)
+        if rc != 0:
+            check(rc, name)
+
     def solve_torch(self, state, coeffs, yaw_lo, yaw_hi, weights=None, want_traj=False, outputs=None, stream=None,
                     warm=None, warm_status=None, want_warm=False, warm_opts=None, model=None):
         """state [6,B], coeffs [5,B], yaw_lo/hi [B], weights [12,B] or None: CUDA tensors, float64 (float32 for a
@@ -105,13 +114,7 @@ class BatchedMPC:
         traj = outputs.get("traj")
         if model is not None:
             self._check_model(model, B)
-        if model is not None and not (warm is not None or want_warm):
-            check(library().mpc_solve_batch_device_model(
-                self._h, B, B, state.data_ptr(), coeffs.data_ptr(), yaw_lo.data_ptr(), yaw_hi.data_ptr(),
-                weights.data_ptr() if weights is not None else None, model.data_ptr(), outputs["out"].data_ptr(),
-                traj.data_ptr() if traj is not None else None, outputs["status"].data_ptr(), outputs["iters"].data_ptr(),
-                C.c_void_p(s.cuda_stream)), "mpc_solve_batch_device_model")
-            return outputs
+        warm_args = None
         if warm is not None or want_warm:
             rows = self.warm_rows()
             if warm is not None and (warm.dtype != torch.float64 or not warm.is_cuda or not warm.is_contiguous() or tuple(warm.shape) != (rows, B)):
@@ -120,22 +123,16 @@ class BatchedMPC:
                 raise ValueError("warm_status must be an int32 CUDA tensor of shape (B,)")
             if outputs.get("warm") is None:
                 outputs["warm"] = torch.empty((rows, B), dtype=torch.float64, device=state.device)
-            head = (self._h, B, B, state.data_ptr(), coeffs.data_ptr(), yaw_lo.data_ptr(), yaw_hi.data_ptr(),
-                    weights.data_ptr() if weights is not None else None)
-            tail = (warm.data_ptr() if warm is not None else None, warm_status.data_ptr() if warm_status is not None else None,
-                    outputs["warm"].data_ptr(), B, C.byref(warm_opts) if warm_opts is not None else None, outputs["out"].data_ptr(),
-                    traj.data_ptr() if traj is not None else None, outputs["status"].data_ptr(), outputs["iters"].data_ptr(),
-                    C.c_void_p(s.cuda_stream))
-            if model is not None:
-                check(library().mpc_solve_batch_device_warm_model(*head, model.data_ptr(), *tail), "mpc_solve_batch_device_warm_model")
-            else:
-                check(library().mpc_solve_batch_device_warm(*head, *tail), "mpc_solve_batch_device_warm")
-            return outputs
-        fn = library().mpc_solve_batch_device_f32 if self.f32 else library().mpc_solve_batch_device
-        check(fn(self._h, B, B, state.data_ptr(), coeffs.data_ptr(), yaw_lo.data_ptr(), yaw_hi.data_ptr(),
-                 weights.data_ptr() if weights is not None else None, outputs["out"].data_ptr(),
-                 traj.data_ptr() if traj is not None else None, outputs["status"].data_ptr(),
-                 outputs["iters"].data_ptr(), C.c_void_p(s.cuda_stream)), "mpc_solve_batch_device")
+            warm_args = (warm.data_ptr() if warm is not None else None, warm_status.data_ptr() if warm_status is not None else None,
+                         outputs["warm"].data_ptr(), B, C.byref(warm_opts) if warm_opts is not None else None)
+        head = (B, B, state.data_ptr(), coeffs.data_ptr(), yaw_lo.data_ptr(), yaw_hi.data_ptr(),
+                weights.data_ptr() if weights is not None else None)
+        outs = (outputs["out"].data_ptr(), traj.data_ptr() if traj is not None else None, outputs["status"].data_ptr(),
+                outputs["iters"].data_ptr(), C.c_void_p(s.cuda_stream))
+        if self.f32 and model is None and warm_args is None:
+            check(library().mpc_solve_batch_device_f32(self._h, *head, *outs), "mpc_solve_batch_device")
+        else:
+            self._call("mpc_solve_batch_device", head, outs, model.data_ptr() if model is not None else None, warm_args)
         return outputs
 
     @staticmethod
@@ -189,28 +186,11 @@ class BatchedMPC:
             self._check_model(model, B)
         outs = (res["out8"].data_ptr(), res["traj"].data_ptr() if want_traj else None, res["status"].data_ptr(), res["iters"].data_ptr(),
                 res["pre"].data_ptr() if want_pre else None, C.c_void_p(s.cuda_stream))
+        warm_args = None
         if warm is not None or want_warm or warm_out is not None:
-            w_in, w_st, w_out, ld_warm = self._warm_args(res, B, dev, warm, warm_status, warm_out)
-            opts = C.byref(warm_opts) if warm_opts is not None else None
-            if model is not None:
-                check(library().mpc_run_batch_device_warm_model(
-                    self._h, B, B, int(npts), pose.data_ptr(), ptsx.data_ptr(), ptsy.data_ptr(), model.data_ptr(), w_in, w_st, w_out, ld_warm,
-                    opts, *outs), "mpc_run_batch_device_warm_model")
-                return res
-            check(library().mpc_run_batch_device_warm(
-                self._h, B, B, int(npts), pose.data_ptr(), ptsx.data_ptr(), ptsy.data_ptr(), w_in, w_st, w_out, ld_warm,
-                C.byref(warm_opts) if warm_opts is not None else None, res["out8"].data_ptr(),
-                res["traj"].data_ptr() if want_traj else None, res["status"].data_ptr(), res["iters"].data_ptr(),
-                res["pre"].data_ptr() if want_pre else None, C.c_void_p(s.cuda_stream)), "mpc_run_batch_device_warm")
-            return res
-        if model is not None:
-            check(library().mpc_run_batch_device_model(self._h, B, B, int(npts), pose.data_ptr(), ptsx.data_ptr(), ptsy.data_ptr(),
-                                                       model.data_ptr(), *outs), "mpc_run_batch_device_model")
-            return res
-        check(library().mpc_run_batch_device(
-            self._h, B, B, int(npts), pose.data_ptr(), ptsx.data_ptr(), ptsy.data_ptr(), res["out8"].data_ptr(),
-            res["traj"].data_ptr() if want_traj else None, res["status"].data_ptr(), res["iters"].data_ptr(),
-            res["pre"].data_ptr() if want_pre else None, C.c_void_p(s.cuda_stream)), "mpc_run_batch_device")
+            warm_args = self._warm_args(res, B, dev, warm, warm_status, warm_out) + (C.byref(warm_opts) if warm_opts is not None else None,)
+        self._call("mpc_run_batch_device", (B, B, int(npts), pose.data_ptr(), ptsx.data_ptr(), ptsy.data_ptr()), outs,
+                   model.data_ptr() if model is not None else None, warm_args)
         return res
 
     def run_numpy(self, pose, ptsx, ptsy, want_traj=False, warm=None, warm_status=None, want_warm=False, warm_opts=None, model=None):
@@ -229,6 +209,8 @@ class BatchedMPC:
             model = f(model)
             if model.shape != (_abi.NMODEL, B):
                 raise ValueError("model must have shape (%d, B)" % _abi.NMODEL)
+        res = {"out8": out8, "status": status, "iters": iters, "pre": pre, "ptsx": px, "ptsy": py, "traj": traj}
+        warm_args = None
         if warm is not None or want_warm:
             rows = self.warm_rows()
             if warm is not None:
@@ -236,23 +218,11 @@ class BatchedMPC:
                 assert warm.shape == (rows, B)
             if warm_status is not None:
                 warm_status = np.ascontiguousarray(warm_status, dtype=np.int32)
-            wout = np.empty((rows, B))
-            if model is not None:
-                check(library().mpc_run_batch_host_warm_model(self._h, B, B, int(npts), p(pose), p(px), p(py), p(model), p(warm), p(warm_status),
-                                                              p(wout), B, C.byref(warm_opts) if warm_opts is not None else None, p(out8),
-                                                              p(traj), p(status), p(iters), p(pre)), "mpc_run_batch_host_warm_model")
-                return {"out8": out8, "status": status, "iters": iters, "pre": pre, "ptsx": px, "ptsy": py, "traj": traj, "warm": wout}
-            check(library().mpc_run_batch_host_warm(self._h, B, B, int(npts), p(pose), p(px), p(py), p(warm), p(warm_status), p(wout), B,
-                                                    C.byref(warm_opts) if warm_opts is not None else None, p(out8), p(traj), p(status),
-                                                    p(iters), p(pre)), "mpc_run_batch_host_warm")
-            return {"out8": out8, "status": status, "iters": iters, "pre": pre, "ptsx": px, "ptsy": py, "traj": traj, "warm": wout}
-        if model is not None:
-            check(library().mpc_run_batch_host_model(self._h, B, B, int(npts), p(pose), p(px), p(py), p(model), p(out8), p(traj), p(status),
-                                                     p(iters), p(pre)), "mpc_run_batch_host_model")
-            return {"out8": out8, "status": status, "iters": iters, "pre": pre, "ptsx": px, "ptsy": py, "traj": traj}
-        check(library().mpc_run_batch_host(self._h, B, B, int(npts), p(pose), p(px), p(py), p(out8), p(traj), p(status), p(iters), p(pre)),
-              "mpc_run_batch_host")
-        return {"out8": out8, "status": status, "iters": iters, "pre": pre, "ptsx": px, "ptsy": py, "traj": traj}
+            res["warm"] = np.empty((rows, B))
+            warm_args = (p(warm), p(warm_status), p(res["warm"]), B, C.byref(warm_opts) if warm_opts is not None else None)
+        self._call("mpc_run_batch_host", (B, B, int(npts), p(pose), p(px), p(py)), (p(out8), p(traj), p(status), p(iters), p(pre)),
+                   p(model), warm_args)
+        return res
 
     def telemetry_torch(self, tel, ptsx, ptsy, extra_latency=0.0, want_out8=False, stream=None, warm=None, warm_status=None,
                         want_warm=False, warm_opts=None, warm_out=None, status_out=None, model=None):
@@ -275,28 +245,11 @@ class BatchedMPC:
         if model is not None:
             self._check_model(model, B)
         outs = (res["cmd"].data_ptr(), res["out8"].data_ptr() if want_out8 else None, res["status"].data_ptr(), C.c_void_p(s.cuda_stream))
+        warm_args = None
         if warm is not None or want_warm or warm_out is not None:
-            w_in, w_st, w_out, ld_warm = self._warm_args(res, B, dev, warm, warm_status, warm_out)
-            if model is not None:
-                check(library().mpc_telemetry_batch_device_warm_model(
-                    self._h, B, B, int(npts), tel.data_ptr(), float(extra_latency), ptsx.data_ptr(), ptsy.data_ptr(), model.data_ptr(), w_in,
-                    w_st, w_out, ld_warm, C.byref(warm_opts) if warm_opts is not None else None, *outs), "mpc_telemetry_batch_device_warm_model")
-                return res
-            check(library().mpc_telemetry_batch_device_warm(
-                self._h, B, B, int(npts), tel.data_ptr(), float(extra_latency), ptsx.data_ptr(), ptsy.data_ptr(), w_in, w_st, w_out,
-                ld_warm, C.byref(warm_opts) if warm_opts is not None else None, res["cmd"].data_ptr(),
-                res["out8"].data_ptr() if want_out8 else None, res["status"].data_ptr(), C.c_void_p(s.cuda_stream)),
-                "mpc_telemetry_batch_device_warm")
-            return res
-        if model is not None:
-            check(library().mpc_telemetry_batch_device_model(
-                self._h, B, B, int(npts), tel.data_ptr(), float(extra_latency), ptsx.data_ptr(), ptsy.data_ptr(), model.data_ptr(), *outs),
-                "mpc_telemetry_batch_device_model")
-            return res
-        check(library().mpc_telemetry_batch_device(
-            self._h, B, B, int(npts), tel.data_ptr(), float(extra_latency), ptsx.data_ptr(), ptsy.data_ptr(),
-            res["cmd"].data_ptr(), res["out8"].data_ptr() if want_out8 else None, res["status"].data_ptr(),
-            C.c_void_p(s.cuda_stream)), "mpc_telemetry_batch_device")
+            warm_args = self._warm_args(res, B, dev, warm, warm_status, warm_out) + (C.byref(warm_opts) if warm_opts is not None else None,)
+        self._call("mpc_telemetry_batch_device", (B, B, int(npts), tel.data_ptr(), float(extra_latency), ptsx.data_ptr(), ptsy.data_ptr()),
+                   outs, model.data_ptr() if model is not None else None, warm_args)
         return res
 
     def rollout_torch(self, state, coeffs, yaw_lo, yaw_hi, steps, weights=None, want_hist=True, stream=None, warm_start=False,
@@ -321,40 +274,15 @@ class BatchedMPC:
         s = stream if stream is not None else torch.cuda.current_stream(dev)
         if model is not None:
             self._check_model(model, B)
-            head = (self._h, B, B, int(steps), state.data_ptr(), coeffs.data_ptr(), yaw_lo.data_ptr(), yaw_hi.data_ptr(),
-                    weights.data_ptr() if weights is not None else None, model.data_ptr())
-            tail = (res["hist"].data_ptr() if want_hist else None, res["status"].data_ptr(), res["iters"].data_ptr(), C.c_void_p(s.cuda_stream))
-            opts = C.byref(warm_opts) if warm_opts is not None else None
-            if fused:
-                check(library().mpc_rollout_batch_device_fused_model(*head, 1 if warm_start else 0, opts, *tail),
-                      "mpc_rollout_batch_device_fused_model")
-                return res
-            if warm_start:
-                check(library().mpc_rollout_batch_device_warm_model(*head, opts, *tail), "mpc_rollout_batch_device_warm_model")
-                return res
-            check(library().mpc_rollout_batch_device_model(
-                self._h, B, B, int(steps), state.data_ptr(), coeffs.data_ptr(), yaw_lo.data_ptr(), yaw_hi.data_ptr(),
-                weights.data_ptr() if weights is not None else None, model.data_ptr(), res["hist"].data_ptr() if want_hist else None,
-                res["status"].data_ptr(), res["iters"].data_ptr(), C.c_void_p(s.cuda_stream)), "mpc_rollout_batch_device_model")
-            return res
-        if fused:
-            check(library().mpc_rollout_batch_device_fused(
-                self._h, B, B, int(steps), state.data_ptr(), coeffs.data_ptr(), yaw_lo.data_ptr(), yaw_hi.data_ptr(),
-                weights.data_ptr() if weights is not None else None, 1 if warm_start else 0,
-                C.byref(warm_opts) if warm_opts is not None else None, res["hist"].data_ptr() if want_hist else None,
-                res["status"].data_ptr(), res["iters"].data_ptr(), C.c_void_p(s.cuda_stream)), "mpc_rollout_batch_device_fused")
-            return res
-        if warm_start:
-            check(library().mpc_rollout_batch_device_warm(
-                self._h, B, B, int(steps), state.data_ptr(), coeffs.data_ptr(), yaw_lo.data_ptr(), yaw_hi.data_ptr(),
-                weights.data_ptr() if weights is not None else None, C.byref(warm_opts) if warm_opts is not None else None,
-                res["hist"].data_ptr() if want_hist else None, res["status"].data_ptr(), res["iters"].data_ptr(),
-                C.c_void_p(s.cuda_stream)), "mpc_rollout_batch_device_warm")
-            return res
-        check(library().mpc_rollout_batch_device(
-            self._h, B, B, int(steps), state.data_ptr(), coeffs.data_ptr(), yaw_lo.data_ptr(), yaw_hi.data_ptr(),
-            weights.data_ptr() if weights is not None else None, res["hist"].data_ptr() if want_hist else None,
-            res["status"].data_ptr(), res["iters"].data_ptr(), C.c_void_p(s.cuda_stream)), "mpc_rollout_batch_device")
+        head = (B, B, int(steps), state.data_ptr(), coeffs.data_ptr(), yaw_lo.data_ptr(), yaw_hi.data_ptr(),
+                weights.data_ptr() if weights is not None else None)
+        outs = (res["hist"].data_ptr() if want_hist else None, res["status"].data_ptr(), res["iters"].data_ptr(), C.c_void_p(s.cuda_stream))
+        opts = C.byref(warm_opts) if warm_opts is not None else None
+        m = model.data_ptr() if model is not None else None
+        if fused:      # (two forms: warm_start and opts are arguments of both)
+            self._call("mpc_rollout_batch_device_fused", head, (1 if warm_start else 0, opts) + outs, m)
+        else:
+            self._call("mpc_rollout_batch_device", head, outs, m, (opts,) if warm_start else None)
         return res
 
     # -- host path (numpy arrays; copies through PCIe) ------------------------
@@ -372,14 +300,15 @@ class BatchedMPC:
         out = np.empty((_abi.NOUT, B), dtype=dt); status = np.empty(B, dtype=np.int32); iters = np.empty(B, dtype=np.int32)
         traj = np.empty((2 * self.N, B), dtype=dt) if want_traj else None
         p = lambda a: a.ctypes.data if a is not None else None
+        head = (B, B, p(state), p(coeffs), p(yaw_lo), p(yaw_hi), p(weights))
+        outs = (p(out), p(traj), p(status), p(iters))
         if model is not None:
             model = np.ascontiguousarray(np.asarray(model, dtype=np.float64))
             assert model.shape == (_abi.NMODEL, B)
-            check(library().mpc_solve_batch_host_model(self._h, B, B, p(state), p(coeffs), p(yaw_lo), p(yaw_hi), p(weights), p(model), p(out),
-                                                       p(traj), p(status), p(iters)), "mpc_solve_batch_host_model")
-            return {"out": out, "status": status, "iters": iters, "traj": traj}
-        fn = library().mpc_solve_batch_host_f32 if self.f32 else library().mpc_solve_batch_host
-        check(fn(self._h, B, B, p(state), p(coeffs), p(yaw_lo), p(yaw_hi), p(weights), p(out), p(traj), p(status), p(iters)), "mpc_solve_batch_host")
+        if self.f32 and model is None:
+            check(library().mpc_solve_batch_host_f32(self._h, *head, *outs), "mpc_solve_batch_host")
+        else:
+            self._call("mpc_solve_batch_host", head, outs, p(model))
         return {"out": out, "status": status, "iters": iters, "traj": traj}
 
     def solve_numpy_warm(self, state, coeffs, yaw_lo, yaw_hi, warm=None, warm_status=None, weights=None, want_traj=False, warm_opts=None,
@@ -402,14 +331,11 @@ class BatchedMPC:
         traj = np.empty((2 * self.N, B)) if want_traj else None
         wout = np.empty((rows, B))
         p = lambda a: a.ctypes.data if a is not None else None
-        head = (self._h, B, B, p(state), p(coeffs), p(yaw_lo), p(yaw_hi), p(weights))
-        tail = (p(warm), p(warm_status), p(wout), B, C.byref(warm_opts) if warm_opts is not None else None, p(out), p(traj), p(status), p(iters))
         if model is not None:
             model = f(model)
             assert model.shape == (_abi.NMODEL, B)
-            check(library().mpc_solve_batch_host_warm_model(*head, p(model), *tail), "mpc_solve_batch_host_warm_model")
-        else:
-            check(library().mpc_solve_batch_host_warm(*head, *tail), "mpc_solve_batch_host_warm")
+        self._call("mpc_solve_batch_host", (B, B, p(state), p(coeffs), p(yaw_lo), p(yaw_hi), p(weights)), (p(out), p(traj), p(status), p(iters)),
+                   p(model), (p(warm), p(warm_status), p(wout), B, C.byref(warm_opts) if warm_opts is not None else None))
         return {"out": out, "status": status, "iters": iters, "traj": traj, "warm": wout}
 
     # -- deferred tails (MpcParams.tail_cut > 0, include/mpc_amd.h) -------------

@@ -129,3 +129,62 @@ def test_inflight_advice(pkg, golden_dir):
     assert pkg.inflight_advice(q, 32768) == 4
     q = p.copy(); q.f64_f32_start = 1
     assert pkg.inflight_advice(q, 65536) == 4
+
+
+BATCH_ENTRY = re.compile(r"mpc_(solve|run|telemetry|rollout|wire_telemetry)_batch")
+
+
+def declared_parameters(name):
+    """The parameter list of `name`'s declaration in include/mpc_amd.h (comments stripped: a mention there is no declaration)."""
+    from carnd_mpc_project_amd import _abi
+    header = re.sub(r"/\*.*?\*/|//[^\n]*", " ", open(os.path.join(_abi.ROOT, "include", "mpc_amd.h")).read(), flags=re.S)
+    found = re.findall(r"\b%s\s*\(([^()]*)\)\s*;" % re.escape(name), header)
+    assert len(found) == 1, (name, found)
+    params = [" ".join(q.split()) for q in found[0].split(",")]
+    return [] if params == ["void"] else params
+
+
+def c_kind(param):
+    """What ctypes has to pass for a declared parameter: "pointer", or the ctypes integer / floating type."""
+    if "*" in param:
+        return "pointer"
+    return {"int64_t": C.c_int64, "int": C.c_int, "double": C.c_double}[param.rsplit(" ", 1)[0].replace("const ", "")]
+
+
+def test_argtypes_match_the_header(pkg):
+    """Every argtypes list of the binding against the declaration it stands for: the same number of parameters and the same kind
+    at each position (a wrong count corrupts the call silently).  Every batch entry point must have one."""
+    from carnd_mpc_project_amd import _abi
+    lib = pkg.library()
+    checked = 0
+    for name in _abi.EXPORTS:
+        params = declared_parameters(name)
+        argtypes = getattr(lib, name).argtypes
+        if BATCH_ENTRY.match(name):
+            assert argtypes is not None, name
+        if argtypes is None:
+            continue
+        assert len(argtypes) == len(params), (name, len(argtypes), params)
+        for i, (t, q) in enumerate(zip(argtypes, params)):
+            kind = c_kind(q)
+            if kind == "pointer":
+                assert t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer), (name, i, q, t)
+            else:
+                assert t is kind, (name, i, q, t)
+        checked += 1
+    assert checked >= 36
+
+
+def test_every_batch_entry_point_refuses_a_null_handle(pkg):
+    """NULL handle, B = 0, NULL arrays: MPC_ERR_INVALID and a text from every form -- the handle is the first thing each checks, so
+    no device is needed."""
+    from carnd_mpc_project_amd import _abi
+    lib = pkg.library()
+    names = [n for n in _abi.EXPORTS if BATCH_ENTRY.match(n)]
+    assert len(names) == 36      # 8 families x 4 forms, the fused rollout's 2, the fp32 solve's 2
+    for name in names:
+        fn = getattr(lib, name)
+        args = [None if "*" in q else (0.0 if c_kind(q) is C.c_double else 0) for q in declared_parameters(name)]
+        assert fn(*args) == -1, name
+        err = lib.mpc_last_error()
+        assert err and b"NULL" in err, (name, err)
