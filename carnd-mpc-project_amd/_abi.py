@@ -99,6 +99,10 @@ EXPORTS = ["mpc_params_default", "mpc_params_load_json", "mpc_create", "mpc_set_
            "mpc_run_batch_device_model", "mpc_run_batch_host_model", "mpc_telemetry_batch_device_model", "mpc_telemetry_batch_host_model",
            "mpc_run_batch_device_warm_model", "mpc_run_batch_host_warm_model", "mpc_telemetry_batch_device_warm_model",
            "mpc_telemetry_batch_host_warm_model", "mpc_wire_telemetry_batch_host_model", "mpc_wire_telemetry_batch_host_warm_model"]
+# ... and every symbol include/mpc_amd_horizon.h declares (the part of the header that mpc_amd.h includes; tests/test_horizon.py)
+HORIZON_EXPORTS = ["mpc_solve_batch_device_horizon", "mpc_solve_batch_host_horizon", "mpc_solve_batch_device_warm_horizon",
+                   "mpc_solve_batch_host_warm_horizon", "mpc_rollout_batch_device_horizon", "mpc_rollout_batch_device_warm_horizon",
+                   "mpc_rollout_batch_device_fused_horizon"]
 
 _lib = None
 
@@ -164,22 +168,23 @@ def library():
     # The batch entry points: one row per family -- (head, outs, stream or not) -- and the rule of include/mpc_amd.h for its four forms:
     # _model puts `model` (one pointer) behind the head, _warm puts `warm` (warm_in, warm_status, warm_out, ld_warm, opts; the
     # stepwise rollout: opts alone) behind that.  The fused rollout has two forms: its warm_start, opts pair leads its outs.
+    # A third rule for the families marked so (the solve and the rollouts): _horizon is _model plus `horizon` (one pointer) behind `model`.
     I64, OPTS = C.c_int64, C.POINTER(MpcWarmOpts)
     H = [C.c_void_p, I64, I64]
     WARM = [DP] * 3 + [I64, OPTS]
-    families = [("mpc_solve_batch_device", H + [DP] * 5, [DP] * 4, True, WARM),
-                ("mpc_solve_batch_host", H + [DP] * 5, [DP] * 4, False, WARM),
-                ("mpc_run_batch_device", H + [C.c_int] + [DP] * 3, [DP] * 5, True, WARM),
-                ("mpc_run_batch_host", H + [C.c_int] + [DP] * 3, [DP] * 5, False, WARM),
-                ("mpc_telemetry_batch_device", H + [C.c_int, DP, C.c_double] + [DP] * 2, [DP] * 3, True, WARM),
-                ("mpc_telemetry_batch_host", H + [C.c_int, DP, C.c_double] + [DP] * 2, [DP] * 2, False, WARM),
-                ("mpc_wire_telemetry_batch_host", [C.c_void_p, I64, C.POINTER(MpcWireTelemetry), DP, C.c_double], [DP] * 2, False, WARM),
-                ("mpc_rollout_batch_device", H + [C.c_int] + [DP] * 5, [DP] * 3, True, [OPTS]),
-                ("mpc_rollout_batch_device_fused", H + [C.c_int] + [DP] * 5, [C.c_int, OPTS] + [DP] * 3, True, None)]
-    for family, head, outs, stream, warm in families:
+    families = [("mpc_solve_batch_device", H + [DP] * 5, [DP] * 4, True, WARM, True),
+                ("mpc_solve_batch_host", H + [DP] * 5, [DP] * 4, False, WARM, True),
+                ("mpc_run_batch_device", H + [C.c_int] + [DP] * 3, [DP] * 5, True, WARM, False),
+                ("mpc_run_batch_host", H + [C.c_int] + [DP] * 3, [DP] * 5, False, WARM, False),
+                ("mpc_telemetry_batch_device", H + [C.c_int, DP, C.c_double] + [DP] * 2, [DP] * 3, True, WARM, False),
+                ("mpc_telemetry_batch_host", H + [C.c_int, DP, C.c_double] + [DP] * 2, [DP] * 2, False, WARM, False),
+                ("mpc_wire_telemetry_batch_host", [C.c_void_p, I64, C.POINTER(MpcWireTelemetry), DP, C.c_double], [DP] * 2, False, WARM, False),
+                ("mpc_rollout_batch_device", H + [C.c_int] + [DP] * 5, [DP] * 3, True, [OPTS], True),
+                ("mpc_rollout_batch_device_fused", H + [C.c_int] + [DP] * 5, [C.c_int, OPTS] + [DP] * 3, True, None, True)]
+    for family, head, outs, stream, warm, has_horizon in families:
         tail = outs + ([C.c_void_p] if stream else [])
         for w_name, w in [("", [])] + ([("_warm", warm)] if warm else []):
-            for m_name, m in (("", []), ("_model", [DP])):
+            for m_name, m in (("", []), ("_model", [DP])) + ((("_horizon", [DP, DP]),) if has_horizon else ()):
                 getattr(L, family + w_name + m_name).argtypes = head + m + w + tail
     L.mpc_solve_batch_device_f32.argtypes = L.mpc_solve_batch_device.argtypes      # (the same pointers, to floats)
     L.mpc_solve_batch_host_f32.argtypes = L.mpc_solve_batch_host.argtypes

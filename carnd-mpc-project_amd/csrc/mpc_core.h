@@ -199,8 +199,12 @@ template <class R> struct AddrSpace;
 template <> struct AddrSpace<double> { typedef gdouble g; typedef ldouble l; };
 template <> struct AddrSpace<float> { typedef gfloat g; typedef lfloat l; };
 
-template <bool STAGING, class R>
+/* LANE_ROWS (the HORIZON builds of the lane kernel: an instance's number of stages is its own, so two lanes of a wave may be on
+ * different stages of the same sweep): the row offset is an ordinary per-lane value -- no readfirstlane, a vector offset on the
+ * wave-uniform tile base, plain global_load / global_store -- and nothing is staged. */
+template <bool STAGING, class R, bool LANE_ROWS = false>
 struct TiledWorkspace {
+  static_assert(!(STAGING && LANE_ROWS), "LDS-DMA copies record k of every lane from a scalar base: per-lane rows are not staged");
   using F = Fields<R>;
   typedef typename AddrSpace<R>::g greal;
   typedef typename AddrSpace<R>::l lreal;
@@ -213,7 +217,8 @@ struct TiledWorkspace {
   static_assert(F::STAGE_SZ % F::G == 0 && F::IT_SZ % F::G == 0, "whole groups");
   /* uniform part: row of (stage k, field f) + position inside the group; vector part: lane and slot */
   MPC_HD gchar *row(int k, int f) const {
-    return (gchar *)tile + MPC_UNIFORM(((unsigned)k * GROUPS + ((unsigned)f / G)) * 1024u + ((unsigned)f % G) * (unsigned)sizeof(R));
+    if constexpr (LANE_ROWS) return (gchar *)tile + (((unsigned)k * GROUPS + ((unsigned)f / G)) * 1024u + ((unsigned)f % G) * (unsigned)sizeof(R));
+    else return (gchar *)tile + MPC_UNIFORM(((unsigned)k * GROUPS + ((unsigned)f / G)) * 1024u + ((unsigned)f % G) * (unsigned)sizeof(R));
   }
   MPC_HD unsigned voff(int I) const { return (unsigned)lane * 16u + ((unsigned)I / G) * 1024u; }
   MPC_HD greal &it(int k, int I, int f) const { return *(greal *)(row(k, f) + voff(I)); }
@@ -682,6 +687,20 @@ struct ModelVals {
          m.max_acceleration > 0.0 && m.max_acceleration < HUGE_VAL && m.max_deceleration < 0.0 && m.max_deceleration > -HUGE_VAL &&
          m.max_speed > 0.0 && m.max_speed < HUGE_VAL;
     return ok ? m : of(P);
+  }
+};
+
+/* What an instance of the mpc_*_horizon entry points brings along: its horizon n (Config::N of the reference, 3 .. the handle's N)
+ * and its column of `model` -- col = nullptr: the handle's own six values, taken as they are (no column is judged). */
+struct HorizonColumn {
+  const double *col;              /* the instance's column of model [MPC_NMODEL][ld], or nullptr */
+  int64_t ld;
+  int n;
+  MPC_HD ModelVals vals(const MpcParams &P, bool &ok) const {
+    if (!col) { ok = true; return ModelVals::of(P); }
+    const double *c = col;
+    const int64_t l = ld;
+    return ModelVals::column(P, [c, l](int q) { return c[q * l]; }, ok);
   }
 };
 
@@ -2148,13 +2167,26 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
     const int s = setup_vals(m, state6, coef5, yaw_lo, yaw_hi, w12, write_start);
     return ok ? s : MPC_STATUS_INFEASIBLE;
   }
+  /* The same for an instance that brings its own horizon as well (the mpc_*_horizon entry points): n = hc.n steps, 8n - 2 variables
+   * and 6n rows as the reference poses them with Config::N = n, on the first n - 1 stage records of the instance's column (the
+   * record of the initial-state rows at index n - 1).  Everything that counts stages -- the sweeps, the warm rules, unpack -- reads
+   * M, so this is the only place that knows.  The six model values: the column's, or the handle's own without one.  A horizon
+   * outside 3 .. P.N ends like an unusable column: MPC_STATUS_INFEASIBLE, the start point of the handle's horizon. */
+  MPC_HD int setup_horizon(const HorizonColumn &hc, const R *state6, const R *coef5, R yaw_lo, R yaw_hi, const R *w12, bool write_start = true) {
+    bool ok;
+    const ModelVals m = hc.vals(P, ok);
+    const bool n_ok = hc.n >= 3 && hc.n <= P.N;
+    const int s = setup_vals(m, state6, coef5, yaw_lo, yaw_hi, w12, write_start, n_ok ? hc.n - 1 : 0);
+    return ok && n_ok ? s : MPC_STATUS_INFEASIBLE;
+  }
+  /* (stages = 0: the handle's N - 1) */
   template <class MV>
-  MPC_HD int setup_vals(const MV &m, const R *state6, const R *coef5, R yaw_lo, R yaw_hi, const R *w12, bool write_start) {
+  MPC_HD int setup_vals(const MV &m, const R *state6, const R *coef5, R yaw_lo, R yaw_hi, const R *w12, bool write_start, int stages = 0) {
     MPC_UNROLL
     for (int i = 0; i < 6; i++) st[i] = state6[i];
     MPC_UNROLL
     for (int i = 0; i < MPC_NCOEF; i++) coef[i] = coef5[i];
-    M = P.N - 1; dt = (R)m.dt; iLf = (R)(1.0 / m.Lf); dtLf = (R)(m.dt / m.Lf);
+    M = stages > 0 ? stages : P.N - 1; dt = (R)m.dt; iLf = (R)(1.0 / m.Lf); dtLf = (R)(m.dt / m.Lf);
     /* IPOPT's bound_relax_factor (default 1e-8, untouched by MPC.cpp:160-179): every finite variable bound is moved
      * outwards by factor * max(1, |bound|) before the solve; the start point is pushed inside the RELAXED bounds and
      * the returned point is projected back into the caller's (unpack).  This is what makes a solve that starts ON a
@@ -2669,6 +2701,12 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
     bool ok;
     unpack_vals(ModelVals::column(P, model, ok), out, traj, want_traj, yaw_lo, yaw_hi);
   }
+  /* ... and with its own horizon: traj keeps the handle's shape, x_0 .. x_{n-1} in rows 0 .. n-1 and y in rows N .. N+n-1 (M says) */
+  template <class OutF, class TrajF>
+  MPC_HD void unpack_horizon(const HorizonColumn &hc, OutF out, TrajF traj, bool want_traj, R yaw_lo, R yaw_hi) const {
+    bool ok;
+    unpack_vals(hc.vals(P, ok), out, traj, want_traj, yaw_lo, yaw_hi);
+  }
   template <class MV, class OutF, class TrajF>
   MPC_HD void unpack_vals(const MV &m, OutF out, TrajF traj, bool want_traj, R yaw_lo, R yaw_hi) const {
     const int I = it(cur);
@@ -2747,7 +2785,8 @@ struct RolloutCar {
  * instance out: the group's first lane in the wave kernels -- instance_store.  The wave kernels (mpc_solve_wave_kernel), the
  * test-only CPU build (tests/host_twin) and solve_instance below are uses of these three and spell nothing of it out themselves;
  * the lane kernel drives Solver::step through a state machine of its own.  Two arguments say which form a call takes, by type:
- *   col   NoColumn: the handle's model values (setup / unpack); or the getter of the instance's column (setup_model / unpack_model)
+ *   col   NoColumn: the handle's model values (setup / unpack); or the getter of the instance's column (setup_model / unpack_model);
+ *         or a HorizonColumn: the instance's horizon and its column, if any (setup_horizon / unpack_horizon)
  *   warm  NoWarm: solve(); or a WarmStart (solve_warm, then warm_store) */
 struct NoColumn {};
 struct NoWarm {};
@@ -2793,6 +2832,7 @@ template <class SV, class Col, class Warm, class R>
 MPC_HD int instance_solve(SV &S, Col col, const Warm &warm, const R *st, const R *cf, R yaw_lo, R yaw_hi, const R *w) {
   int r;
   if constexpr (std::is_same<Col, NoColumn>::value) r = S.setup(st, cf, yaw_lo, yaw_hi, w, true);
+  else if constexpr (std::is_same<Col, HorizonColumn>::value) r = S.setup_horizon(col, st, cf, yaw_lo, yaw_hi, w, true);
   else r = S.setup_model(col, st, cf, yaw_lo, yaw_hi, w, true);
   if (r != MPC_STATUS_SUCCESS) return r;
   if constexpr (std::is_same<Warm, NoWarm>::value) return S.solve();
@@ -2803,6 +2843,7 @@ MPC_HD int instance_solve(SV &S, Col col, const Warm &warm, const R *st, const R
 template <class SV, class Col, class Warm, class OutF, class TrajF, class R>
 MPC_HD int instance_store(const SV &S, Col col, const Warm &warm, OutF out, TrajF traj, bool want_traj, R yaw_lo, R yaw_hi) {
   if constexpr (std::is_same<Col, NoColumn>::value) S.unpack(out, traj, want_traj, yaw_lo, yaw_hi);
+  else if constexpr (std::is_same<Col, HorizonColumn>::value) S.unpack_horizon(col, out, traj, want_traj, yaw_lo, yaw_hi);
   else S.unpack_model(col, out, traj, want_traj, yaw_lo, yaw_hi);
   if constexpr (!std::is_same<Warm, NoWarm>::value) {
     if (warm.out) {

@@ -63,6 +63,7 @@ constexpr int kCounterInts = kPhaseCounterInts + mpc::kTakeBins;   /* ... and be
 static_assert(kCounterInts <= 64, "a counter block is zeroed by the lanes of one wave");
 constexpr int kCounterRing = 32;    /* counter blocks: solve call n uses block n % 32 and zeroes block (n + 16) % 32 for its next user */
 constexpr int kParkRows = 47;       /* Solver::PARK_N */
+constexpr size_t kMailboxBytes = (size_t)kParkRows * 64 * sizeof(double) + 2 * 64 * sizeof(int);   /* lane compaction: the scalars of up to 64 moving instances, their index and passes */
 constexpr int kFinPromote = -2, kFinScratch = -3;   /* a lane that waits to hand its instance to the fp64 phase (promoted / to be solved from scratch) */
 constexpr int kTailMaxRing = 512;   /* deferred tails: batches whose stragglers may be outstanding at once */
 constexpr int kFreshRing = 24;      /* fresh queues: one per batch between its launch and the completion of the tail slice that absorbs its stragglers */
@@ -188,9 +189,9 @@ struct MpcPhase {
   int64_t ord_ld;
 };
 
-/* What a build of mpc_solve_kernel gets on top of MpcPhase is composed of three parts, and MpcPhaseOf<ROLL, WARM, MODEL> inherits
- * exactly the parts its build reads; MpcPhaseOf<false, false, false> is MpcPhase itself, so the kernel arguments of the builds
- * without any of them are what they were.
+/* What a build of mpc_solve_kernel gets on top of MpcPhase is composed of four parts (the fourth, HORIZON, further down), and
+ * MpcPhaseOf<ROLL, WARM, MODEL, HORIZON> inherits exactly the parts its build reads; MpcPhaseOf<false, false, false> is MpcPhase
+ * itself, so the kernel arguments of the builds without any of them are what they were.
  *
  * WARM (the mpc_*_warm entry points; the warm rollouts): mpc::WarmCall, the warm buffers addressed by INSTANCE at both ends --
  * quantity-major, so neighbouring lanes coalesce like every other array at the ABI, and lane compaction may move an instance between
@@ -218,20 +219,29 @@ struct MpcRollPart {
   int32_t *status, *iters;        /* per car: worst status, summed iterations (iters may be nullptr) */
 };
 
+/* HORIZON (the mpc_*_horizon entry points): the horizon of every instance, [ld] int32 addressed by INSTANCE like the model values,
+ * and read in the same places -- wherever a lane runs set-up for an instance -- so it follows the instance from lane to lane.  These
+ * builds are MODEL builds with one more part; their `model` may be nullptr (the handle's own six values). */
+struct MpcHorizonPart {
+  const int32_t *horizon;
+};
+
 template <bool ON, class Part> struct MpcPartIf : Part {};
 template <class Part> struct MpcPartIf<false, Part> {};
-template <bool ROLL, bool WARM, bool MODEL>
-struct MpcPhaseParts : MpcPhase, MpcPartIf<WARM, mpc::WarmCall>, MpcPartIf<ROLL, MpcRollPart>, MpcPartIf<MODEL, MpcModelPart> {};
-template <bool ROLL, bool WARM, bool MODEL>
-using MpcPhaseOf = std::conditional_t<ROLL || WARM || MODEL, MpcPhaseParts<ROLL, WARM, MODEL>, MpcPhase>;
+template <bool ROLL, bool WARM, bool MODEL, bool HORIZON = false>
+struct MpcPhaseParts : MpcPhase, MpcPartIf<WARM, mpc::WarmCall>, MpcPartIf<ROLL, MpcRollPart>, MpcPartIf<MODEL, MpcModelPart>, MpcPartIf<HORIZON, MpcHorizonPart> {};
+template <bool ROLL, bool WARM, bool MODEL, bool HORIZON = false>
+using MpcPhaseOf = std::conditional_t<ROLL || WARM || MODEL || HORIZON, MpcPhaseParts<ROLL, WARM, MODEL, HORIZON>, MpcPhase>;
 /* a phase's value from its parts: those the build does not inherit are left out */
-template <bool ROLL, bool WARM, bool MODEL>
-static MpcPhaseOf<ROLL, WARM, MODEL> phase_of(const MpcPhase &T, const mpc::WarmCall &warm, const MpcRollPart &roll, const MpcModelPart &model) {
-  MpcPhaseOf<ROLL, WARM, MODEL> X;
+template <bool ROLL, bool WARM, bool MODEL, bool HORIZON = false>
+static MpcPhaseOf<ROLL, WARM, MODEL, HORIZON> phase_of(const MpcPhase &T, const mpc::WarmCall &warm, const MpcRollPart &roll, const MpcModelPart &model,
+                                                       const MpcHorizonPart &horizon = {}) {
+  MpcPhaseOf<ROLL, WARM, MODEL, HORIZON> X;
   static_cast<MpcPhase &>(X) = T;
   if constexpr (WARM) static_cast<mpc::WarmCall &>(X) = warm;
   if constexpr (ROLL) static_cast<MpcRollPart &>(X) = roll;
   if constexpr (MODEL) static_cast<MpcModelPart &>(X) = model;
+  if constexpr (HORIZON) static_cast<MpcHorizonPart &>(X) = horizon;
   return X;
 }
 
@@ -320,19 +330,26 @@ template <class RIO, class R> struct OutRef {
  * With WARM: warm_point() judges a record against the relaxed box that setup_model has just set from the column, and the cold solve
  * that follows a refused record or a failed warm attempt starts from the solver's own members -- no set-up in between.  With ROLL:
  * the car taken again is set up from its column like a fresh one, and the hand-over of a step projects into the column's limits. */
-template <bool STAGING, class R, class RIO = R, class RSRC = RIO, bool SOC = false, bool WARM = false, bool ROLL = false, bool MODEL = false>
+/* HORIZON (the mpc_*_horizon entry points): a MODEL build in which every set-up also reads the instance's horizon n from T.horizon
+ * (Solver::setup_horizon: M = n - 1 stages) and `model` may be nullptr.  The lanes of a wave then differ in their number of stages,
+ * so these builds are not staged and address their rows per lane (TiledWorkspace<false, R, true>): every sweep is an ordinary
+ * divergent loop, a lane leaves it after its own M stages, and a pass of the wave costs the longest horizon among its running lanes.
+ * Their dynamic LDS is the mailbox of lane compaction alone.  A moved instance is set up again from its index, horizon included. */
+template <bool STAGING, class R, class RIO = R, class RSRC = RIO, bool SOC = false, bool WARM = false, bool ROLL = false, bool MODEL = false,
+          bool HORIZON = false>
 __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
     const MpcParams P, const int64_t B, const int64_t ld, const int64_t ldo, const RIO *__restrict__ state,
     const RIO *__restrict__ coeffs, const RIO *__restrict__ yaw_lo, const RIO *__restrict__ yaw_hi,
     const RIO *__restrict__ weights, RIO *__restrict__ out, RIO *__restrict__ traj,
     int32_t *__restrict__ status, int32_t *__restrict__ iters, R *__restrict__ wsbase,
     const int64_t tile_reals,
-    const MpcPhaseOf<ROLL, WARM, MODEL> T) {
+    const MpcPhaseOf<ROLL, WARM, MODEL, HORIZON> T) {
   extern __shared__ double smem[];
+  static_assert(!HORIZON || (MODEL && !STAGING && !SOC), "per-instance horizon: a MODEL build without staging and SOC");
   static_assert(!WARM || (sizeof(R) == 8 && std::is_same<R, RIO>::value && std::is_same<R, RSRC>::value && !SOC), "warm start: the plain fp64 solve only");
   static_assert(!ROLL || (sizeof(R) == 8 && std::is_same<R, RIO>::value && std::is_same<R, RSRC>::value && !SOC), "fused rollout: the plain fp64 solve only");
   static_assert(!MODEL || (sizeof(R) == 8 && std::is_same<R, RIO>::value && std::is_same<R, RSRC>::value), "per-instance model values: the fp64 solve only");
-  using WS = std::conditional_t<SOC, mpc::TiledSocWorkspace<STAGING, R>, mpc::TiledWorkspace<STAGING, R>>;
+  using WS = std::conditional_t<SOC, mpc::TiledSocWorkspace<STAGING, R>, mpc::TiledWorkspace<STAGING, R, HORIZON>>;
   using SV = mpc::Solver<WS, R, 0, SOC>;
   using FL = mpc::Fields<R>;
   static_assert(SV::PARK_N == kParkRows, "park buffer rows");
@@ -357,7 +374,7 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
     /* ---- lane compaction, part 1: is it worth it now?  (see MpcPhase.compact_gap) ---- */
     bool want_compact = false;
     int cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, g_min = 0;
-    if (STAGING && T.compact_gap > 0) {
+    if ((STAGING || HORIZON) && T.compact_gap > 0) {
       if (MPC_WAVE_ANY(more) && (int64_t)__hip_atomic_load(T.take, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= n_work) more = false;
       if (!MPC_WAVE_ANY(more)) {
         if (cooldown > 0) --cooldown;
@@ -410,7 +427,10 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
             using Car = mpc::RolloutCar;
             double *o = T.hist + (int64_t)step * T.hist_step + i;
             const int64_t l = ldo;
-            if constexpr (MODEL) {             /* the car's own limits, from its column */
+            if constexpr (HORIZON) {
+              S.unpack_horizon(mpc::HorizonColumn{T.model ? T.model + i : nullptr, ld, T.horizon[i]}, [o, l](int q) { return OutRef<RIO, R>{o + q * l}; },
+                               [](int) { return OutRef<RIO, R>{nullptr}; }, false, (R)yaw_lo[i], (R)yaw_hi[i]);
+            } else if constexpr (MODEL) {             /* the car's own limits, from its column */
               const double *mc = T.model + i;
               int64_t lm = ld;
               if constexpr (!ROLL) lm = T.ld_model;
@@ -443,7 +463,12 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
           RIO *o = out + i;
           RIO *t = traj ? traj + i : nullptr;
           const int64_t l = ldo;
-          if constexpr (MODEL) {
+          if constexpr (HORIZON) {
+            int64_t lm = ld;
+            if constexpr (!ROLL) lm = T.ld_model;
+            S.unpack_horizon(mpc::HorizonColumn{T.model ? T.model + i : nullptr, lm, T.horizon[i]}, [o, l](int q) { return OutRef<RIO, R>{o + q * l}; },
+                             [t, l](int q) { return OutRef<RIO, R>{t + q * l}; }, traj != nullptr, (R)yaw_lo[i], (R)yaw_hi[i]);
+          } else if constexpr (MODEL) {
             const double *mc = T.model + i;
             int64_t lm = ld;
             if constexpr (!ROLL) lm = T.ld_model;
@@ -511,7 +536,12 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
             if constexpr (WARM && ROLL) warm_cand = again_warm;   /* (the column this lane stored when it finished the step before) */
             else if constexpr (WARM) warm_cand = T.warm_in != nullptr && (T.warm_status == nullptr || T.warm_status[i] == MPC_STATUS_SUCCESS);
             int s0;
-            if constexpr (MODEL) {
+            if constexpr (HORIZON) {
+              int64_t lm = ld;
+              if constexpr (!ROLL) lm = T.ld_model;
+              s0 = S.setup_horizon(mpc::HorizonColumn{T.model ? T.model + i : nullptr, lm, T.horizon[i]}, st, cf, (R)yaw_lo[i], (R)yaw_hi[i], w,
+                                   (!T.resume || from_scratch) && !warm_cand);
+            } else if constexpr (MODEL) {
               const double *mc = T.model + i;
               int64_t lm = ld;
               if constexpr (!ROLL) lm = T.ld_model;
@@ -606,7 +636,7 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
       const int n = n_mv < n_fr ? n_mv : n_fr;
       if (n > 0) {
         ws.stage_drain();                        /* the trial sweep's stores have landed, the staging buffers are idle */
-        static_assert(!STAGING || staging_lds_bytes<R>() >= (size_t)kParkRows * 64 * sizeof(R) + 2 * 64 * sizeof(int), "the mailbox must fit the staging buffers");
+        static_assert(!STAGING || staging_lds_bytes<R>() >= (size_t)kParkRows * 64 * sizeof(R) + 2 * 64 * sizeof(int), "the mailbox must fit the staging buffers");      /* (HORIZON builds: launched with exactly the mailbox, kMailboxBytes) */
         R *mb = (R *)smem;                       /* [kParkRows][64]: Solver::park scalars (in the solver's own precision) ... */
         int *mi = (int *)(mb + kParkRows * 64);  /* ... [2][64]: instance, passes */
         const unsigned long long below = (1ull << threadIdx.x) - 1ull;
@@ -622,6 +652,7 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        if constexpr (HORIZON) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      /* (not staged: stage_drain() above is empty, and a lane is about to read another lane's column) */
         if (is_dst) {
           unsigned long long m = mv;
           for (int r = 0; r < my_f; ++r) m &= m - 1ull;
@@ -639,7 +670,11 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
 #pragma unroll
             for (int q = 0; q < MPC_NW; q++) w[q] = (R)P.weights[q];
           }
-          if constexpr (MODEL) {      /* the instance has changed lanes: its column comes with it */
+          if constexpr (HORIZON) {    /* the instance has changed lanes: its horizon and its column come with it */
+            int64_t lm = ld;
+            if constexpr (!ROLL) lm = T.ld_model;
+            (void)S.setup_horizon(mpc::HorizonColumn{T.model ? T.model + i : nullptr, lm, T.horizon[i]}, st, cf, (R)yaw_lo[i], (R)yaw_hi[i], w, false);
+          } else if constexpr (MODEL) {      /* the instance has changed lanes: its column comes with it */
             const double *mc = T.model + i;
             int64_t lm = ld;
             if constexpr (!ROLL) lm = T.ld_model;
@@ -651,7 +686,9 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
           wsrc.lane = src;
           /* (plain loads: the column was written through this CU's own L1 by a lane of this wave, and stage_drain() has waited
            * for the stores; keeping two stages in flight was measured: no difference) */
-          for (int k = 0; k < P.N - 1; ++k) {
+          int n_rec = P.N - 1;
+          if constexpr (HORIZON) n_rec = S.M;      /* (the instance's own stages; set-up above has read its horizon) */
+          for (int k = 0; k < n_rec; ++k) {
             R rec[FL::IT_SZ];
 #pragma unroll
             for (int f = 0; f < FL::IT_SZ; f++) rec[f] = wsrc.it(k, I, f);
@@ -1238,6 +1275,8 @@ struct MpcHandle {
   /* warm start (allocated on first use): the rollout's warm buffer, [mpc_warm_rows(N)][io_stride] doubles, and the device side of the
    * host entry point's warm_in / warm_out (one block, read and written in place) with the status the warm data came with */
   double *d_warm = nullptr, *d_warm_io = nullptr;
+  double *d_warm_o = nullptr;         /* host forms with a horizon: warm_out on its own (rows an instance does not write come back as the caller has them) */
+  int32_t *d_horizon = nullptr;       /* ... and the horizons of a host-array call */
   double *d_model = nullptr;      /* the device side of mpc_solve_batch_host_model's model array (allocated on first use) */
   int32_t *d_warm_st = nullptr;
   int64_t n_roll_fused = 0, n_roll_stepwise = 0;   /* mpc_rollout_batch_device_fused calls that ran the fused kernel / the stepwise loop (mpc_rollout_fused_info) */
@@ -1454,6 +1493,8 @@ extern "C" void mpc_destroy(MpcHandle *h) {
   if (h->d_warm) (void)hipFree(h->d_warm);
   if (h->d_model) (void)hipFree(h->d_model);
   if (h->d_warm_io) (void)hipFree(h->d_warm_io);
+  if (h->d_warm_o) (void)hipFree(h->d_warm_o);
+  if (h->d_horizon) (void)hipFree(h->d_horizon);
   if (h->d_warm_st) (void)hipFree(h->d_warm_st);
   if (h->tail_ready) (void)tail_drain(h);         /* stragglers still queued are finished: their batches' arrays may be read afterwards */
   if (h->tail_stream) (void)hipStreamSynchronize(h->tail_stream);
@@ -1921,6 +1962,8 @@ struct CallExtras {
   const double *model = nullptr;   /* a model call (fp64 handles): [MPC_NMODEL][ld_model], see MpcModelPart */
   int64_t ld_model = 0;            /* 0: the ld of the solve's inputs.  (run() sets its own: it solves from the handle's rows at the handle's stride, the columns stay where the caller has them) */
   bool model_wave = false;         /* a model call of the run() / telemetry entry points: the wave MODEL kernels up to wave_max_batch */
+  const int32_t *horizon = nullptr;   /* a horizon call (fp64 handles, no SOC): [ld] like the inputs; dispatched as a model call, `model` may be NULL */
+  bool model_call() const { return model != nullptr || horizon != nullptr; }
   const WarmIO *warm_io() const { return warm ? &w : nullptr; }
 };
 /* ... and where a deferring launch hands its stragglers: its batch's slot of the ring and its fresh queue */
@@ -1944,7 +1987,8 @@ template <int V> using Int = std::integral_constant<int, V>;
 template <class F>
 static int with_bool(bool b, F f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 /* f(soc, warm, model): the builds of an fp64 solve kernel, all six of them -- plain, SOC, WARM, MODEL, MODEL+SOC, MODEL+WARM.  A warm
- * call has no SOC (call_extras refuses it on a handle with max_soc > 0), so there is no SOC+WARM build. */
+ * call has no SOC (call_extras refuses it on a handle with max_soc > 0), so there is no SOC+WARM build.  (The HORIZON builds of the
+ * lane kernel -- cold and WARM, never SOC -- are chosen in launch_lanes and rollout_fused_impl, which are their only launch sites.) */
 template <class F>
 static int with_build(bool soc, bool warm, bool model, F f) {
   constexpr std::true_type yes{};
@@ -2017,12 +2061,13 @@ static int launch_wave(MpcHandle *h, const SolveIO<R> &io, hipStream_t s, bool s
 }
 
 /* The lane kernel (an instance per lane; `ws`: the workspace of the phase).  single: the build that MPC_STAGING and, on an fp64
- * handle, with_build select: max_soc, a warm call, a model call (model.model).  The two phases of a mixed-precision solve are builds of
+ * handle, with_build select: max_soc, a warm call, a model call (model.model) -- or, with `horizon`, the HORIZON builds (cold, WARM; never
+ * staged, their LDS the mailbox of lane compaction).  The two phases of a mixed-precision solve are builds of
  * their own: the fp32 solver, and the fp64 solver that takes its iterates from fp32 records -- whatever RIO, the type at the ABI, is. */
 enum class LaneBuild { single, mixed_f32, mixed_f64 };
 template <class RIO>
 static int launch_lanes(MpcHandle *h, LaneBuild build, const SolveIO<RIO> &io, hipStream_t s, void *ws, bool soc, const MpcPhase &T,
-                        const WarmIO *warm = nullptr, const MpcModelPart &model = {}) {
+                        const WarmIO *warm = nullptr, const MpcModelPart &model = {}, const int32_t *horizon = nullptr) {
   const unsigned grid = (unsigned)((io.B + kBlock - 1) / kBlock);
   /* (r, rsrc: values of the solver's reals and of the reals its resumed iterates come in) */
   auto go = [&](auto staging, auto r, auto rsrc, auto soc_build, auto warm_build, int64_t tile_reals, auto model_build) {
@@ -2034,6 +2079,14 @@ static int launch_lanes(MpcHandle *h, LaneBuild build, const SolveIO<RIO> &io, h
   };
   constexpr std::true_type yes{};
   constexpr std::false_type no{};
+  if constexpr (sizeof(RIO) == 8) {
+    if (horizon && build == LaneBuild::single)
+      return with_bool(warm != nullptr, [&](auto warm_build) {
+        constexpr bool WARM = decltype(warm_build)::value;
+        return launch_kernel(mpc_solve_kernel<false, double, double, double, false, WARM, false, true, true>, grid, T.compact_gap > 0 ? kMailboxBytes : 0, s, h,
+                             io, (double *)ws, h->ws_stride, phase_of<false, WARM, true, true>(T, warm ? *warm : WarmIO{}, {}, model, {horizon}));
+      });
+  }
   if (build == LaneBuild::mixed_f32) return go(yes, float{}, RIO{}, no, no, h->ws_stride_f32, no);
   if (build == LaneBuild::mixed_f64) return with_bool(soc, [&](auto soc_build) { return go(yes, double{}, float{}, soc_build, no, h->ws_stride_f64, no); });
   return with_bool(h->staging, [&](auto staging) {
@@ -2189,17 +2242,20 @@ extern "C" int mpc_warm_opts_default(MpcWarmOpts *o) {
  * model needs an fp64 handle that does not start in fp32.  A call with neither is checked for its handle only. */
 static CallExtras call_extras(const MpcHandle *h, const double *model = nullptr, bool warm = false, const double *warm_in = nullptr,
                               const int32_t *warm_status = nullptr, double *warm_out = nullptr, int64_t ld_warm = 0,
-                              const MpcWarmOpts *opts = nullptr) {
+                              const MpcWarmOpts *opts = nullptr, const int32_t *horizon = nullptr) {
   CallExtras x;
-  x.warm = warm; x.model = model;
+  x.warm = warm; x.model = model; x.horizon = horizon;
   x.w = WarmIO{warm_in, warm_status, warm_out, ld_warm, {}, 0};
   const auto refuse = [&x](int rc, const char *why) { g_last_error = why; x.refused = rc; return x; };
   if (!h) return refuse(MPC_ERR_INVALID, "NULL handle");
   const bool f64 = h->params.precision == MPC_PRECISION_F64;
-  if (model && !f64) return refuse(MPC_ERR_INVALID, "per-instance model values: fp64 handles only (this one was created with MPC_PRECISION_F32)");
+  if ((model || horizon) && !f64) return refuse(MPC_ERR_INVALID, "per-instance model values: fp64 handles only (this one was created with MPC_PRECISION_F32)");
+  if (horizon && h->params.max_soc > 0)
+    return refuse(MPC_ERR_UNSUPPORTED, "a per-instance horizon is not available with the second-order correction (max_soc > 0): set MpcParams.max_soc = 0, or pass horizon = NULL");
   if (!warm) return x;
-  if (!model && !f64) return refuse(MPC_ERR_INVALID, "warm start: fp64 handles only (this one was created with MPC_PRECISION_F32)");
-  if (!model && h->mixed)
+  const bool as_model = model || horizon;      /* (a horizon call is dispatched as a model call: the model rule decides) */
+  if (!as_model && !f64) return refuse(MPC_ERR_INVALID, "warm start: fp64 handles only (this one was created with MPC_PRECISION_F32)");
+  if (!as_model && h->mixed)
     return refuse(MPC_ERR_UNSUPPORTED, "warm start is not available on a handle whose solve starts in fp32 (two launches): create it with MpcParams.f64_f32_start = 0");
   if (h->params.max_soc > 0) return refuse(MPC_ERR_UNSUPPORTED, "warm start is not available with the second-order correction: set MpcParams.max_soc = 0");
   (void)mpc_warm_opts_default(&x.w.wopts);
@@ -2236,7 +2292,7 @@ static int launch_solve(MpcHandle *h, const SolveIO<R> &call, void *stream_, uns
   const int64_t B = io.B;
   hipStream_t s = (hipStream_t)stream_;   /* NULL = HIP's default (null) stream, exactly as passed */
   const MpcModelPart mp{x.model, x.ld_model ? x.ld_model : io.ld};
-  const bool model = x.model != nullptr;
+  const bool model = x.model_call();
   const bool may_defer = (flags & kDefer) && !warm && !model, may_order = (flags & kOrder) && !warm && !model;
   /* MpcParams.max_soc > 0 on an fp64 handle: the SOC builds of the kernels (the mixed-precision launch decides for its fp64 phase
    * itself) */
@@ -2294,7 +2350,7 @@ static int launch_solve(MpcHandle *h, const SolveIO<R> &call, void *stream_, uns
       if (n_cuts > 0) T.compact_gap = 0;     /* (a phase that parks keeps iterates in its columns) */
       tail_fields(h, tp, T);
       if (ordered) { T.ord_cnt = C.cb + kPhaseCounterInts; T.ord_list = h->d_take_list; T.ord_ld = S; }
-      MPC_TRY(launch_lanes(h, LaneBuild::single, io, s, wr ? h->ws2 : h->ws, soc, T, warm, mp));
+      MPC_TRY(launch_lanes(h, LaneBuild::single, io, s, wr ? h->ws2 : h->ws, soc, T, warm, mp, x.horizon));
     }
   }
   return solve_end(h, io, s, rec, tp, (flags & kStats) != 0);
@@ -2331,6 +2387,23 @@ extern "C" int mpc_solve_batch_device_warm_model(MpcHandle *h, int64_t B, int64_
                                                  void *stream_) {
   return launch_solve<double>(h, {B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters}, stream_, kStats,
                               call_extras(h, model, true, warm_in, warm_status, warm_out, ld_warm, opts));
+}
+
+/* ... and the two _horizon forms: the _model forms plus `horizon` (NULL: the _model form itself, which with model == NULL is the plain one) */
+extern "C" int mpc_solve_batch_device_horizon(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
+                                              const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
+                                              const int32_t *horizon, double *out, double *traj, int32_t *status, int32_t *iters, void *stream_) {
+  return launch_solve<double>(h, {B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters}, stream_,
+                              model || horizon ? kStats : kStats | kDefer | kOrder, call_extras(h, model, false, nullptr, nullptr, nullptr, 0, nullptr, horizon));
+}
+
+extern "C" int mpc_solve_batch_device_warm_horizon(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
+                                                   const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
+                                                   const int32_t *horizon, const double *warm_in, const int32_t *warm_status, double *warm_out,
+                                                   int64_t ld_warm, const MpcWarmOpts *opts, double *out, double *traj, int32_t *status,
+                                                   int32_t *iters, void *stream_) {
+  return launch_solve<double>(h, {B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters}, stream_, kStats,
+                              call_extras(h, model, true, warm_in, warm_status, warm_out, ld_warm, opts, horizon));
 }
 
 /* MPC_PRECISION_F32: the same solve with fp32 inputs, outputs and workspace (handle created with precision F32) */
@@ -2469,11 +2542,18 @@ static int host_extras_in(MpcHandle *h, int64_t B, const CallExtras &hx, const d
     }
   }
   if (hw.warm_out) dx->w.warm_out = h->d_warm_io;
+  if (hw.warm_out && hx.horizon) {
+    /* an instance writes the records of its own stages only: the rows behind them must come back as the caller has them, so
+     * the caller's warm_out goes in first, into a block of its own (warm_in may be another array) */
+    MPC_TRY(ensure_dev(&h->d_warm_o, sizeof(double) * (size_t)warm_rows * (size_t)S));
+    MPC_HIP_CHECK(hipMemcpy2DAsync(h->d_warm_o, sizeof(double) * S, hw.warm_out, sizeof(double) * hw.ld_warm, sizeof(double) * B, warm_rows, hipMemcpyHostToDevice, s));
+    dx->w.warm_out = h->d_warm_o;
+  }
   return MPC_OK;
 }
 static int host_extras_out(MpcHandle *h, int64_t B, const CallExtras &hx, hipStream_t s) {
   if (!hx.warm || !hx.w.warm_out) return MPC_OK;
-  MPC_HIP_CHECK(hipMemcpy2DAsync(hx.w.warm_out, sizeof(double) * hx.w.ld_warm, h->d_warm_io, sizeof(double) * h->io_stride, sizeof(double) * B,
+  MPC_HIP_CHECK(hipMemcpy2DAsync(hx.w.warm_out, sizeof(double) * hx.w.ld_warm, hx.horizon ? h->d_warm_o : h->d_warm_io, sizeof(double) * h->io_stride, sizeof(double) * B,
                                  mpc_warm_rows(h->params.N), hipMemcpyDeviceToHost, s));
   return MPC_OK;
 }
@@ -2664,6 +2744,21 @@ extern "C" int mpc_rollout_batch_device_warm_model(MpcHandle *h, int64_t B, int6
                       call_extras(h, model, true, nullptr, nullptr, nullptr, 0, opts));
 }
 
+extern "C" int mpc_rollout_batch_device_horizon(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
+                                                const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
+                                                const int32_t *horizon, double *hist, int32_t *status, int32_t *iters, void *stream_) {
+  return rollout_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, hist, status, iters, stream_,
+                      call_extras(h, model, false, nullptr, nullptr, nullptr, 0, nullptr, horizon));
+}
+
+extern "C" int mpc_rollout_batch_device_warm_horizon(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
+                                                     const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
+                                                     const int32_t *horizon, const MpcWarmOpts *opts, double *hist, int32_t *status,
+                                                     int32_t *iters, void *stream_) {
+  return rollout_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, hist, status, iters, stream_,
+                      call_extras(h, model, true, nullptr, nullptr, nullptr, 0, opts, horizon));
+}
+
 /* The rollout in one launch: the ROLL build of the lane kernel, a lane per car for all `steps` solves (see mpc_solve_kernel).  One
  * rule decides: fused == stepwise on every handle.  The fused kernel is the single-phase fp64 lane kernel, so it runs where the
  * stepwise loop would launch exactly that at every step (an fp64 handle, no fp32 start, no SOC, B above the wave limit); everywhere
@@ -2677,8 +2772,9 @@ static int rollout_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, do
   MPC_TRY(x.refused);
   MPC_TRY(rollout_args(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, status));
   const double *model = x.model;
-  const bool wave_path = !model && h->wave_max_batch > 0 && B <= h->wave_max_batch;
-  if (B == 0 || h->params.precision != MPC_PRECISION_F64 || (h->mixed && !model) || h->params.max_soc > 0 || wave_path) {
+  const bool as_model = x.model_call();          /* (a horizon call is dispatched as a model call) */
+  const bool wave_path = !as_model && h->wave_max_batch > 0 && B <= h->wave_max_batch;
+  if (B == 0 || h->params.precision != MPC_PRECISION_F64 || (h->mixed && !as_model) || h->params.max_soc > 0 || wave_path) {
     MPC_TRY(rollout_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, hist, status, iters, stream_, x));
     ++h->n_roll_stepwise;
     return MPC_OK;
@@ -2703,6 +2799,13 @@ static int rollout_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, do
   const WarmIO wc{warm, nullptr, warm, h->io_stride, x.w.wopts, 0};
   const MpcRollPart roll{steps, o9, hist ? 9 * ld : 0, state, status, iters};
   const unsigned grid = (unsigned)((B + kBlock - 1) / kBlock);
+  if (x.horizon) {                               /* the ROLL+HORIZON builds: not staged, no LDS (no lane compaction here) */
+    MPC_TRY(with_bool(x.warm, [&](auto warm_build) {
+      constexpr bool WARM = decltype(warm_build)::value;
+      return launch_kernel(mpc_solve_kernel<false, double, double, double, false, WARM, true, true, true>, grid, 0, s, h, io, (double *)h->ws, h->ws_stride,
+                           phase_of<true, WARM, true, true>(T, wc, roll, {model, ld}, {x.horizon}));
+    }));
+  } else
   MPC_TRY(with_bool(h->staging, [&](auto staging) {
     return with_build(false, x.warm, model != nullptr, [&](auto, auto warm_build, auto model_build) {      /* (no SOC here: those handles loop) */
       constexpr bool STAGING = decltype(staging)::value, WARM = decltype(warm_build)::value, MODEL = decltype(model_build)::value;
@@ -2728,6 +2831,14 @@ extern "C" int mpc_rollout_batch_device_fused_model(MpcHandle *h, int64_t B, int
                                                     void *stream_) {
   return rollout_fused_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, hist, status, iters, stream_,
                             call_extras(h, model, warm_start != 0, nullptr, nullptr, nullptr, 0, opts));
+}
+
+extern "C" int mpc_rollout_batch_device_fused_horizon(MpcHandle *h, int64_t B, int64_t ld, int steps, double *state, const double *coeffs,
+                                                      const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
+                                                      const int32_t *horizon, int warm_start, const MpcWarmOpts *opts, double *hist,
+                                                      int32_t *status, int32_t *iters, void *stream_) {
+  return rollout_fused_impl(h, B, ld, steps, state, coeffs, yaw_lo, yaw_hi, weights, hist, status, iters, stream_,
+                            call_extras(h, model, warm_start != 0, nullptr, nullptr, nullptr, 0, opts, horizon));
 }
 
 extern "C" int mpc_rollout_fused_info(const MpcHandle *h, int64_t *out2) {
@@ -2801,6 +2912,17 @@ static int solve_host(MpcHandle *h, int64_t B, int64_t ld, const R *state, const
     MPC_HIP_CHECK(hipMemcpy2DAsync(h->d_model, sizeof(double) * L, x.model, sizeof(double) * ld, sizeof(double) * B, MPC_NMODEL, hipMemcpyHostToDevice, s));
     dx.model = h->d_model;
   }
+  if (x.horizon) {
+    /* the horizons go along like the model columns.  An instance writes only the first n points of each half of its traj column:
+     * the rows behind them come back as the caller has them, so the caller's traj goes in with the inputs */
+    MPC_TRY(ensure_dev(&h->d_horizon, sizeof(int32_t) * (size_t)S));
+    MPC_HIP_CHECK(hipMemcpyAsync(h->d_horizon, x.horizon, sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
+    dx.horizon = h->d_horizon;
+    if (traj) {
+      for_rows(2 * N, sizeof(R) * B, [=](int q) { memcpy(ho + (MPC_NOUT + q) * L, traj + q * ld, sizeof(R) * B); });
+      MPC_HIP_CHECK(hipMemcpyAsync(d_t, ho + MPC_NOUT * L, sizeof(R) * 2 * N * L, hipMemcpyHostToDevice, s));
+    }
+  }
   MPC_TRY(launch_solve<R>(h, {B, L, L, di, di + 6 * L, di + 11 * L, di + 12 * L, weights ? di + 13 * L : nullptr, d_o, traj ? d_t : nullptr, d_st, d_it},
                           (void *)s, kStats | kOrder, dx));
   MPC_TRY(host_extras_out(h, B, x, s));
@@ -2843,6 +2965,22 @@ extern "C" int mpc_solve_batch_host_warm_model(MpcHandle *h, int64_t B, int64_t 
                                                const MpcWarmOpts *opts, double *out, double *traj, int32_t *status, int32_t *iters) {
   return solve_host<double>(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters,
                             call_extras(h, model, true, warm_in, warm_status, warm_out, ld_warm, opts));
+}
+
+extern "C" int mpc_solve_batch_host_horizon(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
+                                            const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
+                                            const int32_t *horizon, double *out, double *traj, int32_t *status, int32_t *iters) {
+  return solve_host<double>(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters,
+                            call_extras(h, model, false, nullptr, nullptr, nullptr, 0, nullptr, horizon));
+}
+
+extern "C" int mpc_solve_batch_host_warm_horizon(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
+                                                 const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
+                                                 const int32_t *horizon, const double *warm_in, const int32_t *warm_status, double *warm_out,
+                                                 int64_t ld_warm, const MpcWarmOpts *opts, double *out, double *traj, int32_t *status,
+                                                 int32_t *iters) {
+  return solve_host<double>(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters,
+                            call_extras(h, model, true, warm_in, warm_status, warm_out, ld_warm, opts, horizon));
 }
 
 extern "C" int mpc_solve_batch_host_f32(MpcHandle *h, int64_t B, int64_t ld, const float *state,

@@ -72,17 +72,19 @@ class BatchedMPC:
         """Rows of this handle's warm buffers: (N-1) * WARM_REC."""
         return _abi.warm_rows(self.N)
 
-    def _call(self, family, head, outs, model=None, warm=None):
+    def _call(self, family, head, outs, model=None, warm=None, horizon=None):
         """Call `family`'s entry point for this call, chosen by the rule of include/mpc_amd.h: the name is the family's, + "_warm"
         for a warm call (`warm`: the values the _warm form takes -- warm_in, warm_status, warm_out, ld_warm, opts; the stepwise
-        rollout: opts alone), + "_model" with `model` (a pointer); the arguments are the handle, head, [model], warm, outs."""
-        name = family + ("_warm" if warm is not None else "") + ("_model" if model is not None else "")
-        rc = getattr(library(), name)(self._h, *head, *(() if model is None else (model,)), *(warm or ()), *outs)
+        rollout: opts alone), + "_model" with `model` (a pointer) or "_horizon" with `horizon` (a pointer; `model` may then be
+        None); the arguments are the handle, head, [model, [horizon]], warm, outs."""
+        extra = () if model is None and horizon is None else ((model,) if horizon is None else (model, horizon))
+        name = family + ("_warm" if warm is not None else "") + ("_horizon" if horizon is not None else "_model" if model is not None else "")
+        rc = getattr(library(), name)(self._h, *head, *extra, *(warm or ()), *outs)
         if rc != 0:
             check(rc, name)
 
     def solve_torch(self, state, coeffs, yaw_lo, yaw_hi, weights=None, want_traj=False, outputs=None, stream=None,
-                    warm=None, warm_status=None, want_warm=False, warm_opts=None, model=None):
+                    warm=None, warm_status=None, want_warm=False, warm_opts=None, model=None, horizon=None):
         """state [6,B], coeffs [5,B], yaw_lo/hi [B], weights [12,B] or None: CUDA tensors, float64 (float32 for a
         handle created with precision F32).  Asynchronous on ``stream`` (default: torch's current stream).  Returns the
         dict of output tensors.
@@ -95,7 +97,12 @@ class BatchedMPC:
         ``model`` [6, B] float64 (fp64 handles; mpc_solve_batch_device_model): dt, Lf, max_steering, max_acceleration,
         max_deceleration and max_speed of every instance (rows _abi.MODEL_*, scenarios.model_rows gives a handle's own) -- one
         launch of the single-phase fp64 solver whatever the handle's dispatch; an unusable column ends INFEASIBLE.  Together
-        with the warm arguments: mpc_solve_batch_device_warm_model -- a record is judged against the instance's own limits."""
+        with the warm arguments: mpc_solve_batch_device_warm_model -- a record is judged against the instance's own limits.
+
+        ``horizon`` [B] int32 (fp64 handles, max_soc = 0; mpc_solve_batch_device_horizon, _warm_horizon): the N of every instance,
+        3 .. the handle's N, with or without ``model``; dispatched like a model call.  "traj" and "warm" keep the handle's shapes:
+        instance i writes x, y of its n points (rows 0..n-1 and N..N+n-1) and the records of its n-1 stages, nothing behind them.
+        Any other value ends that instance INFEASIBLE.  Sort a batch by horizon: a wave is as slow as its longest one."""
         import torch
         B = state.shape[1]
         dt = self._dtype()
@@ -114,6 +121,8 @@ class BatchedMPC:
         traj = outputs.get("traj")
         if model is not None:
             self._check_model(model, B)
+        if horizon is not None:
+            self._check_horizon(horizon, B)
         warm_args = None
         if warm is not None or want_warm:
             rows = self.warm_rows()
@@ -129,11 +138,25 @@ class BatchedMPC:
                 weights.data_ptr() if weights is not None else None)
         outs = (outputs["out"].data_ptr(), traj.data_ptr() if traj is not None else None, outputs["status"].data_ptr(),
                 outputs["iters"].data_ptr(), C.c_void_p(s.cuda_stream))
-        if self.f32 and model is None and warm_args is None:
+        if self.f32 and model is None and warm_args is None and horizon is None:
             check(library().mpc_solve_batch_device_f32(self._h, *head, *outs), "mpc_solve_batch_device")
         else:
-            self._call("mpc_solve_batch_device", head, outs, model.data_ptr() if model is not None else None, warm_args)
+            self._call("mpc_solve_batch_device", head, outs, model.data_ptr() if model is not None else None, warm_args,
+                       horizon.data_ptr() if horizon is not None else None)
         return outputs
+
+    @staticmethod
+    def _check_horizon(horizon, B):
+        import torch
+        if horizon.dtype != torch.int32 or not horizon.is_cuda or not horizon.is_contiguous() or tuple(horizon.shape) != (B,):
+            raise ValueError("horizon must be a contiguous int32 CUDA tensor of shape (B,)")
+
+    @staticmethod
+    def _host_horizon(horizon, B):
+        horizon = np.ascontiguousarray(np.asarray(horizon, dtype=np.int32))
+        if horizon.shape != (B,):
+            raise ValueError("horizon must have shape (B,)")
+        return horizon
 
     @staticmethod
     def _check_model(model, B):
@@ -253,7 +276,7 @@ class BatchedMPC:
         return res
 
     def rollout_torch(self, state, coeffs, yaw_lo, yaw_hi, steps, weights=None, want_hist=True, stream=None, warm_start=False,
-                      warm_opts=None, fused=False, model=None):
+                      warm_opts=None, fused=False, model=None, horizon=None):
         """Closed loop of src/test.cpp:79-111 for a batch: `steps` cold-started solves, each fed with the previous
         step-1 state.  `state` [6,B] is advanced in place.  Returns hist [steps,9,B], worst status, summed iters.
         ``warm_start``: every step after the first starts from the solution of the step before
@@ -261,7 +284,9 @@ class BatchedMPC:
         ``fused``: the same rollout in one launch, every car advancing on its own (mpc_rollout_batch_device_fused; bitwise the
         same results, rollout_fused_info() tells whether the fused kernel or the stepwise loop ran).
         ``model`` [6, B]: every car's own dt, Lf and limits, as in solve_torch -- with every combination of ``warm_start`` and
-        ``fused`` (mpc_rollout_batch_device_model, _warm_model, _fused_model)."""
+        ``fused`` (mpc_rollout_batch_device_model, _warm_model, _fused_model).
+        ``horizon`` [B] int32: every car's own N as in solve_torch, with every combination as well (mpc_rollout_batch_device_horizon,
+        _warm_horizon, _fused_horizon; the one launch runs at every B)."""
         import torch
         B = state.shape[1]
         dev = state.device
@@ -274,21 +299,26 @@ class BatchedMPC:
         s = stream if stream is not None else torch.cuda.current_stream(dev)
         if model is not None:
             self._check_model(model, B)
+        if horizon is not None:
+            self._check_horizon(horizon, B)
         head = (B, B, int(steps), state.data_ptr(), coeffs.data_ptr(), yaw_lo.data_ptr(), yaw_hi.data_ptr(),
                 weights.data_ptr() if weights is not None else None)
         outs = (res["hist"].data_ptr() if want_hist else None, res["status"].data_ptr(), res["iters"].data_ptr(), C.c_void_p(s.cuda_stream))
         opts = C.byref(warm_opts) if warm_opts is not None else None
         m = model.data_ptr() if model is not None else None
+        hz = horizon.data_ptr() if horizon is not None else None
         if fused:      # (two forms: warm_start and opts are arguments of both)
-            self._call("mpc_rollout_batch_device_fused", head, (1 if warm_start else 0, opts) + outs, m)
+            self._call("mpc_rollout_batch_device_fused", head, (1 if warm_start else 0, opts) + outs, m, horizon=hz)
         else:
-            self._call("mpc_rollout_batch_device", head, outs, m, (opts,) if warm_start else None)
+            self._call("mpc_rollout_batch_device", head, outs, m, (opts,) if warm_start else None, horizon=hz)
         return res
 
     # -- host path (numpy arrays; copies through PCIe) ------------------------
-    def solve_numpy(self, state, coeffs, yaw_lo, yaw_hi, weights=None, want_traj=False, model=None):
+    def solve_numpy(self, state, coeffs, yaw_lo, yaw_hi, weights=None, want_traj=False, model=None, horizon=None, traj_out=None):
         """Host arrays through mpc_solve_batch_host (float64), or mpc_solve_batch_host_f32 for an MPC_PRECISION_F32 handle.
-        ``model`` [6, B] float64: per-instance dt, Lf and limits as in solve_torch (mpc_solve_batch_host_model, fp64 handles)."""
+        ``model`` [6, B] float64: per-instance dt, Lf and limits as in solve_torch (mpc_solve_batch_host_model, fp64 handles).
+        ``horizon`` [B] int32: per-instance N as in solve_torch (mpc_solve_batch_host_horizon); the rows of "traj" that an instance
+        does not write hold NaN, or what ``traj_out`` [2N, B] (written in place) held."""
         dt = np.float32 if self.f32 else np.float64
         f = lambda a: np.ascontiguousarray(np.asarray(a, dtype=dt))
         state, coeffs, yaw_lo, yaw_hi = f(state), f(coeffs), f(yaw_lo), f(yaw_hi)
@@ -298,24 +328,36 @@ class BatchedMPC:
             weights = f(weights)
             assert weights.shape == (_abi.NW, B)
         out = np.empty((_abi.NOUT, B), dtype=dt); status = np.empty(B, dtype=np.int32); iters = np.empty(B, dtype=np.int32)
-        traj = np.empty((2 * self.N, B), dtype=dt) if want_traj else None
+        traj = self._host_traj(B, dt, want_traj, horizon, traj_out)
         p = lambda a: a.ctypes.data if a is not None else None
         head = (B, B, p(state), p(coeffs), p(yaw_lo), p(yaw_hi), p(weights))
         outs = (p(out), p(traj), p(status), p(iters))
         if model is not None:
             model = np.ascontiguousarray(np.asarray(model, dtype=np.float64))
             assert model.shape == (_abi.NMODEL, B)
-        if self.f32 and model is None:
+        if horizon is not None:
+            horizon = self._host_horizon(horizon, B)
+        if self.f32 and model is None and horizon is None:
             check(library().mpc_solve_batch_host_f32(self._h, *head, *outs), "mpc_solve_batch_host")
         else:
-            self._call("mpc_solve_batch_host", head, outs, p(model))
+            self._call("mpc_solve_batch_host", head, outs, p(model), horizon=p(horizon))
         return {"out": out, "status": status, "iters": iters, "traj": traj}
 
+    def _host_traj(self, B, dt, want_traj, horizon, traj_out):
+        if traj_out is not None:
+            assert traj_out.shape == (2 * self.N, B) and traj_out.dtype == dt and traj_out.flags.c_contiguous
+            return traj_out
+        if not want_traj:
+            return None
+        return np.full((2 * self.N, B), np.nan, dtype=dt) if horizon is not None else np.empty((2 * self.N, B), dtype=dt)
+
     def solve_numpy_warm(self, state, coeffs, yaw_lo, yaw_hi, warm=None, warm_status=None, weights=None, want_traj=False, warm_opts=None,
-                         model=None):
+                         model=None, horizon=None, traj_out=None, warm_out=None):
         """Host arrays through mpc_solve_batch_host_warm (fp64 handles): like solve_numpy, with "warm" [warm_rows(), B] in the
         result; ``warm`` / ``warm_status``: that array and the status of an earlier call.  ``model`` [6, B]: as in solve_numpy
-        (mpc_solve_batch_host_warm_model)."""
+        (mpc_solve_batch_host_warm_model).  ``horizon`` [B] int32: as in solve_numpy (mpc_solve_batch_host_warm_horizon): an instance
+        reads and writes the records of its own n-1 stages; the rows of "warm" behind them hold NaN, or what ``warm_out``
+        [warm_rows(), B] (written in place; may be ``warm`` itself) held."""
         f = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64))
         state, coeffs, yaw_lo, yaw_hi = f(state), f(coeffs), f(yaw_lo), f(yaw_hi)
         B = state.shape[1]
@@ -328,14 +370,20 @@ class BatchedMPC:
         if weights is not None:
             weights = f(weights)
         out = np.empty((_abi.NOUT, B)); status = np.empty(B, dtype=np.int32); iters = np.empty(B, dtype=np.int32)
-        traj = np.empty((2 * self.N, B)) if want_traj else None
-        wout = np.empty((rows, B))
+        traj = self._host_traj(B, np.float64, want_traj, horizon, traj_out)
+        if warm_out is not None:
+            assert warm_out.shape == (rows, B) and warm_out.dtype == np.float64 and warm_out.flags.c_contiguous
+            wout = warm_out
+        else:
+            wout = np.full((rows, B), np.nan) if horizon is not None else np.empty((rows, B))
         p = lambda a: a.ctypes.data if a is not None else None
         if model is not None:
             model = f(model)
             assert model.shape == (_abi.NMODEL, B)
+        if horizon is not None:
+            horizon = self._host_horizon(horizon, B)
         self._call("mpc_solve_batch_host", (B, B, p(state), p(coeffs), p(yaw_lo), p(yaw_hi), p(weights)), (p(out), p(traj), p(status), p(iters)),
-                   p(model), (p(warm), p(warm_status), p(wout), B, C.byref(warm_opts) if warm_opts is not None else None))
+                   p(model), (p(warm), p(warm_status), p(wout), B, C.byref(warm_opts) if warm_opts is not None else None), horizon=p(horizon))
         return {"out": out, "status": status, "iters": iters, "traj": traj, "warm": wout}
 
     # -- deferred tails (MpcParams.tail_cut > 0, include/mpc_amd.h) -------------

@@ -510,6 +510,13 @@ int mpc_rollout_batch_device_fused_model(MpcHandle *h, int64_t B, int64_t ld, in
                                          const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
                                          int warm_start, const MpcWarmOpts *opts, double *hist, int32_t *status, int32_t *iters,
                                          void *stream);
+/* ---- per-instance horizon: the N of every instance -----------------------------------------------------------------------------
+ * One more rule next to the two above: the _horizon form of an entry point is its _model form plus `horizon`, [ld] int32, directly
+ * behind `model`: instance i is solved as the reference solves it with Config::N = horizon[i], 3 .. the handle's N, in one launch on
+ * one handle.  Seven entry points have one -- the solve (device, host), the warm solve (device, host) and the three rollouts; run(),
+ * the telemetry handler, the wire forms and the C++ drop-in have none, deliberately.  The section and its seven declarations live in
+ * a header of their own, which this one includes: */
+#include "mpc_amd_horizon.h"
 /* ---- per-instance model values on the run() path: a fleet of different vehicles behind one handler ----------------------------
  * Each entry point is the one of the same name without `_model` plus `model`, [MPC_NMODEL][ld] doubles addressed with the call's
  * ld (rows MPC_MODEL_*), directly behind `ptsy`; the wire forms further down take it as [MPC_NMODEL][B] directly behind
