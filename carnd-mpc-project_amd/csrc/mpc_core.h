@@ -670,7 +670,7 @@ MPC_HD double speed_target(const MpcParams &P, double angle, double maxv) {
  * Solver::unpack() are the only places of the solve that read them, and they read them as fields of these names: of the handle's
  * MpcParams itself (the existing signatures -- each field read where it is used, as before there was a choice, so the kernels
  * without per-instance values are instruction for instruction what they were) or of this struct, filled from the instance's column
- * (ModelVals::column, setup_model() / unpack_model()). */
+ * (ModelVals::column, through the column argument of setup() / unpack(): NoColumn, ModelColumn, HorizonColumn below). */
 struct ModelVals {
   double dt, Lf, max_steering, max_acceleration, max_deceleration, max_speed;
   MPC_HD static ModelVals of(const MpcParams &P) { return ModelVals{P.dt, P.Lf, P.max_steering, P.max_acceleration, P.max_deceleration, P.max_speed}; }
@@ -690,6 +690,32 @@ struct ModelVals {
   }
 };
 
+/* The column argument of Solver::setup() / unpack(): what an instance brings along of its own, by type.  Each type says what the
+ * instance's model values are -- vals(): `ok` false for a column that cannot be used, the values then the handle's -- and how many
+ * stages it has -- stages(): 0 = the handle's N - 1, `ok` cleared for a horizon that cannot be used.
+ * NoColumn: nothing; vals() is the handle's MpcParams itself, so every field is read where it is used (see ModelVals). */
+struct NoColumn {
+  MPC_HD const MpcParams &vals(const MpcParams &P, bool &ok) const { ok = true; return P; }
+  MPC_HD int stages(const MpcParams &, bool &) const { return 0; }
+};
+/* The instance's column of model [MPC_NMODEL][ld] (the mpc_*_model entry points); also the `get` of ModelVals::column. */
+struct ModelColumn {
+  const double *col;
+  int64_t ld;
+  MPC_HD double operator()(int row) const { return col[row * ld]; }
+  MPC_HD ModelVals vals(const MpcParams &P, bool &ok) const { return ModelVals::column(P, *this, ok); }
+  MPC_HD int stages(const MpcParams &, bool &) const { return 0; }
+};
+/* A model column that the caller reads itself, get(row): what instance_solve / instance_store make of a bare getter in the place
+ * of the column (host code; the kernels name their columns). */
+template <class Get>
+struct GetterColumn {
+  Get get;
+  MPC_HD ModelVals vals(const MpcParams &P, bool &ok) const { return ModelVals::column(P, get, ok); }
+  MPC_HD int stages(const MpcParams &, bool &) const { return 0; }
+};
+template <class Col, class = void> struct is_column : std::false_type {};
+template <class Col> struct is_column<Col, decltype((void)&Col::stages)> : std::true_type {};
 /* What an instance of the mpc_*_horizon entry points brings along: its horizon n (Config::N of the reference, 3 .. the handle's N)
  * and its column of `model` -- col = nullptr: the handle's own six values, taken as they are (no column is judged). */
 struct HorizonColumn {
@@ -698,9 +724,12 @@ struct HorizonColumn {
   int n;
   MPC_HD ModelVals vals(const MpcParams &P, bool &ok) const {
     if (!col) { ok = true; return ModelVals::of(P); }
-    const double *c = col;
-    const int64_t l = ld;
-    return ModelVals::column(P, [c, l](int q) { return c[q * l]; }, ok);
+    return ModelColumn{col, ld}.vals(P, ok);
+  }
+  MPC_HD int stages(const MpcParams &P, bool &ok) const {
+    const bool n_ok = n >= 3 && n <= P.N;
+    ok = ok && n_ok;
+    return n_ok ? n - 1 : 0;
   }
 };
 
@@ -2154,34 +2183,27 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
   /* ------------------------------------------------------------------ */
   /* set-up: instance constants, start point (MPC.cpp:204-257)           */
   /* ------------------------------------------------------------------ */
-  MPC_HD int setup(const R *state6, const R *coef5, R yaw_lo, R yaw_hi, const R *w12,
-                   bool write_start = true) {
-    return setup_vals(P, state6, coef5, yaw_lo, yaw_hi, w12, write_start);
-  }
-  /* The same for an instance that brings its own model values: `model(row)` reads its column of model [MPC_NMODEL][ld].  A column
-   * that ModelVals::column refuses ends as MPC_STATUS_INFEASIBLE with the start point of the handle's own values. */
-  template <class Get>
-  MPC_HD int setup_model(Get model, const R *state6, const R *coef5, R yaw_lo, R yaw_hi, const R *w12, bool write_start = true) {
+  /* `col` (NoColumn, ModelColumn, HorizonColumn) says what the instance brings along.  A ModelColumn: its own model values; a column
+   * that ModelVals::column refuses ends as MPC_STATUS_INFEASIBLE with the start point of the handle's own values.  A HorizonColumn:
+   * its own horizon as well, n = col.n steps, 8n - 2 variables and 6n rows as the reference poses them with Config::N = n, on the
+   * first n - 1 stage records of the instance's column (the record of the initial-state rows at index n - 1).  Everything that
+   * counts stages -- the sweeps, the warm rules, unpack -- reads M, so this is the only place that knows.  A horizon outside
+   * 3 .. P.N ends like an unusable column: MPC_STATUS_INFEASIBLE, the start point of the handle's horizon. */
+  template <class Col>
+  MPC_HD int setup(const Col &col, const R *state6, const R *coef5, R yaw_lo, R yaw_hi, const R *w12, bool write_start = true) {
     bool ok;
-    const ModelVals m = ModelVals::column(P, model, ok);
-    const int s = setup_vals(m, state6, coef5, yaw_lo, yaw_hi, w12, write_start);
+    const auto &m = col.vals(P, ok);
+    const int stages = col.stages(P, ok);
+    const int s = setup_vals(m, state6, coef5, yaw_lo, yaw_hi, w12, write_start, stages);
     return ok ? s : MPC_STATUS_INFEASIBLE;
   }
-  /* The same for an instance that brings its own horizon as well (the mpc_*_horizon entry points): n = hc.n steps, 8n - 2 variables
-   * and 6n rows as the reference poses them with Config::N = n, on the first n - 1 stage records of the instance's column (the
-   * record of the initial-state rows at index n - 1).  Everything that counts stages -- the sweeps, the warm rules, unpack -- reads
-   * M, so this is the only place that knows.  The six model values: the column's, or the handle's own without one.  A horizon
-   * outside 3 .. P.N ends like an unusable column: MPC_STATUS_INFEASIBLE, the start point of the handle's horizon. */
-  MPC_HD int setup_horizon(const HorizonColumn &hc, const R *state6, const R *coef5, R yaw_lo, R yaw_hi, const R *w12, bool write_start = true) {
-    bool ok;
-    const ModelVals m = hc.vals(P, ok);
-    const bool n_ok = hc.n >= 3 && hc.n <= P.N;
-    const int s = setup_vals(m, state6, coef5, yaw_lo, yaw_hi, w12, write_start, n_ok ? hc.n - 1 : 0);
-    return ok && n_ok ? s : MPC_STATUS_INFEASIBLE;
+  /* (a caller that never has a column -- host code around one Solver -- may leave NoColumn out; unpack likewise) */
+  MPC_HD int setup(const R *state6, const R *coef5, R yaw_lo, R yaw_hi, const R *w12, bool write_start = true) {
+    return setup(NoColumn{}, state6, coef5, yaw_lo, yaw_hi, w12, write_start);
   }
   /* (stages = 0: the handle's N - 1) */
   template <class MV>
-  MPC_HD int setup_vals(const MV &m, const R *state6, const R *coef5, R yaw_lo, R yaw_hi, const R *w12, bool write_start, int stages = 0) {
+  MPC_HD int setup_vals(const MV &m, const R *state6, const R *coef5, R yaw_lo, R yaw_hi, const R *w12, bool write_start, int stages) {
     MPC_UNROLL
     for (int i = 0; i < 6; i++) st[i] = state6[i];
     MPC_UNROLL
@@ -2285,7 +2307,7 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
     for (;;) {
       const int r = step();
       if (r == MPC_RUNNING) continue;
-      if (r == MPC_STATUS_LINESEARCH && attempt == 0 && !no_restart) {
+      if (r == MPC_STATUS_LINESEARCH && attempt == 0 && !no_restart) {      /* (next_attempt, written out: see there) */
         attempt = 1; it_total += iters;
         start_point();
         begin(false);
@@ -2294,6 +2316,29 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
       iters += it_total;
       return r;
     }
+  }
+  /* The restart rule, for every driver of step(): what follows an attempt that has ended with r (not MPC_RUNNING).  An attempt
+   * of -1 -- an iterate that came from elsewhere: a warm record, the fp32 phase -- that did not end in SUCCESS is followed by the
+   * complete cold solve (least-squares start, attempt 0); the first line-search failure of a cold solve by the one restart with
+   * zero multipliers (attempt 1).  Returns true if the instance goes on: its iterations so far are in it_total, and start_point()
+   * and begin() have been called.  false: r is final.
+   * The lane kernel, the tail-slice kernel and the CPU twins' own loops call this.  solve() and solve_warm() keep the rule written
+   * out: with the call in their loops the wave kernels, which sit at 512 registers, come out of the register allocator with 8 more
+   * bytes of scratch in six builds (136 -> 144, 176 -> 184, 72 -> 80), whichever way the call is written. */
+  MPC_HD bool next_attempt(int r, int &attempt, int &it_total) {
+    if (attempt < 0 && r != MPC_STATUS_SUCCESS) {
+      attempt = 0; it_total += iters;
+      start_point();
+      begin(true);
+      return true;
+    }
+    if (r == MPC_STATUS_LINESEARCH && attempt == 0 && !no_restart) {
+      attempt = 1; it_total += iters;
+      start_point();
+      begin(false);
+      return true;
+    }
+    return false;
   }
 
   /* ------------------------------------------------------------------ */
@@ -2375,7 +2420,7 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
     for (;;) {
       const int r = step();
       if (r == MPC_RUNNING) continue;
-      if (attempt < 0 && r != MPC_STATUS_SUCCESS) {
+      if (attempt < 0 && r != MPC_STATUS_SUCCESS) {      /* (next_attempt, written out: see there) */
         attempt = 0; it_total += iters;
         start_point();
         begin(true);
@@ -2690,22 +2735,17 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
   /* MPC.cpp:306-324: out9 and the optional N-point trajectory */
   /* yaw_lo / yaw_hi: the caller's psi-bounds of this instance (the solver itself holds the relaxed ones): with
    * honor_original_bounds (IPOPT 3.12 default "yes") the returned point is projected into the bounds the user gave */
+  /* `col`: the column setup() was given.  An instance with its own model values: its unrelaxed limits are read from its column
+   * again here, at the hand-over point, instead of being carried through the iteration (a refused column: the handle's, as in
+   * setup).  With its own horizon: traj keeps the handle's shape, x_0 .. x_{n-1} in rows 0 .. n-1 and y in rows N .. N+n-1 (M says) */
+  template <class Col, class OutF, class TrajF>
+  MPC_HD void unpack(const Col &col, OutF out, TrajF traj, bool want_traj, R yaw_lo, R yaw_hi) const {
+    bool ok;
+    unpack_vals(col.vals(P, ok), out, traj, want_traj, yaw_lo, yaw_hi);
+  }
   template <class OutF, class TrajF>
   MPC_HD void unpack(OutF out, TrajF traj, bool want_traj, R yaw_lo, R yaw_hi) const {
-    unpack_vals(P, out, traj, want_traj, yaw_lo, yaw_hi);
-  }
-  /* The same for an instance with its own model values: its unrelaxed limits are read from its column again here, at the hand-over
-   * point, instead of being carried through the iteration (a refused column: the handle's, as in setup_model) */
-  template <class Get, class OutF, class TrajF>
-  MPC_HD void unpack_model(Get model, OutF out, TrajF traj, bool want_traj, R yaw_lo, R yaw_hi) const {
-    bool ok;
-    unpack_vals(ModelVals::column(P, model, ok), out, traj, want_traj, yaw_lo, yaw_hi);
-  }
-  /* ... and with its own horizon: traj keeps the handle's shape, x_0 .. x_{n-1} in rows 0 .. n-1 and y in rows N .. N+n-1 (M says) */
-  template <class OutF, class TrajF>
-  MPC_HD void unpack_horizon(const HorizonColumn &hc, OutF out, TrajF traj, bool want_traj, R yaw_lo, R yaw_hi) const {
-    bool ok;
-    unpack_vals(hc.vals(P, ok), out, traj, want_traj, yaw_lo, yaw_hi);
+    unpack(NoColumn{}, out, traj, want_traj, yaw_lo, yaw_hi);
   }
   template <class MV, class OutF, class TrajF>
   MPC_HD void unpack_vals(const MV &m, OutF out, TrajF traj, bool want_traj, R yaw_lo, R yaw_hi) const {
@@ -2784,11 +2824,13 @@ struct RolloutCar {
  * The sequence every caller with a Solver object per instance runs: gather_instance, instance_solve and -- by whoever writes the
  * instance out: the group's first lane in the wave kernels -- instance_store.  The wave kernels (mpc_solve_wave_kernel), the
  * test-only CPU build (tests/host_twin) and solve_instance below are uses of these three and spell nothing of it out themselves;
- * the lane kernel drives Solver::step through a state machine of its own.  Two arguments say which form a call takes, by type:
- *   col   NoColumn: the handle's model values (setup / unpack); or the getter of the instance's column (setup_model / unpack_model);
- *         or a HorizonColumn: the instance's horizon and its column, if any (setup_horizon / unpack_horizon)
+ * the lane kernel and the tail-slice kernel keep a state machine of their own around Solver::step -- their lanes are on different
+ * instances in different phases -- but spell none of the steps out either: the gather is gather_instance, set-up and hand-over are
+ * Solver::setup / unpack on the same column types, and what follows a finished attempt is Solver::next_attempt, as in solve() and
+ * solve_warm().  Two arguments say which form a call takes, by type:
+ *   col   NoColumn: the handle's model values; a ModelColumn: the instance's column; a HorizonColumn: the instance's horizon and
+ *         its column, if any (all three through Solver::setup / unpack); a bare getter get(row): a GetterColumn of it
  *   warm  NoWarm: solve(); or a WarmStart (solve_warm, then warm_store) */
-struct NoColumn {};
 struct NoWarm {};
 struct WarmStart {
   bool warm;                      /* start from `column`; false: cold, as solve() */
@@ -2830,21 +2872,20 @@ MPC_HD void gather_instance(const MpcParams &P, int64_t i, int64_t ld, const RIO
 /* set-up and solve; returns the status */
 template <class SV, class Col, class Warm, class R>
 MPC_HD int instance_solve(SV &S, Col col, const Warm &warm, const R *st, const R *cf, R yaw_lo, R yaw_hi, const R *w) {
-  int r;
-  if constexpr (std::is_same<Col, NoColumn>::value) r = S.setup(st, cf, yaw_lo, yaw_hi, w, true);
-  else if constexpr (std::is_same<Col, HorizonColumn>::value) r = S.setup_horizon(col, st, cf, yaw_lo, yaw_hi, w, true);
-  else r = S.setup_model(col, st, cf, yaw_lo, yaw_hi, w, true);
-  if (r != MPC_STATUS_SUCCESS) return r;
-  if constexpr (std::is_same<Warm, NoWarm>::value) return S.solve();
-  else return S.solve_warm(warm.warm, warm.column, *warm.opts);
+  if constexpr (!is_column<Col>::value) return instance_solve(S, GetterColumn<Col>{col}, warm, st, cf, yaw_lo, yaw_hi, w);
+  else {
+    const int r = S.setup(col, st, cf, yaw_lo, yaw_hi, w, true);
+    if (r != MPC_STATUS_SUCCESS) return r;
+    if constexpr (std::is_same<Warm, NoWarm>::value) return S.solve();
+    else return S.solve_warm(warm.warm, warm.column, *warm.opts);
+  }
 }
 
 /* the hand-over through the caller's accessors (Solver::unpack), the final iterate whatever the status; returns the iterations */
 template <class SV, class Col, class Warm, class OutF, class TrajF, class R>
 MPC_HD int instance_store(const SV &S, Col col, const Warm &warm, OutF out, TrajF traj, bool want_traj, R yaw_lo, R yaw_hi) {
-  if constexpr (std::is_same<Col, NoColumn>::value) S.unpack(out, traj, want_traj, yaw_lo, yaw_hi);
-  else if constexpr (std::is_same<Col, HorizonColumn>::value) S.unpack_horizon(col, out, traj, want_traj, yaw_lo, yaw_hi);
-  else S.unpack_model(col, out, traj, want_traj, yaw_lo, yaw_hi);
+  if constexpr (!is_column<Col>::value) S.unpack(GetterColumn<Col>{col}, out, traj, want_traj, yaw_lo, yaw_hi);
+  else S.unpack(col, out, traj, want_traj, yaw_lo, yaw_hi);
   if constexpr (!std::is_same<Warm, NoWarm>::value) {
     if (warm.out) {
       double *wo = warm.out;

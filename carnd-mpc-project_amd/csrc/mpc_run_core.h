@@ -250,8 +250,7 @@ MPC_HD void command_from_run(const MV &m, const double *o8, double *steer_cmd, d
 /* instance i's column of model [MPC_NMODEL][ld]; a column that cannot be used: the handle's values (the solve reports it INFEASIBLE) */
 MPC_HD ModelVals model_vals_of(const MpcParams &P, const double *model, int64_t ld, int64_t i) {
   bool ok;
-  const double *mc = model + i;
-  return ModelVals::column(P, [mc, ld](int q) { return mc[q * ld]; }, ok);
+  return ModelColumn{model + i, ld}.vals(P, ok);
 }
 
 /* pose [6][ld] (TELEMETRY: the simulator's telemetry rows, latency compensation first, mpc_main.cpp:126-159) and the waypoints

@@ -286,16 +286,35 @@ __global__ __launch_bounds__(kBlock) void mpc_take_key_kernel(const float horizo
 /* Copies between queue entries and a lane's workspace column.  Loads first, then stores, a stage (or 16 rows) at a time: written as
  * `dst[..] = src[..]` in one loop the compiler must assume that a store aliases the next load and waits for every load before the
  * next one goes out -- 200 round trips of ~2 us per entry, which priced a wave's life at +10 % per deferred instance. */
-template <class R, class WS>
-__device__ __forceinline__ void tile_from_column(R *__restrict__ dst, const WS &ws, int I, int M) {      /* dst: lane's place in a [M][IT_SZ][64] tile */
+/* One iterate of M stages: the whole record of stage k through load(k, f), then store(k, rec).  The ends: */
+template <class R, class Load, class Store>
+__device__ __forceinline__ void copy_iterate(int M, Load load, Store store) {
   using FL = mpc::Fields<R>;
   for (int k = 0; k < M; ++k) {
     R rec[FL::IT_SZ];
 #pragma unroll
-    for (int f = 0; f < FL::IT_SZ; f++) rec[f] = ws.it(k, I, f);
-#pragma unroll
-    for (int f = 0; f < FL::IT_SZ; f++) dst[(k * FL::IT_SZ + f) * 64] = rec[f];
+    for (int f = 0; f < FL::IT_SZ; f++) rec[f] = load(k, f);
+    store(k, rec);
   }
+}
+/* ... iterate slot I of a workspace column */
+template <class R, class WS>
+__device__ __forceinline__ auto column_load(const WS &ws, int I) { return [&ws, I](int k, int f) -> R { return ws.it(k, I, f); }; }
+template <class R, class WS>
+__device__ __forceinline__ auto column_store(WS &ws, int I) {
+  return [&ws, I](int k, const R *rec) { ws.template store_run<0, mpc::Fields<R>::IT_SZ>(k, I, rec); };
+}
+/* ... entry e's place in the [cap / 64][M][IT_SZ][64] reals of a queue (MpcTailQ.iter, MpcPhase.p_iter) */
+template <class R>
+__device__ __forceinline__ R *tile_place(void *base, int64_t e, int M) { return (R *)base + (e >> 6) * (int64_t)M * mpc::Fields<R>::IT_SZ * 64 + (e & 63); }
+template <class R>
+__device__ __forceinline__ auto tile_load(const R *src) { return [src](int k, int f) { return src[(k * mpc::Fields<R>::IT_SZ + f) * 64]; }; }
+template <class R>
+__device__ __forceinline__ auto tile_store(R *dst) {
+  return [dst](int k, const R *rec) {
+#pragma unroll
+    for (int f = 0; f < mpc::Fields<R>::IT_SZ; f++) dst[(k * mpc::Fields<R>::IT_SZ + f) * 64] = rec[f];
+  };
 }
 __device__ __forceinline__ void rows_copy(double *__restrict__ dk, int64_t dl, const double *__restrict__ pk, int64_t lp, int q0, int q1) {
   for (int q = q0; q < q1; q += 16) {
@@ -313,6 +332,34 @@ template <class RIO, class R> struct OutRef {
   __device__ __host__ void operator=(R v) const { *p = (RIO)v; }
 };
 
+/* The column argument of Solver::setup / unpack for instance i in the build at hand (mpc::NoColumn, ModelColumn, HorizonColumn).
+ * The only place that knows where the model values lie: a rollout's columns are the caller's, rows ld apart like its inputs; a
+ * solve's have T.ld_model (MpcModelPart). */
+template <bool ROLL, bool MODEL, bool HORIZON, class Phase>
+__device__ __forceinline__ auto instance_column(const Phase &T, int64_t ld, int64_t i) {
+  if constexpr (MODEL) {
+    int64_t lm = ld;
+    if constexpr (!ROLL) lm = T.ld_model;
+    if constexpr (HORIZON) return mpc::HorizonColumn{T.model ? T.model + i : nullptr, lm, T.horizon[i]};
+    else return mpc::ModelColumn{T.model + i, lm};
+  } else return mpc::NoColumn{};
+}
+
+/* Instance i, which this lane has taken as far as the phase goes, is appended to the list of the next phase: its index, this lane's
+ * column (where its iterate is, unless the caller copies it out) and the solver's scalars; row 35 says whether the next phase
+ * continues the iterate (clean) or solves the instance from the start point (from_scratch).  Returns the list position. */
+template <class SV>
+__device__ __forceinline__ int64_t park_for_next_phase(const MpcPhase &T, const SV &S, int64_t i, int attempt, int it_total, bool from_scratch) {
+  const int64_t pos = (int64_t)atomicAdd(T.n_out, 1);
+  T.out_inst[pos] = (int32_t)i;
+  T.out_src[pos] = (int32_t)(blockIdx.x * 64u + threadIdx.x);
+  double *pk = T.out_park + pos;
+  const int64_t lp = T.ld_park;
+  S.park([pk, lp](int q) -> double & { return pk[q * lp]; }, attempt, it_total);
+  pk[35 * lp] = from_scratch ? 1.0 : 0.0;
+  return pos;
+}
+
 /* RIO: the type of the arrays at the ABI (inputs, outputs); R: the solver's.  They differ only in the fp64 phase of a
  * mixed-precision solve on an MPC_PRECISION_F32 handle (RIO = float, R = double).  RSRC: the reals of the workspace a
  * promote_in phase takes its iterates from. */
@@ -326,12 +373,12 @@ template <class RIO, class R> struct OutRef {
  * or consumes the counter.  These builds are launched without lane compaction, cuts and deferred tails (the step index lives in
  * the lane's registers and does not travel). */
 /* MODEL (the mpc_*_model entry points): every set-up and the hand-over read dt, Lf and the four limits from the instance's column of
- * T.model instead of P (Solver::setup_model / unpack_model), by instance index and outside the sweeps; nothing else differs.
- * With WARM: warm_point() judges a record against the relaxed box that setup_model has just set from the column, and the cold solve
+ * T.model instead of P (Solver::setup / unpack with the mpc::ModelColumn of instance_column), by instance index and outside the sweeps;
+ * nothing else differs.  With WARM: warm_point() judges a record against the relaxed box that set-up has just set from the column, and the cold solve
  * that follows a refused record or a failed warm attempt starts from the solver's own members -- no set-up in between.  With ROLL:
  * the car taken again is set up from its column like a fresh one, and the hand-over of a step projects into the column's limits. */
 /* HORIZON (the mpc_*_horizon entry points): a MODEL build in which every set-up also reads the instance's horizon n from T.horizon
- * (Solver::setup_horizon: M = n - 1 stages) and `model` may be nullptr.  The lanes of a wave then differ in their number of stages,
+ * (an mpc::HorizonColumn: M = n - 1 stages) and `model` may be nullptr.  The lanes of a wave then differ in their number of stages,
  * so these builds are not staged and address their rows per lane (TiledWorkspace<false, R, true>): every sweep is an ordinary
  * divergent loop, a lane leaves it after its own M stages, and a pass of the wave costs the longest horizon among its running lanes.
  * Their dynamic LDS is the mailbox of lane compaction alone.  A moved instance is set up again from its index, horizon included. */
@@ -400,24 +447,10 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
         if (fin && fin_status <= kFinPromote) {
           /* mixed precision, promoted iterates in their own buffer: the hand-over to the next phase happens here, for all the
            * lanes of the wave that are waiting for it at once (done lane by lane as they promote it cost 20 % of the rate) */
-          const int64_t pos = (int64_t)atomicAdd(T.n_out, 1);
-          T.out_inst[pos] = (int32_t)i;
-          T.out_src[pos] = (int32_t)(blockIdx.x * 64u + threadIdx.x);
-          double *pk = T.out_park + pos;
-          const int64_t lp = T.ld_park;
-          S.park([pk, lp](int q) -> double & { return pk[q * lp]; }, attempt, it_total);
-          pk[35 * lp] = fin_status == kFinPromote ? 0.0 : 1.0;
+          const int64_t pos = park_for_next_phase(T, S, i, attempt, it_total, fin_status != kFinPromote);
           if (fin_status == kFinPromote) {
             ws.stage_drain();                          /* the trial sweep's stores of this wave have landed */
-            const int I = S.cur ? FL::IT1 : FL::IT0, M = P.N - 1;
-            R *dst = (R *)T.p_iter + (pos >> 6) * (int64_t)M * FL::IT_SZ * 64 + (pos & 63);
-            for (int k = 0; k < M; ++k) {
-              R rec[FL::IT_SZ];
-#pragma unroll
-              for (int f = 0; f < FL::IT_SZ; f++) rec[f] = ws.it(k, I, f);
-#pragma unroll
-              for (int f = 0; f < FL::IT_SZ; f++) dst[(k * FL::IT_SZ + f) * 64] = rec[f];
-            }
+            copy_iterate<R>(P.N - 1, column_load<R>(ws, S.cur ? FL::IT1 : FL::IT0), tile_store(tile_place<R>(T.p_iter, pos, P.N - 1)));
           }
           fin = false;
         }
@@ -427,16 +460,10 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
             using Car = mpc::RolloutCar;
             double *o = T.hist + (int64_t)step * T.hist_step + i;
             const int64_t l = ldo;
-            if constexpr (HORIZON) {
-              S.unpack_horizon(mpc::HorizonColumn{T.model ? T.model + i : nullptr, ld, T.horizon[i]}, [o, l](int q) { return OutRef<RIO, R>{o + q * l}; },
-                               [](int) { return OutRef<RIO, R>{nullptr}; }, false, (R)yaw_lo[i], (R)yaw_hi[i]);
-            } else if constexpr (MODEL) {             /* the car's own limits, from its column */
-              const double *mc = T.model + i;
-              int64_t lm = ld;
-              if constexpr (!ROLL) lm = T.ld_model;
-              S.unpack_model([mc, lm](int q) { return mc[q * lm]; }, [o, l](int q) { return OutRef<RIO, R>{o + q * l}; },
-                             [](int) { return OutRef<RIO, R>{nullptr}; }, false, (R)yaw_lo[i], (R)yaw_hi[i]);
-            } else S.unpack([o, l](int q) { return OutRef<RIO, R>{o + q * l}; }, [](int) { return OutRef<RIO, R>{nullptr}; }, false, (R)yaw_lo[i], (R)yaw_hi[i]);
+            const R ylo = (R)yaw_lo[i], yhi = (R)yaw_hi[i];
+            /* (MODEL: the car's own limits, from its column) */
+            S.unpack(instance_column<ROLL, MODEL, HORIZON>(T, ld, i), [o, l](int q) { return OutRef<RIO, R>{o + q * l}; },
+                     [](int) { return OutRef<RIO, R>{nullptr}; }, false, ylo, yhi);
             double *sp = T.state + i;
             const int64_t ls = ld;
             Car::next_state([o, l](int q) { return o[q * l]; }, [sp, ls](int q, double v) { sp[q * ls] = v; });
@@ -463,21 +490,9 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
           RIO *o = out + i;
           RIO *t = traj ? traj + i : nullptr;
           const int64_t l = ldo;
-          if constexpr (HORIZON) {
-            int64_t lm = ld;
-            if constexpr (!ROLL) lm = T.ld_model;
-            S.unpack_horizon(mpc::HorizonColumn{T.model ? T.model + i : nullptr, lm, T.horizon[i]}, [o, l](int q) { return OutRef<RIO, R>{o + q * l}; },
-                             [t, l](int q) { return OutRef<RIO, R>{t + q * l}; }, traj != nullptr, (R)yaw_lo[i], (R)yaw_hi[i]);
-          } else if constexpr (MODEL) {
-            const double *mc = T.model + i;
-            int64_t lm = ld;
-            if constexpr (!ROLL) lm = T.ld_model;
-            S.unpack_model([mc, lm](int q) { return mc[q * lm]; }, [o, l](int q) { return OutRef<RIO, R>{o + q * l}; },
-                           [t, l](int q) { return OutRef<RIO, R>{t + q * l}; }, traj != nullptr, (R)yaw_lo[i], (R)yaw_hi[i]);
-          } else {
-            S.unpack([o, l](int q) { return OutRef<RIO, R>{o + q * l}; }, [t, l](int q) { return OutRef<RIO, R>{t + q * l}; }, traj != nullptr,
-                     (R)yaw_lo[i], (R)yaw_hi[i]);
-          }
+          const R ylo = (R)yaw_lo[i], yhi = (R)yaw_hi[i];
+          S.unpack(instance_column<ROLL, MODEL, HORIZON>(T, ld, i), [o, l](int q) { return OutRef<RIO, R>{o + q * l}; },
+                   [t, l](int q) { return OutRef<RIO, R>{t + q * l}; }, traj != nullptr, ylo, yhi);
           if constexpr (WARM) {
             /* the final iterate, whatever the status (the caller's next solve looks at the status) */
             if (T.warm_out) {
@@ -514,44 +529,20 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
               if ((uint64_t)i >= (uint64_t)B) i = pos;     /* (cannot happen: the lists hold 0 .. B-1 once each; results never go out of bounds) */
             }
             R st[6], cf[MPC_NCOEF], w[MPC_NW];
-            if constexpr (ROLL) {
-              /* the car's state as it stands: the start state, or the six doubles this lane stored at the step before */
-#pragma unroll
-              for (int q = 0; q < 6; q++) st[q] = (R)T.state[q * ld + i];
-            } else {
-#pragma unroll
-              for (int q = 0; q < 6; q++) st[q] = (R)state[q * ld + i];
-            }
-#pragma unroll
-            for (int q = 0; q < MPC_NCOEF; q++) cf[q] = (R)coeffs[q * ld + i];
-            if (weights) {
-#pragma unroll
-              for (int q = 0; q < MPC_NW; q++) w[q] = (R)weights[q * ld + i];
-            } else {
-#pragma unroll
-              for (int q = 0; q < MPC_NW; q++) w[q] = (R)P.weights[q];
-            }
+            const RIO *sp = state;
+            if constexpr (ROLL) sp = T.state;      /* the car's state as it stands: the start state, or the six doubles this lane stored at the step before */
+            mpc::gather_instance(P, i, ld, sp, coeffs, weights, st, cf, w);
+            const R ylo = (R)yaw_lo[i], yhi = (R)yaw_hi[i];
             const bool from_scratch = T.promote_in && T.in_park[pos + 35 * T.ld_park] != 0.0;   /* the fp32 phase gave up on it */
             bool warm = false, warm_cand = false;   /* WARM: this instance has a valid column in warm_in / starts from it */
             if constexpr (WARM && ROLL) warm_cand = again_warm;   /* (the column this lane stored when it finished the step before) */
             else if constexpr (WARM) warm_cand = T.warm_in != nullptr && (T.warm_status == nullptr || T.warm_status[i] == MPC_STATUS_SUCCESS);
-            int s0;
-            if constexpr (HORIZON) {
-              int64_t lm = ld;
-              if constexpr (!ROLL) lm = T.ld_model;
-              s0 = S.setup_horizon(mpc::HorizonColumn{T.model ? T.model + i : nullptr, lm, T.horizon[i]}, st, cf, (R)yaw_lo[i], (R)yaw_hi[i], w,
-                                   (!T.resume || from_scratch) && !warm_cand);
-            } else if constexpr (MODEL) {
-              const double *mc = T.model + i;
-              int64_t lm = ld;
-              if constexpr (!ROLL) lm = T.ld_model;
-              s0 = S.setup_model([mc, lm](int q) { return mc[q * lm]; }, st, cf, (R)yaw_lo[i], (R)yaw_hi[i], w, (!T.resume || from_scratch) && !warm_cand);
-            } else s0 = S.setup(st, cf, (R)yaw_lo[i], (R)yaw_hi[i], w, (!T.resume || from_scratch) && !warm_cand);
+            const int s0 = S.setup(instance_column<ROLL, MODEL, HORIZON>(T, ld, i), st, cf, ylo, yhi, w, (!T.resume || from_scratch) && !warm_cand);
             if constexpr (WARM) {
               if (warm_cand) {
                 if (s0 == MPC_STATUS_SUCCESS) {
                   const bool box = T.psi_box != 0;
-                  warm = S.warm_point(mpc::WarmColumn{T.warm_in + i, T.ld_warm, box ? (double)yaw_lo[i] : -HUGE_VAL, box ? (double)yaw_hi[i] : HUGE_VAL}, T.wopts);
+                  warm = S.warm_point(mpc::WarmColumn{T.warm_in + i, T.ld_warm, box ? (double)ylo : -HUGE_VAL, box ? (double)yhi : HUGE_VAL}, T.wopts);
                 }
                 if (!warm) S.start_point();     /* set-up left slot 0 to the warm point, and the column holds no iterate of this NLP */
               }
@@ -598,12 +589,7 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
                 WS wsrc = ws;
                 wsrc.tile = (typename WS::greal *)((const R *)T.src_ws + (int64_t)(src >> 6) * tile_reals);
                 wsrc.lane = src & 63;
-                for (int k = 0; k < P.N - 1; ++k) {
-                  R rec[FL::IT_SZ];
-#pragma unroll
-                  for (int f = 0; f < FL::IT_SZ; f++) rec[f] = wsrc.it(k, I, f);
-                  ws.template store_run<0, FL::IT_SZ>(k, I, rec);
-                }
+                copy_iterate<R>(P.N - 1, column_load<R>(wsrc, I), column_store<R>(ws, I));
               }
               passes = 0; have = true;
             } else if (s0 == MPC_STATUS_SUCCESS) { S.begin(true); attempt = 0; it_total = 0; passes = 0; have = true; }
@@ -659,27 +645,10 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
           const int src = __builtin_ctzll(m);
           i = (int64_t)mi[src]; passes = mi[64 + src];
           R st[6], cf[MPC_NCOEF], w[MPC_NW];
-#pragma unroll
-          for (int q = 0; q < 6; q++) st[q] = (R)state[q * ld + i];
-#pragma unroll
-          for (int q = 0; q < MPC_NCOEF; q++) cf[q] = (R)coeffs[q * ld + i];
-          if (weights) {
-#pragma unroll
-            for (int q = 0; q < MPC_NW; q++) w[q] = (R)weights[q * ld + i];
-          } else {
-#pragma unroll
-            for (int q = 0; q < MPC_NW; q++) w[q] = (R)P.weights[q];
-          }
-          if constexpr (HORIZON) {    /* the instance has changed lanes: its horizon and its column come with it */
-            int64_t lm = ld;
-            if constexpr (!ROLL) lm = T.ld_model;
-            (void)S.setup_horizon(mpc::HorizonColumn{T.model ? T.model + i : nullptr, lm, T.horizon[i]}, st, cf, (R)yaw_lo[i], (R)yaw_hi[i], w, false);
-          } else if constexpr (MODEL) {      /* the instance has changed lanes: its column comes with it */
-            const double *mc = T.model + i;
-            int64_t lm = ld;
-            if constexpr (!ROLL) lm = T.ld_model;
-            (void)S.setup_model([mc, lm](int q) { return mc[q * lm]; }, st, cf, (R)yaw_lo[i], (R)yaw_hi[i], w, false);
-          } else (void)S.setup(st, cf, (R)yaw_lo[i], (R)yaw_hi[i], w, false);
+          mpc::gather_instance(P, i, ld, state, coeffs, weights, st, cf, w);
+          const R ylo = (R)yaw_lo[i], yhi = (R)yaw_hi[i];
+          /* (the instance has changed lanes: its column and its horizon, if it has any, come with it) */
+          (void)S.setup(instance_column<ROLL, MODEL, HORIZON>(T, ld, i), st, cf, ylo, yhi, w, false);
           S.unpark([mb, src](int q) -> R { return mb[q * 64 + src]; }, attempt, it_total);
           const int I = S.cur ? FL::IT1 : FL::IT0;
           WS wsrc = ws;
@@ -688,12 +657,7 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
            * for the stores; keeping two stages in flight was measured: no difference) */
           int n_rec = P.N - 1;
           if constexpr (HORIZON) n_rec = S.M;      /* (the instance's own stages; set-up above has read its horizon) */
-          for (int k = 0; k < n_rec; ++k) {
-            R rec[FL::IT_SZ];
-#pragma unroll
-            for (int f = 0; f < FL::IT_SZ; f++) rec[f] = wsrc.it(k, I, f);
-            ws.template store_run<0, FL::IT_SZ>(k, I, rec);
-          }
+          copy_iterate<R>(n_rec, column_load<R>(wsrc, I), column_store<R>(ws, I));
           have = true;
         }
         __builtin_amdgcn_wave_barrier();
@@ -718,31 +682,17 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
         /* the same with the iterate left in its column (MpcParams.f32_phase_refill = 0): the next phase's solver takes over.
          * Not-a-number in the fp32 phase (states far from the origin late in a closed loop: x^4 terms, lost digits) is not a
          * verdict on the instance: the fp64 solver gets it from the start point (row 35 of the parked scalars says so). */
-        const int64_t pos = (int64_t)atomicAdd(T.n_out, 1);
-        T.out_inst[pos] = (int32_t)i;
-        T.out_src[pos] = (int32_t)(blockIdx.x * 64u + threadIdx.x);
-        double *pk = T.out_park + pos;
-        const int64_t lp = T.ld_park;
-        S.park([pk, lp](int q) -> double & { return pk[q * lp]; }, attempt, it_total);
-        pk[35 * lp] = (r == SV::MPC_PROMOTE && S.promote_clean) ? 0.0 : 1.0;
+        (void)park_for_next_phase(T, S, i, attempt, it_total, !(r == SV::MPC_PROMOTE && S.promote_clean));
         have = false; more = false; col_busy = true;     /* the column keeps the parked iterate: this lane takes nothing else */
       } else if (r != SV::MPC_RUNNING) {
-        if (attempt < 0 && r != MPC_STATUS_SUCCESS) {
-          /* An instance the fp32 phase started (attempt -1) and the fp64 phase could not finish (1-3 of 8 192 at N = 25: the
-           * line search fails from where fp32 left it): it is solved again from the start point exactly as the single-phase
-           * solve does it -- first attempt, then the restart if that fails -- so status AND returned point are that solve's
-           * (the named hard instances of tests/helpers.py stay what the oracle says).  Trying the restart first is cheaper
-           * for these stragglers (their chain: fp32 + the failed fp64 continuation + a whole solve) but was measured to return
-           * the restart's local minimum, or its last iterate, where the single-phase solve returns the first attempt's. */
-          attempt = 0; it_total += S.iters;
-          S.start_point();
-          S.begin(true);
-        } else if (r == MPC_STATUS_LINESEARCH && attempt == 0 && !S.no_restart) {
-          /* the stand-in for IPOPT's restoration phase: once more from the start point, zero multipliers */
-          attempt = 1; it_total += S.iters;
-          S.start_point();
-          S.begin(false);
-        } else { fin = true; fin_status = r; have = false; }
+        /* The restart rule (Solver::next_attempt): the stand-in for IPOPT's restoration phase -- once more from the start point,
+         * zero multipliers -- and, before it, the instance the fp32 phase started (attempt -1) and the fp64 phase could not finish
+         * (1-3 of 8 192 at N = 25: the line search fails from where fp32 left it): it is solved again from the start point exactly
+         * as the single-phase solve does it -- first attempt, then the restart if that fails -- so status AND returned point are
+         * that solve's (the named hard instances of tests/helpers.py stay what the oracle says).  Trying the restart first is
+         * cheaper for these stragglers (their chain: fp32 + the failed fp64 continuation + a whole solve) but was measured to return
+         * the restart's local minimum, or its last iterate, where the single-phase solve returns the first attempt's. */
+        if (!S.next_attempt(r, attempt, it_total)) { fin = true; fin_status = r; have = false; }
       } else if (T.tail_cut > 0 && (passes >= T.tail_cut || (few && passes >= T.tail_few_from)) && S.phase == SV::PH_DIR && !queue_full) {
         const int pos = atomicAdd(T.tq.count, 1);
         if (pos >= T.tq.cap) queue_full = true;     /* it finishes here, and so does whatever else this lane takes */
@@ -752,14 +702,9 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
           S.park([pk, lp](int q) -> double & { return pk[q * lp]; }, attempt, it_total);
           pk += kParkRows * lp;
           {
-            double in[kTailInRows];
-#pragma unroll
-            for (int q = 0; q < 6; q++) in[q] = (double)state[q * ld + i];
-#pragma unroll
-            for (int q = 0; q < MPC_NCOEF; q++) in[6 + q] = (double)coeffs[q * ld + i];
+            double in[kTailInRows];      /* state, coefficients, psi box, weights: the rows mpc_tail_slice_kernel gathers from */
+            mpc::gather_instance(P, i, ld, state, coeffs, weights, in, in + 6, in + 13);
             in[11] = (double)yaw_lo[i]; in[12] = (double)yaw_hi[i];
-#pragma unroll
-            for (int q = 0; q < MPC_NW; q++) in[13 + q] = weights ? (double)weights[q * ld + i] : P.weights[q];
 #pragma unroll
             for (int q = 0; q < kTailInRows; q++) pk[q * lp] = in[q];
           }
@@ -771,20 +716,15 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
           ws.stage_drain();                          /* the trial sweep's stores of this wave have landed */
           /* (copied by the lane itself: the whole wave copying a deferring lane's column -- two round trips instead of twenty --
            * was built in round 4 and measured: no change in the launch's duration, 2.67 ms either way) */
-          tile_from_column<R>((R *)T.tq.iter + (int64_t)(pos >> 6) * (P.N - 1) * FL::IT_SZ * 64 + (pos & 63), ws, S.cur ? FL::IT1 : FL::IT0, P.N - 1);
+          copy_iterate<R>(P.N - 1, column_load<R>(ws, S.cur ? FL::IT1 : FL::IT0), tile_store(tile_place<R>(T.tq.iter, pos, P.N - 1)));
           status[i] = MPC_STATUS_PENDING;
           if (iters) iters[i] = S.iters + it_total;
           have = false;                              /* the lane takes its next instance at the next hand-over */
         }
       } else if (T.pass_cut > 0 && passes >= T.pass_cut && S.phase == SV::PH_DIR) {
         /* still running: park it for the next phase */
-        const int64_t pos = (int64_t)atomicAdd(T.n_out, 1);
-        T.out_inst[pos] = (int32_t)i;
-        T.out_src[pos] = (int32_t)(blockIdx.x * 64u + threadIdx.x);
-        double *pk = T.out_park + pos;
-        const int64_t lp = T.ld_park;
-        S.park([pk, lp](int q) -> double & { return pk[q * lp]; }, attempt, it_total);
-        have = false; more = false; col_busy = true;     /* the column keeps the parked iterate: this lane takes nothing else */
+        (void)park_for_next_phase(T, S, i, attempt, it_total, false);
+        have = false; more = false; col_busy = true;   /* the column keeps the parked iterate: this lane takes nothing else */
       }
     }
   }
@@ -867,7 +807,7 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_tail_slice_kernel(const MpcPara
       } else {
         RIO *o = ob + i;
         RIO *t = tb ? tb + i : nullptr;
-        S.unpack([o, l](int q) { return OutRef<RIO, R>{o + q * l}; }, [t, l](int q) { return OutRef<RIO, R>{t + q * l}; }, t != nullptr, ylo_user, yhi_user);
+        S.unpack(mpc::NoColumn{}, [o, l](int q) { return OutRef<RIO, R>{o + q * l}; }, [t, l](int q) { return OutRef<RIO, R>{t + q * l}; }, t != nullptr, ylo_user, yhi_user);
         st_arr[i] = fin_status;
         if (it_arr) it_arr[i] = S.iters + it_total;
         const int old = atomicSub(A.remaining + slot, 1);
@@ -887,7 +827,7 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_tail_slice_kernel(const MpcPara
         }
         const R *it_src = nullptr;
         for (int j = 0; j < A.n_src; j++)
-          if (j == sj) { pk = A.src[j].park + g; lp = A.src[j].cap; it_src = (const R *)A.src[j].iter + (g >> 6) * (int64_t)M * FL::IT_SZ * 64 + (g & 63); }
+          if (j == sj) { pk = A.src[j].park + g; lp = A.src[j].cap; it_src = tile_place<R>(A.src[j].iter, g, M); }
         int dpos = -1;
         if (spent) {                               /* the budget is spent: the entry moves to the next slice as it is, if there is room */
           dpos = atomicAdd(A.dst.count, 1);
@@ -898,35 +838,18 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_tail_slice_kernel(const MpcPara
           double *dk = A.dst.park + dpos;
           const int64_t dl = A.dst.cap;
           rows_copy(dk, dl, pk, lp, 0, kTailRows);
-          R *it_dst = (R *)A.dst.iter + (int64_t)(dpos >> 6) * M * FL::IT_SZ * 64 + (dpos & 63);
-          for (int k = 0; k < M; ++k) {
-            R rec[FL::IT_SZ];
-#pragma unroll
-            for (int f = 0; f < FL::IT_SZ; f++) rec[f] = it_src[(k * FL::IT_SZ + f) * 64];
-#pragma unroll
-            for (int f = 0; f < FL::IT_SZ; f++) it_dst[(k * FL::IT_SZ + f) * 64] = rec[f];
-          }
+          copy_iterate<R>(M, tile_load(it_src), tile_store(tile_place<R>(A.dst.iter, dpos, M)));
         } else {
+          /* the rows the tail cut wrote behind the solver's scalars: the same arrays at stride lp, the psi box between them */
           const double *pin = pk + (int64_t)kParkRows * lp;
           R st[6], cf[MPC_NCOEF], w[MPC_NW];
-#pragma unroll
-          for (int q = 0; q < 6; q++) st[q] = (R)pin[q * lp];
-#pragma unroll
-          for (int q = 0; q < MPC_NCOEF; q++) cf[q] = (R)pin[(6 + q) * lp];
-#pragma unroll
-          for (int q = 0; q < MPC_NW; q++) w[q] = (R)pin[(13 + q) * lp];
+          mpc::gather_instance(P, 0, lp, pin, pin + 6 * lp, pin + 13 * lp, st, cf, w);
           ylo_user = (R)pin[11 * lp]; yhi_user = (R)pin[12 * lp];
-          (void)S.setup(st, cf, ylo_user, yhi_user, w, false);
+          (void)S.setup(mpc::NoColumn{}, st, cf, ylo_user, yhi_user, w, false);
           const double *pq = pk;
           const int64_t lq = lp;
           S.unpark([pq, lq](int q) -> double { return pq[q * lq]; }, attempt, it_total);
-          const int I = S.cur ? FL::IT1 : FL::IT0;
-          for (int k = 0; k < M; ++k) {
-            R rec[FL::IT_SZ];
-#pragma unroll
-            for (int f = 0; f < FL::IT_SZ; f++) rec[f] = it_src[(k * FL::IT_SZ + f) * 64];
-            ws.template store_run<0, FL::IT_SZ>(k, I, rec);
-          }
+          copy_iterate<R>(M, tile_load(it_src), column_store<R>(ws, S.cur ? FL::IT1 : FL::IT0));
           have = true;
         }
       }
@@ -935,15 +858,7 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_tail_slice_kernel(const MpcPara
     if (have) {
       const int r = S.step();
       if (r != SV::MPC_RUNNING) {
-        if (attempt < 0 && r != MPC_STATUS_SUCCESS) {        /* (as in mpc_solve_kernel: started by the fp32 phase, not finished by fp64) */
-          attempt = 0; it_total += S.iters;
-          S.start_point();
-          S.begin(true);
-        } else if (r == MPC_STATUS_LINESEARCH && attempt == 0 && !S.no_restart) {
-          attempt = 1; it_total += S.iters;
-          S.start_point();
-          S.begin(false);
-        } else { fin = true; fin_status = r; have = false; keep = false; }
+        if (!S.next_attempt(r, attempt, it_total)) { fin = true; fin_status = r; have = false; keep = false; }
       } else if (spent && !keep && S.phase == SV::PH_DIR) {
         /* still running when the slice's budget is spent: parked for the next slice (its inputs and destination come along) */
         const int dpos = atomicAdd(A.dst.count, 1);
@@ -955,7 +870,7 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_tail_slice_kernel(const MpcPara
           S.park([dk, dl](int q) -> double & { return dk[q * dl]; }, attempt, it_total);
           rows_copy(dk, dl, pk, lp, kParkRows, kTailRows);
           ws.stage_drain();
-          tile_from_column<R>((R *)A.dst.iter + (int64_t)(dpos >> 6) * M * FL::IT_SZ * 64 + (dpos & 63), ws, S.cur ? FL::IT1 : FL::IT0, M);
+          copy_iterate<R>(M, column_load<R>(ws, S.cur ? FL::IT1 : FL::IT0), tile_store(tile_place<R>(A.dst.iter, dpos, M)));
           have = false;
         }
       }
@@ -999,8 +914,8 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_tail_slice_kernel(const MpcPara
  * WARM (the mpc_*_warm entry points): every lane of the group reads the instance's column of warm_in (Solver::solve_warm: the warm
  * attempt, then the complete cold solve if that does not end in SUCCESS); the first lane writes warm_out.
  * MODEL (the mpc_run_*_model / mpc_telemetry_*_model entry points): every lane of the group reads the group's column once, and
- * Solver::setup_model / unpack_model take the place of setup / unpack; warm_point judges a record against the relaxed box that
- * setup_model has just set from the column.
+ * Solver::setup / unpack get it as an mpc::ModelColumn; warm_point judges a record against the relaxed box that set-up has just
+ * set from the column.
  * `Extra`: what the WARM and MODEL builds take behind the solve arguments, one struct each in this order (mpc::WarmCall,
  * MpcModelPart); a build that is neither has the arguments it had. */
 template <bool WARM> struct WaveStatusPtr { typedef int32_t *__restrict__ type; };
@@ -1042,7 +957,7 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_wave_kernel(
       const MpcModelPart &W = std::get<sizeof...(Extra) - 1>(std::tie(extra...));
 #pragma unroll
       for (int q = 0; q < MPC_NMODEL; q++) mv[q] = W.model[q * W.ld_model + i];
-      return [&mv](int q) { return mv[q]; };
+      return mpc::ModelColumn{mv, 1};
     } else return mpc::NoColumn{};
   }();
   const int r = mpc::instance_solve(S, col, warm, st, cf, ylo, yhi, w);
@@ -1986,16 +1901,18 @@ template <int V> using Int = std::integral_constant<int, V>;
 /* f(std::true_type) or f(std::false_type): a run-time switch as a template argument */
 template <class F>
 static int with_bool(bool b, F f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
-/* f(soc, warm, model): the builds of an fp64 solve kernel, all six of them -- plain, SOC, WARM, MODEL, MODEL+SOC, MODEL+WARM.  A warm
- * call has no SOC (call_extras refuses it on a handle with max_soc > 0), so there is no SOC+WARM build.  (The HORIZON builds of the
- * lane kernel -- cold and WARM, never SOC -- are chosen in launch_lanes and rollout_fused_impl, which are their only launch sites.) */
+/* f(soc, warm, model, horizon): the builds of an fp64 solve kernel, all eight of them -- plain, SOC, WARM, MODEL, MODEL+SOC,
+ * MODEL+WARM, and the HORIZON builds of the lane kernel (MODEL builds by construction), cold and WARM.  A warm call has no SOC
+ * (call_extras refuses it on a handle with max_soc > 0) and neither has a horizon call, so there is no SOC+WARM or SOC+HORIZON build.
+ * (The wave path has no horizon: launch_wave passes false and never sees the last two.) */
 template <class F>
-static int with_build(bool soc, bool warm, bool model, F f) {
+static int with_build(bool soc, bool warm, bool model, bool horizon, F f) {
   constexpr std::true_type yes{};
   constexpr std::false_type no{};
-  if (warm) return model ? f(no, yes, yes) : f(no, yes, no);
-  if (soc) return model ? f(yes, no, yes) : f(yes, no, no);
-  return model ? f(no, no, yes) : f(no, no, no);
+  if (horizon) return warm ? f(no, yes, yes, yes) : f(no, no, yes, yes);
+  if (warm) return model ? f(no, yes, yes, no) : f(no, yes, no, no);
+  if (soc) return model ? f(yes, no, yes, no) : f(yes, no, no, no);
+  return model ? f(no, no, yes, no) : f(no, no, no, no);
 }
 /* the argument a kernel takes only in the builds with ON: (*p) or nothing, for std::apply */
 template <bool ON, class T>
@@ -2042,7 +1959,7 @@ static int launch_wave(MpcHandle *h, const SolveIO<R> &io, hipStream_t s, bool s
     constexpr int LPI = decltype(lpi)::value, G = 64 / LPI;
     const unsigned grid = (unsigned)((io.B + G - 1) / G);
     if constexpr (sizeof(R) == 8) {
-      return with_build(soc, warm != nullptr, model.model != nullptr, [&](auto soc_build, auto warm_build, auto model_build) {
+      return with_build(soc, warm != nullptr, model.model != nullptr, false, [&](auto soc_build, auto warm_build, auto model_build, auto) {
         constexpr bool SOC = decltype(soc_build)::value, WARM = decltype(warm_build)::value, MODEL = decltype(model_build)::value;
         const size_t lds = G * (per + (SOC ? (size_t)mpc::soc_fields_per_instance(h->params.N) * sizeof(R) : 0));
         return std::apply([&](auto... extra) {
@@ -2061,7 +1978,7 @@ static int launch_wave(MpcHandle *h, const SolveIO<R> &io, hipStream_t s, bool s
 }
 
 /* The lane kernel (an instance per lane; `ws`: the workspace of the phase).  single: the build that MPC_STAGING and, on an fp64
- * handle, with_build select: max_soc, a warm call, a model call (model.model) -- or, with `horizon`, the HORIZON builds (cold, WARM; never
+ * handle, with_build select: max_soc, a warm call, a model call (model.model), a horizon call (`horizon`: the HORIZON builds, never
  * staged, their LDS the mailbox of lane compaction).  The two phases of a mixed-precision solve are builds of
  * their own: the fp32 solver, and the fp64 solver that takes its iterates from fp32 records -- whatever RIO, the type at the ABI, is. */
 enum class LaneBuild { single, mixed_f32, mixed_f64 };
@@ -2070,32 +1987,25 @@ static int launch_lanes(MpcHandle *h, LaneBuild build, const SolveIO<RIO> &io, h
                         const WarmIO *warm = nullptr, const MpcModelPart &model = {}, const int32_t *horizon = nullptr) {
   const unsigned grid = (unsigned)((io.B + kBlock - 1) / kBlock);
   /* (r, rsrc: values of the solver's reals and of the reals its resumed iterates come in) */
-  auto go = [&](auto staging, auto r, auto rsrc, auto soc_build, auto warm_build, int64_t tile_reals, auto model_build) {
+  auto go = [&](auto staging, auto r, auto rsrc, auto soc_build, auto warm_build, int64_t tile_reals, auto model_build, auto horizon_build) {
     using R = decltype(r);
-    constexpr bool STAGING = decltype(staging)::value, WARM = decltype(warm_build)::value, MODEL = decltype(model_build)::value;
-    return launch_kernel(mpc_solve_kernel<STAGING, R, RIO, decltype(rsrc), decltype(soc_build)::value, WARM, false, MODEL>, grid,
-                         STAGING ? staging_lds_bytes<R>() : 0, s, h, io, (R *)ws, tile_reals,
-                         phase_of<false, WARM, MODEL>(T, warm ? *warm : WarmIO{}, {}, model));
+    constexpr bool HORIZON = decltype(horizon_build)::value, STAGING = decltype(staging)::value && !HORIZON;
+    constexpr bool WARM = decltype(warm_build)::value, MODEL = decltype(model_build)::value;
+    const size_t lds = HORIZON ? (T.compact_gap > 0 ? kMailboxBytes : 0) : STAGING ? staging_lds_bytes<R>() : 0;
+    return launch_kernel(mpc_solve_kernel<STAGING, R, RIO, decltype(rsrc), decltype(soc_build)::value, WARM, false, MODEL, HORIZON>, grid, lds, s, h, io,
+                         (R *)ws, tile_reals, phase_of<false, WARM, MODEL, HORIZON>(T, warm ? *warm : WarmIO{}, {}, model, {horizon}));
   };
   constexpr std::true_type yes{};
   constexpr std::false_type no{};
-  if constexpr (sizeof(RIO) == 8) {
-    if (horizon && build == LaneBuild::single)
-      return with_bool(warm != nullptr, [&](auto warm_build) {
-        constexpr bool WARM = decltype(warm_build)::value;
-        return launch_kernel(mpc_solve_kernel<false, double, double, double, false, WARM, false, true, true>, grid, T.compact_gap > 0 ? kMailboxBytes : 0, s, h,
-                             io, (double *)ws, h->ws_stride, phase_of<false, WARM, true, true>(T, warm ? *warm : WarmIO{}, {}, model, {horizon}));
-      });
-  }
-  if (build == LaneBuild::mixed_f32) return go(yes, float{}, RIO{}, no, no, h->ws_stride_f32, no);
-  if (build == LaneBuild::mixed_f64) return with_bool(soc, [&](auto soc_build) { return go(yes, double{}, float{}, soc_build, no, h->ws_stride_f64, no); });
+  if (build == LaneBuild::mixed_f32) return go(yes, float{}, RIO{}, no, no, h->ws_stride_f32, no, no);
+  if (build == LaneBuild::mixed_f64) return with_bool(soc, [&](auto soc_build) { return go(yes, double{}, float{}, soc_build, no, h->ws_stride_f64, no, no); });
   return with_bool(h->staging, [&](auto staging) {
     if constexpr (sizeof(RIO) == 8) {
-      return with_build(soc, warm != nullptr, model.model != nullptr, [&](auto soc_build, auto warm_build, auto model_build) {
-        return go(staging, RIO{}, RIO{}, soc_build, warm_build, h->ws_stride, model_build);
+      return with_build(soc, warm != nullptr, model.model != nullptr, horizon != nullptr, [&](auto soc_build, auto warm_build, auto model_build, auto horizon_build) {
+        return go(staging, RIO{}, RIO{}, soc_build, warm_build, h->ws_stride, model_build, horizon_build);
       });
     } else {
-      return go(staging, RIO{}, RIO{}, no, no, h->ws_stride, no);
+      return go(staging, RIO{}, RIO{}, no, no, h->ws_stride, no, no);
     }
   });
 }
@@ -2799,18 +2709,13 @@ static int rollout_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, do
   const WarmIO wc{warm, nullptr, warm, h->io_stride, x.w.wopts, 0};
   const MpcRollPart roll{steps, o9, hist ? 9 * ld : 0, state, status, iters};
   const unsigned grid = (unsigned)((B + kBlock - 1) / kBlock);
-  if (x.horizon) {                               /* the ROLL+HORIZON builds: not staged, no LDS (no lane compaction here) */
-    MPC_TRY(with_bool(x.warm, [&](auto warm_build) {
-      constexpr bool WARM = decltype(warm_build)::value;
-      return launch_kernel(mpc_solve_kernel<false, double, double, double, false, WARM, true, true, true>, grid, 0, s, h, io, (double *)h->ws, h->ws_stride,
-                           phase_of<true, WARM, true, true>(T, wc, roll, {model, ld}, {x.horizon}));
-    }));
-  } else
   MPC_TRY(with_bool(h->staging, [&](auto staging) {
-    return with_build(false, x.warm, model != nullptr, [&](auto, auto warm_build, auto model_build) {      /* (no SOC here: those handles loop) */
-      constexpr bool STAGING = decltype(staging)::value, WARM = decltype(warm_build)::value, MODEL = decltype(model_build)::value;
-      return launch_kernel(mpc_solve_kernel<STAGING, double, double, double, false, WARM, true, MODEL>, grid, STAGING ? staging_lds_bytes<double>() : 0,
-                           s, h, io, (double *)h->ws, h->ws_stride, phase_of<true, WARM, MODEL>(T, wc, roll, {model, ld}));
+    /* (no SOC here: those handles loop; the ROLL+HORIZON builds: not staged, no LDS -- no lane compaction here) */
+    return with_build(false, x.warm, model != nullptr, x.horizon != nullptr, [&](auto, auto warm_build, auto model_build, auto horizon_build) {
+      constexpr bool HORIZON = decltype(horizon_build)::value, STAGING = decltype(staging)::value && !HORIZON;
+      constexpr bool WARM = decltype(warm_build)::value, MODEL = decltype(model_build)::value;
+      return launch_kernel(mpc_solve_kernel<STAGING, double, double, double, false, WARM, true, MODEL, HORIZON>, grid, STAGING ? staging_lds_bytes<double>() : 0,
+                           s, h, io, (double *)h->ws, h->ws_stride, phase_of<true, WARM, MODEL, HORIZON>(T, wc, roll, {model, ld}, {x.horizon}));
     });
   }));
   MPC_TRY(solve_end(h, io, s, rec, tp, false));

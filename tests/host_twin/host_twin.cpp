@@ -113,7 +113,7 @@ static int solve_parked_t(const MpcParams *p, int64_t B, int64_t ld, int pass_cu
         const int r = cur->step();
         ++passes;
         if (r != SV::MPC_RUNNING) {
-          if (r == MPC_STATUS_LINESEARCH && attempt == 0 && !cur->no_restart) { attempt = 1; it_total += cur->iters; cur->start_point(); cur->begin(false); continue; }
+          if (cur->next_attempt(r, attempt, it_total)) continue;
           s = r; cur->iters += it_total; fin = cur;
           break;
         }
@@ -216,16 +216,8 @@ static int solve_mixed_t(const MpcParams *p, int64_t B, int64_t ld, const RIO *s
           D.begin(true); attempt = 0; it_total = A.iter + it_total; in_double = true;
           continue;
         }
-        if (in_double && attempt < 0 && r != MPC_STATUS_SUCCESS) {   /* started by fp32, not finished by fp64: solved again as the single-phase solve does it */
-          attempt = 0; it_total += D.iters; D.start_point(); D.begin(true);
-          continue;
-        }
-        if (r == MPC_STATUS_LINESEARCH && attempt == 0 && !(in_double ? D.no_restart : A.no_restart)) {
-          attempt = 1;
-          if (in_double) { it_total += D.iters; D.start_point(); D.begin(false); }
-          else { it_total += A.iters; A.start_point(); A.begin(false); }
-          continue;
-        }
+        /* (attempt -1: started by fp32, not finished by fp64: solved again as the single-phase solve does it) */
+        if (in_double ? D.next_attempt(r, attempt, it_total) : A.next_attempt(r, attempt, it_total)) continue;
         s = r;
         break;
       }
@@ -292,7 +284,7 @@ static int traffic_t(const MpcParams *p, int64_t B, int64_t ld, const R *state, 
         const int r = S.step();
         ++passes;
         if (r == SV::MPC_RUNNING) continue;
-        if (r == MPC_STATUS_LINESEARCH && attempt == 0 && !S.no_restart) { attempt = 1; it_total += S.iters; S.start_point(); S.begin(false); continue; }
+        if (S.next_attempt(r, attempt, it_total)) continue;
         break;
       }
     }

@@ -34,7 +34,7 @@ def population(pkg, params, waypoints, B=193):
 
 
 def twin_model_solve(twin, params, batch, model, weights=None, want_traj=True):
-    """Solver::setup_model / unpack_model of the device header, CPU build, with the arguments of mpc_solve_batch_host_model."""
+    """Solver::setup / unpack of the device header on the instance's model column, CPU build, with the arguments of mpc_solve_batch_host_model."""
     f = lambda a: np.ascontiguousarray(a, dtype=np.float64)
     st, cf, yl, yh, md = f(batch["state"]), f(batch["coeffs"]), f(batch["yaw_lo"]), f(batch["yaw_hi"]), f(model)
     B = st.shape[1]

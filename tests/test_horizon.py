@@ -1,6 +1,6 @@
 """Per-instance horizon (include/mpc_amd_horizon.h: the seven mpc_*_horizon entry points), checked without a GPU: the CPU build
 tests/host_twin/horizon_twin.cpp runs the per-instance driver of csrc/mpc_core.h with an mpc::HorizonColumn -- the
-Solver::setup_horizon / solve_warm / warm_store / unpack_horizon and mpc::RolloutCar that the HORIZON builds of the lane kernel
+Solver::setup / solve_warm / warm_store / unpack (on an mpc::HorizonColumn) and mpc::RolloutCar that the HORIZON builds of the lane kernel
 run per lane.  Yardsticks: the existing twin on handles created with N = n (bitwise), and the oracle with one OrcConfig of
 N = n_i per instance."""
 import ctypes as C

@@ -1,5 +1,5 @@
 """Per-instance model values (include/mpc_amd.h, "per-instance model values": dt, Lf and the four limits of every instance in
-model [6][ld]), checked without a GPU: the CPU build tests/host_twin (mpc_twin_solve) calls the same Solver::setup_model / unpack_model as the MODEL
+model [6][ld]), checked without a GPU: the CPU build tests/host_twin (mpc_twin_solve) calls the same Solver::setup / unpack (on the instance's model column) as the MODEL
 builds of the lane kernel.  The yardstick is the oracle solving every instance with its own OrcConfig."""
 import ctypes as C
 import os

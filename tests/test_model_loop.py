@@ -1,6 +1,6 @@
 """Warm starts and closed loops with per-instance model values (include/mpc_amd.h: mpc_solve_batch_*_warm_model,
 mpc_rollout_batch_device_warm_model, mpc_rollout_batch_device_fused_model), checked without a GPU: the CPU build tests/host_twin (mpc_twin_solve / mpc_twin_rollout)
-calls the same Solver::setup_model / solve_warm / warm_store / unpack_model and mpc::RolloutCar as the WARM+MODEL and ROLL+MODEL builds
+calls the same Solver::setup / solve_warm / warm_store / unpack (on the instance's model column) and mpc::RolloutCar as the WARM+MODEL and ROLL+MODEL builds
 of the lane kernel.  Yardsticks: the plain twins (uniform rows), the cold loop, and the oracle's own cold loop with one OrcConfig per
 car."""
 import ctypes as C

@@ -1,5 +1,5 @@
 """run() and the telemetry handler with per-instance model values, on the CPU: tests/host_twin (mpc_twin_run) -- the templated run_pre /
-telemetry_to_pose / run_post / command_from_run of csrc/mpc_run_core.h around Solver::setup_model / solve_warm / unpack_model, built
+telemetry_to_pose / run_post / command_from_run of csrc/mpc_run_core.h around Solver::setup / solve_warm / unpack (on the instance's model column), built
 with g++ -- against the oracle's mpc_run / telemetry_handler with a per-car OrcConfig on the stated population (48 lake-track cars,
 seed 77, the columns of draw_rows seed 9), against tests/host_twin (mpc_twin_run without a model array) for columns that repeat the handle's values, and on columns
 that cannot be used."""

@@ -153,10 +153,15 @@ def test_correction_leaves_the_headline_population_almost_untouched(pkg, host_tw
 def test_an_instance_is_parked_only_between_line_searches():
     """The correction's state (Solver's SocState, the SOC records) lives within one line search and is not carried by park()/unpark():
     every place in the kernels that parks an instance does so at phase PH_DIR -- or hands over from the fp32 solver, which never
-    corrects (MPC_PROMOTE)."""
+    corrects (MPC_PROMOTE).  A place that parks is a call of Solver::park or of park_for_next_phase, the one helper that appends an
+    instance to the next phase's list (its own call of Solver::park, inside its body, is what those places run)."""
     src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "carnd-mpc-project_amd", "csrc",
                             "mpc_solver.hip")).read().split("\n")
-    sites = [i for i, l in enumerate(src) if "S.park(" in l]
+    defs = [i for i, l in enumerate(src) if "park_for_next_phase(const MpcPhase" in l]
+    assert len(defs) == 1
+    end = next(i for i in range(defs[0], len(src)) if src[i] == "}")
+    assert sum("S.park(" in l for l in src[defs[0]:end]) == 1
+    sites = [i for i, l in enumerate(src) if ("S.park(" in l or "park_for_next_phase(" in l) and not defs[0] <= i <= end]
     assert len(sites) >= 6
     for i in sites:
         ctx = "\n".join(src[max(0, i - 16):i])
