@@ -20,6 +20,7 @@
 namespace mpc {
 
 enum : int { RUN_MAX_PTS = 8 };
+#define RUN_MAX_STEERING_ANGLE 1.57079632679489661923   /* rad: the largest |steering| of a pose / |steering_angle| of a telemetry row that is taken as one */
 
 /* Rows of `pre` [RUN_PRE_ROWS][ld], what the pre-solve half hands to the solve and to the post-solve half (and to the caller who
  * asks for it): the solve's inputs first, in the order a solve call takes them */
@@ -100,14 +101,35 @@ MPC_HD double table_lookup(const double *xs, int nx, const double *ys, int ny, d
   return fmin(ys[ny - 1], maxv);
 }
 
+/* normalizeAngle (utils.h:87-92): an angle -> [-pi, pi).  The reference subtracts 2 pi until the value fits, a loop whose trip
+ * count is the caller's number: 1.6e11 turns for psi = 1e12, and no end at all for an infinity or for |psi| above ~1e17, where
+ * the subtraction no longer changes the value.  Here no trip count depends on data:
+ *   |a| <= MPC_NORMALIZE_SEQ_RANGE (64 pi and a little)  the reference's sequential subtraction, at most NORMALIZE_SEQ_TURNS turns: bit for bit what
+ *                                         the two while loops gave (202 - 32 * 2 pi < pi, so 32 turns reach the interval from there);
+ *   beyond it, |a| < 1e9 (fsincos' range) ONE reduction a - rint(a / 2 pi) * 2 pi in a single FMA, then the turns above take the
+ *                                         one step that may be left.  Against the exact remainder: within 4 ulp(|a|) -- a itself is
+ *                                         only known to half an ulp, and the double 2 pi is off by 3.9e-17 relative, a third of one;
+ *   not finite, or |a| >= 1e9             returned as it came: fsincos flags such an angle with not-a-number and the instance ends
+ *                                         with a status (there is no such heading in this model). */
+enum : int { NORMALIZE_SEQ_TURNS = 32 };
+#define MPC_NORMALIZE_SEQ_RANGE 202.0
+static_assert(MPC_NORMALIZE_SEQ_RANGE > 64.0 * M_PI && MPC_NORMALIZE_SEQ_RANGE - NORMALIZE_SEQ_TURNS * 2.0 * M_PI < 3.0, "the turns reach [-pi, pi)");
+MPC_HD double normalize_angle(double a) {
+  if (!(fabs(a) < 1.0e9)) return a;
+  if (fabs(a) > MPC_NORMALIZE_SEQ_RANGE) a = fma(-rint(a * 1.59154943091895345554e-01), 2.0 * M_PI, a);
+  MPC_STAGE_LOOP      /* (one copy of the turn: unrolled 32 times it costs mpc_run_pre_kernel a register, 169 instead of 168, and with it a wave of occupancy) */
+  for (int turn = 0; turn < NORMALIZE_SEQ_TURNS; turn++) {
+    if (a >= M_PI) a -= 2.0 * M_PI;
+    else if (a < -M_PI) a += 2.0 * M_PI;
+    else break;
+  }
+  return a;
+}
+
 /* RoadGeometry::orientation (RoadGeometry.cpp:41-47) */
 MPC_HD double road_orientation(const double *c, double px, double dir) {
   double psi = atan(poly5_der(c, px));
-  if (dir < 0.0) {
-    psi += M_PI;
-    while (psi >= M_PI) psi -= 2.0 * M_PI;
-    while (psi < -M_PI) psi += 2.0 * M_PI;
-  }
+  if (dir < 0.0) psi = normalize_angle(psi + M_PI);
   return psi;
 }
 
@@ -176,13 +198,19 @@ MPC_HD void run_pre(const MpcParams &P, const MV &m_, const double *pose, double
   MPC_UNROLL
   for (int i = 0; i < RUN_MAX_PTS; i++) if (i == n - 1) back = px[i];
   const double dir = back - 0.0;                                                  /* computeOrientationChange(0, back) */
-  R.max_yaw_change = (road_orientation(c, back, dir) - road_orientation(c, 0.0, dir)) * (back - front) / back;   /* :339 */
+  /* (a road whose first and last waypoint have the same x in the car's frame -- all of them at one x, all of them at the car -- has
+   * no extent along the car's axis and no fit that means anything: not-a-number here, and through the psi box a status) */
+  const double span = back - front;
+  R.max_yaw_change = (road_orientation(c, back, dir) - road_orientation(c, 0.0, dir)) * (span != 0.0 ? span : NAN) / back;   /* :339 */
   const double max_speed = table_lookup(P.yaw_changes, P.n_yaw_changes, P.yaw_change_speeds, P.n_yaw_change_speeds,
                                         R.max_yaw_change, m.max_speed);           /* :340 */
   R.target_speed = table_lookup(P.steers, P.n_steers, P.steer_speeds, P.n_steer_speeds, pose[4], max_speed);   /* :342 */
   if (R.max_yaw_change < 0.0) { R.yaw_lo = R.max_yaw_change; R.yaw_hi = 0.1; }   /* :345-352 */
   else { R.yaw_lo = -0.1; R.yaw_hi = R.max_yaw_change; }
-  R.state[0] = 0.0; R.state[1] = 0.0; R.state[2] = 0.0; R.state[3] = pose[3]; R.state[4] = cte; R.state[5] = epsi;   /* :355-356 */
+  /* (a steering angle that is no angle of a wheel -- not a number, beyond a quarter turn -- only picks a row of the speed table above
+   * and would pass unnoticed: the instance is handed to the solve without a speed, which ends it with a status) */
+  const double v0 = fabs(pose[4]) <= RUN_MAX_STEERING_ANGLE ? pose[3] : NAN;
+  R.state[0] = 0.0; R.state[1] = 0.0; R.state[2] = 0.0; R.state[3] = v0; R.state[4] = cte; R.state[5] = epsi;   /* :355-356 */
 }
 
 MPC_HD void run_pre(const MpcParams &P, const double *pose, double *px, double *py, int n, RunPre &R) { run_pre(P, P, pose, px, py, n, R); }
@@ -203,16 +231,15 @@ MPC_HD void run_post(const MpcParams &P, double max_yaw_change, double target_sp
 }
 
 /* ---- N2: the telemetry handler around run(), src/mpc_main.cpp:126-159 and :171-174 ------------------ */
-/* tel = {x, y, psi (rad, any range), speed (mph), steering_angle (simulator sign), previous throttle command};
+/* tel = {x, y, psi (rad, any range: normalize_angle above says what becomes of it), speed (mph), steering_angle (simulator sign), previous throttle command};
  * extra = the handler's mean solve time added to Config::lookahead (mpc_main.cpp:158).
  * -> pose {x,y,psi,v,steering,acceleration} after latency compensation (Vehicle::update + Vehicle::move) */
 template <class MV>
 MPC_HD void telemetry_to_pose(const MpcParams &P, const MV &m_, const double *tel, double extra, double *pose) {
   const MV &m = run_model_of(P, m_);
-  double psi = tel[2];
-  while (psi >= M_PI) psi -= 2.0 * M_PI;                 /* normalizeAngle, mpc_main.cpp:127 */
-  while (psi < -M_PI) psi += 2.0 * M_PI;
-  const double v = tel[3] * 1609.34 / 3600.0;            /* MpH2MpS, :129 */
+  const double psi = normalize_angle(tel[2]);            /* normalizeAngle, mpc_main.cpp:127 */
+  const double mph = tel[3] >= 0.0 ? tel[3] : NAN;       /* (a speedometer reading below zero is none: the instance ends with a status) */
+  const double v = mph * 1609.34 / 3600.0;               /* MpH2MpS, :129 */
   const double steer = -tel[4];                          /* :131 */
   const double acc = (tel[5] - v / 50.0) * 6.0;          /* :156 */
   pose[0] = tel[0]; pose[1] = tel[1]; pose[2] = psi; pose[3] = v; pose[4] = steer; pose[5] = acc;

@@ -41,15 +41,19 @@ bool find_value(const std::string &s, const char *key, size_t &pos) {
     p += pat.size();
   }
 }
-bool get_num(const std::string &s, const char *key, double &out) {
+/* strtod reads "inf", "nan" and "1e999" as numbers; JSON has none of them and the handler has no use for them: such a value
+ * makes the frame malformed.  NUM_ABSENT: no such key, or no number behind it; NUM_BAD: a number that is not finite */
+enum { NUM_BAD = -1, NUM_ABSENT = 0, NUM_OK = 1 };
+int get_num(const std::string &s, const char *key, double &out) {
   size_t p;
-  if (!find_value(s, key, p)) return false;
+  if (!find_value(s, key, p)) return NUM_ABSENT;
   const char *b = s.c_str() + p;
   char *end;
   const double v = strtod(b, &end);
-  if (end == b) return false;
+  if (end == b) return NUM_ABSENT;
+  if (!std::isfinite(v)) return NUM_BAD;
   out = v;
-  return true;
+  return NUM_OK;
 }
 int get_arr(const std::string &s, const char *key, double *out, int cap) {
   size_t p;
@@ -63,7 +67,7 @@ int get_arr(const std::string &s, const char *key, double *out, int cap) {
     if (*c == ']' || !*c) break;
     char *end;
     const double v = strtod(c, &end);
-    if (end == c) return -1;
+    if (end == c || !std::isfinite(v)) return -1;
     if (n < cap) out[n] = v;
     n++;
     c = end;
@@ -102,10 +106,12 @@ extern "C" int mpc_wire_parse(const char *frame, int64_t len, MpcWireTelemetry *
   const int nx = get_arr(obj, "ptsx", out->ptsx, 8), ny = get_arr(obj, "ptsy", out->ptsy, 8);
   if (nx < 3 || nx > 8 || ny != nx) return MPC_ERR_INVALID;
   out->npts = nx;
-  if (!get_num(obj, "x", out->x) || !get_num(obj, "y", out->y) || !get_num(obj, "psi", out->psi) ||
-      !get_num(obj, "speed", out->speed) || !get_num(obj, "steering_angle", out->steering_angle))
+  if (get_num(obj, "x", out->x) != NUM_OK || get_num(obj, "y", out->y) != NUM_OK || get_num(obj, "psi", out->psi) != NUM_OK ||
+      get_num(obj, "speed", out->speed) != NUM_OK || get_num(obj, "steering_angle", out->steering_angle) != NUM_OK)
     return MPC_ERR_INVALID;
-  if (!get_num(obj, "throttle", out->throttle)) out->throttle = 0.0;      /* read only by the COLLECT_DATA build (:137) */
+  const int thr = get_num(obj, "throttle", out->throttle);               /* read only by the COLLECT_DATA build (:137) */
+  if (thr == NUM_BAD) return MPC_ERR_INVALID;
+  if (thr == NUM_ABSENT) out->throttle = 0.0;
   return MPC_WIRE_TELEMETRY;
 }
 

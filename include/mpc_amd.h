@@ -328,7 +328,24 @@ int mpc_run_batch_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const doub
  *   extra_latency seconds added to Config::lookahead (the handler's mean solve time, mpc_main.cpp:158)
  *   ptsx, ptsy    as in mpc_run_batch_device (in: global, out: vehicle frame)
  *   cmd [2][ld]   steering_angle and throttle of the reply (mpc_main.cpp:183-184)
- *   out8 [8][ld] or NULL   run()'s own return vector */
+ *   out8 [8][ld] or NULL   run()'s own return vector
+ * What run() and the handler owe an instance whose inputs no caller should send -- every mpc_run_batch_* and mpc_telemetry_batch_*
+ * entry point, their _warm, _model and _host forms, the wire forms, MPC::run() of the drop-in: the same as the solve.  A status
+ * other than MPC_STATUS_SUCCESS, a launch that ends (no loop in the device code has a trip count that the data decide), and no effect
+ * on the other instances of the batch, which come out bit for bit as in a batch without it.  out8, cmd and pre of such an instance
+ * may hold not-a-number.  What counts as such an input:
+ *   - a value of tel / pose, or a waypoint, that is not finite, or so large that the frame change overflows;
+ *   - psi: any finite value is an angle.  tel's psi is brought to [-pi, pi): up to |psi| = 202 (more than 64 pi) by the reference's
+ *     sequential subtraction, bit for bit; beyond that by one reduction psi - rint(psi / 2 pi) * 2 pi, within 4 ulp(|psi|) of the
+ *     exact remainder; from |psi| = 1e9 on (the range of the sine / cosine of this library) and for a psi that is not finite the
+ *     instance ends with a status.  pose's psi is taken as it is, with the same limit of 1e9;
+ *   - speed [mph] below zero (a speedometer has no such reading; v of a pose may be negative, as the state of a solve may), or
+ *     beyond the (relaxed) speed limit, which is MPC_STATUS_INFEASIBLE as ever;
+ *   - |steering_angle| (tel) or |steering| (pose) above pi / 2, or not a number;
+ *   - waypoints whose first and last have the same x in the car's frame (all at one x, all at the car): no road along the car's axis;
+ *   - with `model`, a column that is not usable (the _model section below).
+ * Waypoints behind the car, in decreasing x, are none: the reference provides for them (RoadGeometry::orientation) and so does
+ * this library.  A warm form starts such an instance as the header says for any refused record or failed warm attempt. */
 int mpc_telemetry_batch_device(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
                                double *ptsx, double *ptsy, double *cmd, double *out8, int32_t *status, void *stream);
 /* The same for host arrays (tel, ptsx, ptsy read only; cmd [2][ld], status [ld] written): one copy in, the kernels, one copy
@@ -585,7 +602,10 @@ typedef struct MpcWireTelemetry {
 /* One text frame `42["telemetry",{...}]`: MPC_WIRE_TELEMETRY and *out filled; MPC_WIRE_MANUAL when the frame carries no
  * data (the reference answers `42["manual",{}]`, mpc_main.cpp:217-219); MPC_WIRE_IGNORE for anything that is not a "42"
  * telemetry event (the reference stays silent); MPC_ERR_INVALID for a malformed telemetry object (the reference would
- * throw out of json::parse). */
+ * throw out of json::parse).  A number that is not finite -- `inf`, `nan`, `1e999`, which strtod would read and JSON does not have --
+ * anywhere in the object (ptsx, ptsy, x, y, psi, speed, steering_angle, throttle) makes the frame malformed: MPC_ERR_INVALID.
+ * lib/mpc_replay answers such a frame like any other it cannot parse: a message on stderr, no reply, exit status 1 at the end, and
+ * the other frames of the group get the replies they get without it. */
 int mpc_wire_parse(const char *frame, int64_t len, MpcWireTelemetry *out);
 /* The reply `42["steer",{...}]` byte for byte as mpc_main.cpp:183-197 builds it with nlohmann::json 2.1.1 (build without
  * PLOT_TRAJECTORY).  Returns the length (NUL-terminated in buf), or MPC_ERR_INVALID if cap is too small. */

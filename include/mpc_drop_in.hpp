@@ -48,10 +48,20 @@ inline double deg2rad(double x) { return x * M_PI / 180; }             /* utils.
 inline double rad2deg(double x) { return x * 180 / M_PI; }             /* utils.h:75 */
 template <typename T> T square(const T &a) { return a * a; }           /* utils.h:81 */
 template <typename T> T clamp(const T a, const T lo, const T hi) { return a < lo ? lo : (a > hi ? hi : a); }
-template <typename T> T normalizeAngle(const T &a) {                   /* utils.h:87-92: [-pi, pi) */
+/* utils.h:87-92: [-pi, pi).  The rule of the library (mpc::normalize_angle, csrc/mpc_run_core.h), bit for bit: up to |a| = 202
+ * (> 64 pi) the reference's sequential subtraction, at most 32 turns; beyond it and below 1e9 one reduction a - rint(a / 2 pi) * 2 pi
+ * first (within 4 ulp(|a|) of the exact remainder); a value that is not finite, or from 1e9 on, comes back as it is -- where the
+ * reference's two while loops would spin 1.6e11 times (1e12) or for ever (an infinity, anything above ~1e17). */
+template <typename T> T normalizeAngle(const T &a) {
+  using std::fabs; using std::fma; using std::rint;
   T r = a;
-  while (r >= M_PI) r -= 2. * M_PI;
-  while (r < -M_PI) r += 2. * M_PI;
+  if (!(fabs(r) < 1.0e9)) return r;
+  if (fabs(r) > 202.0) r = fma(-rint(r * 1.59154943091895345554e-01), T(2. * M_PI), r);
+  for (int turn = 0; turn < 32; turn++) {
+    if (r >= M_PI) r -= 2. * M_PI;
+    else if (r < -M_PI) r += 2. * M_PI;
+    else break;
+  }
   return r;
 }
 const double EPSILON = 1E-6;                                           /* utils.h:95 */

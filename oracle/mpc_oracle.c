@@ -57,11 +57,19 @@ static double polyder3(const double *c, int nc, double x) {
   return r;
 }
 
-/* src/utils/utils.h:87-92 */
+/* src/utils/utils.h:87-92, with a bounded trip count (the reference's two while loops never end on an infinity): its sequential
+ * subtraction up to |a| = 202 (> 64 pi; at most 32 turns, the reference's result bit for bit), one reduction by rint(a / 2 pi)
+ * turns first beyond that, and a value that is not finite or not below 1e9 returned as it is -- the rule of the product's
+ * mpc::normalize_angle */
 double orc_normalize_angle(double a) {
   double r = a;
-  while (r >= M_PI) r -= 2. * M_PI;
-  while (r < -M_PI) r += 2. * M_PI;
+  if (!(fabs(r) < 1.0e9)) return r;
+  if (fabs(r) > 202.0) r = fma(-rint(r * 1.59154943091895345554e-01), 2. * M_PI, r);
+  for (int turn = 0; turn < 32; turn++) {
+    if (r >= M_PI) r -= 2. * M_PI;
+    else if (r < -M_PI) r += 2. * M_PI;
+    else break;
+  }
   return r;
 }
 

@@ -32,6 +32,33 @@ def test_drop_in_compiles_and_fails_loudly_without_gpu(drop_in_binary, golden_di
     assert r.returncode == 3 and "mpc_create failed" in r.stderr      # no silent CPU path
 
 
+def test_drop_in_normalize_angle_returns_and_is_the_librarys(tmp_path):
+    """normalizeAngle of the drop-in on the psi values of tests/run_garbage_helpers.py (an infinity, 1e300 and 1e12 among them, on which
+    the reference's two while loops do not end, or not today): it returns -- the program runs under a time limit -- and gives bit for bit
+    what mpc::normalize_angle of the library gives (host build of csrc/mpc_run_core.h)."""
+    import math
+    import run_garbage_helpers as H
+    out = str(tmp_path / "normalize_angle_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "carnd-mpc-project_amd", "csrc"),
+                           "-o", out, os.path.join(ROOT, "tests", "cpp", "normalize_angle_test.cpp")])
+    values = [v for _, v in H.PSI_OUT_OF_RANGE + H.PSI_IN_RANGE] + [0.0, 3.0, -3.5, math.pi, -math.pi, 64 * math.pi, 202.0, 202.5, -1e6]
+    r = subprocess.run([out] + [float(v).hex() if math.isfinite(v) else repr(float(v)) for v in values], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr
+    lines = r.stdout.strip().splitlines()
+    assert len(lines) == len(values)
+    for v, l in zip(values, lines):
+        a, drop_in, library = l.split()
+        assert drop_in == library, (v, l)
+        if math.isfinite(v):
+            assert float.fromhex(a) == v
+            if abs(v) < 1e9:
+                assert -math.pi <= float.fromhex(drop_in) < math.pi, (v, l)
+            else:
+                assert float.fromhex(drop_in) == v                     # out of range: handed on as it came
+        else:
+            assert drop_in in ("inf", "-inf", "nan", "-nan") and (drop_in.lstrip("-") == "nan" or drop_in == a)
+
+
 @pytest.mark.gpu
 def test_drop_in_reproduces_test_cpp_sequence(drop_in_binary, golden_dir):
     r = subprocess.run([drop_in_binary, os.path.join(golden_dir, "config-stable.json"), "25"], capture_output=True, text=True)

@@ -45,6 +45,37 @@ def test_parse_frames(pkg):
         assert L.mpc_wire_parse(frame, len(frame), C.byref(t)) == want, frame
 
 
+POISON = ('"psi":1e999', '"psi":inf', '"psi":-Infinity', '"speed":nan', '"x":1e999', '"y":-inf', '"steering_angle":NaN', '"throttle":1e999')
+
+
+def _poisoned(frame, field):
+    """`frame` with the value of one field replaced by a number that is not finite; field = '"key":value'"""
+    import re
+    key = field.split(":")[0]
+    out, n = re.subn(re.escape(key) + r":[^,}\]]+", field, frame, count=1)
+    assert n == 1, (frame, field)
+    return out
+
+
+def test_parse_refuses_numbers_that_are_not_finite(pkg):
+    """strtod reads inf, nan and 1e999; the parser must not hand them to the handler: MPC_ERR_INVALID, for every number of the object,
+    the waypoint lists included -- and the same frame without the poison parses."""
+    L = pkg.library()
+    t = pkg.MpcWireTelemetry()
+    good = _frame(-40.62, 108.73, 3.733651, 41.5, 0.0312, 0.55, [-32.16, -43.49, -61.09, -78.29, -93.05, -107.77], [113.36, 105.94, 92.88, 78.73, 65.34, 50.57])
+    assert L.mpc_wire_parse(good.encode(), len(good), C.byref(t)) == 1
+    for field in POISON:
+        f = _poisoned(good, field).encode()
+        assert L.mpc_wire_parse(f, len(f), C.byref(t)) == -1, f
+    for bad in ("-43.49,inf,-78.29", "-43.49,1e999,-78.29", "-43.49,nan,-78.29"):
+        for key in ("ptsx", "ptsy"):
+            f = good.replace('"%s":[' % key, '"%s":[%s,' % (key, bad), 1).encode()
+            assert L.mpc_wire_parse(f, len(f), C.byref(t)) == -1, f
+    # a large finite number is a number: the handler deals with it (tests/test_run_garbage.py)
+    f = _poisoned(good, '"psi":1e300').encode()
+    assert L.mpc_wire_parse(f, len(f), C.byref(t)) == 1 and t.psi == 1e300
+
+
 def test_reply_framing_is_byte_exact(pkg):
     L = pkg.library()
     buf = C.create_string_buffer(256)
@@ -104,6 +135,37 @@ def test_replay_tool_matches_oracle_handler(pkg, golden_dir, waypoints):
                 assert abs(d["steering_angle"] - ref_steer) * params.max_steering < 5 * TOL_STEER
                 assert abs(d["throttle"] - ref_thr) < 1e-5
             prev[i] = d["throttle"]
+
+
+@pytest.mark.gpu
+def test_replay_tool_skips_a_poisoned_frame(pkg, golden_dir, waypoints):
+    """lib/mpc_replay with one frame "psi":1e999 between good ones, in the first and in the second round: it is reported like any
+    frame that cannot be parsed (stderr, exit status 1, no reply), the tool ends, and every other frame gets the reply it gets
+    without it, byte for byte."""
+    cfgname = "config-fast.json"
+    params = pkg.params_from_json(os.path.join(golden_dir, cfgname))
+    B = 8
+    f1, _, _ = _frames_for(pkg, params, waypoints, B, 75)
+    f2, _, _ = _frames_for(pkg, params, waypoints, B, 76)
+    exe = os.path.join(os.path.dirname(pkg.library_path()), "mpc_replay")
+    cfg = os.path.join(golden_dir, cfgname)
+    ref = subprocess.run([exe, cfg, "--cars", str(B)], input="\n".join(f1 + f2) + "\n", capture_output=True, text=True, timeout=120)
+    assert ref.returncode == 0, ref.stderr
+    ref_lines = ref.stdout.splitlines()
+    assert len(ref_lines) == 2 * B
+    bad1, bad2 = 3, 6
+    g1, g2 = list(f1), list(f2)
+    g1[bad1] = _poisoned(f1[bad1], '"psi":1e999'); g2[bad2] = _poisoned(f2[bad2], '"speed":nan')
+    r = subprocess.run([exe, cfg, "--cars", str(B)], input="\n".join(g1 + g2) + "\n", capture_output=True, text=True, timeout=120)
+    assert r.returncode == 1
+    assert "line %d: malformed telemetry frame" % (bad1 + 1) in r.stderr and "line %d: malformed telemetry frame" % (B + bad2 + 1) in r.stderr
+    want = [l for i, l in enumerate(ref_lines) if i not in (bad1, B + bad2)]
+    # (car bad1 of round 2 carries the throttle of its own previous reply, which it did not get: its frame is compared apart)
+    got = r.stdout.splitlines()
+    assert len(got) == 2 * B - 2
+    skip = B - 1 + bad1                      # car bad1's reply of round 2, in the output without round 1's missing line
+    assert [l for i, l in enumerate(got) if i != skip] == [l for i, l in enumerate(want) if i != skip]
+    assert got[skip].startswith('42["steer",')
 
 
 @pytest.mark.gpu
