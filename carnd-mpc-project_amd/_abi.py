@@ -103,6 +103,15 @@ EXPORTS = ["mpc_params_default", "mpc_params_load_json", "mpc_create", "mpc_set_
 HORIZON_EXPORTS = ["mpc_solve_batch_device_horizon", "mpc_solve_batch_host_horizon", "mpc_solve_batch_device_warm_horizon",
                    "mpc_solve_batch_host_warm_horizon", "mpc_rollout_batch_device_horizon", "mpc_rollout_batch_device_warm_horizon",
                    "mpc_rollout_batch_device_fused_horizon"]
+# ... and include/mpc_amd_certify.h (the certificate of a stored point; tests/test_certify.py)
+CERTIFY_EXPORTS = ["mpc_certify_batch_device", "mpc_certify_batch_host"]
+NCERT = 12       # MPC_NCERT: rows of cert [NCERT][ld], in the order of CERT_ROWS
+(CERT_OBJ, CERT_CONSTR_VIOL, CERT_DUAL_INF, CERT_COMPL, CERT_NLP_ERROR, CERT_BOUND_VIOL, CERT_OBJ_SCALING, CERT_COST_CTE, CERT_COST_EPSI,
+ CERT_COST_V, CERT_COST_DELTA, CERT_COST_DDELTA) = range(NCERT)
+CERT_ROWS = ("obj", "constr_viol", "dual_inf", "compl", "nlp_error", "bound_viol", "obj_scaling", "cost_cte", "cost_epsi", "cost_v",
+             "cost_delta", "cost_ddelta")
+CERT_CONVERGED, CERT_ACCEPTABLE, CERT_NOT_CONVERGED, CERT_NOT_A_POINT, CERT_NO_PROBLEM = range(5)
+CERT_VERDICT_NAMES = {0: "converged", 1: "acceptable", 2: "not_converged", 3: "not_a_point", 4: "no_problem"}
 
 _lib = None
 
@@ -186,6 +195,9 @@ def library():
         for w_name, w in [("", [])] + ([("_warm", warm)] if warm else []):
             for m_name, m in (("", []), ("_model", [DP])) + ((("_horizon", [DP, DP]),) if has_horizon else ()):
                 getattr(L, family + w_name + m_name).argtypes = head + m + w + tail
+    # the certificate: the _horizon solve's inputs, then sol, ld_sol, cert, verdict (and the stream)
+    L.mpc_certify_batch_host.argtypes = H + [DP] * 7 + [DP, I64, DP, DP]
+    L.mpc_certify_batch_device.argtypes = L.mpc_certify_batch_host.argtypes + [C.c_void_p]
     L.mpc_solve_batch_device_f32.argtypes = L.mpc_solve_batch_device.argtypes      # (the same pointers, to floats)
     L.mpc_solve_batch_host_f32.argtypes = L.mpc_solve_batch_host.argtypes
     L.mpc_wire_parse.argtypes = [C.c_char_p, C.c_int64, C.POINTER(MpcWireTelemetry)]

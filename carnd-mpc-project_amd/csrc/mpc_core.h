@@ -2909,5 +2909,182 @@ MPC_HD int solve_instance(const MpcParams &P, WS ws, const R *state6, const R *c
   return status;
 }
 
+#if MPC_S0_VARIABLE
+/* ---- the certificate of a stored point (mpc_certify_batch_*, include/mpc_amd_certify.h) ------------------------------------------
+ * certify_instance evaluates the NLP of a solve once, at the primal-dual point get(k, f) = field f (Layout<double>) of the record of
+ * stage k, and hands the MPC_NCERT measures to put(row, value); it returns the verdict.  The kernel (mpc_certify_kernel) and the
+ * test-only CPU build (tests/certify_twin) both run it through certify_batch_instance below and spell nothing of it themselves.
+ *   Set-up: Solver::setup on the instance's column with write_start = false -- the frozen weights, vref, the i = 0 terms, df, the
+ *     relaxed box, the tolerances and every refusal (state outside its bounds, unusable model column, horizon outside 3 .. N) are the
+ *     solve's own, from the one place that derives them.  The Solver object is one without a workspace (NoWorkspace): nothing of it
+ *     but what setup() fills is used, and linearise(), kkt_error(), converged_at(), acceptable_at().
+ *   Stage model: Solver::linearise, as everywhere -- the residual of every model row and sin / cos / f' / f'' of the Jacobian.  One
+ *     entry is formed here: d atan(f') / dx = f'' / (1 + f'^2) as a correctly rounded quotient of L.fpp and L.fp instead of L.g1,
+ *     whose reciprocal (frcp1: one Newton step on the device, a division on the CPU) only shapes Newton systems and differs in its
+ *     last bits between the two builds; with it the device and the CPU build agree bit for bit.
+ *   Stationarity and complementarity: a second, plain spelling of the rows of the trial sweep (Solver::costate_trial, "rows of u_k",
+ *     "rows of s_k", "terminal state rows") over the record, NOT that sweep at step length 0: the sweep reads a direction and writes
+ *     a trial iterate, so it needs a workspace of two iterate slots per stage, and the certificate has none.  The numbers agree with
+ *     the solver's to rounding.
+ * One pass over k, forwards: step k holds (s_k, lam_k, the duals of psi_k, v_k) in registers, loads record k = (s_{k+1}, u_k,
+ * lam_{k+1}, duals), evaluates transition k once, the rows of s_k, and the rows of u_{k-1}, which wait for delta_k.  The trip count is
+ * the instance's number of stages, 2 .. N - 1, which set-up has checked; no value of the record decides a branch that is not a
+ * select.  The initial state's own rows are no part of it (the record holds no multipliers for them): kkt_error() counts as with
+ * MpcParams.initial_state_rows = 0. */
+template <class R>
+struct NoWorkspace {
+  static constexpr bool kSocDefault = false;
+  mutable R sink = R(0.0);
+  MPC_HD R &it(int, int, int) const { return sink; }       /* (start_point(), which setup() names behind write_start) */
+  MPC_HD void setD(int, int, R) const {}
+};
+
+template <class Col, class Get, class Put>
+MPC_HD int certify_instance(const MpcParams &P, const Col &col, const double *st, const double *cf, double yaw_lo, double yaw_hi,
+                            const double *w, Get get, Put put) {
+  typedef double R;
+  using SV = Solver<NoWorkspace<R>, R>;
+  using IC = IpmConst<R>;
+  using F = Layout<R>;
+  static_assert((int)F::IT_SZ == MPC_WARM_REC, "the record of a warm buffer is the fp64 iterate record");
+  const R nan = (R)NAN;
+  SV S(P, NoWorkspace<R>{});
+  if (S.setup(col, st, cf, yaw_lo, yaw_hi, w, false) != MPC_STATUS_SUCCESS) {
+    MPC_UNROLL
+    for (int r = 0; r < MPC_NCERT; r++) put(r, nan);
+    return MPC_CERT_NO_PROBLEM;
+  }
+  S.s0_rows = false;
+  bool col_ok;
+  const auto &m = col.vals(P, col_ok);          /* the caller's own bounds (unpack reads them the same way) */
+  const R lo[4] = {S.yl, S.vl, S.dl, S.al}, hi[4] = {S.yu, S.vu, S.du, S.au};
+  const R clo[4] = {yaw_lo, (R)-m.max_speed, (R)-m.max_steering, (R)m.max_deceleration};
+  const R chi[4] = {yaw_hi, (R)m.max_speed, (R)m.max_steering, (R)m.max_acceleration};
+  const R df = S.df, wc = S.wc, we = S.we, wv = S.wv, wd = S.wd, wdd = S.wdd, vref = S.vref, dt = S.dt, dtLf = S.dtLf;
+  const int M = S.M;
+  typename SV::EvalR e;
+  e.theta = 0; e.cinf = 0; e.f = 0; e.L = 0; e.dinf = 0; e.cmin = IC::huge; e.cmax = 0; e.lsum = 0; e.zsum = 0; e.du0 = 0; e.ok = true;
+  bool finite = true, inside = true;
+  R bviol = R(0.0);
+  /* the five groups of the objective, beginning with their i = 0 terms */
+  const R dv0 = st[3] - S.vref0;
+  R f_cte = S.wc0 * st[4] * st[4], f_epsi = S.we0 * st[5] * st[5], f_v = wv * dv0 * dv0 + S.wneg0 * st[3] * st[3], f_del = R(0.0), f_dd = R(0.0);
+  /* carried from step k-1: s_k, lam_k, the duals of psi_k and v_k; and what the rows of u_{k-1} wait with */
+  R sk[6], lk[6] = {0, 0, 0, 0, 0, 0}, zs0 = 0, zs1 = 0, zs2 = 0, zs3 = 0;
+  R del_p = 0, ddl_p = 0, bl_p = 0, zdl_p = 0, zdu_p = 0;
+  MPC_UNROLL
+  for (int i = 0; i < 6; i++) sk[i] = st[i];
+  /* rows of u_{k-1}, once delta_k is known (ddn = delta_k - delta_{k-1}; 0 behind the last control) */
+  const auto delta_row = [&](R ddn) {
+    const R rd = df * (R(2.0) * wd * del_p + R(2.0) * wdd * ddl_p - R(2.0) * wdd * ddn) - bl_p - zdl_p + zdu_p;
+    e.dinf = mpc_max(e.dinf, mpc_abs(rd));
+  };
+  MPC_STAGE_LOOP
+  for (int k = 0; k < M; ++k) {
+    R rec[MPC_WARM_REC];
+    MPC_UNROLL
+    for (int f = 0; f < MPC_WARM_REC; f++) rec[f] = get(k, f);
+    MPC_UNROLL
+    for (int f = 0; f < MPC_WARM_REC; f++) finite = finite && mpc_abs(rec[f]) <= IC::huge;      /* (false for a NaN) */
+    const R *sn = rec + F::F_S, *ln = rec + F::F_LAM;
+    const R del = rec[F::F_U], acc = rec[F::F_U + 1];
+    /* ---- transition k, (s_k, u_k) -> s_{k+1}: the model rows of index k+1 ---- */
+    typename SV::LinR L;
+    S.linearise(sk, del, acc, sn, L);
+    MPC_UNROLL
+    for (int i = 0; i < 6; i++) e.cinf = mpc_max(e.cinf, mpc_abs(L.c[i]));
+    /* ---- the bounds of psi_{k+1}, v_{k+1}, delta_k, a_k ---- */
+    const R xb[4] = {sn[2], sn[3], del, acc};
+    MPC_UNROLL
+    for (int b = 0; b < 4; b++) {
+      const R x = xb[b], zl = rec[F::F_ZL + b], zu = rec[F::F_ZU + b];
+      inside = inside && x >= lo[b] && x <= hi[b] && zl >= R(0.0) && zu >= R(0.0);
+      bviol = mpc_max(bviol, mpc_max(clo[b] - x, x - chi[b]));
+      const R pl = (x - lo[b]) * zl, pu = (hi[b] - x) * zu;
+      e.cmin = mpc_min(e.cmin, mpc_min(pl, pu)); e.cmax = mpc_max(e.cmax, mpc_max(pl, pu));
+      e.zsum += zl + zu;
+    }
+    MPC_UNROLL
+    for (int i = 0; i < 6; i++) e.lsum += mpc_abs(ln[i]);
+    /* ---- objective terms of (s_{k+1}, u_k) ---- */
+    const R dv = sn[3] - vref, ddl = k >= 1 ? del - del_p : R(0.0);          /* delta_k - delta_{k-1} */
+    f_cte += wc * sn[4] * sn[4]; f_epsi += we * sn[5] * sn[5]; f_v += wv * dv * dv; f_del += wd * del * del; f_dd += wdd * ddl * ddl;
+    /* ---- stationarity ---- */
+    if (k >= 1) delta_row(ddl);
+    const R ra = -dt * ln[3] - rec[F::F_ZL + 3] + rec[F::F_ZU + 3];            /* row of a_k */
+    e.dinf = mpc_max(e.dinf, mpc_abs(ra));
+    const R v = sk[3], vdt = v * dt, l25 = ln[2] + ln[5];
+    if (k >= 1) {
+      /* rows of s_k with A_k of this point */
+      const R g1 = L.fpp / (R(1.0) + L.fp * L.fp), Apv = del * dtLf;
+      const R r0 = lk[0] - (ln[0] + L.fp * ln[4] - g1 * ln[5]);
+      const R r1 = lk[1] - (ln[1] - ln[4]);
+      const R r2 = lk[2] - (-vdt * L.sp * ln[0] + vdt * L.cp * ln[1] + l25) - zs0 + zs1;
+      const R r3 = df * R(2.0) * (wv * (sk[3] - vref)) + lk[3] -
+                   (dt * L.cp * ln[0] + dt * L.sp * ln[1] + Apv * l25 + ln[3] + dt * L.se * ln[4]) - zs2 + zs3;
+      const R r4 = df * R(2.0) * wc * sk[4] + lk[4];
+      const R r5 = df * R(2.0) * we * sk[5] + lk[5] - vdt * L.ce * ln[4];
+      e.dinf = mpc_max(e.dinf, mpc_max(mpc_max(mpc_abs(r0), mpc_abs(r1)), mpc_max(mpc_max(mpc_abs(r2), mpc_abs(r3)), mpc_max(mpc_abs(r4), mpc_abs(r5)))));
+    }
+    /* carry to step k+1 */
+    del_p = del; ddl_p = ddl; bl_p = (v * dtLf) * l25; zdl_p = rec[F::F_ZL + 2]; zdu_p = rec[F::F_ZU + 2];
+    MPC_UNROLL
+    for (int i = 0; i < 6; i++) { sk[i] = sn[i]; lk[i] = ln[i]; }
+    zs0 = rec[F::F_ZL + 0]; zs1 = rec[F::F_ZU + 0]; zs2 = rec[F::F_ZL + 1]; zs3 = rec[F::F_ZU + 1];
+  }
+  delta_row(R(0.0));
+  {
+    /* terminal state rows */
+    const R r2 = lk[2] - zs0 + zs1;
+    const R r3 = df * R(2.0) * wv * (sk[3] - vref) + lk[3] - zs2 + zs3;
+    const R r4 = df * R(2.0) * wc * sk[4] + lk[4];
+    const R r5 = df * R(2.0) * we * sk[5] + lk[5];
+    e.dinf = mpc_max(e.dinf, mpc_max(mpc_max(mpc_abs(lk[0]), mpc_abs(lk[1])), mpc_max(mpc_max(mpc_abs(r2), mpc_abs(r3)), mpc_max(mpc_abs(r4), mpc_abs(r5)))));
+  }
+  if (!finite || !inside) {
+    MPC_UNROLL
+    for (int r = 0; r < MPC_NCERT; r++) put(r, r == MPC_CERT_BOUND_VIOL && finite ? bviol : nan);
+    return MPC_CERT_NOT_A_POINT;
+  }
+  const R E0 = S.kkt_error(e, R(0.0));
+  put(MPC_CERT_OBJ, f_cte + f_epsi + f_v + f_del + f_dd);
+  put(MPC_CERT_CONSTR_VIOL, e.cinf);
+  put(MPC_CERT_DUAL_INF, e.dinf / df);
+  put(MPC_CERT_COMPL, e.cmax / df);
+  put(MPC_CERT_NLP_ERROR, E0);
+  put(MPC_CERT_BOUND_VIOL, bviol);
+  put(MPC_CERT_OBJ_SCALING, df);
+  put(MPC_CERT_COST_CTE, f_cte); put(MPC_CERT_COST_EPSI, f_epsi); put(MPC_CERT_COST_V, f_v);
+  put(MPC_CERT_COST_DELTA, f_del); put(MPC_CERT_COST_DDELTA, f_dd);
+  return S.converged_at(e, E0) ? MPC_CERT_CONVERGED : (S.acceptable_at(e, E0) ? MPC_CERT_ACCEPTABLE : MPC_CERT_NOT_CONVERGED);
+}
+
+/* Instance i of a certify call, end to end: the gather of every solve, the instance's column `col` (NoColumn, ModelColumn, HorizonColumn), the records
+ * of its column of sol [mpc_warm_rows(N)][ld_sol], and the rows of cert [MPC_NCERT][ld] and verdict [ld]. */
+template <class Col>
+MPC_HD void certify_batch_instance(const MpcParams &P, const Col &col, int64_t i, int64_t ld, const double *state, const double *coeffs,
+                                   const double *yaw_lo, const double *yaw_hi, const double *weights, const double *sol, int64_t ld_sol,
+                                   double *cert, int32_t *verdict) {
+  double st[6], cf[MPC_NCOEF], w[MPC_NW];
+  gather_instance(P, i, ld, state, coeffs, weights, st, cf, w);
+  const double *sc = sol + i;
+  double *cc = cert + i;
+  verdict[i] = certify_instance(P, col, st, cf, yaw_lo[i], yaw_hi[i], w,
+                                [sc, ld_sol](int k, int f) { return sc[(int64_t)(k * MPC_WARM_REC + f) * ld_sol]; },
+                                [cc, ld](int r, double v) { cc[(int64_t)r * ld] = v; });
+}
+/* ... and the column of instance i by what the call brought (KIND: 0 nothing, 1 `model`, 2 `horizon`, with `model` or without) */
+template <int KIND>
+MPC_HD void certify_batch_instance(const MpcParams &P, int64_t i, int64_t ld, const double *state, const double *coeffs, const double *yaw_lo,
+                                   const double *yaw_hi, const double *weights, const double *model, const int32_t *horizon, const double *sol,
+                                   int64_t ld_sol, double *cert, int32_t *verdict) {
+  if constexpr (KIND == 2)
+    certify_batch_instance(P, HorizonColumn{model ? model + i : nullptr, ld, horizon[i]}, i, ld, state, coeffs, yaw_lo, yaw_hi, weights, sol, ld_sol, cert, verdict);
+  else if constexpr (KIND == 1)
+    certify_batch_instance(P, ModelColumn{model + i, ld}, i, ld, state, coeffs, yaw_lo, yaw_hi, weights, sol, ld_sol, cert, verdict);
+  else certify_batch_instance(P, NoColumn{}, i, ld, state, coeffs, yaw_lo, yaw_hi, weights, sol, ld_sol, cert, verdict);
+}
+#endif
+
 }  // namespace mpc
 #endif /* MPC_CORE_H */

@@ -1019,6 +1019,24 @@ __global__ __launch_bounds__(256) void mpc_rollout_step_kernel(int64_t B, int64_
   if (iters) iters[i] = (first ? 0 : iters[i]) + it_step[i];
 }
 
+/* The certificate of a stored point (mpc_certify_batch_*), one instance per lane: mpc::certify_batch_instance of mpc_core.h.  A lane
+ * walks the stage records of its column of `sol` once -- consecutive lanes read consecutive addresses of every row, like `state` --
+ * and keeps the neighbouring state, multipliers and steering values in registers: no workspace, no LDS, no loop whose trip count the
+ * data decide.  KIND: what the call brought (0 nothing, 1 `model`, 2 `horizon`).  256 lanes per block: the body holds about 60 live
+ * doubles (one record, the carried stage, the stage model, the sums) and compiles to about 210 vector registers, no scratch. */
+constexpr int kCertBlock = 256;
+template <int KIND>
+__global__ __launch_bounds__(kCertBlock) void mpc_certify_kernel(const MpcParams P, int64_t B, int64_t ld, const double *__restrict__ state,
+                                                                 const double *__restrict__ coeffs, const double *__restrict__ yaw_lo,
+                                                                 const double *__restrict__ yaw_hi, const double *__restrict__ weights,
+                                                                 const double *__restrict__ model, const int32_t *__restrict__ horizon,
+                                                                 const double *__restrict__ sol, int64_t ld_sol, double *__restrict__ cert,
+                                                                 int32_t *__restrict__ verdict) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B) return;
+  mpc::certify_batch_instance<KIND>(P, i, ld, state, coeffs, yaw_lo, yaw_hi, weights, model, horizon, sol, ld_sol, cert, verdict);
+}
+
 /* Statistics of a batch, accumulated into handle-owned memory right behind the solve (mpc_get_stats never touches
  * the caller's arrays again): acc[0..4] = instances per status code 0..3 and "any other", acc[5] = sum of iterations,
  * acc[6] = max, acc[7] = pending, acc[8] = MPC_STATUS_ACCEPTABLE. */
@@ -2893,6 +2911,86 @@ extern "C" int mpc_solve_batch_host_f32(MpcHandle *h, int64_t B, int64_t ld, con
                                         const float *weights, float *out, float *traj, int32_t *status,
                                         int32_t *iters) {
   return solve_host<float>(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters, call_extras(h));
+}
+
+/* ---- the certificate of a stored point (include/mpc_amd_certify.h) ---- */
+/* What both forms check before they touch anything: the handle and the model rule (call_extras), the precision -- also of a call
+ * without model and horizon -- and the batch (check_batch).  *empty: B == 0, nothing to do (the arrays may be NULL). */
+static int certify_args(const MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs, const double *yaw_lo,
+                        const double *yaw_hi, const double *model, const double *sol, int64_t ld_sol, const double *cert,
+                        const int32_t *verdict, bool *empty) {
+  MPC_TRY(call_extras(h, model).refused);
+  if (h->params.precision != MPC_PRECISION_F64) {
+    g_last_error = "certificate: fp64 handles only (this one was created with MPC_PRECISION_F32)";
+    return MPC_ERR_INVALID;
+  }
+  MPC_TRY(check_batch(h, B, ld));
+  if (ld_sol < B) { g_last_error = "ld_sol < B"; return MPC_ERR_INVALID; }
+  *empty = B == 0;
+  if (B > 0 && (!state || !coeffs || !yaw_lo || !yaw_hi || !sol || !cert || !verdict)) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
+  return MPC_OK;
+}
+
+/* the one launch, on device arrays */
+static int certify_launch(const MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs, const double *yaw_lo,
+                          const double *yaw_hi, const double *weights, const double *model, const int32_t *horizon, const double *sol,
+                          int64_t ld_sol, double *cert, int32_t *verdict, hipStream_t s) {
+  const dim3 grid((unsigned)((B + kCertBlock - 1) / kCertBlock)), block(kCertBlock);
+  const auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, h->params, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, model, horizon, sol, ld_sol, cert, verdict);
+  };
+  if (horizon) launch(mpc_certify_kernel<2>);
+  else if (model) launch(mpc_certify_kernel<1>);
+  else launch(mpc_certify_kernel<0>);
+  MPC_HIP_CHECK(hipGetLastError());
+  return MPC_OK;
+}
+
+extern "C" int mpc_certify_batch_device(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
+                                        const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
+                                        const int32_t *horizon, const double *sol, int64_t ld_sol, double *cert, int32_t *verdict,
+                                        void *stream_) {
+  bool empty = false;
+  MPC_TRY(certify_args(h, B, ld, state, coeffs, yaw_lo, yaw_hi, model, sol, ld_sol, cert, verdict, &empty));
+  if (empty) return MPC_OK;
+  MPC_ON_DEVICE(h);
+  return certify_launch(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, model, horizon, sol, ld_sol, cert, verdict, (hipStream_t)stream_);
+}
+
+/* Host arrays: one copy in, the launch, one copy out on the handle's own device and stream; synchronises.  The staging block is the
+ * one the run() and telemetry host forms keep on the handle (grown on demand), rows of leading dimension L:
+ * state 6 | coeffs 5 | yaw_lo | yaw_hi | weights 12 | model 6 | sol | cert 12 | horizon and verdict (int32 each, one row). */
+extern "C" int mpc_certify_batch_host(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
+                                      const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
+                                      const int32_t *horizon, const double *sol, int64_t ld_sol, double *cert, int32_t *verdict) {
+  bool empty = false;
+  MPC_TRY(certify_args(h, B, ld, state, coeffs, yaw_lo, yaw_hi, model, sol, ld_sol, cert, verdict, &empty));
+  if (empty) return MPC_OK;
+  MPC_ON_DEVICE(h);
+  const int64_t L = (B + 7) / 8 * 8, sol_rows = mpc_warm_rows(h->params.N);
+  const int64_t in_rows = 6 + MPC_NCOEF + 2 + MPC_NW + MPC_NMODEL;
+  MPC_TRY(grow_dev(&h->d_tel, &h->tel_bytes, sizeof(double) * (size_t)((in_rows + sol_rows + MPC_NCERT + 1) * L)));
+  double *d_st = h->d_tel, *d_cf = d_st + 6 * L, *d_yl = d_cf + MPC_NCOEF * L, *d_yh = d_yl + L, *d_w = d_yh + L, *d_model = d_w + MPC_NW * L;
+  double *d_sol = d_model + MPC_NMODEL * L, *d_cert = d_sol + sol_rows * L;
+  int32_t *d_hz = (int32_t *)(d_cert + MPC_NCERT * L), *d_verdict = d_hz + L;
+  hipStream_t s = h->stream;
+  const auto rows_in = [&](double *dst, const double *src, int64_t src_ld, int64_t rows) {
+    return hipMemcpy2DAsync(dst, sizeof(double) * L, src, sizeof(double) * src_ld, sizeof(double) * B, (size_t)rows, hipMemcpyHostToDevice, s);
+  };
+  MPC_HIP_CHECK(rows_in(d_st, state, ld, 6));
+  MPC_HIP_CHECK(rows_in(d_cf, coeffs, ld, MPC_NCOEF));
+  MPC_HIP_CHECK(rows_in(d_yl, yaw_lo, ld, 1));
+  MPC_HIP_CHECK(rows_in(d_yh, yaw_hi, ld, 1));
+  if (weights) MPC_HIP_CHECK(rows_in(d_w, weights, ld, MPC_NW));
+  if (model) MPC_HIP_CHECK(rows_in(d_model, model, ld, MPC_NMODEL));
+  MPC_HIP_CHECK(rows_in(d_sol, sol, ld_sol, sol_rows));
+  if (horizon) MPC_HIP_CHECK(hipMemcpyAsync(d_hz, horizon, sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
+  MPC_TRY(certify_launch(h, B, L, d_st, d_cf, d_yl, d_yh, weights ? d_w : nullptr, model ? d_model : nullptr, horizon ? d_hz : nullptr, d_sol, L,
+                         d_cert, d_verdict, s));
+  MPC_HIP_CHECK(hipMemcpy2DAsync(cert, sizeof(double) * ld, d_cert, sizeof(double) * L, sizeof(double) * B, MPC_NCERT, hipMemcpyDeviceToHost, s));
+  MPC_HIP_CHECK(hipMemcpyAsync(verdict, d_verdict, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
+  MPC_HIP_CHECK(hipStreamSynchronize(s));
+  return MPC_OK;
 }
 
 extern "C" int mpc_get_stats(MpcHandle *h, MpcBatchStats *st) {

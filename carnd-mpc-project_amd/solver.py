@@ -386,6 +386,47 @@ class BatchedMPC:
                    p(model), (p(warm), p(warm_status), p(wout), B, C.byref(warm_opts) if warm_opts is not None else None), horizon=p(horizon))
         return {"out": out, "status": status, "iters": iters, "traj": traj, "warm": wout}
 
+    # -- the certificate of a stored point (include/mpc_amd_certify.h) ----------
+    def certify_torch(self, state, coeffs, yaw_lo, yaw_hi, sol, weights=None, model=None, horizon=None, stream=None):
+        """IPOPT's final error summary for stored primal-dual points (mpc_certify_batch_device; fp64 handles): ``sol``
+        [warm_rows(), B] float64 is the "warm" tensor of any warm-capable call (a cold one with want_warm=True gives the solution
+        of a solve), read as it is; the other arguments are those of the solve that wrote it.  One launch on ``stream``, nothing is
+        solved.  Returns {"cert": [NCERT, B] float64 (rows _abi.CERT_*), "verdict": [B] int32 (_abi.CERT_VERDICT_NAMES)}."""
+        import torch
+        B = state.shape[1]
+        for name, t, shape in (("state", state, (6, B)), ("coeffs", coeffs, (5, B)), ("yaw_lo", yaw_lo, (B,)), ("yaw_hi", yaw_hi, (B,)),
+                               ("sol", sol, (self.warm_rows(), B)), ("weights", weights, (_abi.NW, B))):
+            if t is not None and (t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape):
+                raise ValueError("%s must be a contiguous float64 CUDA tensor of shape %s" % (name, shape))
+        if model is not None:
+            self._check_model(model, B)
+        if horizon is not None:
+            self._check_horizon(horizon, B)
+        s = stream if stream is not None else torch.cuda.current_stream(state.device)
+        res = {"cert": torch.empty((_abi.NCERT, B), dtype=torch.float64, device=state.device),
+               "verdict": torch.empty((B,), dtype=torch.int32, device=state.device)}
+        p = lambda t: t.data_ptr() if t is not None else None
+        check(library().mpc_certify_batch_device(self._h, B, B, p(state), p(coeffs), p(yaw_lo), p(yaw_hi), p(weights), p(model), p(horizon),
+                                                 p(sol), B, p(res["cert"]), p(res["verdict"]), C.c_void_p(s.cuda_stream)),
+              "mpc_certify_batch_device")
+        return res
+
+    def certify_numpy(self, state, coeffs, yaw_lo, yaw_hi, sol, weights=None, model=None, horizon=None):
+        """certify_torch for host arrays (mpc_certify_batch_host): one copy in, the launch, one copy out; synchronises."""
+        f = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64)) if a is not None else None
+        state, coeffs, yaw_lo, yaw_hi, sol, weights, model = f(state), f(coeffs), f(yaw_lo), f(yaw_hi), f(sol), f(weights), f(model)
+        B = state.shape[1]
+        assert state.shape == (6, B) and coeffs.shape == (5, B) and yaw_lo.shape == (B,) and yaw_hi.shape == (B,)
+        assert sol.shape == (self.warm_rows(), B) and (weights is None or weights.shape == (_abi.NW, B))
+        assert model is None or model.shape == (_abi.NMODEL, B)
+        if horizon is not None:
+            horizon = self._host_horizon(horizon, B)
+        cert = np.empty((_abi.NCERT, B)); verdict = np.empty(B, dtype=np.int32)
+        p = lambda a: a.ctypes.data if a is not None else None
+        check(library().mpc_certify_batch_host(self._h, B, B, p(state), p(coeffs), p(yaw_lo), p(yaw_hi), p(weights), p(model), p(horizon),
+                                               p(sol), B, p(cert), p(verdict)), "mpc_certify_batch_host")
+        return {"cert": cert, "verdict": verdict}
+
     # -- deferred tails (MpcParams.tail_cut > 0, include/mpc_amd.h) -------------
     def last_batch_id(self):
         return int(library().mpc_last_batch_id(self._h))

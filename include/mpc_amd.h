@@ -534,6 +534,13 @@ int mpc_rollout_batch_device_fused_model(MpcHandle *h, int64_t B, int64_t ld, in
  * the telemetry handler, the wire forms and the C++ drop-in have none, deliberately.  The section and its seven declarations live in
  * a header of their own, which this one includes: */
 #include "mpc_amd_horizon.h"
+/* ---- certify a stored solution: IPOPT's final error summary for a point the caller names ---------------------------------------
+ * Two entry points evaluate the NLP of the solve once, at a stored primal-dual point (a warm buffer: warm_out of any _warm entry
+ * point), and write twelve measures per instance -- objective, constraint violation, dual infeasibility, complementarity, overall
+ * NLP error, bound violation, objective scaling, the five cost groups -- and a verdict by the handle's tolerances.  One launch, a
+ * lane per instance; nothing is solved and nothing else changes.  The section and its declarations live in a header of their own,
+ * which this one includes: */
+#include "mpc_amd_certify.h"
 /* ---- per-instance model values on the run() path: a fleet of different vehicles behind one handler ----------------------------
  * Each entry point is the one of the same name without `_model` plus `model`, [MPC_NMODEL][ld] doubles addressed with the call's
  * ld (rows MPC_MODEL_*), directly behind `ptsy`; the wire forms further down take it as [MPC_NMODEL][B] directly behind
