@@ -804,12 +804,7 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
    * initial-state variables count in the dual infeasibility (after a step the fraction-to-the-boundary rule has cut they hold
    * (1 - alpha) of their old residual plus the curvature of stage 0 along the step), lam0 counts in its scaling, z0 in the
    * complementarity and in the dual step length.  They are carried for that: costate_trial() treats them as the record of a
-   * stage "-1".  -DMPC_S0_VARIABLE=0 builds the solver with the initial state as plain data (A/B
-   * measurements only). */
-#ifndef MPC_S0_VARIABLE
-#define MPC_S0_VARIABLE 1
-#endif
-#if MPC_S0_VARIABLE
+   * stage "-1". */
   R p0, v0k;
   R wc0, we0, vref0, wneg0;   /* the i = 0 terms of the objective (MPC.cpp:71-92), whose variables are the initial state's */
   bool s0_rows = false;       /* MpcParams.initial_state_rows: lam0 / z0 carried and counted in the error measure */
@@ -824,7 +819,6 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
     MPC_UNROLL
     for (int b = 0; b < 2; b++) { ws.it(M, I, F_ZL + b) = R(1.0); ws.it(M, I, F_ZU + b) = R(1.0); }      /* bound_mult_init_val */
   }
-#endif
   /* interior-point state */
   int cur;     /* slot of the current iterate */
   R mu, tau, df;
@@ -903,9 +897,7 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
     if (k == 0) {
       MPC_UNROLL
       for (int i = 0; i < 6; i++) s[i] = st[i];
-#if MPC_S0_VARIABLE
       s[2] = p0; s[3] = v0k;
-#endif
     } else {
       MPC_UNROLL
       for (int i = 0; i < 6; i++) s[i] = ws.it(k - 1, I, F_S + i);
@@ -923,16 +915,31 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
   /* Returns false when some R~_k is not positive definite (wrong        */
   /* inertia): the caller raises the regularisation dw and repeats.      */
   /* ------------------------------------------------------------------ */
+  /* Both forms of the sweep (backward_wave: one instance per wavefront; backward: one per lane) pick the lower triangle of the
+   * symmetric value function with PM and apply G^T with MPC_GT, on their own locals Pm, Aex .. Bp.  Macros, not functions: a product
+   * handed to MPC_GT (Pcc * Acx) lands textually inside the expressions that use it, where -ffp-contract=on fuses it into the add or
+   * subtract next to it; a function argument would be rounded first, and other bits come out (profiles/sweeps_once_ab.md). */
+#define PM(i, j) Pm[(i) >= (j) ? (i) : (j)][(i) >= (j) ? (j) : (i)]
+  /* G^T applied to a (6-vector, c-scalar): outputs for inputs x,y,psi,v,e,delta,a */
+#define MPC_GT(w, wcs, o)                                                         \
+  do {                                                                            \
+    const R w24_ = (w)[2] + (w)[4];                                          \
+    (o)[0] = (w)[0] + Aex * (w)[4] + Acx * (wcs);                                 \
+    (o)[1] = (w)[1] - (wcs);                                                      \
+    (o)[2] = Axp * (w)[0] + Ayp * (w)[1] + w24_;                                  \
+    (o)[3] = Axv * (w)[0] + Ayv * (w)[1] + Apv * w24_ + (w)[3] + Acv * (wcs);     \
+    (o)[4] = Ace * (wcs);                                                         \
+    (o)[5] = Bp * w24_ + (w)[5];                                                  \
+    (o)[6] = dt * (w)[3];                                                         \
+  } while (0)
   /* The Riccati sweep with one instance per wavefront: lane k prepares stage k (inputs, model, reciprocal slacks, control and state
    * terms); the value-function recursion runs through the lanes in descending order -- the stage algebra of backward(), statement
    * for statement, on the value function the lane before broadcast (29 numbers) -- and lane k stores stage k's gains. */
   MPC_HD bool backward_wave(R dw, bool soc) {
     const int I = it(cur), J = it(1 - cur);         /* J: where the gains go */
     /* value function of (x,y,psi,v,e,d) [+ c] at stage k+1; only the lower triangle of the symmetric
-     * matrices is ever written or read (PM/MX pick it), so the other half never occupies registers */
+     * matrices is ever written or read (PM picks it), so the other half never occupies registers */
     R Pm[6][6], p[6], Pcc, pc;
-#define PM(i, j) Pm[(i) >= (j) ? (i) : (j)][(i) >= (j) ? (j) : (i)]
-#define MX(i, j) Mx[(i) >= (j) ? (i) : (j)][(i) >= (j) ? (j) : (i)]
     MPC_UNROLL
     for (int i = 0; i < 6; i++) {
       p[i] = 0;
@@ -971,9 +978,7 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
     } else {
       MPC_UNROLL
       for (int i = 0; i < 6; i++) sk[i] = st[i];
-#if MPC_S0_VARIABLE
       sk[2] = p0; sk[3] = v0k;
-#endif
     }
     const R v = sk[3];
     LinR L;
@@ -1006,18 +1011,6 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
       for (int i = 0; i < 6; i++)
         t[i] = p[i] + PM(i, 0) * r0 + PM(i, 1) * r1 + PM(i, 2) * r2 + PM(i, 3) * r3 + PM(i, 4) * r4;
       const R tc = pc + Pcc * rc;
-      /* G^T applied to a (6-vector, c-scalar): outputs for inputs x,y,psi,v,e,delta,a */
-#define MPC_GT(w, wcs, o)                                                         \
-  do {                                                                            \
-    const R w24_ = (w)[2] + (w)[4];                                          \
-    (o)[0] = (w)[0] + Aex * (w)[4] + Acx * (wcs);                                 \
-    (o)[1] = (w)[1] - (wcs);                                                      \
-    (o)[2] = Axp * (w)[0] + Ayp * (w)[1] + w24_;                                  \
-    (o)[3] = Axv * (w)[0] + Ayv * (w)[1] + Apv * w24_ + (w)[3] + Acv * (wcs);     \
-    (o)[4] = Ace * (wcs);                                                         \
-    (o)[5] = Bp * w24_ + (w)[5];                                                  \
-    (o)[6] = dt * (w)[3];                                                         \
-  } while (0)
       R qt[7];
       MPC_GT(t, tc, qt);
       const R rt_d = qt[5] + gdel, rt_a = qt[6] + gacc;
@@ -1136,9 +1129,6 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
       }
       Pcc = wave_bcast<WAVE>(Pcc, tk, wbase); pc = wave_bcast<WAVE>(pc, tk, wbase);
     }
-#undef MPC_GT
-#undef PM
-#undef MX
     return ok_all;
   }
 
@@ -1146,10 +1136,8 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
     if constexpr (WAVE) return backward_wave(dw, soc);
     const int I = it(cur), J = it(1 - cur);         /* J: where the gains go */
     /* value function of (x,y,psi,v,e,d) [+ c] at stage k+1; only the lower triangle of the symmetric
-     * matrices is ever written or read (PM/MX pick it), so the other half never occupies registers */
+     * matrices is ever written or read (PM picks it), so the other half never occupies registers */
     R Pm[6][6], p[6], Pcc, pc;
-#define PM(i, j) Pm[(i) >= (j) ? (i) : (j)][(i) >= (j) ? (j) : (i)]
-#define MX(i, j) Mx[(i) >= (j) ? (i) : (j)][(i) >= (j) ? (j) : (i)]
     MPC_UNROLL
     for (int i = 0; i < 6; i++) {
       p[i] = 0;
@@ -1202,9 +1190,7 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
       } else {
         MPC_UNROLL
         for (int i = 0; i < 6; i++) sk[i] = st[i];
-#if MPC_S0_VARIABLE
         sk[2] = p0; sk[3] = v0k;
-#endif
       }
       const R v = sk[3];
       LinR L;
@@ -1221,18 +1207,6 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
       for (int i = 0; i < 6; i++)
         t[i] = p[i] + PM(i, 0) * r0 + PM(i, 1) * r1 + PM(i, 2) * r2 + PM(i, 3) * r3 + PM(i, 4) * r4;
       const R tc = pc + Pcc * rc;
-      /* G^T applied to a (6-vector, c-scalar): outputs for inputs x,y,psi,v,e,delta,a */
-#define MPC_GT(w, wcs, o)                                                         \
-  do {                                                                            \
-    const R w24_ = (w)[2] + (w)[4];                                          \
-    (o)[0] = (w)[0] + Aex * (w)[4] + Acx * (wcs);                                 \
-    (o)[1] = (w)[1] - (wcs);                                                      \
-    (o)[2] = Axp * (w)[0] + Ayp * (w)[1] + w24_;                                  \
-    (o)[3] = Axv * (w)[0] + Ayv * (w)[1] + Apv * w24_ + (w)[3] + Acv * (wcs);     \
-    (o)[4] = Ace * (wcs);                                                         \
-    (o)[5] = Bp * w24_ + (w)[5];                                                  \
-    (o)[6] = dt * (w)[3];                                                         \
-  } while (0)
       R qt[7];
       MPC_GT(t, tc, qt);
       /* the stage's own control terms */
@@ -1363,11 +1337,10 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
       zld = ws.sit(bk, k - 1, I, F_ZL + 2); zud = ws.sit(bk, k - 1, I, F_ZU + 2);
       zla = ws.sit(bk, k - 1, I, F_ZL + 3); zua = ws.sit(bk, k - 1, I, F_ZU + 3);
     }
-#undef MPC_GT
-#undef PM
-#undef MX
     return true;
   }
+#undef MPC_GT
+#undef PM
 
   /* ------------------------------------------------------------------ */
   /* forward sweep: Newton direction ds, du; step limits; dphi           */
@@ -1409,7 +1382,6 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
     R d0 = 0, d1 = 0, d2 = 0, d3 = 0, d5 = 0, ddprev = 0;
     R rmax = R(0.0), rzmax = R(0.0);
     dphi = R(0.0); dxinf = R(0.0); xinf = R(0.0);
-#if MPC_S0_VARIABLE
     d2 = rsc * (st[2] - p0); d3 = rsc * (st[3] - v0k);
     if (d2 != R(0.0) || d3 != R(0.0)) {
       const R islp = frcp1(p0 - yl), isup = frcp1(yu - p0), islv = frcp1(v0k - vl), isuv = frcp1(vu - v0k);
@@ -1418,7 +1390,6 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
       dxinf = mpc_max(mpc_abs(d2), mpc_abs(d3));
     }
     const R s0d2 = d2, s0d3 = d3;
-#endif
     R dn[D_N] = {0, 0, 0, 0, 0, 0, 0, 0};
     /* ---- the recursion: stage t is lane t's turn ---- */
     for (int t = 0; t < M; ++t) {
@@ -1454,7 +1425,6 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
       rmax = wave_bcast<WAVE>(rm, t, wbase); rzmax = wave_bcast<WAVE>(rz, t, wbase); dphi = wave_bcast<WAVE>(dp, t, wbase); dxinf = wave_bcast<WAVE>(dxs, t, wbase); xinf = wave_bcast<WAVE>(xis, t, wbase);
     }
     if (mine) ws.template store_run<F_D, D_N>(k, 0, dn);
-#if MPC_S0_VARIABLE
     if (s0_rows && !lsm) {
       const R xs0[2] = {p0, v0k}, lo0[2] = {yl, vl}, hi0[2] = {yu, vu}, dx0[2] = {s0d2, s0d3};
       MPC_UNROLL
@@ -1466,7 +1436,6 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
         rzmax = mpc_max(rzmax, mpc_max(-dzl * frcp1(zl0), -dzu * frcp1(zu0)));
       }
     }
-#endif
     amax = (rmax > tau) ? tau / rmax : R(1.0);
     az = (rzmax > tau) ? tau / rzmax : R(1.0);
   }
@@ -1481,7 +1450,6 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
     dphi = R(0.0); dxinf = R(0.0); xinf = R(0.0);
     R sk[6];
     load_state(0, I, sk);
-#if MPC_S0_VARIABLE
     /* ds_0: the pinning rows are linear, the full step restores them (zero for an instance whose start was not pushed) */
     d2 = rsc * (st[2] - p0); d3 = rsc * (st[3] - v0k);
     if (d2 != R(0.0) || d3 != R(0.0)) {
@@ -1493,16 +1461,13 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
       dxinf = mpc_max(mpc_abs(d2), mpc_abs(d3));
     }
     const R s0d2 = d2, s0d3 = d3;
-#endif
     /* staging: stage k's iterate record and gains in buffer k&1, stage k+1 requested meanwhile */
     ws.stage_drain();
     ws.stage_fetch_itf(0, 0, I);
     ws.stage_fetch_g(0, 0, J);
-#if MPC_S0_VARIABLE
     /* (asked for here, used behind the loop: the loads travel with the first record's) */
     R z0lp = R(1.0), z0up = R(1.0), z0lv = R(1.0), z0uv = R(1.0);
     if (s0_rows) { z0lp = s0_z(I, 0, 0); z0up = s0_z(I, 0, 1); z0lv = s0_z(I, 1, 0); z0uv = s0_z(I, 1, 1); }
-#endif
     MPC_STAGE_LOOP
     for (int k = 0; k < M; ++k) {
       const int bf = k & 1;
@@ -1563,22 +1528,20 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
       MPC_UNROLL
       for (int i = 0; i < 6; i++) sk[i] = sn[i];
     }
-    #if MPC_S0_VARIABLE
-        if (s0_rows && !lsm) {
-          /* the bound duals of psi_0, v_0 take part in the fraction-to-the-boundary rule of the duals */
-          const R xs0[2] = {p0, v0k}, lo0[2] = {yl, vl}, hi0[2] = {yu, vu}, dx0[2] = {s0d2, s0d3};
-          const R zl0[2] = {z0lp, z0lv}, zu0[2] = {z0up, z0uv};
-          MPC_UNROLL
-          for (int b = 0; b < 2; b++) {
-            const R isl = frcp1(xs0[b] - lo0[b]), isu = frcp1(hi0[b] - xs0[b]);
-            const R dzl = mu * isl - zl0[b] - zl0[b] * isl * dx0[b];
-            const R dzu = mu * isu - zu0[b] + zu0[b] * isu * dx0[b];
-            rzmax = mpc_max(rzmax, mpc_max(-dzl * frcp1(zl0[b]), -dzu * frcp1(zu0[b])));
-          }
-        }
-    #endif
-        /* fraction to the boundary, W&B eq. (15): alpha = min(1, tau / max ratio) */
-        amax = (rmax > tau) ? tau / rmax : R(1.0);
+    if (s0_rows && !lsm) {
+      /* the bound duals of psi_0, v_0 take part in the fraction-to-the-boundary rule of the duals */
+      const R xs0[2] = {p0, v0k}, lo0[2] = {yl, vl}, hi0[2] = {yu, vu}, dx0[2] = {s0d2, s0d3};
+      const R zl0[2] = {z0lp, z0lv}, zu0[2] = {z0up, z0uv};
+      MPC_UNROLL
+      for (int b = 0; b < 2; b++) {
+        const R isl = frcp1(xs0[b] - lo0[b]), isu = frcp1(hi0[b] - xs0[b]);
+        const R dzl = mu * isl - zl0[b] - zl0[b] * isl * dx0[b];
+        const R dzu = mu * isu - zu0[b] + zu0[b] * isu * dx0[b];
+        rzmax = mpc_max(rzmax, mpc_max(-dzl * frcp1(zl0[b]), -dzu * frcp1(zu0[b])));
+      }
+    }
+    /* fraction to the boundary, W&B eq. (15): alpha = min(1, tau / max ratio) */
+    amax = (rmax > tau) ? tau / rmax : R(1.0);
     az = (rzmax > tau) ? tau / rzmax : R(1.0);
   }
 
@@ -1615,14 +1578,12 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
     ws.stage_drain();
     ws.stage_fetch_it(0, M - 1, I);
     ws.stage_fetch_d(0, M - 1);
-#if MPC_S0_VARIABLE
     /* the record of the initial state's own rows (used by the last step): asked for here, so that it travels with the first stage record */
     R c_l0 = 0, c_l1 = 0, c_l2 = 0, c_l3 = 0, c_l4 = 0, c_l5 = 0, c_zlp = 0, c_zup = 0, c_zlv = 0, c_zuv = 0;
     if (s0_rows) {
       c_l0 = s0_lam(I, 0); c_l1 = s0_lam(I, 1); c_l2 = s0_lam(I, 2); c_l3 = s0_lam(I, 3); c_l4 = s0_lam(I, 4); c_l5 = s0_lam(I, 5);
       c_zlp = s0_z(I, 0, 0); c_zup = s0_z(I, 0, 1); c_zlv = s0_z(I, 1, 0); c_zuv = s0_z(I, 1, 1);
     }
-#endif
     /* the step of a stage as a function of whether it is the last one (k = 0: the initial state's own rows, no record to
      * fetch): the loop runs the general form, the epilogue the other, and neither carries the other's registers */
     auto step_k = [&](auto kz_, const int k) {
@@ -1739,7 +1700,6 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
         } else {
           MPC_UNROLL
           for (int i = 0; i < 6; i++) { s_o[i] = st[i]; s_t[i] = st[i]; }
-#if MPC_S0_VARIABLE
           s_o[2] = p0; s_o[3] = v0k;
           s_t[2] = trial_x0(p0, st[2], alpha); s_t[3] = trial_x0(v0k, st[3], alpha);
           const R c2 = s_t[2] - st[2], c3 = s_t[3] - st[3];    /* residuals of the pinning rows of psi_0, v_0 */
@@ -1763,7 +1723,7 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
               const R mub = lsm ? R(0.0) : mu;
               const R Hpp = lsm ? R(1.0) : c_zlp * islp + c_zup * isup;
               const R Hvv = lsm ? R(1.0) : df * R(2.0) * (wv + wneg0) + c_zlv * islv + c_zuv * isuv;
-                const R gp = mub * (isup - islp);
+              const R gp = mub * (isup - islp);
               const R gv = df * R(2.0) * (wv * (v0k - vref0) + wneg0 * v0k) + mub * (isuv - islv);
               const R ge = df * R(2.0) * we0 * s_o[5], gc = df * R(2.0) * wc0 * s_o[4];
               const R v = s_o[3];
@@ -1781,7 +1741,7 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
                            (Hvv + dw) * ds3 - Hvd * ddk;
               const R n4 = -gc;
               const R n5 = vdt * ce * L4 - ge - Hev * ds3;
-                dl0 = n0 - c_l0; dl1 = n1 - c_l1; dl2 = n2 - c_l2; dl3 = n3 - c_l3; dl4 = n4 - c_l4; dl5 = n5 - c_l5;
+              dl0 = n0 - c_l0; dl1 = n1 - c_l1; dl2 = n2 - c_l2; dl3 = n3 - c_l3; dl4 = n4 - c_l4; dl5 = n5 - c_l5;
               lmax = mpc_max(lmax, mpc_max(mpc_max(mpc_max(mpc_abs(dl0), mpc_abs(dl1)), mpc_max(mpc_abs(dl2), mpc_abs(dl3))), mpc_max(mpc_abs(dl4), mpc_abs(dl5))));
             }
             lam_t[0] = c_l0 + alpha_l * dl0; lam_t[1] = c_l1 + alpha_l * dl1; lam_t[2] = c_l2 + alpha_l * dl2;
@@ -1809,7 +1769,6 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
             }
             zs0 = z0_t[0]; zs1 = z0_t[1]; zs2 = z0_t[2]; zs3 = z0_t[3];
           }
-#endif
         }
         if (KZ || k < M) {
           /* ---- trial: transition k, (s_k, u_k) -> s_{k+1} ---- */
@@ -1827,15 +1786,10 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
           const R ra = -dt * ln_t[3] - zal_t + zau_t;
           Ev.dinf = mpc_max(Ev.dinf, mpc_max(mpc_abs(rd), mpc_abs(ra)));
           /* rows of s_k (k>=1) with A_k of the trial point */
-#if MPC_S0_VARIABLE
           if (!KZ || s0_rows) {
             /* (k = 0: the rows of the initial state's own variables, with the i = 0 terms of the objective) */
             const R gvk = !KZ ? wv * (s_t[3] - vref) : wv * (s_t[3] - vref0) + wneg0 * s_t[3];
             const R wck = !KZ ? wc : wc0, wek = !KZ ? we : we0;
-#else
-          if (!KZ) {
-            const R gvk = wv * (s_t[3] - vref), wck = wc, wek = we;
-#endif
             const R r0 = lam_t[0] - (ln_t[0] + L.fp * ln_t[4] - L.g1 * ln_t[5]);
             const R r1 = lam_t[1] - (ln_t[1] - ln_t[4]);
             const R r2 = lam_t[2] - (-vdt * L.sp * ln_t[0] + vdt * L.cp * ln_t[1] + l25) - zs0 + zs1;
@@ -2066,9 +2020,7 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
         if (k == 0) {
           MPC_UNROLL
           for (int i = 0; i < 6; i++) sk[i] = st[i];
-#if MPC_S0_VARIABLE
           sk[2] = trial_x0(p0, st[2], at); sk[3] = trial_x0(v0k, st[3], at);
-#endif
         } else {
           MPC_UNROLL
           for (int i = 0; i < 6; i++) sk[i] = ws.it(k - 1, J, F_S + i);
@@ -2113,12 +2065,8 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
   /* a pinned start value after a step of length alpha; exactly the pinned value once it has arrived */
   MPC_HD R trial_x0(R x0, R pinned, R alpha_) const { return x0 == pinned ? pinned : x0 + alpha_ * (pinned - x0); }
   MPC_HD R kkt_error(const EvalR &e, R mu_) const {
-#if MPC_S0_VARIABLE
     /* (with the initial state's own rows: the reference's 6N rows; bounds of psi_i, v_i (i = 0..N-1), delta_i, a_i) */
     const R m = s0_rows ? R(6.0) * (M + 1) : R(6.0) * M, nb = s0_rows ? R(8.0) * M + R(4.0) : R(8.0) * M;
-#else
-    const R m = R(6.0) * M, nb = R(8.0) * M;
-#endif
     const R sd = mpc_max(IC::s_max, (e.lsum + e.zsum) / (m + nb)) / IC::s_max;
     const R sc = mpc_max(IC::s_max, e.zsum / nb) / IC::s_max;
     const R compl_ = mpc_max(mpc_abs(e.cmax - mu_), mpc_abs(e.cmin - mu_));
@@ -2234,16 +2182,11 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
     wv = w12[2]; wd = w12[3]; wdd = w12[4];
     vref = (R)speed_target(P, 0.0, m.max_speed);
     /* i = 0 terms: constants of the objective (their variables are fixed), MPC.cpp:71-92 */
-#if !MPC_S0_VARIABLE
-    R wc0, we0, vref0;
-#endif
     wc0 = ((double)mpc_abs(st[4]) < P.cte_panic) ? w12[0] : w12[11];
     we0 = ((double)mpc_abs(st[5]) > P.epsi_panic) ? w12[10] : w12[1];
     vref0 = (R)speed_target(P, (double)st[2], m.max_speed);
-#if MPC_S0_VARIABLE
     wneg0 = (st[3] < R(0.0)) ? w12[9] : R(0.0);
     s0_rows = P.initial_state_rows != 0;
-#endif
     cost0 = wc0 * st[4] * st[4] + we0 * st[5] * st[5] + wv * (st[3] - vref0) * (st[3] - vref0);
     R g0 = mpc_max(mpc_abs(R(2.0) * wc0 * st[4]), mpc_abs(R(2.0) * we0 * st[5]));
     R gv0 = R(2.0) * wv * (st[3] - vref0);
@@ -2447,7 +2390,6 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
     a(22) = (R)nf; a(23) = (R)iter; a(24) = (R)n_reg; a(25) = (R)cur; a(26) = E.ok ? R(1.0) : R(0.0);
     a(27) = ls_start ? R(1.0) : R(0.0); a(28) = (R)attempt; a(29) = (R)it_total;
     a(30) = out_step; a(31) = (R)n_polish; a(32) = out_prev; a(35) = R(0.0); a(36) = (R)acc_count;
-#if MPC_S0_VARIABLE
     a(33) = p0; a(34) = v0k;
     if (s0_rows) {
       const int Ic = it(cur);
@@ -2457,10 +2399,6 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
     } else {
       for (int q = 37; q < 47; q++) a(q) = R(0.0);
     }
-#else
-    a(33) = R(0.0); a(34) = R(0.0);
-    for (int q = 37; q < 47; q++) a(q) = R(0.0);
-#endif
   }
   template <class A> MPC_HD void unpark(A a, int &attempt, int &it_total) {
     begin(a(27) != R(0.0));
@@ -2469,7 +2407,6 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
     fph2 = a(17); fph3 = a(18); theta_max = a(19); theta_min = a(20); dw_last = a(21);
     nf = (int)a(22); iter = (int)a(23); n_reg = (int)a(24); cur = (int)a(25); E.ok = a(26) != R(0.0);
     attempt = (int)a(28); it_total = (int)a(29); out_step = a(30); n_polish = (int)a(31); out_prev = a(32); acc_count = (int)a(36);
-#if MPC_S0_VARIABLE
     p0 = a(33); v0k = a(34);
     if (s0_rows) {
       const int Ic = it(cur);
@@ -2477,7 +2414,6 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
       for (int i = 0; i < 6; i++) ws.it(M, Ic, F_LAM + i) = a(37 + i);
       ws.it(M, Ic, F_ZL + 0) = a(43); ws.it(M, Ic, F_ZU + 0) = a(44); ws.it(M, Ic, F_ZL + 1) = a(45); ws.it(M, Ic, F_ZU + 1) = a(46);
     }
-#endif
     iters = iter; phase = PH_DIR;
   }
 
@@ -2486,11 +2422,9 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
   MPC_HD void promoted() {
     phase = PH_EVAL0; keep_theta = true; ls_start = false; nf = 0; n_polish = 0; acc_count = 0; out_step = out_prev = IC::huge;
     alpha = alpha_l = alpha_z = dw_cur = R(0.0);
-#if MPC_S0_VARIABLE
     /* psi_0 / v_0 have arrived at their pinned values long before a hand-over (a factor 100 per iteration); the other
      * precision's copy of them may lie outside THIS solver's relaxed bounds by its rounding, so they are taken as arrived */
     p0 = st[2]; v0k = st[3];
-#endif
   }
 
   MPC_HD void begin(bool ls) {
@@ -2499,10 +2433,8 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
      * start point (primal part unchanged) with the estimated multipliers, so a separate evaluation is only needed
      * when that estimate is rejected or not wanted */
     phase = ls ? PH_LS : PH_EVAL0; iter = 0; ls_start = ls; tiny = false; n_polish = 0; acc_count = 0; no_restart = false; out_step = out_prev = IC::huge;
-#if MPC_S0_VARIABLE
     p0 = pushed(st[2], yl, yu); v0k = pushed(st[3], vl, vu);
     if (s0_rows) s0_reset(IT0);
-#endif
     alpha = alpha_l = alpha_z = dw_cur = R(0.0);
     theta_max = theta_min = dw_last = R(0.0);
     theta_k = phi_k = pth = pdp = amin = R(0.0);
@@ -2687,9 +2619,7 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
       if (!ftype) filter_add((R(1.0) - IC::gamma_theta) * theta_k, phi_k - IC::gamma_phi * theta_k);
       cur = 1 - cur;
       E = T;
-#if MPC_S0_VARIABLE
       p0 = trial_x0(p0, st[2], alpha); v0k = trial_x0(v0k, st[3], alpha);
-#endif
       /* fp32: the outputs must have been still for two steps in a row (steps are noisy and can be short for other reasons) */
       /* what the polish watches: the step of the outputs (delta_0, a_0), and 0.03 x the largest step of any primal variable
        * -- the predicted trajectory, whose far end is the least determined part of the solution, has then moved by less than
@@ -2909,7 +2839,6 @@ MPC_HD int solve_instance(const MpcParams &P, WS ws, const R *state6, const R *c
   return status;
 }
 
-#if MPC_S0_VARIABLE
 /* ---- the certificate of a stored point (mpc_certify_batch_*, include/mpc_amd_certify.h) ------------------------------------------
  * certify_instance evaluates the NLP of a solve once, at the primal-dual point get(k, f) = field f (Layout<double>) of the record of
  * stage k, and hands the MPC_NCERT measures to put(row, value); it returns the verdict.  The kernel (mpc_certify_kernel) and the
@@ -3084,7 +3013,6 @@ MPC_HD void certify_batch_instance(const MpcParams &P, int64_t i, int64_t ld, co
     certify_batch_instance(P, ModelColumn{model + i, ld}, i, ld, state, coeffs, yaw_lo, yaw_hi, weights, sol, ld_sol, cert, verdict);
   else certify_batch_instance(P, NoColumn{}, i, ld, state, coeffs, yaw_lo, yaw_hi, weights, sol, ld_sol, cert, verdict);
 }
-#endif
 
 }  // namespace mpc
 #endif /* MPC_CORE_H */
