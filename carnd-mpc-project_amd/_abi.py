@@ -113,6 +113,20 @@ CERT_ROWS = ("obj", "constr_viol", "dual_inf", "compl", "nlp_error", "bound_viol
 CERT_CONVERGED, CERT_ACCEPTABLE, CERT_NOT_CONVERGED, CERT_NOT_A_POINT, CERT_NO_PROBLEM = range(5)
 CERT_VERDICT_NAMES = {0: "converged", 1: "acceptable", 2: "not_converged", 3: "not_a_point", 4: "no_problem"}
 
+# ... and include/mpc_amd_drive.h (track driving; tests/test_drive.py)
+DRIVE_EXPORTS = ["mpc_drive_opts_default", "mpc_drive_batch_device", "mpc_drive_batch_device_fused", "mpc_drive_batch_host", "mpc_drive_info"]
+DRIVE_MAX_TRACK, DRIVE_NSUM, DRIVE_REC = 4096, 8, 13      # MPC_DRIVE_MAX_TRACK, rows of summary [NSUM][ld], rows of a step of hist [REC][ld]
+(DRIVE_SUM_MAX_CTE, DRIVE_SUM_CTE2, DRIVE_SUM_MAX_EPSI, DRIVE_SUM_SPEED, DRIVE_SUM_MIN_SPEED, DRIVE_SUM_PROGRESS, DRIVE_SUM_FIRST_OFF,
+ DRIVE_SUM_FAILED) = range(DRIVE_NSUM)
+DRIVE_REC_CAR, DRIVE_REC_CMD, DRIVE_REC_CTE, DRIVE_REC_EPSI, DRIVE_REC_STATUS, DRIVE_REC_ITERS, DRIVE_REC_K = 0, 6, 8, 9, 10, 11, 12
+
+
+class MpcDriveOpts(C.Structure):
+    """Mirror of ``struct MpcDriveOpts`` (include/mpc_amd_drive.h)."""
+    _fields_ = [("size", C.c_int32), ("npts", C.c_int32), ("sub_old", C.c_int32), ("sub_new", C.c_int32), ("warm_start", C.c_int32),
+                ("reserved", C.c_int32), ("h", C.c_double), ("extra_latency", C.c_double), ("cte_limit", C.c_double)]
+
+
 _lib = None
 
 
@@ -198,6 +212,12 @@ def library():
     # the certificate: the _horizon solve's inputs, then sol, ld_sol, cert, verdict (and the stream)
     L.mpc_certify_batch_host.argtypes = H + [DP] * 7 + [DP, I64, DP, DP]
     L.mpc_certify_batch_device.argtypes = L.mpc_certify_batch_host.argtypes + [C.c_void_p]
+    # track driving: B, ld, steps, car, track_x, track_y, n_track, weights, opts, warm_opts, summary, hist, status, iters (and the stream)
+    L.mpc_drive_opts_default.argtypes = [C.POINTER(MpcParams), C.POINTER(MpcDriveOpts)]
+    L.mpc_drive_batch_host.argtypes = H + [C.c_int] + [DP] * 3 + [C.c_int, DP, C.POINTER(MpcDriveOpts), OPTS] + [DP] * 4
+    L.mpc_drive_batch_device.argtypes = L.mpc_drive_batch_host.argtypes + [C.c_void_p]
+    L.mpc_drive_batch_device_fused.argtypes = L.mpc_drive_batch_device.argtypes
+    L.mpc_drive_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.mpc_solve_batch_device_f32.argtypes = L.mpc_solve_batch_device.argtypes      # (the same pointers, to floats)
     L.mpc_solve_batch_host_f32.argtypes = L.mpc_solve_batch_host.argtypes
     L.mpc_wire_parse.argtypes = [C.c_char_p, C.c_int64, C.POINTER(MpcWireTelemetry)]
@@ -252,6 +272,15 @@ def warm_to_vars(warm, state, N):
     v[6 * N:7 * N - 1] = rec[:, 6]
     v[7 * N - 1:] = rec[:, 7]
     return v
+
+
+def drive_opts_default(params, **overrides):
+    """mpc_drive_opts_default for these parameters (needs no device), with keyword overrides (warm_start=1, sub_new=10 ...)."""
+    o = MpcDriveOpts()
+    check(library().mpc_drive_opts_default(C.byref(params), C.byref(o)), "mpc_drive_opts_default")
+    for k, v in overrides.items():
+        setattr(o, k, v)
+    return o
 
 
 def inflight_advice(params, B):

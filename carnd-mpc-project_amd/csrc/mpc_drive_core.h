@@ -1,0 +1,144 @@
+/*
+ * mpc_drive_core.h -- one car of the track-driving loop (include/mpc_amd_drive.h) between two calls of the telemetry handler: the
+ * waypoint window at its position, the plant that moves it under the command it was sent, and what the call keeps per car.
+ *
+ * THE PLANT IS NOT THE UNITY SIMULATOR.  It is the reference's own model of it: Vehicle::move (src/model/Vehicle.cpp:145-168), the
+ * kinematic step of the handler's latency compensation, fed the way the handler reads a telemetry message (mpc_main.cpp:129, :131,
+ * :156).  One instance per lane, everything in registers; compiles for the device and, for the test-only CPU build
+ * (tests/drive_twin), as plain C++.
+ */
+#ifndef MPC_DRIVE_CORE_H
+#define MPC_DRIVE_CORE_H
+
+#include "mpc_run_core.h"
+
+namespace mpc {
+
+MPC_HD bool drive_finite(double v) { return fabs(v) < HUGE_VAL; }
+
+/* The window's first waypoint k (0 .. n-1) for a car at (x, y) on the cyclic track tx / ty [n]: j = the nearest waypoint (smallest
+ * dx * dx + dy * dy; ties: the lowest index; not-a-number never wins: j = 0 for a position that is not finite), k = j if the car is
+ * past it along the segment to the next one, (p - w_j) . (w_{j+1} - w_j) > 0, else the one before.  n trips, whatever the data; the
+ * track is read at the loop index, the same address in every lane. */
+MPC_HD int drive_window(const double *__restrict__ tx, const double *__restrict__ ty, int n, double x, double y) {
+  double best = HUGE_VAL;
+  int j = 0;
+  MPC_STAGE_LOOP
+  for (int q = 0; q < n; q++) {
+    const double dx = x - tx[q], dy = y - ty[q];
+    const double d = dx * dx + dy * dy;
+    if (d < best) { best = d; j = q; }
+  }
+  const int jn = j + 1 == n ? 0 : j + 1;
+  const double wx = tx[j], wy = ty[j];
+  const double dot = (x - wx) * (tx[jn] - wx) + (y - wy) * (ty[jn] - wy);
+  return dot > 0.0 ? j : (j == 0 ? n - 1 : j - 1);
+}
+
+/* w[k .. k + npts - 1], cyclically (npts <= n) -> ptsx / ptsy [npts][ld], column i */
+MPC_HD void drive_window_points(const double *__restrict__ tx, const double *__restrict__ ty, int n, int k, int npts, double *ptsx,
+                                double *ptsy, int64_t ld, int64_t i) {
+  MPC_UNROLL
+  for (int q = 0; q < RUN_MAX_PTS; q++) {
+    if (q < npts) {
+      int idx = k + q;
+      if (idx >= n) idx -= n;
+      ptsx[q * ld + i] = tx[idx]; ptsy[q * ld + i] = ty[idx];
+    }
+  }
+}
+
+/* the signed cyclic difference of two window indices: k - k_prev brought to (-n / 2, n / 2] */
+MPC_HD int drive_progress(int k, int k_prev, int n) {
+  int d = k - k_prev;
+  if (d < 0) d += n;
+  if (2 * d > n) d -= n;
+  return d;
+}
+
+/* One plant substep of length h on car = {x, y, psi, speed [mph], steering_angle, throttle}: the handler's reading of the message
+ * (MpH2MpS mpc_main.cpp:129, the sign :131, the acceleration :156 -- from the speed of this substep), Vehicle::move(h)
+ * (Vehicle.cpp:145-168; the clamp at :156 is overwritten at :167), the speed back to mph (MpS2MpH, utils.h:19-21) */
+MPC_HD void drive_substep(const MpcParams &P, double *car, double h) {
+  const double v = car[3] * 1609.34 / 3600.0;
+  const double steer = -car[4];
+  const double accel = (car[5] - v / 50.0) * 6.0;
+  const double dist = v * h;
+  double sn, cs;
+  fsincos(car[2], &sn, &cs);
+  car[0] = car[0] + dist * cs;
+  car[1] = car[1] + dist * sn;
+  car[2] = car[2] + steer * dist / P.Lf;
+  car[3] = (v + accel * h) * 3600.0 / 1609.34;
+}
+
+/* The plant between two messages: sub_old substeps under the command in force (rows 4 / 5), then the reply takes effect --
+ * (cmd_steer * max_steering, cmd_throttle); a reply that is not finite leaves the old command in force --, then sub_new substeps.
+ * psi is not normalised: the handler does that. */
+MPC_HD void drive_plant(const MpcParams &P, double *car, double cmd_steer, double cmd_throttle, int sub_old, int sub_new, double h) {
+  MPC_STAGE_LOOP
+  for (int s = 0; s < sub_old; s++) drive_substep(P, car, h);
+  if (drive_finite(cmd_steer) && drive_finite(cmd_throttle)) { car[4] = cmd_steer * P.max_steering; car[5] = cmd_throttle; }
+  MPC_STAGE_LOOP
+  for (int s = 0; s < sub_new; s++) drive_substep(P, car, h);
+}
+
+/* The summary rows of one car (MPC_DRIVE_SUM_*), step `step` (0-based) folded in; dk = the progress of this step (0 at step 0).
+ * A not-a-number never wins a maximum or the minimum. */
+MPC_HD void drive_summary(int step, double *sum, double cte0, double epsi0, double speed, int dk, int status, double cte_limit) {
+  const double ac = fabs(cte0), ae = fabs(epsi0);
+  const bool first = step == 0;
+  const double m0 = first ? 0.0 : sum[MPC_DRIVE_SUM_MAX_CTE], m2 = first ? 0.0 : sum[MPC_DRIVE_SUM_MAX_EPSI];
+  const double m4 = first ? HUGE_VAL : sum[MPC_DRIVE_SUM_MIN_SPEED];
+  sum[MPC_DRIVE_SUM_MAX_CTE] = ac > m0 ? ac : m0;
+  sum[MPC_DRIVE_SUM_CTE2] = (first ? 0.0 : sum[MPC_DRIVE_SUM_CTE2]) + cte0 * cte0;
+  sum[MPC_DRIVE_SUM_MAX_EPSI] = ae > m2 ? ae : m2;
+  sum[MPC_DRIVE_SUM_SPEED] = (first ? 0.0 : sum[MPC_DRIVE_SUM_SPEED]) + speed;
+  sum[MPC_DRIVE_SUM_MIN_SPEED] = speed < m4 ? speed : m4;
+  sum[MPC_DRIVE_SUM_PROGRESS] = (first ? 0.0 : sum[MPC_DRIVE_SUM_PROGRESS]) + (double)dk;
+  const double off = first ? -1.0 : sum[MPC_DRIVE_SUM_FIRST_OFF];
+  sum[MPC_DRIVE_SUM_FIRST_OFF] = (off < 0.0 && ac > cte_limit) ? (double)step : off;
+  sum[MPC_DRIVE_SUM_FAILED] = (first ? 0.0 : sum[MPC_DRIVE_SUM_FAILED]) + (status != MPC_STATUS_SUCCESS ? 1.0 : 0.0);
+}
+
+/* ---- one car of a batch between the handler's reply and the next message, as the plant-and-summary kernel and the CPU build run it:
+ * car [6][ld] in / out, cmd [2][ld], pre [RUN_PRE_ROWS][ldp] (the handler's own rows: cte0, epsi0), the step's status and iterations,
+ * the window index of this step and of the one before; summary [MPC_DRIVE_NSUM][ld], rec = this step's block of hist
+ * [MPC_DRIVE_REC][ld] or nullptr, status / iters (or nullptr) per car: worst code, summed iterations (mpc::RolloutCar). */
+MPC_HD void drive_step_instance(const MpcParams &P, const MpcDriveOpts &O, int64_t i, int64_t ld, int step, int n_track, double *car,
+                                const double *cmd, const double *pre, int64_t ldp, int32_t st_step, int32_t it_step, int k, int k_prev,
+                                double *summary, double *rec, int32_t *status, int32_t *iters) {
+  double c[6], sum[MPC_DRIVE_NSUM] = {};
+  MPC_UNROLL
+  for (int q = 0; q < 6; q++) c[q] = car[q * ld + i];
+  const double cs = cmd[i], ct = cmd[ld + i];
+  const double cte0 = pre[(RUN_PRE_STATE + 4) * ldp + i], epsi0 = pre[(RUN_PRE_STATE + 5) * ldp + i];
+  if (rec) {
+    MPC_UNROLL
+    for (int q = 0; q < 6; q++) rec[(MPC_DRIVE_REC_CAR + q) * ld + i] = c[q];
+    rec[MPC_DRIVE_REC_CMD * ld + i] = cs; rec[(MPC_DRIVE_REC_CMD + 1) * ld + i] = ct;
+    rec[MPC_DRIVE_REC_CTE * ld + i] = cte0; rec[MPC_DRIVE_REC_EPSI * ld + i] = epsi0;
+    rec[MPC_DRIVE_REC_STATUS * ld + i] = (double)st_step; rec[MPC_DRIVE_REC_ITERS * ld + i] = (double)it_step;
+    rec[MPC_DRIVE_REC_K * ld + i] = (double)k;
+  }
+  if (step > 0) {
+    MPC_UNROLL
+    for (int q = 0; q < MPC_DRIVE_NSUM; q++) sum[q] = summary[q * ld + i];
+  }
+  drive_summary(step, sum, cte0, epsi0, c[3], step > 0 ? drive_progress(k, k_prev, n_track) : 0, st_step, O.cte_limit);
+  MPC_UNROLL
+  for (int q = 0; q < MPC_DRIVE_NSUM; q++) summary[q * ld + i] = sum[q];
+  int32_t worst = 0, total = 0;
+  if (step > 0) worst = status[i];
+  status[i] = RolloutCar::fold_status(step, worst, st_step);
+  if (iters) {
+    if (step > 0) total = iters[i];
+    iters[i] = RolloutCar::sum_iters(step, total, it_step);
+  }
+  drive_plant(P, c, cs, ct, O.sub_old, O.sub_new, O.h);
+  MPC_UNROLL
+  for (int q = 0; q < 6; q++) car[q * ld + i] = c[q];
+}
+
+}  // namespace mpc
+#endif

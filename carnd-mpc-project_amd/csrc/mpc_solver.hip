@@ -20,6 +20,7 @@
 
 #include "mpc_core.h"
 #include "mpc_run_core.h"
+#include "mpc_drive_core.h"
 #include "mpc_take_key.h"
 
 namespace {
@@ -226,17 +227,37 @@ struct MpcHorizonPart {
   const int32_t *horizon;
 };
 
+/* DRIVE (mpc_drive_batch_device_fused): a ROLL build whose car follows a track.  Between two solves the lane runs, for its own car
+ * and through the car's own columns of the arrays below, what the stepwise loop runs in five launches: the window (mpc::drive_window),
+ * the handler's pre-solve half (mpc::run_pre_instance<true>) at the take and at every hand-over with steps left, and at a finished
+ * step the post-solve half (mpc::run_post_instance) and plant, summary and record (mpc::drive_step_instance).  The solve reads its
+ * state, coefficients and psi box from the rows of `pre` this lane has just written, so none of these pointers is const or
+ * __restrict__, and the kernel's own state / coeffs / yaw_lo / yaw_hi arguments are not dereferenced in these builds.  steps, status
+ * and iters are the roll part's; the kernel's ld is the stride of pre and of the weights, ldo the caller's leading dimension. */
+struct MpcDrivePart {
+  MpcDriveOpts O;
+  double *car;                    /* [6][ldo] in / out */
+  const double *track_x, *track_y;
+  int32_t n_track;
+  double *ptsx, *ptsy, *cmd;      /* [8][ldo], [8][ldo], [2][ldo]: the handle's rows */
+  double *pre;                    /* [RUN_PRE_ROWS][ld]: the handle's rows */
+  double *out9;                   /* [9][ldo]: the handle's rows */
+  double *summary, *rec;          /* [MPC_DRIVE_NSUM][ldo]; hist [steps][MPC_DRIVE_REC][ldo] or nullptr */
+};
+
 template <bool ON, class Part> struct MpcPartIf : Part {};
 template <class Part> struct MpcPartIf<false, Part> {};
-template <bool ROLL, bool WARM, bool MODEL, bool HORIZON = false>
-struct MpcPhaseParts : MpcPhase, MpcPartIf<WARM, mpc::WarmCall>, MpcPartIf<ROLL, MpcRollPart>, MpcPartIf<MODEL, MpcModelPart>, MpcPartIf<HORIZON, MpcHorizonPart> {};
-template <bool ROLL, bool WARM, bool MODEL, bool HORIZON = false>
-using MpcPhaseOf = std::conditional_t<ROLL || WARM || MODEL || HORIZON, MpcPhaseParts<ROLL, WARM, MODEL, HORIZON>, MpcPhase>;
+template <bool ROLL, bool WARM, bool MODEL, bool HORIZON = false, bool DRIVE = false>
+struct MpcPhaseParts : MpcPhase, MpcPartIf<WARM, mpc::WarmCall>, MpcPartIf<ROLL, MpcRollPart>, MpcPartIf<MODEL, MpcModelPart>, MpcPartIf<HORIZON, MpcHorizonPart>,
+                       MpcPartIf<DRIVE, MpcDrivePart> {};
+template <bool ROLL, bool WARM, bool MODEL, bool HORIZON = false, bool DRIVE = false>
+using MpcPhaseOf = std::conditional_t<ROLL || WARM || MODEL || HORIZON, MpcPhaseParts<ROLL, WARM, MODEL, HORIZON, DRIVE>, MpcPhase>;
 /* a phase's value from its parts: those the build does not inherit are left out */
-template <bool ROLL, bool WARM, bool MODEL, bool HORIZON = false>
-static MpcPhaseOf<ROLL, WARM, MODEL, HORIZON> phase_of(const MpcPhase &T, const mpc::WarmCall &warm, const MpcRollPart &roll, const MpcModelPart &model,
-                                                       const MpcHorizonPart &horizon = {}) {
-  MpcPhaseOf<ROLL, WARM, MODEL, HORIZON> X;
+template <bool ROLL, bool WARM, bool MODEL, bool HORIZON = false, bool DRIVE = false>
+static MpcPhaseOf<ROLL, WARM, MODEL, HORIZON, DRIVE> phase_of(const MpcPhase &T, const mpc::WarmCall &warm, const MpcRollPart &roll, const MpcModelPart &model,
+                                                              const MpcHorizonPart &horizon = {}, const MpcDrivePart &drive = {}) {
+  MpcPhaseOf<ROLL, WARM, MODEL, HORIZON, DRIVE> X;
+  if constexpr (DRIVE) static_cast<MpcDrivePart &>(X) = drive;
   static_cast<MpcPhase &>(X) = T;
   if constexpr (WARM) static_cast<mpc::WarmCall &>(X) = warm;
   if constexpr (ROLL) static_cast<MpcRollPart &>(X) = roll;
@@ -383,15 +404,16 @@ __device__ __forceinline__ int64_t park_for_next_phase(const MpcPhase &T, const 
  * divergent loop, a lane leaves it after its own M stages, and a pass of the wave costs the longest horizon among its running lanes.
  * Their dynamic LDS is the mailbox of lane compaction alone.  A moved instance is set up again from its index, horizon included. */
 template <bool STAGING, class R, class RIO = R, class RSRC = RIO, bool SOC = false, bool WARM = false, bool ROLL = false, bool MODEL = false,
-          bool HORIZON = false>
+          bool HORIZON = false, bool DRIVE = false>
 __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
     const MpcParams P, const int64_t B, const int64_t ld, const int64_t ldo, const RIO *__restrict__ state,
     const RIO *__restrict__ coeffs, const RIO *__restrict__ yaw_lo, const RIO *__restrict__ yaw_hi,
     const RIO *__restrict__ weights, RIO *__restrict__ out, RIO *__restrict__ traj,
     int32_t *__restrict__ status, int32_t *__restrict__ iters, R *__restrict__ wsbase,
     const int64_t tile_reals,
-    const MpcPhaseOf<ROLL, WARM, MODEL, HORIZON> T) {
+    const MpcPhaseOf<ROLL, WARM, MODEL, HORIZON, DRIVE> T) {
   extern __shared__ double smem[];
+  static_assert(!DRIVE || (ROLL && !MODEL && !HORIZON && !SOC), "track driving: a ROLL build without MODEL, HORIZON and SOC");
   static_assert(!HORIZON || (MODEL && !STAGING && !SOC), "per-instance horizon: a MODEL build without staging and SOC");
   static_assert(!WARM || (sizeof(R) == 8 && std::is_same<R, RIO>::value && std::is_same<R, RSRC>::value && !SOC), "warm start: the plain fp64 solve only");
   static_assert(!ROLL || (sizeof(R) == 8 && std::is_same<R, RIO>::value && std::is_same<R, RSRC>::value && !SOC), "fused rollout: the plain fp64 solve only");
@@ -414,6 +436,8 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
   bool col_busy = false;                         /* this lane's column holds a parked iterate */
   int attempt = 0, it_total = 0, passes = 0, fin_status = 0, waited = 0, cooldown = 0;
   int step = 0;                                  /* ROLL: solves of car i finished so far */
+  int drive_k = 0, drive_k_prev = 0;             /* DRIVE: the window index of the car's current step and of the one before */
+  (void)drive_k; (void)drive_k_prev;
   const int64_t n_work = T.resume ? (int64_t)*T.n_in : B;
   (void)col_busy; (void)cooldown; (void)step;
   for (;;) {
@@ -458,6 +482,21 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
         if constexpr (ROLL) {
           if (fin) {
             using Car = mpc::RolloutCar;
+            if constexpr (DRIVE) {
+              /* the solve's nine rows, then what the post kernel and the plant-and-summary kernel do for this car */
+              double *o = T.out9 + i;
+              const int64_t l = ldo;
+              const R ylo = (R)T.pre[mpc::RUN_PRE_YAW_LO * ld + i], yhi = (R)T.pre[mpc::RUN_PRE_YAW_HI * ld + i];
+              S.unpack(mpc::NoColumn{}, [o, l](int q) { return OutRef<RIO, R>{o + q * l}; }, [](int) { return OutRef<RIO, R>{nullptr}; }, false, ylo, yhi);
+              if constexpr (WARM) {
+                double *wo = T.warm_out + i;
+                const int64_t lw = T.ld_warm;
+                S.warm_store([wo, lw](int k, int f, R v) { wo[(int64_t)(k * MPC_WARM_REC + f) * lw] = v; });
+              }
+              mpc::run_post_instance(P, P, i, T.pre, ld, T.out9, ldo, (double *)nullptr, T.cmd, ldo);
+              mpc::drive_step_instance(P, T.O, i, ldo, step, T.n_track, T.car, T.cmd, T.pre, ld, fin_status, S.iters + it_total, drive_k, drive_k_prev,
+                                       T.summary, T.rec ? T.rec + (int64_t)step * MPC_DRIVE_REC * ldo : nullptr, T.status, T.iters);
+            } else {
             double *o = T.hist + (int64_t)step * T.hist_step + i;
             const int64_t l = ldo;
             const R ylo = (R)yaw_lo[i], yhi = (R)yaw_hi[i];
@@ -478,6 +517,7 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
               double *wo = T.warm_out + i;
               const int64_t lw = T.ld_warm;
               S.warm_store([wo, lw](int k, int f, R v) { wo[(int64_t)(k * MPC_WARM_REC + f) * lw] = v; });
+            }
             }
             ++step;
             again = step < T.steps;
@@ -529,10 +569,22 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
               if ((uint64_t)i >= (uint64_t)B) i = pos;     /* (cannot happen: the lists hold 0 .. B-1 once each; results never go out of bounds) */
             }
             R st[6], cf[MPC_NCOEF], w[MPC_NW];
-            const RIO *sp = state;
-            if constexpr (ROLL) sp = T.state;      /* the car's state as it stands: the start state, or the six doubles this lane stored at the step before */
-            mpc::gather_instance(P, i, ld, sp, coeffs, weights, st, cf, w);
-            const R ylo = (R)yaw_lo[i], yhi = (R)yaw_hi[i];
+            R ylo_in, yhi_in;
+            if constexpr (DRIVE) {
+              /* the car as it stands: its window, the handler's pre-solve half into the car's column of `pre`, and the solve's inputs from there */
+              drive_k_prev = drive_k;
+              drive_k = mpc::drive_window(T.track_x, T.track_y, T.n_track, T.car[i], T.car[ldo + i]);
+              mpc::drive_window_points(T.track_x, T.track_y, T.n_track, drive_k, T.O.npts, T.ptsx, T.ptsy, ldo, i);
+              (void)mpc::run_pre_instance<true>(P, P, i, ldo, T.O.npts, T.car, T.O.extra_latency, T.ptsx, T.ptsy, T.pre, ld);
+              mpc::gather_instance(P, i, ld, T.pre + mpc::RUN_PRE_STATE * ld, T.pre + mpc::RUN_PRE_COEFFS * ld, weights, st, cf, w);
+              ylo_in = (R)T.pre[mpc::RUN_PRE_YAW_LO * ld + i]; yhi_in = (R)T.pre[mpc::RUN_PRE_YAW_HI * ld + i];
+            } else {
+              const RIO *sp = state;
+              if constexpr (ROLL) sp = T.state;      /* the car's state as it stands: the start state, or the six doubles this lane stored at the step before */
+              mpc::gather_instance(P, i, ld, sp, coeffs, weights, st, cf, w);
+              ylo_in = (R)yaw_lo[i]; yhi_in = (R)yaw_hi[i];
+            }
+            const R ylo = ylo_in, yhi = yhi_in;
             const bool from_scratch = T.promote_in && T.in_park[pos + 35 * T.ld_park] != 0.0;   /* the fp32 phase gave up on it */
             bool warm = false, warm_cand = false;   /* WARM: this instance has a valid column in warm_in / starts from it */
             if constexpr (WARM && ROLL) warm_cand = again_warm;   /* (the column this lane stored when it finished the step before) */
@@ -1019,6 +1071,34 @@ __global__ __launch_bounds__(256) void mpc_rollout_step_kernel(int64_t B, int64_
   if (iters) iters[i] = (first ? 0 : iters[i]) + it_step[i];
 }
 
+/* Track driving (mpc_drive_batch_*, include/mpc_amd_drive.h), the two kernels around the handler's three: one car per lane, 256 per
+ * block, no LDS, mpc::drive_* of mpc_drive_core.h.  The track is read at the loop index -- the same address in every lane of a wave,
+ * scalar loads -- and once per lane at the car's own nearest waypoint and window.
+ * Sense: the window index of every car at its position and the window's waypoints, laid out as the handler takes them. */
+__global__ __launch_bounds__(256) void mpc_drive_sense_kernel(int64_t B, int64_t ld, int npts, const double *__restrict__ car,
+                                                              const double *__restrict__ track_x, const double *__restrict__ track_y,
+                                                              int n_track, double *__restrict__ ptsx, double *__restrict__ ptsy,
+                                                              int32_t *__restrict__ k_now) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B) return;
+  const int k = mpc::drive_window(track_x, track_y, n_track, car[i], car[ld + i]);
+  mpc::drive_window_points(track_x, track_y, n_track, k, npts, ptsx, ptsy, ld, i);
+  k_now[i] = k;
+}
+
+/* Plant and summary: the step's record and summary rows, the car's worst status and summed iterations, then the car moved under the
+ * command it was sent (mpc::drive_step_instance).  pre: the handler's own rows of this step (cte0, epsi0). */
+__global__ __launch_bounds__(256) void mpc_drive_plant_kernel(const MpcParams P, const MpcDriveOpts O, int64_t B, int64_t ld, int step, int n_track,
+                                                              double *__restrict__ car, const double *__restrict__ cmd,
+                                                              const double *__restrict__ pre, int64_t ldp, const int32_t *__restrict__ st_step,
+                                                              const int32_t *__restrict__ it_step, const int32_t *k_now,
+                                                              const int32_t *k_prev, double *__restrict__ summary,
+                                                              double *__restrict__ rec, int32_t *__restrict__ status, int32_t *__restrict__ iters) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B) return;
+  mpc::drive_step_instance(P, O, i, ld, step, n_track, car, cmd, pre, ldp, st_step[i], it_step[i], k_now[i], k_prev[i], summary, rec, status, iters);
+}
+
 /* The certificate of a stored point (mpc_certify_batch_*), one instance per lane: mpc::certify_batch_instance of mpc_core.h.  A lane
  * walks the stage records of its column of `sol` once -- consecutive lanes read consecutive addresses of every row, like `state` --
  * and keeps the neighbouring state, multipliers and steering values in registers: no workspace, no LDS, no loop whose trip count the
@@ -1213,6 +1293,14 @@ struct MpcHandle {
   double *d_model = nullptr;      /* the device side of mpc_solve_batch_host_model's model array (allocated on first use) */
   int32_t *d_warm_st = nullptr;
   int64_t n_roll_fused = 0, n_roll_stepwise = 0;   /* mpc_rollout_batch_device_fused calls that ran the fused kernel / the stepwise loop (mpc_rollout_fused_info) */
+  /* track driving (allocated on first use): the window rows, the reply and the window indices of two steps, with the caller's leading
+   * dimension -- ptsx [8][ld], ptsy [8][ld], cmd [2][ld], k [2][ld] int32 --; the caller's weights at the handle's stride, as run()'s solve
+   * reads its inputs; calls that ran the one launch / the stepwise loop (mpc_drive_info) */
+  double *d_drive = nullptr, *d_drive_w = nullptr;
+  size_t drive_bytes = 0;
+  double *d_drive_host = nullptr;     /* mpc_drive_batch_host: device staging, grown on demand */
+  size_t drive_host_bytes = 0;
+  int64_t n_drive_fused = 0, n_drive_stepwise = 0;
   double *d_tel = nullptr;       /* mpc_telemetry_batch_host: device staging, grown on demand */
   size_t tel_bytes = 0;
   /* last call */
@@ -1423,6 +1511,9 @@ extern "C" void mpc_destroy(MpcHandle *h) {
   if (h->d_take_list) (void)hipFree(h->d_take_list);
   if (h->d_piter) (void)hipFree(h->d_piter);
   if (h->d_tel) (void)hipFree(h->d_tel);
+  if (h->d_drive) (void)hipFree(h->d_drive);
+  if (h->d_drive_w) (void)hipFree(h->d_drive_w);
+  if (h->d_drive_host) (void)hipFree(h->d_drive_host);
   if (h->d_warm) (void)hipFree(h->d_warm);
   if (h->d_model) (void)hipFree(h->d_model);
   if (h->d_warm_io) (void)hipFree(h->d_warm_io);
@@ -1896,6 +1987,7 @@ struct CallExtras {
   int64_t ld_model = 0;            /* 0: the ld of the solve's inputs.  (run() sets its own: it solves from the handle's rows at the handle's stride, the columns stay where the caller has them) */
   bool model_wave = false;         /* a model call of the run() / telemetry entry points: the wave MODEL kernels up to wave_max_batch */
   const int32_t *horizon = nullptr;   /* a horizon call (fp64 handles, no SOC): [ld] like the inputs; dispatched as a model call, `model` may be NULL */
+  const double *run_weights = nullptr;   /* run() / telemetry only (the drive loop): per-instance weights of the solve, [MPC_NW][io_stride] like the rows run() solves from */
   bool model_call() const { return model != nullptr || horizon != nullptr; }
   const WarmIO *warm_io() const { return warm ? &w : nullptr; }
 };
@@ -2381,7 +2473,7 @@ static int run_impl(MpcHandle *h, int64_t B, int64_t ld, int npts, const double 
   MPC_HIP_CHECK(hipGetLastError());
   x.w.psi_box = 1; x.ld_model = ld; x.model_wave = true;      /* the run() path's own */
   MPC_TRY(launch_solve<double>(h, {B, S, ld, d_pre + mpc::RUN_PRE_STATE * S, d_pre + mpc::RUN_PRE_COEFFS * S, d_pre + mpc::RUN_PRE_YAW_LO * S,
-                                   d_pre + mpc::RUN_PRE_YAW_HI * S, nullptr, h->d_run9, traj, status, iters}, stream_, kStats, x));
+                                   d_pre + mpc::RUN_PRE_YAW_HI * S, x.run_weights, h->d_run9, traj, status, iters}, stream_, kStats, x));
   around([&](auto model_build, auto... mp) {
     hipLaunchKernelGGL((mpc_run_post_kernel<decltype(model_build)::value, decltype(mp)...>), dim3(grid), dim3(256), 0, s, h->params, B, d_pre, S,
                        h->d_run9, ld, out8, cmd, ld, mp...);
@@ -2767,6 +2859,195 @@ extern "C" int mpc_rollout_batch_device_fused_horizon(MpcHandle *h, int64_t B, i
 extern "C" int mpc_rollout_fused_info(const MpcHandle *h, int64_t *out2) {
   if (!h || !out2) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
   out2[0] = h->n_roll_fused; out2[1] = h->n_roll_stepwise;
+  return MPC_OK;
+}
+
+/* ---- track driving (include/mpc_amd_drive.h) -------------------------------------------------------------------------------------- */
+extern "C" int mpc_drive_opts_default(const MpcParams *p, MpcDriveOpts *o) {
+  if (!p || !o) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
+  memset(o, 0, sizeof(*o));
+  o->size = (int32_t)sizeof(MpcDriveOpts); o->npts = 6; o->h = 0.01;
+  o->sub_old = (p->latency_ms + 5) / 10;             /* the command in force lasts for the latency, in substeps of 10 ms */
+  o->sub_new = p->latency_ms != 0 ? 2 : 10;
+  o->warm_start = 0; o->extra_latency = 0.0; o->cte_limit = 3.0;
+  return MPC_OK;
+}
+
+/* what the drive entry points check before they touch anything; *O: the options in effect (opts = NULL: the defaults) */
+static int drive_args(const MpcHandle *h, int64_t B, int64_t ld, int steps, const double *car, const double *track_x, const double *track_y,
+                      int n_track, const MpcDriveOpts *opts, const double *summary, const int32_t *status, MpcDriveOpts *O) {
+  const auto refuse = [](const char *why) { g_last_error = why; return MPC_ERR_INVALID; };
+  if (!h) return refuse("NULL handle");
+  if (opts) {
+    if (opts->size != (int32_t)sizeof(MpcDriveOpts)) return refuse("MpcDriveOpts.size mismatch (fill it with mpc_drive_opts_default)");
+    *O = *opts;
+  } else (void)mpc_drive_opts_default(&h->params, O);
+  if (h->params.precision != MPC_PRECISION_F64) return refuse("track driving: fp64 handles only (this one was created with MPC_PRECISION_F32)");
+  if (steps < 1) return refuse("steps < 1");
+  if (O->npts < 3 || O->npts > mpc::RUN_MAX_PTS) return refuse("MpcDriveOpts.npts must be 3..8");
+  if (n_track < O->npts || n_track > MPC_DRIVE_MAX_TRACK) return refuse("n_track must be npts..MPC_DRIVE_MAX_TRACK");
+  if (O->sub_old < 0 || O->sub_new < 0) return refuse("MpcDriveOpts: a substep count below 0");
+  if ((int64_t)O->sub_old + O->sub_new < 1 || (int64_t)O->sub_old + O->sub_new > 1000) return refuse("MpcDriveOpts: sub_old + sub_new must be 1..1000");
+  if (!(O->h > 0.0) || !mpc::drive_finite(O->h)) return refuse("MpcDriveOpts.h must be finite and > 0");
+  if (B < 0 || ld < B) return refuse("ld < B");
+  if (B > h->max_batch) return refuse("B exceeds the handle's max_batch");
+  if (!car || !track_x || !track_y || !summary || !status) return refuse("NULL argument");
+  return MPC_OK;
+}
+
+/* the handle's rows both forms work in: the window rows and the reply, the warm buffer of a warm call, and the caller's weights copied
+ * to the handle's stride (*w_out; NULL without weights) */
+static int drive_rows(MpcHandle *h, int64_t B, int64_t ld, bool warm, const double *weights, hipStream_t s, const double **w_out) {
+  const int64_t S = h->io_stride;
+  MPC_TRY(grow_dev(&h->d_drive, &h->drive_bytes, sizeof(double) * (size_t)((2 * mpc::RUN_MAX_PTS + 2) * ld) + sizeof(int32_t) * (size_t)(2 * ld)));
+  if (warm) MPC_TRY(ensure_dev(&h->d_warm, sizeof(double) * (size_t)mpc_warm_rows(h->params.N) * (size_t)S));
+  *w_out = nullptr;
+  if (weights) {
+    MPC_TRY(ensure_dev(&h->d_drive_w, sizeof(double) * MPC_NW * S));
+    MPC_HIP_CHECK(hipMemcpy2DAsync(h->d_drive_w, sizeof(double) * S, weights, sizeof(double) * ld, sizeof(double) * B, MPC_NW, hipMemcpyDeviceToDevice, s));
+    *w_out = h->d_drive_w;
+  }
+  return MPC_OK;
+}
+
+/* The stepwise loop: `steps` x (sense kernel, the telemetry handler -- run_impl with tel, the weights and an iterations pointer --,
+ * plant-and-summary kernel) on the caller's stream; no host synchronisation.  x.warm: every step after the first is the _warm handler
+ * on the handle's own buffer, in place (rollout_impl's arrangement). */
+static int drive_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y, int n_track,
+                      const double *weights, const MpcDriveOpts &O, CallExtras x, double *summary, double *hist, int32_t *status,
+                      int32_t *iters, void *stream_) {
+  MPC_ON_DEVICE(h);
+  const int64_t S = h->io_stride;
+  const int P8 = mpc::RUN_MAX_PTS;
+  hipStream_t s = (hipStream_t)stream_;
+  MPC_TRY(drive_rows(h, B, ld, x.warm, weights, s, &x.run_weights));
+  MPC_TRY(ensure_dev(&h->d_rstat, sizeof(int32_t) * S));
+  double *ptsx = h->d_drive, *ptsy = ptsx + P8 * ld, *cmd = ptsy + P8 * ld;
+  int32_t *kbuf = (int32_t *)(cmd + 2 * ld);
+  const unsigned grid = (unsigned)((B + 255) / 256);
+  for (int t = 0; t < steps; t++) {
+    /* (the first step has no step before it: it is handed its own row, and mpc::drive_step_instance does not look at the value) */
+    int32_t *k_now = kbuf + (int64_t)(t & 1) * ld, *k_prev = t == 0 ? k_now : kbuf + (int64_t)((t & 1) ^ 1) * ld;
+    hipLaunchKernelGGL(mpc_drive_sense_kernel, dim3(grid), dim3(256), 0, s, B, ld, (int)O.npts, car, track_x, track_y, n_track, ptsx, ptsy, k_now);
+    MPC_HIP_CHECK(hipGetLastError());
+    x.w = WarmIO{t == 0 ? nullptr : h->d_warm, h->d_rstat, h->d_warm, S, x.w.wopts, 0};
+    MPC_TRY(run_impl(h, B, ld, O.npts, car, true, O.extra_latency, ptsx, ptsy, nullptr, cmd, nullptr, h->d_rstat, h->d_iters, nullptr, stream_, x));
+    hipLaunchKernelGGL(mpc_drive_plant_kernel, dim3(grid), dim3(256), 0, s, h->params, O, B, ld, t, n_track, car, cmd, h->d_run, S, h->d_rstat,
+                       h->d_iters, k_now, k_prev, summary, hist ? hist + (int64_t)t * MPC_DRIVE_REC * ld : nullptr, status, iters);
+    MPC_HIP_CHECK(hipGetLastError());
+  }
+  ++h->n_drive_stepwise;
+  return record_stats(h, B, status, iters, s);   /* as the rollouts: worst status per car, iterations summed over the steps */
+}
+
+extern "C" int mpc_drive_batch_device(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                                      int n_track, const double *weights, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts,
+                                      double *summary, double *hist, int32_t *status, int32_t *iters, void *stream_) {
+  MpcDriveOpts O;
+  MPC_TRY(drive_args(h, B, ld, steps, car, track_x, track_y, n_track, opts, summary, status, &O));
+  const CallExtras x = call_extras(h, nullptr, O.warm_start != 0, nullptr, nullptr, nullptr, 0, warm_opts);
+  MPC_TRY(x.refused);
+  if (B == 0) { h->last_B = 0; return MPC_OK; }
+  return drive_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
+}
+
+/* The loop in one launch: the DRIVE build of the lane kernel (see mpc_solve_kernel and MpcDrivePart), a lane per car for all `steps`
+ * messages.  rollout_fused_impl's rule decides: the one launch runs where the stepwise loop would launch exactly the single-phase fp64
+ * lane kernel at every step (no fp32 start, no SOC, B above the wave limit); everywhere else the call IS the stepwise loop. */
+static int drive_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y, int n_track,
+                            const double *weights, const MpcDriveOpts &O, const CallExtras &x, double *summary, double *hist, int32_t *status,
+                            int32_t *iters, void *stream_) {
+  const bool wave_path = h->wave_max_batch > 0 && B <= h->wave_max_batch;
+  if (h->mixed || h->params.max_soc > 0 || wave_path)
+    return drive_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
+  MPC_TRY(check_batch(h, B, ld));
+  if (h->params.n_yaw_change_speeds < 1 || h->params.n_steer_speeds < 1) { g_last_error = "run(): empty speed tables (load a config-*.json)"; return MPC_ERR_INVALID; }
+  if (h->params.max_fit_order > 5) { g_last_error = "run(): max_fit_order > 5 is not built (fit orders 2..4)"; return MPC_ERR_UNSUPPORTED; }
+  MPC_ON_DEVICE(h);
+  const int64_t S = h->io_stride;
+  const int P8 = mpc::RUN_MAX_PTS;
+  hipStream_t s = (hipStream_t)stream_;
+  const double *w_dev = nullptr;
+  MPC_TRY(drive_rows(h, B, ld, x.warm, weights, s, &w_dev));
+  MPC_TRY(ensure_dev(&h->d_run, sizeof(double) * mpc::RUN_PRE_ROWS * S));
+  MPC_TRY(grow_dev(&h->d_run9, &h->run9_bytes, sizeof(double) * 9 * ld));
+  double *d_pre = h->d_run, *ptsx = h->d_drive, *ptsy = ptsx + P8 * ld, *cmd = ptsy + P8 * ld;
+  const SolveIO<double> io{B, S, ld, d_pre + mpc::RUN_PRE_STATE * S, d_pre + mpc::RUN_PRE_COEFFS * S, d_pre + mpc::RUN_PRE_YAW_LO * S,
+                           d_pre + mpc::RUN_PRE_YAW_HI * S, w_dev, h->d_run9, nullptr, status, iters ? iters : h->d_iters};
+  std::optional<DeviceGuard> guard;
+  MpcHandle::BatchRec *rec = nullptr;
+  MPC_TRY(solve_begin(h, io, nullptr, guard, &rec));
+  const CounterBlocks C = take_counters(h);
+  MPC_HIP_CHECK(hipEventRecord(h->ev0, s));
+  MpcPhase T = phase_defaults(h, B);
+  T.take = C.cb; T.n_out = C.cb + 1; T.zero_next = C.zero_next;
+  T.compact_gap = 0;                             /* (the step index does not travel with a moved instance) */
+  const TailPlace tp;
+  tail_fields(h, tp, T);
+  double *warm = x.warm ? h->d_warm : nullptr;
+  const WarmIO wc{warm, nullptr, warm, S, x.w.wopts, 1};      /* (psi_box: the run() path's rule) */
+  const MpcRollPart roll{steps, nullptr, 0, nullptr, status, iters};
+  const MpcDrivePart drive{O, car, track_x, track_y, n_track, ptsx, ptsy, cmd, d_pre, h->d_run9, summary, hist};
+  const unsigned grid = (unsigned)((B + kBlock - 1) / kBlock);
+  MPC_TRY(with_bool(h->staging, [&](auto staging) {
+    return with_bool(x.warm, [&](auto warm_build) {
+      constexpr bool STAGING = decltype(staging)::value, WARM = decltype(warm_build)::value;
+      return launch_kernel(mpc_solve_kernel<STAGING, double, double, double, false, WARM, true, false, false, true>, grid, STAGING ? staging_lds_bytes<double>() : 0,
+                           s, h, io, (double *)h->ws, h->ws_stride, phase_of<true, WARM, false, false, true>(T, wc, roll, {}, {}, drive));
+    });
+  }));
+  MPC_TRY(solve_end(h, io, s, rec, tp, false));
+  ++h->n_drive_fused;
+  return record_stats(h, B, status, iters, s);
+}
+
+extern "C" int mpc_drive_batch_device_fused(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                                            int n_track, const double *weights, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts,
+                                            double *summary, double *hist, int32_t *status, int32_t *iters, void *stream_) {
+  MpcDriveOpts O;
+  MPC_TRY(drive_args(h, B, ld, steps, car, track_x, track_y, n_track, opts, summary, status, &O));
+  const CallExtras x = call_extras(h, nullptr, O.warm_start != 0, nullptr, nullptr, nullptr, 0, warm_opts);
+  MPC_TRY(x.refused);
+  if (B == 0) { h->last_B = 0; return MPC_OK; }
+  return drive_fused_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
+}
+
+/* The same for host arrays: one copy in, the loop on the handle's own device and stream, one copy out; synchronises.  Staging kept on
+ * the handle and grown on demand, like the telemetry handler's. */
+extern "C" int mpc_drive_batch_host(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                                    int n_track, const double *weights, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts,
+                                    double *summary, double *hist, int32_t *status, int32_t *iters) {
+  MpcDriveOpts O;
+  MPC_TRY(drive_args(h, B, ld, steps, car, track_x, track_y, n_track, opts, summary, status, &O));
+  const CallExtras x = call_extras(h, nullptr, O.warm_start != 0, nullptr, nullptr, nullptr, 0, warm_opts);
+  MPC_TRY(x.refused);
+  if (B == 0) { h->last_B = 0; return MPC_OK; }
+  MPC_ON_DEVICE(h);
+  const int64_t L = (B + 7) / 8 * 8;
+  const int64_t rows = 6 + MPC_DRIVE_NSUM + (weights ? MPC_NW : 0) + (hist ? (int64_t)steps * MPC_DRIVE_REC : 0);
+  MPC_TRY(grow_dev(&h->d_drive_host, &h->drive_host_bytes, sizeof(double) * (size_t)(rows * L + 2 * n_track) + sizeof(int32_t) * (size_t)(2 * L)));
+  double *d = h->d_drive_host;
+  double *d_car = d, *d_sum = d_car + 6 * L, *d_w = d_sum + MPC_DRIVE_NSUM * L, *d_hist = d_w + (weights ? MPC_NW * L : 0);
+  double *d_tx = d_hist + (hist ? (int64_t)steps * MPC_DRIVE_REC * L : 0), *d_ty = d_tx + n_track;
+  int32_t *d_st = (int32_t *)(d_ty + n_track), *d_it = d_st + L;
+  hipStream_t s = h->stream;
+  MPC_HIP_CHECK(hipMemcpy2DAsync(d_car, sizeof(double) * L, car, sizeof(double) * ld, sizeof(double) * B, 6, hipMemcpyHostToDevice, s));
+  if (weights) MPC_HIP_CHECK(hipMemcpy2DAsync(d_w, sizeof(double) * L, weights, sizeof(double) * ld, sizeof(double) * B, MPC_NW, hipMemcpyHostToDevice, s));
+  MPC_HIP_CHECK(hipMemcpyAsync(d_tx, track_x, sizeof(double) * n_track, hipMemcpyHostToDevice, s));
+  MPC_HIP_CHECK(hipMemcpyAsync(d_ty, track_y, sizeof(double) * n_track, hipMemcpyHostToDevice, s));
+  MPC_TRY(drive_impl(h, B, L, steps, d_car, d_tx, d_ty, n_track, weights ? d_w : nullptr, O, x, d_sum, hist ? d_hist : nullptr, d_st, d_it, (void *)s));
+  MPC_HIP_CHECK(hipMemcpy2DAsync(car, sizeof(double) * ld, d_car, sizeof(double) * L, sizeof(double) * B, 6, hipMemcpyDeviceToHost, s));
+  MPC_HIP_CHECK(hipMemcpy2DAsync(summary, sizeof(double) * ld, d_sum, sizeof(double) * L, sizeof(double) * B, MPC_DRIVE_NSUM, hipMemcpyDeviceToHost, s));
+  if (hist) MPC_HIP_CHECK(hipMemcpy2DAsync(hist, sizeof(double) * ld, d_hist, sizeof(double) * L, sizeof(double) * B, (size_t)steps * MPC_DRIVE_REC, hipMemcpyDeviceToHost, s));
+  MPC_HIP_CHECK(hipMemcpyAsync(status, d_st, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
+  if (iters) MPC_HIP_CHECK(hipMemcpyAsync(iters, d_it, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
+  MPC_HIP_CHECK(hipStreamSynchronize(s));
+  return MPC_OK;
+}
+
+extern "C" int mpc_drive_info(const MpcHandle *h, int64_t *out2) {
+  if (!h || !out2) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
+  out2[0] = h->n_drive_fused; out2[1] = h->n_drive_stepwise;
   return MPC_OK;
 }
 

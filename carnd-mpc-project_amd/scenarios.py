@@ -231,5 +231,22 @@ def model_rows(params, B):
     return np.ascontiguousarray(np.tile(col[:, None], (1, int(B))))
 
 
+def track_starts(B, params, waypoints, seed=DEFAULT_SEED):
+    """Start cars for the drive loop (BatchedMPC.drive_torch): B cars on the track -- on a random segment, on its centre line --
+    heading along it, at 20-60 mph (capped at 0.95 of the parameter set's max_speed), wheels straight, and the throttle that holds
+    the speed under the plant's own acceleration rule, (throttle - v / 50) * 6 = 0.  -> car [6, B] float64, the rows of `tel`:
+    x, y, psi [rad], speed [mph], steering_angle, throttle."""
+    wp = np.asarray(waypoints, dtype=np.float64)
+    g = _rng(seed, 7)
+    k = g.integers(0, len(wp), B)
+    frac = g.uniform(0.0, 1.0, B)
+    mph = np.minimum(g.uniform(20.0, 60.0, B), 0.95 * params.max_speed * 3600.0 / 1609.34)
+    a, b = wp[k], wp[(k + 1) % len(wp)]
+    seg = b - a
+    v = mph * 1609.34 / 3600.0
+    return np.ascontiguousarray(np.stack([a[:, 0] + frac * seg[:, 0], a[:, 1] + frac * seg[:, 1], np.arctan2(seg[:, 1], seg[:, 0]), mph,
+                                          np.zeros(B), v / 50.0]))
+
+
 def golden_dir():
     return os.path.join(_abi.ROOT, "tests", "golden")

@@ -313,6 +313,60 @@ class BatchedMPC:
             self._call("mpc_rollout_batch_device", head, outs, m, (opts,) if warm_start else None, horizon=hz)
         return res
 
+    # -- track driving (include/mpc_amd_drive.h) --------------------------------
+    def drive_opts(self, **overrides):
+        """This handle's MpcDriveOpts defaults (mpc_drive_opts_default), with keyword overrides."""
+        return _abi.drive_opts_default(self.params, **overrides)
+
+    def drive_torch(self, car, track_x, track_y, steps, weights=None, opts=None, warm_opts=None, want_hist=True, fused=False, stream=None):
+        """Drive B cars along a cyclic track for `steps` telemetry messages on the device (mpc_drive_batch_device): per message the
+        waypoint window at the car's position, the telemetry handler (cold, or warm with opts.warm_start) and the plant -- the
+        reference's own kinematic model, not the simulator.  car [6, B] = x, y, psi, speed [mph], steering_angle, throttle is advanced
+        in place; track_x / track_y [n] float64 CUDA tensors; weights [12, B] or None; opts: an MpcDriveOpts (None: drive_opts()).
+        Returns a dict of tensors: "car" (the same tensor), "summary" [8, B] (rows _abi.DRIVE_SUM_*), "hist" [steps, 13, B] (rows
+        _abi.DRIVE_REC_*) or None, "status" (worst), "iters" (summed).  ``fused``: the same drive in one launch, every car advancing on
+        its own (mpc_drive_batch_device_fused; bitwise the same results, drive_info() tells whether the one launch or the stepwise loop
+        ran)."""
+        import torch
+        B = car.shape[1]
+        dev = car.device
+        n = int(track_x.shape[0])
+        for name, t, shape in (("car", car, (6, B)), ("track_x", track_x, (n,)), ("track_y", track_y, (n,)), ("weights", weights, (_abi.NW, B))):
+            if t is not None and (t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape):
+                raise ValueError("%s must be a contiguous float64 CUDA tensor of shape %s" % (name, shape))
+        res = {"car": car, "summary": torch.empty((_abi.DRIVE_NSUM, B), dtype=torch.float64, device=dev),
+               "hist": torch.empty((steps, _abi.DRIVE_REC, B), dtype=torch.float64, device=dev) if want_hist else None,
+               "status": torch.empty((B,), dtype=torch.int32, device=dev), "iters": torch.empty((B,), dtype=torch.int32, device=dev)}
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        name = "mpc_drive_batch_device_fused" if fused else "mpc_drive_batch_device"
+        check(getattr(library(), name)(self._h, B, B, int(steps), car.data_ptr(), track_x.data_ptr(), track_y.data_ptr(), n,
+                                               weights.data_ptr() if weights is not None else None,
+                                               C.byref(opts) if opts is not None else None, C.byref(warm_opts) if warm_opts is not None else None,
+                                               res["summary"].data_ptr(), res["hist"].data_ptr() if want_hist else None,
+                                               res["status"].data_ptr(), res["iters"].data_ptr(), C.c_void_p(s.cuda_stream)),
+              name)
+        return res
+
+    def drive_numpy(self, car, track_x, track_y, steps, weights=None, opts=None, warm_opts=None, want_hist=True):
+        """drive_torch for host arrays (mpc_drive_batch_host): one copy in, the loop, one copy out; synchronises.  `car` is copied:
+        the cars after the last step are "car" of the result."""
+        f = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64)) if a is not None else None
+        car, tx, ty, weights = f(car).copy(), f(track_x), f(track_y), f(weights)
+        B, n = car.shape[1], tx.shape[0]
+        assert car.shape == (6, B) and ty.shape == (n,) and (weights is None or weights.shape == (_abi.NW, B))
+        res = {"car": car, "summary": np.empty((_abi.DRIVE_NSUM, B)), "hist": np.empty((steps, _abi.DRIVE_REC, B)) if want_hist else None,
+               "status": np.empty(B, dtype=np.int32), "iters": np.empty(B, dtype=np.int32)}
+        p = lambda a: a.ctypes.data if a is not None else None
+        check(library().mpc_drive_batch_host(self._h, B, B, int(steps), p(car), p(tx), p(ty), n, p(weights),
+                                             C.byref(opts) if opts is not None else None, C.byref(warm_opts) if warm_opts is not None else None,
+                                             p(res["summary"]), p(res["hist"]), p(res["status"]), p(res["iters"])), "mpc_drive_batch_host")
+        return res
+
+    def drive_info(self):
+        a = (C.c_int64 * 2)()
+        check(library().mpc_drive_info(self._h, a), "mpc_drive_info")
+        return {"fused_launches": int(a[0]), "stepwise_loops": int(a[1])}
+
     # -- host path (numpy arrays; copies through PCIe) ------------------------
     def solve_numpy(self, state, coeffs, yaw_lo, yaw_hi, weights=None, want_traj=False, model=None, horizon=None, traj_out=None):
         """Host arrays through mpc_solve_batch_host (float64), or mpc_solve_batch_host_f32 for an MPC_PRECISION_F32 handle.

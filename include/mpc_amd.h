@@ -541,6 +541,12 @@ int mpc_rollout_batch_device_fused_model(MpcHandle *h, int64_t B, int64_t ld, in
  * lane per instance; nothing is solved and nothing else changes.  The section and its declarations live in a header of their own,
  * which this one includes: */
 #include "mpc_amd_certify.h"
+/* ---- track driving: window, handler and plant on the device, `steps` messages in one call --------------------------------------
+ * The mpc_drive_* entry points drive B cars along a cyclic track of waypoints: per message the waypoint window at the car's position,
+ * the telemetry handler of this header (cold or warm, optionally with per-instance weights) and the reference's own kinematic model
+ * as the plant, with a summary per car and, if asked for, a record per step.  Nothing returns to the host between the steps.  The
+ * section and its declarations live in a header of their own, which this one includes: */
+#include "mpc_amd_drive.h"
 /* ---- per-instance model values on the run() path: a fleet of different vehicles behind one handler ----------------------------
  * Each entry point is the one of the same name without `_model` plus `model`, [MPC_NMODEL][ld] doubles addressed with the call's
  * ld (rows MPC_MODEL_*), directly behind `ptsy`; the wire forms further down take it as [MPC_NMODEL][B] directly behind

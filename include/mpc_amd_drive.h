@@ -1,0 +1,94 @@
+/*
+ * mpc_amd_drive.h -- track driving on the device.  Part of include/mpc_amd.h, which includes it (do not include it on its own): the
+ * mpc_drive_* entry points and everything a caller needs to know about them.
+ */
+#ifndef MPC_AMD_DRIVE_H
+#define MPC_AMD_DRIVE_H
+#ifndef MPC_AMD_H
+#error "include mpc_amd.h"
+#endif
+
+/* ---- track driving: waypoint window, telemetry handler and plant, `steps` times, in one call -------------------------------------
+ * Does this configuration get the car round the track, and how well?  A call drives B cars for `steps` telemetry messages.  Per
+ * message and car: pick the waypoint window at the car's position, run the telemetry handler on (car, window, extra_latency) -- the
+ * very call mpc_telemetry_batch_device makes, or its _warm form -- and move the car under the command it was sent, late.  Nothing
+ * returns to the host between the steps and nothing is synchronised.
+ *
+ * THE PLANT IS NOT THE UNITY SIMULATOR.  It is the reference's own model of it: the kinematic step the reference uses to compensate
+ * its latency (Vehicle::move, src/model/Vehicle.cpp:145-168) with the handler's own reading of the telemetry (the sign of the steering
+ * angle, src/mpc_main.cpp:131; the acceleration (throttle - v / 50) * 6, src/mpc_main.cpp:156).  A lap under this plant says how the
+ * controller does in the world it believes in; it says nothing about tyres, drag or the simulator's actuator dynamics.
+ *
+ * A car: six doubles, the rows of car [6][ld] = the rows of `tel` of the telemetry entry points --
+ *   0, 1, 2  x, y, psi [rad]      3  speed [mph]      4  steering_angle [rad, simulator sign]      5  throttle
+ *   Rows 4 and 5 are the command in force.  In: the cars at the first message; out: the cars after the last plant step.
+ * A track: track_x [n_track], track_y [n_track], device doubles, cyclic, npts <= n_track <= MPC_DRIVE_MAX_TRACK.
+ * Window.  j = the waypoint with the smallest dx * dx + dy * dy (ties: the lowest index; a distance that is not a number never
+ *   wins, so j = 0 for a car whose position is not finite); k = j if (p - w_j) . (w_{j+1} - w_j) > 0, else j - 1; the window is
+ *   w[k .. k + npts - 1], cyclically, k in 0 .. n_track - 1.  The search has n_track trips: no data decides a branch around a loop.
+ * Handler.  mpc_telemetry_batch_device on (car, window, extra_latency), or with warm_start != 0 mpc_telemetry_batch_device_warm (the
+ *   run()-path rule: records unshifted by default, psi projected into the new box; step 1 is cold, a car whose previous step did not
+ *   succeed starts cold).  The warm buffer lives in the handle, as for mpc_rollout_batch_device_warm.  One addition: weights
+ *   [MPC_NW][ld], or NULL, is passed to every solve as mpc_solve_batch_device takes it.  Small batches go through the wave kernels
+ *   exactly as the telemetry entry point does.
+ * Plant.  sub_old substeps of length h under rows 4 / 5; then rows 4 / 5 become (cmd_steer * max_steering, cmd_throttle) -- if either
+ *   is not finite the old command stays in force --; then sub_new substeps.  One substep: v = speed * 1609.34 / 3600,
+ *   steer = -steering_angle, accel = (throttle - v / 50) * 6 (recomputed every substep), Vehicle::move(h), speed back to mph.  psi is
+ *   not normalised: the handler does that.
+ * summary [MPC_DRIVE_NSUM][ld], accumulated in step order:
+ *   0 max |cte0|   1 sum cte0^2   2 max |epsi0|   3 sum of speed [mph] at message times   4 min speed   5 progress in waypoints
+ *   (sum of the signed cyclic difference of k)   6 first step with |cte0| > cte_limit, or -1   7 steps whose status is not SUCCESS
+ *   (cte0, epsi0: rows 4 and 5 of the state run() hands to the solve; a not-a-number never wins a maximum or minimum)
+ * hist [steps][MPC_DRIVE_REC][ld] or NULL, per step and car, as doubles:
+ *   0..5 the car at message time   6, 7 cmd   8, 9 cte0, epsi0   10, 11 status, iterations   12 k
+ * status [ld]: worst (largest) code over the steps; iters [ld] or NULL: iterations summed -- the conventions of the rollouts.
+ * Containment: what the telemetry entry points owe a car no caller should send (not-a-number, a negative speed, a position far from
+ *   the track) holds at every step: a status, a launch that ends, and every other car bit for bit as in a batch without it.
+ *
+ * mpc_drive_opts_default needs no device: npts 6, h 0.01, sub_old = round(latency_ms / 10), sub_new = 2 if latency_ms is non-zero and
+ *   10 otherwise, warm_start 0, extra_latency 0, cte_limit 3.  opts = NULL: these defaults for the handle's parameters; warm_opts = NULL:
+ *   those of mpc_warm_opts_default (read only with warm_start).
+ * Refusals.  MPC_ERR_INVALID with a message: a wrong `size`, steps < 1, npts outside 3..8, n_track outside npts..MPC_DRIVE_MAX_TRACK, a
+ *   sub count below 0, sub_old + sub_new outside 1..1000, h not finite or <= 0, ld < B, a NULL among car / track / summary / status,
+ *   an MPC_PRECISION_F32 handle.  warm_start with max_soc > 0: MPC_ERR_UNSUPPORTED, as for every warm call.
+ * mpc_drive_batch_device enqueues steps x (window kernel, the handler's three launches, plant-and-summary kernel) on `stream`: every
+ *   step lasts as long as its slowest car.
+ * mpc_drive_batch_device_fused: the same arguments, ONE launch: a lane keeps its car for all `steps` messages and starts the next
+ *   message as soon as its own is done.  Every array the call writes (car, summary, hist, status, iters) holds BITWISE what the stepwise
+ *   call writes.  The one launch serves the handles and sizes of mpc_rollout_batch_device_fused -- a single-phase fp64 lane-kernel
+ *   solve (no fp32 start), max_soc = 0, B above the wave limit; everywhere else the call runs the stepwise loop itself.
+ * mpc_drive_batch_host: the stepwise loop for host arrays (track included), on the handle's own device and stream; synchronises.
+ * mpc_drive_info: out2[0] = calls so far that ran the one launch, out2[1] = calls that ran the stepwise loop. */
+#define MPC_DRIVE_MAX_TRACK 4096
+#define MPC_DRIVE_NSUM 8
+#define MPC_DRIVE_REC 13
+enum { MPC_DRIVE_SUM_MAX_CTE = 0, MPC_DRIVE_SUM_CTE2, MPC_DRIVE_SUM_MAX_EPSI, MPC_DRIVE_SUM_SPEED, MPC_DRIVE_SUM_MIN_SPEED,
+       MPC_DRIVE_SUM_PROGRESS, MPC_DRIVE_SUM_FIRST_OFF, MPC_DRIVE_SUM_FAILED };
+enum { MPC_DRIVE_REC_CAR = 0, MPC_DRIVE_REC_CMD = 6, MPC_DRIVE_REC_CTE = 8, MPC_DRIVE_REC_EPSI = 9, MPC_DRIVE_REC_STATUS = 10,
+       MPC_DRIVE_REC_ITERS = 11, MPC_DRIVE_REC_K = 12 };
+
+typedef struct MpcDriveOpts {
+  int32_t size;            /* sizeof(MpcDriveOpts) */
+  int32_t npts;            /* waypoints per window, 3..8 */
+  int32_t sub_old;         /* plant substeps under the command in force before the reply takes effect */
+  int32_t sub_new;         /* ... and under the reply */
+  int32_t warm_start;      /* 0: every step cold; else the _warm handler from step 2 on */
+  int32_t reserved;
+  double h;                /* length of a plant substep [s] */
+  double extra_latency;    /* as for mpc_telemetry_batch_device */
+  double cte_limit;        /* summary row 6 */
+} MpcDriveOpts;
+
+int mpc_drive_opts_default(const MpcParams *p, MpcDriveOpts *o);
+int mpc_drive_batch_device(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                           int n_track, const double *weights, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary,
+                           double *hist, int32_t *status, int32_t *iters, void *stream);
+int mpc_drive_batch_device_fused(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                                 int n_track, const double *weights, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary,
+                                 double *hist, int32_t *status, int32_t *iters, void *stream);
+int mpc_drive_batch_host(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                         int n_track, const double *weights, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary,
+                         double *hist, int32_t *status, int32_t *iters);
+int mpc_drive_info(const MpcHandle *h, int64_t *out2);
+
+#endif /* MPC_AMD_DRIVE_H */

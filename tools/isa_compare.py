@@ -32,14 +32,15 @@ def demangle(names):
 
 
 def key(name):
-    """the demangled name without what only the newer build has: mpc_solve_kernel is known by its first eight template arguments (a
-    ninth, `false`, is the newer build's; its last parameter's type spells the same arguments out again)"""
+    """the demangled name without what only the newer build has: mpc_solve_kernel is known by its first eight template arguments
+    (further ones that are `false` -- HORIZON, DRIVE -- are a newer build's; its last parameter's type spells the same arguments out
+    again)"""
     m = re.search(r"mpc_solve_kernel<([^()]*?)>\(", name)
     if not m:
         return name
     args = m.group(1).split(", ")
-    if len(args) == 9 and args[8] == "false":
-        args = args[:8]
+    while len(args) > 8 and args[-1] == "false":
+        args.pop()
     return "mpc_solve_kernel<%s>" % ", ".join(args)
 
 
