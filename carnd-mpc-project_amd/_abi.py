@@ -114,7 +114,8 @@ CERT_CONVERGED, CERT_ACCEPTABLE, CERT_NOT_CONVERGED, CERT_NOT_A_POINT, CERT_NO_P
 CERT_VERDICT_NAMES = {0: "converged", 1: "acceptable", 2: "not_converged", 3: "not_a_point", 4: "no_problem"}
 
 # ... and include/mpc_amd_drive.h (track driving; tests/test_drive.py)
-DRIVE_EXPORTS = ["mpc_drive_opts_default", "mpc_drive_batch_device", "mpc_drive_batch_device_fused", "mpc_drive_batch_host", "mpc_drive_info"]
+DRIVE_EXPORTS = ["mpc_drive_opts_default", "mpc_drive_batch_device", "mpc_drive_batch_device_fused", "mpc_drive_batch_host", "mpc_drive_info",
+                 "mpc_drive_batch_device_model", "mpc_drive_batch_device_fused_model", "mpc_drive_batch_host_model"]
 DRIVE_MAX_TRACK, DRIVE_NSUM, DRIVE_REC = 4096, 8, 13      # MPC_DRIVE_MAX_TRACK, rows of summary [NSUM][ld], rows of a step of hist [REC][ld]
 (DRIVE_SUM_MAX_CTE, DRIVE_SUM_CTE2, DRIVE_SUM_MAX_EPSI, DRIVE_SUM_SPEED, DRIVE_SUM_MIN_SPEED, DRIVE_SUM_PROGRESS, DRIVE_SUM_FIRST_OFF,
  DRIVE_SUM_FAILED) = range(DRIVE_NSUM)
@@ -217,6 +218,10 @@ def library():
     L.mpc_drive_batch_host.argtypes = H + [C.c_int] + [DP] * 3 + [C.c_int, DP, C.POINTER(MpcDriveOpts), OPTS] + [DP] * 4
     L.mpc_drive_batch_device.argtypes = L.mpc_drive_batch_host.argtypes + [C.c_void_p]
     L.mpc_drive_batch_device_fused.argtypes = L.mpc_drive_batch_device.argtypes
+    # ... and their _model forms: `model` (one pointer) directly behind `weights`
+    drive_head = H + [C.c_int] + [DP] * 3 + [C.c_int, DP]
+    for name in ("mpc_drive_batch_host", "mpc_drive_batch_device", "mpc_drive_batch_device_fused"):
+        getattr(L, name + "_model").argtypes = drive_head + [DP] + getattr(L, name).argtypes[len(drive_head):]
     L.mpc_drive_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.mpc_solve_batch_device_f32.argtypes = L.mpc_solve_batch_device.argtypes      # (the same pointers, to floats)
     L.mpc_solve_batch_host_f32.argtypes = L.mpc_solve_batch_host.argtypes

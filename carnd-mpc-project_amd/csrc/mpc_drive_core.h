@@ -56,10 +56,15 @@ MPC_HD int drive_progress(int k, int k_prev, int n) {
   return d;
 }
 
+/* Where the plant reads Lf and max_steering: `m`, the template argument of mpc_run_core.h's functions (run_model_of) -- the handle's
+ * MpcParams itself (the entry points without `model`: their callers pass P twice) or the car's mpc::ModelVals (the mpc_drive_*_model
+ * entry points; a column that cannot be used has become the handle's values there, model_vals_of). */
 /* One plant substep of length h on car = {x, y, psi, speed [mph], steering_angle, throttle}: the handler's reading of the message
  * (MpH2MpS mpc_main.cpp:129, the sign :131, the acceleration :156 -- from the speed of this substep), Vehicle::move(h)
  * (Vehicle.cpp:145-168; the clamp at :156 is overwritten at :167), the speed back to mph (MpS2MpH, utils.h:19-21) */
-MPC_HD void drive_substep(const MpcParams &P, double *car, double h) {
+template <class MV>
+MPC_HD void drive_substep(const MpcParams &P, const MV &m_, double *car, double h) {
+  const MV &m = run_model_of(P, m_);
   const double v = car[3] * 1609.34 / 3600.0;
   const double steer = -car[4];
   const double accel = (car[5] - v / 50.0) * 6.0;
@@ -68,19 +73,24 @@ MPC_HD void drive_substep(const MpcParams &P, double *car, double h) {
   fsincos(car[2], &sn, &cs);
   car[0] = car[0] + dist * cs;
   car[1] = car[1] + dist * sn;
-  car[2] = car[2] + steer * dist / P.Lf;
+  car[2] = car[2] + steer * dist / m.Lf;
   car[3] = (v + accel * h) * 3600.0 / 1609.34;
 }
 
 /* The plant between two messages: sub_old substeps under the command in force (rows 4 / 5), then the reply takes effect --
  * (cmd_steer * max_steering, cmd_throttle); a reply that is not finite leaves the old command in force --, then sub_new substeps.
  * psi is not normalised: the handler does that. */
+template <class MV>
+MPC_HD void drive_plant(const MpcParams &P, const MV &m_, double *car, double cmd_steer, double cmd_throttle, int sub_old, int sub_new, double h) {
+  const MV &m = run_model_of(P, m_);
+  MPC_STAGE_LOOP
+  for (int s = 0; s < sub_old; s++) drive_substep(P, m, car, h);
+  if (drive_finite(cmd_steer) && drive_finite(cmd_throttle)) { car[4] = cmd_steer * m.max_steering; car[5] = cmd_throttle; }
+  MPC_STAGE_LOOP
+  for (int s = 0; s < sub_new; s++) drive_substep(P, m, car, h);
+}
 MPC_HD void drive_plant(const MpcParams &P, double *car, double cmd_steer, double cmd_throttle, int sub_old, int sub_new, double h) {
-  MPC_STAGE_LOOP
-  for (int s = 0; s < sub_old; s++) drive_substep(P, car, h);
-  if (drive_finite(cmd_steer) && drive_finite(cmd_throttle)) { car[4] = cmd_steer * P.max_steering; car[5] = cmd_throttle; }
-  MPC_STAGE_LOOP
-  for (int s = 0; s < sub_new; s++) drive_substep(P, car, h);
+  drive_plant(P, P, car, cmd_steer, cmd_throttle, sub_old, sub_new, h);
 }
 
 /* The summary rows of one car (MPC_DRIVE_SUM_*), step `step` (0-based) folded in; dk = the progress of this step (0 at step 0).
@@ -104,8 +114,10 @@ MPC_HD void drive_summary(int step, double *sum, double cte0, double epsi0, doub
 /* ---- one car of a batch between the handler's reply and the next message, as the plant-and-summary kernel and the CPU build run it:
  * car [6][ld] in / out, cmd [2][ld], pre [RUN_PRE_ROWS][ldp] (the handler's own rows: cte0, epsi0), the step's status and iterations,
  * the window index of this step and of the one before; summary [MPC_DRIVE_NSUM][ld], rec = this step's block of hist
- * [MPC_DRIVE_REC][ld] or nullptr, status / iters (or nullptr) per car: worst code, summed iterations (mpc::RolloutCar). */
-MPC_HD void drive_step_instance(const MpcParams &P, const MpcDriveOpts &O, int64_t i, int64_t ld, int step, int n_track, double *car,
+ * [MPC_DRIVE_REC][ld] or nullptr, status / iters (or nullptr) per car: worst code, summed iterations (mpc::RolloutCar).  m: the plant's
+ * model values, as above. */
+template <class MV>
+MPC_HD void drive_step_instance(const MpcParams &P, const MV &m, const MpcDriveOpts &O, int64_t i, int64_t ld, int step, int n_track, double *car,
                                 const double *cmd, const double *pre, int64_t ldp, int32_t st_step, int32_t it_step, int k, int k_prev,
                                 double *summary, double *rec, int32_t *status, int32_t *iters) {
   double c[6], sum[MPC_DRIVE_NSUM] = {};
@@ -135,9 +147,14 @@ MPC_HD void drive_step_instance(const MpcParams &P, const MpcDriveOpts &O, int64
     if (step > 0) total = iters[i];
     iters[i] = RolloutCar::sum_iters(step, total, it_step);
   }
-  drive_plant(P, c, cs, ct, O.sub_old, O.sub_new, O.h);
+  drive_plant(P, m, c, cs, ct, O.sub_old, O.sub_new, O.h);
   MPC_UNROLL
   for (int q = 0; q < 6; q++) car[q * ld + i] = c[q];
+}
+MPC_HD void drive_step_instance(const MpcParams &P, const MpcDriveOpts &O, int64_t i, int64_t ld, int step, int n_track, double *car,
+                                const double *cmd, const double *pre, int64_t ldp, int32_t st_step, int32_t it_step, int k, int k_prev,
+                                double *summary, double *rec, int32_t *status, int32_t *iters) {
+  drive_step_instance(P, P, O, i, ld, step, n_track, car, cmd, pre, ldp, st_step, it_step, k, k_prev, summary, rec, status, iters);
 }
 
 }  // namespace mpc

@@ -233,7 +233,10 @@ struct MpcHorizonPart {
  * step the post-solve half (mpc::run_post_instance) and plant, summary and record (mpc::drive_step_instance).  The solve reads its
  * state, coefficients and psi box from the rows of `pre` this lane has just written, so none of these pointers is const or
  * __restrict__, and the kernel's own state / coeffs / yaw_lo / yaw_hi arguments are not dereferenced in these builds.  steps, status
- * and iters are the roll part's; the kernel's ld is the stride of pre and of the weights, ldo the caller's leading dimension. */
+ * and iters are the roll part's; the kernel's ld is the stride of pre and of the weights, ldo the caller's leading dimension.
+ * With MODEL (mpc_drive_batch_device_fused_model): the car's column of T.model -- the caller's array, rows T.ld_model = ldo apart -- is
+ * read by instance index at the take (the pre-solve half, set-up) and again at the hand-over (unpack, the post-solve half, the plant);
+ * it is not carried across the sweeps. */
 struct MpcDrivePart {
   MpcDriveOpts O;
   double *car;                    /* [6][ldo] in / out */
@@ -355,15 +358,23 @@ template <class RIO, class R> struct OutRef {
 
 /* The column argument of Solver::setup / unpack for instance i in the build at hand (mpc::NoColumn, ModelColumn, HorizonColumn).
  * The only place that knows where the model values lie: a rollout's columns are the caller's, rows ld apart like its inputs; a
- * solve's have T.ld_model (MpcModelPart). */
-template <bool ROLL, bool MODEL, bool HORIZON, class Phase>
+ * solve's have T.ld_model (MpcModelPart), and so have a drive's (its ld is the stride of the handle's rows, the columns stay the
+ * caller's). */
+template <bool ROLL, bool MODEL, bool HORIZON, bool DRIVE = false, class Phase>
 __device__ __forceinline__ auto instance_column(const Phase &T, int64_t ld, int64_t i) {
   if constexpr (MODEL) {
     int64_t lm = ld;
-    if constexpr (!ROLL) lm = T.ld_model;
+    if constexpr (!ROLL || DRIVE) lm = T.ld_model;
     if constexpr (HORIZON) return mpc::HorizonColumn{T.model ? T.model + i : nullptr, lm, T.horizon[i]};
     else return mpc::ModelColumn{T.model + i, lm};
   } else return mpc::NoColumn{};
+}
+/* ... and the same column as the values mpc_run_core.h and mpc_drive_core.h read (DRIVE builds): the handle's MpcParams itself without
+ * MODEL, so that those builds read every field from P where it is used */
+template <bool MODEL, class Phase>
+__device__ __forceinline__ decltype(auto) drive_model_vals(const MpcParams &P, const Phase &T, int64_t i) {
+  if constexpr (MODEL) return mpc::model_vals_of(P, T.model, T.ld_model, i);
+  else return (P);
 }
 
 /* Instance i, which this lane has taken as far as the phase goes, is appended to the list of the next phase: its index, this lane's
@@ -413,7 +424,7 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
     const int64_t tile_reals,
     const MpcPhaseOf<ROLL, WARM, MODEL, HORIZON, DRIVE> T) {
   extern __shared__ double smem[];
-  static_assert(!DRIVE || (ROLL && !MODEL && !HORIZON && !SOC), "track driving: a ROLL build without MODEL, HORIZON and SOC");
+  static_assert(!DRIVE || (ROLL && !HORIZON && !SOC), "track driving: a ROLL build without HORIZON and SOC");
   static_assert(!HORIZON || (MODEL && !STAGING && !SOC), "per-instance horizon: a MODEL build without staging and SOC");
   static_assert(!WARM || (sizeof(R) == 8 && std::is_same<R, RIO>::value && std::is_same<R, RSRC>::value && !SOC), "warm start: the plain fp64 solve only");
   static_assert(!ROLL || (sizeof(R) == 8 && std::is_same<R, RIO>::value && std::is_same<R, RSRC>::value && !SOC), "fused rollout: the plain fp64 solve only");
@@ -487,14 +498,17 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
               double *o = T.out9 + i;
               const int64_t l = ldo;
               const R ylo = (R)T.pre[mpc::RUN_PRE_YAW_LO * ld + i], yhi = (R)T.pre[mpc::RUN_PRE_YAW_HI * ld + i];
-              S.unpack(mpc::NoColumn{}, [o, l](int q) { return OutRef<RIO, R>{o + q * l}; }, [](int) { return OutRef<RIO, R>{nullptr}; }, false, ylo, yhi);
+              S.unpack(instance_column<ROLL, MODEL, HORIZON, DRIVE>(T, ld, i), [o, l](int q) { return OutRef<RIO, R>{o + q * l}; },
+                       [](int) { return OutRef<RIO, R>{nullptr}; }, false, ylo, yhi);
               if constexpr (WARM) {
                 double *wo = T.warm_out + i;
                 const int64_t lw = T.ld_warm;
                 S.warm_store([wo, lw](int k, int f, R v) { wo[(int64_t)(k * MPC_WARM_REC + f) * lw] = v; });
               }
-              mpc::run_post_instance(P, P, i, T.pre, ld, T.out9, ldo, (double *)nullptr, T.cmd, ldo);
-              mpc::drive_step_instance(P, T.O, i, ldo, step, T.n_track, T.car, T.cmd, T.pre, ld, fin_status, S.iters + it_total, drive_k, drive_k_prev,
+              /* (MODEL: the car's column, read again here -- it is not carried across the sweeps) */
+              const auto &mv = drive_model_vals<MODEL>(P, T, i);
+              mpc::run_post_instance(P, mv, i, T.pre, ld, T.out9, ldo, (double *)nullptr, T.cmd, ldo);
+              mpc::drive_step_instance(P, mv, T.O, i, ldo, step, T.n_track, T.car, T.cmd, T.pre, ld, fin_status, S.iters + it_total, drive_k, drive_k_prev,
                                        T.summary, T.rec ? T.rec + (int64_t)step * MPC_DRIVE_REC * ldo : nullptr, T.status, T.iters);
             } else {
             double *o = T.hist + (int64_t)step * T.hist_step + i;
@@ -575,7 +589,7 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
               drive_k_prev = drive_k;
               drive_k = mpc::drive_window(T.track_x, T.track_y, T.n_track, T.car[i], T.car[ldo + i]);
               mpc::drive_window_points(T.track_x, T.track_y, T.n_track, drive_k, T.O.npts, T.ptsx, T.ptsy, ldo, i);
-              (void)mpc::run_pre_instance<true>(P, P, i, ldo, T.O.npts, T.car, T.O.extra_latency, T.ptsx, T.ptsy, T.pre, ld);
+              (void)mpc::run_pre_instance<true>(P, drive_model_vals<MODEL>(P, T, i), i, ldo, T.O.npts, T.car, T.O.extra_latency, T.ptsx, T.ptsy, T.pre, ld);
               mpc::gather_instance(P, i, ld, T.pre + mpc::RUN_PRE_STATE * ld, T.pre + mpc::RUN_PRE_COEFFS * ld, weights, st, cf, w);
               ylo_in = (R)T.pre[mpc::RUN_PRE_YAW_LO * ld + i]; yhi_in = (R)T.pre[mpc::RUN_PRE_YAW_HI * ld + i];
             } else {
@@ -589,7 +603,7 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
             bool warm = false, warm_cand = false;   /* WARM: this instance has a valid column in warm_in / starts from it */
             if constexpr (WARM && ROLL) warm_cand = again_warm;   /* (the column this lane stored when it finished the step before) */
             else if constexpr (WARM) warm_cand = T.warm_in != nullptr && (T.warm_status == nullptr || T.warm_status[i] == MPC_STATUS_SUCCESS);
-            const int s0 = S.setup(instance_column<ROLL, MODEL, HORIZON>(T, ld, i), st, cf, ylo, yhi, w, (!T.resume || from_scratch) && !warm_cand);
+            const int s0 = S.setup(instance_column<ROLL, MODEL, HORIZON, DRIVE>(T, ld, i), st, cf, ylo, yhi, w, (!T.resume || from_scratch) && !warm_cand);
             if constexpr (WARM) {
               if (warm_cand) {
                 if (s0 == MPC_STATUS_SUCCESS) {
@@ -1096,7 +1110,22 @@ __global__ __launch_bounds__(256) void mpc_drive_plant_kernel(const MpcParams P,
                                                               double *__restrict__ rec, int32_t *__restrict__ status, int32_t *__restrict__ iters) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B) return;
-  mpc::drive_step_instance(P, O, i, ld, step, n_track, car, cmd, pre, ldp, st_step[i], it_step[i], k_now[i], k_prev[i], summary, rec, status, iters);
+  mpc::drive_step_instance(P, P, O, i, ld, step, n_track, car, cmd, pre, ldp, st_step[i], it_step[i], k_now[i], k_prev[i], summary, rec, status, iters);
+}
+/* ... its MODEL build (the mpc_drive_*_model entry points): one more argument, and the lane reads its car's column of it once -- Lf in
+ * the heading update, max_steering in turning the reply into the steering angle in force.  A column that cannot be used: the handle's
+ * values (mpc::model_vals_of); the handler has reported the car INFEASIBLE. */
+__global__ __launch_bounds__(256) void mpc_drive_plant_model_kernel(const MpcParams P, const MpcDriveOpts O, int64_t B, int64_t ld, int step, int n_track,
+                                                                    double *__restrict__ car, const double *__restrict__ cmd,
+                                                                    const double *__restrict__ pre, int64_t ldp, const int32_t *__restrict__ st_step,
+                                                                    const int32_t *__restrict__ it_step, const int32_t *k_now,
+                                                                    const int32_t *k_prev, double *__restrict__ summary,
+                                                                    double *__restrict__ rec, int32_t *__restrict__ status, int32_t *__restrict__ iters,
+                                                                    const MpcModelPart W) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B) return;
+  mpc::drive_step_instance(P, mpc::model_vals_of(P, W.model, W.ld_model, i), O, i, ld, step, n_track, car, cmd, pre, ldp, st_step[i], it_step[i], k_now[i],
+                           k_prev[i], summary, rec, status, iters);
 }
 
 /* The certificate of a stored point (mpc_certify_batch_*), one instance per lane: mpc::certify_batch_instance of mpc_core.h.  A lane
@@ -2912,7 +2941,8 @@ static int drive_rows(MpcHandle *h, int64_t B, int64_t ld, bool warm, const doub
 
 /* The stepwise loop: `steps` x (sense kernel, the telemetry handler -- run_impl with tel, the weights and an iterations pointer --,
  * plant-and-summary kernel) on the caller's stream; no host synchronisation.  x.warm: every step after the first is the _warm handler
- * on the handle's own buffer, in place (rollout_impl's arrangement). */
+ * on the handle's own buffer, in place (rollout_impl's arrangement).  x.model (device, [MPC_NMODEL][ld]): the handler is the
+ * telemetry _model call -- run_impl reads the columns where the caller has them -- and the plant kernel its MODEL build. */
 static int drive_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y, int n_track,
                       const double *weights, const MpcDriveOpts &O, CallExtras x, double *summary, double *hist, int32_t *status,
                       int32_t *iters, void *stream_) {
@@ -2932,33 +2962,58 @@ static int drive_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *ca
     MPC_HIP_CHECK(hipGetLastError());
     x.w = WarmIO{t == 0 ? nullptr : h->d_warm, h->d_rstat, h->d_warm, S, x.w.wopts, 0};
     MPC_TRY(run_impl(h, B, ld, O.npts, car, true, O.extra_latency, ptsx, ptsy, nullptr, cmd, nullptr, h->d_rstat, h->d_iters, nullptr, stream_, x));
-    hipLaunchKernelGGL(mpc_drive_plant_kernel, dim3(grid), dim3(256), 0, s, h->params, O, B, ld, t, n_track, car, cmd, h->d_run, S, h->d_rstat,
-                       h->d_iters, k_now, k_prev, summary, hist ? hist + (int64_t)t * MPC_DRIVE_REC * ld : nullptr, status, iters);
+    double *rec = hist ? hist + (int64_t)t * MPC_DRIVE_REC * ld : nullptr;
+    if (x.model)
+      hipLaunchKernelGGL(mpc_drive_plant_model_kernel, dim3(grid), dim3(256), 0, s, h->params, O, B, ld, t, n_track, car, cmd, h->d_run, S, h->d_rstat,
+                         h->d_iters, k_now, k_prev, summary, rec, status, iters, MpcModelPart{x.model, ld});
+    else
+      hipLaunchKernelGGL(mpc_drive_plant_kernel, dim3(grid), dim3(256), 0, s, h->params, O, B, ld, t, n_track, car, cmd, h->d_run, S, h->d_rstat,
+                         h->d_iters, k_now, k_prev, summary, rec, status, iters);
     MPC_HIP_CHECK(hipGetLastError());
   }
   ++h->n_drive_stepwise;
   return record_stats(h, B, status, iters, s);   /* as the rollouts: worst status per car, iterations summed over the steps */
 }
 
+/* What every drive entry point does first: with `model`, the model rule (which handles a model call is accepted on, call_extras);
+ * drive_args; then the call's extras -- the warm refusals and the options in effect. */
+static int drive_call(const MpcHandle *h, int64_t B, int64_t ld, int steps, const double *car, const double *track_x, const double *track_y,
+                      int n_track, const double *model, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, const double *summary,
+                      const int32_t *status, MpcDriveOpts *O, CallExtras *x) {
+  if (h && model) MPC_TRY(call_extras(h, model).refused);
+  MPC_TRY(drive_args(h, B, ld, steps, car, track_x, track_y, n_track, opts, summary, status, O));
+  *x = call_extras(h, model, O->warm_start != 0, nullptr, nullptr, nullptr, 0, warm_opts);
+  return x->refused;
+}
+
+extern "C" int mpc_drive_batch_device_model(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
+                                            const double *track_y, int n_track, const double *weights, const double *model,
+                                            const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist,
+                                            int32_t *status, int32_t *iters, void *stream_) {
+  MpcDriveOpts O;
+  CallExtras x;
+  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, opts, warm_opts, summary, status, &O, &x));
+  if (B == 0) { h->last_B = 0; return MPC_OK; }
+  return drive_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
+}
 extern "C" int mpc_drive_batch_device(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
                                       int n_track, const double *weights, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts,
                                       double *summary, double *hist, int32_t *status, int32_t *iters, void *stream_) {
-  MpcDriveOpts O;
-  MPC_TRY(drive_args(h, B, ld, steps, car, track_x, track_y, n_track, opts, summary, status, &O));
-  const CallExtras x = call_extras(h, nullptr, O.warm_start != 0, nullptr, nullptr, nullptr, 0, warm_opts);
-  MPC_TRY(x.refused);
-  if (B == 0) { h->last_B = 0; return MPC_OK; }
-  return drive_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
+  return mpc_drive_batch_device_model(h, B, ld, steps, car, track_x, track_y, n_track, weights, nullptr, opts, warm_opts, summary, hist, status, iters,
+                                      stream_);
 }
 
 /* The loop in one launch: the DRIVE build of the lane kernel (see mpc_solve_kernel and MpcDrivePart), a lane per car for all `steps`
  * messages.  rollout_fused_impl's rule decides: the one launch runs where the stepwise loop would launch exactly the single-phase fp64
- * lane kernel at every step (no fp32 start, no SOC, B above the wave limit); everywhere else the call IS the stepwise loop. */
+ * lane kernel at every step (no fp32 start, no SOC, B above the wave limit); everywhere else the call IS the stepwise loop.
+ * x.model: the DRIVE x MODEL builds, where the stepwise model loop launches the lane kernel's MODEL build at every step -- the same
+ * rule, but on a handle whose ordinary solve starts in fp32 as well: a model solve is the single-phase fp64 launch on h->ws there. */
 static int drive_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y, int n_track,
                             const double *weights, const MpcDriveOpts &O, const CallExtras &x, double *summary, double *hist, int32_t *status,
                             int32_t *iters, void *stream_) {
   const bool wave_path = h->wave_max_batch > 0 && B <= h->wave_max_batch;
-  if (h->mixed || h->params.max_soc > 0 || wave_path)
+  const double *model = x.model;
+  if ((h->mixed && !model) || h->params.max_soc > 0 || wave_path)
     return drive_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
   MPC_TRY(check_batch(h, B, ld));
   if (h->params.n_yaw_change_speeds < 1 || h->params.n_steer_speeds < 1) { g_last_error = "run(): empty speed tables (load a config-*.json)"; return MPC_ERR_INVALID; }
@@ -2991,9 +3046,11 @@ static int drive_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, doub
   const unsigned grid = (unsigned)((B + kBlock - 1) / kBlock);
   MPC_TRY(with_bool(h->staging, [&](auto staging) {
     return with_bool(x.warm, [&](auto warm_build) {
-      constexpr bool STAGING = decltype(staging)::value, WARM = decltype(warm_build)::value;
-      return launch_kernel(mpc_solve_kernel<STAGING, double, double, double, false, WARM, true, false, false, true>, grid, STAGING ? staging_lds_bytes<double>() : 0,
-                           s, h, io, (double *)h->ws, h->ws_stride, phase_of<true, WARM, false, false, true>(T, wc, roll, {}, {}, drive));
+      return with_bool(model != nullptr, [&](auto model_build) {
+        constexpr bool STAGING = decltype(staging)::value, WARM = decltype(warm_build)::value, MODEL = decltype(model_build)::value;
+        return launch_kernel(mpc_solve_kernel<STAGING, double, double, double, false, WARM, true, MODEL, false, true>, grid, STAGING ? staging_lds_bytes<double>() : 0,
+                             s, h, io, (double *)h->ws, h->ws_stride, phase_of<true, WARM, MODEL, false, true>(T, wc, roll, {model, ld}, {}, drive));
+      });
     });
   }));
   MPC_TRY(solve_end(h, io, s, rec, tp, false));
@@ -3001,38 +3058,47 @@ static int drive_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, doub
   return record_stats(h, B, status, iters, s);
 }
 
-extern "C" int mpc_drive_batch_device_fused(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
-                                            int n_track, const double *weights, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts,
-                                            double *summary, double *hist, int32_t *status, int32_t *iters, void *stream_) {
+extern "C" int mpc_drive_batch_device_fused_model(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
+                                                  const double *track_y, int n_track, const double *weights, const double *model,
+                                                  const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist,
+                                                  int32_t *status, int32_t *iters, void *stream_) {
   MpcDriveOpts O;
-  MPC_TRY(drive_args(h, B, ld, steps, car, track_x, track_y, n_track, opts, summary, status, &O));
-  const CallExtras x = call_extras(h, nullptr, O.warm_start != 0, nullptr, nullptr, nullptr, 0, warm_opts);
-  MPC_TRY(x.refused);
+  CallExtras x;
+  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, opts, warm_opts, summary, status, &O, &x));
   if (B == 0) { h->last_B = 0; return MPC_OK; }
   return drive_fused_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
 }
+extern "C" int mpc_drive_batch_device_fused(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                                            int n_track, const double *weights, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts,
+                                            double *summary, double *hist, int32_t *status, int32_t *iters, void *stream_) {
+  return mpc_drive_batch_device_fused_model(h, B, ld, steps, car, track_x, track_y, n_track, weights, nullptr, opts, warm_opts, summary, hist, status,
+                                            iters, stream_);
+}
 
 /* The same for host arrays: one copy in, the loop on the handle's own device and stream, one copy out; synchronises.  Staging kept on
- * the handle and grown on demand, like the telemetry handler's. */
-extern "C" int mpc_drive_batch_host(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
-                                    int n_track, const double *weights, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts,
-                                    double *summary, double *hist, int32_t *status, int32_t *iters) {
+ * the handle and grown on demand, like the telemetry handler's.  model (host, [MPC_NMODEL][ld]) is copied in with the other inputs. */
+extern "C" int mpc_drive_batch_host_model(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                                          int n_track, const double *weights, const double *model, const MpcDriveOpts *opts,
+                                          const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status, int32_t *iters) {
   MpcDriveOpts O;
-  MPC_TRY(drive_args(h, B, ld, steps, car, track_x, track_y, n_track, opts, summary, status, &O));
-  const CallExtras x = call_extras(h, nullptr, O.warm_start != 0, nullptr, nullptr, nullptr, 0, warm_opts);
-  MPC_TRY(x.refused);
+  CallExtras x;
+  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, opts, warm_opts, summary, status, &O, &x));
   if (B == 0) { h->last_B = 0; return MPC_OK; }
   MPC_ON_DEVICE(h);
   const int64_t L = (B + 7) / 8 * 8;
-  const int64_t rows = 6 + MPC_DRIVE_NSUM + (weights ? MPC_NW : 0) + (hist ? (int64_t)steps * MPC_DRIVE_REC : 0);
+  const int64_t rows = 6 + MPC_DRIVE_NSUM + (weights ? MPC_NW : 0) + (hist ? (int64_t)steps * MPC_DRIVE_REC : 0) + (model ? MPC_NMODEL : 0);
   MPC_TRY(grow_dev(&h->d_drive_host, &h->drive_host_bytes, sizeof(double) * (size_t)(rows * L + 2 * n_track) + sizeof(int32_t) * (size_t)(2 * L)));
   double *d = h->d_drive_host;
   double *d_car = d, *d_sum = d_car + 6 * L, *d_w = d_sum + MPC_DRIVE_NSUM * L, *d_hist = d_w + (weights ? MPC_NW * L : 0);
-  double *d_tx = d_hist + (hist ? (int64_t)steps * MPC_DRIVE_REC * L : 0), *d_ty = d_tx + n_track;
+  double *d_model = d_hist + (hist ? (int64_t)steps * MPC_DRIVE_REC * L : 0), *d_tx = d_model + (model ? MPC_NMODEL * L : 0), *d_ty = d_tx + n_track;
   int32_t *d_st = (int32_t *)(d_ty + n_track), *d_it = d_st + L;
   hipStream_t s = h->stream;
   MPC_HIP_CHECK(hipMemcpy2DAsync(d_car, sizeof(double) * L, car, sizeof(double) * ld, sizeof(double) * B, 6, hipMemcpyHostToDevice, s));
   if (weights) MPC_HIP_CHECK(hipMemcpy2DAsync(d_w, sizeof(double) * L, weights, sizeof(double) * ld, sizeof(double) * B, MPC_NW, hipMemcpyHostToDevice, s));
+  if (model) {
+    MPC_HIP_CHECK(hipMemcpy2DAsync(d_model, sizeof(double) * L, model, sizeof(double) * ld, sizeof(double) * B, MPC_NMODEL, hipMemcpyHostToDevice, s));
+    x.model = d_model;
+  }
   MPC_HIP_CHECK(hipMemcpyAsync(d_tx, track_x, sizeof(double) * n_track, hipMemcpyHostToDevice, s));
   MPC_HIP_CHECK(hipMemcpyAsync(d_ty, track_y, sizeof(double) * n_track, hipMemcpyHostToDevice, s));
   MPC_TRY(drive_impl(h, B, L, steps, d_car, d_tx, d_ty, n_track, weights ? d_w : nullptr, O, x, d_sum, hist ? d_hist : nullptr, d_st, d_it, (void *)s));
@@ -3043,6 +3109,11 @@ extern "C" int mpc_drive_batch_host(MpcHandle *h, int64_t B, int64_t ld, int ste
   if (iters) MPC_HIP_CHECK(hipMemcpyAsync(iters, d_it, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipStreamSynchronize(s));
   return MPC_OK;
+}
+extern "C" int mpc_drive_batch_host(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                                    int n_track, const double *weights, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts,
+                                    double *summary, double *hist, int32_t *status, int32_t *iters) {
+  return mpc_drive_batch_host_model(h, B, ld, steps, car, track_x, track_y, n_track, weights, nullptr, opts, warm_opts, summary, hist, status, iters);
 }
 
 extern "C" int mpc_drive_info(const MpcHandle *h, int64_t *out2) {

@@ -318,7 +318,8 @@ class BatchedMPC:
         """This handle's MpcDriveOpts defaults (mpc_drive_opts_default), with keyword overrides."""
         return _abi.drive_opts_default(self.params, **overrides)
 
-    def drive_torch(self, car, track_x, track_y, steps, weights=None, opts=None, warm_opts=None, want_hist=True, fused=False, stream=None):
+    def drive_torch(self, car, track_x, track_y, steps, weights=None, opts=None, warm_opts=None, want_hist=True, fused=False, stream=None,
+                    model=None):
         """Drive B cars along a cyclic track for `steps` telemetry messages on the device (mpc_drive_batch_device): per message the
         waypoint window at the car's position, the telemetry handler (cold, or warm with opts.warm_start) and the plant -- the
         reference's own kinematic model, not the simulator.  car [6, B] = x, y, psi, speed [mph], steering_angle, throttle is advanced
@@ -326,9 +327,13 @@ class BatchedMPC:
         Returns a dict of tensors: "car" (the same tensor), "summary" [8, B] (rows _abi.DRIVE_SUM_*), "hist" [steps, 13, B] (rows
         _abi.DRIVE_REC_*) or None, "status" (worst), "iters" (summed).  ``fused``: the same drive in one launch, every car advancing on
         its own (mpc_drive_batch_device_fused; bitwise the same results, drive_info() tells whether the one launch or the stepwise loop
-        ran)."""
+        ran).  ``model`` [6, B] float64 as in telemetry_torch (mpc_drive_batch_device_model, _fused_model; fp64 handles): every car's own
+        dt, Lf and limits, in the handler and in the plant (Lf in the heading update, max_steering in the steering angle in force) --
+        one call answers "how fast can this tuning go round the track" with a row of max_speed values."""
         import torch
         B = car.shape[1]
+        if model is not None:
+            self._check_model(model, B)
         dev = car.device
         n = int(track_x.shape[0])
         for name, t, shape in (("car", car, (6, B)), ("track_x", track_x, (n,)), ("track_y", track_y, (n,)), ("weights", weights, (_abi.NW, B))):
@@ -338,28 +343,34 @@ class BatchedMPC:
                "hist": torch.empty((steps, _abi.DRIVE_REC, B), dtype=torch.float64, device=dev) if want_hist else None,
                "status": torch.empty((B,), dtype=torch.int32, device=dev), "iters": torch.empty((B,), dtype=torch.int32, device=dev)}
         s = stream if stream is not None else torch.cuda.current_stream(dev)
-        name = "mpc_drive_batch_device_fused" if fused else "mpc_drive_batch_device"
+        name = ("mpc_drive_batch_device_fused" if fused else "mpc_drive_batch_device") + ("_model" if model is not None else "")
         check(getattr(library(), name)(self._h, B, B, int(steps), car.data_ptr(), track_x.data_ptr(), track_y.data_ptr(), n,
                                                weights.data_ptr() if weights is not None else None,
+                                               *((model.data_ptr(),) if model is not None else ()),
                                                C.byref(opts) if opts is not None else None, C.byref(warm_opts) if warm_opts is not None else None,
                                                res["summary"].data_ptr(), res["hist"].data_ptr() if want_hist else None,
                                                res["status"].data_ptr(), res["iters"].data_ptr(), C.c_void_p(s.cuda_stream)),
               name)
         return res
 
-    def drive_numpy(self, car, track_x, track_y, steps, weights=None, opts=None, warm_opts=None, want_hist=True):
+    def drive_numpy(self, car, track_x, track_y, steps, weights=None, opts=None, warm_opts=None, want_hist=True, model=None):
         """drive_torch for host arrays (mpc_drive_batch_host): one copy in, the loop, one copy out; synchronises.  `car` is copied:
-        the cars after the last step are "car" of the result."""
+        the cars after the last step are "car" of the result.  ``model`` [6, B]: as in drive_torch (mpc_drive_batch_host_model)."""
         f = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64)) if a is not None else None
         car, tx, ty, weights = f(car).copy(), f(track_x), f(track_y), f(weights)
         B, n = car.shape[1], tx.shape[0]
         assert car.shape == (6, B) and ty.shape == (n,) and (weights is None or weights.shape == (_abi.NW, B))
+        if model is not None:
+            model = f(model)
+            if model.shape != (_abi.NMODEL, B):
+                raise ValueError("model must have shape (%d, B)" % _abi.NMODEL)
         res = {"car": car, "summary": np.empty((_abi.DRIVE_NSUM, B)), "hist": np.empty((steps, _abi.DRIVE_REC, B)) if want_hist else None,
                "status": np.empty(B, dtype=np.int32), "iters": np.empty(B, dtype=np.int32)}
         p = lambda a: a.ctypes.data if a is not None else None
-        check(library().mpc_drive_batch_host(self._h, B, B, int(steps), p(car), p(tx), p(ty), n, p(weights),
-                                             C.byref(opts) if opts is not None else None, C.byref(warm_opts) if warm_opts is not None else None,
-                                             p(res["summary"]), p(res["hist"]), p(res["status"]), p(res["iters"])), "mpc_drive_batch_host")
+        name = "mpc_drive_batch_host" + ("_model" if model is not None else "")
+        check(getattr(library(), name)(self._h, B, B, int(steps), p(car), p(tx), p(ty), n, p(weights), *((p(model),) if model is not None else ()),
+                                       C.byref(opts) if opts is not None else None, C.byref(warm_opts) if warm_opts is not None else None,
+                                       p(res["summary"]), p(res["hist"]), p(res["status"]), p(res["iters"])), name)
         return res
 
     def drive_info(self):

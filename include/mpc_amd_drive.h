@@ -58,7 +58,35 @@
  *   call writes.  The one launch serves the handles and sizes of mpc_rollout_batch_device_fused -- a single-phase fp64 lane-kernel
  *   solve (no fp32 start), max_soc = 0, B above the wave limit; everywhere else the call runs the stepwise loop itself.
  * mpc_drive_batch_host: the stepwise loop for host arrays (track included), on the handle's own device and stream; synchronises.
- * mpc_drive_info: out2[0] = calls so far that ran the one launch, out2[1] = calls that ran the stepwise loop. */
+ * mpc_drive_info: out2[0] = calls so far that ran the one launch, out2[1] = calls that ran the stepwise loop.
+ *
+ * ---- per-car model values: mpc_drive_*_model ---------------------------------------------------------------------------------------
+ * How fast can this tuning go round the track, and which limits make it leave the road?  One call, one car per value.  Each _model
+ * form is the one without plus `model` directly behind `weights` (the rule of mpc_amd.h for _model forms): [MPC_NMODEL][ld] doubles
+ * addressed with the call's ld, rows MPC_MODEL_* (dt, Lf, max_steering, max_acceleration, max_deceleration, max_speed); the host form
+ * takes a host array and copies it in with the other inputs.
+ * model == NULL: the call IS the entry point without _model -- bitwise, with all of its conventions, dispatch and refusals.
+ * model != NULL: car i is driven with its own column in three places.
+ *   Handler: the call mpc_telemetry_batch_device_model makes (or, with warm_start, mpc_telemetry_batch_device_warm_model) on (car,
+ *     window, extra_latency, model), plus `weights`: the six values in the solve, max_speed in the cap of the speed tables and the
+ *     throttle's `keep` term, max_steering in the normalisation of the reply, Lf in the latency compensation, the two acceleration
+ *     limits in computeThrottle; warm: a record is judged against the car's own relaxed box.  Dispatch is the handler's: the wave
+ *     kernel's MODEL build up to wave_max_batch, the lane kernel's MODEL build above it, the same bits from both.
+ *   Plant, both uses: psi += steer * dist / Lf_i, and the reply takes effect as (cmd_steer * max_steering_i, cmd_throttle) -- cmd_steer
+ *     was normalised by that same max_steering_i, so the angle in force is the angle the solve chose.
+ *   Unchanged: the window rule, the summary and record rows, the status and iteration conventions, MpcDriveOpts.  sub_old, sub_new and h
+ *     stay the call's: there is no per-car latency or substep count, and no _horizon form (the run() path has none).
+ * A column that cannot be used (the _model rule: a value that is not finite, dt <= 0, Lf <= 0, max_steering <= 0, max_speed <= 0,
+ *   max_acceleration <= 0, max_deceleration >= 0): the handle's values take its place in the handler's pre- and post-processing and in
+ *   the plant, every step of that car ends MPC_STATUS_INFEASIBLE, car / summary / hist hold no not-a-number because of it, and every
+ *   other car is bit for bit what it is in a batch without the defect.  The same holds for a car faster than its own relaxed speed limit.
+ * Handles: the model rule -- every fp64 handle, also one whose ordinary solve starts in fp32 (served on its fp64 workspace, bitwise a
+ *   handle created with f64_f32_start = 0).  An MPC_PRECISION_F32 handle: MPC_ERR_INVALID (per-instance model values: fp64 handles
+ *   only), checked first; then every refusal above, unchanged.  warm_start with max_soc > 0: MPC_ERR_UNSUPPORTED.
+ * mpc_drive_batch_device_fused_model writes BITWISE what mpc_drive_batch_device_model writes.  It runs the one launch where the
+ *   stepwise model loop would launch the lane kernel's MODEL build at every step -- B above the wave limit (wave_max_batch < 0: every
+ *   B), max_soc = 0 -- on every fp64 handle: one more case than the form without _model serves, because a model solve is never the
+ *   two-launch fp32-start solve.  Everywhere else it runs the stepwise loop itself; mpc_drive_info counts both kinds. */
 #define MPC_DRIVE_MAX_TRACK 4096
 #define MPC_DRIVE_NSUM 8
 #define MPC_DRIVE_REC 13
@@ -89,6 +117,16 @@ int mpc_drive_batch_device_fused(MpcHandle *h, int64_t B, int64_t ld, int steps,
 int mpc_drive_batch_host(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
                          int n_track, const double *weights, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary,
                          double *hist, int32_t *status, int32_t *iters);
+int mpc_drive_batch_device_model(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                                 int n_track, const double *weights, const double *model, const MpcDriveOpts *opts,
+                                 const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status, int32_t *iters, void *stream);
+int mpc_drive_batch_device_fused_model(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
+                                       const double *track_y, int n_track, const double *weights, const double *model,
+                                       const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status,
+                                       int32_t *iters, void *stream);
+int mpc_drive_batch_host_model(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                               int n_track, const double *weights, const double *model, const MpcDriveOpts *opts,
+                               const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status, int32_t *iters);
 int mpc_drive_info(const MpcHandle *h, int64_t *out2);
 
 #endif /* MPC_AMD_DRIVE_H */

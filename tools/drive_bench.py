@@ -10,7 +10,15 @@ telemetry messages, config-fast, cold and warm,
 
 Each figure is the median of --reps runs after --warmup runs, timed
 between two events on the stream; the iteration counts of the stepwise run's records say what the slowest car of a step costs.
-Writes --out (default profiles/drive.json); needs an MI355X."""
+Writes --out (default profiles/drive.json); needs an MI355X.
+
+--model: the mpc_drive_*_model entry points instead (default --out profiles/drive_model.json) --
+  model      the stepwise and the one-launch form with every column the handle's own values (scenarios.model_rows), cold and warm,
+  no_model   the same calls without `model` in the same process, and whether the two wrote the same bits (--parent FILE: the rows a
+             run of this tool on the parent commit wrote in the same session are copied in beside them),
+  sweep      one drive with real variation: --speeds values of max_speed x --cars cars in ONE warm one-launch call of --sweep-steps
+             messages, every value on the same starts -- per value: how many cars leave the road (summary row "first step off the
+             road"), when, how fast they went and how far they got."""
 import argparse
 import json
 import os
@@ -33,8 +41,14 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="config-fast.json")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "drive.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--model", action="store_true", help="measure the _model entry points and run the top-speed sweep")
+    ap.add_argument("--parent", default=None, help="--model: a file this tool wrote on the parent commit in the same session")
+    ap.add_argument("--speeds", type=int, default=16)
+    ap.add_argument("--cars", type=int, default=4096)
+    ap.add_argument("--sweep-steps", type=int, default=300)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "drive_model.json" if a.model else "drive.json")
     import torch
     assert torch.cuda.is_available(), "this benchmark needs a GPU"
     pkg = G.load_package()
@@ -60,6 +74,8 @@ def main():
             if rep >= a.warmup:
                 ms.append(e0.elapsed_time(e1))
         return ms, out
+    if a.model:
+        return model_rows(a, pkg, params, wp, t, timed, car0, d_car0, d_tx, d_ty)
     for warm in (0, 1):
         with pkg.BatchedMPC(params, B, device=0) as mpc:
             opts = mpc.drive_opts(warm_start=warm)
@@ -105,6 +121,64 @@ def main():
             print(json.dumps(rows[-1]), flush=True)
     doc = {"tool": "tools/drive_bench.py", "config": a.config, "device": torch.cuda.get_device_name(0), "timing": "median of reps runs after warmup runs, between two events",
            "rows": rows}
+    json.dump(doc, open(a.out, "w"), indent=1)
+    print("wrote", a.out)
+
+
+def model_rows(a, pkg, params, wp, t, timed, car0, d_car0, d_tx, d_ty):
+    import torch
+    B, steps = a.batch, a.steps
+    rows = []
+    bits = lambda x: x.view(torch.int64) if x.dtype == torch.float64 else x
+    same = lambda p, q: all(torch.equal(bits(p[k]), bits(q[k])) for k in ("car", "summary", "hist", "status", "iters"))
+    d_model = t(pkg.scenarios.model_rows(params, B))
+    for warm in (0, 1):
+        with pkg.BatchedMPC(params, B, device=0) as mpc:
+            opts = mpc.drive_opts(warm_start=warm)
+            got = {}
+            for what, model in (("no_model", None), ("model", d_model)):
+                for form, fused in (("fused", True), ("stepwise", False)):
+                    ms, res = timed(lambda: mpc.drive_torch(d_car0.clone(), d_tx, d_ty, steps, opts=opts, fused=fused, model=model))
+                    got[what, form] = res
+                    it = res["hist"][:, 11]
+                    rows.append({"what": what, "form": form, "warm_start": warm, "B": B, "steps": steps, "ms_median": float(np.median(ms)),
+                                 "ms_min": float(min(ms)), "ms_max": float(max(ms)), "reps": a.reps, "warmup": a.warmup,
+                                 "solves_per_s": B * steps / (1e-3 * float(np.median(ms))), "iters_per_solve": float(it.mean()),
+                                 "non_success_solves": int((res["hist"][:, 10] != 0).sum())})
+                    print(json.dumps(rows[-1]), flush=True)
+            rows.append({"what": "bits", "warm_start": warm, "model_fused_equals_model_stepwise": bool(same(got["model", "fused"], got["model", "stepwise"])),
+                         "uniform_model_equals_no_model": bool(same(got["model", "stepwise"], got["no_model", "stepwise"])), "drive_info": mpc.drive_info()})
+            print(json.dumps(rows[-1]), flush=True)
+    # the sweep: every value of max_speed on the same starts, in one call; a start is no faster than 0.9 x the car's own limit
+    n_v, n_c = a.speeds, a.cars
+    mph = np.linspace(40.0, params.max_speed * 3600.0 / 1609.34, n_v)
+    cars = np.tile(pkg.scenarios.track_starts(n_c, params, wp, seed=123), (1, n_v))
+    model = pkg.scenarios.model_rows(params, n_v * n_c)
+    model[5] = np.repeat(mph * 1609.34 / 3600.0, n_c)
+    cars[3] = np.minimum(cars[3], 0.9 * np.repeat(mph, n_c))
+    sweep = []
+    with pkg.BatchedMPC(params, n_v * n_c, device=0) as mpc:
+        opts = mpc.drive_opts(warm_start=1)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        res = mpc.drive_torch(t(cars), d_tx, d_ty, a.sweep_steps, opts=opts, fused=True, want_hist=False, model=t(model))
+        e1.record()
+        torch.cuda.synchronize()
+        summ, st = res["summary"].cpu().numpy().reshape(8, n_v, n_c), res["status"].cpu().numpy().reshape(n_v, n_c)
+        for q in range(n_v):
+            off = summ[6, q]
+            sweep.append({"max_speed_mph": float(mph[q]), "cars": n_c, "cars_off_the_road": int((off >= 0).sum()),
+                          "first_step_off_the_road_min_median": [float(off[off >= 0].min()), float(np.median(off[off >= 0]))] if (off >= 0).any() else None,
+                          "mean_speed_mph": float(summ[3, q].mean() / a.sweep_steps), "max_abs_cte_p50_p99_max": [float(np.quantile(summ[0, q], v)) for v in (0.5, 0.99, 1.0)],
+                          "progress_waypoints_mean": float(summ[5, q].mean()), "cars_with_a_failed_step": int((summ[7, q] > 0).sum()),
+                          "worst_status_counts": np.bincount(st[q], minlength=6).tolist()})
+            print(json.dumps(sweep[-1]), flush=True)
+        sweep_doc = {"values": n_v, "cars_per_value": n_c, "steps": a.sweep_steps, "call": "mpc_drive_batch_device_fused_model, warm_start = 1, hist = NULL",
+                     "cte_limit": opts.cte_limit, "ms": float(e0.elapsed_time(e1)), "drive_info": mpc.drive_info(), "rows": sweep}
+    doc = {"tool": "tools/drive_bench.py --model", "config": a.config, "device": torch.cuda.get_device_name(0),
+           "timing": "median of reps runs after warmup runs, between two events", "rows": rows, "sweep": sweep_doc}
+    if a.parent:
+        doc["parent_commit_rows_same_session"] = json.load(open(a.parent))["rows"]
     json.dump(doc, open(a.out, "w"), indent=1)
     print("wrote", a.out)
 
