@@ -115,7 +115,11 @@ CERT_VERDICT_NAMES = {0: "converged", 1: "acceptable", 2: "not_converged", 3: "n
 
 # ... and include/mpc_amd_drive.h (track driving; tests/test_drive.py)
 DRIVE_EXPORTS = ["mpc_drive_opts_default", "mpc_drive_batch_device", "mpc_drive_batch_device_fused", "mpc_drive_batch_host", "mpc_drive_info",
-                 "mpc_drive_batch_device_model", "mpc_drive_batch_device_fused_model", "mpc_drive_batch_host_model"]
+                 "mpc_drive_batch_device_model", "mpc_drive_batch_device_fused_model", "mpc_drive_batch_host_model",
+                 "mpc_drive_batch_device_latency", "mpc_drive_batch_device_fused_latency", "mpc_drive_batch_host_latency",
+                 "mpc_telemetry_batch_device_latency", "mpc_telemetry_batch_host_latency"]
+NLATENCY = 3     # MPC_NLATENCY: rows of a latency array, [NLATENCY][ld] (the mpc_drive_*_latency entry points)
+LATENCY_COMP, LATENCY_SUB_OLD, LATENCY_SUB_NEW = range(NLATENCY)
 DRIVE_MAX_TRACK, DRIVE_NSUM, DRIVE_REC = 4096, 8, 13      # MPC_DRIVE_MAX_TRACK, rows of summary [NSUM][ld], rows of a step of hist [REC][ld]
 (DRIVE_SUM_MAX_CTE, DRIVE_SUM_CTE2, DRIVE_SUM_MAX_EPSI, DRIVE_SUM_SPEED, DRIVE_SUM_MIN_SPEED, DRIVE_SUM_PROGRESS, DRIVE_SUM_FIRST_OFF,
  DRIVE_SUM_FAILED) = range(DRIVE_NSUM)
@@ -222,6 +226,13 @@ def library():
     drive_head = H + [C.c_int] + [DP] * 3 + [C.c_int, DP]
     for name in ("mpc_drive_batch_host", "mpc_drive_batch_device", "mpc_drive_batch_device_fused"):
         getattr(L, name + "_model").argtypes = drive_head + [DP] + getattr(L, name).argtypes[len(drive_head):]
+    # ... and their _latency forms: `latency` (one pointer) directly behind `model`; the telemetry handler's: the _warm_model form plus
+    # `comp` (one pointer) directly behind extra_latency
+    for name in ("mpc_drive_batch_host", "mpc_drive_batch_device", "mpc_drive_batch_device_fused"):
+        getattr(L, name + "_latency").argtypes = drive_head + [DP, DP] + getattr(L, name).argtypes[len(drive_head):]
+    tel_head = H + [C.c_int, DP, C.c_double]
+    for name in ("mpc_telemetry_batch_device", "mpc_telemetry_batch_host"):
+        getattr(L, name + "_latency").argtypes = tel_head + [DP] + getattr(L, name + "_warm_model").argtypes[len(tel_head):]
     L.mpc_drive_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.mpc_solve_batch_device_f32.argtypes = L.mpc_solve_batch_device.argtypes      # (the same pointers, to floats)
     L.mpc_solve_batch_host_f32.argtypes = L.mpc_solve_batch_host.argtypes

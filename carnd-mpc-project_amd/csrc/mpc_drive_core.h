@@ -93,6 +93,24 @@ MPC_HD void drive_plant(const MpcParams &P, double *car, double cmd_steer, doubl
   drive_plant(P, P, car, cmd_steer, cmd_throttle, sub_old, sub_new, h);
 }
 
+/* Car i's column of latency [MPC_NLATENCY][ld] (the mpc_drive_*_latency entry points): the seconds its handler compensates for and its
+ * own substep counts, doubles holding integer values.  A column that cannot be used -- a value that is not finite, comp < 0, a count
+ * that is no integer or below 0, sub_old + sub_new outside 1..1000 -- : comp is not-a-number, which the handler turns into a status
+ * (mpc::run_comp_ok), and the counts are the call's.  The counts handed on are checked: 0 .. 1000, whatever the array holds. */
+struct DriveLatency {
+  double comp;
+  int sub_old, sub_new;
+};
+MPC_HD DriveLatency drive_latency_of(const MpcDriveOpts &O, const double *latency, int64_t ld, int64_t i) {
+  const double c = latency[MPC_LATENCY_COMP * ld + i], so = latency[MPC_LATENCY_SUB_OLD * ld + i], sn = latency[MPC_LATENCY_SUB_NEW * ld + i];
+  const bool ok = run_comp_usable(c) && so >= 0.0 && sn >= 0.0 && so + sn >= 1.0 && so + sn <= 1000.0 && so == rint(so) && sn == rint(sn);
+  DriveLatency L;
+  L.comp = ok ? c : NAN;
+  L.sub_old = ok ? (int)so : O.sub_old;
+  L.sub_new = ok ? (int)sn : O.sub_new;
+  return L;
+}
+
 /* The summary rows of one car (MPC_DRIVE_SUM_*), step `step` (0-based) folded in; dk = the progress of this step (0 at step 0).
  * A not-a-number never wins a maximum or the minimum. */
 MPC_HD void drive_summary(int step, double *sum, double cte0, double epsi0, double speed, int dk, int status, double cte_limit) {
@@ -113,12 +131,12 @@ MPC_HD void drive_summary(int step, double *sum, double cte0, double epsi0, doub
 
 /* ---- one car of a batch between the handler's reply and the next message, as the plant-and-summary kernel and the CPU build run it:
  * car [6][ld] in / out, cmd [2][ld], pre [RUN_PRE_ROWS][ldp] (the handler's own rows: cte0, epsi0), the step's status and iterations,
- * the window index of this step and of the one before; summary [MPC_DRIVE_NSUM][ld], rec = this step's block of hist
- * [MPC_DRIVE_REC][ld] or nullptr, status / iters (or nullptr) per car: worst code, summed iterations (mpc::RolloutCar).  m: the plant's
+ * the window index of this step and of the one before; sub_old / sub_new: the car's substep counts (the forms without: the call's);
+ * summary [MPC_DRIVE_NSUM][ld], rec = this step's block of hist [MPC_DRIVE_REC][ld] or nullptr, status / iters (or nullptr) per car: worst code, summed iterations (mpc::RolloutCar).  m: the plant's
  * model values, as above. */
 template <class MV>
-MPC_HD void drive_step_instance(const MpcParams &P, const MV &m, const MpcDriveOpts &O, int64_t i, int64_t ld, int step, int n_track, double *car,
-                                const double *cmd, const double *pre, int64_t ldp, int32_t st_step, int32_t it_step, int k, int k_prev,
+MPC_HD void drive_step_instance(const MpcParams &P, const MV &m, const MpcDriveOpts &O, int sub_old, int sub_new, int64_t i, int64_t ld, int step,
+                                int n_track, double *car, const double *cmd, const double *pre, int64_t ldp, int32_t st_step, int32_t it_step, int k, int k_prev,
                                 double *summary, double *rec, int32_t *status, int32_t *iters) {
   double c[6], sum[MPC_DRIVE_NSUM] = {};
   MPC_UNROLL
@@ -147,9 +165,15 @@ MPC_HD void drive_step_instance(const MpcParams &P, const MV &m, const MpcDriveO
     if (step > 0) total = iters[i];
     iters[i] = RolloutCar::sum_iters(step, total, it_step);
   }
-  drive_plant(P, m, c, cs, ct, O.sub_old, O.sub_new, O.h);
+  drive_plant(P, m, c, cs, ct, sub_old, sub_new, O.h);
   MPC_UNROLL
   for (int q = 0; q < 6; q++) car[q * ld + i] = c[q];
+}
+template <class MV>
+MPC_HD void drive_step_instance(const MpcParams &P, const MV &m, const MpcDriveOpts &O, int64_t i, int64_t ld, int step, int n_track, double *car,
+                                const double *cmd, const double *pre, int64_t ldp, int32_t st_step, int32_t it_step, int k, int k_prev,
+                                double *summary, double *rec, int32_t *status, int32_t *iters) {
+  drive_step_instance(P, m, O, O.sub_old, O.sub_new, i, ld, step, n_track, car, cmd, pre, ldp, st_step, it_step, k, k_prev, summary, rec, status, iters);
 }
 MPC_HD void drive_step_instance(const MpcParams &P, const MpcDriveOpts &O, int64_t i, int64_t ld, int step, int n_track, double *car,
                                 const double *cmd, const double *pre, int64_t ldp, int32_t st_step, int32_t it_step, int k, int k_prev,

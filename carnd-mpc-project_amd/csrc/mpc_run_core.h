@@ -234,17 +234,47 @@ MPC_HD void run_post(const MpcParams &P, double max_yaw_change, double target_sp
 /* tel = {x, y, psi (rad, any range: normalize_angle above says what becomes of it), speed (mph), steering_angle (simulator sign), previous throttle command};
  * extra = the handler's mean solve time added to Config::lookahead (mpc_main.cpp:158).
  * -> pose {x,y,psi,v,steering,acceleration} after latency compensation (Vehicle::update + Vehicle::move) */
-template <class MV>
-MPC_HD void telemetry_to_pose(const MpcParams &P, const MV &m_, const double *tel, double extra, double *pose) {
+/* How long the handler compensates for: `lc`, a template argument like `m` --
+ *   a double          the handle's rule (every entry point without per-instance latency: they are instruction for instruction what they
+ *                     were): Vehicle::move if P.latency_ms != 0, over P.lookahead + lc seconds (lc = the call's extra_latency);
+ *   RunComp{own, s}   own: this instance's own `s` seconds (the mpc_telemetry_*_latency / mpc_drive_*_latency entry points): Vehicle::move if
+ *                     s > 0, over s seconds -- s == 0 is the reference's `if (Config::latency)` not taken.  A value that cannot be used
+ *                     (not finite, below 0) moves nothing and takes the speed away, like a speedometer reading below zero: the instance
+ *                     ends with a status.  !own: the handle's rule with extra = s, decided at run time (the one-launch drive, whose
+ *                     array may be NULL). */
+struct RunComp {
+  bool own;
+  double s;
+};
+MPC_HD bool run_comp_usable(double s) { return s >= 0.0 && s < HUGE_VAL; }
+/* the three questions telemetry_to_pose asks: can the value be used, is there a move, over how many seconds */
+template <class LC>
+MPC_HD bool run_comp_ok(const LC &lc) {
+  if constexpr (std::is_same<LC, RunComp>::value) return !lc.own || run_comp_usable(lc.s);
+  else return true;
+}
+template <class LC>
+MPC_HD bool run_comp_on(const MpcParams &P, const LC &lc) {
+  if constexpr (std::is_same<LC, RunComp>::value) return lc.own ? (run_comp_usable(lc.s) && lc.s > 0.0) : P.latency_ms != 0;
+  else return P.latency_ms != 0;
+}
+template <class LC>
+MPC_HD double run_comp_seconds(const MpcParams &P, const LC &lc) {
+  if constexpr (std::is_same<LC, RunComp>::value) return lc.own ? lc.s : P.lookahead + lc.s;
+  else return P.lookahead + lc;
+}
+template <class MV, class LC>
+MPC_HD void telemetry_to_pose(const MpcParams &P, const MV &m_, const double *tel, const LC &lc, double *pose) {
   const MV &m = run_model_of(P, m_);
   const double psi = normalize_angle(tel[2]);            /* normalizeAngle, mpc_main.cpp:127 */
-  const double mph = tel[3] >= 0.0 ? tel[3] : NAN;       /* (a speedometer reading below zero is none: the instance ends with a status) */
+  /* (a speedometer reading below zero is none: the instance ends with a status -- and so does one whose compensation is no time span) */
+  const double mph = (tel[3] >= 0.0 && run_comp_ok(lc)) ? tel[3] : NAN;
   const double v = mph * 1609.34 / 3600.0;               /* MpH2MpS, :129 */
   const double steer = -tel[4];                          /* :131 */
   const double acc = (tel[5] - v / 50.0) * 6.0;          /* :156 */
   pose[0] = tel[0]; pose[1] = tel[1]; pose[2] = psi; pose[3] = v; pose[4] = steer; pose[5] = acc;
-  if (P.latency_ms != 0) {                               /* :157-159, Vehicle::move (Vehicle.cpp:145-168) */
-    const double dtm = P.lookahead + extra;
+  if (run_comp_on(P, lc)) {                              /* :157-159, Vehicle::move (Vehicle.cpp:145-168) */
+    const double dtm = run_comp_seconds(P, lc);
     const double dist = v * dtm;
     double sn, cs;
     fsincos(psi, &sn, &cs);
@@ -281,9 +311,10 @@ MPC_HD ModelVals model_vals_of(const MpcParams &P, const double *model, int64_t 
 }
 
 /* pose [6][ld] (TELEMETRY: the simulator's telemetry rows, latency compensation first, mpc_main.cpp:126-159) and the waypoints
- * ptsx / ptsy [npts][ld], which become the vehicle-frame ones in place -> pre [RUN_PRE_ROWS][ldp].  Returns the fit's coefficient count. */
-template <bool TELEMETRY, class MV>
-MPC_HD int run_pre_instance(const MpcParams &P, const MV &m, int64_t i, int64_t ld, int npts, const double *pose, double extra,
+ * ptsx / ptsy [npts][ld], which become the vehicle-frame ones in place -> pre [RUN_PRE_ROWS][ldp].  Returns the fit's coefficient count.
+ * extra: the call's extra_latency, or the instance's own RunComp. */
+template <bool TELEMETRY, class MV, class LC>
+MPC_HD int run_pre_instance(const MpcParams &P, const MV &m, int64_t i, int64_t ld, int npts, const double *pose, const LC &extra,
                             double *ptsx, double *ptsy, double *pre, int64_t ldp) {
   double po[6], px[RUN_MAX_PTS], py[RUN_MAX_PTS];
   MPC_UNROLL

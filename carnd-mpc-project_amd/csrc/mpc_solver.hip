@@ -236,7 +236,11 @@ struct MpcHorizonPart {
  * and iters are the roll part's; the kernel's ld is the stride of pre and of the weights, ldo the caller's leading dimension.
  * With MODEL (mpc_drive_batch_device_fused_model): the car's column of T.model -- the caller's array, rows T.ld_model = ldo apart -- is
  * read by instance index at the take (the pre-solve half, set-up) and again at the hand-over (unpack, the post-solve half, the plant);
- * it is not carried across the sweeps. */
+ * it is not carried across the sweeps.
+ * latency (mpc_drive_batch_device_fused_latency): the car's column of [MPC_NLATENCY][ldo], or nullptr -- the call's own extra_latency and
+ * substep counts, the very values the builds read before this pointer existed.  Read like the model column: by instance index at the
+ * take (what the pre-solve half compensates for) and again at the hand-over (the plant's counts), and not carried in between.  A
+ * pointer, not a template argument: the lane kernel has the builds it had. */
 struct MpcDrivePart {
   MpcDriveOpts O;
   double *car;                    /* [6][ldo] in / out */
@@ -246,6 +250,7 @@ struct MpcDrivePart {
   double *pre;                    /* [RUN_PRE_ROWS][ld]: the handle's rows */
   double *out9;                   /* [9][ldo]: the handle's rows */
   double *summary, *rec;          /* [MPC_DRIVE_NSUM][ldo]; hist [steps][MPC_DRIVE_REC][ldo] or nullptr */
+  const double *latency;          /* [MPC_NLATENCY][ldo] or nullptr */
 };
 
 template <bool ON, class Part> struct MpcPartIf : Part {};
@@ -508,7 +513,12 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
               /* (MODEL: the car's column, read again here -- it is not carried across the sweeps) */
               const auto &mv = drive_model_vals<MODEL>(P, T, i);
               mpc::run_post_instance(P, mv, i, T.pre, ld, T.out9, ldo, (double *)nullptr, T.cmd, ldo);
-              mpc::drive_step_instance(P, mv, T.O, i, ldo, step, T.n_track, T.car, T.cmd, T.pre, ld, fin_status, S.iters + it_total, drive_k, drive_k_prev,
+              int sub_old = T.O.sub_old, sub_new = T.O.sub_new;
+              if (T.latency) {
+                const mpc::DriveLatency dl = mpc::drive_latency_of(T.O, T.latency, ldo, i);
+                sub_old = dl.sub_old; sub_new = dl.sub_new;
+              }
+              mpc::drive_step_instance(P, mv, T.O, sub_old, sub_new, i, ldo, step, T.n_track, T.car, T.cmd, T.pre, ld, fin_status, S.iters + it_total, drive_k, drive_k_prev,
                                        T.summary, T.rec ? T.rec + (int64_t)step * MPC_DRIVE_REC * ldo : nullptr, T.status, T.iters);
             } else {
             double *o = T.hist + (int64_t)step * T.hist_step + i;
@@ -589,7 +599,9 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
               drive_k_prev = drive_k;
               drive_k = mpc::drive_window(T.track_x, T.track_y, T.n_track, T.car[i], T.car[ldo + i]);
               mpc::drive_window_points(T.track_x, T.track_y, T.n_track, drive_k, T.O.npts, T.ptsx, T.ptsy, ldo, i);
-              (void)mpc::run_pre_instance<true>(P, drive_model_vals<MODEL>(P, T, i), i, ldo, T.O.npts, T.car, T.O.extra_latency, T.ptsx, T.ptsy, T.pre, ld);
+              mpc::RunComp lc{false, T.O.extra_latency};
+              if (T.latency) lc = mpc::RunComp{true, mpc::drive_latency_of(T.O, T.latency, ldo, i).comp};
+              (void)mpc::run_pre_instance<true>(P, drive_model_vals<MODEL>(P, T, i), i, ldo, T.O.npts, T.car, lc, T.ptsx, T.ptsy, T.pre, ld);
               mpc::gather_instance(P, i, ld, T.pre + mpc::RUN_PRE_STATE * ld, T.pre + mpc::RUN_PRE_COEFFS * ld, weights, st, cf, w);
               ylo_in = (R)T.pre[mpc::RUN_PRE_YAW_LO * ld + i]; yhi_in = (R)T.pre[mpc::RUN_PRE_YAW_HI * ld + i];
             } else {
@@ -1058,6 +1070,23 @@ __global__ __launch_bounds__(256) void mpc_run_pre_kernel(const MpcParams P, int
   } else mpc::run_pre_instance<TELEMETRY>(P, P, i, ld, npts, pose, extra, ptsx, ptsy, pre, ldp);
 }
 
+/* ... the build of the telemetry handler with per-instance latency (mpc_telemetry_batch_*_latency): comp [ld], the seconds instance i
+ * compensates for (mpc::RunComp), read once per lane, coalesced like the rows of `pose` and under no condition. */
+template <bool MODEL, class... Model>
+__global__ __launch_bounds__(256) void mpc_run_pre_comp_kernel(const MpcParams P, int64_t B, int64_t ld, int npts,
+                                                               const double *__restrict__ pose, const double *__restrict__ comp,
+                                                               double *__restrict__ ptsx, double *__restrict__ ptsy, double *__restrict__ pre,
+                                                               int64_t ldp, const Model... model) {
+  static_assert(sizeof...(Model) == (MODEL ? 1 : 0), "the MODEL builds take one MpcModelPart");
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B) return;
+  const mpc::RunComp lc{true, comp[i]};
+  if constexpr (MODEL) {
+    const MpcModelPart &W = (model, ...);
+    mpc::run_pre_instance<true>(P, mpc::model_vals_of(P, W.model, W.ld_model, i), i, ld, npts, pose, lc, ptsx, ptsy, pre, ldp);
+  } else mpc::run_pre_instance<true>(P, P, i, ld, npts, pose, lc, ptsx, ptsy, pre, ldp);
+}
+
 template <bool MODEL, class... Model>
 __global__ __launch_bounds__(256) void mpc_run_post_kernel(const MpcParams P, int64_t B, const double *__restrict__ pre, int64_t ldp,
                                                            const double *__restrict__ out9, int64_t ld9, double *__restrict__ out8,
@@ -1126,6 +1155,37 @@ __global__ __launch_bounds__(256) void mpc_drive_plant_model_kernel(const MpcPar
   if (i >= B) return;
   mpc::drive_step_instance(P, mpc::model_vals_of(P, W.model, W.ld_model, i), O, i, ld, step, n_track, car, cmd, pre, ldp, st_step[i], it_step[i], k_now[i],
                            k_prev[i], summary, rec, status, iters);
+}
+
+/* ... and its builds with per-car latency (the mpc_drive_*_latency entry points): the lane reads its car's column of latency
+ * [MPC_NLATENCY][ld] once and moves the car with its own substep counts (mpc::drive_latency_of: checked, 0 .. 1000). */
+template <bool MODEL, class... Model>
+__global__ __launch_bounds__(256) void mpc_drive_plant_latency_kernel(const MpcParams P, const MpcDriveOpts O, int64_t B, int64_t ld, int step, int n_track,
+                                                                      double *__restrict__ car, const double *__restrict__ cmd,
+                                                                      const double *__restrict__ pre, int64_t ldp, const int32_t *__restrict__ st_step,
+                                                                      const int32_t *__restrict__ it_step, const int32_t *k_now,
+                                                                      const int32_t *k_prev, double *__restrict__ summary,
+                                                                      double *__restrict__ rec, int32_t *__restrict__ status, int32_t *__restrict__ iters,
+                                                                      const double *__restrict__ latency, const Model... model) {
+  static_assert(sizeof...(Model) == (MODEL ? 1 : 0), "the MODEL builds take one MpcModelPart");
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B) return;
+  const mpc::DriveLatency dl = mpc::drive_latency_of(O, latency, ld, i);
+  if constexpr (MODEL) {
+    const MpcModelPart &W = (model, ...);
+    mpc::drive_step_instance(P, mpc::model_vals_of(P, W.model, W.ld_model, i), O, dl.sub_old, dl.sub_new, i, ld, step, n_track, car, cmd, pre, ldp, st_step[i],
+                             it_step[i], k_now[i], k_prev[i], summary, rec, status, iters);
+  } else
+    mpc::drive_step_instance(P, P, O, dl.sub_old, dl.sub_new, i, ld, step, n_track, car, cmd, pre, ldp, st_step[i], it_step[i], k_now[i], k_prev[i], summary, rec,
+                             status, iters);
+}
+/* What the stepwise loop's handler compensates for, per car: comp [ld] <- row MPC_LATENCY_COMP of the car's column, not-a-number for
+ * a column that cannot be used (the handler turns that into a status).  Once per call. */
+__global__ __launch_bounds__(256) void mpc_drive_comp_kernel(const MpcDriveOpts O, int64_t B, int64_t ld, const double *__restrict__ latency,
+                                                             double *__restrict__ comp) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B) return;
+  comp[i] = mpc::drive_latency_of(O, latency, ld, i).comp;
 }
 
 /* The certificate of a stored point (mpc_certify_batch_*), one instance per lane: mpc::certify_batch_instance of mpc_core.h.  A lane
@@ -2016,6 +2076,7 @@ struct CallExtras {
   int64_t ld_model = 0;            /* 0: the ld of the solve's inputs.  (run() sets its own: it solves from the handle's rows at the handle's stride, the columns stay where the caller has them) */
   bool model_wave = false;         /* a model call of the run() / telemetry entry points: the wave MODEL kernels up to wave_max_batch */
   const int32_t *horizon = nullptr;   /* a horizon call (fp64 handles, no SOC): [ld] like the inputs; dispatched as a model call, `model` may be NULL */
+  const double *latency = nullptr;   /* a latency call (fp64 handles): the telemetry handler's comp [ld]; the drive's [MPC_NLATENCY][ld] */
   const double *run_weights = nullptr;   /* run() / telemetry only (the drive loop): per-instance weights of the solve, [MPC_NW][io_stride] like the rows run() solves from */
   bool model_call() const { return model != nullptr || horizon != nullptr; }
   const WarmIO *warm_io() const { return warm ? &w : nullptr; }
@@ -2291,9 +2352,9 @@ extern "C" int mpc_warm_opts_default(MpcWarmOpts *o) {
  * model needs an fp64 handle that does not start in fp32.  A call with neither is checked for its handle only. */
 static CallExtras call_extras(const MpcHandle *h, const double *model = nullptr, bool warm = false, const double *warm_in = nullptr,
                               const int32_t *warm_status = nullptr, double *warm_out = nullptr, int64_t ld_warm = 0,
-                              const MpcWarmOpts *opts = nullptr, const int32_t *horizon = nullptr) {
+                              const MpcWarmOpts *opts = nullptr, const int32_t *horizon = nullptr, const double *latency = nullptr) {
   CallExtras x;
-  x.warm = warm; x.model = model; x.horizon = horizon;
+  x.warm = warm; x.model = model; x.horizon = horizon; x.latency = latency;
   x.w = WarmIO{warm_in, warm_status, warm_out, ld_warm, {}, 0};
   const auto refuse = [&x](int rc, const char *why) { g_last_error = why; x.refused = rc; return x; };
   if (!h) return refuse(MPC_ERR_INVALID, "NULL handle");
@@ -2301,6 +2362,7 @@ static CallExtras call_extras(const MpcHandle *h, const double *model = nullptr,
   if ((model || horizon) && !f64) return refuse(MPC_ERR_INVALID, "per-instance model values: fp64 handles only (this one was created with MPC_PRECISION_F32)");
   if (horizon && h->params.max_soc > 0)
     return refuse(MPC_ERR_UNSUPPORTED, "a per-instance horizon is not available with the second-order correction (max_soc > 0): set MpcParams.max_soc = 0, or pass horizon = NULL");
+  if (latency && !f64) return refuse(MPC_ERR_INVALID, "per-instance latency: fp64 handles only (this one was created with MPC_PRECISION_F32)");
   if (!warm) return x;
   const bool as_model = model || horizon;      /* (a horizon call is dispatched as a model call: the model rule decides) */
   if (!as_model && !f64) return refuse(MPC_ERR_INVALID, "warm start: fp64 handles only (this one was created with MPC_PRECISION_F32)");
@@ -2467,7 +2529,8 @@ extern "C" int mpc_solve_batch_device_f32(MpcHandle *h, int64_t B, int64_t ld, c
  * three kernels, the solve started from the previous call's records with their psi projected
  * into the box run_pre derives for this call (mpc::WarmColumn).  x.model (device, [MPC_NMODEL][ld]): the MODEL
  * forms of the pre and post kernels, and a model solve between them that reads its inputs from the handle's rows at the handle's
- * stride and the columns from the caller's array at the caller's ld (CallExtras::ld_model) -- the array is not copied. */
+ * stride and the columns from the caller's array at the caller's ld (CallExtras::ld_model) -- the array is not copied.
+ * x.latency (device, comp [ld], with tel): the pre kernel's build that compensates per instance; `extra` is not read. */
 static int run_impl(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, bool tel, double extra, double *ptsx,
                     double *ptsy, double *out8, double *cmd, double *traj, int32_t *status, int32_t *iters, double *pre,
                     void *stream_, CallExtras x) {
@@ -2492,7 +2555,13 @@ static int run_impl(MpcHandle *h, int64_t B, int64_t ld, int npts, const double 
   const double *model = x.model;
   /* the two kernels around the solve: f(MODEL build or not, the argument the MODEL builds take behind the others) */
   const auto around = [&](auto f) { return model ? f(std::true_type{}, MpcModelPart{model, ld}) : f(std::false_type{}); };
-  around([&](auto model_build, auto... mp) {
+  if (tel && x.latency)
+    around([&](auto model_build, auto... mp) {
+      hipLaunchKernelGGL((mpc_run_pre_comp_kernel<decltype(model_build)::value, decltype(mp)...>), dim3(grid), dim3(256), 0, s, h->params, B, ld, npts, pose,
+                         x.latency, ptsx, ptsy, d_pre, S, mp...);
+      return MPC_OK;
+    });
+  else around([&](auto model_build, auto... mp) {
     return with_bool(tel, [&](auto telemetry) {
       hipLaunchKernelGGL((mpc_run_pre_kernel<decltype(telemetry)::value, decltype(model_build)::value, decltype(mp)...>), dim3(grid), dim3(256), 0, s,
                          h->params, B, ld, npts, pose, tel ? extra : 0.0, ptsx, ptsy, d_pre, S, mp...);
@@ -2562,12 +2631,19 @@ extern "C" int mpc_run_batch_device_warm_model(MpcHandle *h, int64_t B, int64_t 
                   call_extras(h, model, true, warm_in, warm_status, warm_out, ld_warm, opts));
 }
 
+extern "C" int mpc_telemetry_batch_device_latency(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
+                                                  const double *comp, double *ptsx, double *ptsy, const double *model, const double *warm_in,
+                                                  const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts,
+                                                  double *cmd, double *out8, int32_t *status, void *stream_) {
+  return run_impl(h, B, ld, npts, tel, true, extra_latency, ptsx, ptsy, out8, cmd, nullptr, status, nullptr, nullptr, stream_,
+                  call_extras(h, model, true, warm_in, warm_status, warm_out, ld_warm, opts, nullptr, comp));
+}
 extern "C" int mpc_telemetry_batch_device_warm_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
                                                      double *ptsx, double *ptsy, const double *model, const double *warm_in,
                                                      const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts,
                                                      double *cmd, double *out8, int32_t *status, void *stream_) {
-  return run_impl(h, B, ld, npts, tel, true, extra_latency, ptsx, ptsy, out8, cmd, nullptr, status, nullptr, nullptr, stream_,
-                  call_extras(h, model, true, warm_in, warm_status, warm_out, ld_warm, opts));
+  return mpc_telemetry_batch_device_latency(h, B, ld, npts, tel, extra_latency, nullptr, ptsx, ptsy, model, warm_in, warm_status, warm_out, ld_warm, opts, cmd,
+                                            out8, status, stream_);
 }
 
 /* A host-array call's extras (`hx`) on the device, *dx: what the launch gets.  The model columns are where the family has copied them
@@ -2613,7 +2689,7 @@ extern "C" void mpc_internal_set_error(const char *msg) { g_last_error = msg ? m
 /* The telemetry handler for host arrays: one copy in, the kernels, one copy out, on the handle's own device and stream
  * (whatever the caller's current device is), staging kept on the handle.  rows of `tel`, `ptsx`, `ptsy` as in
  * mpc_telemetry_batch_device with leading dimension ld; the waypoint arrays are inputs only here.  x.model (host, [MPC_NMODEL][ld]):
- * six more rows of the staging block, copied in with the other inputs. */
+ * six more rows of the staging block, copied in with the other inputs; x.latency (host, comp [ld]): one more. */
 static int telemetry_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency, const double *ptsx,
                           const double *ptsy, double *cmd, int32_t *status, const CallExtras &x) {
   MPC_TRY(x.refused);
@@ -2622,17 +2698,19 @@ static int telemetry_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const d
   if (B == 0) { h->last_B = 0; return MPC_OK; }
   if (!tel || !ptsx || !ptsy || !cmd || !status) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
   MPC_ON_DEVICE(h);
-  const int64_t rows = 6 + 2 * npts, L = (B + 7) / 8 * 8, model_rows = x.model ? MPC_NMODEL : 0;
-  MPC_TRY(grow_dev(&h->d_tel, &h->tel_bytes, sizeof(double) * (size_t)((rows + 2 + model_rows) * L) + sizeof(int32_t) * (size_t)L));
-  double *d = h->d_tel, *d_cmd = d + rows * L, *d_model = d_cmd + 2 * L;
-  int32_t *d_st = (int32_t *)(d_model + model_rows * L);
+  const int64_t rows = 6 + 2 * npts, L = (B + 7) / 8 * 8, model_rows = x.model ? MPC_NMODEL : 0, comp_rows = x.latency ? 1 : 0;
+  MPC_TRY(grow_dev(&h->d_tel, &h->tel_bytes, sizeof(double) * (size_t)((rows + 2 + model_rows + comp_rows) * L) + sizeof(int32_t) * (size_t)L));
+  double *d = h->d_tel, *d_cmd = d + rows * L, *d_model = d_cmd + 2 * L, *d_comp = d_model + model_rows * L;
+  int32_t *d_st = (int32_t *)(d_comp + comp_rows * L);
   hipStream_t s = h->stream;
   MPC_HIP_CHECK(hipMemcpy2DAsync(d, sizeof(double) * L, tel, sizeof(double) * ld, sizeof(double) * B, 6, hipMemcpyHostToDevice, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(d + 6 * L, sizeof(double) * L, ptsx, sizeof(double) * ld, sizeof(double) * B, npts, hipMemcpyHostToDevice, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(d + (6 + npts) * L, sizeof(double) * L, ptsy, sizeof(double) * ld, sizeof(double) * B, npts, hipMemcpyHostToDevice, s));
   if (x.model) MPC_HIP_CHECK(hipMemcpy2DAsync(d_model, sizeof(double) * L, x.model, sizeof(double) * ld, sizeof(double) * B, MPC_NMODEL, hipMemcpyHostToDevice, s));
+  if (x.latency) MPC_HIP_CHECK(hipMemcpyAsync(d_comp, x.latency, sizeof(double) * B, hipMemcpyHostToDevice, s));
   CallExtras dx;
   MPC_TRY(host_extras_in(h, B, x, x.model ? d_model : nullptr, s, &dx));
+  if (x.latency) dx.latency = d_comp;
   MPC_TRY(run_impl(h, B, L, npts, d, true, extra_latency, d + 6 * L, d + (6 + npts) * L, nullptr, d_cmd, nullptr, d_st, nullptr, nullptr, (void *)s, dx));
   MPC_TRY(host_extras_out(h, B, x, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(cmd, sizeof(double) * ld, d_cmd, sizeof(double) * L, sizeof(double) * B, 2, hipMemcpyDeviceToHost, s));
@@ -2658,12 +2736,19 @@ extern "C" int mpc_telemetry_batch_host_model(MpcHandle *h, int64_t B, int64_t l
   return telemetry_host(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, cmd, status, call_extras(h, model));
 }
 
+extern "C" int mpc_telemetry_batch_host_latency(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
+                                                const double *comp, const double *ptsx, const double *ptsy, const double *model, const double *warm_in,
+                                                const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts,
+                                                double *cmd, int32_t *status) {
+  return telemetry_host(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, cmd, status,
+                        call_extras(h, model, true, warm_in, warm_status, warm_out, ld_warm, opts, nullptr, comp));
+}
 extern "C" int mpc_telemetry_batch_host_warm_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
                                                    const double *ptsx, const double *ptsy, const double *model, const double *warm_in,
                                                    const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts,
                                                    double *cmd, int32_t *status) {
-  return telemetry_host(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, cmd, status,
-                        call_extras(h, model, true, warm_in, warm_status, warm_out, ld_warm, opts));
+  return mpc_telemetry_batch_host_latency(h, B, ld, npts, tel, extra_latency, nullptr, ptsx, ptsy, model, warm_in, warm_status, warm_out, ld_warm, opts, cmd,
+                                          status);
 }
 
 /* MPC::run() for host arrays (the drop-in's B = 1 case, include/mpc_drop_in.hpp): one copy in, the three kernels of
@@ -2924,11 +3009,11 @@ static int drive_args(const MpcHandle *h, int64_t B, int64_t ld, int steps, cons
   return MPC_OK;
 }
 
-/* the handle's rows both forms work in: the window rows and the reply, the warm buffer of a warm call, and the caller's weights copied
+/* the handle's rows both forms work in: the window rows and the reply, the stepwise loop's two index rows and its comp row, the warm buffer of a warm call, and the caller's weights copied
  * to the handle's stride (*w_out; NULL without weights) */
 static int drive_rows(MpcHandle *h, int64_t B, int64_t ld, bool warm, const double *weights, hipStream_t s, const double **w_out) {
   const int64_t S = h->io_stride;
-  MPC_TRY(grow_dev(&h->d_drive, &h->drive_bytes, sizeof(double) * (size_t)((2 * mpc::RUN_MAX_PTS + 2) * ld) + sizeof(int32_t) * (size_t)(2 * ld)));
+  MPC_TRY(grow_dev(&h->d_drive, &h->drive_bytes, sizeof(double) * (size_t)((2 * mpc::RUN_MAX_PTS + 3) * ld) + sizeof(int32_t) * (size_t)(2 * ld)));
   if (warm) MPC_TRY(ensure_dev(&h->d_warm, sizeof(double) * (size_t)mpc_warm_rows(h->params.N) * (size_t)S));
   *w_out = nullptr;
   if (weights) {
@@ -2942,7 +3027,9 @@ static int drive_rows(MpcHandle *h, int64_t B, int64_t ld, bool warm, const doub
 /* The stepwise loop: `steps` x (sense kernel, the telemetry handler -- run_impl with tel, the weights and an iterations pointer --,
  * plant-and-summary kernel) on the caller's stream; no host synchronisation.  x.warm: every step after the first is the _warm handler
  * on the handle's own buffer, in place (rollout_impl's arrangement).  x.model (device, [MPC_NMODEL][ld]): the handler is the
- * telemetry _model call -- run_impl reads the columns where the caller has them -- and the plant kernel its MODEL build. */
+ * telemetry _model call -- run_impl reads the columns where the caller has them -- and the plant kernel its MODEL build.
+ * x.latency (device, [MPC_NLATENCY][ld]): one more kernel first, the comp row the handler takes (not-a-number for a column that cannot
+ * be used); the handler is the telemetry _latency call on it and the plant kernel its latency build, with or without model. */
 static int drive_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y, int n_track,
                       const double *weights, const MpcDriveOpts &O, CallExtras x, double *summary, double *hist, int32_t *status,
                       int32_t *iters, void *stream_) {
@@ -2955,6 +3042,13 @@ static int drive_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *ca
   double *ptsx = h->d_drive, *ptsy = ptsx + P8 * ld, *cmd = ptsy + P8 * ld;
   int32_t *kbuf = (int32_t *)(cmd + 2 * ld);
   const unsigned grid = (unsigned)((B + 255) / 256);
+  const double *latency = x.latency;
+  if (latency) {
+    double *comp = (double *)(kbuf + 2 * ld);
+    hipLaunchKernelGGL(mpc_drive_comp_kernel, dim3(grid), dim3(256), 0, s, O, B, ld, latency, comp);
+    MPC_HIP_CHECK(hipGetLastError());
+    x.latency = comp;                              /* what run_impl takes: the handler's comp [ld] */
+  }
   for (int t = 0; t < steps; t++) {
     /* (the first step has no step before it: it is handed its own row, and mpc::drive_step_instance does not look at the value) */
     int32_t *k_now = kbuf + (int64_t)(t & 1) * ld, *k_prev = t == 0 ? k_now : kbuf + (int64_t)((t & 1) ^ 1) * ld;
@@ -2963,7 +3057,13 @@ static int drive_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *ca
     x.w = WarmIO{t == 0 ? nullptr : h->d_warm, h->d_rstat, h->d_warm, S, x.w.wopts, 0};
     MPC_TRY(run_impl(h, B, ld, O.npts, car, true, O.extra_latency, ptsx, ptsy, nullptr, cmd, nullptr, h->d_rstat, h->d_iters, nullptr, stream_, x));
     double *rec = hist ? hist + (int64_t)t * MPC_DRIVE_REC * ld : nullptr;
-    if (x.model)
+    if (latency && x.model)
+      hipLaunchKernelGGL((mpc_drive_plant_latency_kernel<true, MpcModelPart>), dim3(grid), dim3(256), 0, s, h->params, O, B, ld, t, n_track, car, cmd, h->d_run, S,
+                         h->d_rstat, h->d_iters, k_now, k_prev, summary, rec, status, iters, latency, MpcModelPart{x.model, ld});
+    else if (latency)
+      hipLaunchKernelGGL((mpc_drive_plant_latency_kernel<false>), dim3(grid), dim3(256), 0, s, h->params, O, B, ld, t, n_track, car, cmd, h->d_run, S,
+                         h->d_rstat, h->d_iters, k_now, k_prev, summary, rec, status, iters, latency);
+    else if (x.model)
       hipLaunchKernelGGL(mpc_drive_plant_model_kernel, dim3(grid), dim3(256), 0, s, h->params, O, B, ld, t, n_track, car, cmd, h->d_run, S, h->d_rstat,
                          h->d_iters, k_now, k_prev, summary, rec, status, iters, MpcModelPart{x.model, ld});
     else
@@ -2978,23 +3078,30 @@ static int drive_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *ca
 /* What every drive entry point does first: with `model`, the model rule (which handles a model call is accepted on, call_extras);
  * drive_args; then the call's extras -- the warm refusals and the options in effect. */
 static int drive_call(const MpcHandle *h, int64_t B, int64_t ld, int steps, const double *car, const double *track_x, const double *track_y,
-                      int n_track, const double *model, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, const double *summary,
-                      const int32_t *status, MpcDriveOpts *O, CallExtras *x) {
+                      int n_track, const double *model, const double *latency, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts,
+                      const double *summary, const int32_t *status, MpcDriveOpts *O, CallExtras *x) {
   if (h && model) MPC_TRY(call_extras(h, model).refused);
   MPC_TRY(drive_args(h, B, ld, steps, car, track_x, track_y, n_track, opts, summary, status, O));
-  *x = call_extras(h, model, O->warm_start != 0, nullptr, nullptr, nullptr, 0, warm_opts);
+  *x = call_extras(h, model, O->warm_start != 0, nullptr, nullptr, nullptr, 0, warm_opts, nullptr, latency);
   return x->refused;
 }
 
+extern "C" int mpc_drive_batch_device_latency(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
+                                              const double *track_y, int n_track, const double *weights, const double *model, const double *latency,
+                                              const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist,
+                                            int32_t *status, int32_t *iters, void *stream_) {
+  MpcDriveOpts O;
+  CallExtras x;
+  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, latency, opts, warm_opts, summary, status, &O, &x));
+  if (B == 0) { h->last_B = 0; return MPC_OK; }
+  return drive_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
+}
 extern "C" int mpc_drive_batch_device_model(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
                                             const double *track_y, int n_track, const double *weights, const double *model,
                                             const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist,
                                             int32_t *status, int32_t *iters, void *stream_) {
-  MpcDriveOpts O;
-  CallExtras x;
-  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, opts, warm_opts, summary, status, &O, &x));
-  if (B == 0) { h->last_B = 0; return MPC_OK; }
-  return drive_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
+  return mpc_drive_batch_device_latency(h, B, ld, steps, car, track_x, track_y, n_track, weights, model, nullptr, opts, warm_opts, summary, hist, status, iters,
+                                        stream_);
 }
 extern "C" int mpc_drive_batch_device(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
                                       int n_track, const double *weights, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts,
@@ -3042,7 +3149,7 @@ static int drive_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, doub
   double *warm = x.warm ? h->d_warm : nullptr;
   const WarmIO wc{warm, nullptr, warm, S, x.w.wopts, 1};      /* (psi_box: the run() path's rule) */
   const MpcRollPart roll{steps, nullptr, 0, nullptr, status, iters};
-  const MpcDrivePart drive{O, car, track_x, track_y, n_track, ptsx, ptsy, cmd, d_pre, h->d_run9, summary, hist};
+  const MpcDrivePart drive{O, car, track_x, track_y, n_track, ptsx, ptsy, cmd, d_pre, h->d_run9, summary, hist, x.latency};
   const unsigned grid = (unsigned)((B + kBlock - 1) / kBlock);
   MPC_TRY(with_bool(h->staging, [&](auto staging) {
     return with_bool(x.warm, [&](auto warm_build) {
@@ -3058,15 +3165,22 @@ static int drive_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, doub
   return record_stats(h, B, status, iters, s);
 }
 
+extern "C" int mpc_drive_batch_device_fused_latency(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
+                                                    const double *track_y, int n_track, const double *weights, const double *model,
+                                                    const double *latency, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist,
+                                                  int32_t *status, int32_t *iters, void *stream_) {
+  MpcDriveOpts O;
+  CallExtras x;
+  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, latency, opts, warm_opts, summary, status, &O, &x));
+  if (B == 0) { h->last_B = 0; return MPC_OK; }
+  return drive_fused_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
+}
 extern "C" int mpc_drive_batch_device_fused_model(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
                                                   const double *track_y, int n_track, const double *weights, const double *model,
                                                   const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist,
                                                   int32_t *status, int32_t *iters, void *stream_) {
-  MpcDriveOpts O;
-  CallExtras x;
-  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, opts, warm_opts, summary, status, &O, &x));
-  if (B == 0) { h->last_B = 0; return MPC_OK; }
-  return drive_fused_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
+  return mpc_drive_batch_device_fused_latency(h, B, ld, steps, car, track_x, track_y, n_track, weights, model, nullptr, opts, warm_opts, summary, hist, status,
+                                              iters, stream_);
 }
 extern "C" int mpc_drive_batch_device_fused(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
                                             int n_track, const double *weights, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts,
@@ -3076,21 +3190,24 @@ extern "C" int mpc_drive_batch_device_fused(MpcHandle *h, int64_t B, int64_t ld,
 }
 
 /* The same for host arrays: one copy in, the loop on the handle's own device and stream, one copy out; synchronises.  Staging kept on
- * the handle and grown on demand, like the telemetry handler's.  model (host, [MPC_NMODEL][ld]) is copied in with the other inputs. */
-extern "C" int mpc_drive_batch_host_model(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
-                                          int n_track, const double *weights, const double *model, const MpcDriveOpts *opts,
+ * the handle and grown on demand, like the telemetry handler's.  model (host, [MPC_NMODEL][ld]) and latency (host, [MPC_NLATENCY][ld])
+ * are copied in with the other inputs. */
+extern "C" int mpc_drive_batch_host_latency(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                                            int n_track, const double *weights, const double *model, const double *latency, const MpcDriveOpts *opts,
                                           const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status, int32_t *iters) {
   MpcDriveOpts O;
   CallExtras x;
-  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, opts, warm_opts, summary, status, &O, &x));
+  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, latency, opts, warm_opts, summary, status, &O, &x));
   if (B == 0) { h->last_B = 0; return MPC_OK; }
   MPC_ON_DEVICE(h);
   const int64_t L = (B + 7) / 8 * 8;
-  const int64_t rows = 6 + MPC_DRIVE_NSUM + (weights ? MPC_NW : 0) + (hist ? (int64_t)steps * MPC_DRIVE_REC : 0) + (model ? MPC_NMODEL : 0);
+  const int64_t rows = 6 + MPC_DRIVE_NSUM + (weights ? MPC_NW : 0) + (hist ? (int64_t)steps * MPC_DRIVE_REC : 0) + (model ? MPC_NMODEL : 0) +
+                       (latency ? MPC_NLATENCY : 0);
   MPC_TRY(grow_dev(&h->d_drive_host, &h->drive_host_bytes, sizeof(double) * (size_t)(rows * L + 2 * n_track) + sizeof(int32_t) * (size_t)(2 * L)));
   double *d = h->d_drive_host;
   double *d_car = d, *d_sum = d_car + 6 * L, *d_w = d_sum + MPC_DRIVE_NSUM * L, *d_hist = d_w + (weights ? MPC_NW * L : 0);
-  double *d_model = d_hist + (hist ? (int64_t)steps * MPC_DRIVE_REC * L : 0), *d_tx = d_model + (model ? MPC_NMODEL * L : 0), *d_ty = d_tx + n_track;
+  double *d_model = d_hist + (hist ? (int64_t)steps * MPC_DRIVE_REC * L : 0), *d_lat = d_model + (model ? MPC_NMODEL * L : 0), *d_tx = d_lat + (latency ? MPC_NLATENCY * L : 0),
+         *d_ty = d_tx + n_track;
   int32_t *d_st = (int32_t *)(d_ty + n_track), *d_it = d_st + L;
   hipStream_t s = h->stream;
   MPC_HIP_CHECK(hipMemcpy2DAsync(d_car, sizeof(double) * L, car, sizeof(double) * ld, sizeof(double) * B, 6, hipMemcpyHostToDevice, s));
@@ -3098,6 +3215,10 @@ extern "C" int mpc_drive_batch_host_model(MpcHandle *h, int64_t B, int64_t ld, i
   if (model) {
     MPC_HIP_CHECK(hipMemcpy2DAsync(d_model, sizeof(double) * L, model, sizeof(double) * ld, sizeof(double) * B, MPC_NMODEL, hipMemcpyHostToDevice, s));
     x.model = d_model;
+  }
+  if (latency) {
+    MPC_HIP_CHECK(hipMemcpy2DAsync(d_lat, sizeof(double) * L, latency, sizeof(double) * ld, sizeof(double) * B, MPC_NLATENCY, hipMemcpyHostToDevice, s));
+    x.latency = d_lat;
   }
   MPC_HIP_CHECK(hipMemcpyAsync(d_tx, track_x, sizeof(double) * n_track, hipMemcpyHostToDevice, s));
   MPC_HIP_CHECK(hipMemcpyAsync(d_ty, track_y, sizeof(double) * n_track, hipMemcpyHostToDevice, s));
@@ -3109,6 +3230,11 @@ extern "C" int mpc_drive_batch_host_model(MpcHandle *h, int64_t B, int64_t ld, i
   if (iters) MPC_HIP_CHECK(hipMemcpyAsync(iters, d_it, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipStreamSynchronize(s));
   return MPC_OK;
+}
+extern "C" int mpc_drive_batch_host_model(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                                          int n_track, const double *weights, const double *model, const MpcDriveOpts *opts,
+                                          const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status, int32_t *iters) {
+  return mpc_drive_batch_host_latency(h, B, ld, steps, car, track_x, track_y, n_track, weights, model, nullptr, opts, warm_opts, summary, hist, status, iters);
 }
 extern "C" int mpc_drive_batch_host(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
                                     int n_track, const double *weights, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts,

@@ -248,5 +248,30 @@ def track_starts(B, params, waypoints, seed=DEFAULT_SEED):
                                           np.zeros(B), v / 50.0]))
 
 
+def latency_grid(B, params, delays_ms, comps_s, period_substeps, h=0.01):
+    """The latency array [3, B] (rows _abi.LATENCY_*) of a stale-time x compensation grid for BatchedMPC.drive_torch(latency=...): the
+    study the reference makes with `-latency N` run N times, as the columns of one call.  delays_ms: how long the command in force
+    stays in force after a message, each a whole number of plant substeps of h seconds (-> sub_old); comps_s: the seconds the handler
+    compensates for (None: the parameter set's own -- lookahead, or 0 with latency_ms = 0); period_substeps: the substeps between
+    two messages, so sub_new = period_substeps - sub_old (0 for a delay of a period or more).  Cell (d, c) of the grid is column
+    d * len(comps_s) + c, and the grid is laid out B / cells times, so that each cell gets as many cars (other starts, other
+    weights).  ValueError: B no multiple of the cells, a delay that is no whole number of substeps, counts outside the call's rule
+    (sub_old + sub_new in 1..1000)."""
+    own = params.lookahead if params.latency_ms != 0 else 0.0
+    comps = np.array([own if c is None else float(c) for c in comps_s], dtype=np.float64)
+    sub = np.array([float(d) / (1000.0 * h) for d in delays_ms], dtype=np.float64)
+    cells = len(sub) * len(comps)
+    if cells < 1 or int(B) < cells or int(B) % cells:
+        raise ValueError("B must be a multiple of len(delays_ms) * len(comps_s)")
+    sub_old = np.round(sub)
+    if (np.abs(sub - sub_old) > 1e-9).any() or (sub_old < 0).any():
+        raise ValueError("every delay must be a whole number of substeps of %g s" % h)
+    sub_new = np.maximum(float(int(period_substeps)) - sub_old, 0.0)
+    if ((sub_old + sub_new < 1) | (sub_old + sub_new > 1000)).any() or not (np.isfinite(comps).all() and (comps >= 0).all()):
+        raise ValueError("sub_old + sub_new must be 1..1000 and every compensation finite and >= 0")
+    grid = np.stack([np.tile(comps, len(sub)), np.repeat(sub_old, len(comps)), np.repeat(sub_new, len(comps))])
+    return np.ascontiguousarray(np.tile(grid, (1, int(B) // cells)))
+
+
 def golden_dir():
     return os.path.join(_abi.ROOT, "tests", "golden")

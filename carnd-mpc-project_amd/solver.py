@@ -248,12 +248,14 @@ class BatchedMPC:
         return res
 
     def telemetry_torch(self, tel, ptsx, ptsy, extra_latency=0.0, want_out8=False, stream=None, warm=None, warm_status=None,
-                        want_warm=False, warm_opts=None, warm_out=None, status_out=None, model=None):
+                        want_warm=False, warm_opts=None, warm_out=None, status_out=None, model=None, comp=None):
         """The telemetry handler around run() (src/mpc_main.cpp:126-174) for a batch: tel [6,B] = x, y, psi,
         speed [mph], steering_angle (simulator sign), previous throttle.  Returns cmd [2,B] = (steering_angle,
         throttle) of the reply, status, and optionally run()'s 8-vector.  The warm arguments are run_torch's
         (mpc_telemetry_batch_device_warm).  ``model`` [6, B] as in run_torch (mpc_telemetry_batch_device_model, _warm_model): each
-        car's own Lf in the latency compensation and its own limits in the steering normalisation and the throttle."""
+        car's own Lf in the latency compensation and its own limits in the steering normalisation and the throttle.
+        ``comp`` [B] float64 (mpc_telemetry_batch_device_latency; fp64 handles): the seconds every instance compensates for, in
+        the place of the handle's latency_ms / lookahead and of ``extra_latency``; 0: no compensation.  Always the warm form of the call."""
         import torch
         B = tel.shape[1]
         npts = ptsx.shape[0]
@@ -271,8 +273,37 @@ class BatchedMPC:
         warm_args = None
         if warm is not None or want_warm or warm_out is not None:
             warm_args = self._warm_args(res, B, dev, warm, warm_status, warm_out) + (C.byref(warm_opts) if warm_opts is not None else None,)
+        if comp is not None:
+            if comp.dtype != torch.float64 or not comp.is_cuda or not comp.is_contiguous() or tuple(comp.shape) != (B,):
+                raise ValueError("comp must be a contiguous float64 CUDA tensor of shape (B,)")
+            if warm_args is None:
+                warm_args = (None, None, None, 0, C.byref(warm_opts) if warm_opts is not None else None)
+            check(library().mpc_telemetry_batch_device_latency(self._h, B, B, int(npts), tel.data_ptr(), float(extra_latency), comp.data_ptr(),
+                                                               ptsx.data_ptr(), ptsy.data_ptr(), model.data_ptr() if model is not None else None,
+                                                               *warm_args, *outs), "mpc_telemetry_batch_device_latency")
+            return res
         self._call("mpc_telemetry_batch_device", (B, B, int(npts), tel.data_ptr(), float(extra_latency), ptsx.data_ptr(), ptsy.data_ptr()),
                    outs, model.data_ptr() if model is not None else None, warm_args)
+        return res
+
+    def telemetry_numpy(self, tel, ptsx, ptsy, extra_latency=0.0, model=None, comp=None, warm_opts=None):
+        """telemetry_torch for host arrays through the _latency form (mpc_telemetry_batch_host_latency; without ``comp`` that is
+        mpc_telemetry_batch_host_warm_model, started cold): one copy in, the kernels, one copy out; synchronises.  Returns "cmd" [2, B]
+        and "status".  ``model`` [6, B], ``comp`` [B]: as in telemetry_torch."""
+        f = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64)) if a is not None else None
+        tel, ptsx, ptsy, model, comp = f(tel), f(ptsx), f(ptsy), f(model), f(comp)
+        B, npts = tel.shape[1], ptsx.shape[0]
+        if tel.shape != (6, B) or ptsx.shape != (npts, B) or ptsy.shape != (npts, B):
+            raise ValueError("tel [6, B], ptsx and ptsy [npts, B]")
+        if model is not None and model.shape != (_abi.NMODEL, B):
+            raise ValueError("model must have shape (%d, B)" % _abi.NMODEL)
+        if comp is not None and comp.shape != (B,):
+            raise ValueError("comp must have shape (B,)")
+        res = {"cmd": np.empty((2, B)), "status": np.empty(B, dtype=np.int32)}
+        p = lambda a: a.ctypes.data if a is not None else None
+        check(library().mpc_telemetry_batch_host_latency(self._h, B, B, int(npts), p(tel), float(extra_latency), p(comp), p(ptsx), p(ptsy), p(model),
+                                                         None, None, None, 0, C.byref(warm_opts) if warm_opts is not None else None,
+                                                         p(res["cmd"]), p(res["status"])), "mpc_telemetry_batch_host_latency")
         return res
 
     def rollout_torch(self, state, coeffs, yaw_lo, yaw_hi, steps, weights=None, want_hist=True, stream=None, warm_start=False,
@@ -319,7 +350,7 @@ class BatchedMPC:
         return _abi.drive_opts_default(self.params, **overrides)
 
     def drive_torch(self, car, track_x, track_y, steps, weights=None, opts=None, warm_opts=None, want_hist=True, fused=False, stream=None,
-                    model=None):
+                    model=None, latency=None):
         """Drive B cars along a cyclic track for `steps` telemetry messages on the device (mpc_drive_batch_device): per message the
         waypoint window at the car's position, the telemetry handler (cold, or warm with opts.warm_start) and the plant -- the
         reference's own kinematic model, not the simulator.  car [6, B] = x, y, psi, speed [mph], steering_angle, throttle is advanced
@@ -329,11 +360,17 @@ class BatchedMPC:
         its own (mpc_drive_batch_device_fused; bitwise the same results, drive_info() tells whether the one launch or the stepwise loop
         ran).  ``model`` [6, B] float64 as in telemetry_torch (mpc_drive_batch_device_model, _fused_model; fp64 handles): every car's own
         dt, Lf and limits, in the handler and in the plant (Lf in the heading update, max_steering in the steering angle in force) --
-        one call answers "how fast can this tuning go round the track" with a row of max_speed values."""
+        one call answers "how fast can this tuning go round the track" with a row of max_speed values.
+        ``latency`` [3, B] float64 (mpc_drive_batch_device_latency, _fused_latency; rows _abi.LATENCY_*): every car's own compensated
+        time [s] in the handler and its own sub_old / sub_new in the plant (scenarios.latency_grid builds a stale-time x compensation
+        grid) -- one call answers "how much delay does this tuning survive, compensated or not"."""
         import torch
         B = car.shape[1]
         if model is not None:
             self._check_model(model, B)
+        if latency is not None and (latency.dtype != torch.float64 or not latency.is_cuda or not latency.is_contiguous() or
+                                    tuple(latency.shape) != (_abi.NLATENCY, B)):
+            raise ValueError("latency must be a contiguous float64 CUDA tensor of shape (%d, B)" % _abi.NLATENCY)
         dev = car.device
         n = int(track_x.shape[0])
         for name, t, shape in (("car", car, (6, B)), ("track_x", track_x, (n,)), ("track_y", track_y, (n,)), ("weights", weights, (_abi.NW, B))):
@@ -343,19 +380,23 @@ class BatchedMPC:
                "hist": torch.empty((steps, _abi.DRIVE_REC, B), dtype=torch.float64, device=dev) if want_hist else None,
                "status": torch.empty((B,), dtype=torch.int32, device=dev), "iters": torch.empty((B,), dtype=torch.int32, device=dev)}
         s = stream if stream is not None else torch.cuda.current_stream(dev)
-        name = ("mpc_drive_batch_device_fused" if fused else "mpc_drive_batch_device") + ("_model" if model is not None else "")
+        name = ("mpc_drive_batch_device_fused" if fused else "mpc_drive_batch_device") + ("_latency" if latency is not None else
+                                                                                           "_model" if model is not None else "")
+        extra = (model.data_ptr(),) if model is not None else ()
+        if latency is not None:
+            extra = (model.data_ptr() if model is not None else None, latency.data_ptr())
         check(getattr(library(), name)(self._h, B, B, int(steps), car.data_ptr(), track_x.data_ptr(), track_y.data_ptr(), n,
-                                               weights.data_ptr() if weights is not None else None,
-                                               *((model.data_ptr(),) if model is not None else ()),
+                                               weights.data_ptr() if weights is not None else None, *extra,
                                                C.byref(opts) if opts is not None else None, C.byref(warm_opts) if warm_opts is not None else None,
                                                res["summary"].data_ptr(), res["hist"].data_ptr() if want_hist else None,
                                                res["status"].data_ptr(), res["iters"].data_ptr(), C.c_void_p(s.cuda_stream)),
               name)
         return res
 
-    def drive_numpy(self, car, track_x, track_y, steps, weights=None, opts=None, warm_opts=None, want_hist=True, model=None):
+    def drive_numpy(self, car, track_x, track_y, steps, weights=None, opts=None, warm_opts=None, want_hist=True, model=None, latency=None):
         """drive_torch for host arrays (mpc_drive_batch_host): one copy in, the loop, one copy out; synchronises.  `car` is copied:
-        the cars after the last step are "car" of the result.  ``model`` [6, B]: as in drive_torch (mpc_drive_batch_host_model)."""
+        the cars after the last step are "car" of the result.  ``model`` [6, B]: as in drive_torch (mpc_drive_batch_host_model); ``latency`` [3, B]: as in
+        drive_torch (mpc_drive_batch_host_latency)."""
         f = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64)) if a is not None else None
         car, tx, ty, weights = f(car).copy(), f(track_x), f(track_y), f(weights)
         B, n = car.shape[1], tx.shape[0]
@@ -367,8 +408,13 @@ class BatchedMPC:
         res = {"car": car, "summary": np.empty((_abi.DRIVE_NSUM, B)), "hist": np.empty((steps, _abi.DRIVE_REC, B)) if want_hist else None,
                "status": np.empty(B, dtype=np.int32), "iters": np.empty(B, dtype=np.int32)}
         p = lambda a: a.ctypes.data if a is not None else None
-        name = "mpc_drive_batch_host" + ("_model" if model is not None else "")
-        check(getattr(library(), name)(self._h, B, B, int(steps), p(car), p(tx), p(ty), n, p(weights), *((p(model),) if model is not None else ()),
+        if latency is not None:
+            latency = f(latency)
+            if latency.shape != (_abi.NLATENCY, B):
+                raise ValueError("latency must have shape (%d, B)" % _abi.NLATENCY)
+        name = "mpc_drive_batch_host" + ("_latency" if latency is not None else "_model" if model is not None else "")
+        extra = (p(model), p(latency)) if latency is not None else ((p(model),) if model is not None else ())
+        check(getattr(library(), name)(self._h, B, B, int(steps), p(car), p(tx), p(ty), n, p(weights), *extra,
                                        C.byref(opts) if opts is not None else None, C.byref(warm_opts) if warm_opts is not None else None,
                                        p(res["summary"]), p(res["hist"]), p(res["status"]), p(res["iters"])), name)
         return res

@@ -603,6 +603,9 @@ int mpc_telemetry_batch_host_warm_model(MpcHandle *h, int64_t B, int64_t ld, int
                                         const double *ptsx, const double *ptsy, const double *model, const double *warm_in,
                                         const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts,
                                         double *cmd, int32_t *status);
+/* Per-instance latency: mpc_telemetry_batch_device_latency and mpc_telemetry_batch_host_latency are the two _warm_model forms above plus
+ * `comp` [ld], the seconds each instance compensates for, directly behind extra_latency.  They are declared and described with the
+ * drive's _latency forms in mpc_amd_drive.h (included above), section "per-car latency". */
 /* ---- the wire side of the handler (src/mpc_main.cpp:26-36, 81-222, DATA.md:5-16) --------
  * Everything between the bytes of a simulator frame and the bytes of the reply; the WebSocket server itself is out of
  * scope.  See csrc/mpc_wire.cpp. */

@@ -75,7 +75,8 @@
  *   Plant, both uses: psi += steer * dist / Lf_i, and the reply takes effect as (cmd_steer * max_steering_i, cmd_throttle) -- cmd_steer
  *     was normalised by that same max_steering_i, so the angle in force is the angle the solve chose.
  *   Unchanged: the window rule, the summary and record rows, the status and iteration conventions, MpcDriveOpts.  sub_old, sub_new and h
- *     stay the call's: there is no per-car latency or substep count, and no _horizon form (the run() path has none).
+ *     stay the call's here (per-car latency and substep counts: the _latency forms below), and there is no _horizon form (the run() path
+     has none).
  * A column that cannot be used (the _model rule: a value that is not finite, dt <= 0, Lf <= 0, max_steering <= 0, max_speed <= 0,
  *   max_acceleration <= 0, max_deceleration >= 0): the handle's values take its place in the handler's pre- and post-processing and in
  *   the plant, every step of that car ends MPC_STATUS_INFEASIBLE, car / summary / hist hold no not-a-number because of it, and every
@@ -86,7 +87,36 @@
  * mpc_drive_batch_device_fused_model writes BITWISE what mpc_drive_batch_device_model writes.  It runs the one launch where the
  *   stepwise model loop would launch the lane kernel's MODEL build at every step -- B above the wave limit (wave_max_batch < 0: every
  *   B), max_soc = 0 -- on every fp64 handle: one more case than the form without _model serves, because a model solve is never the
- *   two-launch fp32-start solve.  Everywhere else it runs the stepwise loop itself; mpc_drive_info counts both kinds. */
+ *   two-launch fp32-start solve.  Everywhere else it runs the stepwise loop itself; mpc_drive_info counts both kinds.
+ *
+ * ---- per-car latency: mpc_drive_*_latency and mpc_telemetry_batch_*_latency ----------------------------------------------------------
+ * How much actuator delay does this tuning survive, and what happens when the delay the handler compensates is not the delay the car
+ * has?  Stale command time x compensated time is a 2-D grid; it is the columns of one call.  This replaces the reference's `-latency N`
+ * run N times (and config-no-latency.json: comp = 0).
+ * Telemetry handler.  mpc_telemetry_batch_device_latency / _host_latency have the arguments of the _warm_model forms plus `comp`, [ld]
+ *   doubles (host form: a host array), directly behind extra_latency; model and the warm arguments may be NULL, as there.
+ *   comp == NULL: the call IS the _warm_model form -- bitwise, the same dispatch and refusals.
+ *   comp != NULL: instance i compensates for comp[i] seconds: Vehicle::move over comp[i] if comp[i] > 0, and no move at comp[i] == 0 (the
+ *     reference's `if (Config::latency)` not taken).  MpcParams.latency_ms, MpcParams.lookahead and extra_latency are not read for it.
+ *     A value that cannot be used -- not finite, or below 0 -- : the instance is handled exactly as one whose speedometer reading is
+ *     negative: the speed handed on is not-a-number, the instance ends with the status that path produces, nothing else in the batch
+ *     changes.  Everything else is the _warm_model form's: fp64 handles only, no warm with max_soc > 0, the wave kernels up to
+ *     wave_max_batch and the lane kernel above it.
+ * Drive.  Each _latency form is the _model form plus `latency` directly behind `model`: [MPC_NLATENCY][ld] doubles addressed with the
+ *   call's ld (host form: a host array, copied in with the other inputs), rows
+ *     MPC_LATENCY_COMP     comp as above, for the handler call of every step
+ *     MPC_LATENCY_SUB_OLD  sub_old of this car in the plant, a double holding an integer value
+ *     MPC_LATENCY_SUB_NEW  sub_new of this car in the plant, likewise
+ *   latency == NULL: the call IS the _model form, bitwise.
+ *   latency != NULL: car i uses its column.  opts->extra_latency, sub_old and sub_new are still validated as above and are the fallback
+ *     below; h, npts, cte_limit, the window rule, the summary and record rows, the status and iteration conventions are unchanged.
+ *   A column that cannot be used -- a value that is not finite, comp < 0, a count that is no integer value or below 0, sub_old + sub_new
+ *     outside 1..1000 -- : the handler treats the car as above, so it carries a status at every step; the plant moves it with the call's
+ *     sub_old and sub_new; car / summary / hist hold no not-a-number because of it; every other car is bit for bit what it is without the
+ *     defect.  No trip count comes from an unchecked double: a launch that ends.
+ *   mpc_drive_batch_device_fused_latency writes BITWISE what mpc_drive_batch_device_latency writes, and runs the one launch under exactly
+ *     the rule of _fused_model (model == NULL: the rule of the plain fused form); everywhere else it runs the stepwise loop.
+ *     mpc_drive_info counts both. */
 #define MPC_DRIVE_MAX_TRACK 4096
 #define MPC_DRIVE_NSUM 8
 #define MPC_DRIVE_REC 13
@@ -94,6 +124,8 @@ enum { MPC_DRIVE_SUM_MAX_CTE = 0, MPC_DRIVE_SUM_CTE2, MPC_DRIVE_SUM_MAX_EPSI, MP
        MPC_DRIVE_SUM_PROGRESS, MPC_DRIVE_SUM_FIRST_OFF, MPC_DRIVE_SUM_FAILED };
 enum { MPC_DRIVE_REC_CAR = 0, MPC_DRIVE_REC_CMD = 6, MPC_DRIVE_REC_CTE = 8, MPC_DRIVE_REC_EPSI = 9, MPC_DRIVE_REC_STATUS = 10,
        MPC_DRIVE_REC_ITERS = 11, MPC_DRIVE_REC_K = 12 };
+#define MPC_NLATENCY 3
+enum { MPC_LATENCY_COMP = 0, MPC_LATENCY_SUB_OLD = 1, MPC_LATENCY_SUB_NEW = 2 };
 
 typedef struct MpcDriveOpts {
   int32_t size;            /* sizeof(MpcDriveOpts) */
@@ -127,6 +159,25 @@ int mpc_drive_batch_device_fused_model(MpcHandle *h, int64_t B, int64_t ld, int 
 int mpc_drive_batch_host_model(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
                                int n_track, const double *weights, const double *model, const MpcDriveOpts *opts,
                                const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status, int32_t *iters);
+int mpc_drive_batch_device_latency(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                                   int n_track, const double *weights, const double *model, const double *latency, const MpcDriveOpts *opts,
+                                   const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status, int32_t *iters, void *stream);
+int mpc_drive_batch_device_fused_latency(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
+                                         const double *track_y, int n_track, const double *weights, const double *model,
+                                         const double *latency, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary,
+                                         double *hist, int32_t *status, int32_t *iters, void *stream);
+int mpc_drive_batch_host_latency(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                                 int n_track, const double *weights, const double *model, const double *latency, const MpcDriveOpts *opts,
+                                 const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status, int32_t *iters);
+/* (declared here, not beside the other telemetry forms: they take what the drive's row MPC_LATENCY_COMP holds) */
+int mpc_telemetry_batch_device_latency(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
+                                       const double *comp, double *ptsx, double *ptsy, const double *model, const double *warm_in,
+                                       const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts, double *cmd,
+                                       double *out8, int32_t *status, void *stream);
+int mpc_telemetry_batch_host_latency(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
+                                     const double *comp, const double *ptsx, const double *ptsy, const double *model, const double *warm_in,
+                                     const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts, double *cmd,
+                                     int32_t *status);
 int mpc_drive_info(const MpcHandle *h, int64_t *out2);
 
 #endif /* MPC_AMD_DRIVE_H */

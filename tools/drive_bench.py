@@ -18,7 +18,13 @@ Writes --out (default profiles/drive.json); needs an MI355X.
              run of this tool on the parent commit wrote in the same session are copied in beside them),
   sweep      one drive with real variation: --speeds values of max_speed x --cars cars in ONE warm one-launch call of --sweep-steps
              messages, every value on the same starts -- per value: how many cars leave the road (summary row "first step off the
-             road"), when, how fast they went and how far they got."""
+             road"), when, how fast they went and how far they got.
+
+--latency: the mpc_drive_*_latency entry points (default --out profiles/drive_latency.json) --
+  grid       --delays stale-command times x --comps compensated times x --cars cars (scenarios.latency_grid, the same starts in every
+             cell) in ONE warm one-launch call of --sweep-steps messages: the off-track map (cars that leave the road per cell), the
+             time of the launch, and the iterations per solve along both axes -- what the reference studies with `-latency N` run N
+             times."""
 import argparse
 import json
 import os
@@ -47,8 +53,14 @@ def main():
     ap.add_argument("--speeds", type=int, default=16)
     ap.add_argument("--cars", type=int, default=4096)
     ap.add_argument("--sweep-steps", type=int, default=300)
+    ap.add_argument("--latency", action="store_true", help="run the stale-time x compensation grid of the _latency entry points")
+    ap.add_argument("--delays", type=int, default=16, help="--latency: stale-command times, 0, 10, 20 ... ms")
+    ap.add_argument("--comps", type=int, default=16, help="--latency: compensated times, 0, 10, 20 ... ms")
+    ap.add_argument("--period", type=int, default=16, help="--latency: plant substeps (10 ms each) between two messages")
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "drive_model.json" if a.model else "drive.json")
+    a.out = a.out or os.path.join(ROOT, "profiles", "drive_latency.json" if a.latency else "drive_model.json" if a.model else "drive.json")
+    if a.latency and a.cars == 4096:
+        a.cars = 16
     import torch
     assert torch.cuda.is_available(), "this benchmark needs a GPU"
     pkg = G.load_package()
@@ -74,6 +86,8 @@ def main():
             if rep >= a.warmup:
                 ms.append(e0.elapsed_time(e1))
         return ms, out
+    if a.latency:
+        return latency_grid(a, pkg, params, wp, t, d_tx, d_ty)
     if a.model:
         return model_rows(a, pkg, params, wp, t, timed, car0, d_car0, d_tx, d_ty)
     for warm in (0, 1):
@@ -179,6 +193,48 @@ def model_rows(a, pkg, params, wp, t, timed, car0, d_car0, d_tx, d_ty):
            "timing": "median of reps runs after warmup runs, between two events", "rows": rows, "sweep": sweep_doc}
     if a.parent:
         doc["parent_commit_rows_same_session"] = json.load(open(a.parent))["rows"]
+    json.dump(doc, open(a.out, "w"), indent=1)
+    print("wrote", a.out)
+
+
+def latency_grid(a, pkg, params, wp, t, d_tx, d_ty):
+    import torch
+    n_d, n_c, n_cars, steps = a.delays, a.comps, a.cars, a.sweep_steps
+    delays_ms, comps_s = [10 * q for q in range(n_d)], [0.01 * q for q in range(n_c)]
+    cells = n_d * n_c
+    B = cells * n_cars
+    lat = pkg.scenarios.latency_grid(B, params, delays_ms, comps_s, a.period)
+    cars = np.repeat(pkg.scenarios.track_starts(n_cars, params, wp, seed=124), cells, axis=1)      # car c of every cell: the same start
+    with pkg.BatchedMPC(params, B, device=0) as mpc:
+        opts = mpc.drive_opts(warm_start=1)
+        run = lambda: mpc.drive_torch(t(cars), d_tx, d_ty, steps, opts=opts, fused=True, want_hist=False, latency=t(lat))
+        run(); torch.cuda.synchronize()                                                           # (the first call grows the handle's rows)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        res = run()
+        e1.record()
+        torch.cuda.synchronize()
+        info = mpc.drive_info()
+    # column = car * cells + delay * n_c + comp
+    summ = res["summary"].cpu().numpy().reshape(8, n_cars, n_d, n_c)
+    iters = res["iters"].cpu().numpy().reshape(n_cars, n_d, n_c) / float(steps)
+    off = (summ[6] >= 0).sum(0)
+    print("cars off the road of %d, rows: stale command time 0 .. %d ms, columns: compensated time 0 .. %d ms" % (n_cars, delays_ms[-1], 10 * (n_c - 1)))
+    for q in range(n_d):
+        print("%4d ms  " % delays_ms[q] + " ".join("%3d" % v for v in off[q]))
+    doc = {"tool": "tools/drive_bench.py --latency", "config": a.config, "device": torch.cuda.get_device_name(0),
+           "call": "mpc_drive_batch_device_fused_latency, warm_start = 1, hist = NULL, one timed call after one untimed", "B": B, "steps": steps,
+           "delays_ms": delays_ms, "comps_s": comps_s, "cars_per_cell": n_cars, "period_substeps": a.period, "cte_limit": opts.cte_limit,
+           "ms": float(e0.elapsed_time(e1)), "solves_per_s": B * steps / (1e-3 * float(e0.elapsed_time(e1))), "drive_info": info,
+           "cars_off_the_road": off.tolist(), "max_abs_cte_median": np.median(summ[0], axis=0).tolist(),
+           "failed_steps_mean": summ[7].mean(0).tolist(), "iterations_per_solve": iters.mean(0).tolist(),
+           "iterations_per_solve_along_the_compensation_axis": iters.mean((0, 1)).tolist(),
+           "iterations_per_solve_along_the_stale_time_axis": iters.mean((0, 2)).tolist(),
+           "iterations_per_solve_by_compensation_minus_stale_time_ms": {
+               str(10 * d): float(np.mean([iters[:, q, q + d].mean() for q in range(n_d) if 0 <= q + d < n_c]))
+               for d in range(-(n_d - 1), n_c) if any(0 <= q + d < n_c for q in range(n_d))}}
+    print("one launch: %d cars x %d messages in %.1f ms; iterations per solve along the compensation axis: %s" % (
+        B, steps, doc["ms"], " ".join("%.2f" % v for v in doc["iterations_per_solve_along_the_compensation_axis"])))
     json.dump(doc, open(a.out, "w"), indent=1)
     print("wrote", a.out)
 
