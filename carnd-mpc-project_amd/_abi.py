@@ -85,7 +85,7 @@ class MpcWarmOpts(C.Structure):
 EXPORTS = ["mpc_params_default", "mpc_params_load_json", "mpc_create", "mpc_set_params", "mpc_destroy",
            "mpc_last_error", "mpc_abi_version", "mpc_solve_batch_device", "mpc_solve_batch_host",
            "mpc_synchronize", "mpc_get_stats", "mpc_debug_math", "mpc_run_batch_device",
-           "mpc_telemetry_batch_device", "mpc_rollout_batch_device", "mpc_debug_math_ext",
+           "mpc_telemetry_batch_device", "mpc_rollout_batch_device", "mpc_debug_math_ext", "mpc_debug_math_all",
            "mpc_solve_batch_device_f32", "mpc_wire_parse", "mpc_wire_format_steer", "mpc_wire_format_manual",
            "mpc_wire_telemetry_batch_host", "mpc_telemetry_batch_host", "mpc_handle_device",
            "mpc_run_batch_host", "mpc_last_batch_id", "mpc_tail_poll", "mpc_tail_wait", "mpc_tail_stream_wait", "mpc_tail_flush", "mpc_tail_pending", "mpc_tail_info", "mpc_solve_batch_host_f32", "mpc_inflight_advice", "mpc_take_order_info",
@@ -177,6 +177,7 @@ def library():
     L.mpc_get_stats.argtypes = [C.c_void_p, C.POINTER(MpcBatchStats)]
     L.mpc_debug_math.argtypes = [C.c_int, C.c_int64] + [C.c_void_p] * 4
     L.mpc_debug_math_ext.argtypes = [C.c_int, C.c_int64] + [C.c_void_p] * 6
+    L.mpc_debug_math_all.argtypes = [C.c_int, C.c_int64] + [C.c_void_p] * 3
     L.mpc_handle_device.argtypes = [C.c_void_p]
     L.mpc_inflight_advice.argtypes = [C.c_void_p, C.c_int64]
     L.mpc_inflight_advice.restype = C.c_int

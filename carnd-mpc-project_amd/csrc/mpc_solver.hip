@@ -1252,6 +1252,25 @@ __global__ void mpc_debug_math_kernel(int64_t n, const double *x, double *sn, do
   at[i] = mpc::fatan(x[i]); lg[i] = mpc::flog(fabs(x[i]));
 }
 
+/* ten rows of mpc_debug_math_all for one real type: fsincos2 with an argument of its own in each slot, the two reciprocals, atan,
+ * log and hpow at the solver's two exponents; out points at this lane's column, rows are n apart */
+template <class R>
+__device__ __forceinline__ void debug_math_rows(R x, R y, double *out, int64_t n) {
+  R sa, ca, sb, cb;
+  mpc::fsincos2(x, y, &sa, &ca, &sb, &cb);
+  out[0] = (double)sa; out[n] = (double)ca; out[2 * n] = (double)sb; out[3 * n] = (double)cb;
+  out[4 * n] = (double)mpc::frcp(x); out[5 * n] = (double)mpc::frcp1(x);
+  out[6 * n] = (double)mpc::fatan(x); out[7 * n] = (double)mpc::flog(x);
+  out[8 * n] = (double)mpc::hpow(x, mpc::IpmConst<R>::s_theta); out[9 * n] = (double)mpc::hpow(x, mpc::IpmConst<R>::s_phi);
+}
+__global__ __launch_bounds__(256) void mpc_debug_math_all_kernel(int64_t n, const double *x, const double *y, double *out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double xi = x[i], yi = y[i];
+  debug_math_rows<double>(xi, yi, out + i, n);
+  debug_math_rows<float>((float)xi, (float)yi, out + 10 * n + i, n);
+}
+
 }  // namespace
 
 /* ---- host side from here on ---------------------------------------------------------------------------------------------------- */
@@ -3513,6 +3532,27 @@ extern "C" int mpc_debug_math_ext(int device, int64_t n, const double *x, double
   for (int q = 0; q < 5 && e == hipSuccess; q++) e = hipMemcpy(outs[q], d + (q + 1) * n, sizeof(double) * n, hipMemcpyDeviceToHost);
   (void)hipFree(d);
   if (e != hipSuccess) { g_last_error = std::string("mpc_debug_math: ") + hipGetErrorString(e); return MPC_ERR_HIP; }
+  return MPC_OK;
+}
+
+extern "C" int mpc_debug_math_all(int device, int64_t n, const double *x, const double *y, double *out) {
+  if (n < 0 || n > (int64_t)1 << 24 || (n > 0 && (!x || !y || !out))) return MPC_ERR_INVALID;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_last_error = "no HIP device"; return MPC_ERR_NO_DEVICE; }
+  if (device >= 0) MPC_HIP_CHECK(hipSetDevice(device));
+  if (n == 0) return MPC_OK;
+  const size_t rows = MPC_DEBUG_MATH_ROWS, un = (size_t)n;
+  double *d = nullptr;   /* x, y, then the rows */
+  MPC_HIP_CHECK(hipMalloc((void **)&d, sizeof(double) * (rows + 2) * un));
+  hipError_t e = hipMemcpy(d, x, sizeof(double) * un, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d + un, y, sizeof(double) * un, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(mpc_debug_math_all_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, n, d, d + un, d + 2 * un);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(out, d + 2 * un, sizeof(double) * rows * un, hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  if (e != hipSuccess) { g_last_error = std::string("mpc_debug_math_all: ") + hipGetErrorString(e); return MPC_ERR_HIP; }
   return MPC_OK;
 }
 

@@ -700,6 +700,14 @@ int mpc_get_stats(MpcHandle *h, MpcBatchStats *stats);
 int mpc_debug_math(int device, int64_t n, const double *x, double *sn, double *cs, double *rc);
 /* the same plus at[i] = atan(x[i]) and lg[i] = log|x[i]| (the solver's own atan and log kernels) */
 int mpc_debug_math_ext(int device, int64_t n, const double *x, double *sn, double *cs, double *rc, double *at, double *lg);
+/* Every light-weight math function of csrc/mpc_core.h at n points, one point per lane (test infrastructure like the two above, not
+ * product API; tests/test_math_conformance.py).  out is [MPC_DEBUG_MATH_ROWS][n]:
+ *   rows 0..9   fp64: fsincos2(x, y) -> sin x, cos x, sin y, cos y;  frcp(x), frcp1(x), fatan(x), flog(x);
+ *                     hpow(x, 1.1), hpow(x, 2.3) (the two exponents of the line search's switching condition)
+ *   rows 10..19 fp32: the same ten from (float)x, (float)y, widened exactly
+ * flog and hpow get x as it comes (no fabs): the caller sends only what it means to send. */
+#define MPC_DEBUG_MATH_ROWS 20
+int mpc_debug_math_all(int device, int64_t n, const double *x, const double *y, double *out);
 
 #ifdef __cplusplus
 }

@@ -59,6 +59,24 @@ extern "C" void mpc_host_twin_math_f32(int64_t n, const float *x, float *sn, flo
 extern "C" void mpc_host_twin_math2(int64_t n, const double *x, double *at, double *lg) {
   for (int64_t i = 0; i < n; i++) { at[i] = mpc::fatan(x[i]); lg[i] = mpc::flog(fabs(x[i])); }
 }
+/* mpc_debug_math_all of the library on the CPU: the same rows ([MPC_DEBUG_MATH_ROWS][n]) from the same mpc:: functions */
+template <class R>
+static void twin_math_rows(R x, R y, double *out, int64_t n) {
+  R sa, ca, sb, cb;
+  mpc::fsincos2(x, y, &sa, &ca, &sb, &cb);
+  out[0] = (double)sa; out[n] = (double)ca; out[2 * n] = (double)sb; out[3 * n] = (double)cb;
+  out[4 * n] = (double)mpc::frcp(x); out[5 * n] = (double)mpc::frcp1(x);
+  out[6 * n] = (double)mpc::fatan(x); out[7 * n] = (double)mpc::flog(x);
+  out[8 * n] = (double)mpc::hpow(x, mpc::IpmConst<R>::s_theta); out[9 * n] = (double)mpc::hpow(x, mpc::IpmConst<R>::s_phi);
+}
+extern "C" int mpc_host_twin_math_all(int64_t n, const double *x, const double *y, double *out) {
+  if (n < 0 || (n > 0 && (!x || !y || !out))) return MPC_ERR_INVALID;
+  for (int64_t i = 0; i < n; i++) {
+    twin_math_rows<double>(x[i], y[i], out + i, n);
+    twin_math_rows<float>((float)x[i], (float)y[i], out + 10 * n + i, n);
+  }
+  return MPC_OK;
+}
 
 /* MPC::run pre/post-processing of the device header, one instance at a time (struct-of-arrays I/O like the ABI):
  * pose[6][ld], pts[npts][ld] in/out, pre[RUN_PRE_ROWS][ld] (the rows: mpc_run_core.h) */
