@@ -117,7 +117,9 @@ CERT_VERDICT_NAMES = {0: "converged", 1: "acceptable", 2: "not_converged", 3: "n
 DRIVE_EXPORTS = ["mpc_drive_opts_default", "mpc_drive_batch_device", "mpc_drive_batch_device_fused", "mpc_drive_batch_host", "mpc_drive_info",
                  "mpc_drive_batch_device_model", "mpc_drive_batch_device_fused_model", "mpc_drive_batch_host_model",
                  "mpc_drive_batch_device_latency", "mpc_drive_batch_device_fused_latency", "mpc_drive_batch_host_latency",
-                 "mpc_telemetry_batch_device_latency", "mpc_telemetry_batch_host_latency"]
+                 "mpc_telemetry_batch_device_latency", "mpc_telemetry_batch_host_latency",
+                 "mpc_drive_batch_device_horizon", "mpc_drive_batch_device_fused_horizon", "mpc_drive_batch_host_horizon",
+                 "mpc_telemetry_batch_device_horizon", "mpc_telemetry_batch_host_horizon"]
 NLATENCY = 3     # MPC_NLATENCY: rows of a latency array, [NLATENCY][ld] (the mpc_drive_*_latency entry points)
 LATENCY_COMP, LATENCY_SUB_OLD, LATENCY_SUB_NEW = range(NLATENCY)
 DRIVE_MAX_TRACK, DRIVE_NSUM, DRIVE_REC = 4096, 8, 13      # MPC_DRIVE_MAX_TRACK, rows of summary [NSUM][ld], rows of a step of hist [REC][ld]
@@ -234,6 +236,13 @@ def library():
     tel_head = H + [C.c_int, DP, C.c_double]
     for name in ("mpc_telemetry_batch_device", "mpc_telemetry_batch_host"):
         getattr(L, name + "_latency").argtypes = tel_head + [DP] + getattr(L, name + "_warm_model").argtypes[len(tel_head):]
+    # ... and the _horizon forms of both: the _latency form plus `horizon` (one pointer) directly behind `model`
+    for name in ("mpc_drive_batch_host", "mpc_drive_batch_device", "mpc_drive_batch_device_fused"):
+        at = len(drive_head) + 1
+        getattr(L, name + "_horizon").argtypes = getattr(L, name + "_latency").argtypes[:at] + [DP] + getattr(L, name + "_latency").argtypes[at:]
+    for name in ("mpc_telemetry_batch_device", "mpc_telemetry_batch_host"):
+        at = len(tel_head) + 4      # (comp, ptsx, ptsy, model)
+        getattr(L, name + "_horizon").argtypes = getattr(L, name + "_latency").argtypes[:at] + [DP] + getattr(L, name + "_latency").argtypes[at:]
     L.mpc_drive_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.mpc_solve_batch_device_f32.argtypes = L.mpc_solve_batch_device.argtypes      # (the same pointers, to floats)
     L.mpc_solve_batch_host_f32.argtypes = L.mpc_solve_batch_host.argtypes

@@ -237,6 +237,9 @@ struct MpcHorizonPart {
  * With MODEL (mpc_drive_batch_device_fused_model): the car's column of T.model -- the caller's array, rows T.ld_model = ldo apart -- is
  * read by instance index at the take (the pre-solve half, set-up) and again at the hand-over (unpack, the post-solve half, the plant);
  * it is not carried across the sweeps.
+ * With HORIZON (mpc_drive_batch_device_fused_horizon; a MODEL build by construction): the car's horizon is read by instance index in the
+ * same two places, through instance_column; T.model may be nullptr there, and drive_model_vals then hands the handle's own six values
+ * to the handler's halves and the plant.  These two builds are not staged and address their rows per lane, like every HORIZON build.
  * latency (mpc_drive_batch_device_fused_latency): the car's column of [MPC_NLATENCY][ldo], or nullptr -- the call's own extra_latency and
  * substep counts, the very values the builds read before this pointer existed.  Read like the model column: by instance index at the
  * take (what the pre-solve half compensates for) and again at the hand-over (the plant's counts), and not carried in between.  A
@@ -376,9 +379,10 @@ __device__ __forceinline__ auto instance_column(const Phase &T, int64_t ld, int6
 }
 /* ... and the same column as the values mpc_run_core.h and mpc_drive_core.h read (DRIVE builds): the handle's MpcParams itself without
  * MODEL, so that those builds read every field from P where it is used */
-template <bool MODEL, class Phase>
+template <bool MODEL, bool HORIZON = false, class Phase>
 __device__ __forceinline__ decltype(auto) drive_model_vals(const MpcParams &P, const Phase &T, int64_t i) {
-  if constexpr (MODEL) return mpc::model_vals_of(P, T.model, T.ld_model, i);
+  if constexpr (HORIZON) return T.model ? mpc::model_vals_of(P, T.model, T.ld_model, i) : mpc::ModelVals::of(P);      /* (a horizon call's `model` may be nullptr: the handle's six values) */
+  else if constexpr (MODEL) return mpc::model_vals_of(P, T.model, T.ld_model, i);
   else return (P);
 }
 
@@ -429,7 +433,7 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
     const int64_t tile_reals,
     const MpcPhaseOf<ROLL, WARM, MODEL, HORIZON, DRIVE> T) {
   extern __shared__ double smem[];
-  static_assert(!DRIVE || (ROLL && !HORIZON && !SOC), "track driving: a ROLL build without HORIZON and SOC");
+  static_assert(!DRIVE || (ROLL && !SOC), "track driving: a ROLL build without SOC");
   static_assert(!HORIZON || (MODEL && !STAGING && !SOC), "per-instance horizon: a MODEL build without staging and SOC");
   static_assert(!WARM || (sizeof(R) == 8 && std::is_same<R, RIO>::value && std::is_same<R, RSRC>::value && !SOC), "warm start: the plain fp64 solve only");
   static_assert(!ROLL || (sizeof(R) == 8 && std::is_same<R, RIO>::value && std::is_same<R, RSRC>::value && !SOC), "fused rollout: the plain fp64 solve only");
@@ -511,7 +515,7 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
                 S.warm_store([wo, lw](int k, int f, R v) { wo[(int64_t)(k * MPC_WARM_REC + f) * lw] = v; });
               }
               /* (MODEL: the car's column, read again here -- it is not carried across the sweeps) */
-              const auto &mv = drive_model_vals<MODEL>(P, T, i);
+              const auto &mv = drive_model_vals<MODEL, HORIZON>(P, T, i);
               mpc::run_post_instance(P, mv, i, T.pre, ld, T.out9, ldo, (double *)nullptr, T.cmd, ldo);
               int sub_old = T.O.sub_old, sub_new = T.O.sub_new;
               if (T.latency) {
@@ -601,7 +605,7 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
               mpc::drive_window_points(T.track_x, T.track_y, T.n_track, drive_k, T.O.npts, T.ptsx, T.ptsy, ldo, i);
               mpc::RunComp lc{false, T.O.extra_latency};
               if (T.latency) lc = mpc::RunComp{true, mpc::drive_latency_of(T.O, T.latency, ldo, i).comp};
-              (void)mpc::run_pre_instance<true>(P, drive_model_vals<MODEL>(P, T, i), i, ldo, T.O.npts, T.car, lc, T.ptsx, T.ptsy, T.pre, ld);
+              (void)mpc::run_pre_instance<true>(P, drive_model_vals<MODEL, HORIZON>(P, T, i), i, ldo, T.O.npts, T.car, lc, T.ptsx, T.ptsy, T.pre, ld);
               mpc::gather_instance(P, i, ld, T.pre + mpc::RUN_PRE_STATE * ld, T.pre + mpc::RUN_PRE_COEFFS * ld, weights, st, cf, w);
               ylo_in = (R)T.pre[mpc::RUN_PRE_YAW_LO * ld + i]; yhi_in = (R)T.pre[mpc::RUN_PRE_YAW_HI * ld + i];
             } else {
@@ -2549,7 +2553,9 @@ extern "C" int mpc_solve_batch_device_f32(MpcHandle *h, int64_t B, int64_t ld, c
  * into the box run_pre derives for this call (mpc::WarmColumn).  x.model (device, [MPC_NMODEL][ld]): the MODEL
  * forms of the pre and post kernels, and a model solve between them that reads its inputs from the handle's rows at the handle's
  * stride and the columns from the caller's array at the caller's ld (CallExtras::ld_model) -- the array is not copied.
- * x.latency (device, comp [ld], with tel): the pre kernel's build that compensates per instance; `extra` is not read. */
+ * x.latency (device, comp [ld], with tel): the pre kernel's build that compensates per instance; `extra` is not read.
+ * x.horizon (device, [ld] int32): the solve between the two kernels is the horizon solve -- the lane kernel's HORIZON build at every
+ * B, cold or warm, with or without model; the pre and post kernels do not read N and are the builds `model` alone selects. */
 static int run_impl(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, bool tel, double extra, double *ptsx,
                     double *ptsy, double *out8, double *cmd, double *traj, int32_t *status, int32_t *iters, double *pre,
                     void *stream_, CallExtras x) {
@@ -2588,7 +2594,7 @@ static int run_impl(MpcHandle *h, int64_t B, int64_t ld, int npts, const double 
     });
   });
   MPC_HIP_CHECK(hipGetLastError());
-  x.w.psi_box = 1; x.ld_model = ld; x.model_wave = true;      /* the run() path's own */
+  x.w.psi_box = 1; x.ld_model = ld; x.model_wave = !x.horizon;      /* the run() path's own (a horizon call has no wave path: the lane kernel's HORIZON build at every B) */
   MPC_TRY(launch_solve<double>(h, {B, S, ld, d_pre + mpc::RUN_PRE_STATE * S, d_pre + mpc::RUN_PRE_COEFFS * S, d_pre + mpc::RUN_PRE_YAW_LO * S,
                                    d_pre + mpc::RUN_PRE_YAW_HI * S, x.run_weights, h->d_run9, traj, status, iters}, stream_, kStats, x));
   around([&](auto model_build, auto... mp) {
@@ -2650,12 +2656,20 @@ extern "C" int mpc_run_batch_device_warm_model(MpcHandle *h, int64_t B, int64_t 
                   call_extras(h, model, true, warm_in, warm_status, warm_out, ld_warm, opts));
 }
 
+/* (include/mpc_amd_drive.h, "per-car horizon": the _latency form plus `horizon` behind model; NULL is the _latency form itself) */
+extern "C" int mpc_telemetry_batch_device_horizon(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
+                                                  const double *comp, double *ptsx, double *ptsy, const double *model, const int32_t *horizon,
+                                                  const double *warm_in, const int32_t *warm_status, double *warm_out, int64_t ld_warm,
+                                                  const MpcWarmOpts *opts, double *cmd, double *out8, int32_t *status, void *stream_) {
+  return run_impl(h, B, ld, npts, tel, true, extra_latency, ptsx, ptsy, out8, cmd, nullptr, status, nullptr, nullptr, stream_,
+                  call_extras(h, model, true, warm_in, warm_status, warm_out, ld_warm, opts, horizon, comp));
+}
 extern "C" int mpc_telemetry_batch_device_latency(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
                                                   const double *comp, double *ptsx, double *ptsy, const double *model, const double *warm_in,
                                                   const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts,
                                                   double *cmd, double *out8, int32_t *status, void *stream_) {
-  return run_impl(h, B, ld, npts, tel, true, extra_latency, ptsx, ptsy, out8, cmd, nullptr, status, nullptr, nullptr, stream_,
-                  call_extras(h, model, true, warm_in, warm_status, warm_out, ld_warm, opts, nullptr, comp));
+  return mpc_telemetry_batch_device_horizon(h, B, ld, npts, tel, extra_latency, comp, ptsx, ptsy, model, nullptr, warm_in, warm_status, warm_out, ld_warm, opts,
+                                            cmd, out8, status, stream_);
 }
 extern "C" int mpc_telemetry_batch_device_warm_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
                                                      double *ptsx, double *ptsy, const double *model, const double *warm_in,
@@ -2708,7 +2722,8 @@ extern "C" void mpc_internal_set_error(const char *msg) { g_last_error = msg ? m
 /* The telemetry handler for host arrays: one copy in, the kernels, one copy out, on the handle's own device and stream
  * (whatever the caller's current device is), staging kept on the handle.  rows of `tel`, `ptsx`, `ptsy` as in
  * mpc_telemetry_batch_device with leading dimension ld; the waypoint arrays are inputs only here.  x.model (host, [MPC_NMODEL][ld]):
- * six more rows of the staging block, copied in with the other inputs; x.latency (host, comp [ld]): one more. */
+ * six more rows of the staging block, copied in with the other inputs; x.latency (host, comp [ld]): one more; x.horizon (host, [ld]
+ * int32): copied to h->d_horizon. */
 static int telemetry_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency, const double *ptsx,
                           const double *ptsy, double *cmd, int32_t *status, const CallExtras &x) {
   MPC_TRY(x.refused);
@@ -2730,6 +2745,11 @@ static int telemetry_host(MpcHandle *h, int64_t B, int64_t ld, int npts, const d
   CallExtras dx;
   MPC_TRY(host_extras_in(h, B, x, x.model ? d_model : nullptr, s, &dx));
   if (x.latency) dx.latency = d_comp;
+  if (x.horizon) {
+    MPC_TRY(ensure_dev(&h->d_horizon, sizeof(int32_t) * (size_t)h->io_stride));
+    MPC_HIP_CHECK(hipMemcpyAsync(h->d_horizon, x.horizon, sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
+    dx.horizon = h->d_horizon;
+  }
   MPC_TRY(run_impl(h, B, L, npts, d, true, extra_latency, d + 6 * L, d + (6 + npts) * L, nullptr, d_cmd, nullptr, d_st, nullptr, nullptr, (void *)s, dx));
   MPC_TRY(host_extras_out(h, B, x, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(cmd, sizeof(double) * ld, d_cmd, sizeof(double) * L, sizeof(double) * B, 2, hipMemcpyDeviceToHost, s));
@@ -2755,12 +2775,19 @@ extern "C" int mpc_telemetry_batch_host_model(MpcHandle *h, int64_t B, int64_t l
   return telemetry_host(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, cmd, status, call_extras(h, model));
 }
 
+extern "C" int mpc_telemetry_batch_host_horizon(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
+                                                const double *comp, const double *ptsx, const double *ptsy, const double *model, const int32_t *horizon,
+                                                const double *warm_in, const int32_t *warm_status, double *warm_out, int64_t ld_warm,
+                                                const MpcWarmOpts *opts, double *cmd, int32_t *status) {
+  return telemetry_host(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, cmd, status,
+                        call_extras(h, model, true, warm_in, warm_status, warm_out, ld_warm, opts, horizon, comp));
+}
 extern "C" int mpc_telemetry_batch_host_latency(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
                                                 const double *comp, const double *ptsx, const double *ptsy, const double *model, const double *warm_in,
                                                 const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts,
                                                 double *cmd, int32_t *status) {
-  return telemetry_host(h, B, ld, npts, tel, extra_latency, ptsx, ptsy, cmd, status,
-                        call_extras(h, model, true, warm_in, warm_status, warm_out, ld_warm, opts, nullptr, comp));
+  return mpc_telemetry_batch_host_horizon(h, B, ld, npts, tel, extra_latency, comp, ptsx, ptsy, model, nullptr, warm_in, warm_status, warm_out, ld_warm, opts, cmd,
+                                          status);
 }
 extern "C" int mpc_telemetry_batch_host_warm_model(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
                                                    const double *ptsx, const double *ptsy, const double *model, const double *warm_in,
@@ -3097,23 +3124,31 @@ static int drive_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *ca
 /* What every drive entry point does first: with `model`, the model rule (which handles a model call is accepted on, call_extras);
  * drive_args; then the call's extras -- the warm refusals and the options in effect. */
 static int drive_call(const MpcHandle *h, int64_t B, int64_t ld, int steps, const double *car, const double *track_x, const double *track_y,
-                      int n_track, const double *model, const double *latency, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts,
-                      const double *summary, const int32_t *status, MpcDriveOpts *O, CallExtras *x) {
-  if (h && model) MPC_TRY(call_extras(h, model).refused);
+                      int n_track, const double *model, const int32_t *horizon, const double *latency, const MpcDriveOpts *opts,
+                      const MpcWarmOpts *warm_opts, const double *summary, const int32_t *status, MpcDriveOpts *O, CallExtras *x) {
+  if (h && (model || horizon)) MPC_TRY(call_extras(h, model, false, nullptr, nullptr, nullptr, 0, nullptr, horizon).refused);
   MPC_TRY(drive_args(h, B, ld, steps, car, track_x, track_y, n_track, opts, summary, status, O));
-  *x = call_extras(h, model, O->warm_start != 0, nullptr, nullptr, nullptr, 0, warm_opts, nullptr, latency);
+  *x = call_extras(h, model, O->warm_start != 0, nullptr, nullptr, nullptr, 0, warm_opts, horizon, latency);
   return x->refused;
 }
 
+/* (the _horizon forms, "per-car horizon" in include/mpc_amd_drive.h: the _latency forms plus `horizon` behind model; NULL is the _latency form itself) */
+extern "C" int mpc_drive_batch_device_horizon(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
+                                              const double *track_y, int n_track, const double *weights, const double *model, const int32_t *horizon,
+                                              const double *latency, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary,
+                                              double *hist, int32_t *status, int32_t *iters, void *stream_) {
+  MpcDriveOpts O;
+  CallExtras x;
+  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, horizon, latency, opts, warm_opts, summary, status, &O, &x));
+  if (B == 0) { h->last_B = 0; return MPC_OK; }
+  return drive_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
+}
 extern "C" int mpc_drive_batch_device_latency(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
                                               const double *track_y, int n_track, const double *weights, const double *model, const double *latency,
                                               const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist,
                                             int32_t *status, int32_t *iters, void *stream_) {
-  MpcDriveOpts O;
-  CallExtras x;
-  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, latency, opts, warm_opts, summary, status, &O, &x));
-  if (B == 0) { h->last_B = 0; return MPC_OK; }
-  return drive_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
+  return mpc_drive_batch_device_horizon(h, B, ld, steps, car, track_x, track_y, n_track, weights, model, nullptr, latency, opts, warm_opts, summary, hist, status,
+                                        iters, stream_);
 }
 extern "C" int mpc_drive_batch_device_model(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
                                             const double *track_y, int n_track, const double *weights, const double *model,
@@ -3133,13 +3168,16 @@ extern "C" int mpc_drive_batch_device(MpcHandle *h, int64_t B, int64_t ld, int s
  * messages.  rollout_fused_impl's rule decides: the one launch runs where the stepwise loop would launch exactly the single-phase fp64
  * lane kernel at every step (no fp32 start, no SOC, B above the wave limit); everywhere else the call IS the stepwise loop.
  * x.model: the DRIVE x MODEL builds, where the stepwise model loop launches the lane kernel's MODEL build at every step -- the same
- * rule, but on a handle whose ordinary solve starts in fp32 as well: a model solve is the single-phase fp64 launch on h->ws there. */
+ * rule, but on a handle whose ordinary solve starts in fp32 as well: a model solve is the single-phase fp64 launch on h->ws there.
+ * x.horizon: the DRIVE x MODEL x HORIZON builds (cold, WARM), where the stepwise horizon loop launches the lane kernel's HORIZON build
+ * at every step: every B >= 1 of every fp64 handle without SOC. */
 static int drive_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y, int n_track,
                             const double *weights, const MpcDriveOpts &O, const CallExtras &x, double *summary, double *hist, int32_t *status,
                             int32_t *iters, void *stream_) {
-  const bool wave_path = h->wave_max_batch > 0 && B <= h->wave_max_batch;
+  /* (a horizon call never takes the wave path or the fp32 start: the one launch at every B >= 1, the rule of rollout_fused_impl) */
+  const bool wave_path = !x.horizon && h->wave_max_batch > 0 && B <= h->wave_max_batch;
   const double *model = x.model;
-  if ((h->mixed && !model) || h->params.max_soc > 0 || wave_path)
+  if ((h->mixed && !x.model_call()) || h->params.max_soc > 0 || wave_path)
     return drive_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
   MPC_TRY(check_batch(h, B, ld));
   if (h->params.n_yaw_change_speeds < 1 || h->params.n_steer_speeds < 1) { g_last_error = "run(): empty speed tables (load a config-*.json)"; return MPC_ERR_INVALID; }
@@ -3170,6 +3208,14 @@ static int drive_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, doub
   const MpcRollPart roll{steps, nullptr, 0, nullptr, status, iters};
   const MpcDrivePart drive{O, car, track_x, track_y, n_track, ptsx, ptsy, cmd, d_pre, h->d_run9, summary, hist, x.latency};
   const unsigned grid = (unsigned)((B + kBlock - 1) / kBlock);
+  if (x.horizon) {
+    /* the DRIVE x HORIZON builds: MODEL builds whose `model` may be nullptr, not staged, per-lane workspace rows, no LDS (no lane compaction here) */
+    MPC_TRY(with_bool(x.warm, [&](auto warm_build) {
+      constexpr bool WARM = decltype(warm_build)::value;
+      return launch_kernel(mpc_solve_kernel<false, double, double, double, false, WARM, true, true, true, true>, grid, 0, s, h, io, (double *)h->ws, h->ws_stride,
+                           phase_of<true, WARM, true, true, true>(T, wc, roll, {model, ld}, {x.horizon}, drive));
+    }));
+  } else
   MPC_TRY(with_bool(h->staging, [&](auto staging) {
     return with_bool(x.warm, [&](auto warm_build) {
       return with_bool(model != nullptr, [&](auto model_build) {
@@ -3184,15 +3230,23 @@ static int drive_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, doub
   return record_stats(h, B, status, iters, s);
 }
 
+extern "C" int mpc_drive_batch_device_fused_horizon(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
+                                                    const double *track_y, int n_track, const double *weights, const double *model,
+                                                    const int32_t *horizon, const double *latency, const MpcDriveOpts *opts,
+                                                    const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status, int32_t *iters,
+                                                    void *stream_) {
+  MpcDriveOpts O;
+  CallExtras x;
+  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, horizon, latency, opts, warm_opts, summary, status, &O, &x));
+  if (B == 0) { h->last_B = 0; return MPC_OK; }
+  return drive_fused_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
+}
 extern "C" int mpc_drive_batch_device_fused_latency(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
                                                     const double *track_y, int n_track, const double *weights, const double *model,
                                                     const double *latency, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist,
                                                   int32_t *status, int32_t *iters, void *stream_) {
-  MpcDriveOpts O;
-  CallExtras x;
-  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, latency, opts, warm_opts, summary, status, &O, &x));
-  if (B == 0) { h->last_B = 0; return MPC_OK; }
-  return drive_fused_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
+  return mpc_drive_batch_device_fused_horizon(h, B, ld, steps, car, track_x, track_y, n_track, weights, model, nullptr, latency, opts, warm_opts, summary, hist,
+                                              status, iters, stream_);
 }
 extern "C" int mpc_drive_batch_device_fused_model(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
                                                   const double *track_y, int n_track, const double *weights, const double *model,
@@ -3209,14 +3263,15 @@ extern "C" int mpc_drive_batch_device_fused(MpcHandle *h, int64_t B, int64_t ld,
 }
 
 /* The same for host arrays: one copy in, the loop on the handle's own device and stream, one copy out; synchronises.  Staging kept on
- * the handle and grown on demand, like the telemetry handler's.  model (host, [MPC_NMODEL][ld]) and latency (host, [MPC_NLATENCY][ld])
- * are copied in with the other inputs. */
-extern "C" int mpc_drive_batch_host_latency(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
-                                            int n_track, const double *weights, const double *model, const double *latency, const MpcDriveOpts *opts,
-                                          const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status, int32_t *iters) {
+ * the handle and grown on demand, like the telemetry handler's.  model (host, [MPC_NMODEL][ld]), latency (host, [MPC_NLATENCY][ld]) and
+ * horizon (host, [ld] int32, to h->d_horizon) are copied in with the other inputs. */
+extern "C" int mpc_drive_batch_host_horizon(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                                            int n_track, const double *weights, const double *model, const int32_t *horizon, const double *latency,
+                                            const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status,
+                                            int32_t *iters) {
   MpcDriveOpts O;
   CallExtras x;
-  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, latency, opts, warm_opts, summary, status, &O, &x));
+  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, horizon, latency, opts, warm_opts, summary, status, &O, &x));
   if (B == 0) { h->last_B = 0; return MPC_OK; }
   MPC_ON_DEVICE(h);
   const int64_t L = (B + 7) / 8 * 8;
@@ -3239,6 +3294,11 @@ extern "C" int mpc_drive_batch_host_latency(MpcHandle *h, int64_t B, int64_t ld,
     MPC_HIP_CHECK(hipMemcpy2DAsync(d_lat, sizeof(double) * L, latency, sizeof(double) * ld, sizeof(double) * B, MPC_NLATENCY, hipMemcpyHostToDevice, s));
     x.latency = d_lat;
   }
+  if (horizon) {
+    MPC_TRY(ensure_dev(&h->d_horizon, sizeof(int32_t) * (size_t)h->io_stride));
+    MPC_HIP_CHECK(hipMemcpyAsync(h->d_horizon, horizon, sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
+    x.horizon = h->d_horizon;
+  }
   MPC_HIP_CHECK(hipMemcpyAsync(d_tx, track_x, sizeof(double) * n_track, hipMemcpyHostToDevice, s));
   MPC_HIP_CHECK(hipMemcpyAsync(d_ty, track_y, sizeof(double) * n_track, hipMemcpyHostToDevice, s));
   MPC_TRY(drive_impl(h, B, L, steps, d_car, d_tx, d_ty, n_track, weights ? d_w : nullptr, O, x, d_sum, hist ? d_hist : nullptr, d_st, d_it, (void *)s));
@@ -3249,6 +3309,12 @@ extern "C" int mpc_drive_batch_host_latency(MpcHandle *h, int64_t B, int64_t ld,
   if (iters) MPC_HIP_CHECK(hipMemcpyAsync(iters, d_it, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipStreamSynchronize(s));
   return MPC_OK;
+}
+extern "C" int mpc_drive_batch_host_latency(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                                            int n_track, const double *weights, const double *model, const double *latency, const MpcDriveOpts *opts,
+                                            const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status, int32_t *iters) {
+  return mpc_drive_batch_host_horizon(h, B, ld, steps, car, track_x, track_y, n_track, weights, model, nullptr, latency, opts, warm_opts, summary, hist, status,
+                                      iters);
 }
 extern "C" int mpc_drive_batch_host_model(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
                                           int n_track, const double *weights, const double *model, const MpcDriveOpts *opts,

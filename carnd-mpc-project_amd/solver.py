@@ -248,14 +248,16 @@ class BatchedMPC:
         return res
 
     def telemetry_torch(self, tel, ptsx, ptsy, extra_latency=0.0, want_out8=False, stream=None, warm=None, warm_status=None,
-                        want_warm=False, warm_opts=None, warm_out=None, status_out=None, model=None, comp=None):
+                        want_warm=False, warm_opts=None, warm_out=None, status_out=None, model=None, comp=None, horizon=None):
         """The telemetry handler around run() (src/mpc_main.cpp:126-174) for a batch: tel [6,B] = x, y, psi,
         speed [mph], steering_angle (simulator sign), previous throttle.  Returns cmd [2,B] = (steering_angle,
         throttle) of the reply, status, and optionally run()'s 8-vector.  The warm arguments are run_torch's
         (mpc_telemetry_batch_device_warm).  ``model`` [6, B] as in run_torch (mpc_telemetry_batch_device_model, _warm_model): each
         car's own Lf in the latency compensation and its own limits in the steering normalisation and the throttle.
         ``comp`` [B] float64 (mpc_telemetry_batch_device_latency; fp64 handles): the seconds every instance compensates for, in
-        the place of the handle's latency_ms / lookahead and of ``extra_latency``; 0: no compensation.  Always the warm form of the call."""
+        the place of the handle's latency_ms / lookahead and of ``extra_latency``; 0: no compensation.  Always the warm form of the call.
+        ``horizon`` [B] int32 (mpc_telemetry_batch_device_horizon; fp64 handles, max_soc = 0): every instance's own N, 3 .. the handle's,
+        as in solve_torch; the lane kernel's HORIZON build at every B.  With or without ``comp`` and ``model``; always the warm form."""
         import torch
         B = tel.shape[1]
         npts = ptsx.shape[0]
@@ -273,23 +275,27 @@ class BatchedMPC:
         warm_args = None
         if warm is not None or want_warm or warm_out is not None:
             warm_args = self._warm_args(res, B, dev, warm, warm_status, warm_out) + (C.byref(warm_opts) if warm_opts is not None else None,)
-        if comp is not None:
-            if comp.dtype != torch.float64 or not comp.is_cuda or not comp.is_contiguous() or tuple(comp.shape) != (B,):
+        if horizon is not None:
+            self._check_horizon(horizon, B)
+        if comp is not None or horizon is not None:
+            if comp is not None and (comp.dtype != torch.float64 or not comp.is_cuda or not comp.is_contiguous() or tuple(comp.shape) != (B,)):
                 raise ValueError("comp must be a contiguous float64 CUDA tensor of shape (B,)")
             if warm_args is None:
                 warm_args = (None, None, None, 0, C.byref(warm_opts) if warm_opts is not None else None)
-            check(library().mpc_telemetry_batch_device_latency(self._h, B, B, int(npts), tel.data_ptr(), float(extra_latency), comp.data_ptr(),
-                                                               ptsx.data_ptr(), ptsy.data_ptr(), model.data_ptr() if model is not None else None,
-                                                               *warm_args, *outs), "mpc_telemetry_batch_device_latency")
+            name = "mpc_telemetry_batch_device" + ("_horizon" if horizon is not None else "_latency")
+            hz = (horizon.data_ptr(),) if horizon is not None else ()
+            check(getattr(library(), name)(self._h, B, B, int(npts), tel.data_ptr(), float(extra_latency), comp.data_ptr() if comp is not None else None,
+                                           ptsx.data_ptr(), ptsy.data_ptr(), model.data_ptr() if model is not None else None, *hz,
+                                           *warm_args, *outs), name)
             return res
         self._call("mpc_telemetry_batch_device", (B, B, int(npts), tel.data_ptr(), float(extra_latency), ptsx.data_ptr(), ptsy.data_ptr()),
                    outs, model.data_ptr() if model is not None else None, warm_args)
         return res
 
-    def telemetry_numpy(self, tel, ptsx, ptsy, extra_latency=0.0, model=None, comp=None, warm_opts=None):
+    def telemetry_numpy(self, tel, ptsx, ptsy, extra_latency=0.0, model=None, comp=None, warm_opts=None, horizon=None):
         """telemetry_torch for host arrays through the _latency form (mpc_telemetry_batch_host_latency; without ``comp`` that is
         mpc_telemetry_batch_host_warm_model, started cold): one copy in, the kernels, one copy out; synchronises.  Returns "cmd" [2, B]
-        and "status".  ``model`` [6, B], ``comp`` [B]: as in telemetry_torch."""
+        and "status".  ``model`` [6, B], ``comp`` [B]: as in telemetry_torch; ``horizon`` [B] int32: mpc_telemetry_batch_host_horizon."""
         f = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64)) if a is not None else None
         tel, ptsx, ptsy, model, comp = f(tel), f(ptsx), f(ptsy), f(model), f(comp)
         B, npts = tel.shape[1], ptsx.shape[0]
@@ -301,9 +307,16 @@ class BatchedMPC:
             raise ValueError("comp must have shape (B,)")
         res = {"cmd": np.empty((2, B)), "status": np.empty(B, dtype=np.int32)}
         p = lambda a: a.ctypes.data if a is not None else None
-        check(library().mpc_telemetry_batch_host_latency(self._h, B, B, int(npts), p(tel), float(extra_latency), p(comp), p(ptsx), p(ptsy), p(model),
-                                                         None, None, None, 0, C.byref(warm_opts) if warm_opts is not None else None,
-                                                         p(res["cmd"]), p(res["status"])), "mpc_telemetry_batch_host_latency")
+        hz = ()
+        if horizon is not None:
+            horizon = np.ascontiguousarray(np.asarray(horizon))
+            if horizon.dtype != np.int32 or horizon.shape != (B,):
+                raise ValueError("horizon must be an int32 array of shape (B,)")
+            hz = (p(horizon),)
+        name = "mpc_telemetry_batch_host" + ("_horizon" if horizon is not None else "_latency")
+        check(getattr(library(), name)(self._h, B, B, int(npts), p(tel), float(extra_latency), p(comp), p(ptsx), p(ptsy), p(model), *hz,
+                                       None, None, None, 0, C.byref(warm_opts) if warm_opts is not None else None,
+                                       p(res["cmd"]), p(res["status"])), name)
         return res
 
     def rollout_torch(self, state, coeffs, yaw_lo, yaw_hi, steps, weights=None, want_hist=True, stream=None, warm_start=False,
@@ -350,7 +363,7 @@ class BatchedMPC:
         return _abi.drive_opts_default(self.params, **overrides)
 
     def drive_torch(self, car, track_x, track_y, steps, weights=None, opts=None, warm_opts=None, want_hist=True, fused=False, stream=None,
-                    model=None, latency=None):
+                    model=None, latency=None, horizon=None):
         """Drive B cars along a cyclic track for `steps` telemetry messages on the device (mpc_drive_batch_device): per message the
         waypoint window at the car's position, the telemetry handler (cold, or warm with opts.warm_start) and the plant -- the
         reference's own kinematic model, not the simulator.  car [6, B] = x, y, psi, speed [mph], steering_angle, throttle is advanced
@@ -363,11 +376,16 @@ class BatchedMPC:
         one call answers "how fast can this tuning go round the track" with a row of max_speed values.
         ``latency`` [3, B] float64 (mpc_drive_batch_device_latency, _fused_latency; rows _abi.LATENCY_*): every car's own compensated
         time [s] in the handler and its own sub_old / sub_new in the plant (scenarios.latency_grid builds a stale-time x compensation
-        grid) -- one call answers "how much delay does this tuning survive, compensated or not"."""
+        grid) -- one call answers "how much delay does this tuning survive, compensated or not".
+        ``horizon`` [B] int32 (mpc_drive_batch_device_horizon, _fused_horizon; fp64 handles, max_soc = 0): every car's own N, 3 .. the
+        handle's, in the handler's solve; with ``model``'s dt row an N x dt grid is the cars of one call.  The lane kernel at every B,
+        the one launch included; sort the cars by horizon (a wave's pass lasts as long as its longest one)."""
         import torch
         B = car.shape[1]
         if model is not None:
             self._check_model(model, B)
+        if horizon is not None:
+            self._check_horizon(horizon, B)
         if latency is not None and (latency.dtype != torch.float64 or not latency.is_cuda or not latency.is_contiguous() or
                                     tuple(latency.shape) != (_abi.NLATENCY, B)):
             raise ValueError("latency must be a contiguous float64 CUDA tensor of shape (%d, B)" % _abi.NLATENCY)
@@ -380,11 +398,12 @@ class BatchedMPC:
                "hist": torch.empty((steps, _abi.DRIVE_REC, B), dtype=torch.float64, device=dev) if want_hist else None,
                "status": torch.empty((B,), dtype=torch.int32, device=dev), "iters": torch.empty((B,), dtype=torch.int32, device=dev)}
         s = stream if stream is not None else torch.cuda.current_stream(dev)
-        name = ("mpc_drive_batch_device_fused" if fused else "mpc_drive_batch_device") + ("_latency" if latency is not None else
-                                                                                           "_model" if model is not None else "")
+        name = ("mpc_drive_batch_device_fused" if fused else "mpc_drive_batch_device") + (
+            "_horizon" if horizon is not None else "_latency" if latency is not None else "_model" if model is not None else "")
         extra = (model.data_ptr(),) if model is not None else ()
-        if latency is not None:
-            extra = (model.data_ptr() if model is not None else None, latency.data_ptr())
+        if latency is not None or horizon is not None:
+            extra = (model.data_ptr() if model is not None else None,) + ((horizon.data_ptr(),) if horizon is not None else ()) + (
+                latency.data_ptr() if latency is not None else None,)
         check(getattr(library(), name)(self._h, B, B, int(steps), car.data_ptr(), track_x.data_ptr(), track_y.data_ptr(), n,
                                                weights.data_ptr() if weights is not None else None, *extra,
                                                C.byref(opts) if opts is not None else None, C.byref(warm_opts) if warm_opts is not None else None,
@@ -393,10 +412,10 @@ class BatchedMPC:
               name)
         return res
 
-    def drive_numpy(self, car, track_x, track_y, steps, weights=None, opts=None, warm_opts=None, want_hist=True, model=None, latency=None):
+    def drive_numpy(self, car, track_x, track_y, steps, weights=None, opts=None, warm_opts=None, want_hist=True, model=None, latency=None, horizon=None):
         """drive_torch for host arrays (mpc_drive_batch_host): one copy in, the loop, one copy out; synchronises.  `car` is copied:
         the cars after the last step are "car" of the result.  ``model`` [6, B]: as in drive_torch (mpc_drive_batch_host_model); ``latency`` [3, B]: as in
-        drive_torch (mpc_drive_batch_host_latency)."""
+        drive_torch (mpc_drive_batch_host_latency); ``horizon`` [B] int32: as in drive_torch (mpc_drive_batch_host_horizon)."""
         f = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64)) if a is not None else None
         car, tx, ty, weights = f(car).copy(), f(track_x), f(track_y), f(weights)
         B, n = car.shape[1], tx.shape[0]
@@ -412,8 +431,14 @@ class BatchedMPC:
             latency = f(latency)
             if latency.shape != (_abi.NLATENCY, B):
                 raise ValueError("latency must have shape (%d, B)" % _abi.NLATENCY)
-        name = "mpc_drive_batch_host" + ("_latency" if latency is not None else "_model" if model is not None else "")
+        if horizon is not None:
+            horizon = np.ascontiguousarray(np.asarray(horizon))
+            if horizon.dtype != np.int32 or horizon.shape != (B,):
+                raise ValueError("horizon must be an int32 array of shape (B,)")
+        name = "mpc_drive_batch_host" + ("_horizon" if horizon is not None else "_latency" if latency is not None else "_model" if model is not None else "")
         extra = (p(model), p(latency)) if latency is not None else ((p(model),) if model is not None else ())
+        if horizon is not None:
+            extra = (p(model), p(horizon), p(latency))
         check(getattr(library(), name)(self._h, B, B, int(steps), p(car), p(tx), p(ty), n, p(weights), *extra,
                                        C.byref(opts) if opts is not None else None, C.byref(warm_opts) if warm_opts is not None else None,
                                        p(res["summary"]), p(res["hist"]), p(res["status"]), p(res["iters"])), name)

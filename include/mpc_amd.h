@@ -530,8 +530,8 @@ int mpc_rollout_batch_device_fused_model(MpcHandle *h, int64_t B, int64_t ld, in
 /* ---- per-instance horizon: the N of every instance -----------------------------------------------------------------------------
  * One more rule next to the two above: the _horizon form of an entry point is its _model form plus `horizon`, [ld] int32, directly
  * behind `model`: instance i is solved as the reference solves it with Config::N = horizon[i], 3 .. the handle's N, in one launch on
- * one handle.  Seven entry points have one -- the solve (device, host), the warm solve (device, host) and the three rollouts; run(),
- * the telemetry handler, the wire forms and the C++ drop-in have none, deliberately.  The section and its seven declarations live in
+ * one handle.  Seven entry points have one -- the solve (device, host), the warm solve (device, host) and the three rollouts; the
+ * telemetry handler and the track drive have theirs in mpc_amd_drive.h, run(), the wire forms and the C++ drop-in have none.  The section and its seven declarations live in
  * a header of their own, which this one includes: */
 #include "mpc_amd_horizon.h"
 /* ---- certify a stored solution: IPOPT's final error summary for a point the caller names ---------------------------------------

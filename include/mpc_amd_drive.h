@@ -75,8 +75,8 @@
  *   Plant, both uses: psi += steer * dist / Lf_i, and the reply takes effect as (cmd_steer * max_steering_i, cmd_throttle) -- cmd_steer
  *     was normalised by that same max_steering_i, so the angle in force is the angle the solve chose.
  *   Unchanged: the window rule, the summary and record rows, the status and iteration conventions, MpcDriveOpts.  sub_old, sub_new and h
- *     stay the call's here (per-car latency and substep counts: the _latency forms below), and there is no _horizon form (the run() path
-     has none).
+ *     stay the call's here (per-car latency and substep counts: the _latency forms below; per-car horizon: the _horizon forms at
+ *     the end).
  * A column that cannot be used (the _model rule: a value that is not finite, dt <= 0, Lf <= 0, max_steering <= 0, max_speed <= 0,
  *   max_acceleration <= 0, max_deceleration >= 0): the handle's values take its place in the handler's pre- and post-processing and in
  *   the plant, every step of that car ends MPC_STATUS_INFEASIBLE, car / summary / hist hold no not-a-number because of it, and every
@@ -116,7 +116,39 @@
  *     defect.  No trip count comes from an unchecked double: a launch that ends.
  *   mpc_drive_batch_device_fused_latency writes BITWISE what mpc_drive_batch_device_latency writes, and runs the one launch under exactly
  *     the rule of _fused_model (model == NULL: the rule of the plain fused form); everywhere else it runs the stepwise loop.
- *     mpc_drive_info counts both. */
+ *     mpc_drive_info counts both.
+ *
+ * ---- per-car horizon: mpc_drive_*_horizon and mpc_telemetry_batch_*_horizon ----------------------------------------------------------
+ * Which N x dt gets this tuning round the track, and how fast?  dt is a row of `model`; N is the column of these forms, so the whole
+ * grid is the cars of one call, and a handler that serves connections with different horizons is one batch.  Each _horizon form is its
+ * _latency form plus `horizon` directly behind `model` (the rule of mpc_amd_horizon.h for _horizon forms): [ld] int32 addressed by
+ * instance; the host forms take a host array and copy it in with the other inputs.  `model`, `comp` / `latency`, `weights` and the warm
+ * arguments may each be NULL as in the _latency forms; with model == NULL the handle's own six values are used.
+ * horizon == NULL: the call IS the _latency form -- bitwise, with its dispatch (the wave kernels up to wave_max_batch), its refusals and
+ *   its mpc_drive_info counts.
+ * horizon != NULL: car i's solve is the solve mpc_solve_batch_device_warm_horizon runs for a column with horizon[i] = n: 8n - 2
+ *   variables and 6n rows, as the reference poses them with Config::N = n.  Nothing else reads N: the window, the fit, the latency
+ *   compensation, the speed tables, the reply, the plant, the summary and record rows are unchanged.
+ *   Valid: 3 <= horizon[i] <= the handle's N.  Any other value follows the _horizon rule: that car's solve ends MPC_STATUS_INFEASIBLE at
+ *   every step with the start point as its solution; the reply computed from it and the car moved under it hold no not-a-number, and
+ *   every other car is bit for bit what it is without the defect.
+ *   Warm start: the drive's buffer in the handle keeps the rows of the handle's N (mpc_warm_rows); car i reads and writes records
+ *   0 .. n - 2 of its column, the run()-path psi projection applies to those records, step 1 is cold and a car whose previous step did
+ *   not succeed starts cold.  The telemetry forms: warm_in / warm_out as for mpc_solve_batch_device_warm_horizon (an instance writes
+ *   the records of its own stages only).
+ *   Dispatch, as for every horizon call: the lane kernel's HORIZON build at every B -- no wave path, also for a batch of one, and no
+ *   fp32 start.  The lanes of a wave differ in their number of stages, so a pass lasts as long as the LONGEST horizon among the wave's
+ *   64 lanes: sort the cars by horizon, so that a wave holds one value, or a few neighbouring ones.  These builds are not staged, so
+ *   a call whose horizons are all equal is slower than the _latency form on a handle created with that N, and one call over a sorted
+ *   N x dt grid was measured about a tenth slower than one _fused_model call per N on handles created with those N, times summed
+ *   (DESIGN.md section 6p.3 has the figures).  It is still the only way to mix horizons behind one handle and one handler.
+ *   Refusals, checked before anything is touched: an MPC_PRECISION_F32 handle: MPC_ERR_INVALID (per-instance model values: fp64
+ *   handles only); max_soc > 0 with a non-NULL horizon: MPC_ERR_UNSUPPORTED (a per-instance horizon is not available with the
+ *   second-order correction); then every refusal of the _latency forms, unchanged.
+ * mpc_drive_batch_device_fused_horizon writes BITWISE what mpc_drive_batch_device_horizon writes.  With a horizon it runs the one launch
+ *   (the lane kernel's ROLL x MODEL x HORIZON x DRIVE builds, cold and warm: not staged, per-lane workspace rows, no lane compaction) at
+ *   every B >= 1 on every fp64 handle with max_soc = 0 -- the rule of mpc_rollout_batch_device_fused_horizon, because a horizon call
+ *   never takes the wave path or the fp32 start; mpc_drive_info counts it.  horizon == NULL: _fused_latency with that form's own rule. */
 #define MPC_DRIVE_MAX_TRACK 4096
 #define MPC_DRIVE_NSUM 8
 #define MPC_DRIVE_REC 13
@@ -178,6 +210,26 @@ int mpc_telemetry_batch_host_latency(MpcHandle *h, int64_t B, int64_t ld, int np
                                      const double *comp, const double *ptsx, const double *ptsy, const double *model, const double *warm_in,
                                      const int32_t *warm_status, double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts, double *cmd,
                                      int32_t *status);
+int mpc_drive_batch_device_horizon(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                                   int n_track, const double *weights, const double *model, const int32_t *horizon, const double *latency,
+                                   const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status,
+                                   int32_t *iters, void *stream);
+int mpc_drive_batch_device_fused_horizon(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
+                                         const double *track_y, int n_track, const double *weights, const double *model,
+                                         const int32_t *horizon, const double *latency, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts,
+                                         double *summary, double *hist, int32_t *status, int32_t *iters, void *stream);
+int mpc_drive_batch_host_horizon(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                                 int n_track, const double *weights, const double *model, const int32_t *horizon, const double *latency,
+                                 const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status,
+                                 int32_t *iters);
+int mpc_telemetry_batch_device_horizon(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
+                                       const double *comp, double *ptsx, double *ptsy, const double *model, const int32_t *horizon,
+                                       const double *warm_in, const int32_t *warm_status, double *warm_out, int64_t ld_warm,
+                                       const MpcWarmOpts *opts, double *cmd, double *out8, int32_t *status, void *stream);
+int mpc_telemetry_batch_host_horizon(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *tel, double extra_latency,
+                                     const double *comp, const double *ptsx, const double *ptsy, const double *model, const int32_t *horizon,
+                                     const double *warm_in, const int32_t *warm_status, double *warm_out, int64_t ld_warm,
+                                     const MpcWarmOpts *opts, double *cmd, int32_t *status);
 int mpc_drive_info(const MpcHandle *h, int64_t *out2);
 
 #endif /* MPC_AMD_DRIVE_H */

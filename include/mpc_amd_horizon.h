@@ -13,8 +13,9 @@
  * that shortens the horizon of some cars -- in one launch on one handle.  One more rule next to the two above: the _horizon form of
  * an entry point is its _model form plus `horizon`, [ld] int32 addressed like yaw_lo (device or host like its neighbours),
  * directly behind `model`.  Seven entry points have one: the solve (device, host), the warm solve (device, host) and the three
- * rollouts.  run(), the telemetry handler, the wire forms and the C++ drop-in have none, deliberately: their problem is one car's
- * message, and the horizon of a handler is the handle's.
+ * rollouts.  The telemetry handler and the track drive have _horizon forms of their own -- their _latency forms plus `horizon` behind
+ * `model` -- declared and described in mpc_amd_drive.h ("per-car horizon"); run(), the wire forms and the C++ drop-in have none: their
+ * problem is one car's message, and its horizon is the handle's.
  * horizon == NULL: the call IS the _model form, bitwise, with every convention and refusal that form has -- with model == NULL too
  *   the plain form, wave path included.
  * horizon != NULL: instance i is solved as the reference solves it with Config::N = horizon[i] -- 8n - 2 variables, 6n rows -- and

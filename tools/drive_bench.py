@@ -24,7 +24,22 @@ Writes --out (default profiles/drive.json); needs an MI355X.
   grid       --delays stale-command times x --comps compensated times x --cars cars (scenarios.latency_grid, the same starts in every
              cell) in ONE warm one-launch call of --sweep-steps messages: the off-track map (cars that leave the road per cell), the
              time of the launch, and the iterations per solve along both axes -- what the reference studies with `-latency N` run N
-             times."""
+             times.
+
+--horizon: the mpc_drive_*_horizon entry points (default --out profiles/drive_horizon.json): an N x dt grid as
+the columns of one call -- horizons 5, 7, 10, 15, 20, 25 on an N = 25 handle x dt 0.05, 0.1, 0.15, 0.2 through `model` x --cars cars per
+cell (the same starts in every cell), --sweep-steps messages, warm.  --legs picks what is run:
+  grid       the cars sorted by horizon: the stepwise form and the one launch, timed; per cell what the drive says (summary rows 0, 3,
+             6, 7: max |cte|, mean speed, cars off the road, failed steps) -- the table a user wants
+  shuffled   the same batch with its columns permuted: every wave then holds every horizon and lasts as long as its longest
+  uniform    every horizon 10 on an N = 10 handle against the _fused_model call on the same handle and cars: what the unstaged HORIZON
+             build costs a drive
+  six        what a caller can do without the _horizon forms: six _fused_model calls on six handles created with those N, each with
+             its four dt values, times summed.  Needs nothing of this commit but the tool, so --root CHECKOUT measures another built
+             checkout's library (the parent commit's, in the same session) with it.
+--forms picks the forms of grid and shuffled (one_launch, stepwise: a stepwise run of 300 messages lasts 300 x the slowest car of each
+step, so it may be given --reps and --warmup of its own in a run of its own; every leg records the reps it was timed with).
+--merge FILE ...: copy the legs of files this tool wrote into --out (legs of the same name are joined)."""
 import argparse
 import json
 import os
@@ -33,6 +48,8 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if "--root" in sys.argv:      # (before the package is imported: --root CHECKOUT measures that checkout's library)
+    ROOT = os.path.abspath(sys.argv[sys.argv.index("--root") + 1])
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import __graft_entry__ as G   # noqa: E402
@@ -57,8 +74,24 @@ def main():
     ap.add_argument("--delays", type=int, default=16, help="--latency: stale-command times, 0, 10, 20 ... ms")
     ap.add_argument("--comps", type=int, default=16, help="--latency: compensated times, 0, 10, 20 ... ms")
     ap.add_argument("--period", type=int, default=16, help="--latency: plant substeps (10 ms each) between two messages")
+    ap.add_argument("--horizon", action="store_true", help="run the N x dt grid of the _horizon entry points")
+    ap.add_argument("--legs", default="grid,shuffled,uniform,six", help="--horizon: which legs to run")
+    ap.add_argument("--forms", default="one_launch,stepwise", help="--horizon: the forms of the grid and shuffled legs")
+    ap.add_argument("--root", default=None, help="--horizon --legs six: another built checkout whose library is measured")
+    ap.add_argument("--merge", nargs="*", default=None, help="--horizon: files of this tool whose legs are copied into --out (nothing is run)")
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "drive_latency.json" if a.latency else "drive_model.json" if a.model else "drive.json")
+    a.out = a.out or os.path.join(ROOT, "profiles", "drive_horizon.json" if a.horizon else "drive_latency.json" if a.latency else
+                                  "drive_model.json" if a.model else "drive.json")
+    if a.horizon and a.merge is not None:
+        doc = {"tool": "tools/drive_bench.py --horizon", "legs": {}}
+        for f in a.merge:
+            d = json.load(open(f))
+            doc.update({k: v for k, v in d.items() if k != "legs"})
+            for name, leg in d["legs"].items():
+                doc["legs"].setdefault(name, {}).update(leg)
+        json.dump(doc, open(a.out, "w"), indent=1)
+        print("wrote", a.out)
+        return
     if a.latency and a.cars == 4096:
         a.cars = 16
     import torch
@@ -70,8 +103,9 @@ def main():
     wp = np.asarray(pkg.scenarios.load_waypoints(os.path.join(gd, "lake_track_waypoints.csv")), dtype=np.float64)
     t = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(dev)
     B, steps = a.batch, a.steps
-    car0 = pkg.scenarios.track_starts(B, params, wp, seed=122)
-    d_car0, d_tx, d_ty = t(car0), t(wp[:, 0]), t(wp[:, 1])
+    d_tx, d_ty = t(wp[:, 0]), t(wp[:, 1])
+    car0 = pkg.scenarios.track_starts(B, params, wp, seed=122) if not a.horizon else None
+    d_car0 = t(car0) if car0 is not None else None
     rows = []
 
     def timed(fn):
@@ -86,6 +120,8 @@ def main():
             if rep >= a.warmup:
                 ms.append(e0.elapsed_time(e1))
         return ms, out
+    if a.horizon:
+        return horizon_grid(a, pkg, gd, wp, t, timed, d_tx, d_ty)
     if a.latency:
         return latency_grid(a, pkg, params, wp, t, d_tx, d_ty)
     if a.model:
@@ -235,6 +271,95 @@ def latency_grid(a, pkg, params, wp, t, d_tx, d_ty):
                for d in range(-(n_d - 1), n_c) if any(0 <= q + d < n_c for q in range(n_d))}}
     print("one launch: %d cars x %d messages in %.1f ms; iterations per solve along the compensation axis: %s" % (
         B, steps, doc["ms"], " ".join("%.2f" % v for v in doc["iterations_per_solve_along_the_compensation_axis"])))
+    json.dump(doc, open(a.out, "w"), indent=1)
+    print("wrote", a.out)
+
+
+HORIZON_NS, HORIZON_DTS = (5, 7, 10, 15, 20, 25), (0.05, 0.1, 0.15, 0.2)
+
+
+def horizon_grid(a, pkg, gd, wp, t, timed, d_tx, d_ty):
+    import torch
+    dev = d_tx.device
+    n_cars, steps = a.cars, a.sweep_steps
+    legs = [x for x in a.legs.split(",") if x]
+    cfg = os.path.join(gd, a.config)
+    big = pkg.params_from_json(cfg, N=max(HORIZON_NS))
+    cells = [(n, dt) for n in HORIZON_NS for dt in HORIZON_DTS]            # sorted by horizon
+    B = len(cells) * n_cars
+    start = pkg.scenarios.track_starts(n_cars, big, wp, seed=125)         # car c of every cell: the same start
+    cars = np.tile(start, (1, len(cells)))
+    model = pkg.scenarios.model_rows(big, B)
+    model[0] = np.repeat([dt for _, dt in cells], n_cars)
+    hz = np.repeat([n for n, _ in cells], n_cars).astype(np.int32)
+    ti = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.int32)).to(dev)
+    med = lambda ms: {"ms_median": float(np.median(ms)), "ms_min": float(min(ms)), "ms_max": float(max(ms)), "reps": a.reps, "warmup": a.warmup}
+    doc = {"tool": "tools/drive_bench.py --horizon", "config": a.config, "device": torch.cuda.get_device_name(0),
+           "timing": "median of reps runs after warmup runs, between two events", "horizons": list(HORIZON_NS), "dts": list(HORIZON_DTS),
+           "cars_per_cell": n_cars, "B": B, "steps": steps, "warm_start": 1, "legs": {}}
+
+    def table(summ, st):
+        out = []
+        summ, st = summ.reshape(8, len(cells), n_cars), st.reshape(len(cells), n_cars)
+        for q, (n, dt) in enumerate(cells):
+            out.append({"N": n, "dt": dt, "max_abs_cte_p50_max": [float(np.median(summ[0, q])), float(summ[0, q].max())],
+                        "mean_speed_mph": float(summ[3, q].mean() / steps), "cars_off_the_road": int((summ[6, q] >= 0).sum()),
+                        "failed_steps_mean": float(summ[7, q].mean()), "cars_with_a_failed_step": int((summ[7, q] > 0).sum())})
+        return out
+
+    def both_forms(mpc, d_cars, d_model, d_hz, tag):
+        opts = mpc.drive_opts(warm_start=1)
+        leg = {}
+        res = {}
+        for form, fused in (("one_launch", True), ("stepwise", False)):
+            if form not in a.forms.split(","):
+                continue
+            ms, res[form] = timed(lambda: mpc.drive_torch(d_cars.clone(), d_tx, d_ty, steps, opts=opts, fused=fused, want_hist=False, model=d_model, horizon=d_hz))
+            leg[form] = dict(med(ms), solves_per_s=B * steps / (1e-3 * float(np.median(ms))), iterations_per_solve=float(res[form]["iters"].double().mean()) / steps)
+            print(tag, form, json.dumps(leg[form]), flush=True)
+        bits = lambda x: x.view(torch.int64) if x.dtype == torch.float64 else x
+        if len(res) == 2:
+            leg["one_launch_bitwise_equal_to_stepwise"] = bool(all(torch.equal(bits(res["one_launch"][k]), bits(res["stepwise"][k])) for k in ("car", "summary", "status", "iters")))
+        return leg, next(iter(res.values()))
+    if "grid" in legs or "shuffled" in legs:
+        with pkg.BatchedMPC(big, B, device=0) as mpc:
+            if "grid" in legs:
+                leg, res = both_forms(mpc, t(cars), t(model), ti(hz), "grid")
+                leg["cells"] = table(res["summary"].cpu().numpy(), res["status"].cpu().numpy())
+                doc["legs"]["grid_sorted_by_horizon"] = leg
+                for row in leg["cells"]:
+                    print(json.dumps(row), flush=True)
+            if "shuffled" in legs:
+                perm = np.random.default_rng(7).permutation(B)
+                leg, _ = both_forms(mpc, t(cars[:, perm]), t(model[:, perm]), ti(hz[perm]), "shuffled")
+                doc["legs"]["grid_shuffled"] = leg
+    if "uniform" in legs:
+        ten = pkg.params_from_json(cfg, N=10)
+        with pkg.BatchedMPC(ten, B, device=0) as mpc:
+            opts = mpc.drive_opts(warm_start=1)
+            d_cars, d_model, d_hz = t(cars), t(model), ti(np.full(B, 10))
+            leg = {}
+            for what, kw in (("fused_horizon_all_10", dict(horizon=d_hz)), ("fused_model", {})):
+                ms, r = timed(lambda: mpc.drive_torch(d_cars.clone(), d_tx, d_ty, steps, opts=opts, fused=True, want_hist=False, model=d_model, **kw))
+                leg[what] = dict(med(ms), iterations_per_solve=float(r["iters"].double().mean()) / steps)
+                leg[what + "_car"] = r["car"]
+                print("uniform", what, json.dumps(leg[what]), flush=True)
+            leg["bitwise_equal"] = bool(torch.equal(leg.pop("fused_horizon_all_10_car").view(torch.int64), leg.pop("fused_model_car").view(torch.int64)))
+            leg["drive_info"] = mpc.drive_info()
+            doc["legs"]["uniform_N_10"] = leg
+    if "six" in legs:
+        leg = {"what": "six mpc_drive_batch_device_fused_model calls on six handles created with N = 5 .. 25, each with its four dt cells; times summed",
+               "library_of": ROOT if a.root else "this checkout", "calls": []}
+        for q, n in enumerate(HORIZON_NS):
+            sl = slice(q * len(HORIZON_DTS) * n_cars, (q + 1) * len(HORIZON_DTS) * n_cars)
+            with pkg.BatchedMPC(pkg.params_from_json(cfg, N=n), sl.stop - sl.start, device=0) as mpc:
+                opts = mpc.drive_opts(warm_start=1)
+                d_cars, d_model = t(cars[:, sl]), t(model[:, sl])
+                ms, r = timed(lambda: mpc.drive_torch(d_cars.clone(), d_tx, d_ty, steps, opts=opts, fused=True, want_hist=False, model=d_model))
+                leg["calls"].append(dict(med(ms), N=n, B=sl.stop - sl.start, iterations_per_solve=float(r["iters"].double().mean()) / steps, drive_info=mpc.drive_info()))
+                print("six", json.dumps(leg["calls"][-1]), flush=True)
+        leg["ms_median_summed"] = float(sum(c["ms_median"] for c in leg["calls"]))
+        doc["legs"]["six_fused_model_calls" + ("_parent_commit" if a.root else "")] = leg
     json.dump(doc, open(a.out, "w"), indent=1)
     print("wrote", a.out)
 
