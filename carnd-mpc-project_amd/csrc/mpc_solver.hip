@@ -1489,6 +1489,16 @@ static int validate_params(const MpcParams *p) {
   if (p->f64_f32_start < 0 || p->f64_f32_start > MPC_F32_START_AUTO) { g_last_error = "f64_f32_start must be 0 (off), 1 (on) or 2 (auto)"; return MPC_ERR_INVALID; }
   if (p->lane_compact < MPC_LANE_COMPACT_AUTO || p->lane_compact > 7) { g_last_error = "lane_compact must be -1 (auto), 0 (off) .. 7"; return MPC_ERR_INVALID; }
   if (p->max_soc < 0 || p->max_soc > MPC_MAX_SOC) { g_last_error = "max_soc must be 0 (off) .. 16 (IPOPT's default is 4)"; return MPC_ERR_INVALID; }
+  /* the termination fields (ABI 4): an MpcParams that was never filled by mpc_params_default holds zeros here, with which no iterate
+   * passes the convergence check and every instance runs to MPC_STATUS_MAXITER */
+  const struct { const char *name; double value; } positive[] = {
+      {"dual_inf_tol", p->dual_inf_tol}, {"constr_viol_tol", p->constr_viol_tol}, {"compl_inf_tol", p->compl_inf_tol},
+      {"acceptable_tol", p->acceptable_tol}, {"acceptable_dual_inf_tol", p->acceptable_dual_inf_tol},
+      {"acceptable_constr_viol_tol", p->acceptable_constr_viol_tol}, {"acceptable_compl_inf_tol", p->acceptable_compl_inf_tol},
+      {"mixed_switch_mu", p->mixed_switch_mu}};
+  for (const auto &f : positive)
+    if (!(f.value > 0)) { g_last_error = std::string(f.name) + " must be positive (mpc_params_default sets it)"; return MPC_ERR_INVALID; }
+  if (p->acceptable_iter < 0) { g_last_error = "acceptable_iter must be 0 (off) or positive"; return MPC_ERR_INVALID; }
   return MPC_OK;
 }
 

@@ -163,7 +163,12 @@ typedef struct MpcParams {
    * angle over the 32 768 instances of SURVEY's N = 25 population (profiles/r04_f32start_vs_plain.jsonl).  Not for short
    * horizons: at N = 10 the workspace of a full device lives in the Infinity Cache and the two launches of the mixed
    * solve cost more than the bytes save (44 against 52 M on the filtered headline): f64_f32_start = 1 stays a choice.
-   * MPC_F32_START_OFF gives the single-phase fp64 solve at every horizon (bitwise the host twin's). */
+   * MPC_F32_START_OFF gives the single-phase fp64 solve at every horizon (bitwise the host twin's).
+   * Reproducibility across batch sizes: with the default AUTO and N >= MPC_F32_START_AUTO_N the BITS of an instance's result depend
+   * on the size of the launch it is part of -- up to wave_max_batch (1 024) instances every iteration runs in fp64, a larger launch
+   * starts in fp32 -- while status and values agree within the fp64 tolerances (1e-6 rad / m/s^2 on the first actuation, 1e-5 m on
+   * the step-1 state and the trajectory, 1e-7 relative on the cost).  Identical bits whatever the batch size need
+   * f64_f32_start = MPC_F32_START_OFF (tests/test_f32_horizons_gpu.py asserts both). */
   int32_t f32_finish;
   int32_t f64_f32_start;
   double mixed_switch_mu;          /* default 2e-5 */

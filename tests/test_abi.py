@@ -89,6 +89,60 @@ def test_invalid_params_rejected(pkg, golden_dir):
         assert rc in (-1, -4), (field, rc)
 
 
+TERMINATION_TOLS = ("dual_inf_tol", "constr_viol_tol", "compl_inf_tol", "acceptable_tol", "acceptable_dual_inf_tol",
+                    "acceptable_constr_viol_tol", "acceptable_compl_inf_tol", "mixed_switch_mu")
+
+
+def _create_rc(pkg, q):
+    """mpc_create's return code and text for `q`.  validate_params runs before the device is looked up: on a machine without a GPU
+    accepted parameters give MPC_ERR_NO_DEVICE (-2), refused ones MPC_ERR_INVALID (-1); with one, 0 (the handle is destroyed)."""
+    h = C.c_void_p()
+    rc = pkg.library().mpc_create(C.byref(q), 0, 16, C.byref(h))
+    err = pkg.library().mpc_last_error() or b""
+    if rc == 0:
+        pkg.library().mpc_destroy(h)
+    return rc, err.decode()
+
+
+@pytest.mark.parametrize("field", TERMINATION_TOLS)
+@pytest.mark.parametrize("value", [0.0, -1e-4, float("nan")])
+def test_termination_tolerances_must_be_positive(pkg, golden_dir, field, value):
+    """The termination fields of ABI 4 and mixed_switch_mu: zero (an MpcParams that mpc_params_default never filled), negative or
+    not a number is MPC_ERR_INVALID with a text that names the field -- with them every instance would run to MPC_STATUS_MAXITER."""
+    q = pkg.params_from_json(os.path.join(golden_dir, "config-stable.json"))
+    setattr(q, field, value)
+    rc, err = _create_rc(pkg, q)
+    assert rc == -1, (field, value, rc, err)
+    assert re.search(r"\b%s\b" % field, err), (field, err)
+
+
+def test_termination_fields_left_zero_are_refused_and_the_shipped_ones_accepted(pkg, golden_dir):
+    """A struct zeroed apart from what validate_params checked before ABI 4's fields is refused; acceptable_iter < 0 is refused, 0
+    ("off") is not; mpc_params_default and the three golden configs pass (-2 without a device, never -1)."""
+    import torch
+    accepted = (0,) if torch.cuda.is_available() else (-2,)
+    good = [pkg.params_default()] + [pkg.params_from_json(os.path.join(golden_dir, n))
+                                     for n in ("config-stable.json", "config-fast.json", "config-no-latency.json")]
+    for q in good:
+        rc, err = _create_rc(pkg, q)
+        assert rc in accepted, (rc, err)
+    d = good[1]
+    z = pkg.MpcParams()
+    for f in ("abi_version", "N", "dt", "Lf", "max_speed", "max_steering", "n_steer_speeds", "max_iter", "tol"):
+        setattr(z, f, getattr(d, f))
+    rc, err = _create_rc(pkg, z)
+    assert rc == -1 and "dual_inf_tol" in err, (rc, err)
+    q = d.copy(); q.acceptable_iter = -1
+    rc, err = _create_rc(pkg, q)
+    assert rc == -1 and "acceptable_iter" in err, (rc, err)
+    q.acceptable_iter = 0
+    rc, err = _create_rc(pkg, q)
+    assert rc in accepted, (rc, err)
+    if not torch.cuda.is_available():
+        q = d.copy(); q.mixed_switch_mu = 0.0
+        assert _create_rc(pkg, q)[0] == -1 and _create_rc(pkg, d)[0] == -2      # refused before the device is looked up
+
+
 @pytest.mark.parametrize("name", ["config-stable.json", "config-fast.json", "config-no-latency.json"])
 def test_params_from_json_against_a_third_reader(pkg, golden_dir, name):
     """mpc_params.cpp and the oracle's reader are both purpose-built flat-JSON parsers (a shared mistake would pass the
