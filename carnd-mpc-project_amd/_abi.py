@@ -119,7 +119,10 @@ DRIVE_EXPORTS = ["mpc_drive_opts_default", "mpc_drive_batch_device", "mpc_drive_
                  "mpc_drive_batch_device_latency", "mpc_drive_batch_device_fused_latency", "mpc_drive_batch_host_latency",
                  "mpc_telemetry_batch_device_latency", "mpc_telemetry_batch_host_latency",
                  "mpc_drive_batch_device_horizon", "mpc_drive_batch_device_fused_horizon", "mpc_drive_batch_host_horizon",
-                 "mpc_telemetry_batch_device_horizon", "mpc_telemetry_batch_host_horizon"]
+                 "mpc_telemetry_batch_device_horizon", "mpc_telemetry_batch_host_horizon",
+                 "mpc_drive_plant_default", "mpc_drive_batch_device_plant", "mpc_drive_batch_device_fused_plant", "mpc_drive_batch_host_plant"]
+NPLANT = 6       # MPC_NPLANT: rows of a plant array, [NPLANT][ld] (the mpc_drive_*_plant entry points)
+PLANT_LF, PLANT_STEER_GAIN, PLANT_STEER_BIAS, PLANT_ACCEL_GAIN, PLANT_DRAG_SPEED, PLANT_DRIFT = range(NPLANT)
 NLATENCY = 3     # MPC_NLATENCY: rows of a latency array, [NLATENCY][ld] (the mpc_drive_*_latency entry points)
 LATENCY_COMP, LATENCY_SUB_OLD, LATENCY_SUB_NEW = range(NLATENCY)
 DRIVE_MAX_TRACK, DRIVE_NSUM, DRIVE_REC = 4096, 8, 13      # MPC_DRIVE_MAX_TRACK, rows of summary [NSUM][ld], rows of a step of hist [REC][ld]
@@ -243,6 +246,11 @@ def library():
     for name in ("mpc_telemetry_batch_device", "mpc_telemetry_batch_host"):
         at = len(tel_head) + 4      # (comp, ptsx, ptsy, model)
         getattr(L, name + "_horizon").argtypes = getattr(L, name + "_latency").argtypes[:at] + [DP] + getattr(L, name + "_latency").argtypes[at:]
+    # ... and the drive's _plant forms: the _horizon form plus `plant` (one pointer) directly behind `latency`
+    for name in ("mpc_drive_batch_host", "mpc_drive_batch_device", "mpc_drive_batch_device_fused"):
+        at = len(drive_head) + 3      # (model, horizon, latency)
+        getattr(L, name + "_plant").argtypes = getattr(L, name + "_horizon").argtypes[:at] + [DP] + getattr(L, name + "_horizon").argtypes[at:]
+    L.mpc_drive_plant_default.argtypes = [C.POINTER(MpcParams), DP]
     L.mpc_drive_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.mpc_solve_batch_device_f32.argtypes = L.mpc_solve_batch_device.argtypes      # (the same pointers, to floats)
     L.mpc_solve_batch_host_f32.argtypes = L.mpc_solve_batch_host.argtypes
@@ -307,6 +315,21 @@ def drive_opts_default(params, **overrides):
     for k, v in overrides.items():
         setattr(o, k, v)
     return o
+
+
+def drive_plant_default(params, B=None, model=None):
+    """mpc_drive_plant_default for these parameters (needs no device): the column {Lf, 1, 0, 6, 50, 0} under which the plant of the
+    mpc_drive_*_plant entry points is the plant of the forms without `plant`.  B = None: the column [NPLANT]; else an array [NPLANT, B]
+    of it, row PLANT_LF from ``model`` [6, B] (its Lf row) if one is given."""
+    import numpy as np
+    col = np.zeros(NPLANT)
+    check(library().mpc_drive_plant_default(C.byref(params), col.ctypes.data), "mpc_drive_plant_default")
+    if B is None:
+        return col
+    a = np.ascontiguousarray(np.repeat(col[:, None], int(B), axis=1))
+    if model is not None:
+        a[PLANT_LF] = np.asarray(model, dtype=np.float64)[MODEL_LF]
+    return a
 
 
 def inflight_advice(params, B):

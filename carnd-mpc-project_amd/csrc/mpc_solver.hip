@@ -243,7 +243,10 @@ struct MpcHorizonPart {
  * latency (mpc_drive_batch_device_fused_latency): the car's column of [MPC_NLATENCY][ldo], or nullptr -- the call's own extra_latency and
  * substep counts, the very values the builds read before this pointer existed.  Read like the model column: by instance index at the
  * take (what the pre-solve half compensates for) and again at the hand-over (the plant's counts), and not carried in between.  A
- * pointer, not a template argument: the lane kernel has the builds it had. */
+ * pointer, not a template argument: the lane kernel has the builds it had.
+ * plant (mpc_drive_batch_device_fused_plant): the car's column of [MPC_NPLANT][ldo], or nullptr -- the default column, the plant of the
+ * forms without.  Read by instance index at the hand-over only, where the plant runs, under the one test mpc::drive_plant_vals_of
+ * makes; likewise a pointer and no template argument. */
 struct MpcDrivePart {
   MpcDriveOpts O;
   double *car;                    /* [6][ldo] in / out */
@@ -254,6 +257,7 @@ struct MpcDrivePart {
   double *out9;                   /* [9][ldo]: the handle's rows */
   double *summary, *rec;          /* [MPC_DRIVE_NSUM][ldo]; hist [steps][MPC_DRIVE_REC][ldo] or nullptr */
   const double *latency;          /* [MPC_NLATENCY][ldo] or nullptr */
+  const double *plant;            /* [MPC_NPLANT][ldo] or nullptr */
 };
 
 template <bool ON, class Part> struct MpcPartIf : Part {};
@@ -522,8 +526,8 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
                 const mpc::DriveLatency dl = mpc::drive_latency_of(T.O, T.latency, ldo, i);
                 sub_old = dl.sub_old; sub_new = dl.sub_new;
               }
-              mpc::drive_step_instance(P, mv, T.O, sub_old, sub_new, i, ldo, step, T.n_track, T.car, T.cmd, T.pre, ld, fin_status, S.iters + it_total, drive_k, drive_k_prev,
-                                       T.summary, T.rec ? T.rec + (int64_t)step * MPC_DRIVE_REC * ldo : nullptr, T.status, T.iters);
+              mpc::drive_step_instance(P, mv, mpc::drive_plant_vals_of(P, mv, T.plant, ldo, i), T.O, sub_old, sub_new, i, ldo, step, T.n_track, T.car, T.cmd, T.pre, ld,
+                                       fin_status, S.iters + it_total, drive_k, drive_k_prev, T.summary, T.rec ? T.rec + (int64_t)step * MPC_DRIVE_REC * ldo : nullptr, T.status, T.iters);
             } else {
             double *o = T.hist + (int64_t)step * T.hist_step + i;
             const int64_t l = ldo;
@@ -1182,6 +1186,28 @@ __global__ __launch_bounds__(256) void mpc_drive_plant_latency_kernel(const MpcP
   } else
     mpc::drive_step_instance(P, P, O, dl.sub_old, dl.sub_new, i, ld, step, n_track, car, cmd, pre, ldp, st_step[i], it_step[i], k_now[i], k_prev[i], summary, rec,
                              status, iters);
+}
+/* ... and its build with per-car plant values (the mpc_drive_*_plant entry points): the lane reads its car's column of plant
+ * [MPC_NPLANT][ld] once and moves the car with it (mpc::drive_plant_vals_of: checked; a column that cannot be used becomes a status).
+ * latency and W.model may each be nullptr here: the call's counts, the handle's values. */
+__global__ __launch_bounds__(256) void mpc_drive_plant_vals_kernel(const MpcParams P, const MpcDriveOpts O, int64_t B, int64_t ld, int step, int n_track,
+                                                                   double *__restrict__ car, const double *__restrict__ cmd,
+                                                                   const double *__restrict__ pre, int64_t ldp, const int32_t *__restrict__ st_step,
+                                                                   const int32_t *__restrict__ it_step, const int32_t *k_now,
+                                                                   const int32_t *k_prev, double *__restrict__ summary,
+                                                                   double *__restrict__ rec, int32_t *__restrict__ status, int32_t *__restrict__ iters,
+                                                                   const double *__restrict__ latency, const MpcModelPart W,
+                                                                   const double *__restrict__ plant) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B) return;
+  int sub_old = O.sub_old, sub_new = O.sub_new;
+  if (latency) {
+    const mpc::DriveLatency dl = mpc::drive_latency_of(O, latency, ld, i);
+    sub_old = dl.sub_old; sub_new = dl.sub_new;
+  }
+  const mpc::ModelVals mv = W.model ? mpc::model_vals_of(P, W.model, W.ld_model, i) : mpc::ModelVals::of(P);
+  mpc::drive_step_instance(P, mv, mpc::drive_plant_vals_of(P, mv, plant, ld, i), O, sub_old, sub_new, i, ld, step, n_track, car, cmd, pre, ldp, st_step[i],
+                           it_step[i], k_now[i], k_prev[i], summary, rec, status, iters);
 }
 /* What the stepwise loop's handler compensates for, per car: comp [ld] <- row MPC_LATENCY_COMP of the car's column, not-a-number for
  * a column that cannot be used (the handler turns that into a status).  Once per call. */
@@ -2110,6 +2136,7 @@ struct CallExtras {
   bool model_wave = false;         /* a model call of the run() / telemetry entry points: the wave MODEL kernels up to wave_max_batch */
   const int32_t *horizon = nullptr;   /* a horizon call (fp64 handles, no SOC): [ld] like the inputs; dispatched as a model call, `model` may be NULL */
   const double *latency = nullptr;   /* a latency call (fp64 handles): the telemetry handler's comp [ld]; the drive's [MPC_NLATENCY][ld] */
+  const double *plant = nullptr;     /* a plant call (the drive, fp64 handles): [MPC_NPLANT][ld], what the cars are moved with */
   const double *run_weights = nullptr;   /* run() / telemetry only (the drive loop): per-instance weights of the solve, [MPC_NW][io_stride] like the rows run() solves from */
   bool model_call() const { return model != nullptr || horizon != nullptr; }
   const WarmIO *warm_io() const { return warm ? &w : nullptr; }
@@ -3043,6 +3070,14 @@ extern "C" int mpc_drive_opts_default(const MpcParams *p, MpcDriveOpts *o) {
   return MPC_OK;
 }
 
+/* the plant column under which the _plant forms move a car as the forms without do (the car's own Lf belongs in row 0) */
+extern "C" int mpc_drive_plant_default(const MpcParams *p, double *col6) {
+  if (!p || !col6) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
+  col6[MPC_PLANT_LF] = p->Lf; col6[MPC_PLANT_STEER_GAIN] = 1.0; col6[MPC_PLANT_STEER_BIAS] = 0.0;
+  col6[MPC_PLANT_ACCEL_GAIN] = 6.0; col6[MPC_PLANT_DRAG_SPEED] = 50.0; col6[MPC_PLANT_DRIFT] = 0.0;
+  return MPC_OK;
+}
+
 /* what the drive entry points check before they touch anything; *O: the options in effect (opts = NULL: the defaults) */
 static int drive_args(const MpcHandle *h, int64_t B, int64_t ld, int steps, const double *car, const double *track_x, const double *track_y,
                       int n_track, const MpcDriveOpts *opts, const double *summary, const int32_t *status, MpcDriveOpts *O) {
@@ -3085,7 +3120,9 @@ static int drive_rows(MpcHandle *h, int64_t B, int64_t ld, bool warm, const doub
  * on the handle's own buffer, in place (rollout_impl's arrangement).  x.model (device, [MPC_NMODEL][ld]): the handler is the
  * telemetry _model call -- run_impl reads the columns where the caller has them -- and the plant kernel its MODEL build.
  * x.latency (device, [MPC_NLATENCY][ld]): one more kernel first, the comp row the handler takes (not-a-number for a column that cannot
- * be used); the handler is the telemetry _latency call on it and the plant kernel its latency build, with or without model. */
+ * be used); the handler is the telemetry _latency call on it and the plant kernel its latency build, with or without model.
+ * x.plant (device, [MPC_NPLANT][ld]): the plant kernel is its plant build, which takes the caller's latency and model or nullptr; the
+ * handler's calls are what they are without it. */
 static int drive_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y, int n_track,
                       const double *weights, const MpcDriveOpts &O, CallExtras x, double *summary, double *hist, int32_t *status,
                       int32_t *iters, void *stream_) {
@@ -3113,7 +3150,10 @@ static int drive_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *ca
     x.w = WarmIO{t == 0 ? nullptr : h->d_warm, h->d_rstat, h->d_warm, S, x.w.wopts, 0};
     MPC_TRY(run_impl(h, B, ld, O.npts, car, true, O.extra_latency, ptsx, ptsy, nullptr, cmd, nullptr, h->d_rstat, h->d_iters, nullptr, stream_, x));
     double *rec = hist ? hist + (int64_t)t * MPC_DRIVE_REC * ld : nullptr;
-    if (latency && x.model)
+    if (x.plant)
+      hipLaunchKernelGGL(mpc_drive_plant_vals_kernel, dim3(grid), dim3(256), 0, s, h->params, O, B, ld, t, n_track, car, cmd, h->d_run, S, h->d_rstat,
+                         h->d_iters, k_now, k_prev, summary, rec, status, iters, latency, MpcModelPart{x.model, ld}, x.plant);
+    else if (latency && x.model)
       hipLaunchKernelGGL((mpc_drive_plant_latency_kernel<true, MpcModelPart>), dim3(grid), dim3(256), 0, s, h->params, O, B, ld, t, n_track, car, cmd, h->d_run, S,
                          h->d_rstat, h->d_iters, k_now, k_prev, summary, rec, status, iters, latency, MpcModelPart{x.model, ld});
     else if (latency)
@@ -3134,24 +3174,37 @@ static int drive_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *ca
 /* What every drive entry point does first: with `model`, the model rule (which handles a model call is accepted on, call_extras);
  * drive_args; then the call's extras -- the warm refusals and the options in effect. */
 static int drive_call(const MpcHandle *h, int64_t B, int64_t ld, int steps, const double *car, const double *track_x, const double *track_y,
-                      int n_track, const double *model, const int32_t *horizon, const double *latency, const MpcDriveOpts *opts,
+                      int n_track, const double *model, const int32_t *horizon, const double *latency, const double *plant, const MpcDriveOpts *opts,
                       const MpcWarmOpts *warm_opts, const double *summary, const int32_t *status, MpcDriveOpts *O, CallExtras *x) {
+  if (h && plant && h->params.precision != MPC_PRECISION_F64) {
+    g_last_error = "track driving: fp64 handles only (this one was created with MPC_PRECISION_F32)";
+    return MPC_ERR_INVALID;
+  }
   if (h && (model || horizon)) MPC_TRY(call_extras(h, model, false, nullptr, nullptr, nullptr, 0, nullptr, horizon).refused);
   MPC_TRY(drive_args(h, B, ld, steps, car, track_x, track_y, n_track, opts, summary, status, O));
   *x = call_extras(h, model, O->warm_start != 0, nullptr, nullptr, nullptr, 0, warm_opts, horizon, latency);
+  x->plant = plant;
   return x->refused;
 }
 
+/* (the _plant forms, "per-car plant values" in include/mpc_amd_drive.h: the _horizon forms plus `plant` behind latency; NULL is the _horizon form itself) */
+extern "C" int mpc_drive_batch_device_plant(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
+                                            const double *track_y, int n_track, const double *weights, const double *model, const int32_t *horizon,
+                                            const double *latency, const double *plant, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts,
+                                            double *summary, double *hist, int32_t *status, int32_t *iters, void *stream_) {
+  MpcDriveOpts O;
+  CallExtras x;
+  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, horizon, latency, plant, opts, warm_opts, summary, status, &O, &x));
+  if (B == 0) { h->last_B = 0; return MPC_OK; }
+  return drive_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
+}
 /* (the _horizon forms, "per-car horizon" in include/mpc_amd_drive.h: the _latency forms plus `horizon` behind model; NULL is the _latency form itself) */
 extern "C" int mpc_drive_batch_device_horizon(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
                                               const double *track_y, int n_track, const double *weights, const double *model, const int32_t *horizon,
                                               const double *latency, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary,
                                               double *hist, int32_t *status, int32_t *iters, void *stream_) {
-  MpcDriveOpts O;
-  CallExtras x;
-  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, horizon, latency, opts, warm_opts, summary, status, &O, &x));
-  if (B == 0) { h->last_B = 0; return MPC_OK; }
-  return drive_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
+  return mpc_drive_batch_device_plant(h, B, ld, steps, car, track_x, track_y, n_track, weights, model, horizon, latency, nullptr, opts, warm_opts, summary, hist,
+                                      status, iters, stream_);
 }
 extern "C" int mpc_drive_batch_device_latency(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
                                               const double *track_y, int n_track, const double *weights, const double *model, const double *latency,
@@ -3216,7 +3269,7 @@ static int drive_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, doub
   double *warm = x.warm ? h->d_warm : nullptr;
   const WarmIO wc{warm, nullptr, warm, S, x.w.wopts, 1};      /* (psi_box: the run() path's rule) */
   const MpcRollPart roll{steps, nullptr, 0, nullptr, status, iters};
-  const MpcDrivePart drive{O, car, track_x, track_y, n_track, ptsx, ptsy, cmd, d_pre, h->d_run9, summary, hist, x.latency};
+  const MpcDrivePart drive{O, car, track_x, track_y, n_track, ptsx, ptsy, cmd, d_pre, h->d_run9, summary, hist, x.latency, x.plant};
   const unsigned grid = (unsigned)((B + kBlock - 1) / kBlock);
   if (x.horizon) {
     /* the DRIVE x HORIZON builds: MODEL builds whose `model` may be nullptr, not staged, per-lane workspace rows, no LDS (no lane compaction here) */
@@ -3240,16 +3293,24 @@ static int drive_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, doub
   return record_stats(h, B, status, iters, s);
 }
 
+extern "C" int mpc_drive_batch_device_fused_plant(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
+                                                  const double *track_y, int n_track, const double *weights, const double *model,
+                                                  const int32_t *horizon, const double *latency, const double *plant, const MpcDriveOpts *opts,
+                                                  const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status, int32_t *iters,
+                                                  void *stream_) {
+  MpcDriveOpts O;
+  CallExtras x;
+  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, horizon, latency, plant, opts, warm_opts, summary, status, &O, &x));
+  if (B == 0) { h->last_B = 0; return MPC_OK; }
+  return drive_fused_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
+}
 extern "C" int mpc_drive_batch_device_fused_horizon(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
                                                     const double *track_y, int n_track, const double *weights, const double *model,
                                                     const int32_t *horizon, const double *latency, const MpcDriveOpts *opts,
                                                     const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status, int32_t *iters,
                                                     void *stream_) {
-  MpcDriveOpts O;
-  CallExtras x;
-  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, horizon, latency, opts, warm_opts, summary, status, &O, &x));
-  if (B == 0) { h->last_B = 0; return MPC_OK; }
-  return drive_fused_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
+  return mpc_drive_batch_device_fused_plant(h, B, ld, steps, car, track_x, track_y, n_track, weights, model, horizon, latency, nullptr, opts, warm_opts, summary,
+                                            hist, status, iters, stream_);
 }
 extern "C" int mpc_drive_batch_device_fused_latency(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
                                                     const double *track_y, int n_track, const double *weights, const double *model,
@@ -3274,24 +3335,24 @@ extern "C" int mpc_drive_batch_device_fused(MpcHandle *h, int64_t B, int64_t ld,
 
 /* The same for host arrays: one copy in, the loop on the handle's own device and stream, one copy out; synchronises.  Staging kept on
  * the handle and grown on demand, like the telemetry handler's.  model (host, [MPC_NMODEL][ld]), latency (host, [MPC_NLATENCY][ld]) and
- * horizon (host, [ld] int32, to h->d_horizon) are copied in with the other inputs. */
-extern "C" int mpc_drive_batch_host_horizon(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
-                                            int n_track, const double *weights, const double *model, const int32_t *horizon, const double *latency,
-                                            const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status,
-                                            int32_t *iters) {
+ * horizon (host, [ld] int32, to h->d_horizon) are copied in with the other inputs, and so is plant (host, [MPC_NPLANT][ld]). */
+extern "C" int mpc_drive_batch_host_plant(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                                          int n_track, const double *weights, const double *model, const int32_t *horizon, const double *latency,
+                                          const double *plant, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist,
+                                          int32_t *status, int32_t *iters) {
   MpcDriveOpts O;
   CallExtras x;
-  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, horizon, latency, opts, warm_opts, summary, status, &O, &x));
+  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, horizon, latency, plant, opts, warm_opts, summary, status, &O, &x));
   if (B == 0) { h->last_B = 0; return MPC_OK; }
   MPC_ON_DEVICE(h);
   const int64_t L = (B + 7) / 8 * 8;
   const int64_t rows = 6 + MPC_DRIVE_NSUM + (weights ? MPC_NW : 0) + (hist ? (int64_t)steps * MPC_DRIVE_REC : 0) + (model ? MPC_NMODEL : 0) +
-                       (latency ? MPC_NLATENCY : 0);
+                       (latency ? MPC_NLATENCY : 0) + (plant ? MPC_NPLANT : 0);
   MPC_TRY(grow_dev(&h->d_drive_host, &h->drive_host_bytes, sizeof(double) * (size_t)(rows * L + 2 * n_track) + sizeof(int32_t) * (size_t)(2 * L)));
   double *d = h->d_drive_host;
   double *d_car = d, *d_sum = d_car + 6 * L, *d_w = d_sum + MPC_DRIVE_NSUM * L, *d_hist = d_w + (weights ? MPC_NW * L : 0);
-  double *d_model = d_hist + (hist ? (int64_t)steps * MPC_DRIVE_REC * L : 0), *d_lat = d_model + (model ? MPC_NMODEL * L : 0), *d_tx = d_lat + (latency ? MPC_NLATENCY * L : 0),
-         *d_ty = d_tx + n_track;
+  double *d_model = d_hist + (hist ? (int64_t)steps * MPC_DRIVE_REC * L : 0), *d_lat = d_model + (model ? MPC_NMODEL * L : 0), *d_plant = d_lat + (latency ? MPC_NLATENCY * L : 0),
+         *d_tx = d_plant + (plant ? MPC_NPLANT * L : 0), *d_ty = d_tx + n_track;
   int32_t *d_st = (int32_t *)(d_ty + n_track), *d_it = d_st + L;
   hipStream_t s = h->stream;
   MPC_HIP_CHECK(hipMemcpy2DAsync(d_car, sizeof(double) * L, car, sizeof(double) * ld, sizeof(double) * B, 6, hipMemcpyHostToDevice, s));
@@ -3303,6 +3364,10 @@ extern "C" int mpc_drive_batch_host_horizon(MpcHandle *h, int64_t B, int64_t ld,
   if (latency) {
     MPC_HIP_CHECK(hipMemcpy2DAsync(d_lat, sizeof(double) * L, latency, sizeof(double) * ld, sizeof(double) * B, MPC_NLATENCY, hipMemcpyHostToDevice, s));
     x.latency = d_lat;
+  }
+  if (plant) {
+    MPC_HIP_CHECK(hipMemcpy2DAsync(d_plant, sizeof(double) * L, plant, sizeof(double) * ld, sizeof(double) * B, MPC_NPLANT, hipMemcpyHostToDevice, s));
+    x.plant = d_plant;
   }
   if (horizon) {
     MPC_TRY(ensure_dev(&h->d_horizon, sizeof(int32_t) * (size_t)h->io_stride));
@@ -3319,6 +3384,13 @@ extern "C" int mpc_drive_batch_host_horizon(MpcHandle *h, int64_t B, int64_t ld,
   if (iters) MPC_HIP_CHECK(hipMemcpyAsync(iters, d_it, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipStreamSynchronize(s));
   return MPC_OK;
+}
+extern "C" int mpc_drive_batch_host_horizon(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                                            int n_track, const double *weights, const double *model, const int32_t *horizon, const double *latency,
+                                            const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status,
+                                            int32_t *iters) {
+  return mpc_drive_batch_host_plant(h, B, ld, steps, car, track_x, track_y, n_track, weights, model, horizon, latency, nullptr, opts, warm_opts, summary, hist,
+                                    status, iters);
 }
 extern "C" int mpc_drive_batch_host_latency(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
                                             int n_track, const double *weights, const double *model, const double *latency, const MpcDriveOpts *opts,

@@ -362,8 +362,13 @@ class BatchedMPC:
         """This handle's MpcDriveOpts defaults (mpc_drive_opts_default), with keyword overrides."""
         return _abi.drive_opts_default(self.params, **overrides)
 
+    def drive_plant_default(self, B=None, model=None):
+        """The default plant column of this handle (mpc_drive_plant_default: Lf, 1, 0, 6, 50, 0), or with B the array [6, B] of it --
+        row 0 from ``model``'s Lf row if one is given: the ``plant=`` under which a drive is the drive without one."""
+        return _abi.drive_plant_default(self.params, B, model)
+
     def drive_torch(self, car, track_x, track_y, steps, weights=None, opts=None, warm_opts=None, want_hist=True, fused=False, stream=None,
-                    model=None, latency=None, horizon=None):
+                    model=None, latency=None, horizon=None, plant=None):
         """Drive B cars along a cyclic track for `steps` telemetry messages on the device (mpc_drive_batch_device): per message the
         waypoint window at the car's position, the telemetry handler (cold, or warm with opts.warm_start) and the plant -- the
         reference's own kinematic model, not the simulator.  car [6, B] = x, y, psi, speed [mph], steering_angle, throttle is advanced
@@ -379,9 +384,16 @@ class BatchedMPC:
         grid) -- one call answers "how much delay does this tuning survive, compensated or not".
         ``horizon`` [B] int32 (mpc_drive_batch_device_horizon, _fused_horizon; fp64 handles, max_soc = 0): every car's own N, 3 .. the
         handle's, in the handler's solve; with ``model``'s dt row an N x dt grid is the cars of one call.  The lane kernel at every B,
-        the one launch included; sort the cars by horizon (a wave's pass lasts as long as its longest one)."""
+        the one launch included; sort the cars by horizon (a wave's pass lasts as long as its longest one).
+        ``plant`` [6, B] float64 (mpc_drive_batch_device_plant, _fused_plant; rows _abi.PLANT_*): the values every car is MOVED with --
+        Lf, steering gain and bias, acceleration gain, drag speed, side drift -- while its handler goes on believing ``model``: one call
+        answers "how wrong may the model be before the car leaves the road".  drive_plant_default(B, model) is the column that changes
+        nothing."""
         import torch
         B = car.shape[1]
+        if plant is not None and (plant.dtype != torch.float64 or not plant.is_cuda or not plant.is_contiguous() or
+                                  tuple(plant.shape) != (_abi.NPLANT, B)):
+            raise ValueError("plant must be a contiguous float64 CUDA tensor of shape (%d, B)" % _abi.NPLANT)
         if model is not None:
             self._check_model(model, B)
         if horizon is not None:
@@ -399,11 +411,14 @@ class BatchedMPC:
                "status": torch.empty((B,), dtype=torch.int32, device=dev), "iters": torch.empty((B,), dtype=torch.int32, device=dev)}
         s = stream if stream is not None else torch.cuda.current_stream(dev)
         name = ("mpc_drive_batch_device_fused" if fused else "mpc_drive_batch_device") + (
-            "_horizon" if horizon is not None else "_latency" if latency is not None else "_model" if model is not None else "")
+            "_plant" if plant is not None else "_horizon" if horizon is not None else "_latency" if latency is not None else
+            "_model" if model is not None else "")
         extra = (model.data_ptr(),) if model is not None else ()
         if latency is not None or horizon is not None:
             extra = (model.data_ptr() if model is not None else None,) + ((horizon.data_ptr(),) if horizon is not None else ()) + (
                 latency.data_ptr() if latency is not None else None,)
+        if plant is not None:
+            extra = tuple(t.data_ptr() if t is not None else None for t in (model, horizon, latency, plant))
         check(getattr(library(), name)(self._h, B, B, int(steps), car.data_ptr(), track_x.data_ptr(), track_y.data_ptr(), n,
                                                weights.data_ptr() if weights is not None else None, *extra,
                                                C.byref(opts) if opts is not None else None, C.byref(warm_opts) if warm_opts is not None else None,
@@ -412,10 +427,12 @@ class BatchedMPC:
               name)
         return res
 
-    def drive_numpy(self, car, track_x, track_y, steps, weights=None, opts=None, warm_opts=None, want_hist=True, model=None, latency=None, horizon=None):
+    def drive_numpy(self, car, track_x, track_y, steps, weights=None, opts=None, warm_opts=None, want_hist=True, model=None, latency=None, horizon=None,
+                    plant=None):
         """drive_torch for host arrays (mpc_drive_batch_host): one copy in, the loop, one copy out; synchronises.  `car` is copied:
         the cars after the last step are "car" of the result.  ``model`` [6, B]: as in drive_torch (mpc_drive_batch_host_model); ``latency`` [3, B]: as in
-        drive_torch (mpc_drive_batch_host_latency); ``horizon`` [B] int32: as in drive_torch (mpc_drive_batch_host_horizon)."""
+        drive_torch (mpc_drive_batch_host_latency); ``horizon`` [B] int32: as in drive_torch (mpc_drive_batch_host_horizon); ``plant`` [6, B]: as in
+        drive_torch (mpc_drive_batch_host_plant)."""
         f = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64)) if a is not None else None
         car, tx, ty, weights = f(car).copy(), f(track_x), f(track_y), f(weights)
         B, n = car.shape[1], tx.shape[0]
@@ -439,6 +456,11 @@ class BatchedMPC:
         extra = (p(model), p(latency)) if latency is not None else ((p(model),) if model is not None else ())
         if horizon is not None:
             extra = (p(model), p(horizon), p(latency))
+        if plant is not None:
+            plant = f(plant)
+            if plant.shape != (_abi.NPLANT, B):
+                raise ValueError("plant must have shape (%d, B)" % _abi.NPLANT)
+            name, extra = "mpc_drive_batch_host_plant", (p(model), p(horizon), p(latency), p(plant))
         check(getattr(library(), name)(self._h, B, B, int(steps), p(car), p(tx), p(ty), n, p(weights), *extra,
                                        C.byref(opts) if opts is not None else None, C.byref(warm_opts) if warm_opts is not None else None,
                                        p(res["summary"]), p(res["hist"]), p(res["status"]), p(res["iters"])), name)

@@ -148,7 +148,42 @@
  * mpc_drive_batch_device_fused_horizon writes BITWISE what mpc_drive_batch_device_horizon writes.  With a horizon it runs the one launch
  *   (the lane kernel's ROLL x MODEL x HORIZON x DRIVE builds, cold and warm: not staged, per-lane workspace rows, no lane compaction) at
  *   every B >= 1 on every fp64 handle with max_soc = 0 -- the rule of mpc_rollout_batch_device_fused_horizon, because a horizon call
- *   never takes the wave path or the fp32 start; mpc_drive_info counts it.  horizon == NULL: _fused_latency with that form's own rule. */
+ *   never takes the wave path or the fp32 start; mpc_drive_info counts it.  horizon == NULL: _fused_latency with that form's own rule.
+ *
+ * ---- per-car plant values: mpc_drive_*_plant -------------------------------------------------------------------------------------------
+ * How wrong may the controller's model be before the car leaves the road?  Everything above varies the controller per car and moves
+ * every car in the world that controller believes in.  These forms vary the world: wheelbase error, steering scale and bias,
+ * acceleration error, a steady side force -- a robustness grid is the columns of one call.  Each _plant form is its _horizon form plus
+ * `plant` directly behind `latency`: [MPC_NPLANT][ld] doubles addressed with the call's ld (host form: a host array, copied in with the
+ * other inputs), rows
+ *     MPC_PLANT_LF          Lf_p: the wheelbase value the car turns with [m]
+ *     MPC_PLANT_STEER_GAIN  g: the actuator's scale, 1 = exact
+ *     MPC_PLANT_STEER_BIAS  b: an offset of the steering angle [rad], in the simulator's sign like row 4 of car
+ *     MPC_PLANT_ACCEL_GAIN  a: the handler's guess is 6
+ *     MPC_PLANT_DRAG_SPEED  d: the handler's guess is 50 [m/s]
+ *     MPC_PLANT_DRIFT       w: a steady speed to the car's left [m/s]
+ *   There is no telemetry form: the handler reads nothing of the plant.
+ * plant == NULL: the call IS the _horizon form -- bitwise, with its dispatch, its refusals and its mpc_drive_info counts.
+ * plant != NULL: car i is moved with its column.  One substep of length h:
+ *     v = speed * 1609.34 / 3600     steer = -(steering_angle * g + b)     accel = (throttle - v / d) * a     dist = v * h
+ *     x += dist * cos(psi) - (w * h) * sin(psi)     y += dist * sin(psi) + (w * h) * cos(psi)     psi += steer * dist / Lf_p
+ *     speed = (v + accel * h) * 3600 / 1609.34
+ *   The handler is untouched: it believes its own `model` (or the handle), compensates with its own Lf, and is told the angle it asked
+ *   for -- rows 4 and 5 of car and of hist stay the commanded values (cmd_steer * max_steering_i, cmd_throttle), the controller's
+ *   normalisation; g models the actuator's scale error.  Unchanged: the window, the summary and record rows, sub_old / sub_new (the
+ *   call's or the latency column's), the warm rule, the dispatch, the mpc_drive_info counts.
+ *   mpc_drive_plant_default needs no device: col6 = {p->Lf, 1, 0, 6, 50, 0}, the column under which the plant is the one above, bit for
+ *   bit; a caller with a `model` array sets row 0 to the car's own Lf.
+ *   A column that cannot be used -- a value that is not finite, Lf_p <= 0, d <= 0 -- : the car is moved with the default column (its Lf
+ *   row: the car's own Lf, the model's or the handle's), and every step of it that the handler ended SUCCESS or ACCEPTABLE is
+ *   MPC_STATUS_INFEASIBLE in hist row 10, summary row 7 and the folded status (any other status of the handler stays).  The handler's
+ *   own status, which decides whether the car's next step starts warm, is not touched, and neither are the iterations.  car / summary /
+ *   hist hold no not-a-number because of it; every other car is bit for bit what it is without the defect.
+ *   Refusals: with plant != NULL an MPC_PRECISION_F32 handle is refused first (track driving: fp64 handles only); then those of the
+ *   _horizon forms, unchanged.
+ *   mpc_drive_batch_device_fused_plant writes BITWISE what mpc_drive_batch_device_plant writes and runs the one launch exactly where
+ *   _fused_horizon would with the same other arguments: the column is one more pointer of the builds that exist, read by instance index
+ *   at the hand-over only. */
 #define MPC_DRIVE_MAX_TRACK 4096
 #define MPC_DRIVE_NSUM 8
 #define MPC_DRIVE_REC 13
@@ -158,6 +193,8 @@ enum { MPC_DRIVE_REC_CAR = 0, MPC_DRIVE_REC_CMD = 6, MPC_DRIVE_REC_CTE = 8, MPC_
        MPC_DRIVE_REC_ITERS = 11, MPC_DRIVE_REC_K = 12 };
 #define MPC_NLATENCY 3
 enum { MPC_LATENCY_COMP = 0, MPC_LATENCY_SUB_OLD = 1, MPC_LATENCY_SUB_NEW = 2 };
+#define MPC_NPLANT 6
+enum { MPC_PLANT_LF = 0, MPC_PLANT_STEER_GAIN, MPC_PLANT_STEER_BIAS, MPC_PLANT_ACCEL_GAIN, MPC_PLANT_DRAG_SPEED, MPC_PLANT_DRIFT };
 
 typedef struct MpcDriveOpts {
   int32_t size;            /* sizeof(MpcDriveOpts) */
@@ -230,6 +267,20 @@ int mpc_telemetry_batch_host_horizon(MpcHandle *h, int64_t B, int64_t ld, int np
                                      const double *comp, const double *ptsx, const double *ptsy, const double *model, const int32_t *horizon,
                                      const double *warm_in, const int32_t *warm_status, double *warm_out, int64_t ld_warm,
                                      const MpcWarmOpts *opts, double *cmd, int32_t *status);
+int mpc_drive_plant_default(const MpcParams *p, double *col6);
+int mpc_drive_batch_device_plant(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                                 int n_track, const double *weights, const double *model, const int32_t *horizon, const double *latency,
+                                 const double *plant, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist,
+                                 int32_t *status, int32_t *iters, void *stream);
+int mpc_drive_batch_device_fused_plant(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
+                                       const double *track_y, int n_track, const double *weights, const double *model,
+                                       const int32_t *horizon, const double *latency, const double *plant, const MpcDriveOpts *opts,
+                                       const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status, int32_t *iters,
+                                       void *stream);
+int mpc_drive_batch_host_plant(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                               int n_track, const double *weights, const double *model, const int32_t *horizon, const double *latency,
+                               const double *plant, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist,
+                               int32_t *status, int32_t *iters);
 int mpc_drive_info(const MpcHandle *h, int64_t *out2);
 
 #endif /* MPC_AMD_DRIVE_H */

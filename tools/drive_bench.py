@@ -39,7 +39,18 @@ cell (the same starts in every cell), --sweep-steps messages, warm.  --legs pick
              checkout's library (the parent commit's, in the same session) with it.
 --forms picks the forms of grid and shuffled (one_launch, stepwise: a stepwise run of 300 messages lasts 300 x the slowest car of each
 step, so it may be given --reps and --warmup of its own in a run of its own; every leg records the reps it was timed with).
---merge FILE ...: copy the legs of files this tool wrote into --out (legs of the same name are joined)."""
+--merge FILE ...: copy the legs of files this tool wrote into --out (legs of the same name are joined).
+
+--plant: the mpc_drive_*_plant entry points (default --out profiles/drive_plant.json) --
+  grid       --ratios values of plant Lf / model Lf (0.5 .. 1.5) x --biases steering biases (-0.1 .. 0.1 rad) x --cars cars (the same
+             starts in every cell) in ONE warm one-launch _fused_plant call of --sweep-steps messages: per cell max |cte| and the first
+             step off the road, and the time of the launch.
+  cost       with --parent CHECKOUT (the parent commit, built): what the feature costs a caller who does not use it.  The plain run
+             and the --model run of this tool, each three times on the parent's library and three times on this one, alternating, every
+             run a process of its own (--root); per leg the six medians of the warm one-launch form are the figures, every other form
+             is recorded beside them.
+--legs grid,plain,model picks what is run (default: all three; plain and model need --parent); what --out already holds is kept: a
+cost leg is a list of sessions, and a run appends one."""
 import argparse
 import json
 import os
@@ -66,7 +77,7 @@ def main():
     ap.add_argument("--config", default="config-fast.json")
     ap.add_argument("--out", default=None)
     ap.add_argument("--model", action="store_true", help="measure the _model entry points and run the top-speed sweep")
-    ap.add_argument("--parent", default=None, help="--model: a file this tool wrote on the parent commit in the same session")
+    ap.add_argument("--parent", default=None, help="--model: a file this tool wrote on the parent commit in the same session; --plant: the parent commit's built checkout (the cost legs)")
     ap.add_argument("--speeds", type=int, default=16)
     ap.add_argument("--cars", type=int, default=4096)
     ap.add_argument("--sweep-steps", type=int, default=300)
@@ -78,9 +89,12 @@ def main():
     ap.add_argument("--legs", default="grid,shuffled,uniform,six", help="--horizon: which legs to run")
     ap.add_argument("--forms", default="one_launch,stepwise", help="--horizon: the forms of the grid and shuffled legs")
     ap.add_argument("--root", default=None, help="--horizon --legs six: another built checkout whose library is measured")
+    ap.add_argument("--plant", action="store_true", help="run the Lf-ratio x steering-bias grid of the _plant entry points")
+    ap.add_argument("--ratios", type=int, default=16, help="--plant: values of plant Lf / model Lf, 0.5 .. 1.5")
+    ap.add_argument("--biases", type=int, default=16, help="--plant: steering biases, -0.1 .. 0.1 rad")
     ap.add_argument("--merge", nargs="*", default=None, help="--horizon: files of this tool whose legs are copied into --out (nothing is run)")
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "drive_horizon.json" if a.horizon else "drive_latency.json" if a.latency else
+    a.out = a.out or os.path.join(ROOT, "profiles", "drive_plant.json" if a.plant else "drive_horizon.json" if a.horizon else "drive_latency.json" if a.latency else
                                   "drive_model.json" if a.model else "drive.json")
     if a.horizon and a.merge is not None:
         doc = {"tool": "tools/drive_bench.py --horizon", "legs": {}}
@@ -92,8 +106,10 @@ def main():
         json.dump(doc, open(a.out, "w"), indent=1)
         print("wrote", a.out)
         return
-    if a.latency and a.cars == 4096:
+    if (a.latency or a.plant) and a.cars == 4096:
         a.cars = 16
+    if a.plant:
+        return plant_grid(a)
     import torch
     assert torch.cuda.is_available(), "this benchmark needs a GPU"
     pkg = G.load_package()
@@ -273,6 +289,99 @@ def latency_grid(a, pkg, params, wp, t, d_tx, d_ty):
         B, steps, doc["ms"], " ".join("%.2f" % v for v in doc["iterations_per_solve_along_the_compensation_axis"])))
     json.dump(doc, open(a.out, "w"), indent=1)
     print("wrote", a.out)
+
+
+def plant_grid(a):
+    import torch
+    assert torch.cuda.is_available(), "this benchmark needs a GPU"
+    pkg = G.load_package()
+    dev = torch.device("cuda:0")
+    gd = os.path.join(ROOT, "tests", "golden")
+    params = pkg.params_from_json(os.path.join(gd, a.config))
+    wp = np.asarray(pkg.scenarios.load_waypoints(os.path.join(gd, "lake_track_waypoints.csv")), dtype=np.float64)
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(dev)
+    n_r, n_b, n_cars, steps = a.ratios, a.biases, a.cars, a.sweep_steps
+    ratios, biases = np.linspace(0.5, 1.5, n_r), np.linspace(-0.1, 0.1, n_b)
+    cells = n_r * n_b
+    B = cells * n_cars
+    # column = car * cells + ratio * n_b + bias; car c of every cell: the same start
+    plant = pkg.drive_plant_default(params, B)
+    plant[0] = params.Lf * np.tile(np.repeat(ratios, n_b), n_cars)
+    plant[2] = np.tile(np.tile(biases, n_r), n_cars)
+    cars = np.repeat(pkg.scenarios.track_starts(n_cars, params, wp, seed=126), cells, axis=1)
+    legs = ["grid", "plain", "model"] if a.legs == ap_default_legs else [x for x in a.legs.split(",") if x]
+    doc = json.load(open(a.out)) if os.path.exists(a.out) else {}
+    doc.update({"tool": "tools/drive_bench.py --plant", "config": a.config, "device": torch.cuda.get_device_name(0)})
+    if "grid" in legs:
+        doc["grid"] = plant_grid_leg(a, pkg, params, wp, t, plant, cars, ratios, biases)
+    if a.parent and ("plain" in legs or "model" in legs):
+        plant_cost_legs(a, doc, legs)
+    json.dump(doc, open(a.out, "w"), indent=1)
+    print("wrote", a.out)
+
+
+ap_default_legs = "grid,shuffled,uniform,six"
+
+
+def plant_grid_leg(a, pkg, params, wp, t, plant, cars, ratios, biases):
+    import torch
+    n_r, n_b, n_cars, steps = a.ratios, a.biases, a.cars, a.sweep_steps
+    B = n_r * n_b * n_cars
+    with pkg.BatchedMPC(params, B, device=0) as mpc:
+        opts = mpc.drive_opts(warm_start=1)
+        d_tx, d_ty = t(wp[:, 0]), t(wp[:, 1])
+        run = lambda: mpc.drive_torch(t(cars), d_tx, d_ty, steps, opts=opts, fused=True, want_hist=False, plant=t(plant))
+        run(); torch.cuda.synchronize()                                                           # (the first call grows the handle's rows)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        res = run()
+        e1.record()
+        torch.cuda.synchronize()
+        info = mpc.drive_info()
+    summ = res["summary"].cpu().numpy().reshape(8, n_cars, n_r, n_b)
+    off = np.where(summ[6] >= 0, summ[6], np.inf)
+    first_off = off.min(0)
+    print("cars off the road of %d, rows: plant Lf / model Lf %.2f .. %.2f, columns: steering bias %.3f .. %.3f rad" % (n_cars, ratios[0], ratios[-1], biases[0], biases[-1]))
+    for q in range(n_r):
+        print("%5.2f  " % ratios[q] + " ".join("%3d" % v for v in (summ[6, :, q] >= 0).sum(0)))
+    leg = {"call": "mpc_drive_batch_device_fused_plant, warm_start = 1, hist = NULL, one timed call after one untimed", "B": B, "steps": steps,
+                    "lf_ratios": ratios.tolist(), "steer_biases_rad": biases.tolist(), "cars_per_cell": n_cars, "cte_limit": opts.cte_limit,
+                    "ms": float(e0.elapsed_time(e1)), "solves_per_s": B * steps / (1e-3 * float(e0.elapsed_time(e1))), "drive_info": info,
+                    "max_abs_cte_max_over_cars": summ[0].max(0).tolist(), "max_abs_cte_median_over_cars": np.median(summ[0], axis=0).tolist(),
+                    "first_step_off_the_road": [[None if np.isinf(v) else int(v) for v in row] for row in first_off],
+                    "cars_off_the_road": (summ[6] >= 0).sum(0).tolist(), "failed_steps_mean": summ[7].mean(0).tolist()}
+    print("one launch: %d cars x %d messages in %.1f ms" % (B, steps, leg["ms"]))
+    return leg
+
+
+def plant_cost_legs(a, doc, legs):
+    import subprocess
+    import tempfile
+    # every run a process of its own, one at a time: the parent's library and this one, alternating
+    here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cost = doc.setdefault("cost_of_the_unused_feature", {"legs": {}})
+    cost.update({"what": "tools/drive_bench.py (plain) and --model, batch %d x %d messages; three runs on the parent commit's library and three on this "
+                         "build's, alternating, every run a process of its own; ms_median of every form per run" % (a.batch, a.steps),
+                 "judged_on": "the warm one-launch form (fused, warm_start = 1; --model: model, fused, warm_start = 1)"})
+    with tempfile.TemporaryDirectory() as d:
+        for leg, extra in (("plain", []), ("model", ["--model", "--speeds", "1", "--cars", "64", "--sweep-steps", "1"])):
+            if leg not in legs:
+                continue
+            runs = {"parent": [], "this_build": []}
+            for r in range(3):
+                for who, root in (("parent", os.path.abspath(a.parent)), ("this_build", here)):
+                    out = os.path.join(d, "%s_%s_%d.json" % (leg, who, r))
+                    subprocess.run([sys.executable, os.path.abspath(__file__), "--root", root, "--out", out, "--batch", str(a.batch), "--steps", str(a.steps),
+                                    "--reps", str(a.reps), "--warmup", str(a.warmup), "--config", a.config] + extra, check=True, stdout=subprocess.DEVNULL, timeout=600)
+                    rows = [x for x in json.load(open(out))["rows"] if "ms_median" in x and x.get("form") != "host_loop"]
+                    runs[who].append({"%s%s_warm%d" % (x["what"] + "_" if "what" in x else "", x["form"], x["warm_start"]): x["ms_median"] for x in rows})
+                    print(leg, who, r, json.dumps(runs[who][-1]), flush=True)
+            key = "model_fused_warm1" if leg == "model" else "fused_warm1"
+            par, new = [x[key] for x in runs["parent"]], [x[key] for x in runs["this_build"]]
+            cost["legs"].setdefault(leg, []).append({"reps": a.reps, "warmup": a.warmup, "runs": runs, "figure": key, "parent_ms": par, "this_build_ms": new, "this_build_median_ms": float(np.median(new)),
+                                 "parent_spread_ms": [min(par), max(par)], "median_inside_the_parent_spread": bool(min(par) <= np.median(new) <= max(par)),
+                                 "median_not_above_the_parent_spread": bool(np.median(new) <= max(par))})
+            print(leg, json.dumps({k: v for k, v in cost["legs"][leg][-1].items() if k != "runs"}), flush=True)
 
 
 HORIZON_NS, HORIZON_DTS = (5, 7, 10, 15, 20, 25), (0.05, 0.1, 0.15, 0.2)
