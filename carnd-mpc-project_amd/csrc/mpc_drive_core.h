@@ -56,11 +56,11 @@ MPC_HD int drive_progress(int k, int k_prev, int n) {
   return d;
 }
 
-/* The plant's own values (the mpc_drive_*_plant entry points): what the car really turns and accelerates with, where the handler goes on
- * believing `m`.  Lf in the heading update; steer = -(steering_angle * gain + bias), bias in the simulator's sign like the angle;
- * accel = (throttle - v / drag) * accel; drift: a steady speed to the car's left [m/s].  ok: the caller's column could be used.
- * DrivePlantNone: the plant of the entry points without `plant`, the expressions below as they always stood and nothing else. */
-struct DrivePlantNone {};
+/* The plant's own values: what the car really turns and accelerates with, where the handler goes on believing `m`.  Lf in the heading
+ * update; steer = -(steering_angle * gain + bias), bias in the simulator's sign like the angle; accel = (throttle - v / drag) * accel;
+ * drift: a steady speed to the car's left [m/s].  ok: the caller's column could be used.  Every car of every entry point is moved
+ * with one of these: its column of `plant` (the mpc_drive_*_plant entry points), or the default column, which is the plant of the
+ * entry points without `plant` bit for bit (drive_substep). */
 struct DrivePlantVals {
   double Lf, gain, bias, accel, drag, drift;
   bool ok;
@@ -87,38 +87,30 @@ MPC_HD DrivePlantVals drive_plant_vals_of(const MpcParams &P, const MV &m_, cons
   return d;
 }
 
-/* Where the plant reads Lf and max_steering: `m`, the template argument of mpc_run_core.h's functions (run_model_of) -- the handle's
- * MpcParams itself (the entry points without `model`: their callers pass P twice) or the car's mpc::ModelVals (the mpc_drive_*_model
- * entry points; a column that cannot be used has become the handle's values there, model_vals_of). */
+/* Where the plant reads max_steering, and the default column its Lf: `m`, the template argument of mpc_run_core.h's functions
+ * (run_model_of) -- the car's mpc::ModelVals (its column of `model`; one that cannot be used has become the handle's values there,
+ * model_vals_of; without `model`, ModelVals::of(P)) or the handle's MpcParams itself. */
 /* One plant substep of length h on car = {x, y, psi, speed [mph], steering_angle, throttle}: the handler's reading of the message
  * (MpH2MpS mpc_main.cpp:129, the sign :131, the acceleration :156 -- from the speed of this substep), Vehicle::move(h)
  * (Vehicle.cpp:145-168; the clamp at :156 is overwritten at :167), the speed back to mph (MpS2MpH, utils.h:19-21).
- * pv: DrivePlantNone or DrivePlantVals.  The terms a plant column adds are statements of their own behind the expressions that
- * stood here before it, so those contract as they did and the default column gives their bits. */
-template <class MV, class PV>
-MPC_HD void drive_substep(const MpcParams &P, const MV &m_, const PV &pv, double *car, double h) {
-  constexpr bool PLANT = std::is_same<PV, DrivePlantVals>::value;
-  (void)pv;
-  const MV &m = run_model_of(P, m_);
-  double Lf = m.Lf, drag = 50.0, acc = 6.0;
-  if constexpr (PLANT) { Lf = pv.Lf; drag = pv.drag; acc = pv.accel; }
+ * The terms a plant column adds are statements of their own behind the expressions that stood here before there were plant columns,
+ * so those contract as they did (-ffp-contract=on works within a statement) and the default column {Lf, 1, 0, 6, 50, 0} gives their
+ * bits: a product with 1, a difference with 0, and a drift of 0 that adds +-0 to a coordinate. */
+MPC_HD void drive_substep(const DrivePlantVals &pv, double *car, double h) {
+  const double Lf = pv.Lf, drag = pv.drag, acc = pv.accel;
   const double v = car[3] * 1609.34 / 3600.0;
   double steer = -car[4];
-  if constexpr (PLANT) {
-    steer = steer * pv.gain;
-    steer = steer - pv.bias;
-  }
+  steer = steer * pv.gain;
+  steer = steer - pv.bias;
   const double accel = (car[5] - v / drag) * acc;
   const double dist = v * h;
   double sn, cs;
   fsincos(car[2], &sn, &cs);
   double x = car[0] + dist * cs;
   double y = car[1] + dist * sn;
-  if constexpr (PLANT) {
-    const double side = pv.drift * h;
-    x = x - side * sn;
-    y = y + side * cs;
-  }
+  const double side = pv.drift * h;
+  x = x - side * sn;
+  y = y + side * cs;
   car[0] = x;
   car[1] = y;
   car[2] = car[2] + steer * dist / Lf;
@@ -128,21 +120,24 @@ MPC_HD void drive_substep(const MpcParams &P, const MV &m_, const PV &pv, double
 /* The plant between two messages: sub_old substeps under the command in force (rows 4 / 5), then the reply takes effect --
  * (cmd_steer * max_steering, cmd_throttle), the controller's normalisation whatever the plant column says; a reply that is not finite
  * leaves the old command in force --, then sub_new substeps.  psi is not normalised: the handler does that. */
-template <class MV, class PV>
-MPC_HD void drive_plant(const MpcParams &P, const MV &m_, const PV &pv, double *car, double cmd_steer, double cmd_throttle, int sub_old, int sub_new, double h) {
+template <class MV>
+MPC_HD void drive_plant(const MpcParams &P, const MV &m_, const DrivePlantVals &pv, double *car, double cmd_steer, double cmd_throttle, int sub_old, int sub_new, double h) {
   const MV &m = run_model_of(P, m_);
   MPC_STAGE_LOOP
-  for (int s = 0; s < sub_old; s++) drive_substep(P, m, pv, car, h);
+  for (int s = 0; s < sub_old; s++) drive_substep(pv, car, h);
   if (drive_finite(cmd_steer) && drive_finite(cmd_throttle)) { car[4] = cmd_steer * m.max_steering; car[5] = cmd_throttle; }
   MPC_STAGE_LOOP
-  for (int s = 0; s < sub_new; s++) drive_substep(P, m, pv, car, h);
+  for (int s = 0; s < sub_new; s++) drive_substep(pv, car, h);
 }
+/* The short call forms -- without plant values: the default column of `m`; without `m`: P itself.  CPU builds that include this header
+ * (test builds of other commits among them) call these; they forward to the one body above and add no path of their own
+ * (tests/cpp/drive_call_forms_test.cpp holds them to its bits).  The device code calls the full form only. */
 template <class MV>
 MPC_HD void drive_plant(const MpcParams &P, const MV &m, double *car, double cmd_steer, double cmd_throttle, int sub_old, int sub_new, double h) {
-  drive_plant(P, m, DrivePlantNone{}, car, cmd_steer, cmd_throttle, sub_old, sub_new, h);
+  drive_plant(P, m, drive_plant_vals_of(P, m, nullptr, 0, 0), car, cmd_steer, cmd_throttle, sub_old, sub_new, h);
 }
 MPC_HD void drive_plant(const MpcParams &P, double *car, double cmd_steer, double cmd_throttle, int sub_old, int sub_new, double h) {
-  drive_plant(P, P, DrivePlantNone{}, car, cmd_steer, cmd_throttle, sub_old, sub_new, h);
+  drive_plant(P, P, car, cmd_steer, cmd_throttle, sub_old, sub_new, h);
 }
 
 /* Car i's column of latency [MPC_NLATENCY][ld] (the mpc_drive_*_latency entry points): the seconds its handler compensates for and its
@@ -183,19 +178,17 @@ MPC_HD void drive_summary(int step, double *sum, double cte0, double epsi0, doub
 
 /* ---- one car of a batch between the handler's reply and the next message, as the plant-and-summary kernel and the CPU build run it:
  * car [6][ld] in / out, cmd [2][ld], pre [RUN_PRE_ROWS][ldp] (the handler's own rows: cte0, epsi0), the step's status and iterations,
- * the window index of this step and of the one before; sub_old / sub_new: the car's substep counts (the forms without: the call's);
- * summary [MPC_DRIVE_NSUM][ld], rec = this step's block of hist [MPC_DRIVE_REC][ld] or nullptr, status / iters (or nullptr) per car: worst code, summed iterations (mpc::RolloutCar).  m: the plant's
- * model values, as above.  pv: the plant's own values (DrivePlantNone: none).  A car whose plant column could not be used carries a
- * status at every step: a step the handler ended SUCCESS or ACCEPTABLE is recorded, summed and folded as INFEASIBLE; st_step itself,
- * which the warm rule reads, is the caller's and stays. */
-template <class MV, class PV>
-MPC_HD void drive_step_instance(const MpcParams &P, const MV &m, const PV &pv, const MpcDriveOpts &O, int sub_old, int sub_new, int64_t i, int64_t ld, int step,
-                                int n_track, double *car, const double *cmd, const double *pre, int64_t ldp, int32_t st_step, int32_t it_step, int k, int k_prev,
-                                double *summary, double *rec, int32_t *status, int32_t *iters) {
-  (void)pv;
-  if constexpr (std::is_same<PV, DrivePlantVals>::value) {
-    if (!pv.ok && (st_step == MPC_STATUS_SUCCESS || st_step == MPC_STATUS_ACCEPTABLE)) st_step = MPC_STATUS_INFEASIBLE;
-  }
+ * the window index of this step and of the one before; sub_old / sub_new: the car's substep counts (its latency column's, or the
+ * call's); summary [MPC_DRIVE_NSUM][ld], rec = this step's block of hist [MPC_DRIVE_REC][ld] or nullptr, status / iters (or nullptr)
+ * per car: worst code, summed iterations (mpc::RolloutCar).  m: the plant's model values, as above.  pv: the plant's own values
+ * (drive_plant_vals_of).  A car whose plant column could not be used carries a status at every step: a step the handler ended
+ * SUCCESS or ACCEPTABLE is recorded, summed and folded as INFEASIBLE; st_step itself, which the warm rule reads, is the caller's and
+ * stays. */
+template <class MV>
+MPC_HD void drive_step_instance(const MpcParams &P, const MV &m, const DrivePlantVals &pv, const MpcDriveOpts &O, int sub_old, int sub_new, int64_t i, int64_t ld,
+                                int step, int n_track, double *car, const double *cmd, const double *pre, int64_t ldp, int32_t st_step, int32_t it_step, int k,
+                                int k_prev, double *summary, double *rec, int32_t *status, int32_t *iters) {
+  if (!pv.ok && (st_step == MPC_STATUS_SUCCESS || st_step == MPC_STATUS_ACCEPTABLE)) st_step = MPC_STATUS_INFEASIBLE;
   double c[6], sum[MPC_DRIVE_NSUM] = {};
   MPC_UNROLL
   for (int q = 0; q < 6; q++) c[q] = car[q * ld + i];
@@ -227,11 +220,14 @@ MPC_HD void drive_step_instance(const MpcParams &P, const MV &m, const PV &pv, c
   MPC_UNROLL
   for (int q = 0; q < 6; q++) car[q * ld + i] = c[q];
 }
+/* The short call forms, as for drive_plant: without plant values (the default column of `m`), without counts (the call's), without `m`
+ * (P itself); each forwards to the one body above. */
 template <class MV>
-MPC_HD void drive_step_instance(const MpcParams &P, const MV &m, const MpcDriveOpts &O, int sub_old, int sub_new, int64_t i, int64_t ld, int step,
-                                int n_track, double *car, const double *cmd, const double *pre, int64_t ldp, int32_t st_step, int32_t it_step, int k, int k_prev,
+MPC_HD void drive_step_instance(const MpcParams &P, const MV &m, const MpcDriveOpts &O, int sub_old, int sub_new, int64_t i, int64_t ld, int step, int n_track,
+                                double *car, const double *cmd, const double *pre, int64_t ldp, int32_t st_step, int32_t it_step, int k, int k_prev,
                                 double *summary, double *rec, int32_t *status, int32_t *iters) {
-  drive_step_instance(P, m, DrivePlantNone{}, O, sub_old, sub_new, i, ld, step, n_track, car, cmd, pre, ldp, st_step, it_step, k, k_prev, summary, rec, status, iters);
+  drive_step_instance(P, m, drive_plant_vals_of(P, m, nullptr, 0, 0), O, sub_old, sub_new, i, ld, step, n_track, car, cmd, pre, ldp, st_step, it_step, k, k_prev,
+                      summary, rec, status, iters);
 }
 template <class MV>
 MPC_HD void drive_step_instance(const MpcParams &P, const MV &m, const MpcDriveOpts &O, int64_t i, int64_t ld, int step, int n_track, double *car,

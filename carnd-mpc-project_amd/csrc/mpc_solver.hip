@@ -246,7 +246,9 @@ struct MpcHorizonPart {
  * pointer, not a template argument: the lane kernel has the builds it had.
  * plant (mpc_drive_batch_device_fused_plant): the car's column of [MPC_NPLANT][ldo], or nullptr -- the default column, the plant of the
  * forms without.  Read by instance index at the hand-over only, where the plant runs, under the one test mpc::drive_plant_vals_of
- * makes; likewise a pointer and no template argument. */
+ * makes; likewise a pointer and no template argument.
+ * latency, model and plant reach the plant the way mpc_drive_plant_kernel hands them on: the car's counts, its mpc::ModelVals and its
+ * mpc::DrivePlantVals into the one mpc::drive_step_instance, so the one launch and the stepwise loop move a car with the same code. */
 struct MpcDrivePart {
   MpcDriveOpts O;
   double *car;                    /* [6][ldo] in / out */
@@ -1122,8 +1124,8 @@ __global__ __launch_bounds__(256) void mpc_rollout_step_kernel(int64_t B, int64_
   if (iters) iters[i] = (first ? 0 : iters[i]) + it_step[i];
 }
 
-/* Track driving (mpc_drive_batch_*, include/mpc_amd_drive.h), the two kernels around the handler's three: one car per lane, 256 per
- * block, no LDS, mpc::drive_* of mpc_drive_core.h.  The track is read at the loop index -- the same address in every lane of a wave,
+/* Track driving (mpc_drive_batch_*, include/mpc_amd_drive.h), the two kernels around the handler's three (and, with per-car latency,
+ * one before the loop): one car per lane, 256 per block, no LDS, mpc::drive_* of mpc_drive_core.h.  The track is read at the loop index -- the same address in every lane of a wave,
  * scalar loads -- and once per lane at the car's own nearest waypoint and window.
  * Sense: the window index of every car at its position and the window's waypoints, laid out as the handler takes them. */
 __global__ __launch_bounds__(256) void mpc_drive_sense_kernel(int64_t B, int64_t ld, int npts, const double *__restrict__ car,
@@ -1137,67 +1139,23 @@ __global__ __launch_bounds__(256) void mpc_drive_sense_kernel(int64_t B, int64_t
   k_now[i] = k;
 }
 
-/* Plant and summary: the step's record and summary rows, the car's worst status and summed iterations, then the car moved under the
- * command it was sent (mpc::drive_step_instance).  pre: the handler's own rows of this step (cte0, epsi0). */
+/* Plant and summary, the one kernel of every drive entry point: the step's record and summary rows, the car's worst status and summed
+ * iterations, then the car moved under the command it was sent (mpc::drive_step_instance).  pre: the handler's own rows of this step
+ * (cte0, epsi0).  The three per-car arrays are the caller's or nullptr, and a lane reads its car's column of each once:
+ *   latency [MPC_NLATENCY][ld]: the car's own substep counts (mpc::drive_latency_of: checked, 0 .. 1000); nullptr: the call's.
+ *   W.model [MPC_NMODEL][W.ld_model]: Lf in the heading update, max_steering in turning the reply into the steering angle in force; a
+ *     column that cannot be used: the handle's values (mpc::model_vals_of; the handler has reported the car INFEASIBLE); nullptr: the
+ *     handle's values.
+ *   plant [MPC_NPLANT][ld]: what the car is moved with (mpc::drive_plant_vals_of: checked; a column that cannot be used becomes a
+ *     status); nullptr: the default column, the plant of the entry points without `plant` bit for bit. */
 __global__ __launch_bounds__(256) void mpc_drive_plant_kernel(const MpcParams P, const MpcDriveOpts O, int64_t B, int64_t ld, int step, int n_track,
                                                               double *__restrict__ car, const double *__restrict__ cmd,
                                                               const double *__restrict__ pre, int64_t ldp, const int32_t *__restrict__ st_step,
                                                               const int32_t *__restrict__ it_step, const int32_t *k_now,
                                                               const int32_t *k_prev, double *__restrict__ summary,
-                                                              double *__restrict__ rec, int32_t *__restrict__ status, int32_t *__restrict__ iters) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B) return;
-  mpc::drive_step_instance(P, P, O, i, ld, step, n_track, car, cmd, pre, ldp, st_step[i], it_step[i], k_now[i], k_prev[i], summary, rec, status, iters);
-}
-/* ... its MODEL build (the mpc_drive_*_model entry points): one more argument, and the lane reads its car's column of it once -- Lf in
- * the heading update, max_steering in turning the reply into the steering angle in force.  A column that cannot be used: the handle's
- * values (mpc::model_vals_of); the handler has reported the car INFEASIBLE. */
-__global__ __launch_bounds__(256) void mpc_drive_plant_model_kernel(const MpcParams P, const MpcDriveOpts O, int64_t B, int64_t ld, int step, int n_track,
-                                                                    double *__restrict__ car, const double *__restrict__ cmd,
-                                                                    const double *__restrict__ pre, int64_t ldp, const int32_t *__restrict__ st_step,
-                                                                    const int32_t *__restrict__ it_step, const int32_t *k_now,
-                                                                    const int32_t *k_prev, double *__restrict__ summary,
-                                                                    double *__restrict__ rec, int32_t *__restrict__ status, int32_t *__restrict__ iters,
-                                                                    const MpcModelPart W) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B) return;
-  mpc::drive_step_instance(P, mpc::model_vals_of(P, W.model, W.ld_model, i), O, i, ld, step, n_track, car, cmd, pre, ldp, st_step[i], it_step[i], k_now[i],
-                           k_prev[i], summary, rec, status, iters);
-}
-
-/* ... and its builds with per-car latency (the mpc_drive_*_latency entry points): the lane reads its car's column of latency
- * [MPC_NLATENCY][ld] once and moves the car with its own substep counts (mpc::drive_latency_of: checked, 0 .. 1000). */
-template <bool MODEL, class... Model>
-__global__ __launch_bounds__(256) void mpc_drive_plant_latency_kernel(const MpcParams P, const MpcDriveOpts O, int64_t B, int64_t ld, int step, int n_track,
-                                                                      double *__restrict__ car, const double *__restrict__ cmd,
-                                                                      const double *__restrict__ pre, int64_t ldp, const int32_t *__restrict__ st_step,
-                                                                      const int32_t *__restrict__ it_step, const int32_t *k_now,
-                                                                      const int32_t *k_prev, double *__restrict__ summary,
-                                                                      double *__restrict__ rec, int32_t *__restrict__ status, int32_t *__restrict__ iters,
-                                                                      const double *__restrict__ latency, const Model... model) {
-  static_assert(sizeof...(Model) == (MODEL ? 1 : 0), "the MODEL builds take one MpcModelPart");
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B) return;
-  const mpc::DriveLatency dl = mpc::drive_latency_of(O, latency, ld, i);
-  if constexpr (MODEL) {
-    const MpcModelPart &W = (model, ...);
-    mpc::drive_step_instance(P, mpc::model_vals_of(P, W.model, W.ld_model, i), O, dl.sub_old, dl.sub_new, i, ld, step, n_track, car, cmd, pre, ldp, st_step[i],
-                             it_step[i], k_now[i], k_prev[i], summary, rec, status, iters);
-  } else
-    mpc::drive_step_instance(P, P, O, dl.sub_old, dl.sub_new, i, ld, step, n_track, car, cmd, pre, ldp, st_step[i], it_step[i], k_now[i], k_prev[i], summary, rec,
-                             status, iters);
-}
-/* ... and its build with per-car plant values (the mpc_drive_*_plant entry points): the lane reads its car's column of plant
- * [MPC_NPLANT][ld] once and moves the car with it (mpc::drive_plant_vals_of: checked; a column that cannot be used becomes a status).
- * latency and W.model may each be nullptr here: the call's counts, the handle's values. */
-__global__ __launch_bounds__(256) void mpc_drive_plant_vals_kernel(const MpcParams P, const MpcDriveOpts O, int64_t B, int64_t ld, int step, int n_track,
-                                                                   double *__restrict__ car, const double *__restrict__ cmd,
-                                                                   const double *__restrict__ pre, int64_t ldp, const int32_t *__restrict__ st_step,
-                                                                   const int32_t *__restrict__ it_step, const int32_t *k_now,
-                                                                   const int32_t *k_prev, double *__restrict__ summary,
-                                                                   double *__restrict__ rec, int32_t *__restrict__ status, int32_t *__restrict__ iters,
-                                                                   const double *__restrict__ latency, const MpcModelPart W,
-                                                                   const double *__restrict__ plant) {
+                                                              double *__restrict__ rec, int32_t *__restrict__ status, int32_t *__restrict__ iters,
+                                                              const double *__restrict__ latency, const MpcModelPart W,
+                                                              const double *__restrict__ plant) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B) return;
   int sub_old = O.sub_old, sub_new = O.sub_new;
@@ -3118,11 +3076,11 @@ static int drive_rows(MpcHandle *h, int64_t B, int64_t ld, bool warm, const doub
 /* The stepwise loop: `steps` x (sense kernel, the telemetry handler -- run_impl with tel, the weights and an iterations pointer --,
  * plant-and-summary kernel) on the caller's stream; no host synchronisation.  x.warm: every step after the first is the _warm handler
  * on the handle's own buffer, in place (rollout_impl's arrangement).  x.model (device, [MPC_NMODEL][ld]): the handler is the
- * telemetry _model call -- run_impl reads the columns where the caller has them -- and the plant kernel its MODEL build.
+ * telemetry _model call -- run_impl reads the columns where the caller has them.
  * x.latency (device, [MPC_NLATENCY][ld]): one more kernel first, the comp row the handler takes (not-a-number for a column that cannot
- * be used); the handler is the telemetry _latency call on it and the plant kernel its latency build, with or without model.
- * x.plant (device, [MPC_NPLANT][ld]): the plant kernel is its plant build, which takes the caller's latency and model or nullptr; the
- * handler's calls are what they are without it. */
+ * be used); the handler is the telemetry _latency call on it, with or without model.
+ * x.plant (device, [MPC_NPLANT][ld]): the handler's calls are what they are without it.
+ * The plant kernel is one, and takes the caller's latency, model and plant as they came, each an array or nullptr. */
 static int drive_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y, int n_track,
                       const double *weights, const MpcDriveOpts &O, CallExtras x, double *summary, double *hist, int32_t *status,
                       int32_t *iters, void *stream_) {
@@ -3150,21 +3108,8 @@ static int drive_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *ca
     x.w = WarmIO{t == 0 ? nullptr : h->d_warm, h->d_rstat, h->d_warm, S, x.w.wopts, 0};
     MPC_TRY(run_impl(h, B, ld, O.npts, car, true, O.extra_latency, ptsx, ptsy, nullptr, cmd, nullptr, h->d_rstat, h->d_iters, nullptr, stream_, x));
     double *rec = hist ? hist + (int64_t)t * MPC_DRIVE_REC * ld : nullptr;
-    if (x.plant)
-      hipLaunchKernelGGL(mpc_drive_plant_vals_kernel, dim3(grid), dim3(256), 0, s, h->params, O, B, ld, t, n_track, car, cmd, h->d_run, S, h->d_rstat,
-                         h->d_iters, k_now, k_prev, summary, rec, status, iters, latency, MpcModelPart{x.model, ld}, x.plant);
-    else if (latency && x.model)
-      hipLaunchKernelGGL((mpc_drive_plant_latency_kernel<true, MpcModelPart>), dim3(grid), dim3(256), 0, s, h->params, O, B, ld, t, n_track, car, cmd, h->d_run, S,
-                         h->d_rstat, h->d_iters, k_now, k_prev, summary, rec, status, iters, latency, MpcModelPart{x.model, ld});
-    else if (latency)
-      hipLaunchKernelGGL((mpc_drive_plant_latency_kernel<false>), dim3(grid), dim3(256), 0, s, h->params, O, B, ld, t, n_track, car, cmd, h->d_run, S,
-                         h->d_rstat, h->d_iters, k_now, k_prev, summary, rec, status, iters, latency);
-    else if (x.model)
-      hipLaunchKernelGGL(mpc_drive_plant_model_kernel, dim3(grid), dim3(256), 0, s, h->params, O, B, ld, t, n_track, car, cmd, h->d_run, S, h->d_rstat,
-                         h->d_iters, k_now, k_prev, summary, rec, status, iters, MpcModelPart{x.model, ld});
-    else
-      hipLaunchKernelGGL(mpc_drive_plant_kernel, dim3(grid), dim3(256), 0, s, h->params, O, B, ld, t, n_track, car, cmd, h->d_run, S, h->d_rstat,
-                         h->d_iters, k_now, k_prev, summary, rec, status, iters);
+    hipLaunchKernelGGL(mpc_drive_plant_kernel, dim3(grid), dim3(256), 0, s, h->params, O, B, ld, t, n_track, car, cmd, h->d_run, S, h->d_rstat, h->d_iters,
+                       k_now, k_prev, summary, rec, status, iters, latency, MpcModelPart{x.model, ld}, x.plant);
     MPC_HIP_CHECK(hipGetLastError());
   }
   ++h->n_drive_stepwise;

@@ -1,6 +1,6 @@
 /*
  * drive_horizon_sanitize.cpp -- TEST-ONLY: the CPU build of the track-driving loop with a per-car horizon
- * (tests/drive_horizon_twin/drive_horizon_twin.cpp, compiled into this program) under AddressSanitizer + UndefinedBehaviorSanitizer.
+ * (tests/drive_twin/drive_twin.cpp, compiled into this program) under AddressSanitizer + UndefinedBehaviorSanitizer.
  * argv[1]: a config file; argv[2]: a text file of numbers -- n_track, B, track_x [n_track], track_y [n_track], car [6][B] -- that
  * tests/test_drive_horizon.py writes: the 16 cars of its mixed batch on the lake track.
  * N = 10, ld = B + 1, 8 messages, cold and warm, horizon (3, 4, 5, 7, 10)[i % 5]: the mixed batch; then the same batch with the
@@ -18,10 +18,17 @@
 
 #include "mpc_amd.h"
 
-extern "C" int mpc_drive_horizon_twin(const MpcParams *p, int64_t B, int64_t ld, int steps, double *car, const double *tx, const double *ty,
-                                      int n_track, const double *weights, const double *model, const int32_t *horizon, const double *latency,
-                                      const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status,
-                                      int32_t *iters);
+extern "C" int mpc_drive_twin_plant(const MpcParams *p, int64_t B, int64_t ld, double *car, const double *cmd, const double *model,
+                                    const double *latency, const double *plant, const MpcDriveOpts *opts, int32_t *ok);
+extern "C" int mpc_drive_twin_handler(const MpcParams *p, int64_t B, int64_t ld, const double *car, const double *comp, const int32_t *k,
+                                      const double *tx, const double *ty, int n_track, const double *weights, const double *model,
+                                      const int32_t *horizon, const MpcDriveOpts *opts, const double *warm_in, const int32_t *warm_status,
+                                      double *warm_out, int64_t ld_warm, const MpcWarmOpts *warm_opts, double *cmd, int32_t *status, int32_t *iters,
+                                      double *cte_epsi);
+extern "C" int mpc_drive_twin(const MpcParams *p, int64_t B, int64_t ld, int steps, double *car, const double *tx, const double *ty, int n_track,
+                              const double *weights, const double *model, const int32_t *horizon, const double *latency, const double *plant,
+                              const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status, int32_t *iters,
+                              int32_t *handler_status);
 
 /* mpc_drive_opts_default and mpc_warm_opts_default live in the product library; their values, restated for a program without it */
 static MpcDriveOpts drive_opts(const MpcParams &p, int warm) {
@@ -77,8 +84,8 @@ int main(int argc, char **argv) {
       r.car = car0;
       r.summary.assign((size_t)MPC_DRIVE_NSUM * ld, sentinel); r.hist.assign((size_t)steps * MPC_DRIVE_REC * ld, sentinel);
       r.status.assign((size_t)ld, isentinel); r.iters.assign((size_t)ld, isentinel);
-      return mpc_drive_horizon_twin(&p, B, ld, steps, r.car.data(), tx.data(), ty.data(), n_track, nullptr, md, n.data(), lat.data(), &o, &wo,
-                                    r.summary.data(), r.hist.data(), r.status.data(), r.iters.data());
+      return mpc_drive_twin(&p, B, ld, steps, r.car.data(), tx.data(), ty.data(), n_track, nullptr, md, n.data(), lat.data(), nullptr, &o, &wo,
+                            r.summary.data(), r.hist.data(), r.status.data(), r.iters.data(), nullptr);
     };
     Result mixed, dirty, with_model;
     if (run(hz, nullptr, mixed) != MPC_OK || run(hz_bad, nullptr, dirty) != MPC_OK || run(hz, model.data(), with_model) != MPC_OK) { printf("warm %d: rc\n", warm); return 4; }

@@ -1,6 +1,6 @@
 /*
  * drive_latency_sanitize.cpp -- TEST-ONLY: the CPU build of the track-driving loop with per-car latency
- * (tests/drive_latency_twin/drive_latency_twin.cpp, compiled into this program) on garbage columns and garbage cars, under
+ * (tests/drive_twin/drive_twin.cpp, compiled into this program) on garbage columns and garbage cars, under
  * AddressSanitizer + UndefinedBehaviorSanitizer.  argv[1]: a config file.  Every array has exactly the size the call states, so a read
  * or write outside a car's column, or past column B, is an error of the run; a count taken from an unchecked double would be one too
  * (the conversion of a not-a-number to int is undefined behaviour).
@@ -18,16 +18,17 @@
 
 #include "mpc_amd.h"
 
-extern "C" int mpc_drive_latency_twin_plant(const MpcParams *p, int64_t B, int64_t ld, double *car, const double *cmd, const double *model,
-                                            const double *latency, const MpcDriveOpts *opts);
-extern "C" int mpc_drive_latency_twin_handler(const MpcParams *p, int64_t B, int64_t ld, const double *car, const double *comp, const int32_t *k,
-                                              const double *tx, const double *ty, int n_track, const double *weights, const double *model,
-                                              const MpcDriveOpts *opts, const double *warm_in, const int32_t *warm_status, double *warm_out,
-                                              int64_t ld_warm, const MpcWarmOpts *warm_opts, double *cmd, int32_t *status, int32_t *iters,
-                                              double *cte_epsi);
-extern "C" int mpc_drive_latency_twin(const MpcParams *p, int64_t B, int64_t ld, int steps, double *car, const double *tx, const double *ty,
-                                      int n_track, const double *weights, const double *model, const double *latency, const MpcDriveOpts *opts,
-                                      const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status, int32_t *iters);
+extern "C" int mpc_drive_twin_plant(const MpcParams *p, int64_t B, int64_t ld, double *car, const double *cmd, const double *model,
+                                    const double *latency, const double *plant, const MpcDriveOpts *opts, int32_t *ok);
+extern "C" int mpc_drive_twin_handler(const MpcParams *p, int64_t B, int64_t ld, const double *car, const double *comp, const int32_t *k,
+                                      const double *tx, const double *ty, int n_track, const double *weights, const double *model,
+                                      const int32_t *horizon, const MpcDriveOpts *opts, const double *warm_in, const int32_t *warm_status,
+                                      double *warm_out, int64_t ld_warm, const MpcWarmOpts *warm_opts, double *cmd, int32_t *status, int32_t *iters,
+                                      double *cte_epsi);
+extern "C" int mpc_drive_twin(const MpcParams *p, int64_t B, int64_t ld, int steps, double *car, const double *tx, const double *ty, int n_track,
+                              const double *weights, const double *model, const int32_t *horizon, const double *latency, const double *plant,
+                              const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status, int32_t *iters,
+                              int32_t *handler_status);
 
 /* mpc_drive_opts_default and mpc_warm_opts_default live in the product library; their values, restated for a program without it */
 static MpcDriveOpts drive_opts(const MpcParams &p, int warm) {
@@ -73,8 +74,8 @@ int main(int argc, char **argv) {
     const MpcDriveOpts o = drive_opts(p, warm);
     std::vector<double> car = car0, summary((size_t)MPC_DRIVE_NSUM * ld, sentinel), hist((size_t)steps * MPC_DRIVE_REC * ld, sentinel);
     std::vector<int32_t> status((size_t)ld, isentinel), iters((size_t)ld, isentinel);
-    const int rc = mpc_drive_latency_twin(&p, B, ld, steps, car.data(), tx.data(), ty.data(), n_track, nullptr, model.data(), lat.data(), &o, &wo,
-                                          summary.data(), hist.data(), status.data(), iters.data());
+    const int rc = mpc_drive_twin(&p, B, ld, steps, car.data(), tx.data(), ty.data(), n_track, nullptr, model.data(), nullptr, lat.data(), nullptr, &o, &wo,
+                                  summary.data(), hist.data(), status.data(), iters.data(), nullptr);
     if (rc != MPC_OK) { printf("warm %d: rc %d\n", warm, rc); return 4; }
     printf("warm %d status", warm);
     for (int i = 0; i < B; i++) printf(" %d", status[i]);
@@ -106,12 +107,12 @@ int main(int argc, char **argv) {
     std::vector<double> car = car0, cmd((size_t)2 * ld, NAN);
     for (int i = 0; i < B; i++) { cmd[i] = 0.1; cmd[(size_t)ld + i] = 0.5; }
     cmd[1] = NAN; cmd[(size_t)ld + 2] = INFINITY;
-    if (mpc_drive_latency_twin_plant(&p, B, ld, car.data(), cmd.data(), model.data(), lat.data(), &o) != MPC_OK) bad++;
+    if (mpc_drive_twin_plant(&p, B, ld, car.data(), cmd.data(), model.data(), lat.data(), nullptr, &o, nullptr) != MPC_OK) bad++;
     for (int i = 4; i <= 9; i++)
       for (int q = 0; q < 6; q++) if (memcmp(&car[(size_t)q * ld + i], &car[(size_t)q * ld], sizeof(double)) != 0) bad++;
     for (int q = 0; q < 6; q++) if (!std::isnan(car[(size_t)q * ld + B])) bad++;
-    if (mpc_drive_latency_twin_plant(&p, B, B - 1, car.data(), cmd.data(), model.data(), lat.data(), &o) != MPC_ERR_INVALID) bad++;
-    if (mpc_drive_latency_twin_plant(&p, B, ld, car.data(), cmd.data(), model.data(), nullptr, &o) != MPC_ERR_INVALID) bad++;
+    if (mpc_drive_twin_plant(&p, B, B - 1, car.data(), cmd.data(), model.data(), lat.data(), nullptr, &o, nullptr) != MPC_ERR_INVALID) bad++;
+    if (mpc_drive_twin_plant(&p, B, ld, car.data(), nullptr, model.data(), lat.data(), nullptr, &o, nullptr) != MPC_ERR_INVALID) bad++;   /* (no reply) */
   }
   /* one handler call on the comp row itself: not-a-number, -1 and an infinity end with a status and a finite reply */
   {
@@ -120,14 +121,14 @@ int main(int argc, char **argv) {
     std::vector<double> cmd((size_t)2 * ld, sentinel), ce((size_t)2 * ld, sentinel), comp(lat.begin(), lat.begin() + ld);
     comp[6] = INFINITY;
     for (int i = 0; i < B; i++) k[i] = i == 3 ? n_track - 1 : 0;
-    if (mpc_drive_latency_twin_handler(&p, B, ld, car0.data(), comp.data(), k.data(), tx.data(), ty.data(), n_track, nullptr, model.data(), &o, nullptr,
-                                       nullptr, nullptr, 0, &wo, cmd.data(), status.data(), iters.data(), ce.data()) != MPC_OK) bad++;
+    if (mpc_drive_twin_handler(&p, B, ld, car0.data(), comp.data(), k.data(), tx.data(), ty.data(), n_track, nullptr, model.data(), nullptr, &o, nullptr,
+                               nullptr, nullptr, 0, &wo, cmd.data(), status.data(), iters.data(), ce.data()) != MPC_OK) bad++;
     for (int i = 4; i <= 6; i++) if (status[i] == MPC_STATUS_SUCCESS || !std::isfinite(cmd[i]) || !std::isfinite(cmd[(size_t)ld + i])) bad++;
     if (memcmp(&cmd[9], &cmd[0], sizeof(double)) != 0 || memcmp(&cmd[(size_t)ld + 9], &cmd[ld], sizeof(double)) != 0 || status[9] != status[0]) bad++;
     if (cmd[B] != sentinel || cmd[(size_t)ld + B] != sentinel || status[B] != isentinel || ce[B] != sentinel) bad++;
     k[2] = n_track;
-    if (mpc_drive_latency_twin_handler(&p, B, ld, car0.data(), comp.data(), k.data(), tx.data(), ty.data(), n_track, nullptr, model.data(), &o, nullptr,
-                                       nullptr, nullptr, 0, &wo, cmd.data(), status.data(), iters.data(), ce.data()) != MPC_ERR_INVALID) bad++;
+    if (mpc_drive_twin_handler(&p, B, ld, car0.data(), comp.data(), k.data(), tx.data(), ty.data(), n_track, nullptr, model.data(), nullptr, &o, nullptr,
+                               nullptr, nullptr, 0, &wo, cmd.data(), status.data(), iters.data(), ce.data()) != MPC_ERR_INVALID) bad++;
   }
   printf("bad %d\n", bad);
   return bad == 0 ? 0 : 1;

@@ -1,6 +1,6 @@
 /*
  * drive_model_sanitize.cpp -- TEST-ONLY: the CPU build of the track-driving loop with per-car model values
- * (tests/drive_model_twin/drive_model_twin.cpp, compiled into this program) on garbage columns and garbage cars, under
+ * (tests/drive_twin/drive_twin.cpp, compiled into this program) on garbage columns and garbage cars, under
  * AddressSanitizer + UndefinedBehaviorSanitizer.  argv[1]: a config file.  Every array has exactly the size the call states, so a read
  * or write outside a car's column, or past column B, is an error of the run.
  * A circular track of 40 waypoints (radius 50 m); N = 10, B = 8, ld = 9, 3 messages, cold and warm.  The columns from B on hold
@@ -16,15 +16,17 @@
 
 #include "mpc_amd.h"
 
-extern "C" int mpc_drive_model_twin_plant(const MpcParams *p, int64_t B, int64_t ld, double *car, const double *cmd, const double *model,
-                                          int sub_old, int sub_new, double h);
-extern "C" int mpc_drive_model_twin_handler(const MpcParams *p, int64_t B, int64_t ld, const double *car, const int32_t *k, const double *tx,
-                                            const double *ty, int n_track, const double *weights, const double *model, const MpcDriveOpts *opts,
-                                            const double *warm_in, const int32_t *warm_status, double *warm_out, int64_t ld_warm,
-                                            const MpcWarmOpts *warm_opts, double *cmd, int32_t *status, int32_t *iters, double *cte_epsi);
-extern "C" int mpc_drive_model_twin(const MpcParams *p, int64_t B, int64_t ld, int steps, double *car, const double *tx, const double *ty,
-                                    int n_track, const double *weights, const double *model, const MpcDriveOpts *opts,
-                                    const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status, int32_t *iters);
+extern "C" int mpc_drive_twin_plant(const MpcParams *p, int64_t B, int64_t ld, double *car, const double *cmd, const double *model,
+                                    const double *latency, const double *plant, const MpcDriveOpts *opts, int32_t *ok);
+extern "C" int mpc_drive_twin_handler(const MpcParams *p, int64_t B, int64_t ld, const double *car, const double *comp, const int32_t *k,
+                                      const double *tx, const double *ty, int n_track, const double *weights, const double *model,
+                                      const int32_t *horizon, const MpcDriveOpts *opts, const double *warm_in, const int32_t *warm_status,
+                                      double *warm_out, int64_t ld_warm, const MpcWarmOpts *warm_opts, double *cmd, int32_t *status, int32_t *iters,
+                                      double *cte_epsi);
+extern "C" int mpc_drive_twin(const MpcParams *p, int64_t B, int64_t ld, int steps, double *car, const double *tx, const double *ty, int n_track,
+                              const double *weights, const double *model, const int32_t *horizon, const double *latency, const double *plant,
+                              const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status, int32_t *iters,
+                              int32_t *handler_status);
 
 /* mpc_drive_opts_default and mpc_warm_opts_default live in the product library; their values, restated for a program without it */
 static MpcDriveOpts drive_opts(const MpcParams &p, int warm) {
@@ -66,8 +68,8 @@ int main(int argc, char **argv) {
     const MpcDriveOpts o = drive_opts(p, warm);
     std::vector<double> car = car0, summary((size_t)MPC_DRIVE_NSUM * ld, sentinel), hist((size_t)steps * MPC_DRIVE_REC * ld, sentinel);
     std::vector<int32_t> status((size_t)ld, isentinel), iters((size_t)ld, isentinel);
-    const int rc = mpc_drive_model_twin(&p, B, ld, steps, car.data(), tx.data(), ty.data(), n_track, nullptr, model.data(), &o, &wo, summary.data(),
-                                        hist.data(), status.data(), iters.data());
+    const int rc = mpc_drive_twin(&p, B, ld, steps, car.data(), tx.data(), ty.data(), n_track, nullptr, model.data(), nullptr, nullptr, nullptr, &o, &wo,
+                                  summary.data(), hist.data(), status.data(), iters.data(), nullptr);
     if (rc != MPC_OK) { printf("warm %d: rc %d\n", warm, rc); return 4; }
     printf("warm %d status", warm);
     for (int i = 0; i < B; i++) printf(" %d", status[i]);
@@ -95,12 +97,14 @@ int main(int argc, char **argv) {
     std::vector<double> car = car0, cmd((size_t)2 * ld, NAN);
     for (int i = 0; i < B; i++) { cmd[i] = 0.1; cmd[(size_t)ld + i] = 0.5; }
     cmd[1] = NAN; cmd[(size_t)ld + 2] = INFINITY;
-    if (mpc_drive_model_twin_plant(&p, B, ld, car.data(), cmd.data(), model.data(), 10, 2, 0.01) != MPC_OK) bad++;
+    MpcDriveOpts po = drive_opts(p, 0);
+    po.sub_old = 10; po.sub_new = 2; po.h = 0.01;
+    if (mpc_drive_twin_plant(&p, B, ld, car.data(), cmd.data(), model.data(), nullptr, nullptr, &po, nullptr) != MPC_OK) bad++;
     for (int i = 4; i <= 7; i++)
       for (int q = 0; q < 6; q++) if (memcmp(&car[(size_t)q * ld + i], &car[(size_t)q * ld], sizeof(double)) != 0) bad++;
     for (int q = 0; q < 6; q++) if (!std::isnan(car[(size_t)q * ld + B])) bad++;
-    if (mpc_drive_model_twin_plant(&p, B, B - 1, car.data(), cmd.data(), model.data(), 10, 2, 0.01) != MPC_ERR_INVALID) bad++;
-    if (mpc_drive_model_twin_plant(&p, B, ld, car.data(), cmd.data(), nullptr, 10, 2, 0.01) != MPC_ERR_INVALID) bad++;
+    if (mpc_drive_twin_plant(&p, B, B - 1, car.data(), cmd.data(), model.data(), nullptr, nullptr, &po, nullptr) != MPC_ERR_INVALID) bad++;
+    if (mpc_drive_twin_plant(&p, B, ld, car.data(), nullptr, model.data(), nullptr, nullptr, &po, nullptr) != MPC_ERR_INVALID) bad++;   /* (no reply) */
   }
   /* one handler call: every window index the track has is taken, one outside it is refused */
   {
@@ -108,14 +112,14 @@ int main(int argc, char **argv) {
     std::vector<int32_t> k((size_t)ld, 0), status((size_t)ld, isentinel), iters((size_t)ld, isentinel);
     std::vector<double> cmd((size_t)2 * ld, sentinel), ce((size_t)2 * ld, sentinel);
     for (int i = 0; i < B; i++) k[i] = i == 3 ? n_track - 1 : 0;
-    if (mpc_drive_model_twin_handler(&p, B, ld, car0.data(), k.data(), tx.data(), ty.data(), n_track, nullptr, model.data(), &o, nullptr, nullptr,
-                                     nullptr, 0, &wo, cmd.data(), status.data(), iters.data(), ce.data()) != MPC_OK) bad++;
+    if (mpc_drive_twin_handler(&p, B, ld, car0.data(), nullptr, k.data(), tx.data(), ty.data(), n_track, nullptr, model.data(), nullptr, &o, nullptr, nullptr,
+                               nullptr, 0, &wo, cmd.data(), status.data(), iters.data(), ce.data()) != MPC_OK) bad++;
     for (int i = 4; i <= 6; i++) if (status[i] != MPC_STATUS_INFEASIBLE || !std::isfinite(cmd[i]) || !std::isfinite(cmd[(size_t)ld + i])) bad++;
     if (memcmp(&cmd[7], &cmd[0], sizeof(double)) != 0 || memcmp(&cmd[(size_t)ld + 7], &cmd[ld], sizeof(double)) != 0 || status[7] != status[0]) bad++;
     if (cmd[B] != sentinel || cmd[(size_t)ld + B] != sentinel || status[B] != isentinel || ce[B] != sentinel) bad++;
     k[2] = n_track;
-    if (mpc_drive_model_twin_handler(&p, B, ld, car0.data(), k.data(), tx.data(), ty.data(), n_track, nullptr, model.data(), &o, nullptr, nullptr,
-                                     nullptr, 0, &wo, cmd.data(), status.data(), iters.data(), ce.data()) != MPC_ERR_INVALID) bad++;
+    if (mpc_drive_twin_handler(&p, B, ld, car0.data(), nullptr, k.data(), tx.data(), ty.data(), n_track, nullptr, model.data(), nullptr, &o, nullptr, nullptr,
+                               nullptr, 0, &wo, cmd.data(), status.data(), iters.data(), ce.data()) != MPC_ERR_INVALID) bad++;
   }
   printf("bad %d\n", bad);
   return bad == 0 ? 0 : 1;

@@ -1,6 +1,6 @@
 /*
  * drive_plant_sanitize.cpp -- TEST-ONLY: the CPU build of the track-driving loop with per-car plant values
- * (tests/drive_plant_twin/drive_plant_twin.cpp, compiled into this program) on garbage columns and garbage cars, under
+ * (tests/drive_twin/drive_twin.cpp, compiled into this program) on garbage columns and garbage cars, under
  * AddressSanitizer + UndefinedBehaviorSanitizer.  argv[1]: a config file.  Every array has exactly the size the call states, so a read
  * or write outside a car's column, or past column B, is an error of the run.
  * A circular track of 40 waypoints (radius 50 m); N = 10, B = 12, ld = 13, 3 messages, cold and warm.  The columns from B on hold
@@ -19,12 +19,17 @@
 
 #include "mpc_amd.h"
 
-extern "C" int mpc_drive_plant_twin_plant(const MpcParams *p, int64_t B, int64_t ld, double *car, const double *cmd, const double *model,
-                                          const double *plant, int sub_old, int sub_new, double h, int32_t *ok);
-extern "C" int mpc_drive_plant_twin(const MpcParams *p, int64_t B, int64_t ld, int steps, double *car, const double *tx, const double *ty,
-                                    int n_track, const double *weights, const double *model, const double *latency, const double *plant,
-                                    const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status,
-                                    int32_t *iters, int32_t *handler_status);
+extern "C" int mpc_drive_twin_plant(const MpcParams *p, int64_t B, int64_t ld, double *car, const double *cmd, const double *model,
+                                    const double *latency, const double *plant, const MpcDriveOpts *opts, int32_t *ok);
+extern "C" int mpc_drive_twin_handler(const MpcParams *p, int64_t B, int64_t ld, const double *car, const double *comp, const int32_t *k,
+                                      const double *tx, const double *ty, int n_track, const double *weights, const double *model,
+                                      const int32_t *horizon, const MpcDriveOpts *opts, const double *warm_in, const int32_t *warm_status,
+                                      double *warm_out, int64_t ld_warm, const MpcWarmOpts *warm_opts, double *cmd, int32_t *status, int32_t *iters,
+                                      double *cte_epsi);
+extern "C" int mpc_drive_twin(const MpcParams *p, int64_t B, int64_t ld, int steps, double *car, const double *tx, const double *ty, int n_track,
+                              const double *weights, const double *model, const int32_t *horizon, const double *latency, const double *plant,
+                              const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status, int32_t *iters,
+                              int32_t *handler_status);
 
 /* mpc_drive_opts_default, mpc_warm_opts_default and mpc_drive_plant_default live in the product library; their values, restated for a
  * program without it */
@@ -77,14 +82,14 @@ int main(int argc, char **argv) {
     const MpcDriveOpts o = drive_opts(p, warm);
     std::vector<double> car = car0, summary((size_t)MPC_DRIVE_NSUM * ld, sentinel), hist((size_t)steps * MPC_DRIVE_REC * ld, sentinel);
     std::vector<int32_t> status((size_t)ld, isentinel), iters((size_t)ld, isentinel), hs((size_t)steps * ld, isentinel);
-    const int rc = mpc_drive_plant_twin(&p, B, ld, steps, car.data(), tx.data(), ty.data(), n_track, nullptr, model.data(), lat.data(), plant.data(), &o,
-                                        &wo, summary.data(), hist.data(), status.data(), iters.data(), hs.data());
+    const int rc = mpc_drive_twin(&p, B, ld, steps, car.data(), tx.data(), ty.data(), n_track, nullptr, model.data(), nullptr, lat.data(), plant.data(), &o,
+                                  &wo, summary.data(), hist.data(), status.data(), iters.data(), hs.data());
     if (rc != MPC_OK) { printf("warm %d: rc %d\n", warm, rc); return 4; }
     /* the same cars under the default column everywhere: what cars 2 - 9 must equal but for their status rows */
     std::vector<double> dcar = car0, dsummary((size_t)MPC_DRIVE_NSUM * ld, sentinel), dhist((size_t)steps * MPC_DRIVE_REC * ld, sentinel);
     std::vector<int32_t> dstatus((size_t)ld, isentinel), diters((size_t)ld, isentinel);
-    if (mpc_drive_plant_twin(&p, B, ld, steps, dcar.data(), tx.data(), ty.data(), n_track, nullptr, model.data(), lat.data(), dplant.data(), &o, &wo,
-                             dsummary.data(), dhist.data(), dstatus.data(), diters.data(), nullptr) != MPC_OK) return 5;
+    if (mpc_drive_twin(&p, B, ld, steps, dcar.data(), tx.data(), ty.data(), n_track, nullptr, model.data(), nullptr, lat.data(), dplant.data(), &o, &wo,
+                       dsummary.data(), dhist.data(), dstatus.data(), diters.data(), nullptr) != MPC_OK) return 5;
     printf("warm %d status", warm);
     for (int i = 0; i < B; i++) printf(" %d", status[i]);
     printf("\n");
@@ -126,16 +131,18 @@ int main(int argc, char **argv) {
     std::vector<int32_t> ok((size_t)ld, isentinel);
     for (int i = 0; i < B; i++) { cmd[i] = 0.1; cmd[(size_t)ld + i] = 0.5; }
     cmd[1] = NAN; cmd[(size_t)ld + 10] = INFINITY;
-    if (mpc_drive_plant_twin_plant(&p, B, ld, car.data(), cmd.data(), model.data(), plant.data(), 10, 2, 0.01, ok.data()) != MPC_OK) bad++;
-    if (mpc_drive_plant_twin_plant(&p, B, ld, dcar.data(), cmd.data(), model.data(), dplant.data(), 10, 2, 0.01, nullptr) != MPC_OK) bad++;
+    MpcDriveOpts po = drive_opts(p, 0);
+    po.sub_old = 10; po.sub_new = 2; po.h = 0.01;
+    if (mpc_drive_twin_plant(&p, B, ld, car.data(), cmd.data(), model.data(), nullptr, plant.data(), &po, ok.data()) != MPC_OK) bad++;
+    if (mpc_drive_twin_plant(&p, B, ld, dcar.data(), cmd.data(), model.data(), nullptr, dplant.data(), &po, nullptr) != MPC_OK) bad++;
     for (int i = 0; i < B; i++) if (ok[i] != ((i >= 2 && i <= 9) ? 0 : 1)) bad++;
     for (int i = 2; i <= 9; i++)
       for (int q = 0; q < 6; q++) if (memcmp(&car[(size_t)q * ld + i], &dcar[(size_t)q * ld + i], sizeof(double)) != 0 || !std::isfinite(car[(size_t)q * ld + i])) bad++;
     for (int q = 0; q < 6; q++) if (memcmp(&car[(size_t)q * ld + 11], &car[(size_t)q * ld], sizeof(double)) != 0) bad++;
     for (int q = 0; q < 6; q++) if (!std::isnan(car[(size_t)q * ld + B])) bad++;
     if (ok[B] != isentinel) bad++;
-    if (mpc_drive_plant_twin_plant(&p, B, B - 1, car.data(), cmd.data(), model.data(), plant.data(), 10, 2, 0.01, nullptr) != MPC_ERR_INVALID) bad++;
-    if (mpc_drive_plant_twin_plant(&p, B, ld, car.data(), cmd.data(), model.data(), nullptr, 10, 2, 0.01, nullptr) != MPC_ERR_INVALID) bad++;
+    if (mpc_drive_twin_plant(&p, B, B - 1, car.data(), cmd.data(), model.data(), nullptr, plant.data(), &po, nullptr) != MPC_ERR_INVALID) bad++;
+    if (mpc_drive_twin_plant(&p, B, ld, car.data(), nullptr, model.data(), nullptr, plant.data(), &po, nullptr) != MPC_ERR_INVALID) bad++;   /* (no reply) */
   }
   printf("bad %d\n", bad);
   return bad == 0 ? 0 : 1;

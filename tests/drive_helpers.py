@@ -1,10 +1,16 @@
-"""Helpers of the track-driving tests (test infrastructure): the TEST-ONLY CPU build of the drive loop (tests/drive_twin), numpy's
-statement of the summary rows, the plant as a composition of the oracle's Vehicle::move, and the oracle's telemetry handler on
-recorded steps -- the comparison is solve by solve, so loop amplification cannot enter.  Shared by tests/test_drive.py and
-tests/test_drive_gpu.py."""
+"""Helpers of the track-driving tests (test infrastructure): the TEST-ONLY CPU build of the drive loop (tests/drive_twin: one library
+for every form, and one call of each of its functions here), numpy's statement of the summary rows, the plant as a composition of the
+oracle's Vehicle::move, the oracle's telemetry handler on recorded steps -- the comparison is solve by solve, so loop amplification
+cannot enter --, and the device side of every form: the raw-ABI call of a drive entry point and the child process that runs a batch
+with cars no caller should send.  Shared by the tests/test_drive*.py; the drive_*_helpers.py modules hold what depends on one per-car
+array."""
 import ctypes as C
+import importlib
+import json
 import os
 import subprocess
+import sys
+import tempfile
 
 import numpy as np
 
@@ -56,11 +62,26 @@ def window_points(waypoints, k, npts=6):
     return np.ascontiguousarray(wp[idx, 0]), np.ascontiguousarray(wp[idx, 1])
 
 
-def twin_plant(twin, params, car, cmd, sub_old, sub_new, h):
-    car, cmd = _f(car).copy(), _f(cmd)
+def plant_opts(params, sub_old, sub_new, h):
+    """the handle's default MpcDriveOpts with these substep counts and this substep length"""
+    import __graft_entry__ as G
+    return G.load_package().drive_opts_default(params, sub_old=sub_old, sub_new=sub_new, h=h)
+
+
+def twin_plant_call(twin, params, car, cmd, opts, model=None, latency=None, plant=None):
+    """mpc_drive_twin_plant: the cars moved with opts' counts (latency: their own) and substep length; model, latency and plant [., B]
+    or None (NULL) -> the moved cars [6, B] and ok [B] (whether each plant column could be used)"""
+    car, cmd, model, latency, plant = _f(car).copy(), _f(cmd), _f(model), _f(latency), _f(plant)
     B = car.shape[1]
-    assert twin.mpc_drive_twin_plant(C.byref(params), C.c_int64(B), C.c_int64(B), vp(car), vp(cmd), C.c_int(sub_old), C.c_int(sub_new), C.c_double(h)) == 0
-    return car
+    assert all(a is None or a.shape == (n, B) for a, n in ((model, 6), (latency, 3), (plant, 6)))
+    ok = np.zeros(B, dtype=np.int32)
+    rc = twin.mpc_drive_twin_plant(C.byref(params), C.c_int64(B), C.c_int64(B), vp(car), vp(cmd), vp(model), vp(latency), vp(plant), C.byref(opts), vp(ok))
+    assert rc == 0, rc
+    return car, ok
+
+
+def twin_plant(twin, params, car, cmd, sub_old, sub_new, h):
+    return twin_plant_call(twin, params, car, cmd, plant_opts(params, sub_old, sub_new, h))[0]
 
 
 def oracle_plant(cfg, car, cmd, max_steering, sub_old, sub_new, h):
@@ -103,36 +124,56 @@ def numpy_plant(car, cmd, params, sub_old, sub_new, h):
     return np.ascontiguousarray(car)
 
 
-def twin_handler(twin, params, waypoints, car, k, opts, warm_opts, weights=None, warm=None, warm_status=None, want_warm=False):
-    """One handler call of the CPU build on cars [6, B] with the windows that start at k -> cmd, status, iters, cte_epsi, warm."""
+def twin_handler_call(twin, params, waypoints, car, k, opts, warm_opts, comp=None, model=None, horizon=None, weights=None, warm=None, warm_status=None,
+                      want_warm=False, keep_warm=False):
+    """mpc_drive_twin_handler: one handler call of the CPU build on cars [6, B] with the windows that start at k; comp [B] (None:
+    opts.extra_latency), model [6, B] and horizon [B] or None (NULL) -> cmd, status, iters, cte_epsi, warm (the rows of params.N;
+    keep_warm: the rows the call does not write keep what `warm` held)."""
     tx, ty = track_of(waypoints)
-    car = _f(car)
+    car, model, comp = _f(car), _f(model), _f(comp)
     B = car.shape[1]
     k = np.ascontiguousarray(k, dtype=np.int32)
+    horizon = np.ascontiguousarray(horizon, dtype=np.int32) if horizon is not None else None
     rows = (params.N - 1) * 22
     cmd = np.zeros((2, B)); status = np.zeros(B, dtype=np.int32); iters = np.zeros(B, dtype=np.int32); ce = np.zeros((2, B))
-    wout = np.zeros((rows, B)) if (want_warm or warm is not None) else None
+    wout = None
+    if want_warm or warm is not None:
+        wout = np.array(warm, dtype=np.float64, copy=True) if (keep_warm and warm is not None) else np.zeros((rows, B))
     warm = _f(warm)
     if warm_status is not None:
         warm_status = np.ascontiguousarray(warm_status, dtype=np.int32)
-    rc = twin.mpc_drive_twin_handler(C.byref(params), C.c_int64(B), C.c_int64(B), vp(car), vp(k), vp(tx), vp(ty), C.c_int(len(tx)), vp(_f(weights)),
-                                     C.byref(opts), vp(warm), vp(warm_status), vp(wout), C.c_int64(B), C.byref(warm_opts), vp(cmd), vp(status),
-                                     vp(iters), vp(ce))
+    rc = twin.mpc_drive_twin_handler(C.byref(params), C.c_int64(B), C.c_int64(B), vp(car), vp(comp), vp(k), vp(tx), vp(ty), C.c_int(len(tx)), vp(_f(weights)),
+                                     vp(model), vp(horizon), C.byref(opts), vp(warm), vp(warm_status), vp(wout), C.c_int64(B), C.byref(warm_opts), vp(cmd),
+                                     vp(status), vp(iters), vp(ce))
     assert rc == 0, rc
     return {"cmd": cmd, "status": status, "iters": iters, "cte_epsi": ce, "warm": wout}
 
 
-def twin_drive(twin, params, waypoints, car, steps, opts, warm_opts, weights=None):
-    """mpc_drive_twin with the arguments of mpc_drive_batch_host -> car, summary, hist [steps, 13, B], status, iters."""
+def twin_handler(twin, params, waypoints, car, k, opts, warm_opts, weights=None, warm=None, warm_status=None, want_warm=False):
+    return twin_handler_call(twin, params, waypoints, car, k, opts, warm_opts, weights=weights, warm=warm, warm_status=warm_status, want_warm=want_warm)
+
+
+def twin_drive_call(twin, params, waypoints, car, steps, opts, warm_opts, model=None, horizon=None, latency=None, plant=None, weights=None):
+    """mpc_drive_twin with the arguments of mpc_drive_batch_host_plant, each per-car array or None (NULL) -> car, summary,
+    hist [steps, 13, B], status, iters, and handler_status [steps, B]: the handler's own status of every step."""
     tx, ty = track_of(waypoints)
-    car = _f(car).copy()
+    car, model, latency, plant = _f(car).copy(), _f(model), _f(latency), _f(plant)
     B = car.shape[1]
+    horizon = np.ascontiguousarray(horizon, dtype=np.int32) if horizon is not None else None
+    assert all(a is None or a.shape == (n, B) for a, n in ((model, 6), (latency, 3), (plant, 6))) and (horizon is None or horizon.shape == (B,))
     summary = np.full((NSUM, B), SENTINEL); hist = np.full((steps, REC, B), SENTINEL)
     status = np.full(B, ISENTINEL, dtype=np.int32); iters = np.full(B, ISENTINEL, dtype=np.int32)
+    hs = np.full((steps, B), ISENTINEL, dtype=np.int32)
     rc = twin.mpc_drive_twin(C.byref(params), C.c_int64(B), C.c_int64(B), C.c_int(steps), vp(car), vp(tx), vp(ty), C.c_int(len(tx)), vp(_f(weights)),
-                             C.byref(opts), C.byref(warm_opts), vp(summary), vp(hist), vp(status), vp(iters))
+                             vp(model), vp(horizon), vp(latency), vp(plant), C.byref(opts), C.byref(warm_opts), vp(summary), vp(hist), vp(status),
+                             vp(iters), vp(hs))
     assert rc == 0, rc
-    return {"car": car, "summary": summary, "hist": hist, "status": status, "iters": iters}
+    return {"car": car, "summary": summary, "hist": hist, "status": status, "iters": iters, "handler_status": hs}
+
+
+def twin_drive(twin, params, waypoints, car, steps, opts, warm_opts, weights=None):
+    """mpc_drive_twin with the arguments of mpc_drive_batch_host"""
+    return twin_drive_call(twin, params, waypoints, car, steps, opts, warm_opts, weights=weights)
 
 
 def summary_from_hist(hist, n_track, cte_limit):
@@ -182,3 +223,143 @@ def oracle_check_steps(cfgname, over, params, waypoints, hist, extra, cars=None)
                 d_thr = max(d_thr, abs(thr - hist[t, REC_CMD + 1, i]))
     assert d_steer <= TOL_STEER and d_thr <= TOL_THROTTLE, (d_steer, d_thr)
     return d_steer, d_thr
+
+
+# ---- the device side (tests/test_drive*_gpu.py) --------------------------------------------------------------------------------------
+CHILD_TIMEOUT_S = 120
+FORMS = {"device": "mpc_drive_batch_device", "fused": "mpc_drive_batch_device_fused", "host": "mpc_drive_batch_host"}
+ENTRY_ARGS = {"": (), "model": ("model",), "latency": ("model", "latency"), "horizon": ("model", "horizon", "latency"),
+              "plant": ("model", "horizon", "latency", "plant")}       # what each entry point takes between `weights` and `opts`
+HZ_PAD = -999          # what the horizon array holds from column B on
+KEYS = ("car", "summary", "hist", "status", "iters")
+
+
+def to_device(a, dev, dtype=np.float64):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
+
+
+def fast_params(pkg, golden_dir, **over):
+    return pkg.params_from_json(os.path.join(golden_dir, "config-fast.json"), **dict(dict(N=10), **over))
+
+
+def device_drive(pkg, params, waypoints, car, steps, dev, model=None, horizon=None, latency=None, plant=None, form="device", entry="plant", warm=0,
+                 weights=None, hist=True, pad=3, opts_over=None, opts=None, mpc=None):
+    """A drive entry point through the raw ABI with ld = B + pad: the symbol FORMS[form] + "_" + entry ("": the one without a suffix),
+    called with exactly that symbol's arguments (ENTRY_ARGS; each array may be None: NULL; an array the symbol does not take must be
+    None).  Inputs hold NaN (horizon: HZ_PAD) from column B on, outputs the sentinels everywhere before the call.  opts: the call's
+    MpcDriveOpts (None: the defaults with warm_start = warm and opts_over).  -> the arrays cut to B, after checking that nothing behind
+    column B was written; and the handle's mpc_drive_info.  mpc: a live handle to use (its info then counts every call made on it)."""
+    import torch
+    lib = pkg.library()
+    B = car.shape[1]
+    ld = B + pad
+    tx, ty = track_of(waypoints)
+    opts = opts if opts is not None else pkg.drive_opts_default(params, warm_start=warm, **(opts_over or {}))
+    given = {"model": model, "horizon": horizon, "latency": latency, "plant": plant}
+    assert all(v is None for k, v in given.items() if k not in ENTRY_ARGS[entry]), entry
+
+    def wide(a, fill=np.nan):
+        if a is None:
+            return None
+        w = np.full((a.shape[0], ld), fill); w[:, :B] = a
+        return w
+    h_car, h_w = wide(car), wide(weights)
+    h_x = {k: wide(v) for k, v in given.items() if k != "horizon"}
+    h_x["horizon"] = None
+    if horizon is not None:
+        h_x["horizon"] = np.full(ld, HZ_PAD, dtype=np.int32); h_x["horizon"][:B] = horizon
+    h_sum = np.full((NSUM, ld), SENTINEL); h_hist = np.full((steps, REC, ld), SENTINEL) if hist else None
+    h_st = np.full(ld, ISENTINEL, dtype=np.int32); h_it = np.full(ld, ISENTINEL, dtype=np.int32)
+    call = getattr(lib, FORMS[form] + ("_" + entry if entry else ""))
+    own = mpc is None
+    if own:
+        mpc = pkg.BatchedMPC(params, max(B, 1), device=0)
+    try:
+        if form == "host":
+            p = lambda a: a.ctypes.data if a is not None else None
+            ex = [p(h_x[k]) for k in ENTRY_ARGS[entry]]
+            rc = call(mpc._h, B, ld, steps, p(h_car), p(tx), p(ty), len(tx), p(h_w), *ex, C.byref(opts), None, p(h_sum), p(h_hist), p(h_st), p(h_it))
+            assert rc == 0, lib.mpc_last_error()
+            got = {"car": h_car, "summary": h_sum, "hist": h_hist, "status": h_st, "iters": h_it}
+        else:
+            dd = lambda a, dt=np.float64: to_device(a, dev, dt) if a is not None else None
+            d = {"car": dd(h_car), "summary": dd(h_sum), "hist": dd(h_hist), "status": dd(h_st, np.int32), "iters": dd(h_it, np.int32)}
+            d_tx, d_ty, d_w = dd(tx), dd(ty), dd(h_w)
+            d_x = {k: dd(v, np.int32 if k == "horizon" else np.float64) for k, v in h_x.items()}
+            p = lambda t: t.data_ptr() if t is not None else None
+            ex = [p(d_x[k]) for k in ENTRY_ARGS[entry]]
+            rc = call(mpc._h, B, ld, steps, p(d["car"]), p(d_tx), p(d_ty), len(tx), p(d_w), *ex, C.byref(opts), None, p(d["summary"]), p(d["hist"]),
+                      p(d["status"]), p(d["iters"]), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            assert rc == 0, lib.mpc_last_error()
+            torch.cuda.synchronize()
+            got = {k: (v.cpu().numpy() if v is not None else None) for k, v in d.items()}
+        info = mpc.drive_info()
+    finally:
+        if own:
+            mpc.close()
+    assert np.isnan(got["car"][:, B:]).all() and (got["summary"][:, B:] == SENTINEL).all() and (got["status"][B:] == ISENTINEL).all() and (got["iters"][B:] == ISENTINEL).all()
+    if hist:
+        assert (got["hist"][:, :, B:] == SENTINEL).all()
+    out = {k: (v[..., :B].copy() if v is not None else None) for k, v in got.items()}
+    assert (out["summary"] != SENTINEL).all() and (out["status"] != ISENTINEL).all() and (out["iters"] != ISENTINEL).all()
+    out["info"] = info
+    return out
+
+
+def same(a, b, keys=KEYS, cars=None):
+    """bitwise, NaN == NaN included (a contained car may hold one in both)"""
+    for k in keys:
+        if a[k] is None or b[k] is None:      # (a call without hist: everything else is compared)
+            continue
+        x, y = (a[k], b[k]) if cars is None else (a[k][..., cars], b[k][..., cars])
+        assert x.shape == y.shape and x.tobytes() == y.tobytes(), k
+
+
+def child_main(path):
+    """Runs in the child: the batches of the case function named in the spec -- "module.function", called with (pkg, params, waypoints)
+    -> [(tag, car, the per-car arrays and entry of device_drive)] -- on the device, cold and warm, results into an .npz.  Every drive is
+    one call; nothing is retried."""
+    sys.path.insert(0, ROOT)
+    import __graft_entry__ as G
+    import torch
+    pkg = G.load_package()
+    spec = json.load(open(path + ".json"))
+    gd = os.path.join(ROOT, "tests", "golden")
+    params = fast_params(pkg, gd, **spec["params_over"])
+    wp = pkg.scenarios.load_waypoints(os.path.join(gd, "lake_track_waypoints.csv"))
+    module, func = spec["case"].rsplit(".", 1)
+    dev = torch.device("cuda:0")
+    out = {}
+    for warm in (0, 1):
+        for tag, car, kw in getattr(importlib.import_module(module), func)(pkg, params, wp):
+            r = device_drive(pkg, params, wp, car, 4, dev, warm=warm, form="fused" if spec["fused"] else "device", **kw)
+            for k in KEYS:
+                out["%d/%s/%s" % (warm, tag, k)] = r[k]
+            out["%d/%s/info" % (warm, tag)] = np.array([r["info"]["fused_launches"], r["info"]["stepwise_loops"]])
+    np.savez(path, **out)
+
+
+def run_in_child(case, fused, wave_max_batch=None, timeout=CHILD_TIMEOUT_S):
+    """The case function `case` ("module.function", see child_main) in a fresh child process -> {(warm, tag): the arrays of
+    device_drive}; a child that does not end within `timeout` seconds fails the caller (subprocess.TimeoutExpired) after it has been
+    killed; the parent checks the exit status"""
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "case.npz")
+        over = {} if wave_max_batch is None else {"wave_max_batch": int(wave_max_batch)}
+        json.dump({"case": case, "params_over": over, "fused": bool(fused)}, open(path + ".json", "w"))
+        env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(ROOT, "tests"), ROOT] + os.environ.get("PYTHONPATH", "").split(os.pathsep)))
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), path], capture_output=True, text=True, timeout=timeout, env=env)
+        assert p.returncode == 0, p.stderr[-4000:]
+        z = np.load(path)
+        res = {}
+        for key in z.files:
+            warm, tag, k = key.split("/")
+            res.setdefault((int(warm), tag), {})[k] = z[key]
+        for r in res.values():
+            r["info"] = {"fused_launches": int(r["info"][0]), "stepwise_loops": int(r["info"][1])}
+    return res
+
+
+if __name__ == "__main__":
+    child_main(sys.argv[1])

@@ -163,3 +163,16 @@ def test_track_starts(pkg, golden_dir, waypoints):
     d = np.sqrt(((car[:2].T[:, None, :] - wp[None]) ** 2).sum(2)).min(1)
     assert d.max() < np.sqrt((np.diff(np.vstack([wp, wp[:1]]), axis=0) ** 2).sum(1)).max()      # on the track: nearer to a waypoint than a segment is long
     assert np.array_equal(car, pkg.scenarios.track_starts(512, params, waypoints, seed=1))
+
+
+def test_short_call_forms_of_the_core(golden_dir):
+    """tests/cpp/drive_call_forms_test.cpp: mpc::drive_plant and mpc::drive_step_instance without plant values / substep counts /
+    model values are the full form on the default column, bit for bit (a stand-alone program, no contraction)."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "carnd-mpc-project_amd", "csrc")
+    with tempfile.TemporaryDirectory() as d:
+        exe = os.path.join(d, "drive_call_forms_test")
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-I" + os.path.join(root, "include"), "-I" + csrc,
+                               os.path.join(root, "tests", "cpp", "drive_call_forms_test.cpp"), os.path.join(csrc, "mpc_params.cpp"), "-lm", "-o", exe])
+        p = subprocess.run([exe, os.path.join(golden_dir, "config-fast.json")], capture_output=True, text=True, timeout=60)
+    assert p.returncode == 0 and "bad 0" in p.stdout, (p.stdout, p.stderr[-2000:])

@@ -38,48 +38,10 @@ def _params(pkg, golden_dir, **over):
     return pkg.params_from_json(os.path.join(golden_dir, "config-fast.json"), N=10, **over)
 
 
-def _drive(pkg, params, waypoints, car, steps, dev, warm=0, weights=None, hist=True, pad=3, host=False, opts=None, fused=False):
-    """mpc_drive_batch_device (fused: mpc_drive_batch_device_fused; host: mpc_drive_batch_host) through the raw ABI with ld = B + pad:
-    inputs hold NaN from column B on, outputs the sentinels everywhere before the call.  -> the arrays cut to B, after checking that nothing behind column B was written; and the handle's
-    mpc_drive_info."""
-    import torch
-    lib = pkg.library()
-    B = car.shape[1]
-    ld = B + pad
-    tx, ty = D.track_of(waypoints)
-    opts = opts if opts is not None else pkg.drive_opts_default(params, warm_start=warm)
-
-    def wide(a, fill=np.nan):
-        w = np.full((a.shape[0], ld), fill); w[:, :B] = a
-        return w
-    h_car = wide(car); h_w = wide(weights) if weights is not None else None
-    h_sum = np.full((D.NSUM, ld), F); h_hist = np.full((steps, D.REC, ld), F) if hist else None
-    h_st = np.full(ld, I, dtype=np.int32); h_it = np.full(ld, I, dtype=np.int32)
-    with pkg.BatchedMPC(params, max(B, 1), device=0) as mpc:
-        if host:
-            p = lambda a: a.ctypes.data if a is not None else None
-            rc = lib.mpc_drive_batch_host(mpc._h, B, ld, steps, p(h_car), p(tx), p(ty), len(tx), p(h_w), C.byref(opts), None, p(h_sum), p(h_hist), p(h_st), p(h_it))
-            assert rc == 0, lib.mpc_last_error()
-            got = {"car": h_car, "summary": h_sum, "hist": h_hist, "status": h_st, "iters": h_it}
-        else:
-            d = {"car": _t(h_car, dev), "summary": _t(h_sum, dev), "hist": _t(h_hist, dev) if hist else None, "status": _t(h_st, dev, np.int32),
-                 "iters": _t(h_it, dev, np.int32)}
-            d_tx, d_ty, d_w = _t(tx, dev), _t(ty, dev), _t(h_w, dev) if h_w is not None else None
-            p = lambda t: t.data_ptr() if t is not None else None
-            call = lib.mpc_drive_batch_device_fused if fused else lib.mpc_drive_batch_device
-            rc = call(mpc._h, B, ld, steps, p(d["car"]), p(d_tx), p(d_ty), len(tx), p(d_w), C.byref(opts), None, p(d["summary"]), p(d["hist"]),
-                      p(d["status"]), p(d["iters"]), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-            assert rc == 0, lib.mpc_last_error()
-            torch.cuda.synchronize()
-            got = {k: (v.cpu().numpy() if v is not None else None) for k, v in d.items()}
-        info = mpc.drive_info()
-    assert np.isnan(got["car"][:, B:]).all() and (got["summary"][:, B:] == F).all() and (got["status"][B:] == I).all() and (got["iters"][B:] == I).all()
-    if hist:
-        assert (got["hist"][:, :, B:] == F).all()
-    out = {k: (v[..., :B].copy() if v is not None else None) for k, v in got.items()}
-    assert (out["summary"] != F).all() and (out["status"] != I).all() and (out["iters"] != I).all()
-    out["info"] = info
-    return out
+def _drive(pkg, params, waypoints, car, steps, dev, host=False, fused=False, **kw):
+    """mpc_drive_batch_device (fused: mpc_drive_batch_device_fused; host: mpc_drive_batch_host) through the raw ABI
+    (drive_helpers.device_drive: ragged ld, NaN and sentinels behind column B)"""
+    return D.device_drive(pkg, params, waypoints, car, steps, dev, form="host" if host else ("fused" if fused else "device"), entry="", **kw)
 
 
 def _same(a, b, what=""):

@@ -1,6 +1,6 @@
 """Track driving and the telemetry handler with a per-car horizon (the mpc_drive_*_horizon and mpc_telemetry_batch_*_horizon entry
 points of include/mpc_amd_drive.h), checked without a GPU: the declarations; the CPU build of the horizon loop
-(tests/drive_horizon_twin) -- with every horizon the handle's N against the latency twin, a mixed batch against the latency twin run with
+(tests/drive_twin) -- with every horizon the handle's N against the latency twin, a mixed batch against the latency twin run with
 MpcParams.N = horizon[i], every recorded solve of the mixed batch against the oracle with N = horizon[i], unusable horizons, the summary
 rows -- and a stand-alone program around it under ASan + UBSan."""
 import ctypes as C
@@ -27,12 +27,7 @@ B16, STEPS = 16, 8
 
 @pytest.fixture(scope="module")
 def twin():
-    return DH.load_drive_horizon_twin()
-
-
-@pytest.fixture(scope="module")
-def lat_twin():
-    return DL.load_drive_latency_twin()
+    return D.load_drive_twin()
 
 
 def _declared(header, name):
@@ -71,8 +66,8 @@ def _cars(pkg, params, waypoints):
 
 
 @pytest.mark.parametrize("warm", [0, 1])
-def test_all_horizons_N_is_the_latency_twin(pkg, twin, lat_twin, golden_dir, waypoints, warm):
-    """horizon = all N: bitwise tests/drive_latency_twin on the same 16 cars x 8 messages, with and without model and latency columns
+def test_all_horizons_N_is_the_latency_twin(pkg, twin, golden_dir, waypoints, warm):
+    """horizon = all N: bitwise tests/drive_twin on the same 16 cars x 8 messages, with and without model and latency columns
     (without: the handle's own values and the call's own scalars, which is what model == NULL is in the horizon twin)."""
     params = DH.fast_params(pkg, golden_dir)
     opts, wopts = pkg.drive_opts_default(params, warm_start=warm), pkg.warm_opts_default()
@@ -80,7 +75,7 @@ def test_all_horizons_N_is_the_latency_twin(pkg, twin, lat_twin, golden_dir, way
     hz = np.full(B16, params.N, dtype=np.int32)
     plain_lat = DH.default_latency(params, opts, B16)
     for model, lat in ((None, None), (draw_rows(params, B16, seed=9), DL.draw_latency(B16))):
-        ref = DL.twin_drive_latency(lat_twin, params, waypoints, car, model if model is not None else uniform_model(params, B16),
+        ref = DL.twin_drive_latency(twin, params, waypoints, car, model if model is not None else uniform_model(params, B16),
                                     lat if lat is not None else plain_lat, STEPS, opts, wopts)
         got = DH.twin_drive_horizon(twin, params, waypoints, car, hz, STEPS, opts, wopts, model=model, latency=lat)
         DH.same(got, ref)
@@ -103,14 +98,14 @@ def mixed(pkg, twin, golden_dir, waypoints):
 
 
 @pytest.mark.parametrize("warm", [0, 1])
-def test_a_mixed_batch_is_its_uniform_parts(pkg, lat_twin, waypoints, mixed, warm):
+def test_a_mixed_batch_is_its_uniform_parts(pkg, twin, waypoints, mixed, warm):
     """Car i is bitwise car i of the latency twin run with MpcParams.N = horizon[i]; and the horizon reaches the solve: the cars of the
     other groups differ."""
     params, opts, car, hz, res = mixed[warm]
     assert sorted(set(hz.tolist())) == list(LOOP_HORIZONS)
     for n in LOOP_HORIZONS:
         q = with_N(params, n)
-        ref = DL.twin_drive_latency(lat_twin, q, waypoints, car, uniform_model(q, B16), DH.default_latency(q, opts, B16), STEPS, opts,
+        ref = DL.twin_drive_latency(twin, q, waypoints, car, uniform_model(q, B16), DH.default_latency(q, opts, B16), STEPS, opts,
                                     pkg.warm_opts_default())
         DH.same(res, ref, cars=np.nonzero(hz == n)[0])
         others = np.nonzero(hz != n)[0]
@@ -166,7 +161,7 @@ def test_horizon_loop_under_asan_ubsan(pkg, golden_dir, waypoints):
             for row in [tx, ty] + list(car):
                 f.write(" ".join(repr(float(v)) for v in row) + "\n")
         subprocess.check_call(["g++", "-std=c++17"] + san + inc + [os.path.join(ROOT, "tests", "cpp", "drive_horizon_sanitize.cpp"),
-                                                                   os.path.join(ROOT, "tests", "drive_horizon_twin", "drive_horizon_twin.cpp"),
+                                                                   os.path.join(ROOT, "tests", "drive_twin", "drive_twin.cpp"),
                                                                    os.path.join(ROOT, "carnd-mpc-project_amd", "csrc", "mpc_params.cpp"), "-lm", "-o", exe])
         env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
         p = subprocess.run([exe, os.path.join(golden_dir, "config-fast.json"), data], capture_output=True, text=True, env=env, timeout=300)

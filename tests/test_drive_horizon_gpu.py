@@ -2,7 +2,7 @@
 _host_horizon, mpc_telemetry_batch_device_horizon / _host_horizon; include/mpc_amd_drive.h): horizon = NULL against the _latency forms;
 a mixed batch against its uniform parts run through the existing _latency form on handles created with N = horizon[i]; the one launch
 against the stepwise form bit for bit at every B; every step against the handler's own entry point; the stepwise form against the CPU
-build (tests/drive_horizon_twin) solve by solve; horizons and cars no caller should send; the host forms, the Python layer, the refusals
+build (tests/drive_twin) solve by solve; horizons and cars no caller should send; the host forms, the Python layer, the refusals
 that need a live handle, and an N = 25 handle whose ordinary solve starts in fp32."""
 import ctypes as C
 import itertools
@@ -13,7 +13,7 @@ import pytest
 import drive_helpers as D
 import drive_horizon_helpers as DH
 import drive_latency_helpers as DL
-from drive_model_helpers import fast_params as _params, to_device as _t
+from drive_helpers import fast_params as _params, to_device as _t
 from helpers import TOL_STEER
 from horizon_helpers import LOOP_HORIZONS
 from model_helpers import draw_rows
@@ -35,7 +35,7 @@ def torch_dev():
 
 @pytest.fixture(scope="module")
 def twin():
-    return DH.load_drive_horizon_twin()
+    return D.load_drive_twin()
 
 
 @pytest.fixture(scope="module")
@@ -181,7 +181,6 @@ def test_stepwise_against_the_cpu_build(pkg, twin, waypoints, loop96, warm):
     assert dev["info"] == STEPWISE
     mem = {"warm": None, "status": None}
     d_steer = d_thr = 0.0
-    lt = DL.load_drive_latency_twin()
     from run_model_helpers import uniform_model
     for t in range(6):
         h = dev["hist"][t]
@@ -195,7 +194,7 @@ def test_stepwise_against_the_cpu_build(pkg, twin, waypoints, loop96, warm):
         d_thr = max(d_thr, np.abs(r["cmd"][1] - h[D.REC_CMD + 1])[ok].max())
         assert np.abs(r["cte_epsi"] - h[D.REC_CTE:D.REC_EPSI + 1])[:, ok].max() <= 1e-9
         nxt = dev["hist"][t + 1, :6] if t < 5 else dev["car"]
-        ref = DL.twin_plant_latency(lt, params, h[:6], h[D.REC_CMD:D.REC_CMD + 2], uniform_model(params, 96), lat, opts)
+        ref = DL.twin_plant_latency(twin, params, h[:6], h[D.REC_CMD:D.REC_CMD + 2], uniform_model(params, 96), lat, opts)
         assert (np.abs(nxt - ref) <= 4 * (lat[DL.SUB_OLD] + lat[DL.SUB_NEW])[None, :] * np.spacing(np.maximum(1.0, np.abs(ref)))).all(), t
         assert np.array_equal(nxt[4], h[D.REC_CMD] * params.max_steering) and np.array_equal(nxt[5], h[D.REC_CMD + 1])
     print("device vs CPU build, warm %d: max |d steer| %.3g rad, |d throttle| %.3g; statuses %s" % (
@@ -211,7 +210,7 @@ def test_containment(fused):
     finite rows, for the four horizons --, and every other car is bitwise what it is in a batch without them.  Both forms.  The drives
     run in a child process under a time limit of its own (the clean and the dirty batch, cold and warm: four launches or loops, nothing
     looped) whose exit status the parent checks."""
-    res = DH.run_containment_in_child(fused)
+    res = D.run_in_child("drive_horizon_helpers.child_runs", fused)
     cols, bad = DH.BAD_HORIZONS, DH.BAD_HORIZONS + DH.BAD_CARS
     for warm in (0, 1):
         a, b = res[warm, "clean"], res[warm, "dirty"]

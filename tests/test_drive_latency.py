@@ -1,5 +1,5 @@
 """Track driving and the telemetry handler with per-car latency (the mpc_drive_*_latency and mpc_telemetry_batch_*_latency entry points
-of include/mpc_amd_drive.h), checked without a GPU: the declarations; the CPU build of the latency loop (tests/drive_latency_twin) --
+of include/mpc_amd_drive.h), checked without a GPU: the declarations; the CPU build of the latency loop (tests/drive_twin) --
 its plant against the composition of the oracle's Vehicle::move with every car's own substep counts and against the build without a
 latency array, its loop against the oracle's telemetry handler with a per-car Config (latency, lookahead) on every recorded step,
 unusable columns -- and a stand-alone program around it under ASan + UBSan."""
@@ -24,7 +24,7 @@ TELEMETRY_FORMS = ("mpc_telemetry_batch_device", "mpc_telemetry_batch_host")
 
 @pytest.fixture(scope="module")
 def twin():
-    return DL.load_drive_latency_twin()
+    return D.load_drive_twin()
 
 
 def _declared(header, name):
@@ -91,7 +91,7 @@ def _plant_cars(B):
 def test_plant_with_per_car_counts(pkg, twin, golden_dir):
     """256 cars with the columns of draw_latency against the composition of O.vehicle_move with each car's own counts.  The bound is
     that of tests/test_drive.py::test_plant with the car's own substep total: 4 x (sub_old_i + sub_new_i) x 1 ulp of max(1, |value|).
-    With uniform columns the plant is bitwise the drive_model_twin plant."""
+    With uniform columns the plant is bitwise the model plant of tests/drive_twin."""
     B = 256
     params = pkg.params_from_json(os.path.join(golden_dir, "config-fast.json"))
     opts = pkg.drive_opts_default(params)
@@ -105,12 +105,12 @@ def test_plant_with_per_car_counts(pkg, twin, golden_dir):
     print("plant with per-car counts: max error / bound per row %s" % (err / bound).max(1))
     assert (err <= bound).all()
     # the counts reach the plant: another car than under the call's own
-    plain = DM.twin_plant_model(DM.load_drive_model_twin(), params, car, cmd, model, opts.sub_old, opts.sub_new, opts.h)
+    plain = DM.twin_plant_model(D.load_drive_twin(), params, car, cmd, model, opts.sub_old, opts.sub_new, opts.h)
     differ = (lat[DL.SUB_OLD] != opts.sub_old) | (lat[DL.SUB_NEW] != opts.sub_new)
     assert differ.sum() > B // 2 and (got[0, differ] != plain[0, differ]).all() and np.array_equal(got[:, ~differ], plain[:, ~differ])
     for so, sn in ((10, 2), (0, 10), (3, 0)):
         assert np.array_equal(DL.twin_plant_latency(twin, params, car, cmd, model, DL.uniform_latency(B, 0.1, so, sn), opts),
-                              DM.twin_plant_model(DM.load_drive_model_twin(), params, car, cmd, model, so, sn, opts.h)), (so, sn)
+                              DM.twin_plant_model(D.load_drive_twin(), params, car, cmd, model, so, sn, opts.h)), (so, sn)
 
 
 @pytest.fixture(scope="module")
@@ -156,7 +156,7 @@ def test_uniform_columns_are_the_scalars(pkg, twin, golden_dir, waypoints, cfgna
     model = uniform_model(params, 16)
     lat = DL.uniform_latency(16, DL.handle_comp(params, 0.013), opts.sub_old, opts.sub_new)
     a = DL.twin_drive_latency(twin, params, waypoints, car, model, lat, 4, opts, pkg.warm_opts_default())
-    b = DM.twin_drive_model(DM.load_drive_model_twin(), params, waypoints, car, model, 4, opts, pkg.warm_opts_default())
+    b = DM.twin_drive_model(D.load_drive_twin(), params, waypoints, car, model, 4, opts, pkg.warm_opts_default())
     DL.same(a, b)
 
 
@@ -194,7 +194,7 @@ def test_latency_loop_on_garbage_under_asan_ubsan(golden_dir):
     with tempfile.TemporaryDirectory() as d:
         exe = os.path.join(d, "drive_latency_sanitize")
         subprocess.check_call(["g++", "-std=c++17"] + san + inc + [os.path.join(ROOT, "tests", "cpp", "drive_latency_sanitize.cpp"),
-                                                                   os.path.join(ROOT, "tests", "drive_latency_twin", "drive_latency_twin.cpp"),
+                                                                   os.path.join(ROOT, "tests", "drive_twin", "drive_twin.cpp"),
                                                                    os.path.join(ROOT, "carnd-mpc-project_amd", "csrc", "mpc_params.cpp"), "-lm", "-o", exe])
         env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
         p = subprocess.run([exe, os.path.join(golden_dir, "config-fast.json")], capture_output=True, text=True, env=env, timeout=300)

@@ -2,7 +2,7 @@
 _host_latency, mpc_telemetry_batch_device_latency / _host_latency; include/mpc_amd_drive.h): latency = NULL against the _model forms;
 uniform columns against the call's scalars; a mixed batch against its uniform parts run through the existing _model form; the one
 launch against the stepwise form bit for bit, across the wave limit and with ragged leading dimensions; every step against the
-handler's own entry point; the stepwise form against the CPU build (tests/drive_latency_twin) solve by solve; columns and cars no
+handler's own entry point; the stepwise form against the CPU build (tests/drive_twin) solve by solve; columns and cars no
 caller should send; the host form, the Python layer and the refusals that need a live handle."""
 import ctypes as C
 import itertools
@@ -12,7 +12,7 @@ import pytest
 
 import drive_helpers as D
 import drive_latency_helpers as DL
-from drive_model_helpers import fast_params as _params, to_device as _t
+from drive_helpers import fast_params as _params, to_device as _t
 from helpers import TOL_STEER
 from model_helpers import draw_rows
 from run_model_helpers import uniform_model
@@ -33,7 +33,7 @@ def torch_dev():
 
 @pytest.fixture(scope="module")
 def twin():
-    return DL.load_drive_latency_twin()
+    return D.load_drive_twin()
 
 
 @pytest.fixture(scope="module")
@@ -204,7 +204,7 @@ def test_containment(pkg, golden_dir, waypoints, wave_max_batch, fused):
     status -- at every step, with finite rows, for the four columns --, and every other car is bitwise what it is in a batch without
     them.  Both forms.  The drives run in a child process under a time limit of its own (the clean and the dirty batch, cold and
     warm: four launches or loops, nothing looped), so that "a launch that ends" is something this test can say."""
-    res = DL.run_containment_in_child(wave_max_batch, fused)
+    res = D.run_in_child("drive_latency_helpers.child_runs", fused, wave_max_batch)
     cols, bad = DL.BAD_COLUMNS, DL.BAD_COLUMNS + DL.BAD_CARS
     for warm in (0, 1):
         a, b = res[warm, "clean"], res[warm, "dirty"]

@@ -1,5 +1,5 @@
 """Track driving with per-car model values (the mpc_drive_*_model entry points of include/mpc_amd_drive.h), checked without a GPU:
-the declarations; the CPU build of the model loop (tests/drive_model_twin) -- its plant against the composition of the oracle's
+the declarations; the CPU build of the model loop (tests/drive_twin) -- its plant against the composition of the oracle's
 Vehicle::move with every car's own Lf and max_steering and against the model-free build, its loop against the oracle's telemetry
 handler with a per-car Config on every recorded step, unusable columns -- and a stand-alone program around it under ASan + UBSan."""
 import ctypes as C
@@ -22,7 +22,7 @@ MODEL_FORMS = ("mpc_drive_batch_device_model", "mpc_drive_batch_device_fused_mod
 
 @pytest.fixture(scope="module")
 def twin():
-    return DM.load_drive_model_twin()
+    return D.load_drive_twin()
 
 
 def test_declarations(pkg, golden_dir):
@@ -162,7 +162,7 @@ def test_model_loop_on_garbage_under_asan_ubsan(golden_dir):
     with tempfile.TemporaryDirectory() as d:
         exe = os.path.join(d, "drive_model_sanitize")
         subprocess.check_call(["g++", "-std=c++17"] + san + inc + [os.path.join(ROOT, "tests", "cpp", "drive_model_sanitize.cpp"),
-                                                                   os.path.join(ROOT, "tests", "drive_model_twin", "drive_model_twin.cpp"),
+                                                                   os.path.join(ROOT, "tests", "drive_twin", "drive_twin.cpp"),
                                                                    os.path.join(ROOT, "carnd-mpc-project_amd", "csrc", "mpc_params.cpp"), "-lm", "-o", exe])
         env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
         p = subprocess.run([exe, os.path.join(golden_dir, "config-fast.json")], capture_output=True, text=True, env=env, timeout=300)

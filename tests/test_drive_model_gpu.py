@@ -1,5 +1,5 @@
 """Track driving with per-car model values on the device (mpc_drive_batch_device_model / _fused_model / _host_model,
-include/mpc_amd_drive.h): the stepwise form against the CPU build of the same functions (tests/drive_model_twin) solve by solve and
+include/mpc_amd_drive.h): the stepwise form against the CPU build of the same functions (tests/drive_twin) solve by solve and
 against the telemetry _model entry points bit for bit; model = NULL against the forms without _model; the one launch (the DRIVE x
 MODEL builds of the lane kernel) against the stepwise form bit for bit, across the wave limit and with ragged leading dimensions;
 columns and cars no caller should send; the host form, the Python layer and the refusals that need a live handle."""
@@ -30,7 +30,7 @@ def torch_dev():
 
 @pytest.fixture(scope="module")
 def twin():
-    return DM.load_drive_model_twin()
+    return D.load_drive_twin()
 
 
 def _same(a, b, what=""):
@@ -198,7 +198,7 @@ def test_containment(pkg, golden_dir, waypoints, wave_max_batch, fused):
     INFEASIBLE at every step with finite rows for the first three --, and every other car is bitwise what it is in a batch without
     them.  Both forms.  The drives run in a child process under a time limit of its own (the clean and the dirty batch, cold and
     warm: four launches or loops), so that "a launch that ends" is something this test can say."""
-    res = DM.run_containment_in_child(wave_max_batch, fused)
+    res = D.run_in_child("drive_model_helpers.child_runs", fused, wave_max_batch)
     _, _, _, _, infeasible, bad = DM.containment_case(pkg, _params(pkg, golden_dir, wave_max_batch=wave_max_batch), waypoints)
     for warm in (0, 1):
         a, b = res[warm, "clean"], res[warm, "dirty"]

@@ -1,5 +1,5 @@
 """Track driving with per-car plant values (the mpc_drive_*_plant entry points of include/mpc_amd_drive.h), checked without a GPU: the
-declarations and the host-only ABI; the CPU build of the plant loop (tests/drive_plant_twin) -- its plant against the substep of the
+declarations and the host-only ABI; the CPU build of the plant loop (tests/drive_twin) -- its plant against the substep of the
 header written once more in long double, the default column against the build without a plant array, the loop against its own
 records, a side drift on the lake track, unusable columns -- and a stand-alone program around it under ASan + UBSan."""
 import ctypes as C
@@ -22,7 +22,7 @@ DRIVE_FORMS = ("mpc_drive_batch_device", "mpc_drive_batch_device_fused", "mpc_dr
 
 @pytest.fixture(scope="module")
 def twin():
-    return DP.load_drive_plant_twin()
+    return D.load_drive_twin()
 
 
 def _declared(header, name):
@@ -122,6 +122,30 @@ def test_plant_against_the_long_double_substep(pkg, twin, golden_dir, sub_old, s
     assert (got[:4] != none[:4]).mean() > 0.9
 
 
+def test_a_standing_car_on_a_zero_coordinate(pkg, twin, golden_dir):
+    """The sign of a coordinate that is exactly zero.  Every form moves the car with x = x - (w * h) * sin(psi), y = y + (w * h) * cos(psi)
+    behind the expressions from before the plant columns, w = 0 without a plant array, so a car that stands (speed, steering, throttle 0)
+    on -0.0 may be put on +0.0 where those expressions alone left it.  Pinned here: no plant array and the default column give the same
+    bytes, and the signs are those of the header's statements in IEEE arithmetic (a fused multiply-add of an exact zero product has
+    them too)."""
+    params = pkg.params_from_json(os.path.join(golden_dir, "config-fast.json"), N=10)
+    psi = np.array([0.3, -0.3, 2.0, -2.0, 0.0, np.pi] * 4)
+    B = len(psi)
+    car = np.zeros((6, B)); car[2] = psi
+    car[0] = np.repeat([0.0, -0.0, 0.0, -0.0], 6); car[1] = np.repeat([0.0, 0.0, -0.0, -0.0], 6)
+    cmd, h = np.zeros((2, B)), 0.01
+    none = D.twin_plant(twin, params, car, cmd, 1, 1, h)
+    col, ok = DP.twin_plant(twin, params, car, cmd, uniform_model(params, B), pkg.drive_plant_default(params, B), 1, 1, h)
+    assert ok.all() and none.tobytes() == col.tobytes()
+    x, y = car[0].copy(), car[1].copy()
+    for _ in range(2):
+        x = (x + (0.0 * h) * np.cos(psi)) - (0.0 * h) * np.sin(psi)
+        y = (y + (0.0 * h) * np.sin(psi)) + (0.0 * h) * np.cos(psi)
+    assert (none[:2] == 0.0).all() and np.array_equal(np.signbit(none[0]), np.signbit(x)) and np.array_equal(np.signbit(none[1]), np.signbit(y))
+    assert np.signbit(car[:2]).sum() > np.signbit(none[:2]).sum() > 0          # some -0.0 became +0.0, some stayed
+    assert np.array_equal(none[2:], car[2:])
+
+
 @pytest.fixture(scope="module")
 def setup16(pkg, golden_dir, waypoints):
     params = pkg.params_from_json(os.path.join(golden_dir, "config-fast.json"), N=10)
@@ -131,12 +155,12 @@ def setup16(pkg, golden_dir, waypoints):
 @pytest.mark.parametrize("warm", [0, 1])
 def test_default_column_is_the_latency_twin(pkg, twin, setup16, waypoints, warm):
     """the default column (its Lf row: the car's own Lf, here a model array with different Lf values): bitwise the
-    tests/drive_latency_twin loop on 16 cars x 8 steps"""
+    tests/drive_twin loop on 16 cars x 8 steps"""
     params, car, model, lat = setup16
     model = model.copy(); model[1] = np.linspace(2.2, 3.2, 16)
     opts, wopts = pkg.drive_opts_default(params, warm_start=warm), pkg.warm_opts_default()
     a = DP.twin_drive_plant(twin, params, waypoints, car, model, lat, pkg.drive_plant_default(params, 16, model), 8, opts, wopts)
-    b = DL.twin_drive_latency(DL.load_drive_latency_twin(), params, waypoints, car, model, lat, 8, opts, wopts)
+    b = DL.twin_drive_latency(D.load_drive_twin(), params, waypoints, car, model, lat, 8, opts, wopts)
     DP.same(a, b)
     assert np.array_equal(a["handler_status"], a["hist"][:, D.REC_STATUS].astype(np.int32))
 
@@ -178,7 +202,7 @@ def test_side_drift_on_the_lake_track(pkg, twin, golden_dir, waypoints):
     mean = {w: r["hist"][20:, D.REC_CTE].mean() for w, r in res.items()}
     print("mean cte0 over the last 20 messages: w = +1 %.4f, w = 0 %.4f, w = -1 %.4f" % (mean[1.0], mean[0.0], mean[-1.0]))
     assert mean[1.0] != 0.0 and mean[-1.0] != 0.0 and np.sign(mean[1.0]) == -np.sign(mean[-1.0])
-    DP.same(res[0.0], DL.twin_drive_latency(DL.load_drive_latency_twin(), params, waypoints, car, model, lat, 40, opts, wopts))
+    DP.same(res[0.0], DL.twin_drive_latency(D.load_drive_twin(), params, waypoints, car, model, lat, 40, opts, wopts))
 
 
 @pytest.mark.parametrize("warm", [0, 1])
@@ -226,7 +250,7 @@ def test_plant_loop_on_garbage_under_asan_ubsan(golden_dir):
     with tempfile.TemporaryDirectory() as d:
         exe = os.path.join(d, "drive_plant_sanitize")
         subprocess.check_call(["g++", "-std=c++17"] + san + inc + [os.path.join(ROOT, "tests", "cpp", "drive_plant_sanitize.cpp"),
-                                                                   os.path.join(ROOT, "tests", "drive_plant_twin", "drive_plant_twin.cpp"),
+                                                                   os.path.join(ROOT, "tests", "drive_twin", "drive_twin.cpp"),
                                                                    os.path.join(ROOT, "carnd-mpc-project_amd", "csrc", "mpc_params.cpp"), "-lm", "-o", exe])
         env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
         p = subprocess.run([exe, os.path.join(golden_dir, "config-fast.json")], capture_output=True, text=True, env=env, timeout=300)

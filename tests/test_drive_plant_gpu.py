@@ -1,7 +1,7 @@
 """Track driving with per-car plant values on the device (mpc_drive_batch_device_plant / _fused_plant / _host_plant;
 include/mpc_amd_drive.h): plant = NULL against the _horizon forms; the default column against plant = NULL; a mixed batch against its
 uniform parts; the one launch against the stepwise form bit for bit, across the wave limit and with ragged leading dimensions; the lane
-kernels against the wave kernels; the stepwise form against the CPU build (tests/drive_plant_twin) step by step; unusable columns; the
+kernels against the wave kernels; the stepwise form against the CPU build (tests/drive_twin) step by step; unusable columns; the
 host form, the Python layer and the refusals that need a live handle."""
 import ctypes as C
 import itertools
@@ -13,7 +13,7 @@ import drive_helpers as D
 import drive_latency_helpers as DL
 import drive_plant_helpers as DP
 from drive_horizon_helpers import mixed_horizons
-from drive_model_helpers import fast_params as _params, to_device as _t
+from drive_helpers import fast_params as _params, to_device as _t
 from helpers import TOL_STEER
 from model_helpers import draw_rows
 from run_model_helpers import uniform_model
@@ -34,7 +34,7 @@ def torch_dev():
 
 @pytest.fixture(scope="module")
 def twin():
-    return DP.load_drive_plant_twin()
+    return D.load_drive_twin()
 
 
 @pytest.fixture(scope="module")
@@ -150,13 +150,12 @@ def test_stepwise_against_the_cpu_build(pkg, twin, golden_dir, waypoints, torch_
     model = uniform_model(params, B)
     tw = DP.twin_drive_plant(twin, params, waypoints, car, model, lat, plant, steps, opts, wopts)
     assert np.array_equal(dev["hist"][:, D.REC_K], tw["hist"][:, D.REC_K]) and np.array_equal(dev["hist"][:, D.REC_STATUS], tw["hist"][:, D.REC_STATUS])
-    lt = DL.load_drive_latency_twin()
     mem = {"warm": None, "status": None}
     d_steer = d_thr = 0.0
     for t in range(steps):
         h = dev["hist"][t]
         assert np.array_equal(D.twin_window(D.load_drive_twin(), waypoints, h[0], h[1]), h[D.REC_K].astype(np.int32))
-        r = DL.twin_handler_latency(lt, params, waypoints, h[:6], lat[DL.COMP], h[D.REC_K], model, opts, wopts, warm=mem["warm"] if warm else None,
+        r = DL.twin_handler_latency(twin, params, waypoints, h[:6], lat[DL.COMP], h[D.REC_K], model, opts, wopts, warm=mem["warm"] if warm else None,
                                     warm_status=mem["status"] if warm else None, want_warm=bool(warm))
         mem["warm"], mem["status"] = r["warm"], r["status"]
         assert np.array_equal(r["status"], h[D.REC_STATUS].astype(np.int32)), t
@@ -184,7 +183,7 @@ def test_unusable_columns(pkg, golden_dir, waypoints, torch_dev, wave_max_batch,
     and the folded status; nothing is not-a-number; the iterations are those of the car under the default column, and so -- warm -- is
     every later step: the next step is still warm-started.  Every other car is bitwise the batch without the defect.  The drives run
     in a child process under a time limit of its own."""
-    res = DP.run_unusable_in_child(wave_max_batch, fused)
+    res = D.run_in_child("drive_plant_helpers.child_runs", fused, wave_max_batch)
     params = _params(pkg, golden_dir, wave_max_batch=wave_max_batch)
     car, plant, dirty, bad = DP.unusable_case(pkg, params, waypoints)
     ref_plant = plant.copy(); ref_plant[:, bad] = pkg.drive_plant_default(params)[:, None]
