@@ -250,6 +250,14 @@ def library():
     for name in ("mpc_drive_batch_host", "mpc_drive_batch_device", "mpc_drive_batch_device_fused"):
         at = len(drive_head) + 3      # (model, horizon, latency)
         getattr(L, name + "_plant").argtypes = getattr(L, name + "_horizon").argtypes[:at] + [DP] + getattr(L, name + "_horizon").argtypes[at:]
+    # ... and the _budget forms (include/mpc_amd_budget.h): `budget` (one pointer) directly behind `horizon` -- of the drive's _plant forms
+    # and of the solve's _warm_horizon forms
+    for name in ("mpc_drive_batch_host", "mpc_drive_batch_device", "mpc_drive_batch_device_fused"):
+        at = len(drive_head) + 2      # (model, horizon)
+        getattr(L, name + "_budget").argtypes = getattr(L, name + "_plant").argtypes[:at] + [DP] + getattr(L, name + "_plant").argtypes[at:]
+    for name in ("mpc_solve_batch_device", "mpc_solve_batch_host"):
+        at = len(H) + 5 + 2           # (state .. weights, model, horizon)
+        getattr(L, name + "_budget").argtypes = getattr(L, name + "_warm_horizon").argtypes[:at] + [DP] + getattr(L, name + "_warm_horizon").argtypes[at:]
     L.mpc_drive_plant_default.argtypes = [C.POINTER(MpcParams), DP]
     L.mpc_drive_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.mpc_solve_batch_device_f32.argtypes = L.mpc_solve_batch_device.argtypes      # (the same pointers, to floats)

@@ -209,6 +209,7 @@ struct TiledWorkspace {
   typedef typename AddrSpace<R>::g greal;
   typedef typename AddrSpace<R>::l lreal;
   static constexpr bool kSocDefault = false;
+  static constexpr bool kBudget = LANE_ROWS;      /* the per-lane-rows builds carry the iteration budget (Solver, "iteration budget") */
   greal *tile;   /* this wave's tile */
   lreal *lbuf;   /* LDS staging area of this wave (STAGING) */
   int lane;
@@ -719,12 +720,15 @@ struct GetterColumn {
 };
 template <class Col, class = void> struct is_column : std::false_type {};
 template <class Col> struct is_column<Col, decltype((void)&Col::stages)> : std::true_type {};
+/* "no budget": what a call without `budget` hands every instance (see Solver, "iteration budget") */
+enum { kNoBudget = 0x7fffffff };
 /* What an instance of the mpc_*_horizon entry points brings along: its horizon n (Config::N of the reference, 3 .. the handle's N)
  * and its column of `model` -- col = nullptr: the handle's own six values, taken as they are (no column is judged). */
 struct HorizonColumn {
   const double *col;              /* the instance's column of model [MPC_NMODEL][ld], or nullptr */
   int64_t ld;
   int n;
+  int budget = kNoBudget;         /* the instance's iteration budget (the mpc_*_budget entry points; Solver, "iteration budget") */
   MPC_HD ModelVals vals(const MpcParams &P, bool &ok) const {
     if (!col) { ok = true; return ModelVals::of(P); }
     return ModelColumn{col, ld}.vals(P, ok);
@@ -771,9 +775,20 @@ template <class R> struct SocState<true, R> {
   R soc_a0, soc_as, soc_th_old, soc_dphi, soc_dxinf, soc_az;
 };
 
+/* iteration budget (Solver, "iteration budget"): the instance's budget and the cap of its current attempt.  Only the solvers on a
+ * workspace that says kBudget carry them -- the per-lane-rows builds of the lane kernel (TiledWorkspace<false, R, true>) and the
+ * test-only CPU builds of the mpc_*_budget calls; an empty base everywhere else: those solver objects are what they were. */
+template <bool ON> struct BudgetState {};
+template <> struct BudgetState<true> {
+  int budget = kNoBudget, iter_cap = 0;
+};
+template <class WS, class = void> struct ws_has_budget : std::false_type {};
+template <class WS> struct ws_has_budget<WS, std::enable_if_t<WS::kBudget>> : std::true_type {};
+
 template <class WS, class R, int WAVE = 0, bool SOC = WS::kSocDefault>
-struct Solver : SocState<SOC && sizeof(R) == 8, R> {
+struct Solver : SocState<SOC && sizeof(R) == 8, R>, BudgetState<ws_has_budget<WS>::value && sizeof(R) == 8> {
   using F = Fields<R>;
+  static constexpr bool kBudget = ws_has_budget<WS>::value && sizeof(R) == 8;
   /* The second-order correction (MpcParams.max_soc, W&B A-5.5..A-5.10) is compiled into the SOC builds only: the fp64 solver of
    * the kernels a max_soc > 0 solve launches (and of the test-only host build).  The fp32 solver never has it. */
   static constexpr bool kSoc = SOC && sizeof(R) == 8;
@@ -2146,6 +2161,10 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
     const auto &m = col.vals(P, ok);
     const int stages = col.stages(P, ok);
     const int s = setup_vals(m, state6, coef5, yaw_lo, yaw_hi, w12, write_start, stages);
+    if constexpr (kBudget) {
+      if constexpr (std::is_same<Col, HorizonColumn>::value) ok = budget_begin(col.budget) && ok;
+      else (void)budget_begin(kNoBudget);
+    }
     return ok ? s : MPC_STATUS_INFEASIBLE;
   }
   /* (a caller that never has a column -- host code around one Solver -- may leave NoColumn out; unpack likewise) */
@@ -2244,6 +2263,44 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
   int reg_tries;
   R theta_k, phi_k, pth, pdp, amin;   /* line-search state */
 
+  /* ------------------------------------------------------------------ */
+  /* iteration budget (the mpc_*_budget entry points, include/mpc_amd_budget.h) */
+  /* ------------------------------------------------------------------ */
+  /* The reference's solve deadline (max_cpu_time = Config::ipoptTimeout, MPC.cpp:176-178), counted in interior-point iterations: an
+   * instance with budget b may take b iterations in one call over ALL of its attempts -- the warm attempt, the cold solve, the one
+   * restart -- counted as `iters` reports them (iter + it_total).  These functions, the two reads of cap() in step() and
+   * warm_status_ok() below the class are the only place that knows the rules; the lane kernel's per-lane-rows builds and the
+   * test-only CPU builds (kBudget) call them, every other build compiles none of it and cap() is P.max_iter itself.
+   *   - cap(): what step() stops an attempt at, behind the convergence and the acceptable-level tests, and what the polish clause
+   *     reads: min(P.max_iter, what is left of the budget), at least 1.  The handle's max_iter still bounds each attempt.
+   *   - an attempt that ends MPC_STATUS_MAXITER with the count at the budget is final, whichever attempt it is (budget_spent):
+   *     no cold solve and no restart follow; the iterate is handed over as a max_iter stop hands it over, iters == b.
+   *   - an attempt that ends otherwise is followed by what follows it without a budget, with what is left (attempt_cap).
+   *   - b < 1 follows the rule of an unusable horizon: set-up answers MPC_STATUS_INFEASIBLE, the start point is reported.
+   *   - kNoBudget (a call without `budget`): cap() == P.max_iter in every attempt and budget_spent() never holds -- the
+   *     arithmetic of a solver without any of this. */
+  MPC_HD int cap() const {
+    if constexpr (kBudget) return this->iter_cap;
+    else return P.max_iter;
+  }
+  MPC_HD bool budget_begin(int b) {
+    if constexpr (kBudget) { this->budget = b; attempt_cap(0); return b >= 1; }
+    else return true;
+  }
+  /* the cap of the attempt that starts with it_total iterations on the count */
+  MPC_HD void attempt_cap(int it_total) {
+    if constexpr (kBudget) {
+      const int left = this->budget - it_total;
+      const int l1 = left < 1 ? 1 : left;
+      this->iter_cap = l1 < P.max_iter ? l1 : P.max_iter;
+    }
+  }
+  /* r ended an attempt that began with it_total on the count: did the budget end it? */
+  MPC_HD bool budget_spent(int r, int it_total) const {
+    if constexpr (kBudget) return r == MPC_STATUS_MAXITER && it_total + iters >= this->budget;
+    else return false;
+  }
+
   /* Solve from the start point that setup()/start_point() has written.
    * A line search that runs out of step length is where IPOPT would enter its feasibility-restoration phase.
    * Stand-in (same as the oracle's): restart ONCE from the start point with zero equality multipliers. */
@@ -2257,6 +2314,7 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
         attempt = 1; it_total += iters;
         start_point();
         begin(false);
+        attempt_cap(it_total);
         continue;
       }
       iters += it_total;
@@ -2272,16 +2330,19 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
    * out: with the call in their loops the wave kernels, which sit at 512 registers, come out of the register allocator with 8 more
    * bytes of scratch in six builds (136 -> 144, 176 -> 184, 72 -> 80), whichever way the call is written. */
   MPC_HD bool next_attempt(int r, int &attempt, int &it_total) {
+    if (budget_spent(r, it_total)) return false;      /* (iteration budget: an end by budget is final in every attempt) */
     if (attempt < 0 && r != MPC_STATUS_SUCCESS) {
       attempt = 0; it_total += iters;
       start_point();
       begin(true);
+      attempt_cap(it_total);
       return true;
     }
     if (r == MPC_STATUS_LINESEARCH && attempt == 0 && !no_restart) {
       attempt = 1; it_total += iters;
       start_point();
       begin(false);
+      attempt_cap(it_total);
       return true;
     }
     return false;
@@ -2366,16 +2427,18 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
     for (;;) {
       const int r = step();
       if (r == MPC_RUNNING) continue;
-      if (attempt < 0 && r != MPC_STATUS_SUCCESS) {      /* (next_attempt, written out: see there) */
+      if (attempt < 0 && r != MPC_STATUS_SUCCESS && !budget_spent(r, it_total)) {      /* (next_attempt, written out: see there) */
         attempt = 0; it_total += iters;
         start_point();
         begin(true);
+        attempt_cap(it_total);
         continue;
       }
       if (r == MPC_STATUS_LINESEARCH && attempt == 0 && !no_restart) {
         attempt = 1; it_total += iters;
         start_point();
         begin(false);
+        attempt_cap(it_total);
         continue;
       }
       iters += it_total;
@@ -2418,6 +2481,7 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
       ws.it(M, Ic, F_ZL + 0) = a(43); ws.it(M, Ic, F_ZU + 0) = a(44); ws.it(M, Ic, F_ZL + 1) = a(45); ws.it(M, Ic, F_ZU + 1) = a(46);
     }
     iters = iter; phase = PH_DIR;
+    attempt_cap(it_total);      /* (iteration budget: set-up has read the budget again, the attempt's cap follows the count) */
   }
 
   /* after unpark() of an instance that another precision parked with MPC_PROMOTE: evaluate the point as this solver sees it
@@ -2494,7 +2558,7 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
            * Newton steps at the final barrier parameter until the outputs (delta_0, a_0) have stopped moving, so
            * that the point returned is the central-path point itself and not whichever iterate crossed tol first
            * (an interior a_0 still moves by ~R(1e-4) per step there).  At most kMaxPolish extra iterations. */
-          if (!P.polish || n_polish >= kMaxPolish || iter >= P.max_iter || (mu <= mu_floor && out_step <= out_tol))
+          if (!P.polish || n_polish >= kMaxPolish || iter >= cap() || (mu <= mu_floor && out_step <= out_tol))
             return MPC_STATUS_SUCCESS;
           ++n_polish;
           if (mu > mu_floor) { mu = mu_floor; tau = mpc_max(IC::tau_min, R(1.0) - mu); nf = 0; }
@@ -2503,7 +2567,7 @@ struct Solver : SocState<SOC && sizeof(R) == 8, R> {
            * STOP_AT_ACCEPTABLE_POINT (tested before the iteration cap, as IPOPT does) */
           if (++acc_count >= P.acceptable_iter) return MPC_STATUS_ACCEPTABLE;
         } else acc_count = 0;
-        if (iter >= P.max_iter) return MPC_STATUS_MAXITER;
+        if (iter >= cap()) return MPC_STATUS_MAXITER;
         /* barrier update, W&B eq. (7) */
         while (kkt_error(E, mu) <= IC::kappa_eps * mu && mu > mu_floor) {
           mu = mpc_max(mu_floor, mpc_min(IC::kappa_mu * mu, mu * mpc_sqrt(mu)));
@@ -2739,6 +2803,11 @@ struct WarmColumn {
  * next solve starts from, what the call reports per car, and which steps may start warm.  The fused rollout (the ROLL builds of the
  * lane kernel) and the test-only CPU build tests/host_twin go through this and nothing else; mpc_rollout_step_kernel states the
  * same rule for the stepwise loop, a launch per step. */
+/* Which records of a warm buffer are candidates, by the status they came with: the iterate of a solve that succeeded -- and, in a
+ * call with a budget (`budgeted`: budget != NULL), the iterate a solve stopped at MPC_STATUS_MAXITER: an interior iterate of the same
+ * NLP, the real-time-iteration scheme.  The box test of warm_point() and every other warm rule apply to both. */
+MPC_HD bool warm_status_ok(int32_t s, bool budgeted) { return s == MPC_STATUS_SUCCESS || (budgeted && s == MPC_STATUS_MAXITER); }
+
 struct RolloutCar {
   /* the next state: rows 0..5 of solve()'s 9-vector {x1, y1, psi1, v1, cte1, epsi1}, as they were written (out9(q) reads, state(q, v) writes) */
   template <class Get, class Put> MPC_HD static void next_state(Get out9, Put state) {
@@ -2750,7 +2819,7 @@ struct RolloutCar {
   /* the car's iterations: summed over its steps */
   MPC_HD static int32_t sum_iters(int step, int32_t so_far, int32_t it) { return (step == 0 ? 0 : so_far) + it; }
   /* step `step` (0-based) of a warm rollout starts from the step before if that one succeeded; the first step is always cold */
-  MPC_HD static bool starts_warm(int step, int32_t prev_status) { return step > 0 && prev_status == MPC_STATUS_SUCCESS; }
+  MPC_HD static bool starts_warm(int step, int32_t prev_status, bool budgeted = false) { return step > 0 && warm_status_ok(prev_status, budgeted); }
 };
 
 /* ---- one instance, end to end ------------------------------------------------------------------------------------------------
@@ -2783,8 +2852,8 @@ struct WarmCall {
   int64_t ld_warm;
   MpcWarmOpts wopts;
   int32_t psi_box;                /* the run() path: psi of the records is projected into the instance's [yaw_lo, yaw_hi] */
-  MPC_HD WarmStart instance(int64_t i, double yaw_lo, double yaw_hi) const {
-    const bool warm = warm_in != nullptr && (warm_status == nullptr || warm_status[i] == MPC_STATUS_SUCCESS);
+  MPC_HD WarmStart instance(int64_t i, double yaw_lo, double yaw_hi, bool budgeted = false) const {
+    const bool warm = warm_in != nullptr && (warm_status == nullptr || warm_status_ok(warm_status[i], budgeted));
     return WarmStart{warm, WarmColumn{warm_in + i, ld_warm, psi_box ? yaw_lo : -HUGE_VAL, psi_box ? yaw_hi : HUGE_VAL}, &wopts,
                      warm_out ? warm_out + i : nullptr, ld_warm};
   }

@@ -224,7 +224,11 @@ struct MpcRollPart {
  * and read in the same places -- wherever a lane runs set-up for an instance -- so it follows the instance from lane to lane.  These
  * builds are MODEL builds with one more part; their `model` may be nullptr (the handle's own six values). */
 struct MpcHorizonPart {
-  const int32_t *horizon;
+  const int32_t *horizon;         /* nullptr (a budget call without horizons): the handle's N for every instance */
+  /* the iteration budget of every instance (the mpc_*_budget entry points), [ld] int32 addressed and read like `horizon`, or nullptr:
+   * one more pointer of the per-lane-rows builds, which hand it to set-up in the instance's mpc::HorizonColumn; the rules are
+   * mpc::Solver's ("iteration budget").  budget != nullptr also widens the warm rule (mpc::warm_status_ok). */
+  const int32_t *budget = nullptr;
 };
 
 /* DRIVE (mpc_drive_batch_device_fused): a ROLL build whose car follows a track.  Between two solves the lane runs, for its own car
@@ -375,11 +379,12 @@ template <class RIO, class R> struct OutRef {
  * solve's have T.ld_model (MpcModelPart), and so have a drive's (its ld is the stride of the handle's rows, the columns stay the
  * caller's). */
 template <bool ROLL, bool MODEL, bool HORIZON, bool DRIVE = false, class Phase>
-__device__ __forceinline__ auto instance_column(const Phase &T, int64_t ld, int64_t i) {
+__device__ __forceinline__ auto instance_column(const MpcParams &P, const Phase &T, int64_t ld, int64_t i) {
+  (void)P;
   if constexpr (MODEL) {
     int64_t lm = ld;
     if constexpr (!ROLL || DRIVE) lm = T.ld_model;
-    if constexpr (HORIZON) return mpc::HorizonColumn{T.model ? T.model + i : nullptr, lm, T.horizon[i]};
+    if constexpr (HORIZON) return mpc::HorizonColumn{T.model ? T.model + i : nullptr, lm, T.horizon ? T.horizon[i] : P.N, T.budget ? T.budget[i] : (int)mpc::kNoBudget};
     else return mpc::ModelColumn{T.model + i, lm};
   } else return mpc::NoColumn{};
 }
@@ -513,7 +518,7 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
               double *o = T.out9 + i;
               const int64_t l = ldo;
               const R ylo = (R)T.pre[mpc::RUN_PRE_YAW_LO * ld + i], yhi = (R)T.pre[mpc::RUN_PRE_YAW_HI * ld + i];
-              S.unpack(instance_column<ROLL, MODEL, HORIZON, DRIVE>(T, ld, i), [o, l](int q) { return OutRef<RIO, R>{o + q * l}; },
+              S.unpack(instance_column<ROLL, MODEL, HORIZON, DRIVE>(P, T, ld, i), [o, l](int q) { return OutRef<RIO, R>{o + q * l}; },
                        [](int) { return OutRef<RIO, R>{nullptr}; }, false, ylo, yhi);
               if constexpr (WARM) {
                 double *wo = T.warm_out + i;
@@ -535,7 +540,7 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
             const int64_t l = ldo;
             const R ylo = (R)yaw_lo[i], yhi = (R)yaw_hi[i];
             /* (MODEL: the car's own limits, from its column) */
-            S.unpack(instance_column<ROLL, MODEL, HORIZON>(T, ld, i), [o, l](int q) { return OutRef<RIO, R>{o + q * l}; },
+            S.unpack(instance_column<ROLL, MODEL, HORIZON>(P, T, ld, i), [o, l](int q) { return OutRef<RIO, R>{o + q * l}; },
                      [](int) { return OutRef<RIO, R>{nullptr}; }, false, ylo, yhi);
             double *sp = T.state + i;
             const int64_t ls = ld;
@@ -555,7 +560,9 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
             }
             ++step;
             again = step < T.steps;
-            again_warm = WARM && again && Car::starts_warm(step, fin_status);
+            bool budgeted = false;                 /* (a budget call: a step that stopped at its budget hands its iterate on, mpc::warm_status_ok) */
+            if constexpr (HORIZON) budgeted = T.budget != nullptr;
+            again_warm = WARM && again && Car::starts_warm(step, fin_status, budgeted);
             if (!again) step = 0;                  /* the car is done: the lane is free for whatever the counter still has */
             fin = false;
           }
@@ -565,7 +572,7 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
           RIO *t = traj ? traj + i : nullptr;
           const int64_t l = ldo;
           const R ylo = (R)yaw_lo[i], yhi = (R)yaw_hi[i];
-          S.unpack(instance_column<ROLL, MODEL, HORIZON>(T, ld, i), [o, l](int q) { return OutRef<RIO, R>{o + q * l}; },
+          S.unpack(instance_column<ROLL, MODEL, HORIZON>(P, T, ld, i), [o, l](int q) { return OutRef<RIO, R>{o + q * l}; },
                    [t, l](int q) { return OutRef<RIO, R>{t + q * l}; }, traj != nullptr, ylo, yhi);
           if constexpr (WARM) {
             /* the final iterate, whatever the status (the caller's next solve looks at the status) */
@@ -624,8 +631,9 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
             const bool from_scratch = T.promote_in && T.in_park[pos + 35 * T.ld_park] != 0.0;   /* the fp32 phase gave up on it */
             bool warm = false, warm_cand = false;   /* WARM: this instance has a valid column in warm_in / starts from it */
             if constexpr (WARM && ROLL) warm_cand = again_warm;   /* (the column this lane stored when it finished the step before) */
+            else if constexpr (WARM && HORIZON) warm_cand = T.warm_in != nullptr && (T.warm_status == nullptr || mpc::warm_status_ok(T.warm_status[i], T.budget != nullptr));
             else if constexpr (WARM) warm_cand = T.warm_in != nullptr && (T.warm_status == nullptr || T.warm_status[i] == MPC_STATUS_SUCCESS);
-            const int s0 = S.setup(instance_column<ROLL, MODEL, HORIZON, DRIVE>(T, ld, i), st, cf, ylo, yhi, w, (!T.resume || from_scratch) && !warm_cand);
+            const int s0 = S.setup(instance_column<ROLL, MODEL, HORIZON, DRIVE>(P, T, ld, i), st, cf, ylo, yhi, w, (!T.resume || from_scratch) && !warm_cand);
             if constexpr (WARM) {
               if (warm_cand) {
                 if (s0 == MPC_STATUS_SUCCESS) {
@@ -736,7 +744,7 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
           mpc::gather_instance(P, i, ld, state, coeffs, weights, st, cf, w);
           const R ylo = (R)yaw_lo[i], yhi = (R)yaw_hi[i];
           /* (the instance has changed lanes: its column and its horizon, if it has any, come with it) */
-          (void)S.setup(instance_column<ROLL, MODEL, HORIZON>(T, ld, i), st, cf, ylo, yhi, w, false);
+          (void)S.setup(instance_column<ROLL, MODEL, HORIZON>(P, T, ld, i), st, cf, ylo, yhi, w, false);
           S.unpark([mb, src](int q) -> R { return mb[q * 64 + src]; }, attempt, it_total);
           const int I = S.cur ? FL::IT1 : FL::IT0;
           WS wsrc = ws;
@@ -1386,6 +1394,7 @@ struct MpcHandle {
   double *d_warm = nullptr, *d_warm_io = nullptr;
   double *d_warm_o = nullptr;         /* host forms with a horizon: warm_out on its own (rows an instance does not write come back as the caller has them) */
   int32_t *d_horizon = nullptr;       /* ... and the horizons of a host-array call */
+  int32_t *d_budget = nullptr;        /* ... and its iteration budgets */
   double *d_model = nullptr;      /* the device side of mpc_solve_batch_host_model's model array (allocated on first use) */
   int32_t *d_warm_st = nullptr;
   int64_t n_roll_fused = 0, n_roll_stepwise = 0;   /* mpc_rollout_batch_device_fused calls that ran the fused kernel / the stepwise loop (mpc_rollout_fused_info) */
@@ -1625,6 +1634,7 @@ extern "C" void mpc_destroy(MpcHandle *h) {
   if (h->d_warm_io) (void)hipFree(h->d_warm_io);
   if (h->d_warm_o) (void)hipFree(h->d_warm_o);
   if (h->d_horizon) (void)hipFree(h->d_horizon);
+  if (h->d_budget) (void)hipFree(h->d_budget);
   if (h->d_warm_st) (void)hipFree(h->d_warm_st);
   if (h->tail_ready) (void)tail_drain(h);         /* stragglers still queued are finished: their batches' arrays may be read afterwards */
   if (h->tail_stream) (void)hipStreamSynchronize(h->tail_stream);
@@ -2093,10 +2103,12 @@ struct CallExtras {
   int64_t ld_model = 0;            /* 0: the ld of the solve's inputs.  (run() sets its own: it solves from the handle's rows at the handle's stride, the columns stay where the caller has them) */
   bool model_wave = false;         /* a model call of the run() / telemetry entry points: the wave MODEL kernels up to wave_max_batch */
   const int32_t *horizon = nullptr;   /* a horizon call (fp64 handles, no SOC): [ld] like the inputs; dispatched as a model call, `model` may be NULL */
+  const int32_t *budget = nullptr;    /* a budget call (include/mpc_amd_budget.h; fp64 handles, no SOC): [ld] like `horizon`, and dispatched like a horizon call -- `horizon` may be NULL */
   const double *latency = nullptr;   /* a latency call (fp64 handles): the telemetry handler's comp [ld]; the drive's [MPC_NLATENCY][ld] */
   const double *plant = nullptr;     /* a plant call (the drive, fp64 handles): [MPC_NPLANT][ld], what the cars are moved with */
   const double *run_weights = nullptr;   /* run() / telemetry only (the drive loop): per-instance weights of the solve, [MPC_NW][io_stride] like the rows run() solves from */
-  bool model_call() const { return model != nullptr || horizon != nullptr; }
+  bool lane_rows() const { return horizon != nullptr || budget != nullptr; }      /* the call runs the lane kernel's per-lane-rows (HORIZON) build */
+  bool model_call() const { return model != nullptr || lane_rows(); }
   const WarmIO *warm_io() const { return warm ? &w : nullptr; }
 };
 /* ... and where a deferring launch hands its stragglers: its batch's slot of the ring and its fresh queue */
@@ -2202,7 +2214,7 @@ static int launch_wave(MpcHandle *h, const SolveIO<R> &io, hipStream_t s, bool s
 enum class LaneBuild { single, mixed_f32, mixed_f64 };
 template <class RIO>
 static int launch_lanes(MpcHandle *h, LaneBuild build, const SolveIO<RIO> &io, hipStream_t s, void *ws, bool soc, const MpcPhase &T,
-                        const WarmIO *warm = nullptr, const MpcModelPart &model = {}, const int32_t *horizon = nullptr) {
+                        const WarmIO *warm = nullptr, const MpcModelPart &model = {}, const MpcHorizonPart *lane_rows = nullptr) {
   const unsigned grid = (unsigned)((io.B + kBlock - 1) / kBlock);
   /* (r, rsrc: values of the solver's reals and of the reals its resumed iterates come in) */
   auto go = [&](auto staging, auto r, auto rsrc, auto soc_build, auto warm_build, int64_t tile_reals, auto model_build, auto horizon_build) {
@@ -2211,7 +2223,7 @@ static int launch_lanes(MpcHandle *h, LaneBuild build, const SolveIO<RIO> &io, h
     constexpr bool WARM = decltype(warm_build)::value, MODEL = decltype(model_build)::value;
     const size_t lds = HORIZON ? (T.compact_gap > 0 ? kMailboxBytes : 0) : STAGING ? staging_lds_bytes<R>() : 0;
     return launch_kernel(mpc_solve_kernel<STAGING, R, RIO, decltype(rsrc), decltype(soc_build)::value, WARM, false, MODEL, HORIZON>, grid, lds, s, h, io,
-                         (R *)ws, tile_reals, phase_of<false, WARM, MODEL, HORIZON>(T, warm ? *warm : WarmIO{}, {}, model, {horizon}));
+                         (R *)ws, tile_reals, phase_of<false, WARM, MODEL, HORIZON>(T, warm ? *warm : WarmIO{}, {}, model, lane_rows ? *lane_rows : MpcHorizonPart{}));
   };
   constexpr std::true_type yes{};
   constexpr std::false_type no{};
@@ -2219,7 +2231,7 @@ static int launch_lanes(MpcHandle *h, LaneBuild build, const SolveIO<RIO> &io, h
   if (build == LaneBuild::mixed_f64) return with_bool(soc, [&](auto soc_build) { return go(yes, double{}, float{}, soc_build, no, h->ws_stride_f64, no, no); });
   return with_bool(h->staging, [&](auto staging) {
     if constexpr (sizeof(RIO) == 8) {
-      return with_build(soc, warm != nullptr, model.model != nullptr, horizon != nullptr, [&](auto soc_build, auto warm_build, auto model_build, auto horizon_build) {
+      return with_build(soc, warm != nullptr, model.model != nullptr, lane_rows != nullptr, [&](auto soc_build, auto warm_build, auto model_build, auto horizon_build) {
         return go(staging, RIO{}, RIO{}, soc_build, warm_build, h->ws_stride, model_build, horizon_build);
       });
     } else {
@@ -2370,19 +2382,22 @@ extern "C" int mpc_warm_opts_default(MpcWarmOpts *o) {
  * model needs an fp64 handle that does not start in fp32.  A call with neither is checked for its handle only. */
 static CallExtras call_extras(const MpcHandle *h, const double *model = nullptr, bool warm = false, const double *warm_in = nullptr,
                               const int32_t *warm_status = nullptr, double *warm_out = nullptr, int64_t ld_warm = 0,
-                              const MpcWarmOpts *opts = nullptr, const int32_t *horizon = nullptr, const double *latency = nullptr) {
+                              const MpcWarmOpts *opts = nullptr, const int32_t *horizon = nullptr, const double *latency = nullptr,
+                              const int32_t *budget = nullptr) {
   CallExtras x;
-  x.warm = warm; x.model = model; x.horizon = horizon; x.latency = latency;
+  x.warm = warm; x.model = model; x.horizon = horizon; x.latency = latency; x.budget = budget;
   x.w = WarmIO{warm_in, warm_status, warm_out, ld_warm, {}, 0};
   const auto refuse = [&x](int rc, const char *why) { g_last_error = why; x.refused = rc; return x; };
   if (!h) return refuse(MPC_ERR_INVALID, "NULL handle");
   const bool f64 = h->params.precision == MPC_PRECISION_F64;
-  if ((model || horizon) && !f64) return refuse(MPC_ERR_INVALID, "per-instance model values: fp64 handles only (this one was created with MPC_PRECISION_F32)");
+  if ((model || horizon || budget) && !f64) return refuse(MPC_ERR_INVALID, "per-instance model values: fp64 handles only (this one was created with MPC_PRECISION_F32)");
   if (horizon && h->params.max_soc > 0)
     return refuse(MPC_ERR_UNSUPPORTED, "a per-instance horizon is not available with the second-order correction (max_soc > 0): set MpcParams.max_soc = 0, or pass horizon = NULL");
+  if (budget && h->params.max_soc > 0)
+    return refuse(MPC_ERR_UNSUPPORTED, "a per-instance iteration budget is not available with the second-order correction (max_soc > 0): set MpcParams.max_soc = 0, or pass budget = NULL");
   if (latency && !f64) return refuse(MPC_ERR_INVALID, "per-instance latency: fp64 handles only (this one was created with MPC_PRECISION_F32)");
   if (!warm) return x;
-  const bool as_model = model || horizon;      /* (a horizon call is dispatched as a model call: the model rule decides) */
+  const bool as_model = model || horizon || budget;      /* (a horizon call and a budget call are dispatched as model calls: the model rule decides) */
   if (!as_model && !f64) return refuse(MPC_ERR_INVALID, "warm start: fp64 handles only (this one was created with MPC_PRECISION_F32)");
   if (!as_model && h->mixed)
     return refuse(MPC_ERR_UNSUPPORTED, "warm start is not available on a handle whose solve starts in fp32 (two launches): create it with MpcParams.f64_f32_start = 0");
@@ -2479,7 +2494,8 @@ static int launch_solve(MpcHandle *h, const SolveIO<R> &call, void *stream_, uns
       if (n_cuts > 0) T.compact_gap = 0;     /* (a phase that parks keeps iterates in its columns) */
       tail_fields(h, tp, T);
       if (ordered) { T.ord_cnt = C.cb + kPhaseCounterInts; T.ord_list = h->d_take_list; T.ord_ld = S; }
-      MPC_TRY(launch_lanes(h, LaneBuild::single, io, s, wr ? h->ws2 : h->ws, soc, T, warm, mp, x.horizon));
+      const MpcHorizonPart hp{x.horizon, x.budget};      /* (a horizon or a budget call: the per-lane-rows build) */
+      MPC_TRY(launch_lanes(h, LaneBuild::single, io, s, wr ? h->ws2 : h->ws, soc, T, warm, mp, x.lane_rows() ? &hp : nullptr));
     }
   }
   return solve_end(h, io, s, rec, tp, (flags & kStats) != 0);
@@ -2526,13 +2542,22 @@ extern "C" int mpc_solve_batch_device_horizon(MpcHandle *h, int64_t B, int64_t l
                               model || horizon ? kStats : kStats | kDefer | kOrder, call_extras(h, model, false, nullptr, nullptr, nullptr, 0, nullptr, horizon));
 }
 
+/* (include/mpc_amd_budget.h: the _warm_horizon form plus `budget` behind horizon; NULL is the _warm_horizon form itself) */
+extern "C" int mpc_solve_batch_device_budget(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
+                                             const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
+                                             const int32_t *horizon, const int32_t *budget, const double *warm_in, const int32_t *warm_status,
+                                             double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts, double *out, double *traj,
+                                             int32_t *status, int32_t *iters, void *stream_) {
+  return launch_solve<double>(h, {B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters}, stream_, kStats,
+                              call_extras(h, model, true, warm_in, warm_status, warm_out, ld_warm, opts, horizon, nullptr, budget));
+}
 extern "C" int mpc_solve_batch_device_warm_horizon(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
                                                    const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
                                                    const int32_t *horizon, const double *warm_in, const int32_t *warm_status, double *warm_out,
                                                    int64_t ld_warm, const MpcWarmOpts *opts, double *out, double *traj, int32_t *status,
                                                    int32_t *iters, void *stream_) {
-  return launch_solve<double>(h, {B, ld, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters}, stream_, kStats,
-                              call_extras(h, model, true, warm_in, warm_status, warm_out, ld_warm, opts, horizon));
+  return mpc_solve_batch_device_budget(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, model, horizon, nullptr, warm_in, warm_status, warm_out, ld_warm, opts,
+                                       out, traj, status, iters, stream_);
 }
 
 /* MPC_PRECISION_F32: the same solve with fp32 inputs, outputs and workspace (handle created with precision F32) */
@@ -2550,7 +2575,9 @@ extern "C" int mpc_solve_batch_device_f32(MpcHandle *h, int64_t B, int64_t ld, c
  * stride and the columns from the caller's array at the caller's ld (CallExtras::ld_model) -- the array is not copied.
  * x.latency (device, comp [ld], with tel): the pre kernel's build that compensates per instance; `extra` is not read.
  * x.horizon (device, [ld] int32): the solve between the two kernels is the horizon solve -- the lane kernel's HORIZON build at every
- * B, cold or warm, with or without model; the pre and post kernels do not read N and are the builds `model` alone selects. */
+ * B, cold or warm, with or without model; the pre and post kernels do not read N and are the builds `model` alone selects.
+ * x.budget (device, [ld] int32; no public entry point sets it here, the stepwise drive does): the solve is the budget solve -- the same
+ * HORIZON build, with or without x.horizon. */
 static int run_impl(MpcHandle *h, int64_t B, int64_t ld, int npts, const double *pose, bool tel, double extra, double *ptsx,
                     double *ptsy, double *out8, double *cmd, double *traj, int32_t *status, int32_t *iters, double *pre,
                     void *stream_, CallExtras x) {
@@ -2589,7 +2616,7 @@ static int run_impl(MpcHandle *h, int64_t B, int64_t ld, int npts, const double 
     });
   });
   MPC_HIP_CHECK(hipGetLastError());
-  x.w.psi_box = 1; x.ld_model = ld; x.model_wave = !x.horizon;      /* the run() path's own (a horizon call has no wave path: the lane kernel's HORIZON build at every B) */
+  x.w.psi_box = 1; x.ld_model = ld; x.model_wave = !x.lane_rows();      /* the run() path's own (a horizon or budget call has no wave path: the lane kernel's HORIZON build at every B) */
   MPC_TRY(launch_solve<double>(h, {B, S, ld, d_pre + mpc::RUN_PRE_STATE * S, d_pre + mpc::RUN_PRE_COEFFS * S, d_pre + mpc::RUN_PRE_YAW_LO * S,
                                    d_pre + mpc::RUN_PRE_YAW_HI * S, x.run_weights, h->d_run9, traj, status, iters}, stream_, kStats, x));
   around([&](auto model_build, auto... mp) {
@@ -2695,7 +2722,7 @@ static int host_extras_in(MpcHandle *h, int64_t B, const CallExtras &hx, const d
     }
   }
   if (hw.warm_out) dx->w.warm_out = h->d_warm_io;
-  if (hw.warm_out && hx.horizon) {
+  if (hw.warm_out && hx.lane_rows()) {
     /* an instance writes the records of its own stages only: the rows behind them must come back as the caller has them, so
      * the caller's warm_out goes in first, into a block of its own (warm_in may be another array) */
     MPC_TRY(ensure_dev(&h->d_warm_o, sizeof(double) * (size_t)warm_rows * (size_t)S));
@@ -2706,7 +2733,7 @@ static int host_extras_in(MpcHandle *h, int64_t B, const CallExtras &hx, const d
 }
 static int host_extras_out(MpcHandle *h, int64_t B, const CallExtras &hx, hipStream_t s) {
   if (!hx.warm || !hx.w.warm_out) return MPC_OK;
-  MPC_HIP_CHECK(hipMemcpy2DAsync(hx.w.warm_out, sizeof(double) * hx.w.ld_warm, hx.horizon ? h->d_warm_o : h->d_warm_io, sizeof(double) * h->io_stride, sizeof(double) * B,
+  MPC_HIP_CHECK(hipMemcpy2DAsync(hx.w.warm_out, sizeof(double) * hx.w.ld_warm, hx.lane_rows() ? h->d_warm_o : h->d_warm_io, sizeof(double) * h->io_stride, sizeof(double) * B,
                                  mpc_warm_rows(h->params.N), hipMemcpyDeviceToHost, s));
   return MPC_OK;
 }
@@ -3119,29 +3146,37 @@ static int drive_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *ca
 /* What every drive entry point does first: with `model`, the model rule (which handles a model call is accepted on, call_extras);
  * drive_args; then the call's extras -- the warm refusals and the options in effect. */
 static int drive_call(const MpcHandle *h, int64_t B, int64_t ld, int steps, const double *car, const double *track_x, const double *track_y,
-                      int n_track, const double *model, const int32_t *horizon, const double *latency, const double *plant, const MpcDriveOpts *opts,
-                      const MpcWarmOpts *warm_opts, const double *summary, const int32_t *status, MpcDriveOpts *O, CallExtras *x) {
+                      int n_track, const double *model, const int32_t *horizon, const int32_t *budget, const double *latency, const double *plant,
+                      const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, const double *summary, const int32_t *status, MpcDriveOpts *O, CallExtras *x) {
   if (h && plant && h->params.precision != MPC_PRECISION_F64) {
     g_last_error = "track driving: fp64 handles only (this one was created with MPC_PRECISION_F32)";
     return MPC_ERR_INVALID;
   }
-  if (h && (model || horizon)) MPC_TRY(call_extras(h, model, false, nullptr, nullptr, nullptr, 0, nullptr, horizon).refused);
+  if (h && (model || horizon || budget)) MPC_TRY(call_extras(h, model, false, nullptr, nullptr, nullptr, 0, nullptr, horizon, nullptr, budget).refused);
   MPC_TRY(drive_args(h, B, ld, steps, car, track_x, track_y, n_track, opts, summary, status, O));
-  *x = call_extras(h, model, O->warm_start != 0, nullptr, nullptr, nullptr, 0, warm_opts, horizon, latency);
+  *x = call_extras(h, model, O->warm_start != 0, nullptr, nullptr, nullptr, 0, warm_opts, horizon, latency, budget);
   x->plant = plant;
   return x->refused;
 }
 
 /* (the _plant forms, "per-car plant values" in include/mpc_amd_drive.h: the _horizon forms plus `plant` behind latency; NULL is the _horizon form itself) */
+/* (the _budget forms, include/mpc_amd_budget.h: the _plant forms plus `budget` behind horizon; NULL is the _plant form itself) */
+extern "C" int mpc_drive_batch_device_budget(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
+                                             const double *track_y, int n_track, const double *weights, const double *model, const int32_t *horizon,
+                                             const int32_t *budget, const double *latency, const double *plant, const MpcDriveOpts *opts,
+                                             const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status, int32_t *iters, void *stream_) {
+  MpcDriveOpts O;
+  CallExtras x;
+  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, horizon, budget, latency, plant, opts, warm_opts, summary, status, &O, &x));
+  if (B == 0) { h->last_B = 0; return MPC_OK; }
+  return drive_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
+}
 extern "C" int mpc_drive_batch_device_plant(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
                                             const double *track_y, int n_track, const double *weights, const double *model, const int32_t *horizon,
                                             const double *latency, const double *plant, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts,
                                             double *summary, double *hist, int32_t *status, int32_t *iters, void *stream_) {
-  MpcDriveOpts O;
-  CallExtras x;
-  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, horizon, latency, plant, opts, warm_opts, summary, status, &O, &x));
-  if (B == 0) { h->last_B = 0; return MPC_OK; }
-  return drive_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
+  return mpc_drive_batch_device_budget(h, B, ld, steps, car, track_x, track_y, n_track, weights, model, horizon, nullptr, latency, plant, opts, warm_opts, summary,
+                                       hist, status, iters, stream_);
 }
 /* (the _horizon forms, "per-car horizon" in include/mpc_amd_drive.h: the _latency forms plus `horizon` behind model; NULL is the _latency form itself) */
 extern "C" int mpc_drive_batch_device_horizon(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
@@ -3183,7 +3218,7 @@ static int drive_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, doub
                             const double *weights, const MpcDriveOpts &O, const CallExtras &x, double *summary, double *hist, int32_t *status,
                             int32_t *iters, void *stream_) {
   /* (a horizon call never takes the wave path or the fp32 start: the one launch at every B >= 1, the rule of rollout_fused_impl) */
-  const bool wave_path = !x.horizon && h->wave_max_batch > 0 && B <= h->wave_max_batch;
+  const bool wave_path = !x.lane_rows() && h->wave_max_batch > 0 && B <= h->wave_max_batch;      /* (a budget call: the horizon call's rule) */
   const double *model = x.model;
   if ((h->mixed && !x.model_call()) || h->params.max_soc > 0 || wave_path)
     return drive_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
@@ -3216,12 +3251,12 @@ static int drive_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, doub
   const MpcRollPart roll{steps, nullptr, 0, nullptr, status, iters};
   const MpcDrivePart drive{O, car, track_x, track_y, n_track, ptsx, ptsy, cmd, d_pre, h->d_run9, summary, hist, x.latency, x.plant};
   const unsigned grid = (unsigned)((B + kBlock - 1) / kBlock);
-  if (x.horizon) {
+  if (x.lane_rows()) {
     /* the DRIVE x HORIZON builds: MODEL builds whose `model` may be nullptr, not staged, per-lane workspace rows, no LDS (no lane compaction here) */
     MPC_TRY(with_bool(x.warm, [&](auto warm_build) {
       constexpr bool WARM = decltype(warm_build)::value;
       return launch_kernel(mpc_solve_kernel<false, double, double, double, false, WARM, true, true, true, true>, grid, 0, s, h, io, (double *)h->ws, h->ws_stride,
-                           phase_of<true, WARM, true, true, true>(T, wc, roll, {model, ld}, {x.horizon}, drive));
+                           phase_of<true, WARM, true, true, true>(T, wc, roll, {model, ld}, {x.horizon, x.budget}, drive));
     }));
   } else
   MPC_TRY(with_bool(h->staging, [&](auto staging) {
@@ -3238,16 +3273,24 @@ static int drive_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, doub
   return record_stats(h, B, status, iters, s);
 }
 
+extern "C" int mpc_drive_batch_device_fused_budget(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
+                                                   const double *track_y, int n_track, const double *weights, const double *model,
+                                                   const int32_t *horizon, const int32_t *budget, const double *latency, const double *plant,
+                                                   const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status,
+                                                   int32_t *iters, void *stream_) {
+  MpcDriveOpts O;
+  CallExtras x;
+  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, horizon, budget, latency, plant, opts, warm_opts, summary, status, &O, &x));
+  if (B == 0) { h->last_B = 0; return MPC_OK; }
+  return drive_fused_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
+}
 extern "C" int mpc_drive_batch_device_fused_plant(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
                                                   const double *track_y, int n_track, const double *weights, const double *model,
                                                   const int32_t *horizon, const double *latency, const double *plant, const MpcDriveOpts *opts,
                                                   const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status, int32_t *iters,
                                                   void *stream_) {
-  MpcDriveOpts O;
-  CallExtras x;
-  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, horizon, latency, plant, opts, warm_opts, summary, status, &O, &x));
-  if (B == 0) { h->last_B = 0; return MPC_OK; }
-  return drive_fused_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
+  return mpc_drive_batch_device_fused_budget(h, B, ld, steps, car, track_x, track_y, n_track, weights, model, horizon, nullptr, latency, plant, opts, warm_opts,
+                                             summary, hist, status, iters, stream_);
 }
 extern "C" int mpc_drive_batch_device_fused_horizon(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
                                                     const double *track_y, int n_track, const double *weights, const double *model,
@@ -3281,13 +3324,13 @@ extern "C" int mpc_drive_batch_device_fused(MpcHandle *h, int64_t B, int64_t ld,
 /* The same for host arrays: one copy in, the loop on the handle's own device and stream, one copy out; synchronises.  Staging kept on
  * the handle and grown on demand, like the telemetry handler's.  model (host, [MPC_NMODEL][ld]), latency (host, [MPC_NLATENCY][ld]) and
  * horizon (host, [ld] int32, to h->d_horizon) are copied in with the other inputs, and so is plant (host, [MPC_NPLANT][ld]). */
-extern "C" int mpc_drive_batch_host_plant(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
-                                          int n_track, const double *weights, const double *model, const int32_t *horizon, const double *latency,
-                                          const double *plant, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist,
-                                          int32_t *status, int32_t *iters) {
+extern "C" int mpc_drive_batch_host_budget(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                                           int n_track, const double *weights, const double *model, const int32_t *horizon, const int32_t *budget,
+                                           const double *latency, const double *plant, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts,
+                                           double *summary, double *hist, int32_t *status, int32_t *iters) {
   MpcDriveOpts O;
   CallExtras x;
-  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, horizon, latency, plant, opts, warm_opts, summary, status, &O, &x));
+  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, horizon, budget, latency, plant, opts, warm_opts, summary, status, &O, &x));
   if (B == 0) { h->last_B = 0; return MPC_OK; }
   MPC_ON_DEVICE(h);
   const int64_t L = (B + 7) / 8 * 8;
@@ -3319,6 +3362,11 @@ extern "C" int mpc_drive_batch_host_plant(MpcHandle *h, int64_t B, int64_t ld, i
     MPC_HIP_CHECK(hipMemcpyAsync(h->d_horizon, horizon, sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
     x.horizon = h->d_horizon;
   }
+  if (budget) {
+    MPC_TRY(ensure_dev(&h->d_budget, sizeof(int32_t) * (size_t)h->io_stride));
+    MPC_HIP_CHECK(hipMemcpyAsync(h->d_budget, budget, sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
+    x.budget = h->d_budget;
+  }
   MPC_HIP_CHECK(hipMemcpyAsync(d_tx, track_x, sizeof(double) * n_track, hipMemcpyHostToDevice, s));
   MPC_HIP_CHECK(hipMemcpyAsync(d_ty, track_y, sizeof(double) * n_track, hipMemcpyHostToDevice, s));
   MPC_TRY(drive_impl(h, B, L, steps, d_car, d_tx, d_ty, n_track, weights ? d_w : nullptr, O, x, d_sum, hist ? d_hist : nullptr, d_st, d_it, (void *)s));
@@ -3329,6 +3377,13 @@ extern "C" int mpc_drive_batch_host_plant(MpcHandle *h, int64_t B, int64_t ld, i
   if (iters) MPC_HIP_CHECK(hipMemcpyAsync(iters, d_it, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipStreamSynchronize(s));
   return MPC_OK;
+}
+extern "C" int mpc_drive_batch_host_plant(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                                          int n_track, const double *weights, const double *model, const int32_t *horizon, const double *latency,
+                                          const double *plant, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist,
+                                          int32_t *status, int32_t *iters) {
+  return mpc_drive_batch_host_budget(h, B, ld, steps, car, track_x, track_y, n_track, weights, model, horizon, nullptr, latency, plant, opts, warm_opts, summary,
+                                     hist, status, iters);
 }
 extern "C" int mpc_drive_batch_host_horizon(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
                                             int n_track, const double *weights, const double *model, const int32_t *horizon, const double *latency,
@@ -3425,12 +3480,19 @@ static int solve_host(MpcHandle *h, int64_t B, int64_t ld, const R *state, const
     MPC_HIP_CHECK(hipMemcpy2DAsync(h->d_model, sizeof(double) * L, x.model, sizeof(double) * ld, sizeof(double) * B, MPC_NMODEL, hipMemcpyHostToDevice, s));
     dx.model = h->d_model;
   }
-  if (x.horizon) {
-    /* the horizons go along like the model columns.  An instance writes only the first n points of each half of its traj column:
-     * the rows behind them come back as the caller has them, so the caller's traj goes in with the inputs */
-    MPC_TRY(ensure_dev(&h->d_horizon, sizeof(int32_t) * (size_t)S));
-    MPC_HIP_CHECK(hipMemcpyAsync(h->d_horizon, x.horizon, sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
-    dx.horizon = h->d_horizon;
+  if (x.lane_rows()) {
+    /* the horizons go along like the model columns, and so do the budgets.  An instance writes only the first n points of each half
+     * of its traj column: the rows behind them come back as the caller has them, so the caller's traj goes in with the inputs */
+    if (x.horizon) {
+      MPC_TRY(ensure_dev(&h->d_horizon, sizeof(int32_t) * (size_t)S));
+      MPC_HIP_CHECK(hipMemcpyAsync(h->d_horizon, x.horizon, sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
+      dx.horizon = h->d_horizon;
+    }
+    if (x.budget) {
+      MPC_TRY(ensure_dev(&h->d_budget, sizeof(int32_t) * (size_t)S));
+      MPC_HIP_CHECK(hipMemcpyAsync(h->d_budget, x.budget, sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
+      dx.budget = h->d_budget;
+    }
     if (traj) {
       for_rows(2 * N, sizeof(R) * B, [=](int q) { memcpy(ho + (MPC_NOUT + q) * L, traj + q * ld, sizeof(R) * B); });
       MPC_HIP_CHECK(hipMemcpyAsync(d_t, ho + MPC_NOUT * L, sizeof(R) * 2 * N * L, hipMemcpyHostToDevice, s));
@@ -3487,13 +3549,21 @@ extern "C" int mpc_solve_batch_host_horizon(MpcHandle *h, int64_t B, int64_t ld,
                             call_extras(h, model, false, nullptr, nullptr, nullptr, 0, nullptr, horizon));
 }
 
+extern "C" int mpc_solve_batch_host_budget(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
+                                           const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
+                                           const int32_t *horizon, const int32_t *budget, const double *warm_in, const int32_t *warm_status,
+                                           double *warm_out, int64_t ld_warm, const MpcWarmOpts *opts, double *out, double *traj,
+                                           int32_t *status, int32_t *iters) {
+  return solve_host<double>(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters,
+                            call_extras(h, model, true, warm_in, warm_status, warm_out, ld_warm, opts, horizon, nullptr, budget));
+}
 extern "C" int mpc_solve_batch_host_warm_horizon(MpcHandle *h, int64_t B, int64_t ld, const double *state, const double *coeffs,
                                                  const double *yaw_lo, const double *yaw_hi, const double *weights, const double *model,
                                                  const int32_t *horizon, const double *warm_in, const int32_t *warm_status, double *warm_out,
                                                  int64_t ld_warm, const MpcWarmOpts *opts, double *out, double *traj, int32_t *status,
                                                  int32_t *iters) {
-  return solve_host<double>(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, out, traj, status, iters,
-                            call_extras(h, model, true, warm_in, warm_status, warm_out, ld_warm, opts, horizon));
+  return mpc_solve_batch_host_budget(h, B, ld, state, coeffs, yaw_lo, yaw_hi, weights, model, horizon, nullptr, warm_in, warm_status, warm_out, ld_warm, opts, out,
+                                     traj, status, iters);
 }
 
 extern "C" int mpc_solve_batch_host_f32(MpcHandle *h, int64_t B, int64_t ld, const float *state,

@@ -72,11 +72,19 @@ class BatchedMPC:
         """Rows of this handle's warm buffers: (N-1) * WARM_REC."""
         return _abi.warm_rows(self.N)
 
-    def _call(self, family, head, outs, model=None, warm=None, horizon=None):
+    def _call(self, family, head, outs, model=None, warm=None, horizon=None, budget=None):
         """Call `family`'s entry point for this call, chosen by the rule of include/mpc_amd.h: the name is the family's, + "_warm"
         for a warm call (`warm`: the values the _warm form takes -- warm_in, warm_status, warm_out, ld_warm, opts; the stepwise
         rollout: opts alone), + "_model" with `model` (a pointer) or "_horizon" with `horizon` (a pointer; `model` may then be
-        None); the arguments are the handle, head, [model, [horizon]], warm, outs."""
+        None); the arguments are the handle, head, [model, [horizon]], warm, outs.  With `budget` (a pointer; the solve families,
+        include/mpc_amd_budget.h): the _budget form -- head, model, horizon, budget, the five warm values (a call without: NULL
+        buffers), outs."""
+        if budget is not None:
+            name = family + "_budget"
+            rc = getattr(library(), name)(self._h, *head, model, horizon, budget, *(warm or (None, None, None, head[0], None)), *outs)
+            if rc != 0:
+                check(rc, name)
+            return
         extra = () if model is None and horizon is None else ((model,) if horizon is None else (model, horizon))
         name = family + ("_warm" if warm is not None else "") + ("_horizon" if horizon is not None else "_model" if model is not None else "")
         rc = getattr(library(), name)(self._h, *head, *extra, *(warm or ()), *outs)
@@ -84,7 +92,7 @@ class BatchedMPC:
             check(rc, name)
 
     def solve_torch(self, state, coeffs, yaw_lo, yaw_hi, weights=None, want_traj=False, outputs=None, stream=None,
-                    warm=None, warm_status=None, want_warm=False, warm_opts=None, model=None, horizon=None):
+                    warm=None, warm_status=None, want_warm=False, warm_opts=None, model=None, horizon=None, budget=None):
         """state [6,B], coeffs [5,B], yaw_lo/hi [B], weights [12,B] or None: CUDA tensors, float64 (float32 for a
         handle created with precision F32).  Asynchronous on ``stream`` (default: torch's current stream).  Returns the
         dict of output tensors.
@@ -102,7 +110,12 @@ class BatchedMPC:
         ``horizon`` [B] int32 (fp64 handles, max_soc = 0; mpc_solve_batch_device_horizon, _warm_horizon): the N of every instance,
         3 .. the handle's N, with or without ``model``; dispatched like a model call.  "traj" and "warm" keep the handle's shapes:
         instance i writes x, y of its n points (rows 0..n-1 and N..N+n-1) and the records of its n-1 stages, nothing behind them.
-        Any other value ends that instance INFEASIBLE.  Sort a batch by horizon: a wave is as slow as its longest one."""
+        Any other value ends that instance INFEASIBLE.  Sort a batch by horizon: a wave is as slow as its longest one.
+
+        ``budget`` [B] int32 (fp64 handles, max_soc = 0; mpc_solve_batch_device_budget): the interior-point iterations every instance
+        may take over all of its attempts -- the reference's solve deadline, counted in iterations.  An instance that uses its
+        budget up ends MAXITER with its current iterate (iters == budget), and with ``budget`` a "warm" record that came with MAXITER is a
+        candidate like one with SUCCESS.  budget < 1 ends that instance INFEASIBLE.  Dispatched like a horizon call."""
         import torch
         B = state.shape[1]
         dt = self._dtype()
@@ -123,6 +136,8 @@ class BatchedMPC:
             self._check_model(model, B)
         if horizon is not None:
             self._check_horizon(horizon, B)
+        if budget is not None:
+            self._check_horizon(budget, B, "budget")
         warm_args = None
         if warm is not None or want_warm:
             rows = self.warm_rows()
@@ -138,24 +153,24 @@ class BatchedMPC:
                 weights.data_ptr() if weights is not None else None)
         outs = (outputs["out"].data_ptr(), traj.data_ptr() if traj is not None else None, outputs["status"].data_ptr(),
                 outputs["iters"].data_ptr(), C.c_void_p(s.cuda_stream))
-        if self.f32 and model is None and warm_args is None and horizon is None:
+        if self.f32 and model is None and warm_args is None and horizon is None and budget is None:
             check(library().mpc_solve_batch_device_f32(self._h, *head, *outs), "mpc_solve_batch_device")
         else:
             self._call("mpc_solve_batch_device", head, outs, model.data_ptr() if model is not None else None, warm_args,
-                       horizon.data_ptr() if horizon is not None else None)
+                       horizon.data_ptr() if horizon is not None else None, budget.data_ptr() if budget is not None else None)
         return outputs
 
     @staticmethod
-    def _check_horizon(horizon, B):
+    def _check_horizon(horizon, B, what="horizon"):
         import torch
         if horizon.dtype != torch.int32 or not horizon.is_cuda or not horizon.is_contiguous() or tuple(horizon.shape) != (B,):
-            raise ValueError("horizon must be a contiguous int32 CUDA tensor of shape (B,)")
+            raise ValueError("%s must be a contiguous int32 CUDA tensor of shape (B,)" % what)
 
     @staticmethod
-    def _host_horizon(horizon, B):
+    def _host_horizon(horizon, B, what="horizon"):
         horizon = np.ascontiguousarray(np.asarray(horizon, dtype=np.int32))
         if horizon.shape != (B,):
-            raise ValueError("horizon must have shape (B,)")
+            raise ValueError("%s must have shape (B,)" % what)
         return horizon
 
     @staticmethod
@@ -368,7 +383,7 @@ class BatchedMPC:
         return _abi.drive_plant_default(self.params, B, model)
 
     def drive_torch(self, car, track_x, track_y, steps, weights=None, opts=None, warm_opts=None, want_hist=True, fused=False, stream=None,
-                    model=None, latency=None, horizon=None, plant=None):
+                    model=None, latency=None, horizon=None, plant=None, budget=None):
         """Drive B cars along a cyclic track for `steps` telemetry messages on the device (mpc_drive_batch_device): per message the
         waypoint window at the car's position, the telemetry handler (cold, or warm with opts.warm_start) and the plant -- the
         reference's own kinematic model, not the simulator.  car [6, B] = x, y, psi, speed [mph], steering_angle, throttle is advanced
@@ -388,9 +403,16 @@ class BatchedMPC:
         ``plant`` [6, B] float64 (mpc_drive_batch_device_plant, _fused_plant; rows _abi.PLANT_*): the values every car is MOVED with --
         Lf, steering gain and bias, acceleration gain, drag speed, side drift -- while its handler goes on believing ``model``: one call
         answers "how wrong may the model be before the car leaves the road".  drive_plant_default(B, model) is the column that changes
-        nothing."""
+        nothing.
+        ``budget`` [B] int32 (mpc_drive_batch_device_budget, _fused_budget; fp64 handles, max_soc = 0): the interior-point iterations
+        every car's handler may spend per message, over all attempts of its solve -- the reference's solve deadline (ipoptTimeout),
+        counted in iterations.  A message that uses its budget up drives the car with the current iterate (status MAXITER) and, with
+        opts.warm_start, hands that iterate to the next message: one call answers "how much solver work per message does this tuning
+        need to stay on the road, cold or warm-started".  The lane kernel at every B, like ``horizon``."""
         import torch
         B = car.shape[1]
+        if budget is not None:
+            self._check_horizon(budget, B, "budget")
         if plant is not None and (plant.dtype != torch.float64 or not plant.is_cuda or not plant.is_contiguous() or
                                   tuple(plant.shape) != (_abi.NPLANT, B)):
             raise ValueError("plant must be a contiguous float64 CUDA tensor of shape (%d, B)" % _abi.NPLANT)
@@ -411,14 +433,16 @@ class BatchedMPC:
                "status": torch.empty((B,), dtype=torch.int32, device=dev), "iters": torch.empty((B,), dtype=torch.int32, device=dev)}
         s = stream if stream is not None else torch.cuda.current_stream(dev)
         name = ("mpc_drive_batch_device_fused" if fused else "mpc_drive_batch_device") + (
-            "_plant" if plant is not None else "_horizon" if horizon is not None else "_latency" if latency is not None else
-            "_model" if model is not None else "")
+            "_budget" if budget is not None else "_plant" if plant is not None else "_horizon" if horizon is not None else
+            "_latency" if latency is not None else "_model" if model is not None else "")
         extra = (model.data_ptr(),) if model is not None else ()
         if latency is not None or horizon is not None:
             extra = (model.data_ptr() if model is not None else None,) + ((horizon.data_ptr(),) if horizon is not None else ()) + (
                 latency.data_ptr() if latency is not None else None,)
         if plant is not None:
             extra = tuple(t.data_ptr() if t is not None else None for t in (model, horizon, latency, plant))
+        if budget is not None:
+            extra = tuple(t.data_ptr() if t is not None else None for t in (model, horizon, budget, latency, plant))
         check(getattr(library(), name)(self._h, B, B, int(steps), car.data_ptr(), track_x.data_ptr(), track_y.data_ptr(), n,
                                                weights.data_ptr() if weights is not None else None, *extra,
                                                C.byref(opts) if opts is not None else None, C.byref(warm_opts) if warm_opts is not None else None,
@@ -428,11 +452,11 @@ class BatchedMPC:
         return res
 
     def drive_numpy(self, car, track_x, track_y, steps, weights=None, opts=None, warm_opts=None, want_hist=True, model=None, latency=None, horizon=None,
-                    plant=None):
+                    plant=None, budget=None):
         """drive_torch for host arrays (mpc_drive_batch_host): one copy in, the loop, one copy out; synchronises.  `car` is copied:
         the cars after the last step are "car" of the result.  ``model`` [6, B]: as in drive_torch (mpc_drive_batch_host_model); ``latency`` [3, B]: as in
         drive_torch (mpc_drive_batch_host_latency); ``horizon`` [B] int32: as in drive_torch (mpc_drive_batch_host_horizon); ``plant`` [6, B]: as in
-        drive_torch (mpc_drive_batch_host_plant)."""
+        drive_torch (mpc_drive_batch_host_plant); ``budget`` [B] int32: as in drive_torch (mpc_drive_batch_host_budget)."""
         f = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64)) if a is not None else None
         car, tx, ty, weights = f(car).copy(), f(track_x), f(track_y), f(weights)
         B, n = car.shape[1], tx.shape[0]
@@ -461,6 +485,11 @@ class BatchedMPC:
             if plant.shape != (_abi.NPLANT, B):
                 raise ValueError("plant must have shape (%d, B)" % _abi.NPLANT)
             name, extra = "mpc_drive_batch_host_plant", (p(model), p(horizon), p(latency), p(plant))
+        if budget is not None:
+            budget = np.ascontiguousarray(np.asarray(budget))
+            if budget.dtype != np.int32 or budget.shape != (B,):
+                raise ValueError("budget must be an int32 array of shape (B,)")
+            name, extra = "mpc_drive_batch_host_budget", (p(model), p(horizon), p(budget), p(latency), p(plant))
         check(getattr(library(), name)(self._h, B, B, int(steps), p(car), p(tx), p(ty), n, p(weights), *extra,
                                        C.byref(opts) if opts is not None else None, C.byref(warm_opts) if warm_opts is not None else None,
                                        p(res["summary"]), p(res["hist"]), p(res["status"]), p(res["iters"])), name)
@@ -510,12 +539,13 @@ class BatchedMPC:
         return np.full((2 * self.N, B), np.nan, dtype=dt) if horizon is not None else np.empty((2 * self.N, B), dtype=dt)
 
     def solve_numpy_warm(self, state, coeffs, yaw_lo, yaw_hi, warm=None, warm_status=None, weights=None, want_traj=False, warm_opts=None,
-                         model=None, horizon=None, traj_out=None, warm_out=None):
+                         model=None, horizon=None, traj_out=None, warm_out=None, budget=None):
         """Host arrays through mpc_solve_batch_host_warm (fp64 handles): like solve_numpy, with "warm" [warm_rows(), B] in the
         result; ``warm`` / ``warm_status``: that array and the status of an earlier call.  ``model`` [6, B]: as in solve_numpy
         (mpc_solve_batch_host_warm_model).  ``horizon`` [B] int32: as in solve_numpy (mpc_solve_batch_host_warm_horizon): an instance
         reads and writes the records of its own n-1 stages; the rows of "warm" behind them hold NaN, or what ``warm_out``
-        [warm_rows(), B] (written in place; may be ``warm`` itself) held."""
+        [warm_rows(), B] (written in place; may be ``warm`` itself) held.  ``budget`` [B] int32: as in solve_torch
+        (mpc_solve_batch_host_budget)."""
         f = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64))
         state, coeffs, yaw_lo, yaw_hi = f(state), f(coeffs), f(yaw_lo), f(yaw_hi)
         B = state.shape[1]
@@ -540,8 +570,11 @@ class BatchedMPC:
             assert model.shape == (_abi.NMODEL, B)
         if horizon is not None:
             horizon = self._host_horizon(horizon, B)
+        if budget is not None:
+            budget = self._host_horizon(budget, B, "budget")
         self._call("mpc_solve_batch_host", (B, B, p(state), p(coeffs), p(yaw_lo), p(yaw_hi), p(weights)), (p(out), p(traj), p(status), p(iters)),
-                   p(model), (p(warm), p(warm_status), p(wout), B, C.byref(warm_opts) if warm_opts is not None else None), horizon=p(horizon))
+                   p(model), (p(warm), p(warm_status), p(wout), B, C.byref(warm_opts) if warm_opts is not None else None), horizon=p(horizon),
+                   budget=p(budget))
         return {"out": out, "status": status, "iters": iters, "traj": traj, "warm": wout}
 
     # -- the certificate of a stored point (include/mpc_amd_certify.h) ----------

@@ -102,7 +102,7 @@ typedef struct MpcParams {
   double lookahead;          /* Config::lookahead = latency * 1e-3 */
   double steer_adj_thresh;   /* Config::steerAdjustmentThresh */
   double steer_adj_ratio;    /* Config::steerAdjustmentRatio (clamped to [0,0.1]) */
-  double ipopt_timeout;      /* Config::ipoptTimeout: carried, not used (we cap iterations) */
+  double ipopt_timeout;      /* Config::ipoptTimeout: carried, not read -- the deadline is a per-instance iteration budget, mpc_amd_budget.h */
   /* solver controls (the reference's IPOPT option string, MPC.cpp:160-179, plus
    * the IPOPT defaults it leaves untouched) */
   int32_t branch_mode;       /* MPC_BRANCH_FROZEN: CppAD tape recorded once at the start point */
@@ -552,6 +552,11 @@ int mpc_rollout_batch_device_fused_model(MpcHandle *h, int64_t B, int64_t ld, in
  * as the plant, with a summary per car and, if asked for, a record per step.  Nothing returns to the host between the steps.  The
  * section and its declarations live in a header of their own, which this one includes: */
 #include "mpc_amd_drive.h"
+/* ---- per-instance iteration budget: the reference's solve deadline (ipoptTimeout), counted in iterations -------------------------
+ * The _budget forms of the warm horizon solve and of the track drive cap the interior-point iterations of every instance over all of
+ * its attempts and hand an unconverged iterate on to the next message.  The section and its declarations live in a header of their
+ * own, which this one includes: */
+#include "mpc_amd_budget.h"
 /* ---- per-instance model values on the run() path: a fleet of different vehicles behind one handler ----------------------------
  * Each entry point is the one of the same name without `_model` plus `model`, [MPC_NMODEL][ld] doubles addressed with the call's
  * ld (rows MPC_MODEL_*), directly behind `ptsy`; the wire forms further down take it as [MPC_NMODEL][B] directly behind

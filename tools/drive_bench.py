@@ -50,7 +50,14 @@ step, so it may be given --reps and --warmup of its own in a run of its own; eve
              run a process of its own (--root); per leg the six medians of the warm one-launch form are the figures, every other form
              is recorded beside them.
 --legs grid,plain,model picks what is run (default: all three; plain and model need --parent); what --out already holds is kept: a
-cost leg is a list of sessions, and a run appends one."""
+cost leg is a list of sessions, and a run appends one.
+
+--budget: the mpc_drive_*_budget entry points (default --out profiles/drive_budget.json) --
+  grid       --budgets iteration budgets x {cold, warm} x --cars cars (the same starts in every cell) on the lake track: per start mode ONE
+             one-launch _fused_budget call of --sweep-steps messages with the budgets as its columns, timed like every figure of this
+             tool; beside it the same cars through the same call with budget = NULL (the _fused_plant form: what the parent commit runs);
+             per budget and start mode the mean iterations per message, the share of messages the budget ended, the share of cars that
+             stay within cte_limit and the median of max |cte|.  What --out already holds is kept."""
 import argparse
 import json
 import os
@@ -92,9 +99,11 @@ def main():
     ap.add_argument("--plant", action="store_true", help="run the Lf-ratio x steering-bias grid of the _plant entry points")
     ap.add_argument("--ratios", type=int, default=16, help="--plant: values of plant Lf / model Lf, 0.5 .. 1.5")
     ap.add_argument("--biases", type=int, default=16, help="--plant: steering biases, -0.1 .. 0.1 rad")
+    ap.add_argument("--budget", action="store_true", help="run the budget x {cold, warm} grid of the _budget entry points")
+    ap.add_argument("--budgets", default="1,2,3,4,5,6,8,12,50", help="--budget: the iteration budgets of the grid")
     ap.add_argument("--merge", nargs="*", default=None, help="--horizon: files of this tool whose legs are copied into --out (nothing is run)")
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "drive_plant.json" if a.plant else "drive_horizon.json" if a.horizon else "drive_latency.json" if a.latency else
+    a.out = a.out or os.path.join(ROOT, "profiles", "drive_budget.json" if a.budget else "drive_plant.json" if a.plant else "drive_horizon.json" if a.horizon else "drive_latency.json" if a.latency else
                                   "drive_model.json" if a.model else "drive.json")
     if a.horizon and a.merge is not None:
         doc = {"tool": "tools/drive_bench.py --horizon", "legs": {}}
@@ -136,6 +145,8 @@ def main():
             if rep >= a.warmup:
                 ms.append(e0.elapsed_time(e1))
         return ms, out
+    if a.budget:
+        return budget_grid(a, pkg, params, wp, t, timed, d_tx, d_ty)
     if a.horizon:
         return horizon_grid(a, pkg, gd, wp, t, timed, d_tx, d_ty)
     if a.latency:
@@ -382,6 +393,44 @@ def plant_cost_legs(a, doc, legs):
                                  "parent_spread_ms": [min(par), max(par)], "median_inside_the_parent_spread": bool(min(par) <= np.median(new) <= max(par)),
                                  "median_not_above_the_parent_spread": bool(np.median(new) <= max(par))})
             print(leg, json.dumps({k: v for k, v in cost["legs"][leg][-1].items() if k != "runs"}), flush=True)
+
+
+def budget_grid(a, pkg, params, wp, t, timed, d_tx, d_ty):
+    import torch
+    budgets = [int(x) for x in a.budgets.split(",") if x]
+    n_b, n_cars, steps = len(budgets), (256 if a.cars == 4096 else a.cars), a.sweep_steps
+    B = n_b * n_cars
+    # column = budget * n_cars + car; car c of every budget: the same start
+    cars = np.tile(pkg.scenarios.track_starts(n_cars, params, wp, seed=127), (1, n_b))
+    d_budget = torch.from_numpy(np.repeat(np.array(budgets, dtype=np.int32), n_cars)).to(d_tx.device)
+    d_cars = t(cars)
+    doc = json.load(open(a.out)) if os.path.exists(a.out) else {}
+    grid = {"call": "mpc_drive_batch_device_fused_budget, hist given (the records say which messages the budget ended)", "B": B, "steps": steps, "budgets": budgets,
+            "cars_per_budget": n_cars, "timing": "median of reps runs after warmup runs, between two events", "start_modes": {}}
+    with pkg.BatchedMPC(params, B, device=0) as mpc:
+        for warm in (0, 1):
+            opts = mpc.drive_opts(warm_start=warm)
+            ms0, base = timed(lambda: mpc.drive_torch(d_cars.clone(), d_tx, d_ty, steps, opts=opts, fused=True))
+            ms, res = timed(lambda: mpc.drive_torch(d_cars.clone(), d_tx, d_ty, steps, opts=opts, fused=True, budget=d_budget))
+            hist = res["hist"].cpu().numpy().reshape(steps, 13, n_b, n_cars)
+            summ = res["summary"].cpu().numpy().reshape(8, n_b, n_cars)
+            bsum, bhist = base["summary"].cpu().numpy(), base["hist"].cpu().numpy()
+            leg = {"ms_median": float(np.median(ms)), "ms_min": float(min(ms)), "ms_max": float(max(ms)), "reps": a.reps, "warmup": a.warmup,
+                   "budget_null_same_cars": {"what": "the same call with budget = NULL: the _fused_plant form, the wave kernels or the staged lane kernel",
+                                             "ms_median": float(np.median(ms0)), "ms_min": float(min(ms0)), "ms_max": float(max(ms0)),
+                                             "iterations_per_message": float(bhist[:, 11].mean()), "share_of_cars_within_cte_limit": float((bsum[6] < 0).mean()),
+                                             "max_abs_cte_median": float(np.median(bsum[0]))},
+                   "cte_limit": opts.cte_limit, "drive_info": mpc.drive_info(), "rows": []}
+            for q, b in enumerate(budgets):
+                leg["rows"].append({"budget": b, "iterations_per_message": float(hist[:, 11, q].mean()), "share_of_messages_ended_by_the_budget": float((hist[:, 10, q] == 1).mean()),
+                                    "share_of_cars_within_cte_limit": float((summ[6, q] < 0).mean()), "max_abs_cte_median": float(np.median(summ[0, q])),
+                                    "first_step_off_the_road_median": float(np.median(summ[6, q][summ[6, q] >= 0])) if (summ[6, q] >= 0).any() else None})
+                print("warm %d" % warm, json.dumps(leg["rows"][-1]), flush=True)
+            print("warm %d: %d cars x %d messages, budget grid %.1f ms, budget = NULL %.1f ms" % (warm, B, steps, leg["ms_median"], leg["budget_null_same_cars"]["ms_median"]), flush=True)
+            grid["start_modes"]["warm" if warm else "cold"] = leg
+    doc.update({"tool": "tools/drive_bench.py --budget", "config": a.config, "device": torch.cuda.get_device_name(0), "grid": grid})
+    json.dump(doc, open(a.out, "w"), indent=1)
+    print("wrote", a.out)
 
 
 HORIZON_NS, HORIZON_DTS = (5, 7, 10, 15, 20, 25), (0.05, 0.1, 0.15, 0.2)
