@@ -12,7 +12,8 @@ The directory is called ``carnd-mpc-project_amd`` (not importable as written);
 """
 from ._abi import (MpcParams, MpcBatchStats, MpcWireTelemetry, MpcError, library, library_path, build_library,
                    params_default, params_from_json, inflight_advice, STATUS_NAMES, PRECISION_F32, PRECISION_F64,
-                   MpcWarmOpts, WARM_REC, warm_rows, warm_opts_default, warm_to_vars, MpcDriveOpts, drive_opts_default, drive_plant_default)
+                   MpcWarmOpts, WARM_REC, warm_rows, warm_opts_default, warm_to_vars, MpcDriveOpts, drive_opts_default, drive_plant_default,
+                   drive_noise_default, drive_noise_draw)
 from .solver import BatchedMPC
 from . import scenarios
 from . import sharding
@@ -20,4 +21,4 @@ from . import sharding
 __all__ = ["MpcParams", "MpcBatchStats", "MpcWireTelemetry", "MpcError", "library", "library_path", "build_library",
            "params_default", "params_from_json", "inflight_advice", "BatchedMPC", "scenarios", "sharding", "STATUS_NAMES",
            "PRECISION_F32", "PRECISION_F64", "MpcWarmOpts", "WARM_REC", "warm_rows", "warm_opts_default", "warm_to_vars",
-           "MpcDriveOpts", "drive_opts_default", "drive_plant_default"]
+           "MpcDriveOpts", "drive_opts_default", "drive_plant_default", "drive_noise_default", "drive_noise_draw"]

@@ -123,6 +123,12 @@ DRIVE_EXPORTS = ["mpc_drive_opts_default", "mpc_drive_batch_device", "mpc_drive_
                  "mpc_drive_plant_default", "mpc_drive_batch_device_plant", "mpc_drive_batch_device_fused_plant", "mpc_drive_batch_host_plant"]
 NPLANT = 6       # MPC_NPLANT: rows of a plant array, [NPLANT][ld] (the mpc_drive_*_plant entry points)
 PLANT_LF, PLANT_STEER_GAIN, PLANT_STEER_BIAS, PLANT_ACCEL_GAIN, PLANT_DRAG_SPEED, PLANT_DRIFT = range(NPLANT)
+# ... and include/mpc_amd_noise.h (the track drive under noise; tests/test_drive_noise.py)
+NOISE_EXPORTS = ["mpc_drive_batch_device_noise", "mpc_drive_batch_device_fused_noise", "mpc_drive_batch_host_noise", "mpc_drive_noise_default",
+                 "mpc_drive_noise_draw", "mpc_debug_philox4x32", "mpc_debug_drive_noise_device"]
+NNOISE = 7       # MPC_NNOISE: rows of a noise array, [NNOISE][ld] (the mpc_drive_*_noise entry points)
+NOISE_SEED, NOISE_POS, NOISE_PSI, NOISE_SPEED, NOISE_STEER, NOISE_DRIFT, NOISE_DROP = range(NNOISE)
+DRAW_Z_X, DRAW_Z_Y, DRAW_Z_PSI, DRAW_Z_SPEED, DRAW_Z_STEER, DRAW_Z_DRIFT, DRAW_U_DROP = range(7)      # MPC_DRAW_*: rows of a draw
 NLATENCY = 3     # MPC_NLATENCY: rows of a latency array, [NLATENCY][ld] (the mpc_drive_*_latency entry points)
 LATENCY_COMP, LATENCY_SUB_OLD, LATENCY_SUB_NEW = range(NLATENCY)
 DRIVE_MAX_TRACK, DRIVE_NSUM, DRIVE_REC = 4096, 8, 13      # MPC_DRIVE_MAX_TRACK, rows of summary [NSUM][ld], rows of a step of hist [REC][ld]
@@ -258,6 +264,16 @@ def library():
     for name in ("mpc_solve_batch_device", "mpc_solve_batch_host"):
         at = len(H) + 5 + 2           # (state .. weights, model, horizon)
         getattr(L, name + "_budget").argtypes = getattr(L, name + "_warm_horizon").argtypes[:at] + [DP] + getattr(L, name + "_warm_horizon").argtypes[at:]
+    # ... and the drive's _noise forms (include/mpc_amd_noise.h): the _budget form plus `noise` (one pointer) directly behind `plant` and
+    # `seen` (one pointer) directly behind `hist`
+    for name in ("mpc_drive_batch_host", "mpc_drive_batch_device", "mpc_drive_batch_device_fused"):
+        a = getattr(L, name + "_budget").argtypes
+        at = len(drive_head) + 5      # (model, horizon, budget, latency, plant)
+        getattr(L, name + "_noise").argtypes = a[:at] + [DP] + a[at:at + 4] + [DP] + a[at + 4:]      # (opts, warm_opts, summary, hist | seen)
+    L.mpc_drive_noise_default.argtypes = [DP]
+    L.mpc_drive_noise_draw.argtypes = [C.c_double, C.c_int32, DP]
+    L.mpc_debug_philox4x32.argtypes = [DP, DP, DP]
+    L.mpc_debug_drive_noise_device.argtypes = [C.c_void_p, I64, DP, DP, DP, C.c_void_p]
     L.mpc_drive_plant_default.argtypes = [C.POINTER(MpcParams), DP]
     L.mpc_drive_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.mpc_solve_batch_device_f32.argtypes = L.mpc_solve_batch_device.argtypes      # (the same pointers, to floats)
@@ -338,6 +354,35 @@ def drive_plant_default(params, B=None, model=None):
     if model is not None:
         a[PLANT_LF] = np.asarray(model, dtype=np.float64)[MODEL_LF]
     return a
+
+
+def drive_noise_default(B=None, seeds=None):
+    """mpc_drive_noise_default (needs no device): the zero column -- seed 0, every sigma 0, p_drop 0 -- under which a drive with
+    ``noise=`` is the drive without.  B = None: the column [NNOISE]; else an array [NNOISE, B] of it, row NOISE_SEED from ``seeds`` [B]
+    (integers in [0, 2**53)) if given: the array a caller then sets the sigma rows of."""
+    import numpy as np
+    col = np.ones(NNOISE)
+    check(library().mpc_drive_noise_default(col.ctypes.data), "mpc_drive_noise_default")
+    if B is None and seeds is None:
+        return col
+    if B is None:
+        B = len(seeds)
+    a = np.ascontiguousarray(np.repeat(col[:, None], int(B), axis=1))
+    if seeds is not None:
+        sd = np.asarray(seeds)
+        if sd.shape != (int(B),) or (sd < 0).any() or (sd >= 2 ** 53).any() or (sd != np.floor(sd)).any():
+            raise ValueError("seeds must be B integers in [0, 2**53)")
+        a[NOISE_SEED] = sd.astype(np.float64)
+    return a
+
+
+def drive_noise_draw(seed, step):
+    """mpc_drive_noise_draw (needs no device): the seven values car `seed` draws at message `step` -- z_x, z_y, z_psi, z_speed,
+    z_steer, z_drift, u_drop (rows DRAW_*)."""
+    import numpy as np
+    out = np.empty(7)
+    check(library().mpc_drive_noise_draw(float(seed), int(step), out.ctypes.data), "mpc_drive_noise_draw")
+    return out
 
 
 def inflight_advice(params, B):

@@ -158,6 +158,157 @@ MPC_HD DriveLatency drive_latency_of(const MpcDriveOpts &O, const double *latenc
   return L;
 }
 
+/* ---- noise: what a car's sensors, actuator and link add per message (include/mpc_amd_noise.h) ----------------------------------------
+ * Philox4x32-10 as published (Salmon, Moraes, Dror, Shaw, SC'11): multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 /
+ * 0xBB67AE85, ten rounds; counter-based, no state.  Plain C++: the high word of a product is __umulhi on the device and the upper half
+ * of a 64-bit product on the host. */
+MPC_HD uint32_t philox_mulhi(uint32_t a, uint32_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __umulhi(a, b);
+#else
+  return (uint32_t)(((uint64_t)a * (uint64_t)b) >> 32);
+#endif
+}
+MPC_HD void philox4x32(const uint32_t *ctr, const uint32_t *key, uint32_t *out) {
+  uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3], k0 = key[0], k1 = key[1];
+  MPC_UNROLL
+  for (int r = 0; r < 10; r++) {
+    const uint32_t hi0 = philox_mulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = philox_mulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+/* a word as a uniform inside (0, 1): (r + 0.5) * 2^-32, exact in a double */
+MPC_HD double drive_uniform(uint32_t r) { return ((double)r + 0.5) * (1.0 / 4294967296.0); }
+/* a normal pair from two words (Box-Muller on the project's own flog and fsincos) */
+MPC_HD void drive_normal_pair(uint32_t ra, uint32_t rb, double *za, double *zb) {
+  const double ua = drive_uniform(ra), ub = drive_uniform(rb);
+  const double rad = sqrt(-2.0 * flog(ua));
+  double sn, cs;
+  fsincos(6.283185307179586 * ub, &sn, &cs);
+  *za = rad * cs;
+  *zb = rad * sn;
+}
+/* The rows of one draw, in the order of the blocks */
+enum { DRIVE_Z_X = 0, DRIVE_Z_Y, DRIVE_Z_PSI, DRIVE_Z_SPEED, DRIVE_Z_STEER, DRIVE_Z_DRIFT, DRIVE_U_DROP, DRIVE_NDRAW };
+/* THE draw of a car with seed s = k1 * 2^32 + k0 at message `step` (0-based): two blocks, key (k0, k1), counter (step, block, 0, 0).
+ * Block 0, pairs (r0, r1), (r2, r3): z_x, z_y, z_psi, z_speed.  Block 1: pair (r0, r1): z_steer, z_drift; r2: u_drop; r3 is not used.
+ * (seed, step) only: no instance index, batch size, leading dimension, lane or launch form enters.  The only place this is spelled;
+ * every kernel and every CPU build calls it.  (Inlined like everything here: behind a call it cost every DRIVE build of the lane
+ * kernel 16 B of scratch for the call's own frame, more than its temporaries cost inline; profiles/drive_noise_resources.md.) */
+struct DriveDraw { double v[DRIVE_NDRAW]; };
+MPC_HD DriveDraw drive_noise_draw(uint32_t k0, uint32_t k1, int32_t step) {
+  DriveDraw d;
+  const uint32_t key[2] = {k0, k1};
+  uint32_t ctr[4] = {(uint32_t)step, 0u, 0u, 0u}, r[4];
+  philox4x32(ctr, key, r);
+  drive_normal_pair(r[0], r[1], d.v + DRIVE_Z_X, d.v + DRIVE_Z_Y);
+  drive_normal_pair(r[2], r[3], d.v + DRIVE_Z_PSI, d.v + DRIVE_Z_SPEED);
+  ctr[1] = 1u;
+  philox4x32(ctr, key, r);
+  drive_normal_pair(r[0], r[1], d.v + DRIVE_Z_STEER, d.v + DRIVE_Z_DRIFT);
+  d.v[DRIVE_U_DROP] = drive_uniform(r[2]);
+  return d;
+}
+/* ... for a seed as a column holds it (drive_seed_ok), into out7 */
+MPC_HD void drive_noise_draw(double seed, int32_t step, double *out7) {
+  const uint64_t s = (uint64_t)seed;
+  const DriveDraw d = drive_noise_draw((uint32_t)s, (uint32_t)(s >> 32), step);
+  MPC_UNROLL
+  for (int q = 0; q < DRIVE_NDRAW; q++) out7[q] = d.v[q];
+}
+/* a seed as the column holds it: a double holding an integer, 0 <= s < 2^53 */
+MPC_HD bool drive_seed_ok(double s) { return s >= 0.0 && s < 9007199254740992.0 && s == rint(s); }
+
+/* Car i's column of noise [MPC_NNOISE][ld] (the mpc_drive_*_noise entry points), or with noise == nullptr the zero column.  A column
+ * that cannot be used -- a value that is not finite, a sigma below 0, p_drop outside [0, 1], a seed that is no integer value or is
+ * outside [0, 2^53) -- : the zero column and ok = false, which drive_step_instance turns into a status (the rule of a plant column). */
+struct DriveNoise {
+  uint32_t k0, k1;
+  double pos, psi, speed, steer, drift, drop;
+  bool ok;
+  MPC_HD bool senses() const { return pos != 0.0 || psi != 0.0 || speed != 0.0; }
+  MPC_HD bool acts() const { return steer != 0.0 || drift != 0.0 || drop != 0.0; }
+};
+MPC_HD DriveNoise drive_noise_of(const double *noise, int64_t ld, int64_t i) {
+  DriveNoise d{0u, 0u, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, true};
+  if (noise) {
+    double c[MPC_NNOISE];
+    bool ok = true;
+    MPC_UNROLL
+    for (int q = 0; q < MPC_NNOISE; q++) { c[q] = noise[q * ld + i]; ok = ok && drive_finite(c[q]); }
+    MPC_UNROLL
+    for (int q = MPC_NOISE_POS; q <= MPC_NOISE_DRIFT; q++) ok = ok && c[q] >= 0.0;
+    ok = ok && c[MPC_NOISE_DROP] >= 0.0 && c[MPC_NOISE_DROP] <= 1.0 && drive_seed_ok(c[MPC_NOISE_SEED]);
+    d.ok = ok;
+    if (ok) {
+      const uint64_t s = (uint64_t)c[MPC_NOISE_SEED];
+      d.k0 = (uint32_t)s; d.k1 = (uint32_t)(s >> 32);
+      d.pos = c[MPC_NOISE_POS]; d.psi = c[MPC_NOISE_PSI]; d.speed = c[MPC_NOISE_SPEED];
+      d.steer = c[MPC_NOISE_STEER]; d.drift = c[MPC_NOISE_DRIFT]; d.drop = c[MPC_NOISE_DROP];
+    }
+  }
+  return d;
+}
+
+/* What the handler is told about car i at message `step`: seen6 [6][lds], column i <- the car's rows 0..3 plus sigma * z, rows 4 / 5
+ * as they are; seen_out (this step's block of the caller's `seen`, [4][ld]) or nullptr gets rows 0..3.  A row whose sigma is exactly 0
+ * is copied, not added to (the zero column hands the car's own bits on, and draws nothing); sigma * z is a statement of its own, so
+ * the sum is the rounded sum of the rounded product.  With sigma_speed > 0 the reading is max(0, speed + sigma * z): noise does not
+ * manufacture a negative speed, which the handler would call a defect.  psi is not normalised: the handler does that. */
+MPC_HD void drive_seen(const DriveNoise &nz, int32_t step, const double *car, int64_t ld, int64_t i, double *seen6, int64_t lds, double *seen_out) {
+  double c[6];
+  MPC_UNROLL
+  for (int q = 0; q < 6; q++) c[q] = car[q * ld + i];
+  if (nz.senses()) {
+    const DriveDraw dr = drive_noise_draw(nz.k0, nz.k1, step);
+    const double *z = dr.v;
+    if (nz.pos != 0.0) {
+      const double dx = nz.pos * z[DRIVE_Z_X], dy = nz.pos * z[DRIVE_Z_Y];
+      c[0] = c[0] + dx;
+      c[1] = c[1] + dy;
+    }
+    if (nz.psi != 0.0) {
+      const double dp = nz.psi * z[DRIVE_Z_PSI];
+      c[2] = c[2] + dp;
+    }
+    if (nz.speed != 0.0) {
+      const double dv = nz.speed * z[DRIVE_Z_SPEED];
+      const double v = c[3] + dv;
+      c[3] = v < 0.0 ? 0.0 : v;
+    }
+  }
+  MPC_UNROLL
+  for (int q = 0; q < 6; q++) seen6[q * lds + i] = c[q];
+  if (seen_out) {
+    MPC_UNROLL
+    for (int q = 0; q < 4; q++) seen_out[q * ld + i] = c[q];
+  }
+}
+
+/* The plant column in force between message `step` and the next: bias + sigma_steer * z_steer, drift + sigma_drift * z_drift, on top
+ * of the car's column or the default column, each a statement of its own and skipped where its sigma is 0 (drive_substep's rule:
+ * what stood there before contracts as it did).  *dropped: u_drop < p_drop, the reply of this message never reaches the car. */
+MPC_HD DrivePlantVals drive_plant_perturbed(DrivePlantVals pv, const DriveNoise &nz, int32_t step, bool *dropped) {
+  *dropped = false;
+  if (nz.acts()) {
+    const DriveDraw dr = drive_noise_draw(nz.k0, nz.k1, step);
+    const double *z = dr.v;
+    if (nz.steer != 0.0) {
+      const double db = nz.steer * z[DRIVE_Z_STEER];
+      pv.bias = pv.bias + db;
+    }
+    if (nz.drift != 0.0) {
+      const double dd = nz.drift * z[DRIVE_Z_DRIFT];
+      pv.drift = pv.drift + dd;
+    }
+    *dropped = z[DRIVE_U_DROP] < nz.drop;
+  }
+  return pv;
+}
+
 /* The summary rows of one car (MPC_DRIVE_SUM_*), step `step` (0-based) folded in; dk = the progress of this step (0 at step 0).
  * A not-a-number never wins a maximum or the minimum. */
 MPC_HD void drive_summary(int step, double *sum, double cte0, double epsi0, double speed, int dk, int status, double cte_limit) {
@@ -181,14 +332,15 @@ MPC_HD void drive_summary(int step, double *sum, double cte0, double epsi0, doub
  * the window index of this step and of the one before; sub_old / sub_new: the car's substep counts (its latency column's, or the
  * call's); summary [MPC_DRIVE_NSUM][ld], rec = this step's block of hist [MPC_DRIVE_REC][ld] or nullptr, status / iters (or nullptr)
  * per car: worst code, summed iterations (mpc::RolloutCar).  m: the plant's model values, as above.  pv: the plant's own values
- * (drive_plant_vals_of).  A car whose plant column could not be used carries a status at every step: a step the handler ended
+ * (drive_plant_vals_of).  nz: the car's noise values (drive_noise_of): what this message adds to the plant column in force, and whether
+ * its reply arrives.  A car whose plant column or noise column could not be used carries a status at every step: a step the handler ended
  * SUCCESS or ACCEPTABLE is recorded, summed and folded as INFEASIBLE; st_step itself, which the warm rule reads, is the caller's and
  * stays. */
 template <class MV>
-MPC_HD void drive_step_instance(const MpcParams &P, const MV &m, const DrivePlantVals &pv, const MpcDriveOpts &O, int sub_old, int sub_new, int64_t i, int64_t ld,
-                                int step, int n_track, double *car, const double *cmd, const double *pre, int64_t ldp, int32_t st_step, int32_t it_step, int k,
-                                int k_prev, double *summary, double *rec, int32_t *status, int32_t *iters) {
-  if (!pv.ok && (st_step == MPC_STATUS_SUCCESS || st_step == MPC_STATUS_ACCEPTABLE)) st_step = MPC_STATUS_INFEASIBLE;
+MPC_HD void drive_step_instance(const MpcParams &P, const MV &m, const DrivePlantVals &pv, const DriveNoise &nz, const MpcDriveOpts &O, int sub_old, int sub_new,
+                                int64_t i, int64_t ld, int step, int n_track, double *car, const double *cmd, const double *pre, int64_t ldp, int32_t st_step,
+                                int32_t it_step, int k, int k_prev, double *summary, double *rec, int32_t *status, int32_t *iters) {
+  if (!(pv.ok && nz.ok) && (st_step == MPC_STATUS_SUCCESS || st_step == MPC_STATUS_ACCEPTABLE)) st_step = MPC_STATUS_INFEASIBLE;
   double c[6], sum[MPC_DRIVE_NSUM] = {};
   MPC_UNROLL
   for (int q = 0; q < 6; q++) c[q] = car[q * ld + i];
@@ -216,12 +368,22 @@ MPC_HD void drive_step_instance(const MpcParams &P, const MV &m, const DrivePlan
     if (step > 0) total = iters[i];
     iters[i] = RolloutCar::sum_iters(step, total, it_step);
   }
-  drive_plant(P, m, pv, c, cs, ct, sub_old, sub_new, O.h);
+  /* (a reply that never arrives is a reply that is not finite to the plant: the command in force stays; the record above holds what was sent) */
+  bool dropped;
+  const DrivePlantVals pn = drive_plant_perturbed(pv, nz, step, &dropped);
+  drive_plant(P, m, pn, c, dropped ? NAN : cs, ct, sub_old, sub_new, O.h);
   MPC_UNROLL
   for (int q = 0; q < 6; q++) car[q * ld + i] = c[q];
 }
-/* The short call forms, as for drive_plant: without plant values (the default column of `m`), without counts (the call's), without `m`
- * (P itself); each forwards to the one body above. */
+/* The short call forms, as for drive_plant: without noise values (the zero column), without plant values (the default column of `m`),
+ * without counts (the call's), without `m` (P itself); each forwards to the one body above. */
+template <class MV>
+MPC_HD void drive_step_instance(const MpcParams &P, const MV &m, const DrivePlantVals &pv, const MpcDriveOpts &O, int sub_old, int sub_new, int64_t i, int64_t ld,
+                                int step, int n_track, double *car, const double *cmd, const double *pre, int64_t ldp, int32_t st_step, int32_t it_step, int k,
+                                int k_prev, double *summary, double *rec, int32_t *status, int32_t *iters) {
+  drive_step_instance(P, m, pv, drive_noise_of(nullptr, 0, 0), O, sub_old, sub_new, i, ld, step, n_track, car, cmd, pre, ldp, st_step, it_step, k, k_prev, summary,
+                      rec, status, iters);
+}
 template <class MV>
 MPC_HD void drive_step_instance(const MpcParams &P, const MV &m, const MpcDriveOpts &O, int sub_old, int sub_new, int64_t i, int64_t ld, int step, int n_track,
                                 double *car, const double *cmd, const double *pre, int64_t ldp, int32_t st_step, int32_t it_step, int k, int k_prev,

@@ -264,7 +264,38 @@ struct MpcDrivePart {
   double *summary, *rec;          /* [MPC_DRIVE_NSUM][ldo]; hist [steps][MPC_DRIVE_REC][ldo] or nullptr */
   const double *latency;          /* [MPC_NLATENCY][ldo] or nullptr */
   const double *plant;            /* [MPC_NPLANT][ldo] or nullptr */
+  /* noise (mpc_drive_batch_device_fused_noise): the car's column of [MPC_NNOISE][ldo], or nullptr -- the zero column.  Read by instance
+   * index where the stepwise loop's two kernels read it: at the take, where mpc::drive_seen writes what the handler is told into the
+   * car's column of the handle's seen rows ([6][ldo] behind cmd in the handle's drive rows, drive_seen6; with both pointers nullptr the
+   * pre-solve half reads the car itself, as it did before these pointers existed) and of this step's block of seen ([steps][4][ldo] or
+   * nullptr), and at the hand-over, where mpc::drive_step_instance perturbs the plant column and drops replies.  Pointers, no template
+   * argument; the seen rows are found from cmd, not carried as a third pointer (a pointer held across the sweeps costs the build registers). */
+  const double *noise = nullptr;
+  double *seen = nullptr;
 };
+/* THE layout of the handle's drive rows (h->d_drive), in rows of ld doubles: the one statement of it, read by drive_rows (the size),
+ * both drive forms (the pointers) and the lane kernel (the seen rows, found from cmd).  A new row goes in here and nowhere else. */
+struct DriveRows {
+  static constexpr int kPtsx = 0, kPtsy = kPtsx + mpc::RUN_MAX_PTS;      /* the window's waypoints, [RUN_MAX_PTS][ld] each */
+  static constexpr int kCmd = kPtsy + mpc::RUN_MAX_PTS;                  /* the reply, [2][ld] */
+  static constexpr int kIdx = kCmd + 2;                                  /* the stepwise loop's two window-index rows, [2][ld] int32: one row of doubles */
+  static constexpr int kComp = kIdx + 1;                                 /* the stepwise loop's comp row of a latency call, [ld] */
+  static constexpr int kSeen = kComp + 1;                                /* what the handler is told in a noise call, [6][ld] */
+  static constexpr int kRows = kSeen + 6;
+  static_assert(2 * sizeof(int32_t) == sizeof(double), "two index rows are one row of doubles");
+  double *base;
+  int64_t ld;
+  __host__ __device__ double *at(int row) const { return base + (int64_t)row * ld; }
+  __host__ __device__ double *ptsx() const { return at(kPtsx); }
+  __host__ __device__ double *ptsy() const { return at(kPtsy); }
+  __host__ __device__ double *cmd() const { return at(kCmd); }
+  __host__ __device__ int32_t *idx(int which) const { return (int32_t *)at(kIdx) + (int64_t)which * ld; }
+  __host__ __device__ double *comp() const { return at(kComp); }
+  __host__ __device__ double *seen6() const { return at(kSeen); }
+  static size_t bytes(int64_t ld) { return sizeof(double) * (size_t)kRows * (size_t)ld; }
+};
+/* the handle's seen rows [6][ld] from the reply rows of the same block (the lane kernel carries cmd, not the block's base) */
+__host__ __device__ static inline double *drive_seen6(double *cmd, int64_t ld) { return DriveRows{cmd - (int64_t)DriveRows::kCmd * ld, ld}.seen6(); }
 
 template <bool ON, class Part> struct MpcPartIf : Part {};
 template <class Part> struct MpcPartIf<false, Part> {};
@@ -533,7 +564,7 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
                 const mpc::DriveLatency dl = mpc::drive_latency_of(T.O, T.latency, ldo, i);
                 sub_old = dl.sub_old; sub_new = dl.sub_new;
               }
-              mpc::drive_step_instance(P, mv, mpc::drive_plant_vals_of(P, mv, T.plant, ldo, i), T.O, sub_old, sub_new, i, ldo, step, T.n_track, T.car, T.cmd, T.pre, ld,
+              mpc::drive_step_instance(P, mv, mpc::drive_plant_vals_of(P, mv, T.plant, ldo, i), mpc::drive_noise_of(T.noise, ldo, i), T.O, sub_old, sub_new, i, ldo, step, T.n_track, T.car, T.cmd, T.pre, ld,
                                        fin_status, S.iters + it_total, drive_k, drive_k_prev, T.summary, T.rec ? T.rec + (int64_t)step * MPC_DRIVE_REC * ldo : nullptr, T.status, T.iters);
             } else {
             double *o = T.hist + (int64_t)step * T.hist_step + i;
@@ -618,7 +649,14 @@ __global__ __launch_bounds__(kBlock, 1) void mpc_solve_kernel(
               mpc::drive_window_points(T.track_x, T.track_y, T.n_track, drive_k, T.O.npts, T.ptsx, T.ptsy, ldo, i);
               mpc::RunComp lc{false, T.O.extra_latency};
               if (T.latency) lc = mpc::RunComp{true, mpc::drive_latency_of(T.O, T.latency, ldo, i).comp};
-              (void)mpc::run_pre_instance<true>(P, drive_model_vals<MODEL, HORIZON>(P, T, i), i, ldo, T.O.npts, T.car, lc, T.ptsx, T.ptsy, T.pre, ld);
+              /* (a noise call: the handler is told the car's column of seen6, written here from the car and this message's draw) */
+              const double *tel = T.car;
+              if (T.noise || T.seen) {
+                double *seen6 = drive_seen6(T.cmd, ldo);
+                mpc::drive_seen(mpc::drive_noise_of(T.noise, ldo, i), step, T.car, ldo, i, seen6, ldo, T.seen ? T.seen + (int64_t)step * 4 * ldo : nullptr);
+                tel = seen6;
+              }
+              (void)mpc::run_pre_instance<true>(P, drive_model_vals<MODEL, HORIZON>(P, T, i), i, ldo, T.O.npts, tel, lc, T.ptsx, T.ptsy, T.pre, ld);
               mpc::gather_instance(P, i, ld, T.pre + mpc::RUN_PRE_STATE * ld, T.pre + mpc::RUN_PRE_COEFFS * ld, weights, st, cf, w);
               ylo_in = (R)T.pre[mpc::RUN_PRE_YAW_LO * ld + i]; yhi_in = (R)T.pre[mpc::RUN_PRE_YAW_HI * ld + i];
             } else {
@@ -1139,12 +1177,16 @@ __global__ __launch_bounds__(256) void mpc_rollout_step_kernel(int64_t B, int64_
 __global__ __launch_bounds__(256) void mpc_drive_sense_kernel(int64_t B, int64_t ld, int npts, const double *__restrict__ car,
                                                               const double *__restrict__ track_x, const double *__restrict__ track_y,
                                                               int n_track, double *__restrict__ ptsx, double *__restrict__ ptsy,
-                                                              int32_t *__restrict__ k_now) {
+                                                              int32_t *__restrict__ k_now, const double *__restrict__ noise, int step,
+                                                              double *__restrict__ seen6, double *__restrict__ seen) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B) return;
   const int k = mpc::drive_window(track_x, track_y, n_track, car[i], car[ld + i]);
   mpc::drive_window_points(track_x, track_y, n_track, k, npts, ptsx, ptsy, ld, i);
   k_now[i] = k;
+  /* a noise call: what the handler is told about the car at this message (mpc::drive_seen), into the handle's rows seen6 [6][ld] and
+   * this step's block of the caller's seen [4][ld] (or nullptr).  The window above is the TRUE car's. */
+  if (seen6) mpc::drive_seen(mpc::drive_noise_of(noise, ld, i), step, car, ld, i, seen6, ld, seen);
 }
 
 /* Plant and summary, the one kernel of every drive entry point: the step's record and summary rows, the car's worst status and summed
@@ -1155,7 +1197,9 @@ __global__ __launch_bounds__(256) void mpc_drive_sense_kernel(int64_t B, int64_t
  *     column that cannot be used: the handle's values (mpc::model_vals_of; the handler has reported the car INFEASIBLE); nullptr: the
  *     handle's values.
  *   plant [MPC_NPLANT][ld]: what the car is moved with (mpc::drive_plant_vals_of: checked; a column that cannot be used becomes a
- *     status); nullptr: the default column, the plant of the entry points without `plant` bit for bit. */
+ *     status); nullptr: the default column, the plant of the entry points without `plant` bit for bit.
+ *   noise [MPC_NNOISE][ld]: what message `step` adds to the plant column in force and whether its reply arrives (mpc::drive_noise_of:
+ *     checked; a column that cannot be used becomes a status); nullptr: the zero column, which draws nothing. */
 __global__ __launch_bounds__(256) void mpc_drive_plant_kernel(const MpcParams P, const MpcDriveOpts O, int64_t B, int64_t ld, int step, int n_track,
                                                               double *__restrict__ car, const double *__restrict__ cmd,
                                                               const double *__restrict__ pre, int64_t ldp, const int32_t *__restrict__ st_step,
@@ -1163,7 +1207,7 @@ __global__ __launch_bounds__(256) void mpc_drive_plant_kernel(const MpcParams P,
                                                               const int32_t *k_prev, double *__restrict__ summary,
                                                               double *__restrict__ rec, int32_t *__restrict__ status, int32_t *__restrict__ iters,
                                                               const double *__restrict__ latency, const MpcModelPart W,
-                                                              const double *__restrict__ plant) {
+                                                              const double *__restrict__ plant, const double *__restrict__ noise) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B) return;
   int sub_old = O.sub_old, sub_new = O.sub_new;
@@ -1172,7 +1216,7 @@ __global__ __launch_bounds__(256) void mpc_drive_plant_kernel(const MpcParams P,
     sub_old = dl.sub_old; sub_new = dl.sub_new;
   }
   const mpc::ModelVals mv = W.model ? mpc::model_vals_of(P, W.model, W.ld_model, i) : mpc::ModelVals::of(P);
-  mpc::drive_step_instance(P, mv, mpc::drive_plant_vals_of(P, mv, plant, ld, i), O, sub_old, sub_new, i, ld, step, n_track, car, cmd, pre, ldp, st_step[i],
+  mpc::drive_step_instance(P, mv, mpc::drive_plant_vals_of(P, mv, plant, ld, i), mpc::drive_noise_of(noise, ld, i), O, sub_old, sub_new, i, ld, step, n_track, car, cmd, pre, ldp, st_step[i],
                            it_step[i], k_now[i], k_prev[i], summary, rec, status, iters);
 }
 /* What the stepwise loop's handler compensates for, per car: comp [ld] <- row MPC_LATENCY_COMP of the car's column, not-a-number for
@@ -1182,6 +1226,24 @@ __global__ __launch_bounds__(256) void mpc_drive_comp_kernel(const MpcDriveOpts 
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B) return;
   comp[i] = mpc::drive_latency_of(O, latency, ld, i).comp;
+}
+/* mpc_debug_drive_noise_device: mpc::drive_noise_draw for n (seed, step) pairs, a pair per lane; out [7][n].  A pair the host
+ * evaluation refuses gives not-a-number. */
+__global__ __launch_bounds__(256) void mpc_debug_drive_noise_kernel(int64_t n, const double *__restrict__ seed, const int32_t *__restrict__ step,
+                                                                    double *__restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double z[mpc::DRIVE_NDRAW];
+  const double sd = seed[i];
+  const int32_t t = step[i];
+  if (mpc::drive_finite(sd) && mpc::drive_seed_ok(sd) && t >= 0) {
+    mpc::drive_noise_draw(sd, t, z);
+  } else {
+    MPC_UNROLL
+    for (int q = 0; q < mpc::DRIVE_NDRAW; q++) z[q] = NAN;
+  }
+  MPC_UNROLL
+  for (int q = 0; q < mpc::DRIVE_NDRAW; q++) out[q * n + i] = z[q];
 }
 
 /* The certificate of a stored point (mpc_certify_batch_*), one instance per lane: mpc::certify_batch_instance of mpc_core.h.  A lane
@@ -2106,6 +2168,9 @@ struct CallExtras {
   const int32_t *budget = nullptr;    /* a budget call (include/mpc_amd_budget.h; fp64 handles, no SOC): [ld] like `horizon`, and dispatched like a horizon call -- `horizon` may be NULL */
   const double *latency = nullptr;   /* a latency call (fp64 handles): the telemetry handler's comp [ld]; the drive's [MPC_NLATENCY][ld] */
   const double *plant = nullptr;     /* a plant call (the drive, fp64 handles): [MPC_NPLANT][ld], what the cars are moved with */
+  const double *noise = nullptr;     /* a noise call (the drive, include/mpc_amd_noise.h): [MPC_NNOISE][ld], what every message adds to what the handler is told and to the plant */
+  double *seen = nullptr;            /* ... and its record of what the handler was told: [steps][4][ld] */
+  bool senses() const { return noise != nullptr || seen != nullptr; }      /* the handler reads the handle's `seen` rows, not the car */
   const double *run_weights = nullptr;   /* run() / telemetry only (the drive loop): per-instance weights of the solve, [MPC_NW][io_stride] like the rows run() solves from */
   bool lane_rows() const { return horizon != nullptr || budget != nullptr; }      /* the call runs the lane kernel's per-lane-rows (HORIZON) build */
   bool model_call() const { return model != nullptr || lane_rows(); }
@@ -3085,11 +3150,11 @@ static int drive_args(const MpcHandle *h, int64_t B, int64_t ld, int steps, cons
   return MPC_OK;
 }
 
-/* the handle's rows both forms work in: the window rows and the reply, the stepwise loop's two index rows and its comp row, the warm buffer of a warm call, and the caller's weights copied
- * to the handle's stride (*w_out; NULL without weights) */
+/* the handle's rows both forms work in: the window rows and the reply, the stepwise loop's two index rows and its comp row, the six rows of what the handler is told in a
+ * noise call (DriveRows), the warm buffer of a warm call, and the caller's weights copied to the handle's stride (*w_out; NULL without weights) */
 static int drive_rows(MpcHandle *h, int64_t B, int64_t ld, bool warm, const double *weights, hipStream_t s, const double **w_out) {
   const int64_t S = h->io_stride;
-  MPC_TRY(grow_dev(&h->d_drive, &h->drive_bytes, sizeof(double) * (size_t)((2 * mpc::RUN_MAX_PTS + 3) * ld) + sizeof(int32_t) * (size_t)(2 * ld)));
+  MPC_TRY(grow_dev(&h->d_drive, &h->drive_bytes, DriveRows::bytes(ld)));
   if (warm) MPC_TRY(ensure_dev(&h->d_warm, sizeof(double) * (size_t)mpc_warm_rows(h->params.N) * (size_t)S));
   *w_out = nullptr;
   if (weights) {
@@ -3107,36 +3172,39 @@ static int drive_rows(MpcHandle *h, int64_t B, int64_t ld, bool warm, const doub
  * x.latency (device, [MPC_NLATENCY][ld]): one more kernel first, the comp row the handler takes (not-a-number for a column that cannot
  * be used); the handler is the telemetry _latency call on it, with or without model.
  * x.plant (device, [MPC_NPLANT][ld]): the handler's calls are what they are without it.
+ * x.noise (device, [MPC_NNOISE][ld]) or x.seen (device, [steps][4][ld]): the sense kernel also writes what the handler is told into the
+ * handle's seen rows, and the handler is pointed at those instead of the car -- the same handler, on the same dispatch.
  * The plant kernel is one, and takes the caller's latency, model and plant as they came, each an array or nullptr. */
 static int drive_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y, int n_track,
                       const double *weights, const MpcDriveOpts &O, CallExtras x, double *summary, double *hist, int32_t *status,
                       int32_t *iters, void *stream_) {
   MPC_ON_DEVICE(h);
   const int64_t S = h->io_stride;
-  const int P8 = mpc::RUN_MAX_PTS;
   hipStream_t s = (hipStream_t)stream_;
   MPC_TRY(drive_rows(h, B, ld, x.warm, weights, s, &x.run_weights));
   MPC_TRY(ensure_dev(&h->d_rstat, sizeof(int32_t) * S));
-  double *ptsx = h->d_drive, *ptsy = ptsx + P8 * ld, *cmd = ptsy + P8 * ld;
-  int32_t *kbuf = (int32_t *)(cmd + 2 * ld);
+  const DriveRows R{h->d_drive, ld};
+  double *ptsx = R.ptsx(), *ptsy = R.ptsy(), *cmd = R.cmd();
+  double *seen6 = x.senses() ? R.seen6() : nullptr;
   const unsigned grid = (unsigned)((B + 255) / 256);
   const double *latency = x.latency;
   if (latency) {
-    double *comp = (double *)(kbuf + 2 * ld);
+    double *comp = R.comp();
     hipLaunchKernelGGL(mpc_drive_comp_kernel, dim3(grid), dim3(256), 0, s, O, B, ld, latency, comp);
     MPC_HIP_CHECK(hipGetLastError());
     x.latency = comp;                              /* what run_impl takes: the handler's comp [ld] */
   }
   for (int t = 0; t < steps; t++) {
     /* (the first step has no step before it: it is handed its own row, and mpc::drive_step_instance does not look at the value) */
-    int32_t *k_now = kbuf + (int64_t)(t & 1) * ld, *k_prev = t == 0 ? k_now : kbuf + (int64_t)((t & 1) ^ 1) * ld;
-    hipLaunchKernelGGL(mpc_drive_sense_kernel, dim3(grid), dim3(256), 0, s, B, ld, (int)O.npts, car, track_x, track_y, n_track, ptsx, ptsy, k_now);
+    int32_t *k_now = R.idx(t & 1), *k_prev = t == 0 ? k_now : R.idx((t & 1) ^ 1);
+    hipLaunchKernelGGL(mpc_drive_sense_kernel, dim3(grid), dim3(256), 0, s, B, ld, (int)O.npts, car, track_x, track_y, n_track, ptsx, ptsy, k_now, x.noise, t, seen6,
+                       x.seen ? x.seen + (int64_t)t * 4 * ld : nullptr);
     MPC_HIP_CHECK(hipGetLastError());
     x.w = WarmIO{t == 0 ? nullptr : h->d_warm, h->d_rstat, h->d_warm, S, x.w.wopts, 0};
-    MPC_TRY(run_impl(h, B, ld, O.npts, car, true, O.extra_latency, ptsx, ptsy, nullptr, cmd, nullptr, h->d_rstat, h->d_iters, nullptr, stream_, x));
+    MPC_TRY(run_impl(h, B, ld, O.npts, seen6 ? seen6 : car, true, O.extra_latency, ptsx, ptsy, nullptr, cmd, nullptr, h->d_rstat, h->d_iters, nullptr, stream_, x));
     double *rec = hist ? hist + (int64_t)t * MPC_DRIVE_REC * ld : nullptr;
     hipLaunchKernelGGL(mpc_drive_plant_kernel, dim3(grid), dim3(256), 0, s, h->params, O, B, ld, t, n_track, car, cmd, h->d_run, S, h->d_rstat, h->d_iters,
-                       k_now, k_prev, summary, rec, status, iters, latency, MpcModelPart{x.model, ld}, x.plant);
+                       k_now, k_prev, summary, rec, status, iters, latency, MpcModelPart{x.model, ld}, x.plant, x.noise);
     MPC_HIP_CHECK(hipGetLastError());
   }
   ++h->n_drive_stepwise;
@@ -3147,8 +3215,9 @@ static int drive_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, double *ca
  * drive_args; then the call's extras -- the warm refusals and the options in effect. */
 static int drive_call(const MpcHandle *h, int64_t B, int64_t ld, int steps, const double *car, const double *track_x, const double *track_y,
                       int n_track, const double *model, const int32_t *horizon, const int32_t *budget, const double *latency, const double *plant,
-                      const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, const double *summary, const int32_t *status, MpcDriveOpts *O, CallExtras *x) {
-  if (h && plant && h->params.precision != MPC_PRECISION_F64) {
+                      const double *noise, double *seen, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, const double *summary, const int32_t *status,
+                      MpcDriveOpts *O, CallExtras *x) {
+  if (h && (plant || noise || seen) && h->params.precision != MPC_PRECISION_F64) {
     g_last_error = "track driving: fp64 handles only (this one was created with MPC_PRECISION_F32)";
     return MPC_ERR_INVALID;
   }
@@ -3156,20 +3225,31 @@ static int drive_call(const MpcHandle *h, int64_t B, int64_t ld, int steps, cons
   MPC_TRY(drive_args(h, B, ld, steps, car, track_x, track_y, n_track, opts, summary, status, O));
   *x = call_extras(h, model, O->warm_start != 0, nullptr, nullptr, nullptr, 0, warm_opts, horizon, latency, budget);
   x->plant = plant;
+  x->noise = noise;
+  x->seen = seen;
   return x->refused;
 }
 
 /* (the _plant forms, "per-car plant values" in include/mpc_amd_drive.h: the _horizon forms plus `plant` behind latency; NULL is the _horizon form itself) */
 /* (the _budget forms, include/mpc_amd_budget.h: the _plant forms plus `budget` behind horizon; NULL is the _plant form itself) */
+/* (the _noise forms, include/mpc_amd_noise.h: the _budget forms plus `noise` behind plant and `seen` behind hist; both NULL is the _budget form itself) */
+extern "C" int mpc_drive_batch_device_noise(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
+                                            const double *track_y, int n_track, const double *weights, const double *model, const int32_t *horizon,
+                                            const int32_t *budget, const double *latency, const double *plant, const double *noise, const MpcDriveOpts *opts,
+                                            const MpcWarmOpts *warm_opts, double *summary, double *hist, double *seen, int32_t *status, int32_t *iters,
+                                            void *stream_) {
+  MpcDriveOpts O;
+  CallExtras x;
+  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, horizon, budget, latency, plant, noise, seen, opts, warm_opts, summary, status, &O, &x));
+  if (B == 0) { h->last_B = 0; return MPC_OK; }
+  return drive_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
+}
 extern "C" int mpc_drive_batch_device_budget(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
                                              const double *track_y, int n_track, const double *weights, const double *model, const int32_t *horizon,
                                              const int32_t *budget, const double *latency, const double *plant, const MpcDriveOpts *opts,
                                              const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status, int32_t *iters, void *stream_) {
-  MpcDriveOpts O;
-  CallExtras x;
-  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, horizon, budget, latency, plant, opts, warm_opts, summary, status, &O, &x));
-  if (B == 0) { h->last_B = 0; return MPC_OK; }
-  return drive_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
+  return mpc_drive_batch_device_noise(h, B, ld, steps, car, track_x, track_y, n_track, weights, model, horizon, budget, latency, plant, nullptr, opts, warm_opts,
+                                      summary, hist, nullptr, status, iters, stream_);
 }
 extern "C" int mpc_drive_batch_device_plant(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
                                             const double *track_y, int n_track, const double *weights, const double *model, const int32_t *horizon,
@@ -3227,13 +3307,13 @@ static int drive_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, doub
   if (h->params.max_fit_order > 5) { g_last_error = "run(): max_fit_order > 5 is not built (fit orders 2..4)"; return MPC_ERR_UNSUPPORTED; }
   MPC_ON_DEVICE(h);
   const int64_t S = h->io_stride;
-  const int P8 = mpc::RUN_MAX_PTS;
   hipStream_t s = (hipStream_t)stream_;
   const double *w_dev = nullptr;
   MPC_TRY(drive_rows(h, B, ld, x.warm, weights, s, &w_dev));
   MPC_TRY(ensure_dev(&h->d_run, sizeof(double) * mpc::RUN_PRE_ROWS * S));
   MPC_TRY(grow_dev(&h->d_run9, &h->run9_bytes, sizeof(double) * 9 * ld));
-  double *d_pre = h->d_run, *ptsx = h->d_drive, *ptsy = ptsx + P8 * ld, *cmd = ptsy + P8 * ld;
+  const DriveRows R{h->d_drive, ld};
+  double *d_pre = h->d_run, *ptsx = R.ptsx(), *ptsy = R.ptsy(), *cmd = R.cmd();
   const SolveIO<double> io{B, S, ld, d_pre + mpc::RUN_PRE_STATE * S, d_pre + mpc::RUN_PRE_COEFFS * S, d_pre + mpc::RUN_PRE_YAW_LO * S,
                            d_pre + mpc::RUN_PRE_YAW_HI * S, w_dev, h->d_run9, nullptr, status, iters ? iters : h->d_iters};
   std::optional<DeviceGuard> guard;
@@ -3249,7 +3329,7 @@ static int drive_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, doub
   double *warm = x.warm ? h->d_warm : nullptr;
   const WarmIO wc{warm, nullptr, warm, S, x.w.wopts, 1};      /* (psi_box: the run() path's rule) */
   const MpcRollPart roll{steps, nullptr, 0, nullptr, status, iters};
-  const MpcDrivePart drive{O, car, track_x, track_y, n_track, ptsx, ptsy, cmd, d_pre, h->d_run9, summary, hist, x.latency, x.plant};
+  const MpcDrivePart drive{O, car, track_x, track_y, n_track, ptsx, ptsy, cmd, d_pre, h->d_run9, summary, hist, x.latency, x.plant, x.noise, x.seen};
   const unsigned grid = (unsigned)((B + kBlock - 1) / kBlock);
   if (x.lane_rows()) {
     /* the DRIVE x HORIZON builds: MODEL builds whose `model` may be nullptr, not staged, per-lane workspace rows, no LDS (no lane compaction here) */
@@ -3273,16 +3353,24 @@ static int drive_fused_impl(MpcHandle *h, int64_t B, int64_t ld, int steps, doub
   return record_stats(h, B, status, iters, s);
 }
 
+extern "C" int mpc_drive_batch_device_fused_noise(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
+                                                  const double *track_y, int n_track, const double *weights, const double *model,
+                                                  const int32_t *horizon, const int32_t *budget, const double *latency, const double *plant,
+                                                  const double *noise, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist,
+                                                  double *seen, int32_t *status, int32_t *iters, void *stream_) {
+  MpcDriveOpts O;
+  CallExtras x;
+  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, horizon, budget, latency, plant, noise, seen, opts, warm_opts, summary, status, &O, &x));
+  if (B == 0) { h->last_B = 0; return MPC_OK; }
+  return drive_fused_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
+}
 extern "C" int mpc_drive_batch_device_fused_budget(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
                                                    const double *track_y, int n_track, const double *weights, const double *model,
                                                    const int32_t *horizon, const int32_t *budget, const double *latency, const double *plant,
                                                    const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts, double *summary, double *hist, int32_t *status,
                                                    int32_t *iters, void *stream_) {
-  MpcDriveOpts O;
-  CallExtras x;
-  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, horizon, budget, latency, plant, opts, warm_opts, summary, status, &O, &x));
-  if (B == 0) { h->last_B = 0; return MPC_OK; }
-  return drive_fused_impl(h, B, ld, steps, car, track_x, track_y, n_track, weights, O, x, summary, hist, status, iters, stream_);
+  return mpc_drive_batch_device_fused_noise(h, B, ld, steps, car, track_x, track_y, n_track, weights, model, horizon, budget, latency, plant, nullptr, opts,
+                                            warm_opts, summary, hist, nullptr, status, iters, stream_);
 }
 extern "C" int mpc_drive_batch_device_fused_plant(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x,
                                                   const double *track_y, int n_track, const double *weights, const double *model,
@@ -3323,24 +3411,26 @@ extern "C" int mpc_drive_batch_device_fused(MpcHandle *h, int64_t B, int64_t ld,
 
 /* The same for host arrays: one copy in, the loop on the handle's own device and stream, one copy out; synchronises.  Staging kept on
  * the handle and grown on demand, like the telemetry handler's.  model (host, [MPC_NMODEL][ld]), latency (host, [MPC_NLATENCY][ld]) and
- * horizon (host, [ld] int32, to h->d_horizon) are copied in with the other inputs, and so is plant (host, [MPC_NPLANT][ld]). */
-extern "C" int mpc_drive_batch_host_budget(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
-                                           int n_track, const double *weights, const double *model, const int32_t *horizon, const int32_t *budget,
-                                           const double *latency, const double *plant, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts,
-                                           double *summary, double *hist, int32_t *status, int32_t *iters) {
+ * horizon (host, [ld] int32, to h->d_horizon) are copied in with the other inputs, and so are plant (host, [MPC_NPLANT][ld]) and noise
+ * (host, [MPC_NNOISE][ld]); seen (host, [steps][4][ld]) is copied out with hist. */
+extern "C" int mpc_drive_batch_host_noise(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                                          int n_track, const double *weights, const double *model, const int32_t *horizon, const int32_t *budget,
+                                          const double *latency, const double *plant, const double *noise, const MpcDriveOpts *opts,
+                                          const MpcWarmOpts *warm_opts, double *summary, double *hist, double *seen, int32_t *status, int32_t *iters) {
   MpcDriveOpts O;
   CallExtras x;
-  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, horizon, budget, latency, plant, opts, warm_opts, summary, status, &O, &x));
+  MPC_TRY(drive_call(h, B, ld, steps, car, track_x, track_y, n_track, model, horizon, budget, latency, plant, noise, seen, opts, warm_opts, summary, status, &O, &x));
   if (B == 0) { h->last_B = 0; return MPC_OK; }
   MPC_ON_DEVICE(h);
   const int64_t L = (B + 7) / 8 * 8;
   const int64_t rows = 6 + MPC_DRIVE_NSUM + (weights ? MPC_NW : 0) + (hist ? (int64_t)steps * MPC_DRIVE_REC : 0) + (model ? MPC_NMODEL : 0) +
-                       (latency ? MPC_NLATENCY : 0) + (plant ? MPC_NPLANT : 0);
+                       (latency ? MPC_NLATENCY : 0) + (plant ? MPC_NPLANT : 0) + (noise ? MPC_NNOISE : 0) + (seen ? (int64_t)steps * 4 : 0);
   MPC_TRY(grow_dev(&h->d_drive_host, &h->drive_host_bytes, sizeof(double) * (size_t)(rows * L + 2 * n_track) + sizeof(int32_t) * (size_t)(2 * L)));
   double *d = h->d_drive_host;
   double *d_car = d, *d_sum = d_car + 6 * L, *d_w = d_sum + MPC_DRIVE_NSUM * L, *d_hist = d_w + (weights ? MPC_NW * L : 0);
   double *d_model = d_hist + (hist ? (int64_t)steps * MPC_DRIVE_REC * L : 0), *d_lat = d_model + (model ? MPC_NMODEL * L : 0), *d_plant = d_lat + (latency ? MPC_NLATENCY * L : 0),
-         *d_tx = d_plant + (plant ? MPC_NPLANT * L : 0), *d_ty = d_tx + n_track;
+         *d_noise = d_plant + (plant ? MPC_NPLANT * L : 0), *d_seen = d_noise + (noise ? MPC_NNOISE * L : 0),
+         *d_tx = d_seen + (seen ? (int64_t)steps * 4 * L : 0), *d_ty = d_tx + n_track;
   int32_t *d_st = (int32_t *)(d_ty + n_track), *d_it = d_st + L;
   hipStream_t s = h->stream;
   MPC_HIP_CHECK(hipMemcpy2DAsync(d_car, sizeof(double) * L, car, sizeof(double) * ld, sizeof(double) * B, 6, hipMemcpyHostToDevice, s));
@@ -3357,6 +3447,11 @@ extern "C" int mpc_drive_batch_host_budget(MpcHandle *h, int64_t B, int64_t ld, 
     MPC_HIP_CHECK(hipMemcpy2DAsync(d_plant, sizeof(double) * L, plant, sizeof(double) * ld, sizeof(double) * B, MPC_NPLANT, hipMemcpyHostToDevice, s));
     x.plant = d_plant;
   }
+  if (noise) {
+    MPC_HIP_CHECK(hipMemcpy2DAsync(d_noise, sizeof(double) * L, noise, sizeof(double) * ld, sizeof(double) * B, MPC_NNOISE, hipMemcpyHostToDevice, s));
+    x.noise = d_noise;
+  }
+  if (seen) x.seen = d_seen;
   if (horizon) {
     MPC_TRY(ensure_dev(&h->d_horizon, sizeof(int32_t) * (size_t)h->io_stride));
     MPC_HIP_CHECK(hipMemcpyAsync(h->d_horizon, horizon, sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
@@ -3373,9 +3468,45 @@ extern "C" int mpc_drive_batch_host_budget(MpcHandle *h, int64_t B, int64_t ld, 
   MPC_HIP_CHECK(hipMemcpy2DAsync(car, sizeof(double) * ld, d_car, sizeof(double) * L, sizeof(double) * B, 6, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipMemcpy2DAsync(summary, sizeof(double) * ld, d_sum, sizeof(double) * L, sizeof(double) * B, MPC_DRIVE_NSUM, hipMemcpyDeviceToHost, s));
   if (hist) MPC_HIP_CHECK(hipMemcpy2DAsync(hist, sizeof(double) * ld, d_hist, sizeof(double) * L, sizeof(double) * B, (size_t)steps * MPC_DRIVE_REC, hipMemcpyDeviceToHost, s));
+  if (seen) MPC_HIP_CHECK(hipMemcpy2DAsync(seen, sizeof(double) * ld, d_seen, sizeof(double) * L, sizeof(double) * B, (size_t)steps * 4, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipMemcpyAsync(status, d_st, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
   if (iters) MPC_HIP_CHECK(hipMemcpyAsync(iters, d_it, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
   MPC_HIP_CHECK(hipStreamSynchronize(s));
+  return MPC_OK;
+}
+extern "C" int mpc_drive_batch_host_budget(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,
+                                           int n_track, const double *weights, const double *model, const int32_t *horizon, const int32_t *budget,
+                                           const double *latency, const double *plant, const MpcDriveOpts *opts, const MpcWarmOpts *warm_opts,
+                                           double *summary, double *hist, int32_t *status, int32_t *iters) {
+  return mpc_drive_batch_host_noise(h, B, ld, steps, car, track_x, track_y, n_track, weights, model, horizon, budget, latency, plant, nullptr, opts, warm_opts, summary,
+                                    hist, nullptr, status, iters);
+}
+/* the zero column, under which a _noise call is the call without noise */
+extern "C" int mpc_drive_noise_default(double *col7) {
+  if (!col7) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
+  for (int q = 0; q < MPC_NNOISE; q++) col7[q] = 0.0;
+  return MPC_OK;
+}
+/* mpc::drive_noise_draw on the host, for a seed as a column holds it */
+extern "C" int mpc_drive_noise_draw(double seed, int32_t step, double *out7) {
+  if (!out7) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
+  if (!mpc::drive_finite(seed) || !mpc::drive_seed_ok(seed)) { g_last_error = "mpc_drive_noise_draw: the seed must be an integer value in [0, 2^53)"; return MPC_ERR_INVALID; }
+  if (step < 0) { g_last_error = "mpc_drive_noise_draw: step < 0"; return MPC_ERR_INVALID; }
+  mpc::drive_noise_draw(seed, step, out7);
+  return MPC_OK;
+}
+extern "C" int mpc_debug_philox4x32(const uint32_t *ctr, const uint32_t *key, uint32_t *out) {
+  if (!ctr || !key || !out) { g_last_error = "NULL argument"; return MPC_ERR_INVALID; }
+  mpc::philox4x32(ctr, key, out);
+  return MPC_OK;
+}
+extern "C" int mpc_debug_drive_noise_device(MpcHandle *h, int64_t n, const double *seed, const int32_t *step, double *out, void *stream_) {
+  if (!h) { g_last_error = "NULL handle"; return MPC_ERR_INVALID; }
+  if (n < 0 || n > (int64_t)1 << 24 || (n > 0 && (!seed || !step || !out))) { g_last_error = "mpc_debug_drive_noise_device: n outside 0 .. 2^24, or a NULL argument"; return MPC_ERR_INVALID; }
+  if (n == 0) return MPC_OK;
+  MPC_ON_DEVICE(h);
+  hipLaunchKernelGGL(mpc_debug_drive_noise_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, n, seed, step, out);
+  MPC_HIP_CHECK(hipGetLastError());
   return MPC_OK;
 }
 extern "C" int mpc_drive_batch_host_plant(MpcHandle *h, int64_t B, int64_t ld, int steps, double *car, const double *track_x, const double *track_y,

@@ -382,8 +382,14 @@ class BatchedMPC:
         row 0 from ``model``'s Lf row if one is given: the ``plant=`` under which a drive is the drive without one."""
         return _abi.drive_plant_default(self.params, B, model)
 
+    @staticmethod
+    def drive_noise_default(B=None, seeds=None):
+        """The zero noise column (mpc_drive_noise_default), or with B / seeds the array [7, B] of it with the seeds in row 0: the
+        ``noise=`` under which a drive is the drive without one, ready to have its sigma rows set (_abi.NOISE_*)."""
+        return _abi.drive_noise_default(B, seeds)
+
     def drive_torch(self, car, track_x, track_y, steps, weights=None, opts=None, warm_opts=None, want_hist=True, fused=False, stream=None,
-                    model=None, latency=None, horizon=None, plant=None, budget=None):
+                    model=None, latency=None, horizon=None, plant=None, budget=None, noise=None, seen=False):
         """Drive B cars along a cyclic track for `steps` telemetry messages on the device (mpc_drive_batch_device): per message the
         waypoint window at the car's position, the telemetry handler (cold, or warm with opts.warm_start) and the plant -- the
         reference's own kinematic model, not the simulator.  car [6, B] = x, y, psi, speed [mph], steering_angle, throttle is advanced
@@ -408,9 +414,18 @@ class BatchedMPC:
         every car's handler may spend per message, over all attempts of its solve -- the reference's solve deadline (ipoptTimeout),
         counted in iterations.  A message that uses its budget up drives the car with the current iterate (status MAXITER) and, with
         opts.warm_start, hands that iterate to the next message: one call answers "how much solver work per message does this tuning
-        need to stay on the road, cold or warm-started".  The lane kernel at every B, like ``horizon``."""
+        need to stay on the road, cold or warm-started".  The lane kernel at every B, like ``horizon``.
+        ``noise`` [7, B] float64 (mpc_drive_batch_device_noise, _fused_noise; rows _abi.NOISE_*: seed, then the sigmas of the reported
+        position, heading and speed, of a per-message steering offset and side gust, and the probability that a reply is lost): every
+        car's own seeded sensor, actuator and link noise -- a Monte-Carlo over noisy drives is seeds x noise levels as the columns of
+        one call.  The draws depend on (seed, message index) alone.  drive_noise_default(B, seeds) is the column that changes nothing.
+        ``seen`` = True: the result has "seen" [steps, 4, B], what the handler was told (x, y, psi, speed) at every message (None
+        otherwise).  Neither changes which kernels run."""
         import torch
         B = car.shape[1]
+        if noise is not None and (noise.dtype != torch.float64 or not noise.is_cuda or not noise.is_contiguous() or
+                                  tuple(noise.shape) != (_abi.NNOISE, B)):
+            raise ValueError("noise must be a contiguous float64 CUDA tensor of shape (%d, B)" % _abi.NNOISE)
         if budget is not None:
             self._check_horizon(budget, B, "budget")
         if plant is not None and (plant.dtype != torch.float64 or not plant.is_cuda or not plant.is_contiguous() or
@@ -430,7 +445,8 @@ class BatchedMPC:
                 raise ValueError("%s must be a contiguous float64 CUDA tensor of shape %s" % (name, shape))
         res = {"car": car, "summary": torch.empty((_abi.DRIVE_NSUM, B), dtype=torch.float64, device=dev),
                "hist": torch.empty((steps, _abi.DRIVE_REC, B), dtype=torch.float64, device=dev) if want_hist else None,
-               "status": torch.empty((B,), dtype=torch.int32, device=dev), "iters": torch.empty((B,), dtype=torch.int32, device=dev)}
+               "status": torch.empty((B,), dtype=torch.int32, device=dev), "iters": torch.empty((B,), dtype=torch.int32, device=dev),
+               "seen": torch.empty((steps, 4, B), dtype=torch.float64, device=dev) if seen else None}
         s = stream if stream is not None else torch.cuda.current_stream(dev)
         name = ("mpc_drive_batch_device_fused" if fused else "mpc_drive_batch_device") + (
             "_budget" if budget is not None else "_plant" if plant is not None else "_horizon" if horizon is not None else
@@ -443,20 +459,26 @@ class BatchedMPC:
             extra = tuple(t.data_ptr() if t is not None else None for t in (model, horizon, latency, plant))
         if budget is not None:
             extra = tuple(t.data_ptr() if t is not None else None for t in (model, horizon, budget, latency, plant))
+        seen_arg = ()
+        if noise is not None or seen:
+            name = ("mpc_drive_batch_device_fused" if fused else "mpc_drive_batch_device") + "_noise"
+            extra = tuple(t.data_ptr() if t is not None else None for t in (model, horizon, budget, latency, plant, noise))
+            seen_arg = (res["seen"].data_ptr() if seen else None,)
         check(getattr(library(), name)(self._h, B, B, int(steps), car.data_ptr(), track_x.data_ptr(), track_y.data_ptr(), n,
                                                weights.data_ptr() if weights is not None else None, *extra,
                                                C.byref(opts) if opts is not None else None, C.byref(warm_opts) if warm_opts is not None else None,
-                                               res["summary"].data_ptr(), res["hist"].data_ptr() if want_hist else None,
+                                               res["summary"].data_ptr(), res["hist"].data_ptr() if want_hist else None, *seen_arg,
                                                res["status"].data_ptr(), res["iters"].data_ptr(), C.c_void_p(s.cuda_stream)),
               name)
         return res
 
     def drive_numpy(self, car, track_x, track_y, steps, weights=None, opts=None, warm_opts=None, want_hist=True, model=None, latency=None, horizon=None,
-                    plant=None, budget=None):
+                    plant=None, budget=None, noise=None, seen=False):
         """drive_torch for host arrays (mpc_drive_batch_host): one copy in, the loop, one copy out; synchronises.  `car` is copied:
         the cars after the last step are "car" of the result.  ``model`` [6, B]: as in drive_torch (mpc_drive_batch_host_model); ``latency`` [3, B]: as in
         drive_torch (mpc_drive_batch_host_latency); ``horizon`` [B] int32: as in drive_torch (mpc_drive_batch_host_horizon); ``plant`` [6, B]: as in
-        drive_torch (mpc_drive_batch_host_plant); ``budget`` [B] int32: as in drive_torch (mpc_drive_batch_host_budget)."""
+        drive_torch (mpc_drive_batch_host_plant); ``budget`` [B] int32: as in drive_torch (mpc_drive_batch_host_budget); ``noise`` [7, B] and ``seen``: as in
+        drive_torch (mpc_drive_batch_host_noise)."""
         f = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64)) if a is not None else None
         car, tx, ty, weights = f(car).copy(), f(track_x), f(track_y), f(weights)
         B, n = car.shape[1], tx.shape[0]
@@ -466,8 +488,13 @@ class BatchedMPC:
             if model.shape != (_abi.NMODEL, B):
                 raise ValueError("model must have shape (%d, B)" % _abi.NMODEL)
         res = {"car": car, "summary": np.empty((_abi.DRIVE_NSUM, B)), "hist": np.empty((steps, _abi.DRIVE_REC, B)) if want_hist else None,
-               "status": np.empty(B, dtype=np.int32), "iters": np.empty(B, dtype=np.int32)}
+               "status": np.empty(B, dtype=np.int32), "iters": np.empty(B, dtype=np.int32), "seen": np.empty((steps, 4, B)) if seen else None}
         p = lambda a: a.ctypes.data if a is not None else None
+        if noise is not None:
+            noise = np.asarray(noise)
+            if noise.dtype != np.float64 or noise.shape != (_abi.NNOISE, B):
+                raise ValueError("noise must be a float64 array of shape (%d, B)" % _abi.NNOISE)
+            noise = np.ascontiguousarray(noise)
         if latency is not None:
             latency = f(latency)
             if latency.shape != (_abi.NLATENCY, B):
@@ -490,9 +517,12 @@ class BatchedMPC:
             if budget.dtype != np.int32 or budget.shape != (B,):
                 raise ValueError("budget must be an int32 array of shape (B,)")
             name, extra = "mpc_drive_batch_host_budget", (p(model), p(horizon), p(budget), p(latency), p(plant))
+        seen_arg = ()
+        if noise is not None or seen:
+            name, extra, seen_arg = "mpc_drive_batch_host_noise", (p(model), p(horizon), p(budget), p(latency), p(plant), p(noise)), (p(res["seen"]),)
         check(getattr(library(), name)(self._h, B, B, int(steps), p(car), p(tx), p(ty), n, p(weights), *extra,
                                        C.byref(opts) if opts is not None else None, C.byref(warm_opts) if warm_opts is not None else None,
-                                       p(res["summary"]), p(res["hist"]), p(res["status"]), p(res["iters"])), name)
+                                       p(res["summary"]), p(res["hist"]), *seen_arg, p(res["status"]), p(res["iters"])), name)
         return res
 
     def drive_info(self):

@@ -557,6 +557,12 @@ int mpc_rollout_batch_device_fused_model(MpcHandle *h, int64_t B, int64_t ld, in
  * its attempts and hand an unconverged iterate on to the next message.  The section and its declarations live in a header of their
  * own, which this one includes: */
 #include "mpc_amd_budget.h"
+/* ---- track drive under noise: seeded per-car sensor, actuator and link noise ------------------------------------------------------
+ * The _noise forms of the track drive hand the handler a noisy reading of every car (`seen`), perturb the plant per message and drop
+ * replies, from a counter-based random stream that depends on the car's seed and the message index alone: a Monte-Carlo over noisy
+ * drives is seeds x noise levels as the columns of one call.  The section and its declarations live in a header of their own, which
+ * this one includes: */
+#include "mpc_amd_noise.h"
 /* ---- per-instance model values on the run() path: a fleet of different vehicles behind one handler ----------------------------
  * Each entry point is the one of the same name without `_model` plus `model`, [MPC_NMODEL][ld] doubles addressed with the call's
  * ld (rows MPC_MODEL_*), directly behind `ptsy`; the wire forms further down take it as [MPC_NMODEL][B] directly behind

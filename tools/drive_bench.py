@@ -84,7 +84,7 @@ def main():
     ap.add_argument("--config", default="config-fast.json")
     ap.add_argument("--out", default=None)
     ap.add_argument("--model", action="store_true", help="measure the _model entry points and run the top-speed sweep")
-    ap.add_argument("--parent", default=None, help="--model: a file this tool wrote on the parent commit in the same session; --plant: the parent commit's built checkout (the cost legs)")
+    ap.add_argument("--parent", default=None, help="--model: a file this tool wrote on the parent commit in the same session; --plant, --noise: the parent commit's built checkout (the cost legs)")
     ap.add_argument("--speeds", type=int, default=16)
     ap.add_argument("--cars", type=int, default=4096)
     ap.add_argument("--sweep-steps", type=int, default=300)
@@ -101,9 +101,13 @@ def main():
     ap.add_argument("--biases", type=int, default=16, help="--plant: steering biases, -0.1 .. 0.1 rad")
     ap.add_argument("--budget", action="store_true", help="run the budget x {cold, warm} grid of the _budget entry points")
     ap.add_argument("--budgets", default="1,2,3,4,5,6,8,12,50", help="--budget: the iteration budgets of the grid")
+    ap.add_argument("--noise", action="store_true", help="run the sigma x seed grid of the _noise entry points (a Monte-Carlo in one call)")
+    ap.add_argument("--sigmas", type=int, default=8, help="--noise: values of sigma_pos, 0 .. 1 m (sigma_psi and sigma_speed scaled with it)")
+    ap.add_argument("--seeds", type=int, default=512, help="--noise: seeds per sigma")
+    ap.add_argument("--noise-mph", type=float, default=40.0, help="--noise: the top speed of the drive [mph] (at the config's own no start stays on the road for 300 messages)")
     ap.add_argument("--merge", nargs="*", default=None, help="--horizon: files of this tool whose legs are copied into --out (nothing is run)")
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "drive_budget.json" if a.budget else "drive_plant.json" if a.plant else "drive_horizon.json" if a.horizon else "drive_latency.json" if a.latency else
+    a.out = a.out or os.path.join(ROOT, "profiles", "drive_noise.json" if a.noise else "drive_budget.json" if a.budget else "drive_plant.json" if a.plant else "drive_horizon.json" if a.horizon else "drive_latency.json" if a.latency else
                                   "drive_model.json" if a.model else "drive.json")
     if a.horizon and a.merge is not None:
         doc = {"tool": "tools/drive_bench.py --horizon", "legs": {}}
@@ -145,6 +149,8 @@ def main():
             if rep >= a.warmup:
                 ms.append(e0.elapsed_time(e1))
         return ms, out
+    if a.noise:
+        return noise_grid(a, pkg, gd, wp, t, d_tx, d_ty)
     if a.budget:
         return budget_grid(a, pkg, params, wp, t, timed, d_tx, d_ty)
     if a.horizon:
@@ -431,6 +437,90 @@ def budget_grid(a, pkg, params, wp, t, timed, d_tx, d_ty):
     doc.update({"tool": "tools/drive_bench.py --budget", "config": a.config, "device": torch.cuda.get_device_name(0), "grid": grid})
     json.dump(doc, open(a.out, "w"), indent=1)
     print("wrote", a.out)
+
+
+def noise_grid(a, pkg, gd, wp, t, d_tx, d_ty):
+    """sigmas x seeds x sweep-steps messages as ONE mpc_drive_batch_device_fused_noise call, cold and warm; beside it the same cars with
+    the zero column and with noise = NULL (the _fused_budget path): the zero-column time against the NULL time is the cost of the feature
+    to a caller who passes the array.  --parent CHECKOUT: the plain drive on the parent commit's library and on this one, alternating (the
+    --plant cost legs): what the feature costs a caller who does not.
+    The drive: --config at a top speed of --noise-mph, from the one of 64 candidate starts (scenarios.track_starts, seed 127) that a
+    noise-free pre-drive keeps on the road with the smallest max |cte0| -- so that FIRST_OFF == -1 at sigma 0 and the noise alone moves it."""
+    import torch
+    from carnd_mpc_project_amd import _abi
+    n_s, n_seeds, steps = a.sigmas, a.seeds, a.sweep_steps
+    B = n_s * n_seeds
+    sig = np.linspace(0.0, 1.0, n_s)
+    params = pkg.params_from_json(os.path.join(gd, a.config), max_speed=a.noise_mph * 1609.34 / 3600.0)
+    cand = pkg.scenarios.track_starts(64, params, wp, seed=127)
+    with pkg.BatchedMPC(params, 64, device=0) as mpc:
+        pre = mpc.drive_torch(t(cand), d_tx, d_ty, steps, opts=mpc.drive_opts(warm_start=0), fused=True, want_hist=False)["summary"].cpu().numpy()
+    on = pre[6] < 0
+    assert on.any(), "no candidate start stays on the road without noise: lower --noise-mph"
+    pick = int(np.argmin(np.where(on, pre[0], np.inf)))
+    print("start: candidate %d of 64 (%d stay on the road without noise), max |cte0| %.3f m over %d messages" % (pick, on.sum(), pre[0, pick], steps), flush=True)
+    # column = sigma * n_seeds + seed; every column: the same start (the spread is the noise's alone), seed s of every sigma: the same stream
+    cars = np.tile(cand[:, pick:pick + 1], (1, B))
+    noise = pkg.drive_noise_default(B, np.tile(10000 + np.arange(n_seeds), n_s))
+    noise[_abi.NOISE_POS] = np.repeat(sig, n_seeds)
+    noise[_abi.NOISE_PSI] = 0.05 * noise[_abi.NOISE_POS]            # 1 m goes with 0.05 rad and 2 mph
+    noise[_abi.NOISE_SPEED] = 2.0 * noise[_abi.NOISE_POS]
+    zero = pkg.drive_noise_default(B, noise[_abi.NOISE_SEED].astype(np.int64))
+    d_cars, d_noise, d_zero = t(cars), t(noise), t(zero)
+    doc = json.load(open(a.out)) if os.path.exists(a.out) else {}
+    grid = {"call": "mpc_drive_batch_device_fused_noise, hist given", "B": B, "steps": steps, "top_speed_mph": a.noise_mph,
+            "start": {"candidate": pick, "of": 64, "candidates_on_the_road_without_noise": int(on.sum()), "max_abs_cte0_without_noise": float(pre[0, pick])},
+            "sigma_pos_m": [float(x) for x in sig],
+            "sigma_psi_rad": [float(0.05 * x) for x in sig], "sigma_speed_mph": [float(2.0 * x) for x in sig], "seeds_per_sigma": n_seeds,
+            "timing": "median of reps runs after warmup runs, between two events; the three calls of a start mode alternate rep by rep", "start_modes": {}}
+    with pkg.BatchedMPC(params, B, device=0) as mpc:
+        for warm in (0, 1):
+            opts = mpc.drive_opts(warm_start=warm)
+            calls = {"noise": lambda: mpc.drive_torch(d_cars.clone(), d_tx, d_ty, steps, opts=opts, fused=True, noise=d_noise),
+                     "zero_column": lambda: mpc.drive_torch(d_cars.clone(), d_tx, d_ty, steps, opts=opts, fused=True, noise=d_zero),
+                     "noise_null": lambda: mpc.drive_torch(d_cars.clone(), d_tx, d_ty, steps, opts=opts, fused=True)}
+            ms, out = {k: [] for k in calls}, {}
+            for r in range(a.warmup + a.reps):          # interleaved: a drift of the clock meets all three alike
+                for k, fn in calls.items():
+                    m, out[k] = timed_once(torch, fn)
+                    if r >= a.warmup:
+                        ms[k].append(m)
+            res = out["noise"]
+            hist = res["hist"].cpu().numpy().reshape(steps, 13, n_s, n_seeds)
+            summ = res["summary"].cpu().numpy().reshape(8, n_s, n_seeds)
+            same = all(torch.equal(out["zero_column"][k], out["noise_null"][k]) for k in ("car", "summary", "hist", "status", "iters"))
+            stat = lambda v: {"ms_median": float(np.median(v)), "ms_min": float(min(v)), "ms_max": float(max(v))}
+            leg = dict(stat(ms["noise"]), reps=a.reps, warmup=a.warmup, cte_limit=opts.cte_limit, drive_info=mpc.drive_info(),
+                       zero_column_same_cars=dict(stat(ms["zero_column"]), bitwise_equal_to_noise_null=bool(same)),
+                       noise_null_same_cars=dict(stat(ms["noise_null"]), what="the same call with noise = NULL: the _fused_budget path"),
+                       zero_column_over_noise_null=float(np.median(ms["zero_column"]) / np.median(ms["noise_null"])),
+                       noise_null_spread_max_over_min=float(max(ms["noise_null"]) / min(ms["noise_null"])), rows=[])
+            for q in range(n_s):
+                leg["rows"].append({"sigma_pos_m": float(sig[q]), "share_of_cars_within_cte_limit": float((summ[6, q] < 0).mean()),
+                                    "first_step_off_the_road_median": float(np.median(summ[6, q][summ[6, q] >= 0])) if (summ[6, q] >= 0).any() else None,
+                                    "max_abs_cte0_p50_p90_p99_max": [float(np.quantile(summ[0, q], x)) for x in (0.5, 0.9, 0.99, 1.0)],
+                                    "iterations_per_message": float(hist[:, 11, q].mean()), "non_success_messages": int((hist[:, 10, q] != 0).sum())})
+                print("warm %d" % warm, json.dumps(leg["rows"][-1]), flush=True)
+            print("warm %d: %d cars x %d messages: noise %.1f ms, zero column %.1f ms, noise = NULL %.1f ms (min .. max %.1f .. %.1f)" % (
+                warm, B, steps, leg["ms_median"], leg["zero_column_same_cars"]["ms_median"], leg["noise_null_same_cars"]["ms_median"],
+                leg["noise_null_same_cars"]["ms_min"], leg["noise_null_same_cars"]["ms_max"]), flush=True)
+            grid["start_modes"]["warm" if warm else "cold"] = leg
+    doc.update({"tool": "tools/drive_bench.py --noise", "config": a.config, "device": torch.cuda.get_device_name(0), "grid": grid})
+    if a.parent:
+        doc.pop("cost_of_the_unused_feature", None)
+        plant_cost_legs(a, doc, ["plain"])
+    json.dump(doc, open(a.out, "w"), indent=1)
+    print("wrote", a.out)
+
+
+def timed_once(torch, fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    out = fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1), out
 
 
 HORIZON_NS, HORIZON_DTS = (5, 7, 10, 15, 20, 25), (0.05, 0.1, 0.15, 0.2)
